@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- overlap-graph construction throughput of the HIP engine on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4_50M_150bp] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4_50M_150bp] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
 
 A "step" is one complete pass of the hot path (GraphCreatorPrefSuf + retainOnlySmallestOffset, reference
 src/main.cpp:244-296: index of the targets, probe of every source, transitive reduction, sorted adjacency lists) over one
 synthetic read set that is already resident in HBM when the timed region starts.  Prints ONE JSON line (rank 0):
   metric   overlap_edges_per_sec   (BASELINE.json: overlap edges/sec; Gbp/s of input reads is `gbp_per_sec`)
   value    edges in the emitted graph x steps / wall time of the K steps (max over ranks), whole job, inputs resident in HBM
+  ms_per_step  wall time of one timed step
+A plain run does only that: set up, W untimed steps (at least one), the K timed steps, the line.  --dump-outputs DIR writes the
+edge list of the last timed step (dump_outputs).  --full adds everything else, each leg as described here:
+  first_call  the first builds of a fresh engine, with and without alga_engine_reserve
+  timed_edges_digest_equal_pairwise  the last timed step's list against one counted pass of the pairwise kernels
   roofline dominant kernel (the probe): SURVEY.md section 8(d) algorithmic bytes / its HIP-event duration vs the 8 TB/s HBM peak
   cpu_baseline  the real reference binary (oracle/_ref/ALGA, kind "reference") -- or the C oracle (kind "port") where it is
                 absent -- timed on this box's host cores on a bounded sample of the same workload; the GPU graph of the same
@@ -127,12 +132,45 @@ def traffic_of(traffic, prefix):
     return int(sum(v)) if v else None
 
 
+DUMP_ROWS = 1_500_000      # 36 MB of float64 edge rows + 12 MB of their row numbers: the dump stays under 64 MB
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir, edges):
+    """What the timed path hands its caller: the edge list [m, 3] (src, dst, offset; device int32) of the graph of the last timed step, as
+    float64 .npy files (float64 holds every int32 exactly):
+      edges.npy         the whole list when it has at most DUMP_ROWS rows; else the rows at edges_rows.npy
+      edges_rows.npy    (only when sampled) sorted row numbers, drawn with a fixed seed: the same rows for the same edge count
+      edges_digest.npy  [count, the list's position-weighted int64 checksum (alga_amd.multigpu.edges_digest) as four 16-bit limbs, low first]"""
+    import torch
+    from alga_amd import multigpu
+    os.makedirs(out_dir, exist_ok=True)
+    m = int(edges.shape[0])
+    rows = None
+    if m > DUMP_ROWS:
+        rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, m, DUMP_ROWS))
+        sample = edges[torch.from_numpy(rows).to(edges.device)]
+    else:
+        sample = edges
+    np.save(os.path.join(out_dir, "edges.npy"), sample.cpu().numpy().astype(np.float64).reshape(-1, 3))
+    if rows is not None:
+        np.save(os.path.join(out_dir, "edges_rows.npy"), rows.astype(np.float64))
+    count, checksum = [int(x) for x in multigpu.edges_digest(edges).cpu()]
+    checksum &= (1 << 64) - 1
+    np.save(os.path.join(out_dir, "edges_digest.npy"), np.array([count] + [(checksum >> (16 * i)) & 0xFFFF for i in range(4)], dtype=np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg4_50M_150bp")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: first-call legs, the counted pass (work counters, roofline, digest of the timed list against "
+                         "it), PCIe-inclusive forms, CPU baseline (the --no-* options below switch single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the edge list of the last one as DIR/*.npy (float64; a fixed sample of rows when it is large)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true")
     ap.add_argument("--no-first-call", action="store_true")
@@ -171,9 +209,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        wall = time.perf_counter() - t_process
-        out["fits_in_driver_run"] = {"wall_s": round(wall, 1), "limit_s": 600, "fits": wall < 600,
-                                     "note": "whole bench.py process: workload generation, first-call legs, counted pass, warmup, timed steps, PCIe leg, CPU baseline"}
+        if args.full:
+            wall = time.perf_counter() - t_process
+            out["fits_in_driver_run"] = {"wall_s": round(wall, 1), "limit_s": 600, "fits": wall < 600,
+                                         "note": "whole bench.py --full process: workload generation, first-call legs, counted pass, warmup, timed steps, PCIe leg, CPU baseline"}
         print(json.dumps(out))
         if out.get("timed_edges_digest_equal_pairwise") is False:
             raise SystemExit("bench.py: the edge list of the last timed step differs from the counted (pairwise) pass: %s" % (out["timed_edges_digest"],))
@@ -193,7 +232,7 @@ def run(args, rank, world, local_rank, dist, t_process=None):
     host_words = host_lens = None
     t_build = time.perf_counter()
     if n_reads >= 4_000_000:
-        wl = workload.device_build(n_reads, read_len, G, seed, err=err, sample_reads=(args.cpu_sample_reads if rank == 0 else 0))
+        wl = workload.device_build(n_reads, read_len, G, seed, err=err, sample_reads=(args.cpu_sample_reads if rank == 0 and args.full else 0))
         d_words, d_lens = wl["words"], wl["lens"]
         sample_codes = wl["sample_codes"]
         how = "generated on the device (alga_amd.workload.device_build)"
@@ -219,7 +258,10 @@ def run(args, rank, world, local_rank, dist, t_process=None):
     first = None
     eng = alga_amd.Engine(local_rank)
     eng.set_option("probe", args.probe)
-    if world == 1 and not args.no_first_call and not args.traffic_pass:
+    if world == 1 and not args.no_first_call and not args.traffic_pass and not args.full:
+        # a plain run: the reserve call alone (part of setting up, as in an assembler), so that the timed engine is prepared as under --full
+        eng.reserve(n_nodes, max_len, lo)
+    elif world == 1 and not args.no_first_call and not args.traffic_pass:
         # (a) the first engine of this process: alga_engine_reserve (an assembler calls it while it still parses / uploads), then the build
         t0 = time.perf_counter()
         eng.reserve(n_nodes, max_len, lo)
@@ -301,14 +343,18 @@ def run(args, rank, world, local_rank, dist, t_process=None):
         return {"traffic_pass": True, "builds": args.warmup + args.steps, "edges": int(n_edges), "config": {"workload": args.config},
                 "pile_buckets": int(s.get("pile_buckets", 0)), "pile_irregular": int(s.get("pile_irregular", 0)), "src_sha256": alga_amd.engine.source_fingerprint()} if rank == 0 else None
 
-    # one counted pass (work counters for the roofline's algorithmic bytes); not timed.  A build that collects the work counters runs
-    # the PAIRWISE kernels (the counters are defined by what those do) -- its edge list is the independent one the timed list is compared with
-    n_edges, st = step(collect_stats=True)
-    stats = dict(st)
-    digest_counted = digest()
-    if world > 1:
-        stats["nodes_live"] = n_nodes                 # whole-job counters (all_reduced); nodes are replicated
-    for _ in range(max(0, args.warmup - 1)):
+    if args.full:
+        # one counted pass (work counters for the roofline's algorithmic bytes); not timed.  A build that collects the work counters runs
+        # the PAIRWISE kernels (the counters are defined by what those do) -- its edge list is the independent one the timed list is compared with
+        n_edges, st = step(collect_stats=True)
+        stats = dict(st)
+        digest_counted = digest()
+        if world > 1:
+            stats["nodes_live"] = n_nodes                 # whole-job counters (all_reduced); nodes are replicated
+        warm = args.warmup - 1                            # (the counted pass is the first untimed step)
+    else:
+        warm = max(1, args.warmup)                        # at least one, as with the counted pass: --warmup 0 still times a warmed engine
+    for _ in range(max(0, warm)):
         step()
     sync_all()
     keys_ms = ("seed", "probe", "group", "reduce", "emit", "exchange", "probe_pairs", "keys", "sort", "gather", "dir", "pile", "supplement")
@@ -320,7 +366,9 @@ def run(args, rank, world, local_rank, dist, t_process=None):
             phase[k] += s.get("ms_" + k, 0.0)
     sync_all()
     dt = time.perf_counter() - t0
-    digest_timed = digest()                   # of the LAST timed step's list, after the clock has stopped
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final["edges"])       # before anything else can reuse the engine memory the list lies in
+    digest_timed = digest() if args.full else None          # of the LAST timed step's list, after the clock has stopped
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -329,8 +377,22 @@ def run(args, rank, world, local_rank, dist, t_process=None):
     out = None
     if rank == 0:
         ms_step = dt / args.steps * 1e3
-        ms = {k: v / args.steps for k, v in phase.items()}
         bases = n_reads * read_len
+        workload_desc = ("%s: %d x %d bp reads, genome %d, seed %d, err %.2f -> %d nodes (both strands, duplicates removed), "
+                         "min_overlap %d, rsoemo %d; %s in %.1f s%s" %
+                         (args.config, n_reads, read_len, G, seed, err, n_nodes, lo, rs, how, t_build,
+                          "; a step = exact overlap graph + approximate supplement (error_rate %.2f)" % err if supplement else ""))
+        if not args.full:
+            out = {"metric": "overlap_edges_per_sec", "value": n_edges * args.steps / dt, "unit": "edges/s",
+                   "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
+                   "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+                   "gbp_per_sec": bases / (ms_step * 1e-3) / 1e9,
+                   "config": {"workload": workload_desc, "nodes": n_nodes, "edges": int(n_edges)},
+                   "device": eng.device_name()}
+            if world > 1:
+                out["multi_gpu_form"] = multi_form
+            return out
+        ms = {k: v / args.steps for k, v in phase.items()}
         alg = algorithmic_bytes(stats, W)
         alg_probe_launch = alg["probe"] / world           # one launch = one rank's share of the sources
         achieved = alg_probe_launch / (ms["probe"] * 1e-3) / 1e9
@@ -393,10 +455,7 @@ def run(args, rank, world, local_rank, dist, t_process=None):
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "gbp_per_sec": bases / (ms_step * 1e-3) / 1e9,
-            "config": {"workload": "%s: %d x %d bp reads, genome %d, seed %d, err %.2f -> %d nodes (both strands, duplicates removed), "
-                                   "min_overlap %d, rsoemo %d; %s in %.1f s%s" %
-                                   (args.config, n_reads, read_len, G, seed, err, n_nodes, lo, rs, how, t_build,
-                                    "; a step = exact overlap graph + approximate supplement (error_rate %.2f)" % err if supplement else ""),
+            "config": {"workload": workload_desc,
                        "nodes": n_nodes, "edges": int(n_edges), "parallelism": "1 GPU" if world == 1 else
                        "strong scaling: the same read set for every N; node set and target index on every rank, sources sharded over %d ranks "
                        "(contiguous id ranges); edge lists gathered on rank 0 over RCCL" % world},

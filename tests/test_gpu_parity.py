@@ -668,7 +668,7 @@ def test_bench_run_as_two_thread_ranks_equals_one_gpu():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
     from fake_dist import run_ranks
-    common = ["--steps", "2", "--warmup", "1", "--config", "cfg3_5M_150bp", "--no-cpu-baseline", "--no-pcie", "--no-first-call"]
+    common = ["--steps", "2", "--warmup", "1", "--config", "cfg3_5M_150bp", "--full", "--no-cpu-baseline", "--no-pcie", "--no-first-call"]
     one = bench.run(bench.parse_args(["--gpus", "1"] + common), 0, 1, 0, None)
     args2 = bench.parse_args(["--gpus", "2"] + common)
     res = run_ranks(2, lambda rank, dist: bench.run(args2, rank, 2, 0, dist))

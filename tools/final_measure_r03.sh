@@ -16,15 +16,15 @@ if [ "$PART" = A ]; then
   tail -3 $OUT/pytest_gpu.log
   [ $rc -ne 0 ] && exit $rc
   for CFG in cfg4_50M_150bp cfg5_10M_150bp_err2; do
-    timeout -k 10 900 bash tools/profile_cmd.sh r03_final_$CFG trx bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-first-call || exit 1
+    timeout -k 10 900 bash tools/profile_cmd.sh r03_final_$CFG trx bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-first-call || exit 1
     python tools/pmc_to_traffic.py gpurun_out/prof_r03_final_$CFG $CFG > $OUT/traffic_$CFG.json || exit 1
     cp gpurun_out/prof_r03_final_$CFG/summary.txt $OUT/rocprof_$CFG.txt
-    timeout -k 10 600 python bench.py --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
+    timeout -k 10 600 python bench.py --full --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
     echo "$CFG: $(python3 -c "import json,sys; d=json.loads(open('$OUT/bench_$CFG.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d['roofline']['frac'], d['roofline']['traffic'])")"
   done
   cp profiles/hbm_traffic.json $OUT/hbm_traffic.json
   for CFG in cfg2_1M_150bp cfg3_5M_150bp; do
-    timeout -k 10 600 python bench.py --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
+    timeout -k 10 600 python bench.py --full --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
     echo "$CFG: $(python3 -c "import json,sys; d=json.loads(open('$OUT/bench_$CFG.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'])")"
   done
 else

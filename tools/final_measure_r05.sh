@@ -29,13 +29,13 @@ if [ "$PART" = A1 ] || [ "$PART" = A2 ]; then
     timeout -k 10 900 bash tools/profile_cmd.sh r05_final_$CFG trx bench.py --config $CFG --traffic-pass --steps $K --warmup $W || exit 1
     python tools/pmc_to_traffic.py gpurun_out/prof_r05_final_$CFG $CFG --builds=$((W + K)) > $OUT/traffic_$CFG.json || exit 1
     cp gpurun_out/prof_r05_final_$CFG/summary.txt $OUT/rocprof_$CFG.txt
-    timeout -k 10 600 python bench.py --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
+    timeout -k 10 600 python bench.py --full --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
     echo "$CFG: $(python3 -c "import json,sys; d=json.loads(open('$OUT/bench_$CFG.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d['roofline']['kernel'], d['roofline']['frac'], d['roofline']['basis'], d['roofline_step'].get('traffic_amplification'), d.get('ms_end_to_end'), d.get('timed_edges_digest_equal_pairwise'))")"
   done
   cp profiles/hbm_traffic.json $OUT/hbm_traffic.json
   [ "$PART" = A1 ] && exit 0
   for CFG in cfg2_1M_150bp cfg3_5M_150bp; do
-    timeout -k 10 600 python bench.py --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
+    timeout -k 10 600 python bench.py --full --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { tail -20 $OUT/bench_$CFG.err; exit 1; }
     echo "$CFG: $(python3 -c "import json,sys; d=json.loads(open('$OUT/bench_$CFG.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d.get('ms_end_to_end'))")"
   done
 elif [ "$PART" = B ]; then

@@ -11,6 +11,6 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fulls
 rc=$?
 tail -5 gpurun_out/${TAG}_pytest.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 900 bash tools/profile_cmd.sh $TAG $PASSES bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie || exit 1
+timeout -k 10 900 bash tools/profile_cmd.sh $TAG $PASSES bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pcie || exit 1
 grep -E "k_|rocprim" gpurun_out/prof_$TAG/summary.txt | head -60
 tail -1 gpurun_out/prof_$TAG/out_trace.log | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({k:d[k] for k in ('ms_per_step','phases_ms','roofline','counters')}))"

@@ -7,7 +7,7 @@ TAG=${1:-gaps}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof_$TAG
-timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_$TAG -- python3 $REPO/bench.py --config cfg5_10M_150bp_err2 --no-cpu-baseline --no-pcie --no-first-call --steps 3 --warmup 2 > $OUT/trace_$TAG.json 2> $OUT/trace_$TAG.err || { tail -5 $OUT/trace_$TAG.err; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_$TAG -- python3 $REPO/bench.py --full --config cfg5_10M_150bp_err2 --no-cpu-baseline --no-pcie --no-first-call --steps 3 --warmup 2 > $OUT/trace_$TAG.json 2> $OUT/trace_$TAG.err || { tail -5 $OUT/trace_$TAG.err; exit 1; }
 cd $REPO
 python3 - <<PY
 import csv,glob

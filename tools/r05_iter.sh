@@ -14,7 +14,7 @@ if [ -n "$PYT" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 if [ $# -gt 0 ]; then
-  timeout -k 10 600 python bench.py "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
+  timeout -k 10 600 python bench.py --full "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; rc=$?
   [ $rc -ne 0 ] && { tail -20 $OUT/bench_$TAG.err; exit $rc; }
   python3 - <<PY
 import json

@@ -22,7 +22,7 @@ for r in rows[start:]:
 print("step total", (pe-t0)/1e3)
 PY
 if [ "${2:-}" = cfg5 ]; then
-  timeout -k 10 500 python bench.py --config cfg5_10M_150bp_err2 --steps 5 --warmup 2 --no-cpu-baseline --no-first-call > $OUT/bench_cfg5_$TAG.json 2> $OUT/bench_cfg5_$TAG.err || { tail -5 $OUT/bench_cfg5_$TAG.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --config cfg5_10M_150bp_err2 --steps 5 --warmup 2 --no-cpu-baseline --no-first-call > $OUT/bench_cfg5_$TAG.json 2> $OUT/bench_cfg5_$TAG.err || { tail -5 $OUT/bench_cfg5_$TAG.err; exit 1; }
   python3 - <<PY
 import json
 d=json.loads(open("$OUT/bench_cfg5_$TAG.json").read().strip().splitlines()[-1])
