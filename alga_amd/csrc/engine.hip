@@ -668,6 +668,7 @@ void alga_engine_destroy(alga_engine *e) {
     for (DevBuf *b : {&e->in_bytes[0], &e->in_bytes[1], &e->in_nl[0], &e->in_nl[1], &e->in_tiles, &e->in_tile_off}) alga_release(*b);
     for (DevBuf *b : {&e->sp_rowptr, &e->sp_sorted, &e->sp_list, &e->sp_cnt, &e->sp_orow, &e->sp_out, &e->sp_in}) alga_release(*b);
     alga_staging_release(e);
+    for (void *&p : e->gfa_pin) { if (p) (void) hipHostFree(p); p = nullptr; }
     for (auto &kv : e->host_lists) free(kv.first);         // host edge lists the caller never gave back (alga_free_edges after this is an error: alga_amd.h)
     e->host_lists.clear();
     engine_free_handles(e);
@@ -723,6 +724,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_test_pile_oom = value != 0;                 // tests only: the pile path's allocation answers out of memory; the build must continue on the pairwise kernels
     } else if (!strcmp(name, "test_unsorted_index")) {
         e->opt_test_unsorted_index = value != 0;           // tests only: the clustered index is built over UNSORTED keys; the build must fail, not fault
+    } else if (!strcmp(name, "gfa_chunk_mb")) {
+        if (value < 1 || value > 4096) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option gfa_chunk_mb: 1 .. 4096");
+        e->opt_gfa_chunk_mb = (int) value;
     } else if (!strcmp(name, "auto_reduction_per_target")) {
         e->opt_force_per_target = value != 0;
     } else return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown option");

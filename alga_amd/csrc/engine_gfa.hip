@@ -1,0 +1,187 @@
+// alga_amd/csrc/engine_gfa.hip -- C ABI of the GFA 1.0 export (include/alga_amd.h: alga_write_gfa_device; kernels in gfa_kernels.hip).
+//
+// Host side: two small read-backs before any byte of text exists (the device's verdict on the input; then the line count, the
+// longest line and the total size with the chunk bounds), then one loop over the chunks: the device formats chunk k into its buffer,
+// the buffer goes down into pinned host buffer k % 2, and a host thread pwrite()s it at its file offset while the device formats
+// chunk k + 1.  The only wait per chunk is the main thread's for the write of chunk k - 2 (whose pinned buffer chunk k reuses).
+#include <hip/hip_runtime.h>
+
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <chrono>
+#include <future>
+#include <vector>
+
+#include "engine_internal.h"
+#include "gfa_kernels.h"
+#include "simplify_kernels.h"
+
+using namespace alga;
+
+namespace {
+
+const char kGfaHeader[] = "H\tVN:Z:1.0\n";
+
+bool write_all(int fd, const char *p, size_t bytes, uint64_t at) {
+    while (bytes) {
+        const ssize_t w = pwrite(fd, p, bytes, (off_t) at);
+        if (w <= 0) return false;
+        p += w; bytes -= (size_t) w; at += (uint64_t) w;
+    }
+    return true;
+}
+
+struct GfaEvents {
+    std::vector<hipEvent_t> ev;
+    ~GfaEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
+};
+
+int gfa_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t m, const char *path, int32_t flags, alga_gfa_info *info,
+             int &fd) {
+    hipStream_t s = e->own_stream;
+    const bool twins = flags & ALGA_GFA_TWINS;
+    GfaCfg c{nodes->words, nodes->stride_words, nodes->len, nodes->n, (const alga_edge_dev *) d_edges, m, twins ? (uint64_t) nodes->n / 2 : (uint64_t) nodes->n,
+             twins ? 1 : 0, (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
+    const uint64_t N = c.n_seg + m;                                 // items: segment lines, then link lines
+    int rc;
+    GfaEvents evs;
+    // [0, 1] checks .. scan, [2, 3] the copies' ends (one per pinned slot), [4 + 2 * (k % 4), 5 + 2 * (k % 4)] the formatting of chunk k
+    // (read back once the write of chunk k is done, two chunks later: four pairs are never overwritten before that)
+    evs.ev.assign(12, nullptr);
+    for (int k = 0; k < 12; k++) HIP_TRY(e, hipEventCreate(&evs.ev[(size_t) k]));
+    if ((rc = alga_ensure(e, e->counters, GFA_COUNTERS * sizeof(unsigned long long)))) return rc;
+    if ((rc = alga_ensure(e, e->gfa_rowptr, ((size_t) nodes->n + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->gfa_sizes, (size_t) (N + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->gfa_off, (size_t) (N + 1) * sizeof(unsigned long long)))) return rc;
+    if ((rc = alga_ensure(e, e->gfa_tiles, (gfa_scan_tiles(N) + 1) * sizeof(unsigned long long)))) return rc;
+    unsigned long long *cnt = (unsigned long long *) e->counters.p, *off = (unsigned long long *) e->gfa_off.p;
+    HIP_TRY(e, hipMemsetAsync(cnt, 0, GFA_COUNTERS * sizeof(unsigned long long), s));
+    HIP_TRY(e, hipEventRecord(evs.ev[0], s));
+    launch_gfa_check(c, cnt, s);
+    if ((rc = alga_check_launch(e, "k_gfa_check"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (const unsigned long long bad = e->h_counters[GFA_FLAGS]) {
+        const char *why = (bad & GFA_BAD_ID) ? "edge endpoint outside [0, n)" : (bad & GFA_BAD_ORDER) ? "edges must be sorted by (src, dst, offset)"
+                        : (bad & GFA_BAD_LEN) ? "negative node length" : "ALGA_GFA_TWINS: len[2k] != len[2k + 1]";
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
+    }
+    // the list is valid: per-source rows, line sizes, byte offsets
+    if (m) {
+        launch_edge_rowptr(c.e, m, c.n, (uint32_t *) e->gfa_rowptr.p, s);
+        if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
+    }
+    launch_gfa_sizes(c, (const uint32_t *) e->gfa_rowptr.p, (uint32_t *) e->gfa_sizes.p, cnt, s);
+    if ((rc = alga_check_launch(e, "k_gfa_sizes"))) return rc;
+    launch_gfa_scan64((const uint32_t *) e->gfa_sizes.p, N, off, (unsigned long long *) e->gfa_tiles.p, s);
+    if ((rc = alga_check_launch(e, "gfa scan"))) return rc;
+    HIP_TRY(e, hipEventRecord(evs.ev[1], s));
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, GFA_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters + GFA_COUNTERS, off + N, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIP_TRY(e, hipEventElapsedTime(&ms, evs.ev[0], evs.ev[1]));
+    double ms_format = ms;
+    const uint64_t total = e->h_counters[GFA_COUNTERS], max_line = e->h_counters[GFA_MAX_LINE];
+    if (info) {
+        info->segments = e->h_counters[GFA_SEGMENTS]; info->links = e->h_counters[GFA_LINKS]; info->links_merged = e->h_counters[GFA_MERGED];
+        info->bytes = sizeof(kGfaHeader) - 1 + total;
+    }
+    // chunks: step = cap - longest line, so that no chunk exceeds cap and each ends at a line boundary
+    uint64_t cap = (uint64_t) e->opt_gfa_chunk_mb << 20;
+    if (cap < 2 * max_line) cap = (2 * max_line + 4095) & ~4095ull;
+    const uint64_t step = cap - max_line, K = total ? (total + step - 1) / step : 0;
+    std::vector<unsigned long long> bounds(2 * (size_t) (K + 1));
+    if (K) {
+        if ((rc = alga_ensure(e, e->gfa_bounds, bounds.size() * sizeof(unsigned long long)))) return rc;
+        launch_gfa_bounds(off, N, step, K, (unsigned long long *) e->gfa_bounds.p, s);
+        if ((rc = alga_check_launch(e, "k_gfa_bounds"))) return rc;
+        HIP_TRY(e, hipMemcpyAsync(bounds.data(), e->gfa_bounds.p, bounds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if ((rc = alga_ensure(e, e->gfa_buf, (size_t) cap))) return rc;
+        if (e->gfa_pin_cap < cap) {
+            for (void *&p : e->gfa_pin) { if (p) HIP_TRY(e, hipHostFree(p)); p = nullptr; }
+            e->gfa_pin_cap = 0;
+            for (void *&p : e->gfa_pin) HIP_TRY(e, hipHostMalloc(&p, (size_t) cap));
+            e->gfa_pin_cap = cap;
+        }
+    }
+    fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) return alga_fail(e, ALGA_ERR_IO, "cannot create the GFA file");
+    const uint64_t head = sizeof(kGfaHeader) - 1;
+    if (!write_all(fd, kGfaHeader, head, 0)) return alga_fail(e, ALGA_ERR_IO, "cannot write the GFA file");
+    std::future<bool> writer[2];
+    int pending_fmt[2] = {-1, -1};                                 // event pair of the chunk the slot holds, -1 none
+    bool io_ok = true;
+    auto finish_slot = [&](int slot) -> int {                      // the write that last used pinned buffer `slot` is done; its format time counted
+        if (writer[slot].valid()) io_ok = writer[slot].get() && io_ok;
+        if (pending_fmt[slot] >= 0) {
+            float t = 0.0f;
+            HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[(size_t) (4 + 2 * pending_fmt[slot])], evs.ev[(size_t) (5 + 2 * pending_fmt[slot])]));
+            ms_format += t;
+            pending_fmt[slot] = -1;
+        }
+        return ALGA_OK;
+    };
+    char *dbuf = (char *) e->gfa_buf.p;
+    int slot = 0, pair = 0;
+    for (uint64_t k = 0; k < K && rc == ALGA_OK && io_ok; k++) {
+        const uint64_t i0 = bounds[(size_t) k], i1 = bounds[(size_t) k + 1];
+        const uint64_t b0 = bounds[(size_t) (K + 1 + k)], bytes = bounds[(size_t) (K + 2 + k)] - b0;
+        if (!bytes) continue;
+        // the formatting of chunk k runs behind the copy of chunk k - 1 (same stream, one device buffer)
+        HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (4 + 2 * pair)], s));
+        launch_gfa_format(c, off, i0, i1, dbuf, s);
+        if ((rc = alga_check_launch(e, "k_gfa_format"))) break;
+        HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (5 + 2 * pair)], s));
+        // ... wait for the write of the chunk two before (it read this pinned buffer) while the device formats
+        if ((rc = finish_slot(slot)) || !io_ok) break;
+        pending_fmt[slot] = pair;
+        pair = (pair + 1) & 3;
+        HIP_TRY(e, hipMemcpyAsync(e->gfa_pin[slot], dbuf, (size_t) bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (2 + slot)], s));
+        hipEvent_t copied = evs.ev[(size_t) (2 + slot)];
+        const char *src = (const char *) e->gfa_pin[slot];
+        const int f = fd;
+        writer[slot] = std::async(std::launch::async, [copied, src, bytes, f, at = head + b0]() {
+            return hipEventSynchronize(copied) == hipSuccess && write_all(f, src, (size_t) bytes, at);
+        });
+        slot ^= 1;
+    }
+    for (int k = 0; k < 2; k++) { const int r = finish_slot(k); if (rc == ALGA_OK) rc = r; }
+    if (rc != ALGA_OK) return rc;
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (!io_ok) return alga_fail(e, ALGA_ERR_IO, "cannot write the GFA file");
+    if (close(fd) != 0) { fd = -1; return alga_fail(e, ALGA_ERR_IO, "cannot close the GFA file"); }
+    fd = -1;
+    if (info) info->ms_format = ms_format;
+    return ALGA_OK;
+}
+
+}  // namespace
+
+extern "C" int alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, const char *path, int32_t flags,
+                                     alga_gfa_info *info) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    const auto t0 = std::chrono::steady_clock::now();
+    if (info) *info = alga_gfa_info{};
+    if (!nodes || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes and path must not be NULL");
+    if (flags & ~(ALGA_GFA_TWINS | ALGA_GFA_SEQUENCES)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown GFA flag");
+    if (nodes->n < 0 || (nodes->n && !nodes->len) || (n_edges && !d_edges)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node set or edge list");
+    if ((flags & ALGA_GFA_SEQUENCES) && nodes->n && (!nodes->words || nodes->stride_words <= 0))
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "ALGA_GFA_SEQUENCES needs the rows");
+    if ((flags & ALGA_GFA_TWINS) && (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "ALGA_GFA_TWINS: the node count must be even");
+    if (n_edges >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 edges");
+    HIP_TRY(e, hipSetDevice(e->device));
+    int fd = -1;
+    const int rc = gfa_impl(e, nodes, d_edges, n_edges, path, flags, info, fd);
+    if (rc != ALGA_OK) {
+        (void) hipStreamSynchronize(e->own_stream);                 // nothing may still copy into the pinned buffers
+        if (fd >= 0) { close(fd); unlink(path); }                  // no partial file is left behind
+        return rc;
+    }
+    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ALGA_OK;
+}

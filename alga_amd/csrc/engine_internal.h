@@ -111,6 +111,11 @@ struct alga_engine {
     size_t      host_spare_cap = 0;
     DevBuf      in_bytes[2], in_nl[2], in_tiles, in_tile_off;   // device ingest: file bytes, line ends, newline counts per tile
     DevBuf      sp_rowptr, sp_sorted, sp_list, sp_cnt, sp_orow, sp_out, sp_in;   // first simplifier step (engine_simplify.hip)
+    // GFA export (engine_gfa.hip): line sizes, their 64-bit byte offsets, per-source row pointers, scan tile sums, chunk bounds, the device chunk
+    DevBuf      gfa_sizes, gfa_off, gfa_rowptr, gfa_tiles, gfa_bounds, gfa_buf;
+    void       *gfa_pin[2] = {nullptr, nullptr};   // pinned host chunks (hipHostMalloc), gfa_pin_cap bytes each
+    size_t      gfa_pin_cap = 0;
+    int         opt_gfa_chunk_mb = 256;            // option "gfa_chunk_mb": size of a formatted chunk of the GFA text
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

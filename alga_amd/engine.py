@@ -157,7 +157,19 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_multi_free_edges", "alga_multi_last_stats", "alga_multi_set_option", "alga_upload_twin_nodes",
            "alga_shard_index_device", "alga_shard_join_device", "alga_shard_small_keys_device", "alga_shard_resolve_device", "alga_shard_place_device",
            "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
-           "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free"]
+           "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
+           "alga_write_gfa_device"]
+
+GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
+
+
+class GfaInfo(C.Structure):
+    """alga_gfa_info"""
+    _fields_ = [("segments", C.c_uint64), ("links", C.c_uint64), ("links_merged", C.c_uint64), ("bytes", C.c_uint64),
+                ("ms_format", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def library_path():
@@ -235,6 +247,7 @@ def load_library():
     lib.alga_shard_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.alga_shard_place_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.alga_write_graph.argtypes = [C.c_char_p, C.c_int32, C.c_void_p, C.c_uint64]
+    lib.alga_write_gfa_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_uint64, C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
     lib.alga_sort_records_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.alga_sort_edges_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -800,6 +813,40 @@ class Engine:
         self._check(self._lib.alga_contig_trim_host(self._h, words.ctypes.data, int(words.shape[1]) if words.ndim == 2 else 1, lens.ctypes.data, len(lens),
                                                     int(threshold), out.ctypes.data))
         return out
+
+    def write_gfa(self, path, words, lens, edges, n_edges=None, twins=True, sequences=True, stream=None):
+        """The graph as GFA 1.0, formatted on the device (alga_write_gfa_device) -> dict of alga_gfa_info.
+        words [n, stride] / lens [n]: the node set as torch device tensors (numpy arrays are uploaded first); edges: a device pointer
+        (with n_edges), an int32 device tensor [m, 3] or a numpy array [m, 3] (uploaded), sorted by (src, dst, offset).
+        twins: ALGA's layout (node 2k+1 = read k, 2k its reverse complement; one segment per pair); sequences: the ACGT field (else `*`).
+        stream: the stream that produced the inputs, synchronised first (the call runs on the engine's own stream)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(words, np.ndarray):
+            words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(dev)
+        if isinstance(lens, np.ndarray):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+        keep = None
+        if isinstance(edges, np.ndarray):
+            e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)
+            keep = torch.from_numpy(e).to(dev)
+            ptr, m = _ptr(keep), len(e)
+        elif isinstance(edges, int):
+            ptr, m = edges, int(n_edges or 0)
+        else:
+            keep = edges
+            ptr, m = _ptr(edges), int(edges.shape[0]) if n_edges is None else int(n_edges)
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        nd = self._nodes_from_torch(words, lens)
+        info = GfaInfo()
+        flags = (GFA_TWINS if twins else 0) | (GFA_SEQUENCES if sequences else 0)
+        self._check(self._lib.alga_write_gfa_device(self._h, C.byref(nd), C.c_void_p(ptr or None), C.c_uint64(m), os.fsencode(path), flags,
+                                                    C.byref(info)))
+        del keep
+        return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)

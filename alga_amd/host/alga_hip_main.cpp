@@ -2,7 +2,7 @@
 //
 //   alga_hip --file1=reads.fasta [--file2=mates.fasta] --output=contigs.fasta [--threads=N] [--error_rate=R | --error-rate=R]
 //            [--serialize=1] [-l MINOVERLAP] [--rsoemo=N] [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1]
-//            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA]
+//            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -15,6 +15,8 @@
 // --deserialize_graph=1 loads that file instead of running its GraphCreator (src/main.cpp:242) and carries on with
 // the unchanged simplifier / contig stages; `--alga=` does that hand-off in one go.
 // Both spellings of the error-rate option are accepted (the reference registers `error_rate` only, src/Params.cpp:226).
+// --gfa=PATH also writes that graph (after the supplement, rank 0's under --gpus) as GFA 1.0 with sequences, formatted on the GPU
+// (alga_write_gfa_device); it is not handed on to stock ALGA.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -38,7 +40,7 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 int main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    std::string file1, file2, output, alga_exe, v;
+    std::string file1, file2, output, alga_exe, gfa, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
     int device = 0, serialize = 1, gpus = 1;
@@ -62,6 +64,7 @@ int main(int argc, char **argv) {
         else if (opt(a, "--gpus", v)) gpus = std::max(1, atoi(v.c_str()));
         else if (opt(a, "--gpu-list", v)) { gpu_list.clear(); for (size_t k = 0; k < v.size();) { gpu_list.push_back(atoi(v.c_str() + k)); size_t c = v.find(',', k); if (c == std::string::npos) break; k = c + 1; } }
         else if (opt(a, "--alga", v)) alga_exe = v;
+        else if (opt(a, "--gfa", v)) gfa = v;
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
         else { fprintf(stderr, "alga_hip: unrecognized option '%s'\n", a); return 2; }
         // the hand-off to stock ALGA drops the error-rate option: the supplement it switches on (src/Params.cpp:357-359) has
@@ -69,7 +72,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -191,6 +194,15 @@ int main(int argc, char **argv) {
             if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: %s (status %d)\n", alga_last_error(engine), rc); return 1; }
         }
         fprintf(stderr, "After supplement G has %llu edges\n", (unsigned long long) n_final);
+    }
+    if (!gfa.empty()) {                                                        // from the device edges, before they are copied back
+        alga_nodes nd{nodes.d_words, nodes.stride_words, nodes.d_len, nodes.n, nullptr, nullptr};
+        alga_gfa_info gi;
+        int rc = alga_write_gfa_device(engine, &nd, d_final, n_final, gfa.c_str(), ALGA_GFA_TWINS | ALGA_GFA_SEQUENCES, &gi);
+        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", gfa.c_str(), alga_last_error(engine), rc); return 1; }
+        fprintf(stderr, "GFA written -> %s: %llu segments, %llu links (%llu twin edges merged), %llu bytes; device %.3f ms, wall %.1f ms\n", gfa.c_str(),
+                (unsigned long long) gi.segments, (unsigned long long) gi.links, (unsigned long long) gi.links_merged, (unsigned long long) gi.bytes,
+                gi.ms_format, gi.ms_total);
     }
     std::vector<alga_edge> final_edges((size_t) n_final);
     if (n_final && alga_copy_to_host(engine, final_edges.data(), d_final, final_edges.size() * sizeof(alga_edge)) != ALGA_OK) { fprintf(stderr, "alga_amd: cannot read the edges back\n"); return 1; }

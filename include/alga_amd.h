@@ -184,6 +184,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *   "local_big_max"              largest per-wave item slice of the SOURCE_SIDE second pass (default -1 = built-in 4096); beyond it
  *                                the build takes PER_TARGET
  *   "auto_reduction_per_target"  != 0: alga_prefsuf_params.reduction == AUTO resolves to PER_TARGET
+ *   "gfa_chunk_mb"               1..4096 (default 256): alga_write_gfa_device formats the text in chunks of at most this many MB (one device buffer,
+ *                                two pinned host buffers of that size; a chunk is never smaller than twice the longest line)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
@@ -645,6 +647,33 @@ int  alga_contig_trim_host(alga_engine *e, const uint32_t *words, int32_t stride
  * deg x {i32 neighbour; i32 offset}}, native endian.  Stock ALGA loads it with
  * --deserialize_graph=1 (src/main.cpp:242).  `edges` must be sorted by (src, dst, offset). */
 int  alga_write_graph(const char *path, int32_t n_nodes, const alga_edge *edges, uint64_t n_edges);
+
+/* ---- graph export: GFA 1.0, formatted on the GPU (alga_amd/csrc/gfa_kernels.hip, engine_gfa.hip) ------------------------
+ * The standard exchange format of assembly / overlap graphs (Bandage, gfatools, other layout tools).  Fields are separated by one tab,
+ * every line ends with '\n':  the header `H VN:Z:1.0`, the segments in ascending order of their name, the links in edge-list order.
+ *   ALGA_GFA_TWINS      ALGA's layout (node 2k+1 = read k, node 2k its reverse complement; every ingest entry point produces it): twin pair k
+ *                       is segment k, written when len[2k+1] > 0 (`S k <ACGT of node 2k+1> LN:i:<len>`), node 2k+1 is orientation +, 2k is -.
+ *                       The twin of edge (a -> b, o), (b^1 -> a^1, len[b] - len[a] + o), is the same link: an edge is written unless its exact
+ *                       twin is in the list too and has the lexicographically smaller (src, dst) (a self-twin b == a^1 once, an edge whose
+ *                       twin is missing on its own).  n odd or len[2k] != len[2k+1]: ALGA_ERR_INVALID_ARGUMENT.
+ *   without it          every node i with len[i] > 0 is segment i, every orientation + and every edge one link.
+ *   ALGA_GFA_SEQUENCES  the segment's sequence from its 2-bit row; without it the field is `*`.
+ * Edge (a -> b, o) is `L <name a> <orient a> <name b> <orient b> <len[a] - o>M`.  `nodes` and `d_edges` are device memory (a build's or the
+ * supplement's result, sorted by (src, dst, offset)); ids outside [0, n), an unsorted list or a negative length answer ALGA_ERR_INVALID_ARGUMENT
+ * (checked on the device) and write no file.  The text is formatted on the device in chunks (option "gfa_chunk_mb") that go down into two
+ * pinned buffers in turn while a host thread writes the previous one; on any error the partial file is removed (ALGA_ERR_IO for the file
+ * system's errors).  Every input must be complete before the call (the engine's own stream runs it). */
+#define ALGA_GFA_TWINS     1
+#define ALGA_GFA_SEQUENCES 2
+typedef struct {
+    uint64_t segments, links;   /* lines written                                                                         */
+    uint64_t links_merged;      /* edges not written because their twin's line stands for them                           */
+    uint64_t bytes;             /* size of the file                                                                      */
+    double   ms_format;         /* device time of the checks, sizes, scan and formatting kernels (HIP events)             */
+    double   ms_total;          /* wall time of the call                                                                 */
+} alga_gfa_info;
+int  alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, const char *path, int32_t flags,
+                           alga_gfa_info *info /* may be NULL */);
 
 #ifdef __cplusplus
 }
