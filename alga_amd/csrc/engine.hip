@@ -137,6 +137,7 @@ int pile_alloc(alga_engine *e, uint64_t n, uint32_t n_buckets, hipStream_t s) {
     if ((rc = alga_ensure(e, e->cl_pile_succ, ((size_t) n + 64) * 16))) return rc;
     if ((rc = alga_ensure(e, e->cl_pile_cnt, PILE_CNT_WORDS * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->cl_pile_own, pile_own_mask_bytes(n)))) return rc;
+    if (e->opt_pile_runs_list && (rc = alga_ensure(e, e->cl_pile_list, pile_list_bytes(n)))) return rc;
     if ((rc = alga_ensure(e, e->cl_defer, (size_t) (n + 64) * sizeof(int32_t)))) return rc;      // (the list of own-list ids first, the probe's defer list later)
     const void *before = e->cl_pile_tab.p;
     const size_t cap_before = e->cl_pile_tab.cap;
@@ -164,6 +165,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
     e->pairs_timed = false;
     e->store_timed = false;
     e->pile_timed = false;
+    e->pile_deg_pending = false;
     // the probe through piles: all sources in entry order, reads of one length without masks (prefsuf_pile.hip: pile_plan)
     // (a range of ids -- a rank's share of the strong-scaling N-GPU build, option pile_range: the same index, the range's side records compacted for the probe)
     const bool all_sources = src_begin == 0 && src_end == pp.nd.n;
@@ -245,6 +247,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                     // that fitted without it must not fail because of it.  Give back what was allocated of it and take the pairwise kernels.
                     (void) hipGetLastError();
                     alga_release(e->cl_pile_tab); alga_release(e->cl_pile_rec); alga_release(e->cl_pile_rec2); alga_release(e->cl_pile_succ); alga_release(e->cl_pile_own);
+                    alga_release(e->cl_pile_list);
                     e->pile_epoch = 0; e->pile_n = -1;
                     e->err.clear();
                     pile = false;
@@ -274,7 +277,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                 const bool from_consensus = e->opt_pile_runs != 0;
                 launch_pile_build(nd, cfg, cc, pp.uniform_len, (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, e->cl_dir.p, e->cl_pile_rec.p, e->cl_pile_rec2.p, e->cl_pile_tab.p,
                                   e->pile_epoch, e->cl_pile_succ.p, e->cl_runs.p, pp.uniform_len - cfg.Lmin + 1, (const unsigned long long *) e->cl_pile_cnt.p,
-                                  from_consensus ? (uint32_t *) e->cl_pile_own.p : nullptr, s);
+                                  from_consensus ? (uint32_t *) e->cl_pile_own.p : nullptr, (from_consensus && e->opt_pile_runs_list) ? e->cl_pile_list.p : nullptr, s);
                 if ((rc = alga_check_launch(e, "k_pile_build"))) return rc;
                 if (keys_only) {
                     // own run lists of the entries outside a first group (6 % at the north-star size) ...
@@ -377,7 +380,9 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                                        cap, cnt, e->n_cu, (uint32_t *) e->outdeg.p, (unsigned long long *) e->loc_first.p, &big, cnt + CNT_DEFERRED, 1, s,
                                        (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, pp.uniform_len,
                                        (piled && e->opt_pile_skip_gather) ? (const unsigned long long *) e->cl_pile_cnt.p : nullptr);
-                if (piled) launch_pile_deg((int32_t) n_src, (unsigned long long *) e->loc_first.p, (uint32_t *) e->outdeg.p, (const unsigned long long *) e->cl_pile_cnt.p, s);
+                // the out-degrees k_pile_probe left in the slots: moved to outdeg by the first pass of finalize_local's scan (option pile_deg_fold), or here
+                e->pile_deg_pending = piled && e->opt_pile_deg_fold != 0;
+                if (piled && !e->pile_deg_pending) launch_pile_deg((int32_t) n_src, (unsigned long long *) e->loc_first.p, (uint32_t *) e->outdeg.p, (const unsigned long long *) e->cl_pile_cnt.p, s);
             } else {
                 launch_probe_clustered(nd, cfg, cc, pp.cluster_eq, e->cl_store.p, e->cl_dir.p, e->cl_runs.p, (const uint8_t *) e->cl_nruns.p, src_begin,
                                        src_end, nullptr, src_begin, (uint32_t *) e->rec_dst.p, (unsigned long long *) e->rec_val.p, cap, cnt, e->n_cu,
@@ -410,6 +415,10 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
             if ((rc = alga_ensure(e, e->loc_big_items, probe_big_bytes(e->n_cu, big.count, pp.local_sw, big.item_cap)))) return rc;
             big.items = e->loc_big_items.p;
             if (!have_table && (rc = build_table())) return rc;            // the second pass probes through the seed table
+            if (e->pile_deg_pending) {                     // (the second pass finds the out-degrees where the first pass's kernels leave them)
+                launch_pile_deg((int32_t) n_src, (unsigned long long *) e->loc_first.p, (uint32_t *) e->outdeg.p, (const unsigned long long *) e->cl_pile_cnt.p, s);
+                e->pile_deg_pending = false;
+            }
             HIP_TRY(e, hipMemsetAsync(cnt + CNT_LOCAL_OVERFLOW, 0, sizeof(unsigned long long), s));
             launch_probe(nd, cfg, (const unsigned long long *) e->table.p, n_buckets, (const uint32_t *) e->filter.p, filter_bits, src_begin, src_end,
                          (uint32_t *) e->rec_dst.p, (unsigned long long *) e->rec_val.p, cap, cnt, e->n_cu, pp.local_sw, (uint32_t *) e->outdeg.p,
@@ -543,7 +552,12 @@ int finalize_local(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_
     if ((rc = alga_ensure(e, e->out_cnt, (size_t) (n_src + 1) * sizeof(uint32_t)))) return rc;
     HIP_TRY(e, hipEventRecord(e->ev[EV_GROUP], s));
     HIP_TRY(e, hipEventRecord(e->ev[EV_REDUCE], s));
-    launch_exclusive_scan((const uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, s);
+    if (e->pile_deg_pending)
+        launch_exclusive_scan_pile_deg((uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, (unsigned long long *) e->loc_first.p,
+                                       (const unsigned long long *) e->cl_pile_cnt.p, s);
+    else
+        launch_exclusive_scan((const uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, s);
+    e->pile_deg_pending = false;
     if ((rc = alga_check_launch(e, "scan(outdeg)"))) return rc;
     const uint64_t E = e->stats.records;                                   // CNT_VALID_RECORDS of the probe == sum of the out-degrees (launch_local_emit zeroes the cursors it needs)
     if (E >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 edges; shard the input");
@@ -698,6 +712,10 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_pile = (value == 2 || value == 3) ? (int) value : (value != 0);       // (2, 3, tests only: no sample -- the pile kernels take every build they can, however many buckets are irregular; 3: in the mixed form)
     } else if (!strcmp(name, "pile_runs")) {
         e->opt_pile_runs = value != 0;
+    } else if (!strcmp(name, "pile_runs_list")) {
+        e->opt_pile_runs_list = value != 0;
+    } else if (!strcmp(name, "pile_deg_fold")) {
+        e->opt_pile_deg_fold = value != 0;
     } else if (!strcmp(name, "pile_check")) {
         e->opt_pile_check = value != 0;
     } else if (!strcmp(name, "pile_skip_gather")) {

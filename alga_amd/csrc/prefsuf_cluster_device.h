@@ -97,11 +97,20 @@ __device__ __forceinline__ void run_slice(const uint4 &rec, uint32_t run_y, uint
     e0 = rec.x + b0; cnt = b1 - b0;
 }
 
+// word k of a row staged in LDS: RS = words between two words of the row (1: a row of its own; TK_ROWS: word-major, one row per thread);
+// RW > 0: the row holds RW words and reads past them are zero (a row's tail is zero anyway -- the storage of the words past RW is saved)
+template <int RS = 1, int RW = 0>
+__device__ __forceinline__ uint32_t row_word(const uint32_t *row, int k) {
+    if (RW > 0) { const uint32_t v = row[(k < RW ? k : RW - 1) * RS]; return k < RW ? v : 0u; }
+    return row[k * RS];
+}
+
 // k-mer starting at nucleotide i of a 2-bit row (words readable up to index (2i >> 5) + 2): its hash and its packed
 // order key (class | 23-bit order | position); the smallest key of a window is the window's minimizer
+template <int RS = 1, int RW = 0>
 __device__ __forceinline__ void kmer_key(const uint32_t *row, int i, bool valid, const ClusterCfg &cc, uint32_t &h, uint32_t &pk) {
     const int bit = 2 * i, q = bit >> 5, r = bit & 31;
-    const uint32_t x0 = row[q], x1 = row[q + 1], x2 = row[q + 2];
+    const uint32_t x0 = row_word<RS, RW>(row, q), x1 = row_word<RS, RW>(row, q + 1), x2 = row_word<RS, RW>(row, q + 2);
     const uint32_t lo = funnel(x0, x1, r) & cc.lo_mask;
     h = kmer_hash(lo, funnel(x1, x2, r) & cc.hi_mask);
     pk = valid ? order_key(h, lo, i) : 0xFFFFFFFFu;
@@ -119,14 +128,16 @@ constexpr int NR_STACK = 8;          // minimum records kept per row and block (
 // steps on the row shifted by the piece's first window; the runs of the pieces are listed one after the other (a minimizer that spans a seam makes
 // two runs: one more look-up for a node, merged again for a pile).
 // RCAP: runs the list holds (rbuf has RCAP + 1 rows; CL_RMAX for a node's list, more for a pile's extent, whose pieces each add a run at their seam)
-template <bool WIDE, int RCAP = CL_RMAX>
+// RS, RW: how the row lies in LDS (row_word)
+template <bool WIDE, int RCAP = CL_RMAX, int RS = 1, int RW = 0>
 __device__ __forceinline__ void node_runs_core(const uint32_t *row, int nwin, bool act, const ClusterCfg &cc, uint32_t (*stk)[TK_ROWS], uint16_t (*rbuf)[TK_ROWS], int t,
                                                int &nr, bool &uncovered, bool &stack_ovf, uint32_t &cur0, int step = 64) {
     constexpr int S0 = NR_STACK + 1;                       // first row of block 0's records
     const int w = cc.w;
     nr = 0; uncovered = false; stack_ovf = false; cur0 = 0xFFFFFFFFu;
     for (int hb = (WIDE && nwin > step) ? ((nwin - 1) / step) * step : 0; hb >= 0; hb -= step) {       // first window of the piece (one pass with hb = 0 unless WIDE)
-        const uint32_t *rowh = row + (hb >> 4);
+        const int h0 = hb >> 4;
+        auto rowh = [&](int k) -> uint32_t { return row_word<RS, RW>(row, h0 + k); };
         const int nwh = !WIDE ? nwin : (nwin - hb < step ? nwin - hb : step);
         const int nk = act ? nwh - 1 + w : 0;              // k-mer positions of the half (relative to hb): <= 127
         // ---- class-0 k-mer positions: bit p of the 128-bit mask (static row indices: registers, no scratch) ----
@@ -135,7 +146,7 @@ __device__ __forceinline__ void node_runs_core(const uint32_t *row, int nwin, bo
             uint32_t dm[4];
 #pragma unroll
             for (int d = 0; d < 4; d++) {
-                const uint32_t x0 = rowh[2 * d], x1 = rowh[2 * d + 1], x2 = rowh[2 * d + 2];
+                const uint32_t x0 = rowh(2 * d), x1 = rowh(2 * d + 1), x2 = rowh(2 * d + 2);
                 dm[d] = compress_even(class0_mask16(x0, x1)) | (compress_even(class0_mask16(x1, x2)) << 16);
             }
             m_lo = (uint64_t) dm[0] | ((uint64_t) dm[1] << 32);
@@ -147,7 +158,7 @@ __device__ __forceinline__ void node_runs_core(const uint32_t *row, int nwin, bo
         uint64_t b1 = w >= 64 ? m_hi : ((m_lo >> w) | (m_hi << (64 - w)));    // uniform branch; bit e = k-mer w + e
         auto key_at = [&](int pos) -> uint32_t {           // order key of the class-0 k-mer at `pos` (relative to the half)
             const int bit = 2 * pos, q = bit >> 5, r = bit & 31;
-            const uint32_t x0 = rowh[q], x1 = rowh[q + 1], x2 = rowh[q + 2];
+            const uint32_t x0 = rowh(q), x1 = rowh(q + 1), x2 = rowh(q + 2);
             return order_key0(kmer_hash(funnel(x0, x1, r) & cc.lo_mask, funnel(x1, x2, r) & cc.hi_mask), pos);
         };
         // ---- (1) block 1, left to right: prefix-minimum records ----

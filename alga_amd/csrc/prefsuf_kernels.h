@@ -79,9 +79,11 @@ void       launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int unif
                               unsigned long long *pile_cnt /* of the sample: [0] buckets (raised to entries / 8), [1] irregular buckets, [2] entries */, int no_sample, hipStream_t s);
 constexpr int PILE_CNT_WORDS = 6;      // {sampled buckets, irregular ones, sampled entries, own-list ids, members checked, members whose lists differ}
 size_t     pile_own_mask_bytes(uint64_t n);
+size_t     pile_list_bytes(uint64_t n);
 void       launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys, const uint32_t *sids, const void *dir, void *rec,
                              void *rec2 /* run lists of the further groups, at the groups' slots */, void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt,
-                             uint32_t *own_mask /* null: the piles' run lists from their outer members' own lists (round 4) */, hipStream_t s);
+                             uint32_t *own_mask /* null: the piles' run lists from their outer members' own lists (round 4) */,
+                             void *plist /* null: k_pile_runs_consensus finds the piles in the side records; else pile_list_bytes(n) of scratch */, hipStream_t s);
 void       launch_pile_own_ids(const uint32_t *own_mask, const uint32_t *sids, uint64_t n_entries, int32_t *list, uint32_t cap, unsigned long long *pile_cnt, hipStream_t s);
 void       launch_pile_check(const void *side, uint64_t n_entries, uint32_t n_buckets, const void *tab, const void *rec2, uint32_t epoch, const void *runs, int n_nodes, int nwin,
                              unsigned long long *pile_cnt, hipStream_t s);
@@ -124,6 +126,7 @@ void launch_rowptr_from_sorted(const uint32_t *keys, const unsigned long long *n
 size_t   scan_scratch_bytes(uint64_t n);
 uint64_t scan_total_index(uint64_t n); // scratch[scan_total_index(n)] holds the 64-bit total after the scan
 void launch_exclusive_scan(const uint32_t *in, uint64_t n, uint32_t *out, uint64_t *scratch, hipStream_t s);
+void launch_exclusive_scan_pile_deg(uint32_t *deg, uint64_t n, uint32_t *out, uint64_t *scratch, unsigned long long *first, const unsigned long long *pile_cnt, hipStream_t s);
 // up to MAIL_SEGS pieces of device memory (32-bit words) -> a pinned host block through its device address (engine: h_counters), one kernel
 constexpr int MAIL_SEGS = 6;
 struct MailSeg { const uint32_t *src; uint32_t words, dst; };            // dst: word offset in the host block

@@ -29,6 +29,7 @@
 #include "prefsuf_common.h"
 #include "prefsuf_kernels.h"
 #include "prefsuf_device.h"
+#include "prefsuf_cluster_device.h"
 
 namespace alga {
 
@@ -635,6 +636,48 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_tile_sums(const uint32_t *_
         for (int k = 0; k < SCAN_ITEMS; k++) {
             uint64_t i = base + (uint64_t) k * SCAN_BLOCK + threadIdx.x;
             if (i < n) s += in[i];
+        }
+    }
+    uint32_t tot;
+    block_exclusive_scan(s, &tot, lds);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
+}
+
+// the tile sums of the out-degrees of a build the pile path kept, and those degrees themselves: k_pile_probe left the out-degree of a source it
+// finished in bit 8 of the source's slot (prefsuf_pile.hip, k_pile_deg -- the same rule, here fused into the pass that reads deg[] anyway).
+// Nothing to move where the sample declined the build (pile_cnt: decided on the device).
+__device__ __forceinline__ uint32_t pile_deg_one(unsigned long long *first, uint64_t i, uint32_t d) {
+    const unsigned long long f = first[i];
+    if (f == LOCAL_FIRST_NONE || d != 0u) return d;        // no edge, or a source the pairwise kernels finished (deg and slot are theirs)
+    if (f & 0x100ull) first[i] = f & ~0x100ull;
+    return 1u + (uint32_t) ((f >> 8) & 1ull);
+}
+__global__ void __launch_bounds__(SCAN_BLOCK) k_scan_tile_sums_pile_deg(uint32_t *__restrict__ deg, uint64_t n, uint64_t *__restrict__ tile_sums, unsigned long long *__restrict__ first,
+                                                                         const unsigned long long *__restrict__ pile_cnt) {
+    __shared__ uint32_t lds[8];
+    const bool move = !pile_cnt_declines(pile_cnt);
+    const uint64_t base = (uint64_t) blockIdx.x * SCAN_TILE;
+    uint32_t s = 0;
+    if (base + SCAN_TILE <= n && (reinterpret_cast<uintptr_t>(deg) & 15u) == 0) {
+        uint4 *d4 = reinterpret_cast<uint4 *>(deg + base);
+#pragma unroll
+        for (int k = 0; k < SCAN_ITEMS / 4; k++) {
+            uint4 v = d4[k * SCAN_BLOCK + threadIdx.x];
+            if (move) {
+                const uint64_t i = base + 4 * ((uint64_t) k * SCAN_BLOCK + threadIdx.x);
+                const uint4 w = make_uint4(pile_deg_one(first, i, v.x), pile_deg_one(first, i + 1, v.y), pile_deg_one(first, i + 2, v.z), pile_deg_one(first, i + 3, v.w));
+                if (w.x != v.x || w.y != v.y || w.z != v.z || w.w != v.w) { d4[k * SCAN_BLOCK + threadIdx.x] = w; v = w; }
+            }
+            s += v.x + v.y + v.z + v.w;
+        }
+    } else {
+        for (int k = 0; k < SCAN_ITEMS; k++) {
+            const uint64_t i = base + (uint64_t) k * SCAN_BLOCK + threadIdx.x;
+            if (i < n) {
+                uint32_t v = deg[i];
+                if (move) { const uint32_t w = pile_deg_one(first, i, v); if (w != v) { deg[i] = w; v = w; } }
+                s += v;
+            }
         }
     }
     uint32_t tot;
@@ -1315,6 +1358,16 @@ void launch_exclusive_scan(const uint32_t *in, uint64_t n, uint32_t *out, uint64
     hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles), dim3(SCAN_BLOCK), 0, s, in, n, scratch);
     hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, s, scratch, tiles);
     hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(SCAN_BLOCK), 0, s, in, n, scratch, out);
+}
+
+// the same scan of the out-degrees of a source-side build the pile path may have kept: the first pass also moves the out-degrees k_pile_probe
+// left in the slots (first[]) to deg[] -- what launch_pile_deg does in a pass of its own
+void launch_exclusive_scan_pile_deg(uint32_t *deg, uint64_t n, uint32_t *out, uint64_t *scratch, unsigned long long *first, const unsigned long long *pile_cnt, hipStream_t s) {
+    if (n == 0) { launch_exclusive_scan(deg, n, out, scratch, s); return; }
+    const uint32_t tiles = (uint32_t) ((n + SCAN_TILE - 1) / SCAN_TILE);
+    hipLaunchKernelGGL(k_scan_tile_sums_pile_deg, dim3(tiles), dim3(SCAN_BLOCK), 0, s, deg, n, scratch, first, pile_cnt);
+    hipLaunchKernelGGL(k_scan_spine, dim3(1), dim3(1024), 0, s, scratch, tiles);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(SCAN_BLOCK), 0, s, (const uint32_t *) deg, n, scratch, out);
 }
 
 uint64_t scan_total_index(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }

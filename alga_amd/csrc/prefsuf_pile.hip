@@ -29,7 +29,8 @@
 //                  members' windows on the pile's axis), into the second half of the bucket's record.
 //   k_pile_probe   one lane per SOURCE (in the order of the entry array): per run the first 64 bytes of the bucket's record, loaded once
 //                  per distinct bucket of a wave; regular sources get their edges, the others go on the defer list of k_probe_clustered.
-//   k_pile_deg     a streaming pass that moves the out-degree k_pile_probe left in the source's slot to deg[].
+//   k_pile_deg     a streaming pass that moves the out-degree k_pile_probe left in the source's slot to deg[] (by default the first pass of the
+//                  out-degree scan does that: k_scan_tile_sums_pile_deg, prefsuf_kernels.hip; option pile_deg_fold).
 // Nothing is approximated: every decision either follows from verified equalities or is handed to the pairwise kernels.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -70,6 +71,11 @@ constexpr int PILE_EQ = 3;                     // entry size this path takes: ro
 // handed on go through k_probe_stream in list mode, ~0.3 ms per million, before the general kernel: prefsuf_cluster_device.h)
 __device__ __forceinline__ bool pile_declines(const unsigned long long *pile_cnt) { return pile_cnt_declines(pile_cnt); }
 
+// a pile's id as the lists carry it: a first group -> its bucket; a further group -> its slot | bit 31
+__device__ __forceinline__ uint32_t pile_who(uint32_t group, uint32_t w, uint32_t n_buckets, uint64_t n_entries) {
+    return group == 0u ? min(w, n_buckets) : (uint32_t) min((uint64_t) w, n_entries) | 0x80000000u;
+}
+
 // the row of node `id`, up to nine words (the pile path takes rows of that size only), straight from the node array
 __device__ __forceinline__ void load_row9(const NodesDev &nd, uint32_t id, uint32_t (&row)[9]) {
     const uint32_t *rp = nd.words + (size_t) id * nd.stride;
@@ -86,7 +92,8 @@ __device__ __forceinline__ void load_row9(const NodesDev &nd, uint32_t id, uint3
 template <bool SAMPLE>
 __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const uint32_t *__restrict__ skeys, const uint32_t *__restrict__ sids, uint64_t n_entries, const uint4 *__restrict__ dir, ClusterCfg cc, int U,
                                                            uint4 *__restrict__ rec, uint4 *__restrict__ tab, uint32_t epoch,
-                                                           uint4 *__restrict__ side, unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask) {
+                                                           uint4 *__restrict__ side, unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask,
+                                                           uint32_t *__restrict__ plist, uint32_t *__restrict__ pcount) {
     if (!SAMPLE && pile_declines(pile_cnt)) return;
     const int idx_shift = cc.idx_shift, kk = cc.kk;
     __shared__ uint32_t sRow[PB_THREADS][PILE_SW];         // the entry's row on the pile's axis, masked to its extent (odd stride: conflict-free)
@@ -97,6 +104,7 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
     __shared__ uint32_t sBad[PB_THREADS];                  // per bucket
     __shared__ uint8_t sTag[PB_THREADS];                   // per leader
     __shared__ uint32_t sCount[3];                         // buckets, irregular buckets, entries of buckets that begin in the tile (sample only)
+    __shared__ uint32_t sPiles;                            // piles this workgroup put on its list (plist)
     const int t = (int) threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * PB_TILE;
     const uint64_t j = base + (uint64_t) t;
@@ -121,6 +129,7 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
     if (part) load_row9(nd, node_id, row);
     sLead[t] = 0ull; sRm[t] = 0ull; sMin[t] = 0xFFFFFFFFu; sMax[t] = 0u; sBad[t] = 0u;
     if (t < 3) sCount[t] = 0u;
+    if (t == 0) sPiles = 0u;
     __syncthreads();
     // the row on the pile's axis: consensus index x (coordinate x - 64) = nucleotide x - 64 + m of the row = bit 2 x + 2 m of the row padded
     // with four zero words in front.  The word offset (2 m) >> 5 is one of 0 .. 3: two selects per word, static register indices.
@@ -226,6 +235,8 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
                 // the last word: the bucket (a first group's record is the bucket's line of `tab`), or the slot of a further group's records
                 side[j] = make_uint4(node_id, succ_id, delta | ((uint32_t) m << 8) | ((uint32_t) k << 16) | (leftmost ? 0x40000000u : 0u) | (first_group ? 0x80000000u : 0u),
                                      k == 0 ? key >> idx_shift : (uint32_t) (e0 + (uint64_t) k));
+                // the pile on this workgroup's list (k_pile_runs_consensus_list: the order is free, each pile writes its own record)
+                if (leftmost && plist) plist[(size_t) blockIdx.x * PB_THREADS + atomicAdd(&sPiles, 1u)] = pile_who((uint32_t) k, k == 0 ? key >> idx_shift : (uint32_t) (e0 + (uint64_t) k), cc.n_buckets, n_entries);
                 // an entry of no pile reads its OWN run list as a source (k_pile_probe): bit j of the mask the list-driven key pass works from
                 if (!first_group && own_mask) atomicOr(&own_mask[j >> 5], 1u << (j & 31u));
             }
@@ -272,6 +283,7 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
     }
     if (SAMPLE && owned) atomicAdd(&sCount[2], 1u);
     __syncthreads();
+    if (!SAMPLE && plist && t == 0) pcount[blockIdx.x] = sPiles;
     if (SAMPLE && t < 3 && sCount[t]) atomicAdd(&pile_cnt[t], (unsigned long long) sCount[t]);      // (the sample is a few thousand workgroups)
 }
 
@@ -364,12 +376,119 @@ __global__ void __launch_bounds__(256) k_pile_runs(const uint4 *__restrict__ sid
 // computes the TARGET keys alone (k_node_runs<., ., false>), and own lists only for the entries outside a first group (own_mask) and for
 // the sources k_pile_probe hands to the general kernel.  A member's own list is the pile's list clipped to its windows, bit for bit
 // (tests/test_gpu_pile.py: test_consensus_run_lists_equal_the_members_own; engine option "pile_check").
-// A block takes a tile of entries, lists the leftmost members (T0, flagged by k_pile_build) in LDS and gives every thread one pile.
+// Two forms (engine option "pile_runs_list"):
+//   k_pile_runs_consensus_list (1) -- k_pile_build leaves the piles it flags in a list per workgroup of its own (PB_THREADS slots and a count, no
+//     atomics beyond the workgroup's LDS); a block of this kernel takes PR_SEGS of those lists, every thread one pile.  The row lies word-major in LDS
+//     and holds the PILE_SW words of the extent only (row_word reads the rest as zero): 19.8 KB per block of 128, four waves per SIMD.
+//   k_pile_runs_consensus (0, round 5) -- a block sweeps a tile of PR_TILE side records for the leftmost members (T0, flagged by k_pile_build),
+//     lists them in LDS and gives every thread one pile: 36 KB per block, two waves per SIMD, and every side record read once more.
 // A pile whose list cannot be made (a window without a class-0 k-mer, more than eight runs, more records than a stack holds) stays without one:
 // its members probe with their own lists (own_mask), and a member whose own list is flagged as well goes to the general kernel.
 constexpr int PR_TILE = 3072;                              // entries per block of k_pile_runs_consensus (~500 piles at 30x: four rounds of 128)
 constexpr int PR_TKW = 21;
 constexpr int PR_RCAP = 14;                                // raw runs of a pile's extent (the eight a list holds after the seams are merged + a run per seam)
+constexpr int PR_SEGS = 32;                                // k_pile_build workgroups (their pile lists) per block of k_pile_runs_consensus_list (~1000 piles at 30x: eight rounds of 128)
+
+// pile `who` (a bucket, or a further group's slot | bit 31; `in`: the thread has one) -> its run list.  row: the thread's row in LDS, word k at row[k * RS]
+// (RW > 0: RW words, node_runs_core reads the rest as zero)
+template <int RS, int RW>
+__device__ __forceinline__ void pile_consensus_one(uint32_t who, bool in, uint32_t *row, uint32_t (*stk)[TK_ROWS], uint16_t (*rbuf)[TK_ROWS], int t, const uint4 *__restrict__ side,
+                                                   uint64_t n_entries, uint4 *__restrict__ tab, const uint4 *__restrict__ rec, uint4 *__restrict__ rec2, const ClusterCfg &cc, int U,
+                                                   int Lmin, uint32_t *__restrict__ own_mask) {
+    const int fs = cc.idx_shift - CL_MBITS;
+    const int step = max(16, min(64, cc.w) & ~15);         // windows per piece of the sweep: no more than w, whole row words (w >= 16 for every shape pile_plan takes)
+    const bool further = (who >> 31) != 0u;                // a further group of its bucket: consensus in rec, list into rec2
+    const uint32_t slot = who & 0x7FFFFFFFu;
+    uint4 *line = tab + (size_t) (further ? 0u : who) * 8;
+    const uint4 *src = further ? rec + (size_t) slot * 4 : (const uint4 *) line;
+    uint32_t S[PILE_SW + 1];
+    unsigned long long rm = 0ull;
+    {
+        const uint4 l0 = src[0], l1 = src[1], l2 = src[2], l3 = src[3];
+        S[0] = l0.x; S[1] = l0.y; S[2] = l0.z; S[3] = l0.w; S[4] = l1.x; S[5] = l1.y; S[6] = l1.z; S[7] = l1.w;
+        S[8] = l2.x; S[9] = l2.y; S[10] = l2.z; S[11] = l2.w; S[12] = l3.x; S[13] = 0u;
+        rm = !in ? 0ull : (further ? (((unsigned long long) l3.w << 32) | l3.z) : (((unsigned long long) l3.z << 32) | l3.y));
+    }
+    const bool act = in && rm != 0ull;
+    const int m_min = act ? __clzll((long long) rm) : 0, m_max = act ? 63 - __builtin_ctzll(rm) : 0;
+    const int len_v = U + m_max - m_min;                   // the pile's extent: [-m_max, -m_min + U)
+    const int nwin = len_v - Lmin + 1;                     // <= 127
+    // the extent as a row of its own: consensus index 64 - m_max onwards (the consensus is zero outside the extent, like the tail of a row)
+    {
+        const int ob = 2 * (64 - m_max), w0 = ob >> 5, sh = ob & 31;          // w0 in 0 .. 4 (4: every member starts at the k-mer)
+        uint32_t m1 = 0u - (uint32_t) (w0 & 1), m2 = 0u - (uint32_t) ((w0 >> 1) & 1), m4 = 0u - (uint32_t) ((w0 >> 2) & 1);
+        asm volatile("" : "+v"(m1), "+v"(m2), "+v"(m4));          // (opaque masks: written as selects the stages become a dynamically indexed array in scratch)
+        uint32_t y1[PILE_SW + 1], y2[PILE_SW + 1], y[PILE_SW + 1];
+#pragma unroll
+        for (int k = 0; k <= PILE_SW; k++) y1[k] = ((k + 1 <= PILE_SW ? S[k + 1] : 0u) & m1) | (S[k] & ~m1);
+#pragma unroll
+        for (int k = 0; k <= PILE_SW; k++) y2[k] = ((k + 2 <= PILE_SW ? y1[k + 2] : 0u) & m2) | (y1[k] & ~m2);
+#pragma unroll
+        for (int k = 0; k <= PILE_SW; k++) y[k] = ((k + 4 <= PILE_SW ? y2[k + 4] : 0u) & m4) | (y2[k] & ~m4);
+#pragma unroll
+        for (int k = 0; k < (RW > 0 ? RW : PR_TKW); k++) row[k * RS] = k < PILE_SW ? funnel(y[k], y[k + 1], sh) : 0u;
+    }
+    // (each thread reads the row it wrote: no barrier)
+    int nr = 0;
+    bool uncovered = false, stack_ovf = false;
+    uint32_t cur0 = 0u;
+    node_runs_core<true, PR_RCAP, RS, RW>(row, nwin, act, cc, stk, rbuf, t, nr, uncovered, stack_ovf, cur0, step);
+    bool ok = act && nr >= 1 && nr <= PR_RCAP && !uncovered && !stack_ovf;
+    // runs as they were found: the last windows first, q | p0 << 8 in the extent's own coordinates, p1 = p0 of the run before.  The record
+    // wants them ascending on the pile's axis (coordinate + 64 in a byte); the two halves of the window range meet at window 64: a minimizer
+    // on both sides of that seam is ONE run (k_pile_probe takes "the same minimizer twice" for a tandem repeat)
+    uint32_t key_[PILE_RUNS], kc_[PILE_RUNS];
+#pragma unroll
+    for (int k = 0; k < PILE_RUNS; k++) { key_[k] = 0u; kc_[k] = 0u; }
+    int n = 0;
+    uint32_t last_q = 0xFFFFFFFFu;
+    const int nrs = nr < PR_RCAP ? nr : PR_RCAP;
+    for (int r = PR_RCAP - 1; r >= 0; r--) {
+        if (ok && r < nrs) {
+            const uint32_t d = rbuf[r][t];
+            const int q = (int) (d & 255u), p0 = (int) (d >> 8);
+            if ((uint32_t) q != last_q) {                  // (the same k-mer as the run before: the seam of two pieces -- one run)
+                uint32_t h, pk;
+                kmer_key<RS, RW>(row, q < 192 ? q : 0, true, cc, h, pk);
+                const uint32_t kv = cluster_key(h, fs), cv = (uint32_t) (q - m_max + 64) | ((uint32_t) (p0 - m_max + 64) << 8);
+#pragma unroll
+                for (int k = 0; k < PILE_RUNS; k++) if (k == n) { key_[k] = kv; kc_[k] = cv; }
+                n++;
+                last_q = (uint32_t) q;
+            }
+        }
+    }
+    ok = ok && n >= 1 && n <= PILE_RUNS;
+    if (in && further) {
+        // a further group: its list in rec2 at the group's slot, laid out like the second half of a bucket's line (word 0 = runs << 8 | end << 16)
+        uint4 *l2 = rec2 + (size_t) slot * 4 - 4;          // (pile_list_store writes line[4 .. 7])
+        pile_list_store(l2, 0u, ok, n, key_, kc_, (uint32_t) (nwin - m_max + 64));
+        if (!ok) {
+            // its members probe with their own lists: the entries of the bucket (it starts k slots back) that carry this group's slot
+            // (the bucket begins k <= 3 slots before the group's slot)
+            const uint64_t jb = slot >= 3u ? (uint64_t) slot - 3u : 0ull;
+            for (uint64_t j2 = jb; j2 < jb + 64u + 3u && j2 < n_entries; j2++) {
+                const uint4 s2 = side[j2];
+                if ((s2.z >> 31) && ((s2.z >> 16) & 3u) != 0u && s2.w == slot) atomicOr(&own_mask[j2 >> 5], 1u << (j2 & 31u));
+            }
+        }
+    } else if (in) {
+        uint32_t *lw = reinterpret_cast<uint32_t *>(line);
+        pile_list_store(line, lw[16], ok, n, key_, kc_, (uint32_t) (nwin - m_max + 64));
+        if (!ok) {
+            // no list (3 piles in 1000: a window without a class-0 k-mer somewhere on the extent, mostly): the members probe with their OWN
+            // lists, as the entries outside a first group do -- noted in own_mask for the list-driven key pass that follows.  (Marking the
+            // bucket irregular instead sent every source with a run in it to the general kernel: 1.7 M more sources at the north-star size.)
+            lw[16] = lw[16] & 255u;
+            const uint32_t cntb = min(lw[16] & 255u, 64u), e0b = lw[17];
+            for (uint32_t i2 = 0; i2 < cntb; i2++) {
+                const uint64_t j2 = (uint64_t) e0b + i2;
+                if (j2 < n_entries) { const uint4 s2 = side[j2]; if ((s2.z >> 31) && ((s2.z >> 16) & 3u) == 0u) atomicOr(&own_mask[j2 >> 5], 1u << (j2 & 31u)); }
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(TK_ROWS) k_pile_runs_consensus(const uint4 *__restrict__ side, uint64_t n_entries, uint32_t n_buckets, uint4 *__restrict__ tab, const uint4 *__restrict__ rec,
                                                                  uint4 *__restrict__ rec2, ClusterCfg cc, int U, int Lmin,
                                                                  const unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask) {
@@ -389,106 +508,46 @@ __global__ void __launch_bounds__(TK_ROWS) k_pile_runs_consensus(const uint4 *__
         if (j < n_entries) {
             const uint4 sd = side[j];
             // (the order of the piles in the list is free: each writes its own record).  A first group: its bucket; a further group: its slot | bit 31
-            if ((sd.z >> 30) & 1u) sList[atomicAdd(&sN, 1u)] = ((sd.z >> 16) & 3u) == 0u ? min(sd.w, n_buckets) : (uint32_t) min((uint64_t) sd.w, n_entries) | 0x80000000u;
+            if ((sd.z >> 30) & 1u) sList[atomicAdd(&sN, 1u)] = pile_who((sd.z >> 16) & 3u, sd.w, n_buckets, n_entries);
         }
     }
     __syncthreads();
     const int np = (int) sN;
-    const int fs = cc.idx_shift - CL_MBITS;
-    const int step = max(16, min(64, cc.w) & ~15);         // windows per piece of the sweep: no more than w, whole row words (w >= 16 for every shape pile_plan takes)
     for (int c0 = 0; c0 < np; c0 += TK_ROWS) {             // uniform
         const bool in = c0 + t < np;
-        const uint32_t who = sList[in ? c0 + t : 0];
-        const bool further = (who >> 31) != 0u;            // a further group of its bucket: consensus in rec, list into rec2
-        const uint32_t slot = who & 0x7FFFFFFFu;
-        uint4 *line = tab + (size_t) (further ? 0u : who) * 8;
-        const uint4 *src = further ? rec + (size_t) slot * 4 : (const uint4 *) line;
-        uint32_t S[PILE_SW + 1];
-        unsigned long long rm = 0ull;
-        {
-            const uint4 l0 = src[0], l1 = src[1], l2 = src[2], l3 = src[3];
-            S[0] = l0.x; S[1] = l0.y; S[2] = l0.z; S[3] = l0.w; S[4] = l1.x; S[5] = l1.y; S[6] = l1.z; S[7] = l1.w;
-            S[8] = l2.x; S[9] = l2.y; S[10] = l2.z; S[11] = l2.w; S[12] = l3.x; S[13] = 0u;
-            rm = !in ? 0ull : (further ? (((unsigned long long) l3.w << 32) | l3.z) : (((unsigned long long) l3.z << 32) | l3.y));
-        }
-        const bool act = in && rm != 0ull;
-        const int m_min = act ? __clzll((long long) rm) : 0, m_max = act ? 63 - __builtin_ctzll(rm) : 0;
-        const int len_v = U + m_max - m_min;               // the pile's extent: [-m_max, -m_min + U)
-        const int nwin = len_v - Lmin + 1;                 // <= 126
-        // the extent as a row of its own: consensus index 64 - m_max onwards (the consensus is zero outside the extent, like the tail of a row)
-        {
-            const int ob = 2 * (64 - m_max), w0 = ob >> 5, sh = ob & 31;          // w0 in 0 .. 4 (4: every member starts at the k-mer)
-            uint32_t m1 = 0u - (uint32_t) (w0 & 1), m2 = 0u - (uint32_t) ((w0 >> 1) & 1), m4 = 0u - (uint32_t) ((w0 >> 2) & 1);
-            asm volatile("" : "+v"(m1), "+v"(m2), "+v"(m4));          // (opaque masks: written as selects the stages become a dynamically indexed array in scratch)
-            uint32_t y1[PILE_SW + 1], y2[PILE_SW + 1], y[PILE_SW + 1];
+        pile_consensus_one<1, 0>(sList[in ? c0 + t : 0], in, s[t], stk, rbuf, t, side, n_entries, tab, rec, rec2, cc, U, Lmin, own_mask);
+    }
+}
+
+// the piles k_pile_build listed: workgroup b of that kernel left its own in plist[b * PB_THREADS ..] and their number in pcount[b]
+__global__ void __launch_bounds__(TK_ROWS) k_pile_runs_consensus_list(const uint32_t *__restrict__ plist, const uint32_t *__restrict__ pcount, uint32_t n_segs, const uint4 *__restrict__ side,
+                                                                      uint64_t n_entries, uint4 *__restrict__ tab, const uint4 *__restrict__ rec, uint4 *__restrict__ rec2, ClusterCfg cc,
+                                                                      int U, int Lmin, const unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask) {
+    if (pile_declines(pile_cnt)) return;
+    __shared__ uint32_t s[PILE_SW][TK_ROWS];               // word-major: thread t's row is s[.][t] (conflict-free without padding)
+    __shared__ uint32_t stk[2 * (NR_STACK + 1)][TK_ROWS];
+    __shared__ uint16_t rbuf[PR_RCAP + 1][TK_ROWS];
+    __shared__ uint32_t sOff[PR_SEGS + 1];                 // piles of the block's segments before segment g
+    const int t = (int) threadIdx.x;
+    const uint32_t seg0 = blockIdx.x * PR_SEGS;
+    if (t < 64) {                                          // one wave: the counts and their prefix
+        const uint32_t g = seg0 + (uint32_t) t;
+        uint32_t c = (t < PR_SEGS && g < n_segs) ? min(pcount[g], (uint32_t) PB_THREADS) : 0u;
 #pragma unroll
-            for (int k = 0; k <= PILE_SW; k++) y1[k] = ((k + 1 <= PILE_SW ? S[k + 1] : 0u) & m1) | (S[k] & ~m1);
+        for (int d = 1; d < PR_SEGS; d <<= 1) { const uint32_t o = __shfl_up(c, d); if (t >= d) c += o; }
+        if (t < PR_SEGS) sOff[t + 1] = c;
+        if (t == 0) sOff[0] = 0u;
+    }
+    __syncthreads();
+    const int np = (int) sOff[PR_SEGS];
+    for (int c0 = 0; c0 < np; c0 += TK_ROWS) {             // uniform
+        const int i = c0 + t;
+        const bool in = i < np;
+        int g = 0;                                         // the segment that holds pile i: the last g with sOff[g] <= i
 #pragma unroll
-            for (int k = 0; k <= PILE_SW; k++) y2[k] = ((k + 2 <= PILE_SW ? y1[k + 2] : 0u) & m2) | (y1[k] & ~m2);
-#pragma unroll
-            for (int k = 0; k <= PILE_SW; k++) y[k] = ((k + 4 <= PILE_SW ? y2[k + 4] : 0u) & m4) | (y2[k] & ~m4);
-#pragma unroll
-            for (int k = 0; k < PR_TKW; k++) s[t][k] = k < PILE_SW ? funnel(y[k], y[k + 1], sh) : 0u;
-        }
-        // (each thread reads the row it wrote: no barrier)
-        int nr = 0;
-        bool uncovered = false, stack_ovf = false;
-        uint32_t cur0 = 0u;
-        node_runs_core<true, PR_RCAP>(s[t], nwin, act, cc, stk, rbuf, t, nr, uncovered, stack_ovf, cur0, step);
-        bool ok = act && nr >= 1 && nr <= PR_RCAP && !uncovered && !stack_ovf;
-        // runs as they were found: the last windows first, q | p0 << 8 in the extent's own coordinates, p1 = p0 of the run before.  The record
-        // wants them ascending on the pile's axis (coordinate + 64 in a byte); the two halves of the window range meet at window 64: a minimizer
-        // on both sides of that seam is ONE run (k_pile_probe takes "the same minimizer twice" for a tandem repeat)
-        uint32_t key_[PILE_RUNS], kc_[PILE_RUNS];
-#pragma unroll
-        for (int k = 0; k < PILE_RUNS; k++) { key_[k] = 0u; kc_[k] = 0u; }
-        int n = 0;
-        uint32_t last_q = 0xFFFFFFFFu;
-        const int nrs = nr < PR_RCAP ? nr : PR_RCAP;
-        for (int r = PR_RCAP - 1; r >= 0; r--) {
-            if (ok && r < nrs) {
-                const uint32_t d = rbuf[r][t];
-                const int q = (int) (d & 255u), p0 = (int) (d >> 8);
-                if ((uint32_t) q != last_q) {              // (the same k-mer as the run before: the seam of two pieces -- one run)
-                    uint32_t h, pk;
-                    kmer_key(s[t], q < 192 ? q : 0, true, cc, h, pk);
-                    const uint32_t kv = cluster_key(h, fs), cv = (uint32_t) (q - m_max + 64) | ((uint32_t) (p0 - m_max + 64) << 8);
-#pragma unroll
-                    for (int k = 0; k < PILE_RUNS; k++) if (k == n) { key_[k] = kv; kc_[k] = cv; }
-                    n++;
-                    last_q = (uint32_t) q;
-                }
-            }
-        }
-        ok = ok && n >= 1 && n <= PILE_RUNS;
-        if (in && further) {
-            // a further group: its list in rec2 at the group's slot, laid out like the second half of a bucket's line (word 0 = runs << 8 | end << 16)
-            uint4 *l2 = rec2 + (size_t) slot * 4 - 4;      // (pile_list_store writes line[4 .. 7])
-            pile_list_store(l2, 0u, ok, n, key_, kc_, (uint32_t) (nwin - m_max + 64));
-            if (!ok) {
-                // its members probe with their own lists: the entries of the bucket (it starts k slots back) that carry this group's slot
-                // (the bucket begins k <= 3 slots before the group's slot)
-                const uint64_t jb = slot >= 3u ? (uint64_t) slot - 3u : 0ull;
-                for (uint64_t j2 = jb; j2 < jb + 64u + 3u && j2 < n_entries; j2++) {
-                    const uint4 s2 = side[j2];
-                    if ((s2.z >> 31) && ((s2.z >> 16) & 3u) != 0u && s2.w == slot) atomicOr(&own_mask[j2 >> 5], 1u << (j2 & 31u));
-                }
-            }
-        } else if (in) {
-            uint32_t *lw = reinterpret_cast<uint32_t *>(line);
-            pile_list_store(line, lw[16], ok, n, key_, kc_, (uint32_t) (nwin - m_max + 64));
-            if (!ok) {
-                // no list (3 piles in 1000: a window without a class-0 k-mer somewhere on the extent, mostly): the members probe with their OWN
-                // lists, as the entries outside a first group do -- noted in own_mask for the list-driven key pass that follows.  (Marking the
-                // bucket irregular instead sent every source with a run in it to the general kernel: 1.7 M more sources at the north-star size.)
-                lw[16] = lw[16] & 255u;
-                const uint32_t cntb = min(lw[16] & 255u, 64u), e0b = lw[17];
-                for (uint32_t i2 = 0; i2 < cntb; i2++) {
-                    const uint64_t j2 = (uint64_t) e0b + i2;
-                    if (j2 < n_entries) { const uint4 s2 = side[j2]; if ((s2.z >> 31) && ((s2.z >> 16) & 3u) == 0u) atomicOr(&own_mask[j2 >> 5], 1u << (j2 & 31u)); }
-                }
-            }
-        }
+        for (int b = PR_SEGS / 2; b >= 1; b >>= 1) g += (g + b <= PR_SEGS - 1 && (int) sOff[g + b] <= i) ? b : 0;
+        const uint32_t who = in ? plist[(size_t) (seg0 + (uint32_t) g) * PB_THREADS + (uint32_t) (i - (int) sOff[g])] : 0u;
+        pile_consensus_one<TK_ROWS, PILE_SW>(who, in, &s[0][t], stk, rbuf, t, side, n_entries, tab, rec, rec2, cc, U, Lmin, own_mask);
     }
 }
 
@@ -1044,22 +1103,28 @@ void launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int uniform_le
     const uint64_t tiles = (n_entries + PB_TILE - 1) / PB_TILE;
     const dim3 sample((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::max<uint64_t>(64, tiles / 32)))), block(PB_THREADS);
     hipLaunchKernelGGL((k_pile_build<true>), sample, block, 0, s, nd, skeys, sids, n_entries, (const uint4 *) dir, cc, uniform_len, (uint4 *) nullptr, (uint4 *) nullptr, 0u, (uint4 *) nullptr, pile_cnt,
-                       (uint32_t *) nullptr);
+                       (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
     hipLaunchKernelGGL(k_pile_sample_close, dim3(1), dim3(1), 0, s, pile_cnt);
 }
 
 // own_mask != null: the run lists come from the consensus (k_pile_runs_consensus) and the entries that read a list of their own are noted
 // in own_mask (zeroed here); null: round 4's form -- the pile's list joined from the own lists of its two outer members (k_pile_runs: every node
 // must have its run list then)
+// plist != null (with own_mask): k_pile_build lists its piles per workgroup and k_pile_runs_consensus_list takes them from there (pile_list_bytes)
 void launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys, const uint32_t *sids, const void *dir, void *rec, void *rec2,
-                       void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt, uint32_t *own_mask, hipStream_t s) {
+                       void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt, uint32_t *own_mask, void *plist, hipStream_t s) {
     const uint64_t n_entries = nd.n > 0 ? (uint64_t) nd.n : 0;
     if (n_entries == 0) return;
     const uint64_t tiles = (n_entries + PB_TILE - 1) / PB_TILE;
+    if (!own_mask) plist = nullptr;
+    uint32_t *pl = (uint32_t *) plist, *pc = pl ? pl + tiles * PB_THREADS : nullptr;
     if (own_mask) (void) hipMemsetAsync(own_mask, 0, pile_own_mask_bytes(n_entries), s);
     hipLaunchKernelGGL((k_pile_build<false>), dim3((unsigned) tiles), dim3(PB_THREADS), 0, s, nd, skeys, sids, n_entries, (const uint4 *) dir, cc, uniform_len, (uint4 *) rec, (uint4 *) tab, epoch,
-                       (uint4 *) side, const_cast<unsigned long long *>(pile_cnt), own_mask);
-    if (own_mask)
+                       (uint4 *) side, const_cast<unsigned long long *>(pile_cnt), own_mask, pl, pc);
+    if (pl)
+        hipLaunchKernelGGL(k_pile_runs_consensus_list, dim3((unsigned) ((tiles + PR_SEGS - 1) / PR_SEGS)), dim3(TK_ROWS), 0, s, (const uint32_t *) pl, (const uint32_t *) pc, (uint32_t) tiles,
+                           (const uint4 *) side, n_entries, (uint4 *) tab, (const uint4 *) rec, (uint4 *) rec2, cc, uniform_len, cfg.Lmin, pile_cnt, own_mask);
+    else if (own_mask)
         hipLaunchKernelGGL(k_pile_runs_consensus, dim3((unsigned) ((n_entries + PR_TILE - 1) / PR_TILE)), dim3(TK_ROWS), 0, s, (const uint4 *) side, n_entries, cc.n_buckets, (uint4 *) tab,
                            (const uint4 *) rec, (uint4 *) rec2, cc, uniform_len, cfg.Lmin, pile_cnt, own_mask);
     else
@@ -1067,6 +1132,9 @@ void launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterC
 }
 
 size_t pile_own_mask_bytes(uint64_t n) { return (size_t) ((n + 31) / 32 + 1024) * 4; }
+
+// the piles' lists of k_pile_build's workgroups: PB_THREADS slots per workgroup, then a count per workgroup
+size_t pile_list_bytes(uint64_t n) { const uint64_t tiles = (n + PB_TILE - 1) / PB_TILE; return (size_t) (tiles * (PB_THREADS + 1) + 64) * 4; }
 
 // the ids of the entries own_mask names -> list (dense; *count = how many: pile_cnt + 3, zeroed by launch_pile_sample)
 void launch_pile_own_ids(const uint32_t *own_mask, const uint32_t *sids, uint64_t n_entries, int32_t *list, uint32_t cap, unsigned long long *pile_cnt, hipStream_t s) {
