@@ -351,7 +351,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                     launch_pile_probe(nd, cfg, cc, pp.uniform_len, e->cl_pile_tab.p, e->pile_epoch, e->cl_pile_rec.p, e->cl_pile_rec2.p, e->cl_pile_succ.p,
                                       e->cl_runs.p, cnt, (uint32_t *) e->outdeg.p, (unsigned long long *) e->loc_first.p, (unsigned long long *) e->loc_second.p,
                                       (int32_t *) e->cl_defer.p, (uint32_t) n_src, (const unsigned long long *) e->cl_pile_cnt.p, e->n_cu, s, src_begin, src_end,
-                                      e->cl_pile_side_r.p, (unsigned long long *) e->cl_pile_cursor.p);
+                                      e->cl_pile_side_r.p, (unsigned long long *) e->cl_pile_cursor.p, e->opt_pile_probe_lean != 0);
                     if ((rc = alga_check_launch(e, "k_pile_probe"))) return rc;
                     // the sources it handed on have no run list of their own yet (the general kernel reads it): a list-driven key pass over the
                     // defer list, whose length the device knows
@@ -716,6 +716,8 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_pile_runs_list = value != 0;
     } else if (!strcmp(name, "pile_deg_fold")) {
         e->opt_pile_deg_fold = value != 0;
+    } else if (!strcmp(name, "pile_probe_lean")) {
+        e->opt_pile_probe_lean = value != 0;
     } else if (!strcmp(name, "pile_check")) {
         e->opt_pile_check = value != 0;
     } else if (!strcmp(name, "pile_skip_gather")) {

@@ -95,7 +95,8 @@ void       launch_probe_stream_list(const NodesDev &nd, const PrefSufCfg &cfg, c
 void       launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const void *tab, uint32_t epoch, const void *rec, const void *rec2, const void *side,
                              const void *runs, unsigned long long *counters, uint32_t *deg, unsigned long long *first, unsigned long long *second, int32_t *defer_list,
                              uint32_t defer_cap, const unsigned long long *pile_cnt, int n_cu, hipStream_t s, int32_t src_begin, int32_t src_end,
-                             void *side_range /* a range that is not all nodes: (src_end - src_begin + 64) * 16 B of scratch */, unsigned long long *cursor /* ... and a word */);
+                             void *side_range /* a range that is not all nodes: (src_end - src_begin + 64) * 16 B of scratch */, unsigned long long *cursor /* ... and a word */,
+                             bool lean = true /* option pile_probe_lean */);
 
 // radix_sort.hip: the engine's own stable LSD radix sort of (u32 key, u32 value) pairs on the key bits [begin_bit, 32)
 size_t     rsort_u32_pairs_temp_bytes(uint64_t n);

@@ -650,6 +650,19 @@ constexpr int PP_LSTRIDE = 20;
 // the waves' waiting for memory -- the chain side record -> run list -> bucket records -> the targets that stand -- at four waves per SIMD
 // (five spill: 9.9 against 7.9 ms): side record and run list are read a tile ahead, the records of the next run are on their way while
 // the current one is compared (of the next two: no faster), the run loop is unrolled over the eight slots (static registers; a wave skips the slots none of its lanes uses).
+// LEAN (engine option "pile_probe_lean", default 1) trims the compare of a record against the source (take_record) and changes nothing it
+// decides; LEAN = false is the round-5 kernel.  Two kinds of vector work were spent on every slot of every wave:
+//   * the source's row taken from the home run: nine funnel shifts, masks and selects into B per slot, although the home run is slot 0
+//     (the slots are shifted down to the source's first run, and only the run that holds window 0 -- the first -- has p0 == 0);
+//   * the place of the last mismatch tracked over all nine words (a compare and two selects per word), although a mismatch at or past
+//     position 63 clears every offset of the set anyway: the five words from position 64 on are only OR-ed together;
+// and the run's windows, offset 0 and the last mismatch are applied to the offset set as one range [lo, hi) instead of three 64-bit masks.
+#ifdef PP_NO_COMPACT
+constexpr bool PP_HOME_ANY_SLOT = true;                    // (slots not shifted: the home run may sit in any slot)
+#else
+constexpr bool PP_HOME_ANY_SLOT = false;
+#endif
+template <bool LEAN>
 __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg cfg, ClusterCfg cc, int U, NodesDev nd, uint64_t n_entries, uint64_t n_mine, int n_nodes,
                                                                  const uint4 *__restrict__ tab, uint32_t epoch, const uint4 *__restrict__ rec, const uint4 *__restrict__ rec2,
                                                                  const uint4 *__restrict__ side, const uint4 *__restrict__ side_src, const uint2 *__restrict__ runs, ProbeOut o,
@@ -815,18 +828,28 @@ __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg
         for (int k = 0; k < 10; k++) x[k] = ss[w0 + k];
         uint32_t dv = 0u;                                  // last word in which the source differs from the consensus, and which
         int dk = 0;
+        uint32_t dhi = 0u;                                 // (LEAN) any difference in words 4 .. 8: positions 64 on
 #pragma unroll
         for (int k = 0; k < 9; k++) {
             const uint32_t sw = funnel(x[k], x[k + 1], sh) & low_bits32(2 * U - 32 * k);
             B[k] = home ? sw : B[k];                       // the home run of a first-group member: this IS the source's row (and the first record a lane sees)
             const uint32_t dd = (sw ^ B[k]) & low_bits32(2 * U - 32 * k);
-            dk = dd ? k : dk;
-            dv = dd ? dd : dv;
+            if (!LEAN || k < 4) {
+                dk = dd ? k : dk;
+                dv = dd ? dd : dv;
+            } else {
+                dhi |= dd;
+            }
         }
         const int mism = dv ? 16 * dk + ((31 - __clz((int) dv)) >> 1) : -1;
         unsigned long long oc = q <= 63 ? (rm >> (63 - q)) : (q - 63 >= 64 ? 0ull : (rm << (q - 63)));            // offset d = q - m
-        oc &= (p1 >= 64 ? ~0ull : ((1ull << p1) - 1ull)) & ~((1ull << (p0 & 63)) - 1ull) & ~1ull;                 // the run's windows; offset 0 is the source itself
-        if (mism >= 0) oc &= mism >= 63 ? 0ull : ~((2ull << mism) - 1ull);
+        if constexpr (LEAN) {                              // the same three masks as one range [lo, hi) of offsets
+            const int lo = dhi != 0u ? 64 : max(max(p0 & 63, 1), mism + 1), hi = min(p1, 64);  // (the last mismatch lies at 64 or later: none)
+            oc &= hi > lo ? (~0ull >> (64 - (hi - lo))) << lo : 0ull;
+        } else {
+            oc &= (p1 >= 64 ? ~0ull : ((1ull << p1) - 1ull)) & ~((1ull << (p0 & 63)) - 1ull) & ~1ull;             // the run's windows; offset 0 is the source itself
+            if (mism >= 0) oc &= mism >= 63 ? 0ull : ~((2ull << mism) - 1ull);
+        }
         oc = (on && !dfr) ? oc : 0ull;
         if (oc != 0ull) {
             uint32_t E[4];                                 // the consensus from the source's end on: 64 positions, defined up to the group's rightmost member
@@ -937,7 +960,7 @@ __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg
         more |= (mt & ~1u) << (4 * a);
         const bool on = (mt & 1u) != 0u;
         if (__ballot(on) == 0ull) continue;                // uniform
-        const bool home = on && row_from_pile && !got_row && ((ry[a] >> 8) & 255u) == 0u;      // the run of window 0
+        const bool home = (!LEAN || PP_HOME_ANY_SLOT || a == 0) && on && row_from_pile && !got_row && ((ry[a] >> 8) & 255u) == 0u;      // the run of window 0
         got_row = got_row || home;
         take_record(li * PP_LSTRIDE, ((unsigned long long) R3.z << 32) | R3.y, a, 0u, ry[a], on, home);
     }
@@ -1197,7 +1220,7 @@ __global__ void __launch_bounds__(256) k_pile_side_range(const uint4 *__restrict
 void launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const void *tab, uint32_t epoch, const void *rec, const void *rec2,
                        const void *side, const void *runs, unsigned long long *counters, uint32_t *deg, unsigned long long *first, unsigned long long *second,
                        int32_t *defer_list, uint32_t defer_cap, const unsigned long long *pile_cnt, int n_cu, hipStream_t s, int32_t src_begin, int32_t src_end,
-                       void *side_range, unsigned long long *cursor) {
+                       void *side_range, unsigned long long *cursor, bool lean) {
     const uint64_t n_entries = nd.n > 0 ? (uint64_t) nd.n : 0;
     if (n_entries == 0 || src_end <= src_begin) return;
     ProbeOut o{};
@@ -1213,7 +1236,7 @@ void launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterC
     }
     const uint64_t tiles = (n_mine + PP_WAVES * 64 - 1) / (PP_WAVES * 64);
     const dim3 grid((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t) std::max(1, n_cu) * (PP_OCC * 4 / PP_WAVES)))), block(PP_WAVES * 64);      // PP_OCC waves per SIMD, four SIMDs per CU
-    hipLaunchKernelGGL(k_pile_probe, grid, block, 0, s, cfg, cc, uniform_len, nd, n_entries, n_mine, nd.n, (const uint4 *) tab, epoch, (const uint4 *) rec, (const uint4 *) rec2,
+    hipLaunchKernelGGL(lean ? k_pile_probe<true> : k_pile_probe<false>, grid, block, 0, s, cfg, cc, uniform_len, nd, n_entries, n_mine, nd.n, (const uint4 *) tab, epoch, (const uint4 *) rec, (const uint4 *) rec2,
                        (const uint4 *) side, (const uint4 *) side_src, (const uint2 *) runs, o, defer_list, defer_cap, pile_cnt);
 }
 

@@ -179,6 +179,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                those lists (four waves per SIMD); 0: k_pile_runs_consensus sweeps the side records for them (round 5; A/B and tests)
  *   "pile_deg_fold"              default 1: the first pass of the out-degree scan moves the out-degrees k_pile_probe left in the sources' slots; 0: a
  *                                pass of its own (k_pile_deg) right behind the probe (A/B and tests)
+ *   "pile_probe_lean"            default 1: k_pile_probe takes a source's row from its home run in slot 0 only and looks for the last mismatch
+ *                                below position 64 only (a mismatch from 64 on clears the whole offset set); 0: the round-5 kernel (A/B and tests)
  *   "pile_check"                 tests only.  != 0: every node gets its own run list as well and every first-group member's is compared with its pile's list
  *                                clipped to the member's windows (alga_prefsuf_stats.pile_list_checked / pile_list_mismatch)
  *   "pile_skip_gather"           default 1: a build the pile path keeps has no entry array (the rows in key order, 48 bytes per node: its kernels
