@@ -37,12 +37,9 @@ struct GfaEvents {
     ~GfaEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
 };
 
-int gfa_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t m, const char *path, int32_t flags, alga_gfa_info *info,
-             int &fd) {
+int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, int &fd) {
     hipStream_t s = e->own_stream;
-    const bool twins = flags & ALGA_GFA_TWINS;
-    GfaCfg c{nodes->words, nodes->stride_words, nodes->len, nodes->n, (const alga_edge_dev *) d_edges, m, twins ? (uint64_t) nodes->n / 2 : (uint64_t) nodes->n,
-             twins ? 1 : 0, (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
+    const uint64_t m = c.m;
     const uint64_t N = c.n_seg + m;                                 // items: segment lines, then link lines
     int rc;
     GfaEvents evs;
@@ -51,7 +48,7 @@ int gfa_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, 
     evs.ev.assign(12, nullptr);
     for (int k = 0; k < 12; k++) HIP_TRY(e, hipEventCreate(&evs.ev[(size_t) k]));
     if ((rc = alga_ensure(e, e->counters, GFA_COUNTERS * sizeof(unsigned long long)))) return rc;
-    if ((rc = alga_ensure(e, e->gfa_rowptr, ((size_t) nodes->n + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->gfa_rowptr, ((size_t) c.n + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_sizes, (size_t) (N + 1) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_off, (size_t) (N + 1) * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_tiles, (gfa_scan_tiles(N) + 1) * sizeof(unsigned long long)))) return rc;
@@ -159,6 +156,18 @@ int gfa_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, 
     return ALGA_OK;
 }
 
+int gfa_run(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, std::chrono::steady_clock::time_point t0) {
+    int fd = -1;
+    const int rc = gfa_impl(e, c, path, info, fd);
+    if (rc != ALGA_OK) {
+        (void) hipStreamSynchronize(e->own_stream);                 // nothing may still copy into the pinned buffers
+        if (fd >= 0) { close(fd); unlink(path); }                  // no partial file is left behind
+        return rc;
+    }
+    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ALGA_OK;
+}
+
 }  // namespace
 
 extern "C" int alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, const char *path, int32_t flags,
@@ -175,13 +184,27 @@ extern "C" int alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, co
     if ((flags & ALGA_GFA_TWINS) && (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "ALGA_GFA_TWINS: the node count must be even");
     if (n_edges >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 edges");
     HIP_TRY(e, hipSetDevice(e->device));
-    int fd = -1;
-    const int rc = gfa_impl(e, nodes, d_edges, n_edges, path, flags, info, fd);
-    if (rc != ALGA_OK) {
-        (void) hipStreamSynchronize(e->own_stream);                 // nothing may still copy into the pinned buffers
-        if (fd >= 0) { close(fd); unlink(path); }                  // no partial file is left behind
-        return rc;
-    }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ALGA_OK;
+    const bool twins = flags & ALGA_GFA_TWINS;
+    GfaCfg c{nodes->words, nodes->stride_words, nodes->len, nodes->n, (const alga_edge_dev *) d_edges, n_edges, twins ? (uint64_t) nodes->n / 2 : (uint64_t) nodes->n,
+             twins ? 1 : 0, (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
+    return gfa_run(e, c, path, info, t0);
+}
+
+// The unitig graph as GFA: the same kernels over the ragged rows (GfaCfg::row_off); pair k is segment k, oriented unitig 2k+1 is `+`.
+extern "C" int alga_write_unitig_gfa_device(alga_engine *e, const alga_unitigs *u, const char *path, int32_t flags, alga_gfa_info *info) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    const auto t0 = std::chrono::steady_clock::now();
+    if (info) *info = alga_gfa_info{};
+    if (!u || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs and path must not be NULL");
+    if (flags & ~ALGA_GFA_SEQUENCES) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown GFA flag (unitigs are always written as twin pairs)");
+    if (!e->ut_valid || u->d_len != (const int32_t *) e->ut_ulen.p || (uint64_t) u->n_pairs != e->ut_n_pairs || u->n_edges != e->ut_n_edges ||
+        u->d_words != (const uint32_t *) e->ut_words.p || u->d_edges != (const alga_edge *) e->ut_edges.p)
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_unitigs_device call on this engine");
+    if (u->n_edges >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 edges");
+    HIP_TRY(e, hipSetDevice(e->device));
+    GfaCfg c{u->d_words, 0, (const int32_t *) e->ut_ulen2.p, 2 * u->n_pairs, (const alga_edge_dev *) u->d_edges, u->n_edges, (uint64_t) u->n_pairs, 1,
+             (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
+    c.row_off = (const unsigned long long *) u->d_word_off;
+    return gfa_run(e, c, path, info, t0);
 }

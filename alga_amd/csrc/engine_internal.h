@@ -121,6 +121,14 @@ struct alga_engine {
     void       *gfa_pin[2] = {nullptr, nullptr};   // pinned host chunks (hipHostMalloc), gfa_pin_cap bytes each
     size_t      gfa_pin_cap = 0;
     int         opt_gfa_chunk_mb = 256;            // option "gfa_chunk_mb": size of a formatted chunk of the GFA text
+    // unitig graph (engine_unitig.hip): sort buffers of the 2 m twin records / the unitig edges, group flags and their scan, E*, its row pointers,
+    // next / offset / prev per node, the two rank and min arrays, tails, winners, pair numbers, per-pair sizes, the result arrays
+    DevBuf      ut_cnt, ut_keys[2], ut_vals[2], ut_flag, ut_pos, ut_best, ut_estar, ut_rowptr, ut_nxt, ut_noff, ut_prv, ut_rank[2], ut_min[2], ut_tail,
+                ut_win, ut_pair, ut_pcnt, ut_ulen, ut_ulen2, ut_uwords, ut_path_off, ut_word_off, ut_tiles, ut_path_node, ut_path_pos, ut_uid, ut_words,
+                ut_edges, ut_link, ut_rnode, ut_rrec[2];      // (ruling set: next / offset pairs, the rulers, their records)
+    int         opt_unitig_ruling = -1;            // option "unitig_ruling": the list ranking ranks a ruling set first (1), never (0), from 2^16 nodes on (-1)
+    uint64_t    ut_n_pairs = 0, ut_n_edges = 0;    // the result at hand (ut_valid: the buffers hold one)
+    bool        ut_valid = false;
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

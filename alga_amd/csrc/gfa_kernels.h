@@ -16,6 +16,12 @@ struct GfaCfg {
     uint64_t m;
     uint64_t n_seg;                 // twins: n / 2, else n
     int32_t twins, seqs;
+    // optional: ragged rows (the unitig graph).  Non-null: the row of node v starts at words + row_off[v >> 1] (one row per twin pair, read
+    // through its odd node; `stride` is not used); null: at words + v * stride
+    const unsigned long long *row_off = nullptr;
+    __host__ __device__ __forceinline__ const uint32_t *row(uint64_t node) const {
+        return row_off ? words + row_off[node >> 1] : words + node * (uint64_t) stride;
+    }
 };
 
 // counters[] (unsigned long long) the kernels fill

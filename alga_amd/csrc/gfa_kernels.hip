@@ -258,7 +258,7 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const uns
         SegLine s;
         s.name = j; s.L = c.len[node]; s.wn = dec_width(j); s.wl = dec_width((uint64_t) s.L);
         s.hp = 2 + s.wn + 1; s.sl = c.seqs ? (uint32_t) s.L : 1u;
-        s.row = c.words + node * (uint64_t) c.stride; s.seqs = c.seqs;
+        s.row = c.row(node); s.seqs = c.seqs;
         char *g0 = buf + (l0 - base), *g1 = buf + (l1 - base);
         char *a0 = (char *) (((uintptr_t) g0 + 15) & ~(uintptr_t) 15), *a1 = (char *) ((uintptr_t) g1 & ~(uintptr_t) 15);
         if (a0 >= a1) {                                               // no whole aligned block inside the line

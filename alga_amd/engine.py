@@ -158,7 +158,7 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_shard_index_device", "alga_shard_join_device", "alga_shard_small_keys_device", "alga_shard_resolve_device", "alga_shard_place_device",
            "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
-           "alga_write_gfa_device"]
+           "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 
@@ -170,6 +170,51 @@ class GfaInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+UNITIG_SKIP_ISOLATED = 1                                         # alga_unitigs_device flag
+
+
+class UnitigsC(C.Structure):
+    """alga_unitigs"""
+    _fields_ = [("n_pairs", C.c_int32), ("d_words", C.c_void_p), ("d_word_off", C.c_void_p), ("d_len", C.c_void_p), ("d_path_node", C.c_void_p),
+                ("d_path_pos", C.c_void_p), ("d_path_off", C.c_void_p), ("d_edges", C.c_void_p), ("n_edges", C.c_uint64)]
+
+
+class UnitigInfo(C.Structure):
+    """alga_unitig_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("edges_in", "edges_sym", "twins_added", "compactable", "cycles_cut", "isolated_skipped", "longest_nodes",
+                                          "longest_bases", "total_bases", "total_nodes")] + [("rank_rounds", C.c_int32)] + \
+               [(k, C.c_double) for k in ("ms_sym", "ms_rank", "ms_layout", "ms_seq", "ms_edges", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Unitigs:
+    """Result of Engine.unitigs: zero-copy torch views of the engine's device memory (valid until the next Engine.unitigs call on
+    that engine; clone what has to live longer) -- words int32 [total words], word_off / path_off int64 [n_pairs + 1], len int32
+    [n_pairs], path_node / path_pos int32 [total nodes], edges int32 [n_edges, 3] -- and .info (dict of alga_unitig_info)."""
+
+    def __init__(self, c, info, device):
+        self._c, self.info, self.n_pairs, self.n_edges = c, info, int(c.n_pairs), int(c.n_edges)
+        P = self.n_pairs
+        dev = "cuda:%d" % device
+        self.word_off = device_view(c.d_word_off, (P + 1,), dev, "<i8")
+        self.path_off = device_view(c.d_path_off, (P + 1,), dev, "<i8")
+        self.len = device_view(c.d_len, (P,), dev)
+        self.words = device_view(c.d_words, (int(self.word_off[-1]),), dev)
+        total_nodes = int(self.path_off[-1])
+        self.path_node = device_view(c.d_path_node, (total_nodes,), dev)
+        self.path_pos = device_view(c.d_path_pos, (total_nodes,), dev)
+        self.edges = device_view(c.d_edges, (self.n_edges, 3), dev)
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/unitig_checker.py"""
+        h = lambda t: t.cpu().numpy().copy()
+        return dict(n_pairs=self.n_pairs, words=h(self.words).view(np.uint32), word_off=h(self.word_off).view(np.uint64), len=h(self.len),
+                    path_node=h(self.path_node), path_pos=h(self.path_pos), path_off=h(self.path_off).view(np.uint64),
+                    edges=h(self.edges).reshape(-1, 3), info=dict(self.info))
 
 
 def library_path():
@@ -283,6 +328,9 @@ def load_library():
     lib.alga_cut_triangles_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.alga_cut_triangles_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.alga_unitigs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(UnitigsC),
+                                        C.POINTER(UnitigInfo)]
+    lib.alga_write_unitig_gfa_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -846,6 +894,46 @@ class Engine:
         self._check(self._lib.alga_write_gfa_device(self._h, C.byref(nd), C.c_void_p(ptr or None), C.c_uint64(m), os.fsencode(path), flags,
                                                     C.byref(info)))
         del keep
+        return info.as_dict()
+
+    def unitigs(self, words, lens, edges, n_edges=None, skip_isolated=False, stream=None):
+        """The unitig graph (alga_unitigs_device: the definition is in include/alga_amd.h) -> Unitigs.
+        words [n, stride] / lens [n]: the node set in the twin layout as torch device tensors (numpy arrays are uploaded first); edges: a
+        device pointer (with n_edges), an int32 device tensor [m, 3] or a numpy array [m, 3] (uploaded), in any order.
+        stream: the stream that produced the inputs, synchronised first (the call runs on the engine's own stream)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(words, np.ndarray):
+            words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(dev)
+        if isinstance(lens, np.ndarray):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+        keep = None
+        if isinstance(edges, np.ndarray):
+            e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)
+            keep = torch.from_numpy(e).to(dev)
+            ptr, m = _ptr(keep), len(e)
+        elif isinstance(edges, int):
+            ptr, m = edges, int(n_edges or 0)
+        else:
+            keep = edges
+            ptr, m = _ptr(edges), int(edges.shape[0]) if n_edges is None else int(n_edges)
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        n = int(lens.shape[0])
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 else 1, _ptr(lens), n, None, None)
+        out, info = UnitigsC(), UnitigInfo()
+        self._check(self._lib.alga_unitigs_device(self._h, C.byref(nd), C.c_void_p(ptr or None), C.c_uint64(m), UNITIG_SKIP_ISOLATED if skip_isolated else 0,
+                                                  None, C.byref(out), C.byref(info)))
+        del keep
+        return Unitigs(out, info.as_dict(), self.device)
+
+    def write_unitig_gfa(self, path, unitigs, sequences=True):
+        """The result of the LAST Engine.unitigs call as GFA 1.0 (alga_write_unitig_gfa_device) -> dict of alga_gfa_info: pair k is segment k,
+        a unitig edge and its twin are one link."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_unitig_gfa_device(self._h, C.byref(unitigs._c), os.fsencode(path), GFA_SEQUENCES if sequences else 0, C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

@@ -2,7 +2,7 @@
 //
 //   alga_hip --file1=reads.fasta [--file2=mates.fasta] --output=contigs.fasta [--threads=N] [--error_rate=R | --error-rate=R]
 //            [--serialize=1] [-l MINOVERLAP] [--rsoemo=N] [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1]
-//            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa]
+//            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -17,10 +17,14 @@
 // Both spellings of the error-rate option are accepted (the reference registers `error_rate` only, src/Params.cpp:226).
 // --gfa=PATH also writes that graph (after the supplement, rank 0's under --gpus) as GFA 1.0 with sequences, formatted on the GPU
 // (alga_write_gfa_device); it is not handed on to stock ALGA.
+// --unitigs=PATH: after the build (and the supplement), on the device: the first simplifier step (alga_cut_triangles_device with the reference's
+// max(250, int(1.75 * LEN))), then the unitig graph without isolated reads (alga_unitigs_device), written as GFA 1.0 with the spelled
+// sequences.  The graph handed on to stock ALGA and --gfa= are what they are without it; the option is not passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <thread>
 #include <cstdio>
@@ -40,7 +44,7 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 int main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    std::string file1, file2, output, alga_exe, gfa, v;
+    std::string file1, file2, output, alga_exe, gfa, unitigs, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
     int device = 0, serialize = 1, gpus = 1;
@@ -65,6 +69,7 @@ int main(int argc, char **argv) {
         else if (opt(a, "--gpu-list", v)) { gpu_list.clear(); for (size_t k = 0; k < v.size();) { gpu_list.push_back(atoi(v.c_str() + k)); size_t c = v.find(',', k); if (c == std::string::npos) break; k = c + 1; } }
         else if (opt(a, "--alga", v)) alga_exe = v;
         else if (opt(a, "--gfa", v)) gfa = v;
+        else if (opt(a, "--unitigs", v)) unitigs = v;
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
         else { fprintf(stderr, "alga_hip: unrecognized option '%s'\n", a); return 2; }
         // the hand-off to stock ALGA drops the error-rate option: the supplement it switches on (src/Params.cpp:357-359) has
@@ -72,7 +77,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -129,7 +134,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "device ingest: upload %.1f ms, lines + records %.1f ms, duplicate/prefix removal %.1f ms (wall)\n", info.ms_upload,
                 info.ms_parse - info.ms_upload, info.ms_preprocess);
         parsed.records = info.records; parsed.removed_n = info.removed_n; parsed.removed_str = info.removed_str;
-        parsed.min_overlap = info.min_overlap; parsed.rsoemo = info.rsoemo; parsed.li_kmer_length = info.li_kmer_length;
+        parsed.min_overlap = info.min_overlap; parsed.rsoemo = info.rsoemo; parsed.li_kmer_length = info.li_kmer_length; parsed.LEN = info.LEN;
         t1 = t_engine + std::chrono::duration_cast<clk::duration>(std::chrono::duration<double, std::milli>(info.ms_parse));
     } else {                                               // ALGA_ERR_UNSUPPORTED: the host parser, then the duplicate / prefix removal on every GPU
         std::string err = alga_host::parse(file1, file2, ip, parsed);
@@ -207,6 +212,29 @@ int main(int argc, char **argv) {
     std::vector<alga_edge> final_edges((size_t) n_final);
     if (n_final && alga_copy_to_host(engine, final_edges.data(), d_final, final_edges.size() * sizeof(alga_edge)) != ALGA_OK) { fprintf(stderr, "alga_amd: cannot read the edges back\n"); return 1; }
     fprintf(stderr, "Before first simplifier graph has %llu edges\n", (unsigned long long) n_final);
+    if (!unitigs.empty()) {                                                    // the edges are on the host already: nothing below touches what is handed on
+        alga_nodes nd{nodes.d_words, nodes.stride_words, nodes.d_len, nodes.n, nullptr, nullptr};
+        const int mopp = std::max(250, (int) (1.75 * parsed.LEN));            // Params::MAX_OFFSET_PARALLEL_PATHS, src/main.cpp:95
+        const alga_edge *d_cut = nullptr;
+        uint64_t n_cut = 0, n_removed = 0;
+        int rc = alga_cut_triangles_device(engine, nodes.n, d_final, n_final, mopp, nullptr, &d_cut, &n_cut, &n_removed);
+        alga_unitigs u;
+        alga_unitig_info ui;
+        alga_gfa_info gi;
+        if (rc == ALGA_OK) rc = alga_unitigs_device(engine, &nd, d_cut, n_cut, ALGA_UNITIG_SKIP_ISOLATED, nullptr, &u, &ui);
+        std::vector<int32_t> ul;
+        if (rc == ALGA_OK) { ul.resize((size_t) u.n_pairs); if (u.n_pairs) rc = alga_copy_to_host(engine, ul.data(), u.d_len, ul.size() * sizeof(int32_t)); }
+        if (rc == ALGA_OK) rc = alga_write_unitig_gfa_device(engine, &u, unitigs.c_str(), ALGA_GFA_SEQUENCES, &gi);
+        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", unitigs.c_str(), alga_last_error(engine), rc); return 1; }
+        std::sort(ul.begin(), ul.end(), [](int32_t a, int32_t b) { return a > b; });
+        long long n50 = 0; uint64_t acc = 0;
+        for (int32_t l : ul) { acc += (uint64_t) l; if (2 * acc >= ui.total_bases) { n50 = l; break; } }
+        fprintf(stderr, "Unitigs written -> %s: %d segments, %llu links, longest %llu nt (%llu reads), N50 %lld, %llu bases; %llu triangle edges cut, %llu isolated reads left out; "
+                "device ms: edges %.3f ranking %.3f (%d rounds) layout %.3f sequences %.3f unitig edges %.3f, call %.1f ms wall; GFA %llu bytes, device %.3f ms, wall %.1f ms\n",
+                unitigs.c_str(), u.n_pairs, (unsigned long long) gi.links, (unsigned long long) ui.longest_bases, (unsigned long long) ui.longest_nodes, n50,
+                (unsigned long long) ui.total_bases, (unsigned long long) n_removed, (unsigned long long) ui.isolated_skipped, ui.ms_sym, ui.ms_rank, ui.rank_rounds,
+                ui.ms_layout, ui.ms_seq, ui.ms_edges, ui.ms_total, (unsigned long long) gi.bytes, gi.ms_format, gi.ms_total);
+    }
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     fprintf(stderr, "HIP start-up %.1f ms, parse %.1f ms, duplicate/prefix removal %.1f ms wall (device %.3f ms), overlap graph %.1f ms wall (device %.3f ms: seed %.3f probe %.3f group %.3f reduce %.3f emit %.3f)\n",
             ms(t0, t_engine), ms(t_engine, t1), ms(t1, t1b), nodes.ms_device, ms(t1b, t2), st.ms_total, st.ms_seed, st.ms_probe, st.ms_group, st.ms_reduce, st.ms_emit);

@@ -192,6 +192,10 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *   "auto_reduction_per_target"  != 0: alga_prefsuf_params.reduction == AUTO resolves to PER_TARGET
  *   "gfa_chunk_mb"               1..4096 (default 256): alga_write_gfa_device formats the text in chunks of at most this many MB (one device buffer,
  *                                two pinned host buffers of that size; a chunk is never smaller than twice the longest line)
+ *   "unitig_ruling"              default -1: the list ranking of alga_unitigs_device ranks a RULING SET first -- the heads and one node in 64 walk to the
+ *                                next ruler, the rulers alone are ranked by pointer jumping, a second walk fills in the nodes between them: ~3 gathers
+ *                                per node instead of one per node and round (5.5 x faster at 1.7 M nodes) -- from 2^16 nodes on (below, a handful of rounds
+ *                                over a cache-resident array costs less than the extra launches); 1: always, 0: never (A/B and tests)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
@@ -680,6 +684,56 @@ typedef struct {
 } alga_gfa_info;
 int  alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, const char *path, int32_t flags,
                            alga_gfa_info *info /* may be NULL */);
+
+/* ---- unitig graph: the maximal non-branching paths of the overlap graph, merged (alga_amd/csrc/unitig_kernels.hip, engine_unitig.hip) ----------
+ * The first half of what the reference does behind the graph (GraphSimplifier::contractPathNodes, Graph::contractPath,
+ * ContigCreatorSinglePath::addContractedPathToString), in its order-free core.  `nodes` is a node set in ALGA's twin layout (node 2k+1 = read k,
+ * 2k = its reverse complement, v^1 = the twin of v) and `d_edges` an edge list IN ANY ORDER, both device memory (a build's result, the supplement's,
+ * alga_cut_triangles_device's).  The definition (tests/unitig_checker.py states it in Python; the device result equals it byte for byte):
+ *   1. checks, on the device, nothing written on refusal (ALGA_ERR_INVALID_ARGUMENT): n even, len[2k] == len[2k+1], ids in range, both ends live
+ *      (len > 0), every edge (a -> b, o) a dovetail: 0 <= o < len[a] and o + len[b] >= len[a].  Offset 0 is accepted.
+ *   2. E*: every edge and its twin (b^1 -> a^1, len[b] - len[a] + o); per (src, dst) only the smallest offset; sorted by (src, dst).
+ *   3. u -> v of E* is COMPACTABLE when outdeg(u) == 1, indeg(v) == 1, v != u, v != u^1.
+ *   4. a cycle of compactable edges is cut: m = the smallest node id over the cycle and its twin cycle; in the cycle that holds m the edge
+ *      p -> m is not compactable, nor is its twin m^1 -> p^1.
+ *   5. oriented unitigs = the maximal paths of compactable edges (a live node with none: a unitig of one node); the twin of v0 .. vk is vk^1 .. v0^1.
+ *   6. of a unitig and its twin the one whose first node has the smaller id is orientation `+`; pairs are numbered in ascending order of that
+ *      id; oriented unitig 2k+1 = `+` of pair k, 2k = `-`.
+ *   7. layout of pair k (`+`): the nodes in path order with pos[v0] = 0, pos[v(i+1)] = pos[v(i)] + offset(v(i) -> v(i+1)); length
+ *      L = pos[vk] + len[vk]; L > 2^31 - 1: ALGA_ERR_CAPACITY.
+ *   8. sequence of pair k: base j is base j - pos[vi] of node vi for the LAST i with pos[vi] <= j; 2-bit packed like every row, ragged: pair k
+ *      occupies the words d_word_off[k] .. d_word_off[k+1], unused tail bits zero.
+ *   9. every edge of E* that is not compactable runs from the last node of a unitig to the first of one: (U(u) -> U(v), pos[u] + o) over
+ *      oriented unitig ids, sorted by (src, dst, offset); twin-symmetric by construction.
+ *  10. ALGA_UNITIG_SKIP_ISOLATED: pairs of one node without any edge in E* are left out before the numbering (Global::removeIsolatedReads).
+ * The result is engine-owned device memory, valid until the next alga_unitigs_device call on `e`; the input graph is not modified. */
+#define ALGA_UNITIG_SKIP_ISOLATED 1
+typedef struct {
+    int32_t         n_pairs;       /* oriented unitig ids: 0 .. 2 * n_pairs                                                          */
+    const uint32_t *d_words;       /* the packed sequences of the `+` orientations                                                   */
+    const uint64_t *d_word_off;    /* n_pairs + 1                                                                                    */
+    const int32_t  *d_len;         /* n_pairs: length in bases                                                                       */
+    const int32_t  *d_path_node;   /* the nodes of the `+` orientations in path order ...                                            */
+    const int32_t  *d_path_pos;    /* ... and the base position of each in its unitig                                                */
+    const uint64_t *d_path_off;    /* n_pairs + 1: pair k owns the entries d_path_off[k] .. d_path_off[k+1]                          */
+    const alga_edge *d_edges;      /* over oriented unitig ids, sorted by (src, dst, offset), twin-symmetric                         */
+    uint64_t        n_edges;
+} alga_unitigs;
+typedef struct {
+    uint64_t edges_in, edges_sym;  /* edges given / edges of E*                                                                      */
+    uint64_t twins_added;          /* (src, dst) pairs of E* that the input did not hold                                             */
+    uint64_t compactable;          /* edges of E* inside unitigs, after the cycle cuts (edges_sym - unitig edges)                    */
+    uint64_t cycles_cut;           /* cycles of compactable edges, a cycle and its twin cycle counted once                           */
+    uint64_t isolated_skipped;     /* pairs left out by ALGA_UNITIG_SKIP_ISOLATED                                                    */
+    uint64_t longest_nodes, longest_bases, total_bases, total_nodes;   /* over the pairs                                             */
+    int32_t  rank_rounds;          /* pointer-jumping rounds of the list ranking: over the ruling set, over the nodes, after cycle cuts */
+    double   ms_sym, ms_rank, ms_layout, ms_seq, ms_edges, ms_total;   /* device time per stage (HIP events) / wall time of the call */
+} alga_unitig_info;
+int  alga_unitigs_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t flags, void *hip_stream,
+                         alga_unitigs *out, alga_unitig_info *info /* may be NULL */);
+/* The unitig graph as GFA 1.0 through the kernels of alga_write_gfa_device: pair k is segment k with its spelled sequence (flags:
+ * ALGA_GFA_SEQUENCES or 0), a unitig edge and its twin are one link.  `u` must be the result of the last alga_unitigs_device call on `e`. */
+int  alga_write_unitig_gfa_device(alga_engine *e, const alga_unitigs *u, const char *path, int32_t flags, alga_gfa_info *info /* may be NULL */);
 
 #ifdef __cplusplus
 }
