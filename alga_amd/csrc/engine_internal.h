@@ -116,6 +116,10 @@ struct alga_engine {
     size_t      host_spare_cap = 0;
     DevBuf      in_bytes[2], in_nl[2], in_tiles, in_tile_off;   // device ingest: file bytes, line ends, newline counts per tile
     DevBuf      sp_rowptr, sp_sorted, sp_list, sp_cnt, sp_orow, sp_out, sp_in;   // first simplifier step (engine_simplify.hip)
+    // dangling-branch removal (engine_simplify.hip, tip_kernels.hip): counters, sort buffers, the unique sorted edges and their reverse, row pointers,
+    // alive / kill bytes, node records of both directions, branching and overflow lists, the overflow route's workspaces, the result
+    DevBuf      tp_cnt, tp_keys[2], tp_vals[2], tp_flag, tp_pos, tp_best, tp_est, tp_rev, tp_rfid, tp_rowptr[2], tp_alive, tp_kill, tp_rec[2], tp_branch,
+                tp_overflow, tp_ws, tp_out;
     // GFA export (engine_gfa.hip): line sizes, their 64-bit byte offsets, per-source row pointers, scan tile sums, chunk bounds, the device chunk
     DevBuf      gfa_sizes, gfa_off, gfa_rowptr, gfa_tiles, gfa_bounds, gfa_buf;
     void       *gfa_pin[2] = {nullptr, nullptr};   // pinned host chunks (hipHostMalloc), gfa_pin_cap bytes each

@@ -1,10 +1,14 @@
-// alga_amd/csrc/engine_simplify.hip -- C ABI of the first simplifier step (simplify_kernels.hip).
+// alga_amd/csrc/engine_simplify.hip -- C ABI of the simplifier steps: the triangle cut (simplify_kernels.hip), the dangling-branch removal
+// (tip_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 
 #include "engine_internal.h"
 #include "simplify_kernels.h"
+#include "tip_kernels.h"
+#include "unitig_kernels.h"
 
 using namespace alga;
 
@@ -41,9 +45,158 @@ int cut_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, i
     return ALGA_OK;
 }
 
+struct TipEvents {
+    hipEvent_t ev[3] = {};
+    ~TipEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
+};
+
+// Host side of the dangling-branch removal: the graph once, then per iteration a down and an up pass and ONE read-back (the two counts of
+// the iteration, which decide whether there is another one).
+int tips_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, int32_t max_offset, hipStream_t s, const alga_edge **d_out, uint64_t *m_out,
+              alga_tips_info *info) {
+    int rc;
+    TipEvents evs;
+    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    const size_t N = (size_t) n;
+    if ((rc = alga_ensure(e, e->tp_cnt, (TIP_COUNTERS + UT_COUNTERS) * sizeof(unsigned long long)))) return rc;
+    unsigned long long *cnt = (unsigned long long *) e->tp_cnt.p;
+    HIP_TRY(e, hipMemsetAsync(cnt, 0, (TIP_COUNTERS + UT_COUNTERS) * sizeof(unsigned long long), s));
+    HIP_TRY(e, hipEventRecord(evs.ev[0], s));
+    launch_tip_check(d_in, m, n, cnt, s);
+    if ((rc = alga_check_launch(e, "k_tip_check"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (const unsigned long long bad = e->h_counters[0])
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, (bad & TIP_BAD_ID) ? "edge endpoint outside [0, n)" : "negative edge offset");
+    // the input is valid: from here on the previous result's buffer is rewritten
+    for (int k = 0; k < 2; k++) {
+        if ((rc = alga_ensure(e, e->tp_keys[k], (size_t) (m + 1) * sizeof(unsigned long long)))) return rc;
+        if ((rc = alga_ensure(e, e->tp_vals[k], (size_t) (m + 1) * sizeof(uint32_t)))) return rc;
+        if ((rc = alga_ensure(e, e->tp_rowptr[k], (N + 2) * sizeof(uint32_t)))) return rc;
+        if ((rc = alga_ensure(e, e->tp_rec[k], (N + 1) * sizeof(TipRec)))) return rc;
+    }
+    if ((rc = alga_ensure(e, e->tp_flag, (size_t) (m + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_pos, (size_t) (m + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_best, (size_t) (m + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_est, (size_t) (m + 1) * sizeof(alga_edge_dev)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_rev, (size_t) (m + 1) * sizeof(alga_edge_dev)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_rfid, (size_t) (m + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_alive, (size_t) (m + 1)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_kill, (size_t) (m + 1)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_branch, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_overflow, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->tp_out, (size_t) (m + 1) * sizeof(alga_edge_dev)))) return rc;
+    if ((rc = alga_ensure(e, e->sort_temp, sort_edges_temp_bytes(m)))) return rc;
+    if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(m)))) return rc;
+    // the overflow route: 64 MB of workspaces of 5 words per node, at least one, at most 1024
+    const int32_t n_ws = (int32_t) std::min<size_t>(std::max<size_t>((64u << 20) / (20 * (N + 1)), 1), 1024);
+    if ((rc = alga_ensure(e, e->tp_ws, (size_t) n_ws * 5 * (N + 1) * sizeof(int32_t)))) return rc;
+    unsigned long long *keys0 = (unsigned long long *) e->tp_keys[0].p, *keys1 = (unsigned long long *) e->tp_keys[1].p;
+    uint32_t *vals0 = (uint32_t *) e->tp_vals[0].p, *vals1 = (uint32_t *) e->tp_vals[1].p;
+    uint32_t *flag = (uint32_t *) e->tp_flag.p, *pos = (uint32_t *) e->tp_pos.p;
+    alga_edge_dev *est = (alga_edge_dev *) e->tp_est.p, *rev = (alga_edge_dev *) e->tp_rev.p;
+    uint8_t *alive = (uint8_t *) e->tp_alive.p, *kill = (uint8_t *) e->tp_kill.p;
+
+    // ---- Graph::retainOnlySmallestOffset: the smallest offset per (src, dst), sorted; both CSR directions
+    int node_bits = 1;
+    while (node_bits < 31 && (1ll << node_bits) < (long long) n) node_bits++;
+    launch_tip_keys(d_in, m, keys0, vals0, s);
+    if ((rc = alga_check_launch(e, "k_tip_keys"))) return rc;
+    HIP_TRY(e, sort_edges(e->sort_temp.p, sort_edges_temp_bytes(m), keys0, keys1, vals0, vals1, m, node_bits, s));
+    launch_ut_group_heads(keys1, vals1, m, flag, (uint32_t *) e->tp_best.p, cnt + TIP_COUNTERS, s);
+    if ((rc = alga_check_launch(e, "k_ut_group_heads"))) return rc;
+    launch_exclusive_scan(flag, m, pos, (uint64_t *) e->scan_scratch.p, s);
+    if ((rc = alga_check_launch(e, "scan(group heads)"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, pos + m, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    const uint64_t ms = *(const uint32_t *) e->h_counters;
+    launch_ut_compact_edges(keys1, flag, pos, (const uint32_t *) e->tp_best.p, m, est, s);
+    if ((rc = alga_check_launch(e, "k_ut_compact_edges"))) return rc;
+    launch_edge_rowptr(est, ms, n, (uint32_t *) e->tp_rowptr[0].p, s);
+    launch_tip_rev_keys(est, ms, keys0, vals0, s);
+    if ((rc = alga_check_launch(e, "k_tip_rev_keys"))) return rc;
+    HIP_TRY(e, sort_edges(e->sort_temp.p, sort_edges_temp_bytes(m), keys0, keys1, vals0, vals1, ms, node_bits, s));
+    launch_tip_rev_edges(keys1, vals1, est, ms, rev, (uint32_t *) e->tp_rfid.p, s);
+    launch_edge_rowptr(rev, ms, n, (uint32_t *) e->tp_rowptr[1].p, s);
+    if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
+    HIP_TRY(e, hipMemsetAsync(alive, 1, (size_t) ms + 1, s));
+    HIP_TRY(e, hipMemsetAsync(kill, 0, (size_t) ms + 1, s));
+    HIP_TRY(e, hipMemsetAsync(e->tp_ws.p, 0xFF, (size_t) n_ws * 5 * (N + 1) * sizeof(int32_t), s));
+    HIP_TRY(e, hipEventRecord(evs.ev[1], s));
+
+    // ---- the loop of simplifyGraphOld
+    const TipDir dirs[2] = {{est, (const uint32_t *) e->tp_rowptr[0].p, nullptr}, {rev, (const uint32_t *) e->tp_rowptr[1].p, (const uint32_t *) e->tp_rfid.p}};
+    TipRec *rec[2] = {(TipRec *) e->tp_rec[0].p, (TipRec *) e->tp_rec[1].p};
+    uint64_t removed_total = 0;
+    int iterations = 0;
+    for (int i = 0;; i++) {
+        HIP_TRY(e, hipMemsetAsync(cnt + TIP_DOWN, 0, 2 * sizeof(unsigned long long), s));
+        for (int dir = 0; dir < 2 && n > 0 && ms > 0; dir++) {
+            HIP_TRY(e, hipMemsetAsync(cnt + TIP_N_BRANCH, 0, 2 * sizeof(unsigned long long), s));
+            launch_tip_degrees(dirs[0], dirs[1], alive, n, dir, rec[0], rec[1], (int32_t *) e->tp_branch.p, cnt, s);
+            if ((rc = alga_check_launch(e, "k_tip_degrees"))) return rc;
+            const TipGraph g{dirs[dir].E, dirs[dir].rowptr, dirs[dir].fid, alive, rec[dir], rec[dir ^ 1]};
+            launch_tip_find(g, (const int32_t *) e->tp_branch.p, n, max_offset, kill, (int32_t *) e->tp_overflow.p, cnt, s);
+            if ((rc = alga_check_launch(e, "k_tip_find"))) return rc;
+            launch_tip_find_overflow(g, (const int32_t *) e->tp_overflow.p, max_offset, kill, (int32_t *) e->tp_ws.p, n, n_ws, cnt, s);
+            if ((rc = alga_check_launch(e, "k_tip_find_overflow"))) return rc;
+            launch_tip_apply(alive, kill, ms, cnt + TIP_DOWN + dir, s);
+            if ((rc = alga_check_launch(e, "k_tip_apply"))) return rc;
+        }
+        HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt + TIP_DOWN, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));
+        const uint64_t down = e->h_counters[0], up = e->h_counters[1];
+        if (info) {
+            if (2 * i < ALGA_TIPS_MAX_PASSES) { info->removed[2 * i] = down; info->removed[2 * i + 1] = up; }
+        }
+        removed_total += down + up;
+        iterations = i + 1;
+        if (down + up == 0 || (i >= 15 && down + up <= 30)) break;      // src/GraphSimplifiers/GraphSimplifier.cpp:210-213
+    }
+    HIP_TRY(e, hipEventRecord(evs.ev[2], s));
+
+    // ---- the survivors, in (src, dst) order
+    launch_tip_flags(alive, ms, flag, s);
+    launch_exclusive_scan(flag, ms, pos, (uint64_t *) e->scan_scratch.p, s);
+    if ((rc = alga_check_launch(e, "scan(alive)"))) return rc;
+    launch_tip_emit(est, flag, pos, ms, (alga_edge_dev *) e->tp_out.p, s);
+    if ((rc = alga_check_launch(e, "k_tip_emit"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, TIP_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    *d_out = (const alga_edge *) e->tp_out.p;
+    *m_out = ms - removed_total;
+    if (info) {
+        info->edges_in = m; info->edges_unique = ms; info->edges_out = ms - removed_total; info->iterations = iterations; info->passes = 2 * iterations;
+        info->removed_total = removed_total; info->branching_nodes = e->h_counters[TIP_BRANCH_TOTAL]; info->overflow_nodes = e->h_counters[TIP_OVERFLOW_TOTAL];
+        float t = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); info->ms_prepare = t;
+        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); info->ms_passes = t;
+    }
+    return ALGA_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int alga_remove_dangling_branches_device(alga_engine *e, int32_t n_nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset, void *hip_stream,
+                                         const alga_edge **d_edges_out, uint64_t *n_edges_out, alga_tips_info *info) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    const auto t0 = std::chrono::steady_clock::now();
+    if (info) *info = alga_tips_info{};
+    if (!d_edges_out || !n_edges_out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "output pointers must not be NULL");
+    *d_edges_out = nullptr; *n_edges_out = 0;
+    if (n_nodes < 0 || (n_edges && !d_edges)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad graph");
+    if (n_edges && !n_nodes) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "edge endpoint outside [0, n)");
+    if (n_edges >= (1ull << 31) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^31 edges");
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
+    const int rc = tips_impl(e, n_nodes, (const alga_edge_dev *) d_edges, n_edges, max_offset, s, d_edges_out, n_edges_out, info);
+    if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); if (info) *info = alga_tips_info{}; return rc; }
+    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ALGA_OK;
+}
 
 int alga_cut_triangles_device(alga_engine *e, int32_t n_nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset_parallel_paths,
                               void *hip_stream, const alga_edge **d_edges_out, uint64_t *n_edges_out, uint64_t *n_removed) {

@@ -2,7 +2,7 @@
 //
 //   alga_hip --file1=reads.fasta [--file2=mates.fasta] --output=contigs.fasta [--threads=N] [--error_rate=R | --error-rate=R]
 //            [--serialize=1] [-l MINOVERLAP] [--rsoemo=N] [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1]
-//            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa]
+//            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -20,6 +20,11 @@
 // --unitigs=PATH: after the build (and the supplement), on the device: the first simplifier step (alga_cut_triangles_device with the reference's
 // max(250, int(1.75 * LEN))), then the unitig graph without isolated reads (alga_unitigs_device), written as GFA 1.0 with the spelled
 // sequences.  The graph handed on to stock ALGA and --gfa= are what they are without it; the option is not passed through.
+// --clip_tips=1 (default 0: every invocation without it behaves as before): with --unitigs=, the dangling branches go between the cut and the
+// unitigs (alga_remove_dangling_branches_device: GraphSimplifier::removeDanglingBranches / removeDanglingUpperBranches iterated as in
+// simplifyGraphOld), build -> supplement -> cut -> clip -> unitigs -> GFA.  The bound is the reference's,
+// int(max(250, int(1.75 * LEN)) * AVG_READ_LENGTH / 100.0f) with AVG_READ_LENGTH the integer mean length of the live reads
+// (Global::calculateAvgReadLength).  Without --unitigs= it does nothing; it is not passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -47,7 +52,7 @@ int main(int argc, char **argv) {
     std::string file1, file2, output, alga_exe, gfa, unitigs, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
-    int device = 0, serialize = 1, gpus = 1;
+    int device = 0, serialize = 1, gpus = 1, clip_tips = 0;
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -70,6 +75,7 @@ int main(int argc, char **argv) {
         else if (opt(a, "--alga", v)) alga_exe = v;
         else if (opt(a, "--gfa", v)) gfa = v;
         else if (opt(a, "--unitigs", v)) unitigs = v;
+        else if (opt(a, "--clip_tips", v)) clip_tips = atoi(v.c_str());
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
         else { fprintf(stderr, "alga_hip: unrecognized option '%s'\n", a); return 2; }
         // the hand-off to stock ALGA drops the error-rate option: the supplement it switches on (src/Params.cpp:357-359) has
@@ -77,7 +83,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -221,6 +227,30 @@ int main(int argc, char **argv) {
         alga_unitigs u;
         alga_unitig_info ui;
         alga_gfa_info gi;
+        if (rc == ALGA_OK && clip_tips) {
+            // Global::calculateAvgReadLength at src/GraphSimplifiers/GraphSimplifier.cpp:179: the mean (a double) over the reads alive after the cut,
+            // i.e. without those the cut graph has no edge at (Global::removeIsolatedReads, :117)
+            std::vector<int32_t> hl((size_t) nodes.n);
+            std::vector<alga_edge> hc((size_t) n_cut);
+            if (nodes.n) rc = alga_copy_to_host(engine, hl.data(), nodes.d_len, hl.size() * sizeof(int32_t));
+            if (rc == ALGA_OK && n_cut) rc = alga_copy_to_host(engine, hc.data(), d_cut, hc.size() * sizeof(alga_edge));
+            std::vector<char> has_edge((size_t) nodes.n, 0);
+            for (const alga_edge &x : hc) { has_edge[(size_t) x.src] = 1; has_edge[(size_t) x.dst] = 1; }
+            double sum = 0; long long cnt = 0;
+            for (size_t k = 0; k < hl.size(); k++) if (hl[k] > 0 && has_edge[k]) { sum += hl[k]; cnt++; }
+            const double avg = cnt ? sum / (double) cnt : 0.0;
+            const int bound = (int) (mopp * avg / (float) 100);                  // MAX_OFFSET_DANGLING_BRANCHES has MAX_OFFSET_PARALLEL_PATHS's value, src/main.cpp:95-96
+            alga_tips_info ti;
+            if (rc == ALGA_OK) rc = alga_remove_dangling_branches_device(engine, nodes.n, d_cut, n_cut, bound, nullptr, &d_cut, &n_cut, &ti);
+            if (rc == ALGA_OK) {
+                fprintf(stderr, "Tips clipped: bound %d (average live read length %.3f), %d iterations, %llu edges removed (", bound, avg, ti.iterations,
+                        (unsigned long long) ti.removed_total);
+                for (int k = 0; k < ti.passes && k < ALGA_TIPS_MAX_PASSES; k++) fprintf(stderr, "%s%llu", k ? " / " : "", (unsigned long long) ti.removed[k]);
+                fprintf(stderr, "), %llu edges left; %llu branching nodes walked, %llu by the overflow route; device ms: prepare %.3f passes %.3f, call %.1f ms wall\n",
+                        (unsigned long long) ti.edges_out, (unsigned long long) ti.branching_nodes, (unsigned long long) ti.overflow_nodes, ti.ms_prepare,
+                        ti.ms_passes, ti.ms_total);
+            }
+        }
         if (rc == ALGA_OK) rc = alga_unitigs_device(engine, &nd, d_cut, n_cut, ALGA_UNITIG_SKIP_ISOLATED, nullptr, &u, &ui);
         std::vector<int32_t> ul;
         if (rc == ALGA_OK) { ul.resize((size_t) u.n_pairs); if (u.n_pairs) rc = alga_copy_to_host(engine, ul.data(), u.d_len, ul.size() * sizeof(int32_t)); }

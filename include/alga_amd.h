@@ -643,6 +643,41 @@ int  alga_cut_triangles_device(alga_engine *e, int32_t n_nodes, const alga_edge 
 int  alga_cut_triangles_host(alga_engine *e, int32_t n_nodes, const alga_edge *edges, uint64_t n_edges, int32_t max_offset_parallel_paths,
                              alga_edge **edges_out, uint64_t *n_edges_out);     /* release with alga_free_edges() */
 
+/* ---- dangling-branch removal: tips are clipped before the unitigs (alga_amd/csrc/tip_kernels.hip, tip_walk.h, engine_simplify.hip) ----------
+ * GraphSimplifier::removeDanglingBranches / removeDanglingUpperBranches as simplifyGraphOld iterates them
+ * (src/GraphSimplifiers/GraphSimplifier.cpp:191-215, :577-820); tests/tips_checker.py restates it in Python and the device result equals that.
+ * A read with a sequencing error near an end has an in-edge and no out-edge (its twin the other way round): every such tip turns a
+ * non-branching path into a branch.  The pipeline on the device: build -> supplement -> cut -> CLIP -> unitigs -> GFA.
+ *   In: `d_edges` in any order, device memory.  Ids outside [0, n_nodes) or a negative offset: ALGA_ERR_INVALID_ARGUMENT, checked on the
+ *   device, nothing written.  First per (src, dst) the smallest offset is kept (Graph::retainOnlySmallestOffset, :191).
+ *   One pass on a graph H whose lists are in ascending neighbour order: for every node `beg` with >= 2 out-edges, for each out-edge (v, o) in
+ *   list order: par[v] = beg (an earlier par[v] is overwritten), v is marked, off = o; while v has exactly one out-edge (son, w): stop if son
+ *   is marked for this beg, else mark it, par[son] = v, off += w, v = son, and stop after the step if off > max_offset.  If v now has no
+ *   out-edge and off <= max_offset, (off, v) is an end.  If every out-edge of beg gave an end, the largest (off, v) is dropped.  From every
+ *   other end up par[] to beg each edge (par[x], x) is to go.  Every beg reads the same unmodified H; the union goes afterwards.
+ *   Iteration i = 0, 1, ...: a down pass on the graph, an up pass on its reverse; it goes on while an iteration removed something and
+ *   stops early when i >= 15 and it removed <= 30 edges (:210-213).
+ *   Out: the surviving edges sorted by (src, dst, offset), engine-owned device memory, valid until the next call of this function.
+ * `max_offset`: the reference passes int(MAX_OFFSET_DANGLING_BRANCHES * AVG_READ_LENGTH / 100.0f) with MAX_OFFSET_DANGLING_BRANCHES =
+ * max(250, int(1.75 * LEN)) and AVG_READ_LENGTH the integer mean length of the reads alive at that moment.
+ * NOT reproduced: the reference removes the found edges through WorkloadManager::parallelBlockExecution(0, size - 1, 3 * threads, ...),
+ * which leaves out the last element of its SHUFFLED removal list when (size - 1) % (3 * threads) == 0 and the only element when size == 1:
+ * one randomly chosen edge then survives the pass and can steer later ones.  This function removes every edge a pass finds.
+ * No host fallback: the walks run in k_tip_find (one thread per branching node, a short list in LDS), and the nodes whose list does not fit
+ * (rows of hundreds of edges, zero-offset chains through many joins) in k_tip_find_overflow with per-node arrays on the device. */
+#define ALGA_TIPS_MAX_PASSES 64
+typedef struct {
+    uint64_t edges_in, edges_unique, edges_out;  /* as given, one per (src, dst), surviving                                        */
+    int32_t  iterations, passes;                 /* passes = 2 * iterations: down, up, down, up, ...                               */
+    uint64_t removed[ALGA_TIPS_MAX_PASSES];      /* edges removed per pass (the first 64 passes; removed_total counts all)         */
+    uint64_t removed_total;
+    uint64_t branching_nodes, overflow_nodes;    /* summed over the passes: nodes walked from, those that took the overflow route   */
+    double   ms_prepare, ms_passes;              /* device time (HIP events): checks + sorts + both CSR directions; the loop        */
+    double   ms_total;                           /* wall time of the call                                                           */
+} alga_tips_info;
+int  alga_remove_dangling_branches_device(alga_engine *e, int32_t n_nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset,
+                                          void *hip_stream, const alga_edge **d_edges_out, uint64_t *n_edges_out, alga_tips_info *info /* may be NULL */);
+
 /* ---- contig trimming: the second use of the PrefSuf creator ---------------------------------------
  * src/main.cpp:633-725: the contigs and their reverse complements become the "reads" of one more GraphCreatorPrefSuf run with
  * MIN_OVERLAP_PREF_SUF = REMOVE_SMALL_OVERLAP_EDGES_MIN_OVERLAP = 25 (overlap lengths stop at 501 as always); the longest
