@@ -120,6 +120,13 @@ struct alga_engine {
     // alive / kill bytes, node records of both directions, branching and overflow lists, the overflow route's workspaces, the result
     DevBuf      tp_cnt, tp_keys[2], tp_vals[2], tp_flag, tp_pos, tp_best, tp_est, tp_rev, tp_rfid, tp_rowptr[2], tp_alive, tp_kill, tp_rec[2], tp_branch,
                 tp_overflow, tp_ws, tp_out;
+    // removal of short parallel paths (engine_simplify.hip, mst_kernels.hip): counters, the mutable rows (row pointers, entries, lengths), owner[],
+    // the two pending lists, winners, the overflow list, the overflow route's workspaces, the output row pointers, the result
+    DevBuf      mp_cnt, mp_rowptr, mp_rows, mp_len, mp_owner, mp_pend[2], mp_win, mp_overflow, mp_overflow2, mp_ws, mp_ws_big, mp_orow, mp_out;
+    // the overflow states whose maps are known to be empty (mst_clear leaves them so): buffer, size and geometry of the last 0xFF fill of each tier;
+    // p == nullptr: fill before use (never filled, reallocated, another geometry, or a call that did not reach its end)
+    struct MstFilled { const void *p = nullptr; size_t bytes = 0; uint32_t hbits = 0, cap_nodes = 0, cap_edges = 0; int32_t n_ws = 0; } mp_filled[2];
+    int         opt_mst_mid_nodes = 4096;          // option "mst_mid_nodes": nodes a state of the first overflow tier holds (and twice as many edges); tests lower it to reach the second tier
     // GFA export (engine_gfa.hip): line sizes, their 64-bit byte offsets, per-source row pointers, scan tile sums, chunk bounds, the device chunk
     DevBuf      gfa_sizes, gfa_off, gfa_rowptr, gfa_tiles, gfa_bounds, gfa_buf;
     void       *gfa_pin[2] = {nullptr, nullptr};   // pinned host chunks (hipHostMalloc), gfa_pin_cap bytes each

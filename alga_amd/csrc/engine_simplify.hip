@@ -1,11 +1,12 @@
-// alga_amd/csrc/engine_simplify.hip -- C ABI of the simplifier steps: the triangle cut (simplify_kernels.hip), the dangling-branch removal
-// (tip_kernels.hip).
+// alga_amd/csrc/engine_simplify.hip -- C ABI of the simplifier steps: the triangle cut (simplify_kernels.hip), the removal of short parallel
+// paths (mst_kernels.hip), the dangling-branch removal (tip_kernels.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 
 #include "engine_internal.h"
+#include "mst_kernels.h"
 #include "simplify_kernels.h"
 #include "tip_kernels.h"
 #include "unitig_kernels.h"
@@ -175,9 +176,151 @@ int tips_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, 
     return ALGA_OK;
 }
 
+// Host side of the removal of short parallel paths: the mutable rows once, then per round claim, select, ONE read-back (the winners and
+// the begs still pending, which decide whether there is a run and another round) and the run.
+int mst_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, int32_t max_offset, hipStream_t s, const alga_edge **d_out, uint64_t *m_out,
+             alga_mst_info *info) {
+    int rc;
+    TipEvents evs;
+    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    const size_t N = (size_t) n;
+    if ((rc = alga_ensure(e, e->mp_cnt, MST_COUNTERS * sizeof(unsigned long long)))) return rc;
+    unsigned long long *cnt = (unsigned long long *) e->mp_cnt.p;
+    HIP_TRY(e, hipMemsetAsync(cnt, 0, MST_COUNTERS * sizeof(unsigned long long), s));
+    HIP_TRY(e, hipEventRecord(evs.ev[0], s));
+    launch_mst_check(d_in, m, n, cnt, s);
+    if ((rc = alga_check_launch(e, "k_mst_check"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (const unsigned long long bad = e->h_counters[0])
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, (bad & MST_BAD_ID) ? "edge endpoint outside [0, n)" : (bad & MST_BAD_OFFSET) ? "negative edge offset"
+                                                                                                                                   : "edges must be grouped by src, in ascending order");
+    // the input is valid: from here on the previous result's buffer is rewritten
+    if ((rc = alga_ensure(e, e->mp_rowptr, (N + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_rows, (size_t) (m + 1) * sizeof(alga_edge_dev)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_len, (N + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_owner, (N + 1) * sizeof(unsigned long long)))) return rc;
+    for (int k = 0; k < 2; k++) if ((rc = alga_ensure(e, e->mp_pend[k], (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_win, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_overflow, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_orow, (N + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_out, (size_t) (m + 1) * sizeof(alga_edge_dev)))) return rc;
+    if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes((uint64_t) n)))) return rc;
+    if ((rc = alga_ensure(e, e->mp_overflow2, (N + 1) * sizeof(int32_t)))) return rc;
+    // the overflow route: 1024 states of opt_mst_mid_nodes nodes and twice as many edges (180 MB), or fewer and smaller ones if that already holds
+    // the whole graph; then, if it does not, states sized for the whole graph: 1 GB of them, at least one, at most 256.  They are allocated up
+    // front (the cost is stated in the header): whether a beg needs one is known only inside a round, and the host reads one block of counts per round
+    MstTiers tiers{};
+    tiers.mid.cap_nodes = (uint32_t) std::min<uint64_t>((uint64_t) e->opt_mst_mid_nodes, (uint64_t) N + 1);
+    tiers.mid.cap_edges = (uint32_t) std::min<uint64_t>(2 * (uint64_t) e->opt_mst_mid_nodes, m + 1);
+    tiers.mid.hbits = mst_hbits_for(tiers.mid.cap_nodes);
+    tiers.mid.n_ws = (int32_t) std::min<uint64_t>(1024, std::max<uint64_t>(N, 1));
+    const bool need_big = (uint64_t) N + 1 > tiers.mid.cap_nodes || m + 1 > tiers.mid.cap_edges;
+    if (need_big) {
+        tiers.big.cap_nodes = (uint32_t) N + 1; tiers.big.cap_edges = (uint32_t) m + 1; tiers.big.hbits = mst_hbits_for((uint64_t) N + 1);
+        tiers.big.n_ws = (int32_t) std::min<size_t>(std::max<size_t>(((size_t) 1 << 30) / (4 * mst_tier_words(tiers.big)), 1), 256);
+    }
+    const size_t mid_bytes = (size_t) tiers.mid.n_ws * mst_tier_words(tiers.mid) * sizeof(uint32_t);
+    const size_t big_bytes = need_big ? (size_t) tiers.big.n_ws * mst_tier_words(tiers.big) * sizeof(uint32_t) : 0;
+    if ((rc = alga_ensure(e, e->mp_ws, mid_bytes))) return rc;
+    if (need_big && (rc = alga_ensure(e, e->mp_ws_big, big_bytes))) return rc;
+    tiers.mid.ws = (uint32_t *) e->mp_ws.p;
+    tiers.big.ws = need_big ? (uint32_t *) e->mp_ws_big.p : nullptr;
+    alga_edge_dev *rows = (alga_edge_dev *) e->mp_rows.p;
+    uint32_t *rowptr = (uint32_t *) e->mp_rowptr.p, *len = (uint32_t *) e->mp_len.p;
+    int32_t *pend[2] = {(int32_t *) e->mp_pend[0].p, (int32_t *) e->mp_pend[1].p};
+
+    if (m) HIP_TRY(e, hipMemcpyAsync(rows, d_in, (size_t) m * sizeof(alga_edge_dev), hipMemcpyDeviceToDevice, s));
+    launch_edge_rowptr(d_in, m, n, rowptr, s);
+    if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
+    launch_mst_init(rowptr, n, len, (unsigned long long *) e->mp_owner.p, pend[0], cnt, s);
+    if ((rc = alga_check_launch(e, "k_mst_init"))) return rc;
+    // the maps of the overflow states must be empty: every walk leaves them so (mst_clear), so a tier is filled only when its buffer or its geometry
+    // is not the one of the last fill -- once per engine for the graphs of one size class, not per call.  Until this call has reached its end
+    // the states count as unknown.
+    const MstTier *tier_of[2] = {&tiers.mid, &tiers.big};
+    const size_t tier_bytes[2] = {mid_bytes, big_bytes};
+    for (int k = 0; k < (need_big ? 2 : 1); k++) {
+        const MstTier &t = *tier_of[k];
+        const alga_engine::MstFilled &f = e->mp_filled[k];
+        if (f.p != t.ws || f.bytes != tier_bytes[k] || f.hbits != t.hbits || f.cap_nodes != t.cap_nodes || f.cap_edges != t.cap_edges || f.n_ws != t.n_ws)
+            HIP_TRY(e, hipMemsetAsync(t.ws, 0xFF, tier_bytes[k], s));
+        e->mp_filled[k].p = nullptr;
+    }
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt + MST_N_PEND0, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipEventRecord(evs.ev[1], s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    uint64_t n_pend = e->h_counters[0];
+    const uint64_t branching = n_pend;
+
+    // ---- the rounds
+    uint64_t rounds = 0, begs_run = 0;
+    for (int cur = 0; n_pend > 0; cur ^= 1) {
+        if (rounds >= 0xFFFFFFFEull) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 rounds");
+        HIP_TRY(e, hipMemsetAsync(cnt + MST_N_WIN, 0, MST_ROUND_COUNTERS * sizeof(unsigned long long), s));   // winners and the overflow counts
+        HIP_TRY(e, hipMemsetAsync(cnt + MST_N_PEND0 + (cur ^ 1), 0, sizeof(unsigned long long), s));
+        const MstRound r{MstGraph{rows, rowptr, len}, (unsigned long long *) e->mp_owner.p, (unsigned long long) (0xFFFFFFFFull - rounds) << 32, max_offset,
+                         (int32_t *) e->mp_win.p, pend[cur ^ 1], (int32_t *) e->mp_overflow.p, (int32_t *) e->mp_overflow2.p, cnt, cur ^ 1};
+        launch_mst_claim(r, pend[cur], cur, n_pend, tiers, s);
+        if ((rc = alga_check_launch(e, "k_mst_claim"))) return rc;
+        launch_mst_select(r, pend[cur], cur, n_pend, tiers, s);
+        if ((rc = alga_check_launch(e, "k_mst_select"))) return rc;
+        HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, MST_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));
+        const uint64_t n_win = e->h_counters[MST_N_WIN];
+        n_pend = e->h_counters[MST_N_PEND0 + (cur ^ 1)];
+        if (n_win == 0) break;                                       // nothing pending branches any more (the smallest that does always wins)
+        launch_mst_run(r, n_win, tiers, s);
+        if ((rc = alga_check_launch(e, "k_mst_run"))) return rc;
+        if (info && rounds < ALGA_MST_MAX_ROUNDS) info->winners[rounds] = n_win;
+        rounds++;
+        begs_run += n_win;
+    }
+    HIP_TRY(e, hipEventRecord(evs.ev[2], s));
+
+    // ---- the rows, closed up
+    launch_exclusive_scan(len, (uint64_t) n, (uint32_t *) e->mp_orow.p, (uint64_t *) e->scan_scratch.p, s);
+    if ((rc = alga_check_launch(e, "scan(len)"))) return rc;
+    if (n > 0) launch_compact_rows(rows, rowptr, len, (const uint32_t *) e->mp_orow.p, n, (alga_edge_dev *) e->mp_out.p, s);
+    if ((rc = alga_check_launch(e, "k_compact_rows"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, MST_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipMemcpyAsync(e->h_counters + MST_COUNTERS, (const uint32_t *) e->mp_orow.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    *d_out = (const alga_edge *) e->mp_out.p;
+    *m_out = n > 0 ? (uint64_t) *(const uint32_t *) (e->h_counters + MST_COUNTERS) : 0;
+    for (int k = 0; k < (need_big ? 2 : 1); k++) e->mp_filled[k] = alga_engine::MstFilled{tier_of[k]->ws, tier_bytes[k], tier_of[k]->hbits, tier_of[k]->cap_nodes, tier_of[k]->cap_edges, tier_of[k]->n_ws};
+    if (info) {
+        info->edges_in = m; info->edges_out = *m_out; info->branching_nodes = branching; info->begs_run = begs_run; info->rounds = rounds;
+        info->overflow_begs = e->h_counters[MST_OVERFLOW_TOTAL]; info->ball_max = e->h_counters[MST_BALL_MAX];
+        float t = 0.0f;
+        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); info->ms_prepare = t;
+        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); info->ms_rounds = t;
+    }
+    return ALGA_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int alga_remove_short_parallel_paths_device(alga_engine *e, int32_t n_nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset, void *hip_stream,
+                                            const alga_edge **d_edges_out, uint64_t *n_edges_out, alga_mst_info *info) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    const auto t0 = std::chrono::steady_clock::now();
+    if (info) *info = alga_mst_info{};
+    if (!d_edges_out || !n_edges_out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "output pointers must not be NULL");
+    *d_edges_out = nullptr; *n_edges_out = 0;
+    if (n_nodes < 0 || (n_edges && !d_edges)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad graph");
+    if (n_edges && !n_nodes) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "edge endpoint outside [0, n)");
+    if (n_edges >= (1ull << 31) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^31 edges");
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
+    const int rc = mst_impl(e, n_nodes, (const alga_edge_dev *) d_edges, n_edges, max_offset, s, d_edges_out, n_edges_out, info);
+    if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); if (info) *info = alga_mst_info{}; *d_edges_out = nullptr; *n_edges_out = 0; return rc; }
+    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ALGA_OK;
+}
 
 int alga_remove_dangling_branches_device(alga_engine *e, int32_t n_nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset, void *hip_stream,
                                          const alga_edge **d_edges_out, uint64_t *n_edges_out, alga_tips_info *info) {

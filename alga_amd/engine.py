@@ -158,7 +158,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_shard_index_device", "alga_shard_join_device", "alga_shard_small_keys_device", "alga_shard_resolve_device", "alga_shard_place_device",
            "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
-           "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device"]
+           "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
+           "alga_remove_short_parallel_paths_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 
@@ -184,6 +185,21 @@ class TipsInfo(C.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "removed"}
         d["removed"] = [int(x) for x in self.removed[: min(self.passes, TIPS_MAX_PASSES)]]
+        return d
+
+
+MST_MAX_ROUNDS = 64                                              # ALGA_MST_MAX_ROUNDS
+
+
+class MstInfo(C.Structure):
+    """alga_mst_info"""
+    _fields_ = [("edges_in", C.c_uint64), ("edges_out", C.c_uint64), ("branching_nodes", C.c_uint64), ("begs_run", C.c_uint64), ("rounds", C.c_uint64),
+                ("winners", C.c_uint64 * MST_MAX_ROUNDS), ("overflow_begs", C.c_uint64), ("ball_max", C.c_uint64),
+                ("ms_prepare", C.c_double), ("ms_rounds", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "winners"}
+        d["winners"] = [int(x) for x in self.winners[: min(self.rounds, MST_MAX_ROUNDS)]]
         return d
 
 
@@ -345,6 +361,8 @@ def load_library():
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.alga_remove_dangling_branches_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p),
                                                          C.POINTER(C.c_uint64), C.POINTER(TipsInfo)]
+    lib.alga_remove_short_parallel_paths_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p),
+                                                            C.POINTER(C.c_uint64), C.POINTER(MstInfo)]
     lib.alga_unitigs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(UnitigsC),
                                         C.POINTER(UnitigInfo)]
     lib.alga_write_unitig_gfa_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
@@ -467,7 +485,7 @@ class Engine:
 
     def set_option(self, name, value):
         """alga_engine_set_option: "probe" ("auto" | "table" | "cluster"), "cluster_bucket_bias", "cluster_pairs", "cluster_order",
-        "local_big_max", "auto_reduction_per_target"."""
+        "local_big_max", "auto_reduction_per_target", "mst_mid_nodes", ... (the list is in include/alga_amd.h)."""
         if name == "probe" and isinstance(value, str):
             value = PROBE[value]
         self._check(self._lib.alga_engine_set_option(self._h, name.encode(), int(value)))
@@ -869,6 +887,36 @@ class Engine:
         self._check(self._lib.alga_cut_triangles_device(self._h, int(n_nodes), C.c_void_p(d_edges_ptr), int(n_edges), int(max_offset_parallel_paths),
                                                         C.c_void_p(stream or 0), C.byref(out), C.byref(m), C.byref(rem)))
         return out.value, int(m.value), int(rem.value)
+
+    def remove_short_parallel_paths(self, n_nodes, edges, max_offset, n_edges=None, stream=None):
+        """Remove the short parallel paths (alga_remove_short_parallel_paths_device: the definition is in include/alga_amd.h) -> (edges, info).
+        edges in: a device pointer (with n_edges), an int32 device tensor [m, 3] or a numpy array [m, 3] (uploaded), grouped by src in ascending
+        order, every list in the order the triangle cut leaves it in.
+        edges out: a zero-copy int32 device tensor [m', 3], grouped by src, the lists in the reference's order, engine-owned, valid until the next
+        call of this method (clone what has to live longer); it goes straight into remove_dangling_branches and unitigs.  info: dict of
+        alga_mst_info, "winners" = the begs run per round.
+        stream: the stream that produced the input, synchronised first (the call runs on the engine's own stream)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        keep = None
+        if isinstance(edges, np.ndarray):
+            e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)
+            keep = torch.from_numpy(e).to(dev)
+            ptr, m = _ptr(keep), len(e)
+        elif isinstance(edges, int):
+            ptr, m = edges, int(n_edges or 0)
+        else:
+            keep = edges
+            ptr, m = _ptr(edges), int(edges.shape[0]) if n_edges is None else int(n_edges)
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        out, mo, info = C.c_void_p(), C.c_uint64(), MstInfo()
+        self._check(self._lib.alga_remove_short_parallel_paths_device(self._h, int(n_nodes), C.c_void_p((ptr or None) if m else None), C.c_uint64(m), int(max_offset),
+                                                                      None, C.byref(out), C.byref(mo), C.byref(info)))
+        del keep
+        return device_view(out.value, (int(mo.value), 3), "cuda:%d" % self.device), info.as_dict()
 
     def remove_dangling_branches(self, n_nodes, edges, max_offset, n_edges=None, stream=None):
         """Clip the tips (alga_remove_dangling_branches_device: the definition is in include/alga_amd.h) -> (edges, info).

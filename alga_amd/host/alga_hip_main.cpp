@@ -3,6 +3,7 @@
 //   alga_hip --file1=reads.fasta [--file2=mates.fasta] --output=contigs.fasta [--threads=N] [--error_rate=R | --error-rate=R]
 //            [--serialize=1] [-l MINOVERLAP] [--rsoemo=N] [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1]
 //            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1]
+//            [--parallel_paths=0|1]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -25,6 +26,10 @@
 // simplifyGraphOld), build -> supplement -> cut -> clip -> unitigs -> GFA.  The bound is the reference's,
 // int(max(250, int(1.75 * LEN)) * AVG_READ_LENGTH / 100.0f) with AVG_READ_LENGTH the integer mean length of the live reads
 // (Global::calculateAvgReadLength).  Without --unitigs= it does nothing; it is not passed through.
+// --parallel_paths=1 (default 0: every invocation without it behaves as before): with --unitigs=, the short parallel paths go between the cut and
+// the clip (alga_remove_short_parallel_paths_device: GraphSimplifier::removeShortParallelPaths), build -> supplement -> cut -> parallel paths ->
+// clip (with --clip_tips=1) -> unitigs -> GFA.  The bound is the reference's, int(double(max(250, int(1.75 * LEN)) * AVG_READ_LENGTH) / 100.0f)
+// with the same AVG_READ_LENGTH.  Without --unitigs= it does nothing; it is not passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -52,7 +57,7 @@ int main(int argc, char **argv) {
     std::string file1, file2, output, alga_exe, gfa, unitigs, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
-    int device = 0, serialize = 1, gpus = 1, clip_tips = 0;
+    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0;
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -76,6 +81,7 @@ int main(int argc, char **argv) {
         else if (opt(a, "--gfa", v)) gfa = v;
         else if (opt(a, "--unitigs", v)) unitigs = v;
         else if (opt(a, "--clip_tips", v)) clip_tips = atoi(v.c_str());
+        else if (opt(a, "--parallel_paths", v)) parallel_paths = atoi(v.c_str());
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
         else { fprintf(stderr, "alga_hip: unrecognized option '%s'\n", a); return 2; }
         // the hand-off to stock ALGA drops the error-rate option: the supplement it switches on (src/Params.cpp:357-359) has
@@ -83,7 +89,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -227,7 +233,7 @@ int main(int argc, char **argv) {
         alga_unitigs u;
         alga_unitig_info ui;
         alga_gfa_info gi;
-        if (rc == ALGA_OK && clip_tips) {
+        if (rc == ALGA_OK && (clip_tips || parallel_paths)) {
             // Global::calculateAvgReadLength at src/GraphSimplifiers/GraphSimplifier.cpp:179: the mean (a double) over the reads alive after the cut,
             // i.e. without those the cut graph has no edge at (Global::removeIsolatedReads, :117)
             std::vector<int32_t> hl((size_t) nodes.n);
@@ -240,9 +246,19 @@ int main(int argc, char **argv) {
             for (size_t k = 0; k < hl.size(); k++) if (hl[k] > 0 && has_edge[k]) { sum += hl[k]; cnt++; }
             const double avg = cnt ? sum / (double) cnt : 0.0;
             const int bound = (int) (mopp * avg / (float) 100);                  // MAX_OFFSET_DANGLING_BRANCHES has MAX_OFFSET_PARALLEL_PATHS's value, src/main.cpp:95-96
+            if (rc == ALGA_OK && parallel_paths) {
+                alga_mst_info mi;
+                rc = alga_remove_short_parallel_paths_device(engine, nodes.n, d_cut, n_cut, bound, nullptr, &d_cut, &n_cut, &mi);
+                if (rc == ALGA_OK)
+                    fprintf(stderr, "Short parallel paths removed: bound %d (average live read length %.3f), %llu edges in, %llu edges out, %llu rounds; %llu of %llu branching nodes "
+                            "ran, %llu by the overflow route, largest ball %llu nodes; device ms: prepare %.3f rounds %.3f, call %.1f ms wall\n", bound, avg,
+                            (unsigned long long) mi.edges_in, (unsigned long long) mi.edges_out, (unsigned long long) mi.rounds, (unsigned long long) mi.begs_run,
+                            (unsigned long long) mi.branching_nodes, (unsigned long long) mi.overflow_begs, (unsigned long long) mi.ball_max, mi.ms_prepare, mi.ms_rounds,
+                            mi.ms_total);
+            }
             alga_tips_info ti;
-            if (rc == ALGA_OK) rc = alga_remove_dangling_branches_device(engine, nodes.n, d_cut, n_cut, bound, nullptr, &d_cut, &n_cut, &ti);
-            if (rc == ALGA_OK) {
+            if (rc == ALGA_OK && clip_tips) rc = alga_remove_dangling_branches_device(engine, nodes.n, d_cut, n_cut, bound, nullptr, &d_cut, &n_cut, &ti);
+            if (rc == ALGA_OK && clip_tips) {
                 fprintf(stderr, "Tips clipped: bound %d (average live read length %.3f), %d iterations, %llu edges removed (", bound, avg, ti.iterations,
                         (unsigned long long) ti.removed_total);
                 for (int k = 0; k < ti.passes && k < ALGA_TIPS_MAX_PASSES; k++) fprintf(stderr, "%s%llu", k ? " / " : "", (unsigned long long) ti.removed[k]);

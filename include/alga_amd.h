@@ -196,6 +196,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                next ruler, the rulers alone are ranked by pointer jumping, a second walk fills in the nodes between them: ~3 gathers
  *                                per node instead of one per node and round (5.5 x faster at 1.7 M nodes) -- from 2^16 nodes on (below, a handful of rounds
  *                                over a cache-resident array costs less than the extra launches); 1: always, 0: never (A/B and tests)
+ *   "mst_mid_nodes"              8..2^20 (default 4096): nodes a state of the first overflow tier of alga_remove_short_parallel_paths_device holds (and twice
+ *                                as many collected edges); a beg that needs more takes a state sized for the whole graph (tests lower it to reach that tier)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
@@ -642,6 +644,63 @@ int  alga_cut_triangles_device(alga_engine *e, int32_t n_nodes, const alga_edge 
                                void *hip_stream, const alga_edge **d_edges_out, uint64_t *n_edges_out, uint64_t *n_removed /* may be NULL */);
 int  alga_cut_triangles_host(alga_engine *e, int32_t n_nodes, const alga_edge *edges, uint64_t n_edges, int32_t max_offset_parallel_paths,
                              alga_edge **edges_out, uint64_t *n_edges_out);     /* release with alga_free_edges() */
+
+/* ---- short parallel paths: bubbles go between the cut and the clip (alga_amd/csrc/mst_kernels.hip, mst_walk.h, engine_simplify.hip) ----------
+ * GraphSimplifier::removeShortParallelPaths, i.e. tryToRemoveShortPathsMST for every node with >= 2 out-edges
+ * (src/GraphSimplifiers/GraphSimplifier.cpp:182, :351-518); tests/tips_checker.py restates it in Python (remove_short_parallel_paths, held to the
+ * reference's own dumps at --threads=1) and the device result equals that, entry for entry.  A sequencing error in the middle of a read opens a
+ * bubble: two paths between the same two nodes.  The step keeps, around every branching node, a tree of the lightest edges.
+ * The pipeline on the device: build -> supplement -> cut -> PARALLEL PATHS -> clip -> unitigs -> GFA.
+ *   In: `d_edges` grouped by src with src ascending, device memory, every list in the order alga_cut_triangles_device leaves it in: list order
+ *   matters.  Ids outside [0, n_nodes), a negative offset or a src smaller than the one before it: ALGA_ERR_INVALID_ARGUMENT, checked on the
+ *   device, nothing written, the previous result untouched.
+ *   One beg: the nodes beg = 0, 1, ..., n - 1 in ascending order, each on the graph the earlier ones left; a node that has >= 2 out-edges at
+ *   that moment does this:
+ *     1. a queue neigh = [beg] is processed in order, dst[beg] = 0;
+ *     2. a node a taken from the queue is expanded only if it has not been expanded before and dst[a] <= max_offset;
+ *     3. expansion walks a's list in list order; an entry (b, o) is skipped if dst[b] is set and dst[b] < dst[a] + o; otherwise
+ *        dst[b] = dst[a] + o, (a, b, o) is appended to `edges` and b to the queue;
+ *     4. for every collected edge in collection order Graph::removeDirectedEdge(a, b): every entry a -> b goes, each swapped with the
+ *        shrinking last position;
+ *     5. `edges` is sorted by (o, a, b);
+ *     6. in that order an edge is pushed to the back of a's list unless an edge into b has been pushed already for this beg.
+ *   Out: grouped by src, every list in exactly the resulting order (a Graph::V filled from it is the reference's graph after the step, entry for
+ *   entry); engine-owned device memory, valid until the next call of this function.  It can hold several edges per (src, dst): the clip
+ *   applies Graph::retainOnlySmallestOffset itself.
+ * `max_offset`: the reference passes int(double(MAX_OFFSET_PARALLEL_PATHS * AVG_READ_LENGTH) / 100.0f) (:182), AVG_READ_LENGTH as for the clip.
+ * The schedule.  A beg reads and writes only the lists of the nodes it expands, and an expanded node has a path of weight <= max_offset from
+ * beg in the graph of that moment.  The step only removes edges (what it pushes back is part of what it took out), so whenever beg runs, what
+ * it expands lies in its ball B(beg): the nodes at shortest-path distance <= max_offset from beg in any EARLIER state of the graph.  Two begs
+ * with disjoint balls commute.  Rounds: the nodes with >= 2 out-edges are pending (one whose degree has fallen below 2 is dropped: a degree
+ * never rises); every pending beg computes its ball on the current graph and claims each node of it with the minimum of the claiming ids; a
+ * beg that holds its whole ball wins -- no smaller pending id touches its ball, now or later -- and the winners run the literal step on the
+ * live lists, in any order.  The smallest pending id always wins.  The host reads one pair of counts per round.  The result is the
+ * sequential ascending-id run's, entry for entry (tests/mst_schedule.py states the schedule in Python; tests/test_mst_schedule_cpu.py).
+ * The number of rounds is the longest chain of overlapping balls with ascending ids: tens of rounds when ids are in random order along the
+ * genome (reads as a sequencer delivers them), proportional to the length of a contig when the reads are numbered in genome order.  That is a
+ * property of the definition (a beg must see what every smaller id within its reach has left), not of this implementation; there is no cap
+ * and no host fallback.  `rounds` reports it.  The ABI number stays 7: like the GFA, unitig and clip calls before it this one only adds to the ABI.
+ * The walks: one wave per beg with the state in LDS (a map of 256 slots, 192 nodes, 256 collected edges); begs that need more (rows of hundreds of
+ * edges, balls of several hundred nodes) take the overflow route with per-beg arrays in a device workspace: 1024 states of 4096 nodes and 8192
+ * edges, and for what even those cannot hold states sized for the whole graph (as many as 1 GB holds, at least one).
+ * Device memory of the engine for this call, kept until the engine goes: 24 bytes per edge and 28 per node for rows, lists and owner[]; 180 MB for
+ * the first overflow tier; and for a graph that one of its states does not hold (more than 4096 nodes or 8192 edges) the second tier, allocated up
+ * front because a round finds out on the device who needs it: one state is 8 * 2^ceil(log2(2 (n + 1))) + 4 (n + 1) + 12 (m + 1) bytes -- 1.1 GB for
+ * 20 M nodes and 5.6 M edges, 16 GB of maps alone towards 2^30 nodes.  The states are filled once, not per call: a walk leaves its map empty. */
+#define ALGA_MST_MAX_ROUNDS 64
+typedef struct {
+    uint64_t edges_in, edges_out;
+    uint64_t branching_nodes;                    /* nodes with >= 2 out-edges in the input: the initially pending                  */
+    uint64_t begs_run;                           /* nodes that ran the step (they still had >= 2 out-edges at their turn)          */
+    uint64_t rounds;
+    uint64_t winners[ALGA_MST_MAX_ROUNDS];       /* begs run per round (the first 64 rounds; begs_run counts all)                  */
+    uint64_t overflow_begs;                      /* begs whose run took the overflow route                                         */
+    uint64_t ball_max;                           /* nodes of the largest ball claimed                                              */
+    double   ms_prepare, ms_rounds;              /* device time (HIP events): checks + rows + pending list; the rounds             */
+    double   ms_total;                           /* wall time of the call                                                          */
+} alga_mst_info;
+int  alga_remove_short_parallel_paths_device(alga_engine *e, int32_t n_nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset,
+                                             void *hip_stream, const alga_edge **d_edges_out, uint64_t *n_edges_out, alga_mst_info *info /* may be NULL */);
 
 /* ---- dangling-branch removal: tips are clipped before the unitigs (alga_amd/csrc/tip_kernels.hip, tip_walk.h, engine_simplify.hip) ----------
  * GraphSimplifier::removeDanglingBranches / removeDanglingUpperBranches as simplifyGraphOld iterates them
