@@ -750,6 +750,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
     } else if (!strcmp(name, "mst_mid_nodes")) {
         if (value < 8 || value > (1 << 20)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option mst_mid_nodes: 8 .. 2^20");
         e->opt_mst_mid_nodes = (int) value;
+    } else if (!strcmp(name, "consensus_max_blocks")) {
+        if (value < 0 || value > (1 << 20)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option consensus_max_blocks: 0 .. 2^20");
+        e->opt_consensus_max_blocks = (int) value;
     } else if (!strcmp(name, "unitig_ruling")) {
         if (value < -1 || value > 1) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option unitig_ruling: -1, 0 or 1");
         e->opt_unitig_ruling = (int) value;

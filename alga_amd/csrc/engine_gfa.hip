@@ -83,7 +83,7 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     const uint64_t total = e->h_counters[GFA_COUNTERS], max_line = e->h_counters[GFA_MAX_LINE];
     if (info) {
         info->segments = e->h_counters[GFA_SEGMENTS]; info->links = e->h_counters[GFA_LINKS]; info->links_merged = e->h_counters[GFA_MERGED];
-        info->bytes = sizeof(kGfaHeader) - 1 + total;
+        info->bytes = (c.fasta ? 0 : sizeof(kGfaHeader) - 1) + total;
     }
     // chunks: step = cap - longest line, so that no chunk exceeds cap and each ends at a line boundary
     uint64_t cap = (uint64_t) e->opt_gfa_chunk_mb << 20;
@@ -105,9 +105,9 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
         }
     }
     fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return alga_fail(e, ALGA_ERR_IO, "cannot create the GFA file");
-    const uint64_t head = sizeof(kGfaHeader) - 1;
-    if (!write_all(fd, kGfaHeader, head, 0)) return alga_fail(e, ALGA_ERR_IO, "cannot write the GFA file");
+    if (fd < 0) return alga_fail(e, ALGA_ERR_IO, c.fasta ? "cannot create the FASTA file" : "cannot create the GFA file");
+    const uint64_t head = c.fasta ? 0 : sizeof(kGfaHeader) - 1;       // (a FASTA file has no header line)
+    if (head && !write_all(fd, kGfaHeader, head, 0)) return alga_fail(e, ALGA_ERR_IO, "cannot write the GFA file");
     std::future<bool> writer[2];
     int pending_fmt[2] = {-1, -1};                                 // event pair of the chunk the slot holds, -1 none
     bool io_ok = true;
@@ -149,8 +149,8 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     for (int k = 0; k < 2; k++) { const int r = finish_slot(k); if (rc == ALGA_OK) rc = r; }
     if (rc != ALGA_OK) return rc;
     HIP_TRY(e, hipStreamSynchronize(s));
-    if (!io_ok) return alga_fail(e, ALGA_ERR_IO, "cannot write the GFA file");
-    if (close(fd) != 0) { fd = -1; return alga_fail(e, ALGA_ERR_IO, "cannot close the GFA file"); }
+    if (!io_ok) return alga_fail(e, ALGA_ERR_IO, c.fasta ? "cannot write the FASTA file" : "cannot write the GFA file");
+    if (close(fd) != 0) { fd = -1; return alga_fail(e, ALGA_ERR_IO, c.fasta ? "cannot close the FASTA file" : "cannot close the GFA file"); }
     fd = -1;
     if (info) info->ms_format = ms_format;
     return ALGA_OK;
@@ -197,14 +197,37 @@ extern "C" int alga_write_unitig_gfa_device(alga_engine *e, const alga_unitigs *
     const auto t0 = std::chrono::steady_clock::now();
     if (info) *info = alga_gfa_info{};
     if (!u || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs and path must not be NULL");
-    if (flags & ~ALGA_GFA_SEQUENCES) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown GFA flag (unitigs are always written as twin pairs)");
+    if (flags & ~(ALGA_GFA_SEQUENCES | ALGA_GFA_CONSENSUS)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown GFA flag (unitigs are always written as twin pairs)");
+    if ((flags & ALGA_GFA_CONSENSUS) && !(flags & ALGA_GFA_SEQUENCES)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "ALGA_GFA_CONSENSUS needs ALGA_GFA_SEQUENCES");
     if (!e->ut_valid || u->d_len != (const int32_t *) e->ut_ulen.p || (uint64_t) u->n_pairs != e->ut_n_pairs || u->n_edges != e->ut_n_edges ||
         u->d_words != (const uint32_t *) e->ut_words.p || u->d_edges != (const alga_edge *) e->ut_edges.p)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_unitigs_device call on this engine");
     if (u->n_edges >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 edges");
     HIP_TRY(e, hipSetDevice(e->device));
-    GfaCfg c{u->d_words, 0, (const int32_t *) e->ut_ulen2.p, 2 * u->n_pairs, (const alga_edge_dev *) u->d_edges, u->n_edges, (uint64_t) u->n_pairs, 1,
-             (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
+    if ((flags & ALGA_GFA_CONSENSUS) && !e->cs_valid) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "ALGA_GFA_CONSENSUS: no consensus of this unitig result on the engine");
+    // the consensus has the layout of the spelled sequences: only the rows differ
+    GfaCfg c{(flags & ALGA_GFA_CONSENSUS) ? (const uint32_t *) e->cs_words.p : u->d_words, 0, (const int32_t *) e->ut_ulen2.p, 2 * u->n_pairs,
+             (const alga_edge_dev *) u->d_edges, u->n_edges, (uint64_t) u->n_pairs, 1, (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
     c.row_off = (const unsigned long long *) u->d_word_off;
+    return gfa_run(e, c, path, info, t0);
+}
+
+// The consensus windows as FASTA: the same pipeline with one item per pair and no links (GfaCfg::fasta)
+extern "C" int alga_write_consensus_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const char *path, int32_t min_length,
+                                                 alga_gfa_info *info) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    const auto t0 = std::chrono::steady_clock::now();
+    if (info) *info = alga_gfa_info{};
+    if (!u || !cons || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs, consensus and path must not be NULL");
+    if (!e->ut_valid || u->d_len != (const int32_t *) e->ut_ulen.p || (uint64_t) u->n_pairs != e->ut_n_pairs || u->d_words != (const uint32_t *) e->ut_words.p)
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_unitigs_device call on this engine");
+    if (!e->cs_valid || cons->n_pairs != u->n_pairs || cons->d_words != (const uint32_t *) e->cs_words.p || cons->d_len != (const int32_t *) e->cs_len.p ||
+        cons->d_trim_left != (const int32_t *) e->cs_trim.p)
+        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_unitig_consensus_device call on this engine");
+    HIP_TRY(e, hipSetDevice(e->device));
+    GfaCfg c{cons->d_words, 0, cons->d_len, u->n_pairs, nullptr, 0, (uint64_t) u->n_pairs, 0, 1};
+    c.row_off = (const unsigned long long *) u->d_word_off;
+    c.fasta = 1; c.min_length = min_length; c.seq_off = cons->d_trim_left;
     return gfa_run(e, c, path, info, t0);
 }

@@ -140,6 +140,13 @@ struct alga_engine {
     int         opt_unitig_ruling = -1;            // option "unitig_ruling": the list ranking ranks a ruling set first (1), never (0), from 2^16 nodes on (-1)
     uint64_t    ut_n_pairs = 0, ut_n_edges = 0;    // the result at hand (ut_valid: the buffers hold one)
     bool        ut_valid = false;
+    int32_t     ut_n_nodes = 0;                    // ... the n of the node set it was made from, the sum of its lengths
+    uint64_t    ut_total_bases = 0;
+    // consensus of the unitigs (engine_consensus.hip): counters, the sequences, the per-word column masks, the vote bytes, per-pair window / changed
+    DevBuf      cs_cnt, cs_words, cs_mask, cs_votes, cs_trim, cs_len, cs_changed;
+    bool        cs_valid = false;                  // the buffers hold the consensus of the unitig result at hand
+    bool        cs_has_votes = false;
+    int         opt_consensus_max_blocks = 0;      // option "consensus_max_blocks": cap on the grids of the consensus kernels (0: their own); tests lower it to make small inputs stride
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

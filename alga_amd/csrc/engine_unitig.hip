@@ -77,7 +77,7 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
     }
     // the input is valid: from here on the previous result's buffers are rewritten
-    e->ut_valid = false;
+    e->ut_valid = false; e->cs_valid = false;
     const size_t N = (size_t) n;
     for (int k = 0; k < 2; k++) {
         if ((rc = alga_ensure(e, e->ut_keys[k], (size_t) (m2 + 1) * sizeof(unsigned long long)))) return rc;
@@ -228,7 +228,7 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
     HIP_TRY(e, hipEventRecord(evs.ev[5], s));
     HIP_TRY(e, hipStreamSynchronize(s));
 
-    e->ut_valid = true; e->ut_n_pairs = P; e->ut_n_edges = mu;
+    e->ut_valid = true; e->ut_n_pairs = P; e->ut_n_edges = mu; e->ut_n_nodes = n; e->ut_total_bases = c[UT_TOTAL_BASES];
     out->n_pairs = (int32_t) P;
     out->d_words = (const uint32_t *) e->ut_words.p; out->d_word_off = (const uint64_t *) word_off; out->d_len = (const int32_t *) e->ut_ulen.p;
     out->d_path_node = (const int32_t *) e->ut_path_node.p; out->d_path_pos = (const int32_t *) e->ut_path_pos.p; out->d_path_off = (const uint64_t *) path_off;

@@ -19,8 +19,12 @@ struct GfaCfg {
     // optional: ragged rows (the unitig graph).  Non-null: the row of node v starts at words + row_off[v >> 1] (one row per twin pair, read
     // through its odd node; `stride` is not used); null: at words + v * stride
     const unsigned long long *row_off = nullptr;
+    // optional: FASTA records instead of segment lines (the consensus windows; twins == 0, m == 0, one ragged row per item): item j is
+    // `>unitig_<j>_length=<len[j]>\n<bases seq_off[j] .. seq_off[j] + len[j] of its row>\n`, written when len[j] >= min_length and len[j] > 0
+    int32_t fasta = 0, min_length = 0;
+    const int32_t *seq_off = nullptr;
     __host__ __device__ __forceinline__ const uint32_t *row(uint64_t node) const {
-        return row_off ? words + row_off[node >> 1] : words + node * (uint64_t) stride;
+        return row_off ? words + row_off[twins ? node >> 1 : node] : words + node * (uint64_t) stride;
     }
 };
 

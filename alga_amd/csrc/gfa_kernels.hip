@@ -63,6 +63,11 @@ __device__ __forceinline__ uint64_t seg_line_bytes(uint64_t name, int32_t L, int
     return L > 0 ? 2 + dec_width(name) + 1 + (seqs ? (uint64_t) L : 1) + 6 + dec_width((uint64_t) L) + 1 : 0;
 }
 
+// > unitig_ name _length= len \n seq \n
+__device__ __forceinline__ uint64_t fasta_record_bytes(uint64_t name, int32_t L, int32_t min_length) {
+    return L > 0 && L >= min_length ? 8 + dec_width(name) + 8 + dec_width((uint64_t) L) + 1 + (uint64_t) L + 1 : 0;
+}
+
 __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_check(GfaCfg c, unsigned long long *__restrict__ counters) {
     const uint64_t items = c.m > (uint64_t) c.n ? c.m : (uint64_t) c.n;
     unsigned long long bad = 0;
@@ -86,8 +91,8 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_sizes(GfaCfg c, uint32_t 
     unsigned long long live = 0, bytes = 0;
     if (j < c.n_seg) {
         const int32_t L = c.len[c.twins ? 2 * j + 1 : j];
-        bytes = seg_line_bytes(j, L, c.seqs);
-        live = L > 0;
+        bytes = c.fasta ? fasta_record_bytes(j, L, c.min_length) : seg_line_bytes(j, L, c.seqs);
+        live = bytes > 0;
         sizes[j] = (uint32_t) bytes;
     }
     live = wave_sum(live);
@@ -214,13 +219,22 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_bounds(const unsigned long lo
     bounds[K + 1 + k] = off[b];
 }
 
-// byte p of a segment line: "S\t" name "\t" seq "\tLN:i:" len "\n"
+// byte p of a segment line: "S\t" name "\t" seq "\tLN:i:" len "\n"; of a FASTA record: ">unitig_" name "_length=" len "\n" seq "\n"
 struct SegLine {
     uint64_t name; int32_t L; int wn, wl; uint32_t hp, sl;           // hp = bytes before the sequence, sl = bytes of the sequence field
     const uint32_t *row; int seqs;
+    int fasta; uint32_t q0;                                           // FASTA: the sequence starts at base q0 of the row
     __device__ __forceinline__ char digit(uint64_t v, int w, int d) const { return (char) ('0' + (v / kPow10[w - 1 - d]) % 10); }
-    __device__ __forceinline__ char base(uint32_t q) const { return (char) ((0x54474341u >> (8 * ((row[q >> 4] >> (2 * (q & 15))) & 3))) & 0xFF); }
+    __device__ __forceinline__ char base(uint32_t q) const { q += q0; return (char) ((0x54474341u >> (8 * ((row[q >> 4] >> (2 * (q & 15))) & 3))) & 0xFF); }
     __device__ char at(uint32_t p) const {
+        if (fasta) {
+            if (p < 8) return ">unitig_"[p];
+            if (p < 8u + wn) return digit(name, wn, (int) p - 8);
+            if (p < 16u + wn) return "_length="[p - 8 - wn];
+            if (p + 1 < hp) return digit((uint64_t) L, wl, (int) (p - 16 - wn));
+            if (p < hp) return '\n';
+            return p - hp < sl ? base(p - hp) : '\n';
+        }
         if (p < hp) return p < 2 ? (p == 0 ? 'S' : '\t') : (p < 2u + wn ? digit(name, wn, (int) p - 2) : '\t');
         const uint32_t q = p - hp;
         if (q < sl) return seqs ? base(q) : '*';
@@ -230,6 +244,7 @@ struct SegLine {
     }
     // 16 bases from sequence index q (all inside the sequence) as 4 little-endian words of ASCII
     __device__ __forceinline__ uint4 bases16(uint32_t q) const {
+        q += q0;
         const uint32_t w = q >> 4, sh = q & 15;
         uint32_t codes = row[w];
         if (sh) codes = (uint32_t) ((((uint64_t) row[w + 1] << 32) | codes) >> (2 * sh));
@@ -257,8 +272,9 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const uns
         const uint64_t node = c.twins ? 2 * j + 1 : j;
         SegLine s;
         s.name = j; s.L = c.len[node]; s.wn = dec_width(j); s.wl = dec_width((uint64_t) s.L);
-        s.hp = 2 + s.wn + 1; s.sl = c.seqs ? (uint32_t) s.L : 1u;
+        s.hp = c.fasta ? 8 + s.wn + 8 + s.wl + 1 : 2 + s.wn + 1; s.sl = c.seqs ? (uint32_t) s.L : 1u;
         s.row = c.row(node); s.seqs = c.seqs;
+        s.fasta = c.fasta; s.q0 = c.fasta ? (uint32_t) c.seq_off[j] : 0u;
         char *g0 = buf + (l0 - base), *g1 = buf + (l1 - base);
         char *a0 = (char *) (((uintptr_t) g0 + 15) & ~(uintptr_t) 15), *a1 = (char *) ((uintptr_t) g1 & ~(uintptr_t) 15);
         if (a0 >= a1) {                                               // no whole aligned block inside the line

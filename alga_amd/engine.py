@@ -159,9 +159,10 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
            "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
-           "alga_remove_short_parallel_paths_device"]
+           "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
+GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
 
 
 class GfaInfo(C.Structure):
@@ -246,6 +247,48 @@ class Unitigs:
         return dict(n_pairs=self.n_pairs, words=h(self.words).view(np.uint32), word_off=h(self.word_off).view(np.uint64), len=h(self.len),
                     path_node=h(self.path_node), path_pos=h(self.path_pos), path_off=h(self.path_off).view(np.uint64),
                     edges=h(self.edges).reshape(-1, 3), info=dict(self.info))
+
+
+CONSENSUS_VOTES = 1                                              # alga_unitig_consensus_device flag
+
+
+class ConsensusC(C.Structure):
+    """alga_consensus"""
+    _fields_ = [("n_pairs", C.c_int32), ("d_words", C.c_void_p), ("d_trim_left", C.c_void_p), ("d_len", C.c_void_p), ("d_changed", C.c_void_p),
+                ("d_votes", C.c_void_p)]
+
+
+class ConsensusInfo(C.Structure):
+    """alga_consensus_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("pairs", "pairs_kept", "columns", "trimmed_bases", "changed", "max_depth", "wide_words")] + \
+               [(k, C.c_double) for k in ("ms_vote", "ms_window", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Consensus:
+    """Result of Engine.unitig_consensus: zero-copy torch views of the engine's device memory (valid until the next Engine.unitig_consensus or
+    Engine.unitigs call on that engine; clone what has to live longer) -- words int32 [total words] (the untrimmed consensus in the layout of
+    Unitigs.words), trim_left / len / changed int32 [n_pairs], votes uint8 [16 * total words] or None -- and .info (dict of
+    alga_consensus_info)."""
+
+    def __init__(self, c, info, unitigs, device):
+        self._c, self.info, self.n_pairs = c, info, int(c.n_pairs)
+        P = self.n_pairs
+        dev = "cuda:%d" % device
+        total_words = int(unitigs.words.shape[0])
+        self.words = device_view(c.d_words, (total_words,), dev)
+        self.trim_left = device_view(c.d_trim_left, (P,), dev)
+        self.len = device_view(c.d_len, (P,), dev)
+        self.changed = device_view(c.d_changed, (P,), dev)
+        self.votes = device_view(c.d_votes, (16 * total_words,), dev, "|u1") if c.d_votes else None
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/consensus_checker.py"""
+        h = lambda t: t.cpu().numpy().copy()
+        return dict(n_pairs=self.n_pairs, words=h(self.words).view(np.uint32), trim_left=h(self.trim_left), len=h(self.len), changed=h(self.changed),
+                    votes=None if self.votes is None else h(self.votes), info=dict(self.info))
 
 
 def library_path():
@@ -366,6 +409,9 @@ def load_library():
     lib.alga_unitigs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(UnitigsC),
                                         C.POINTER(UnitigInfo)]
     lib.alga_write_unitig_gfa_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
+    lib.alga_unitig_consensus_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(UnitigsC), C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.POINTER(ConsensusC), C.POINTER(ConsensusInfo)]
+    lib.alga_write_consensus_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1022,11 +1068,42 @@ class Engine:
         del keep
         return Unitigs(out, info.as_dict(), self.device)
 
-    def write_unitig_gfa(self, path, unitigs, sequences=True):
+    def write_unitig_gfa(self, path, unitigs, sequences=True, consensus=None):
         """The result of the LAST Engine.unitigs call as GFA 1.0 (alga_write_unitig_gfa_device) -> dict of alga_gfa_info: pair k is segment k,
-        a unitig edge and its twin are one link."""
+        a unitig edge and its twin are one link.  consensus: the result of the LAST Engine.unitig_consensus call -- the segments then carry
+        the untrimmed consensus instead of the spelled sequence (the link overlaps hold for it as they are)."""
         info = GfaInfo()
-        self._check(self._lib.alga_write_unitig_gfa_device(self._h, C.byref(unitigs._c), os.fsencode(path), GFA_SEQUENCES if sequences else 0, C.byref(info)))
+        flags = (GFA_SEQUENCES if sequences else 0) | (GFA_CONSENSUS if consensus is not None else 0)
+        self._check(self._lib.alga_write_unitig_gfa_device(self._h, C.byref(unitigs._c), os.fsencode(path), flags, C.byref(info)))
+        return info.as_dict()
+
+    def unitig_consensus(self, words, lens, unitigs, min_votes=3, votes=False, stream=None):
+        """Consensus sequences of the unitigs (alga_unitig_consensus_device: the definition is in include/alga_amd.h) -> Consensus.
+        words / lens: the node set the LAST Engine.unitigs call was made from (torch device tensors; numpy arrays are uploaded first);
+        unitigs: that call's result.  min_votes: the window ends at the first / last column whose winning base has more votes than this
+        (the reference: 3; 0: no trimming).  votes: also return the winning count of every column (one byte, saturated at 255)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(words, np.ndarray):
+            words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(dev)
+        if isinstance(lens, np.ndarray):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 else 1, _ptr(lens), int(lens.shape[0]), None, None)
+        out, info = ConsensusC(), ConsensusInfo()
+        self._check(self._lib.alga_unitig_consensus_device(self._h, C.byref(nd), C.byref(unitigs._c), int(min_votes), CONSENSUS_VOTES if votes else 0,
+                                                           None, C.byref(out), C.byref(info)))
+        return Consensus(out, info.as_dict(), unitigs, self.device)
+
+    def write_consensus_fasta(self, path, unitigs, consensus, min_length=200):
+        """The windows of the LAST Engine.unitig_consensus call as FASTA (alga_write_consensus_fasta_device) -> dict of alga_gfa_info
+        (segments = records): `>unitig_<k>_length=<len>` and the sequence on one line, for every pair with len >= min_length."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_consensus_fasta_device(self._h, C.byref(unitigs._c), C.byref(consensus._c), os.fsencode(path), int(min_length),
+                                                                C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):
@@ -1167,11 +1244,11 @@ class _DevArray:
 
 
 def device_view(ptr, shape, device=None, typestr="<i4"):
-    """torch tensor (int32, or int64 with typestr "<i8") aliasing `ptr` (no copy).  Valid until the engine reuses
+    """torch tensor (int32, int64 with typestr "<i8", uint8 with "|u1") aliasing `ptr` (no copy).  Valid until the engine reuses
     the buffer."""
     import torch
     if int(np.prod(shape)) == 0:
-        return torch.empty(tuple(shape), dtype=torch.int32 if typestr == "<i4" else torch.int64, device=device or "cuda")
+        return torch.empty(tuple(shape), dtype={"<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8}[typestr], device=device or "cuda")
     return torch.as_tensor(_DevArray(ptr, shape, typestr), device=device or "cuda")
 
 

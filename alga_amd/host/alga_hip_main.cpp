@@ -3,7 +3,7 @@
 //   alga_hip --file1=reads.fasta [--file2=mates.fasta] --output=contigs.fasta [--threads=N] [--error_rate=R | --error-rate=R]
 //            [--serialize=1] [-l MINOVERLAP] [--rsoemo=N] [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1]
 //            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1]
-//            [--parallel_paths=0|1]
+//            [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200] [--consensus_min_votes=3]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -30,6 +30,11 @@
 // the clip (alga_remove_short_parallel_paths_device: GraphSimplifier::removeShortParallelPaths), build -> supplement -> cut -> parallel paths ->
 // clip (with --clip_tips=1) -> unitigs -> GFA.  The bound is the reference's, int(double(max(250, int(1.75 * LEN)) * AVG_READ_LENGTH) / 100.0f)
 // with the same AVG_READ_LENGTH.  Without --unitigs= it does nothing; it is not passed through.
+// --consensus=PATH: the same chain as --unitigs= (it honours --clip_tips and --parallel_paths, and works with or without --unitigs=), then the
+// consensus of every unitig (alga_unitig_consensus_device: each column a majority vote of the reads over it, the ends cut back to the first / last
+// column with more than --consensus_min_votes votes -- Contig::correctSnipsInContig, whose THR is 3), written as FASTA for the windows of at
+// least --consensus_min_length bases (alga_write_consensus_fasta_device).  --unitigs= still writes the spelled sequences.  None of the three
+// options is passed through; every invocation without --consensus= behaves as before.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -54,10 +59,10 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 int main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    std::string file1, file2, output, alga_exe, gfa, unitigs, v;
+    std::string file1, file2, output, alga_exe, gfa, unitigs, consensus, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
-    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0;
+    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3;
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -82,6 +87,9 @@ int main(int argc, char **argv) {
         else if (opt(a, "--unitigs", v)) unitigs = v;
         else if (opt(a, "--clip_tips", v)) clip_tips = atoi(v.c_str());
         else if (opt(a, "--parallel_paths", v)) parallel_paths = atoi(v.c_str());
+        else if (opt(a, "--consensus", v)) consensus = v;
+        else if (opt(a, "--consensus_min_length", v)) consensus_min_length = atoi(v.c_str());
+        else if (opt(a, "--consensus_min_votes", v)) consensus_min_votes = atoi(v.c_str());
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
         else { fprintf(stderr, "alga_hip: unrecognized option '%s'\n", a); return 2; }
         // the hand-off to stock ALGA drops the error-rate option: the supplement it switches on (src/Params.cpp:357-359) has
@@ -89,7 +97,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -224,7 +232,7 @@ int main(int argc, char **argv) {
     std::vector<alga_edge> final_edges((size_t) n_final);
     if (n_final && alga_copy_to_host(engine, final_edges.data(), d_final, final_edges.size() * sizeof(alga_edge)) != ALGA_OK) { fprintf(stderr, "alga_amd: cannot read the edges back\n"); return 1; }
     fprintf(stderr, "Before first simplifier graph has %llu edges\n", (unsigned long long) n_final);
-    if (!unitigs.empty()) {                                                    // the edges are on the host already: nothing below touches what is handed on
+    if (!unitigs.empty() || !consensus.empty()) {                              // the edges are on the host already: nothing below touches what is handed on
         alga_nodes nd{nodes.d_words, nodes.stride_words, nodes.d_len, nodes.n, nullptr, nullptr};
         const int mopp = std::max(250, (int) (1.75 * parsed.LEN));            // Params::MAX_OFFSET_PARALLEL_PATHS, src/main.cpp:95
         const alga_edge *d_cut = nullptr;
@@ -270,8 +278,22 @@ int main(int argc, char **argv) {
         if (rc == ALGA_OK) rc = alga_unitigs_device(engine, &nd, d_cut, n_cut, ALGA_UNITIG_SKIP_ISOLATED, nullptr, &u, &ui);
         std::vector<int32_t> ul;
         if (rc == ALGA_OK) { ul.resize((size_t) u.n_pairs); if (u.n_pairs) rc = alga_copy_to_host(engine, ul.data(), u.d_len, ul.size() * sizeof(int32_t)); }
-        if (rc == ALGA_OK) rc = alga_write_unitig_gfa_device(engine, &u, unitigs.c_str(), ALGA_GFA_SEQUENCES, &gi);
-        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", unitigs.c_str(), alga_last_error(engine), rc); return 1; }
+        if (rc == ALGA_OK && !unitigs.empty()) rc = alga_write_unitig_gfa_device(engine, &u, unitigs.c_str(), ALGA_GFA_SEQUENCES, &gi);
+        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", (unitigs.empty() ? consensus : unitigs).c_str(), alga_last_error(engine), rc); return 1; }
+        if (!consensus.empty()) {
+            alga_consensus cs;
+            alga_consensus_info ci;
+            alga_gfa_info fi;
+            rc = alga_unitig_consensus_device(engine, &nd, &u, consensus_min_votes, 0, nullptr, &cs, &ci);
+            if (rc == ALGA_OK) rc = alga_write_consensus_fasta_device(engine, &u, &cs, consensus.c_str(), consensus_min_length, &fi);
+            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", consensus.c_str(), alga_last_error(engine), rc); return 1; }
+            fprintf(stderr, "Consensus written -> %s: %llu records of %llu unitigs (%llu with a window), %llu of %llu columns kept, %llu columns differ from the spelled "
+                    "sequences, depth up to %llu (%llu words by the wide route); device ms: vote %.3f window %.3f, call %.1f ms wall; FASTA %llu bytes, device %.3f ms, "
+                    "wall %.1f ms\n", consensus.c_str(), (unsigned long long) fi.segments, (unsigned long long) ci.pairs, (unsigned long long) ci.pairs_kept,
+                    (unsigned long long) ci.trimmed_bases, (unsigned long long) ci.columns, (unsigned long long) ci.changed, (unsigned long long) ci.max_depth,
+                    (unsigned long long) ci.wide_words, ci.ms_vote, ci.ms_window, ci.ms_total, (unsigned long long) fi.bytes, fi.ms_format, fi.ms_total);
+        }
+        if (!unitigs.empty()) {
         std::sort(ul.begin(), ul.end(), [](int32_t a, int32_t b) { return a > b; });
         long long n50 = 0; uint64_t acc = 0;
         for (int32_t l : ul) { acc += (uint64_t) l; if (2 * acc >= ui.total_bases) { n50 = l; break; } }
@@ -280,6 +302,7 @@ int main(int argc, char **argv) {
                 unitigs.c_str(), u.n_pairs, (unsigned long long) gi.links, (unsigned long long) ui.longest_bases, (unsigned long long) ui.longest_nodes, n50,
                 (unsigned long long) ui.total_bases, (unsigned long long) n_removed, (unsigned long long) ui.isolated_skipped, ui.ms_sym, ui.ms_rank, ui.rank_rounds,
                 ui.ms_layout, ui.ms_seq, ui.ms_edges, ui.ms_total, (unsigned long long) gi.bytes, gi.ms_format, gi.ms_total);
+        }
     }
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     fprintf(stderr, "HIP start-up %.1f ms, parse %.1f ms, duplicate/prefix removal %.1f ms wall (device %.3f ms), overlap graph %.1f ms wall (device %.3f ms: seed %.3f probe %.3f group %.3f reduce %.3f emit %.3f)\n",

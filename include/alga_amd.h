@@ -198,6 +198,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                over a cache-resident array costs less than the extra launches); 1: always, 0: never (A/B and tests)
  *   "mst_mid_nodes"              8..2^20 (default 4096): nodes a state of the first overflow tier of alga_remove_short_parallel_paths_device holds (and twice
  *                                as many collected edges); a beg that needs more takes a state sized for the whole graph (tests lower it to reach that tier)
+ *   "consensus_max_blocks"       0..2^20 (default 0 = the kernels' own caps): the largest grid of the kernels of alga_unitig_consensus_device; what does not
+ *                                fit is done by grid stride (tests lower it to make small inputs stride)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
@@ -826,8 +828,60 @@ typedef struct {
 int  alga_unitigs_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t flags, void *hip_stream,
                          alga_unitigs *out, alga_unitig_info *info /* may be NULL */);
 /* The unitig graph as GFA 1.0 through the kernels of alga_write_gfa_device: pair k is segment k with its spelled sequence (flags:
- * ALGA_GFA_SEQUENCES or 0), a unitig edge and its twin are one link.  `u` must be the result of the last alga_unitigs_device call on `e`. */
+ * ALGA_GFA_SEQUENCES or 0), a unitig edge and its twin are one link.  `u` must be the result of the last alga_unitigs_device call on `e`.
+ * ALGA_GFA_CONSENSUS (with ALGA_GFA_SEQUENCES): the segments carry the untrimmed consensus of the last alga_unitig_consensus_device call on `e`
+ * (made from `u`) instead of the spelled sequence; without the flag the file is what it was before that call existed. */
+#define ALGA_GFA_CONSENSUS 4
 int  alga_write_unitig_gfa_device(alga_engine *e, const alga_unitigs *u, const char *path, int32_t flags, alga_gfa_info *info /* may be NULL */);
+
+/* ---- consensus sequences of the unitigs: every column decided by the reads laid over it (alga_amd/csrc/consensus_kernels.hip, engine_consensus.hip) ----
+ * The second half of what the reference does with a contracted path (Contig::correctSnipsInContig, called from
+ * ContigCreatorSinglePath::getAllContigs): step 8 above spells a unitig from one read per column and so carries that read's substitutions; here
+ * every column is a majority vote of all the reads over it, and the two ends are cut back to the first and last well-supported column.  On the
+ * reference's fixtures whose simplified graph is one path (f1_cfg1, f3_paired) the window below IS the reference's contig, byte for byte up to
+ * strand.  The build -> supplement -> cut -> parallel paths -> clip -> unitigs -> CONSENSUS -> GFA / FASTA chain stays on the device.
+ * `u` must be the result of the last alga_unitigs_device call on `e` and `nodes` the node set it was made from.  The definition
+ * (tests/consensus_checker.py states it in Python, once line for line after the reference and once as a pile-up; the device result equals both
+ * byte for byte), for pair k with length L, path entries i = 0 .. c-1, node v_i at position p_i:
+ *   votes      cnt[b][j] = the number of entries i with p_i <= j < p_i + len[v_i] whose base j - p_i is b.  The dovetail check of the unitig
+ *              call guarantees that every column is covered; even nodes vote with their own rows, as step 8 reads them.
+ *   base       of column j: the smallest b with the largest cnt[b][j] (std::max_element over A, C, G, T = 0 .. 3); votes[j] = that count.
+ *   window     first / last = the first / last column with votes[j] > min_votes (the reference: 3; 0: nothing is trimmed; negative:
+ *              ALGA_ERR_INVALID_ARGUMENT): d_trim_left[k] = first, d_len[k] = last - first + 1; no such column: both 0.
+ *   output     d_words: the UNTRIMMED consensus in exactly the ragged layout of u.d_words (same d_word_off, tail bits zero) -- the trimmed
+ *              sequence is a window of it, there is no second copy, and the link overlaps of the unitig graph stay valid for it;
+ *              d_changed[k]: the columns of the whole unitig where the consensus differs from the spelled base; with ALGA_CONSENSUS_VOTES
+ *              d_votes: one byte per column at index 16 * d_word_off[k] + j, saturated at 255 (no count saturates before the vote: a word
+ *              of 16 columns that more than 255 entries cover is counted by a second kernel with 32-bit counters, `wide_words`).
+ * Checks, on the device, nothing written on refusal (ALGA_ERR_INVALID_ARGUMENT): `u` is not the engine's last unitig result, nodes->n is odd or
+ * not the n of that call, a path node is >= n, a length does not fit the rows or the layout of `u`.
+ * The result is engine-owned device memory, valid until the next alga_unitig_consensus_device or alga_unitigs_device call on `e`. */
+#define ALGA_CONSENSUS_VOTES 1
+typedef struct {
+    int32_t         n_pairs;       /* u.n_pairs                                                                                      */
+    const uint32_t *d_words;       /* the untrimmed consensus sequences, laid out by u.d_word_off                                    */
+    const int32_t  *d_trim_left;   /* n_pairs: first column of the window                                                            */
+    const int32_t  *d_len;         /* n_pairs: length of the window (0: no column has more than min_votes votes)                     */
+    const int32_t  *d_changed;     /* n_pairs: columns that differ from the spelled sequence                                         */
+    const uint8_t  *d_votes;       /* ALGA_CONSENSUS_VOTES: 16 * total words bytes, else NULL                                        */
+} alga_consensus;
+typedef struct {
+    uint64_t pairs, pairs_kept;    /* pairs / pairs with d_len > 0                                                                   */
+    uint64_t columns;              /* sum of the unitigs' lengths                                                                    */
+    uint64_t trimmed_bases;        /* sum of d_len                                                                                   */
+    uint64_t changed;              /* sum of d_changed                                                                               */
+    uint64_t max_depth;            /* the largest number of path entries that cover (part of) one 16-column word                     */
+    uint64_t wide_words;           /* words that more than 255 entries cover (counted with 32-bit counters)                          */
+    double   ms_vote, ms_window, ms_total;   /* device time of the checks and votes / of the windows (HIP events), wall time of the call */
+} alga_consensus_info;
+int  alga_unitig_consensus_device(alga_engine *e, const alga_nodes *nodes, const alga_unitigs *u, int32_t min_votes, int32_t flags, void *hip_stream,
+                                  alga_consensus *out, alga_consensus_info *info /* may be NULL */);
+/* The windows as FASTA through the chunk pipeline of alga_write_gfa_device: in pair order, for every pair with d_len[k] >= min_length and
+ * d_len[k] > 0, the record `>unitig_<k>_length=<d_len[k]>\n<ACGT of the window>\n` (the sequence on one line, as OutputWriterNew::writeContig
+ * writes it).  `u` / `cons` must be the last unitig / consensus results on `e`.  info: segments = records written, bytes = size of the file.
+ * No pair selected: an empty file.  On an error the partial file is removed. */
+int  alga_write_consensus_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const char *path, int32_t min_length,
+                                       alga_gfa_info *info /* may be NULL */);
 
 #ifdef __cplusplus
 }
