@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "contig_kernels.h"
 #include "gfa_kernels.h"
 #include "simplify_kernels.h"
 
@@ -229,5 +230,16 @@ extern "C" int alga_write_consensus_fasta_device(alga_engine *e, const alga_unit
     GfaCfg c{cons->d_words, 0, cons->d_len, u->n_pairs, nullptr, 0, (uint64_t) u->n_pairs, 0, 1};
     c.row_off = (const unsigned long long *) u->d_word_off;
     c.fasta = 1; c.min_length = min_length; c.seq_off = cons->d_trim_left;
+    if (e->ut_is_contig) {                                           // the records are numbered as they are written: a scan of the selection
+        const uint64_t P = (uint64_t) u->n_pairs;
+        int rc;
+        if ((rc = alga_ensure(e, e->ct_names, (size_t) (2 * P + 4) * sizeof(uint32_t)))) return rc;
+        if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(P)))) return rc;
+        uint32_t *sel = (uint32_t *) e->ct_names.p, *rank = sel + P + 1;
+        launch_ct_fasta_select(cons->d_len, P, min_length, sel, e->own_stream);
+        launch_exclusive_scan(sel, P, rank, (uint64_t *) e->scan_scratch.p, e->own_stream);
+        if ((rc = alga_check_launch(e, "scan(fasta records)"))) return rc;
+        c.rec_rank = rank;
+    }
     return gfa_run(e, c, path, info, t0);
 }

@@ -142,6 +142,13 @@ struct alga_engine {
     bool        ut_valid = false;
     int32_t     ut_n_nodes = 0;                    // ... the n of the node set it was made from, the sum of its lengths
     uint64_t    ut_total_bases = 0;
+    bool        ut_is_contig = false;              // the result at hand came from alga_contigs_device (the FASTA names its records contig_id=<j>)
+    // contigs (engine_contig.hip): counters, the base graph B of a round (two buffers in turn) and its row pointers, P flags, per-run smallest read
+    // index, the chain records and the chain that enters every run, drop marks, flags and their scan, the group sort, the per-group best
+    // (weight, key), H with the triangle cut's workspaces, and for the contig graph: winners, pair numbers, oriented ids, their chains, degrees,
+    // the edge sort
+    DevBuf      ct_cnt, ct_B[2], ct_rowptr, ct_pflag, ct_runkey, ct_chain, ct_headchain, ct_drop, ct_flag, ct_pos, ct_keys[2], ct_vals[2], ct_hw, ct_hk, ct_H,
+                ct_hrow, ct_hsorted, ct_hlist, ct_hcnt, ct_win, ct_pair, ct_oid, ct_cid, ct_deg, ct_epos, ct_ekeys[2], ct_evals[2], ct_names;
     // consensus of the unitigs (engine_consensus.hip): counters, the sequences, the per-word column masks, the vote bytes, per-pair window / changed
     DevBuf      cs_cnt, cs_words, cs_mask, cs_votes, cs_trim, cs_len, cs_changed;
     bool        cs_valid = false;                  // the buffers hold the consensus of the unitig result at hand
@@ -258,6 +265,15 @@ int  alga_staged_d2h(alga_engine *e, void *h_dst, const void *d_src, size_t byte
 void alga_staging_release(alga_engine *e);
 void *alga_host_list_take(alga_engine *e, size_t bytes);
 void alga_host_list_give(alga_engine *e, void *p);
+
+// engine_unitig.hip, shared with engine_contig.hip: the device's verdict on a node set and edge list (unitig step 1), E* with its row pointers
+// (step 2, into ut_estar / ut_rowptr), and the list ranking along nxt[] in both forms with the cycle-minimum jump (records: ut_rank[cur]).
+// cnt: UT_COUNTERS + ALGA_UT_MAX_ROUNDS zeroed 64-bit words; a ranking uses one word per jump round from cnt[UT_COUNTERS + rounds] on.
+constexpr int ALGA_UT_MAX_ROUNDS = 112;            // three ranking phases (rulers, nodes, nodes after the cuts) of at most 34 rounds each
+int alga_ut_check(alga_engine *e, const alga_nodes *nodes, const alga::alga_edge_dev *d_in, uint64_t m, unsigned long long *cnt, hipStream_t s);
+int alga_ut_estar(alga_engine *e, const alga_nodes *nodes, const alga::alga_edge_dev *d_in, uint64_t m, unsigned long long *cnt, hipStream_t s, uint64_t *ms_out);
+int alga_ut_rank(alga_engine *e, const int32_t *len, int32_t n, int32_t *nxt, const int32_t *noff, int32_t *prv, unsigned long long *cnt, uint32_t *p_flag,
+                 int &cur, int &rounds, hipStream_t s);
 
 inline int alga_check_launch(alga_engine *e, const char *what) {
     hipError_t err = hipGetLastError();

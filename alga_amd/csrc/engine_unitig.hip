@@ -11,13 +11,12 @@
 #include "engine_internal.h"
 #include "gfa_kernels.h"
 #include "simplify_kernels.h"
+#include "contig_kernels.h"
 #include "unitig_kernels.h"
 
 using namespace alga;
 
 namespace {
-
-constexpr int UT_MAX_ROUNDS = 112;                                  // three ranking phases (rulers, nodes, nodes after the cuts) of at most 34 rounds each
 
 struct UtEvents {
     hipEvent_t ev[6] = {};
@@ -42,7 +41,7 @@ int rank_rounds(alga_engine *e, DevBuf *buf, int32_t n, unsigned long long *cnt,
     int rc;
     open = 0;
     for (int k = 0; k < 34; k++) {
-        if (rounds >= UT_MAX_ROUNDS) return alga_fail(e, ALGA_ERR_HIP, "unitigs: the list ranking did not settle");
+        if (rounds >= ALGA_UT_MAX_ROUNDS) return alga_fail(e, ALGA_ERR_HIP, "unitigs: the list ranking did not settle");
         unsigned long long *slot = cnt + UT_COUNTERS + rounds;
         launch_ut_rank_jump((const UtRank *) buf[cur].p, (UtRank *) buf[cur ^ 1].p, n, slot, s);
         if ((rc = alga_check_launch(e, "k_ut_rank_jump"))) return rc;
@@ -55,19 +54,12 @@ int rank_rounds(alga_engine *e, DevBuf *buf, int32_t n, unsigned long long *cnt,
     return ALGA_OK;
 }
 
-int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d_in, uint64_t m, int32_t flags, hipStream_t s, alga_unitigs *out,
-                 alga_unitig_info *info) {
-    const int32_t n = nodes->n;
-    const uint64_t m2 = 2 * m;
+}  // namespace
+
+// step 1 (shared with engine_contig.hip): the device's verdict on the input; nothing but cnt[] is written
+int alga_ut_check(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d_in, uint64_t m, unsigned long long *cnt, hipStream_t s) {
     int rc;
-    UtEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
-    const size_t n_cnt = UT_COUNTERS + UT_MAX_ROUNDS;
-    if ((rc = alga_ensure(e, e->ut_cnt, n_cnt * sizeof(unsigned long long)))) return rc;
-    unsigned long long *cnt = (unsigned long long *) e->ut_cnt.p;
-    HIP_TRY(e, hipMemsetAsync(cnt, 0, n_cnt * sizeof(unsigned long long), s));
-    HIP_TRY(e, hipEventRecord(evs.ev[0], s));
-    launch_ut_check(nodes->len, n, d_in, m, cnt, s);
+    launch_ut_check(nodes->len, nodes->n, d_in, m, cnt, s);
     if ((rc = alga_check_launch(e, "k_ut_check"))) return rc;
     if ((rc = read_u64(e, cnt, 1, s))) return rc;
     if (const unsigned long long bad = e->h_counters[UT_FLAGS]) {
@@ -76,37 +68,29 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
                         : "edge is not a dovetail: 0 <= offset < len[src] and offset + len[dst] >= len[src]";
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
     }
-    // the input is valid: from here on the previous result's buffers are rewritten
-    e->ut_valid = false; e->cs_valid = false;
+    return ALGA_OK;
+}
+
+// step 2 (shared): E* in ut_estar, its row pointers in ut_rowptr; the sort buffers, flags and scan positions are sized for 2 m records
+int alga_ut_estar(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d_in, uint64_t m, unsigned long long *cnt, hipStream_t s, uint64_t *ms_out) {
+    const int32_t n = nodes->n;
+    const uint64_t m2 = 2 * m;
     const size_t N = (size_t) n;
+    int rc;
     for (int k = 0; k < 2; k++) {
         if ((rc = alga_ensure(e, e->ut_keys[k], (size_t) (m2 + 1) * sizeof(unsigned long long)))) return rc;
         if ((rc = alga_ensure(e, e->ut_vals[k], (size_t) (m2 + 1) * sizeof(uint32_t)))) return rc;
-        if ((rc = alga_ensure(e, e->ut_rank[k], (N + 1) * sizeof(UtRank)))) return rc;
     }
     if ((rc = alga_ensure(e, e->ut_flag, (size_t) (m2 + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->ut_pos, (size_t) (m2 + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->ut_best, (size_t) (m2 + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->ut_estar, (size_t) (m2 + 1) * sizeof(alga_edge_dev)))) return rc;
     if ((rc = alga_ensure(e, e->ut_rowptr, (N + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_nxt, (N + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_noff, (N + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_prv, (N + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_tail, (N + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_win, (N + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_pair, (N + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_uid, (N + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_path_node, (N + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->ut_path_pos, (N + 1) * sizeof(int32_t)))) return rc;
     if ((rc = alga_ensure(e, e->sort_temp, sort_edges_temp_bytes(m2)))) return rc;
     if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(std::max<uint64_t>(m2, N))))) return rc;
     unsigned long long *keys0 = (unsigned long long *) e->ut_keys[0].p, *keys1 = (unsigned long long *) e->ut_keys[1].p;
     uint32_t *vals0 = (uint32_t *) e->ut_vals[0].p, *vals1 = (uint32_t *) e->ut_vals[1].p;
-    uint32_t *flag = (uint32_t *) e->ut_flag.p, *pos = (uint32_t *) e->ut_pos.p, *rowptr = (uint32_t *) e->ut_rowptr.p;
-    alga_edge_dev *estar = (alga_edge_dev *) e->ut_estar.p;
-    int32_t *nxt = (int32_t *) e->ut_nxt.p, *noff = (int32_t *) e->ut_noff.p, *prv = (int32_t *) e->ut_prv.p, *tail = (int32_t *) e->ut_tail.p;
-
-    // ---- E*: twins, sort, the smallest offset per (src, dst), row pointers
+    uint32_t *flag = (uint32_t *) e->ut_flag.p, *pos = (uint32_t *) e->ut_pos.p;
     int node_bits = 1;
     while (node_bits < 31 && (1ll << node_bits) < (long long) n) node_bits++;
     launch_ut_twins(nodes->len, d_in, m, keys0, vals0, s);
@@ -118,18 +102,23 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
     if ((rc = alga_check_launch(e, "scan(group heads)"))) return rc;
     uint64_t ms = 0;
     if ((rc = read_u32(e, pos + m2, s, &ms))) return rc;
-    launch_ut_compact_edges(keys1, flag, pos, (const uint32_t *) e->ut_best.p, m2, estar, s);
+    launch_ut_compact_edges(keys1, flag, pos, (const uint32_t *) e->ut_best.p, m2, (alga_edge_dev *) e->ut_estar.p, s);
     if ((rc = alga_check_launch(e, "k_ut_compact_edges"))) return rc;
-    launch_edge_rowptr(estar, ms, n, rowptr, s);
+    launch_edge_rowptr((const alga_edge_dev *) e->ut_estar.p, ms, n, (uint32_t *) e->ut_rowptr.p, s);
     if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
-    HIP_TRY(e, hipEventRecord(evs.ev[1], s));
+    *ms_out = ms;
+    return ALGA_OK;
+}
 
-    // ---- next / prev, list ranking, cycles
-    launch_ut_next(estar, rowptr, n, nxt, noff, s);
-    launch_ut_prev(nxt, n, prv, s);
-    int cur = 0, rounds = 0;
+// the list ranking along nxt[] / prv[] (shared), in both forms, with the cycle-minimum jump for what stays unresolved.  p_flag == nullptr: the
+// unitig cut (step 4); else the contig form: m and m^1 leave P (k_ct_open_cycles).  Records: e->ut_rank[cur]; ut_win / ut_pair are scratch.
+int alga_ut_rank(alga_engine *e, const int32_t *len, int32_t n, int32_t *nxt, const int32_t *noff, int32_t *prv, unsigned long long *cnt, uint32_t *p_flag,
+                 int &cur, int &rounds, hipStream_t s) {
+    const size_t N = (size_t) n;
+    int rc;
+    cur = 0;
     uint64_t open = 0;
-    launch_ut_rank_init(nodes->len, prv, noff, n, 0, (UtRank *) e->ut_rank[0].p, s);
+    launch_ut_rank_init(len, prv, noff, n, 0, (UtRank *) e->ut_rank[0].p, s);
     if ((rc = alga_check_launch(e, "k_ut_rank_init"))) return rc;
     const bool ruling = e->opt_unitig_ruling < 0 ? n >= (1 << 16) : e->opt_unitig_ruling != 0;
     if (ruling && n > 0) {
@@ -137,7 +126,7 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
         // and the rounds below find nothing left to do unless there are cycles
         uint32_t *rflag = (uint32_t *) e->ut_win.p, *ridx = (uint32_t *) e->ut_pair.p;         // (free until the numbering)
         if ((rc = alga_ensure(e, e->ut_link, (N + 1) * sizeof(int2)))) return rc;
-        launch_ut_ruler_flags(nodes->len, prv, n, rflag, s);
+        launch_ut_ruler_flags(len, prv, n, rflag, s);
         launch_ut_links(nxt, noff, n, (int2 *) e->ut_link.p, s);
         launch_exclusive_scan(rflag, (uint64_t) n, ridx, (uint64_t *) e->scan_scratch.p, s);
         if ((rc = alga_check_launch(e, "scan(rulers)"))) return rc;
@@ -161,12 +150,59 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
         while (jumps < 34 && (1ull << (jumps - 1)) < open) jumps++;  // 2^jumps >= 2 * open: every node has seen its whole cycle
         launch_ut_min_init(r, prv, n, (UtMin *) e->ut_min[0].p, s);
         for (int k = 0; k < jumps; k++) { launch_ut_min_jump(r, (const UtMin *) e->ut_min[mc].p, (UtMin *) e->ut_min[mc ^ 1].p, n, s); mc ^= 1; }
-        launch_ut_cut(r, (const UtMin *) e->ut_min[mc].p, n, nxt, prv, cnt, s);
-        launch_ut_rank_init(nodes->len, prv, noff, n, 1, (UtRank *) e->ut_rank[cur].p, s);
+        if (p_flag) launch_ct_open_cycles(r, (const UtMin *) e->ut_min[mc].p, n, nxt, prv, p_flag, cnt, s);
+        else launch_ut_cut(r, (const UtMin *) e->ut_min[mc].p, n, nxt, prv, cnt, s);
+        launch_ut_rank_init(len, prv, noff, n, 1, (UtRank *) e->ut_rank[cur].p, s);
         if ((rc = alga_check_launch(e, "unitig cycle cuts"))) return rc;
         if ((rc = rank_rounds(e, e->ut_rank, n, cnt, cur, rounds, open, s))) return rc;
         if (open) return alga_fail(e, ALGA_ERR_HIP, "unitigs: nodes left unranked after the cycle cuts");
     }
+    return ALGA_OK;
+}
+
+namespace {
+
+int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d_in, uint64_t m, int32_t flags, hipStream_t s, alga_unitigs *out,
+                 alga_unitig_info *info) {
+    const int32_t n = nodes->n;
+    const uint64_t m2 = 2 * m;
+    int rc;
+    UtEvents evs;
+    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    const size_t n_cnt = UT_COUNTERS + ALGA_UT_MAX_ROUNDS;
+    if ((rc = alga_ensure(e, e->ut_cnt, n_cnt * sizeof(unsigned long long)))) return rc;
+    unsigned long long *cnt = (unsigned long long *) e->ut_cnt.p;
+    HIP_TRY(e, hipMemsetAsync(cnt, 0, n_cnt * sizeof(unsigned long long), s));
+    HIP_TRY(e, hipEventRecord(evs.ev[0], s));
+    if ((rc = alga_ut_check(e, nodes, d_in, m, cnt, s))) return rc;
+    // the input is valid: from here on the previous result's buffers are rewritten
+    e->ut_valid = false; e->cs_valid = false; e->ut_is_contig = false;
+    const size_t N = (size_t) n;
+    for (int k = 0; k < 2; k++) if ((rc = alga_ensure(e, e->ut_rank[k], (N + 1) * sizeof(UtRank)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_nxt, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_noff, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_prv, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_tail, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_win, (N + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_pair, (N + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_uid, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_path_node, (N + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = alga_ensure(e, e->ut_path_pos, (N + 1) * sizeof(int32_t)))) return rc;
+    // ---- E*: twins, sort, the smallest offset per (src, dst), row pointers
+    uint64_t ms = 0;
+    if ((rc = alga_ut_estar(e, nodes, d_in, m, cnt, s, &ms))) return rc;
+    unsigned long long *keys0 = (unsigned long long *) e->ut_keys[0].p, *keys1 = (unsigned long long *) e->ut_keys[1].p;
+    uint32_t *vals0 = (uint32_t *) e->ut_vals[0].p, *vals1 = (uint32_t *) e->ut_vals[1].p;
+    uint32_t *flag = (uint32_t *) e->ut_flag.p, *pos = (uint32_t *) e->ut_pos.p, *rowptr = (uint32_t *) e->ut_rowptr.p;
+    alga_edge_dev *estar = (alga_edge_dev *) e->ut_estar.p;
+    int32_t *nxt = (int32_t *) e->ut_nxt.p, *noff = (int32_t *) e->ut_noff.p, *prv = (int32_t *) e->ut_prv.p, *tail = (int32_t *) e->ut_tail.p;
+    HIP_TRY(e, hipEventRecord(evs.ev[1], s));
+
+    // ---- next / prev, list ranking, cycles
+    launch_ut_next(estar, rowptr, n, nxt, noff, s);
+    launch_ut_prev(nxt, n, prv, s);
+    int cur = 0, rounds = 0;
+    if ((rc = alga_ut_rank(e, nodes->len, n, nxt, noff, prv, cnt, nullptr, cur, rounds, s))) return rc;
     const UtRank *r = (const UtRank *) e->ut_rank[cur].p;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 

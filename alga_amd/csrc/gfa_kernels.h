@@ -23,6 +23,8 @@ struct GfaCfg {
     // `>unitig_<j>_length=<len[j]>\n<bases seq_off[j] .. seq_off[j] + len[j] of its row>\n`, written when len[j] >= min_length and len[j] > 0
     int32_t fasta = 0, min_length = 0;
     const int32_t *seq_off = nullptr;
+    // optional, FASTA only: the records of a contig result, `>contig_id=<rec_rank[j]>_length=<len[j]>` (rec_rank[j] = records written before item j)
+    const uint32_t *rec_rank = nullptr;
     __host__ __device__ __forceinline__ const uint32_t *row(uint64_t node) const {
         return row_off ? words + row_off[twins ? node >> 1 : node] : words + node * (uint64_t) stride;
     }

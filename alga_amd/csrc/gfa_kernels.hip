@@ -63,9 +63,9 @@ __device__ __forceinline__ uint64_t seg_line_bytes(uint64_t name, int32_t L, int
     return L > 0 ? 2 + dec_width(name) + 1 + (seqs ? (uint64_t) L : 1) + 6 + dec_width((uint64_t) L) + 1 : 0;
 }
 
-// > unitig_ name _length= len \n seq \n
-__device__ __forceinline__ uint64_t fasta_record_bytes(uint64_t name, int32_t L, int32_t min_length) {
-    return L > 0 && L >= min_length ? 8 + dec_width(name) + 8 + dec_width((uint64_t) L) + 1 + (uint64_t) L + 1 : 0;
+// > unitig_ name _length= len \n seq \n  (prefix: 8 bytes, or the 11 of ">contig_id=")
+__device__ __forceinline__ uint64_t fasta_record_bytes(uint64_t name, int32_t L, int32_t min_length, uint32_t prefix) {
+    return L > 0 && L >= min_length ? prefix + dec_width(name) + 8 + dec_width((uint64_t) L) + 1 + (uint64_t) L + 1 : 0;
 }
 
 __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_check(GfaCfg c, unsigned long long *__restrict__ counters) {
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_sizes(GfaCfg c, uint32_t 
     unsigned long long live = 0, bytes = 0;
     if (j < c.n_seg) {
         const int32_t L = c.len[c.twins ? 2 * j + 1 : j];
-        bytes = c.fasta ? fasta_record_bytes(j, L, c.min_length) : seg_line_bytes(j, L, c.seqs);
+        bytes = c.fasta ? fasta_record_bytes(c.rec_rank ? c.rec_rank[j] : j, L, c.min_length, c.rec_rank ? 11u : 8u) : seg_line_bytes(j, L, c.seqs);
         live = bytes > 0;
         sizes[j] = (uint32_t) bytes;
     }
@@ -220,7 +220,8 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_bounds(const unsigned long lo
 }
 
 // byte p of a segment line: "S\t" name "\t" seq "\tLN:i:" len "\n"; of a FASTA record: ">unitig_" name "_length=" len "\n" seq "\n"
-struct SegLine {
+// CONTIG: the FASTA of a contig result (">contig_id=" and the record's rank as its name); false: the code as it was before that form existed
+template <bool CONTIG> struct SegLine {
     uint64_t name; int32_t L; int wn, wl; uint32_t hp, sl;           // hp = bytes before the sequence, sl = bytes of the sequence field
     const uint32_t *row; int seqs;
     int fasta; uint32_t q0;                                           // FASTA: the sequence starts at base q0 of the row
@@ -228,10 +229,11 @@ struct SegLine {
     __device__ __forceinline__ char base(uint32_t q) const { q += q0; return (char) ((0x54474341u >> (8 * ((row[q >> 4] >> (2 * (q & 15))) & 3))) & 0xFF); }
     __device__ char at(uint32_t p) const {
         if (fasta) {
-            if (p < 8) return ">unitig_"[p];
-            if (p < 8u + wn) return digit(name, wn, (int) p - 8);
-            if (p < 16u + wn) return "_length="[p - 8 - wn];
-            if (p + 1 < hp) return digit((uint64_t) L, wl, (int) (p - 16 - wn));
+            constexpr uint32_t fp = CONTIG ? 11u : 8u;
+            if (p < fp) return CONTIG ? ">contig_id="[p] : ">unitig_"[p];
+            if (p < fp + wn) return digit(name, wn, (int) (p - fp));
+            if (p < fp + 8u + wn) return "_length="[p - fp - wn];
+            if (p + 1 < hp) return digit((uint64_t) L, wl, (int) (p - fp - 8 - wn));
             if (p < hp) return '\n';
             return p - hp < sl ? base(p - hp) : '\n';
         }
@@ -261,7 +263,7 @@ struct SegLine {
 };
 
 // one wave per segment item in [i0, i1) (items below n_seg); buf + off[j] - base is the line's first byte
-__global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
+template <bool CONTIG> __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
                                                              char *__restrict__ buf) {
     const int lane = threadIdx.x & 63;
     const uint64_t base = off[i0];
@@ -270,9 +272,9 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const uns
         const uint64_t l0 = off[j], l1 = off[j + 1];
         if (l0 == l1) continue;
         const uint64_t node = c.twins ? 2 * j + 1 : j;
-        SegLine s;
-        s.name = j; s.L = c.len[node]; s.wn = dec_width(j); s.wl = dec_width((uint64_t) s.L);
-        s.hp = c.fasta ? 8 + s.wn + 8 + s.wl + 1 : 2 + s.wn + 1; s.sl = c.seqs ? (uint32_t) s.L : 1u;
+        SegLine<CONTIG> s;
+        s.name = CONTIG ? c.rec_rank[j] : j; s.L = c.len[node]; s.wn = dec_width(s.name); s.wl = dec_width((uint64_t) s.L);
+        s.hp = c.fasta ? (CONTIG ? 11 : 8) + s.wn + 8 + s.wl + 1 : 2 + s.wn + 1; s.sl = c.seqs ? (uint32_t) s.L : 1u;
         s.row = c.row(node); s.seqs = c.seqs;
         s.fasta = c.fasta; s.q0 = c.fasta ? (uint32_t) c.seq_off[j] : 0u;
         char *g0 = buf + (l0 - base), *g1 = buf + (l1 - base);
@@ -354,7 +356,8 @@ void launch_gfa_format(const GfaCfg &c, const unsigned long long *off, uint64_t 
     const uint64_t s1 = i1 < c.n_seg ? i1 : c.n_seg;
     if (i0 < s1) {
         const uint64_t g = grid_of(s1 - i0, GFA_BLOCK / 64);
-        hipLaunchKernelGGL(k_gfa_seg_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
+        if (c.fasta && c.rec_rank) hipLaunchKernelGGL(k_gfa_seg_write<true>, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
+        else hipLaunchKernelGGL(k_gfa_seg_write<false>, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
     }
     const uint64_t l0 = i0 > c.n_seg ? i0 : c.n_seg;
     if (l0 < i1) {

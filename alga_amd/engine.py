@@ -159,7 +159,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
            "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
-           "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device"]
+           "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device",
+           "alga_contigs_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -221,6 +222,24 @@ class UnitigInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+CONTIG_MAX_ROUNDS = 64
+
+
+class ContigInfo(C.Structure):
+    """alga_contig_info"""
+    _PER_ROUND = ("chains", "parallel_drops", "groups_cut", "base_edges_dropped")
+    _fields_ = [(k, C.c_uint64) for k in ("edges_in", "edges_sym", "rounds")] + [(k, C.c_uint64 * CONTIG_MAX_ROUNDS) for k in _PER_ROUND] + \
+               [(k, C.c_uint64) for k in ("final_edges", "path_nodes", "junction_nodes", "cycles_cut", "closed_chains", "reads_dropped", "longest_nodes",
+                                          "longest_bases", "total_bases")] + [("rank_rounds", C.c_int32)] + \
+               [(k, C.c_double) for k in ("ms_sym", "ms_rounds", "ms_layout", "ms_seq", "ms_edges", "ms_total")]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in self._PER_ROUND}
+        for k in self._PER_ROUND:
+            d[k] = list(getattr(self, k))[: min(int(self.rounds), CONTIG_MAX_ROUNDS)]
+        return d
 
 
 class Unitigs:
@@ -408,6 +427,8 @@ def load_library():
                                                             C.POINTER(C.c_uint64), C.POINTER(MstInfo)]
     lib.alga_unitigs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(UnitigsC),
                                         C.POINTER(UnitigInfo)]
+    lib.alga_contigs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(UnitigsC),
+                                        C.POINTER(ContigInfo)]
     lib.alga_write_unitig_gfa_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
     lib.alga_unitig_consensus_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(UnitigsC), C.c_int32, C.c_int32, C.c_void_p,
                                                  C.POINTER(ConsensusC), C.POINTER(ConsensusInfo)]
@@ -1064,6 +1085,41 @@ class Engine:
         nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 else 1, _ptr(lens), n, None, None)
         out, info = UnitigsC(), UnitigInfo()
         self._check(self._lib.alga_unitigs_device(self._h, C.byref(nd), C.c_void_p(ptr or None), C.c_uint64(m), UNITIG_SKIP_ISOLATED if skip_isolated else 0,
+                                                  None, C.byref(out), C.byref(info)))
+        del keep
+        return Unitigs(out, info.as_dict(), self.device)
+
+    def contigs(self, words, lens, edges, max_offset, n_edges=None, stream=None):
+        """The contigs (alga_contigs_device: contract, cut the contracted graph at max_offset, contract again; the definition is in
+        include/alga_amd.h) -> Unitigs, with .info a dict of alga_contig_info.  The result becomes the engine's current unitig result:
+        unitig_consensus, write_unitig_gfa and write_consensus_fasta take it (the FASTA then names its records contig_id=<j>).
+        words [n, stride] / lens [n]: the node set in the twin layout as torch device tensors (numpy arrays are uploaded first); edges: a
+        device pointer (with n_edges), an int32 device tensor [m, 3] or a numpy array [m, 3] (uploaded), in any order.
+        stream: the stream that produced the inputs, synchronised first (the call runs on the engine's own stream)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(words, np.ndarray):
+            words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(dev)
+        if isinstance(lens, np.ndarray):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+        keep = None
+        if isinstance(edges, np.ndarray):
+            e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)
+            keep = torch.from_numpy(e).to(dev)
+            ptr, m = _ptr(keep), len(e)
+        elif isinstance(edges, int):
+            ptr, m = edges, int(n_edges or 0)
+        else:
+            keep = edges
+            ptr, m = _ptr(edges), int(edges.shape[0]) if n_edges is None else int(n_edges)
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        n = int(lens.shape[0])
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 else 1, _ptr(lens), n, None, None)
+        out, info = UnitigsC(), ContigInfo()
+        self._check(self._lib.alga_contigs_device(self._h, C.byref(nd), C.c_void_p(ptr or None), C.c_uint64(m), int(max_offset), 0,
                                                   None, C.byref(out), C.byref(info)))
         del keep
         return Unitigs(out, info.as_dict(), self.device)

@@ -4,6 +4,7 @@
 //            [--serialize=1] [-l MINOVERLAP] [--rsoemo=N] [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1]
 //            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1]
 //            [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200] [--consensus_min_votes=3]
+//            [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -35,6 +36,11 @@
 // column with more than --consensus_min_votes votes -- Contig::correctSnipsInContig, whose THR is 3), written as FASTA for the windows of at
 // least --consensus_min_length bases (alga_write_consensus_fasta_device).  --unitigs= still writes the spelled sequences.  None of the three
 // options is passed through; every invocation without --consensus= behaves as before.
+// --contigs=PATH: the same chain up to the clip (it honours --parallel_paths and --clip_tips), then the contigs (alga_contigs_device: contract, cut the
+// contracted graph with the cut's own bound, contract again), their consensus with --consensus_min_votes, written as FASTA with the reference's
+// record names (`>contig_id=<j>_length=<len>`) for the windows of at least --contigs_min_length bases (default max(200, int(1.75 * LEN)),
+// src/main.cpp:94); --contigs_gfa=PATH beside it: the contig graph with the spelled sequences.  No stock binary (--alga=) is needed for these
+// contigs.  None of the three options is passed through; every invocation without them behaves as before.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -59,10 +65,10 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 int main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    std::string file1, file2, output, alga_exe, gfa, unitigs, consensus, v;
+    std::string file1, file2, output, alga_exe, gfa, unitigs, consensus, contigs, contigs_gfa, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
-    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3;
+    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1;
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -88,6 +94,9 @@ int main(int argc, char **argv) {
         else if (opt(a, "--clip_tips", v)) clip_tips = atoi(v.c_str());
         else if (opt(a, "--parallel_paths", v)) parallel_paths = atoi(v.c_str());
         else if (opt(a, "--consensus", v)) consensus = v;
+        else if (opt(a, "--contigs", v)) contigs = v;
+        else if (opt(a, "--contigs_gfa", v)) contigs_gfa = v;
+        else if (opt(a, "--contigs_min_length", v)) contigs_min_length = atoi(v.c_str());
         else if (opt(a, "--consensus_min_length", v)) consensus_min_length = atoi(v.c_str());
         else if (opt(a, "--consensus_min_votes", v)) consensus_min_votes = atoi(v.c_str());
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
@@ -97,7 +106,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -232,7 +241,8 @@ int main(int argc, char **argv) {
     std::vector<alga_edge> final_edges((size_t) n_final);
     if (n_final && alga_copy_to_host(engine, final_edges.data(), d_final, final_edges.size() * sizeof(alga_edge)) != ALGA_OK) { fprintf(stderr, "alga_amd: cannot read the edges back\n"); return 1; }
     fprintf(stderr, "Before first simplifier graph has %llu edges\n", (unsigned long long) n_final);
-    if (!unitigs.empty() || !consensus.empty()) {                              // the edges are on the host already: nothing below touches what is handed on
+    const bool want_unitigs = !unitigs.empty() || !consensus.empty();
+    if (want_unitigs || !contigs.empty()) {                                    // the edges are on the host already: nothing below touches what is handed on
         alga_nodes nd{nodes.d_words, nodes.stride_words, nodes.d_len, nodes.n, nullptr, nullptr};
         const int mopp = std::max(250, (int) (1.75 * parsed.LEN));            // Params::MAX_OFFSET_PARALLEL_PATHS, src/main.cpp:95
         const alga_edge *d_cut = nullptr;
@@ -275,9 +285,9 @@ int main(int argc, char **argv) {
                         ti.ms_passes, ti.ms_total);
             }
         }
-        if (rc == ALGA_OK) rc = alga_unitigs_device(engine, &nd, d_cut, n_cut, ALGA_UNITIG_SKIP_ISOLATED, nullptr, &u, &ui);
+        if (rc == ALGA_OK && want_unitigs) rc = alga_unitigs_device(engine, &nd, d_cut, n_cut, ALGA_UNITIG_SKIP_ISOLATED, nullptr, &u, &ui);
         std::vector<int32_t> ul;
-        if (rc == ALGA_OK) { ul.resize((size_t) u.n_pairs); if (u.n_pairs) rc = alga_copy_to_host(engine, ul.data(), u.d_len, ul.size() * sizeof(int32_t)); }
+        if (rc == ALGA_OK && want_unitigs) { ul.resize((size_t) u.n_pairs); if (u.n_pairs) rc = alga_copy_to_host(engine, ul.data(), u.d_len, ul.size() * sizeof(int32_t)); }
         if (rc == ALGA_OK && !unitigs.empty()) rc = alga_write_unitig_gfa_device(engine, &u, unitigs.c_str(), ALGA_GFA_SEQUENCES, &gi);
         if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", (unitigs.empty() ? consensus : unitigs).c_str(), alga_last_error(engine), rc); return 1; }
         if (!consensus.empty()) {
@@ -302,6 +312,28 @@ int main(int argc, char **argv) {
                 unitigs.c_str(), u.n_pairs, (unsigned long long) gi.links, (unsigned long long) ui.longest_bases, (unsigned long long) ui.longest_nodes, n50,
                 (unsigned long long) ui.total_bases, (unsigned long long) n_removed, (unsigned long long) ui.isolated_skipped, ui.ms_sym, ui.ms_rank, ui.rank_rounds,
                 ui.ms_layout, ui.ms_seq, ui.ms_edges, ui.ms_total, (unsigned long long) gi.bytes, gi.ms_format, gi.ms_total);
+        }
+        if (!contigs.empty()) {                                               // last: the contig result replaces the unitigs on the engine; d_cut stays valid
+            alga_unitigs cu;
+            alga_contig_info ki;
+            alga_consensus cs;
+            alga_consensus_info ci;
+            alga_gfa_info fi, cgi;
+            const int min_len = contigs_min_length >= 0 ? contigs_min_length : std::max(200, (int) (1.75 * parsed.LEN));   // src/main.cpp:94
+            rc = alga_contigs_device(engine, &nd, d_cut, n_cut, mopp, 0, nullptr, &cu, &ki);
+            if (rc == ALGA_OK && !contigs_gfa.empty()) rc = alga_write_unitig_gfa_device(engine, &cu, contigs_gfa.c_str(), ALGA_GFA_SEQUENCES, &cgi);
+            if (rc == ALGA_OK) rc = alga_unitig_consensus_device(engine, &nd, &cu, consensus_min_votes, 0, nullptr, &cs, &ci);
+            if (rc == ALGA_OK) rc = alga_write_consensus_fasta_device(engine, &cu, &cs, contigs.c_str(), min_len, &fi);
+            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", contigs.c_str(), alga_last_error(engine), rc); return 1; }
+            fprintf(stderr, "Contigs written -> %s: %llu records of %d contigs (min length %d), longest %llu nt (%llu reads); %llu rounds, %llu -> %llu edges, %llu reads "
+                    "dropped, %llu path nodes, %llu junction nodes; device ms: edges %.3f rounds %.3f layout %.3f sequences %.3f contig graph %.3f, call %.1f ms "
+                    "wall; consensus %.1f ms wall; FASTA %llu bytes, wall %.1f ms\n", contigs.c_str(), (unsigned long long) fi.segments, cu.n_pairs, min_len,
+                    (unsigned long long) ki.longest_bases, (unsigned long long) ki.longest_nodes, (unsigned long long) ki.rounds, (unsigned long long) ki.edges_sym,
+                    (unsigned long long) ki.final_edges, (unsigned long long) ki.reads_dropped, (unsigned long long) ki.path_nodes, (unsigned long long) ki.junction_nodes,
+                    ki.ms_sym, ki.ms_rounds, ki.ms_layout, ki.ms_seq, ki.ms_edges, ki.ms_total, ci.ms_total, (unsigned long long) fi.bytes, fi.ms_total);
+            if (!contigs_gfa.empty())
+                fprintf(stderr, "Contig graph written -> %s: %llu segments, %llu links, %llu bytes\n", contigs_gfa.c_str(), (unsigned long long) cgi.segments,
+                        (unsigned long long) cgi.links, (unsigned long long) cgi.bytes);
         }
     }
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

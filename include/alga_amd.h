@@ -883,6 +883,64 @@ int  alga_unitig_consensus_device(alga_engine *e, const alga_nodes *nodes, const
 int  alga_write_consensus_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const char *path, int32_t min_length,
                                        alga_gfa_info *info /* may be NULL */);
 
+/* ---- contigs: contract, cut the contracted graph, contract again (alga_amd/csrc/contig_kernels.hip, engine_contig.hip) -------------------------
+ * What the reference does between the simplified graph and its contigs (src/main.cpp:416-419: GraphSimplifier::contractPathNodes, the triangle cut
+ * on the contracted graph, contractPathNodes again; ContigCreatorSinglePath::getContigOmitShortCyclesFrom: one contig per contracted edge, with the
+ * junction reads at both ends), in an order-free, twin-symmetric form.  Input as for alga_unitigs_device, plus `max_offset`: the bound of
+ * alga_cut_triangles_device (the reference: MAX_OFFSET_PARALLEL_PATHS).  The definition (tests/contig_checker.py states it in Python; the device
+ * result equals it array for array):
+ *   1. the checks of unitig step 1; B = E* (unitig step 2).
+ *   2. a round on B, repeated:
+ *      a. P = the nodes with indeg = outdeg = 1 whose one successor and one predecessor are neither the node nor its twin.  A cycle made only of
+ *         P nodes is opened as unitig step 4 chooses: m = the smallest id over the cycle and its twin cycle; m and m^1 count as not in P.
+ *         `cycles_cut` counts a cycle and its twin once (those of the final B).
+ *      b. for every edge a -> b with a not in P the CHAIN is a, b, then the successors while the current node is in P; its end c is the first
+ *         node not in P, its weight w the sum of the offsets.  Every edge of B lies in exactly one chain.  A chain is CLOSED when c is a or a^1;
+ *         closed chains take no part in c. and d.
+ *      c. among the open chains with the same (a, c) the lightest is the REPRESENTATIVE; on a tie the chain whose interior (the nodes between a
+ *         and c) holds the smallest read index v >> 1 wins, a chain without interior loses; if that ties too, all the tied chains are
+ *         representatives.  Every other chain of the group with w <= max_offset is DROPPED; a heavier one stays (Graph::contractPath refuses it).
+ *      d. H holds one edge (a, c, w of the representative) per group.  The survivors are what alga_cut_triangles_device leaves of H at max_offset.
+ *         A group whose H edge goes, or whose twin group's (c^1, a^1) H edge goes, has its representatives DROPPED (with reads of several lengths
+ *         w <= max_offset is not twin-symmetric; this keeps B so).
+ *      e. dropping a chain removes its edges and their twins from B.  Nothing dropped: stop.  Else the next round; there is no cap on the rounds
+ *         and no host fallback (a round that continues removes at least one edge).
+ *   3. the contigs are the chains of the final B, closed ones included.  Of a chain and its twin (the reversed chain of the twin nodes) the one with
+ *      the smaller (first node, second node) is `+`; a chain that is its own twin occurs once.  Pairs are numbered by ascending (first node,
+ *      second node) of `+`; oriented contig 2k+1 = `+` of pair k, 2k = its twin.  Layout, length and spelled sequence follow unitig steps 7-8
+ *      literally (a and c are the first and the last entry; a junction read is in every contig that ends or starts there).  A node without an edge
+ *      in the final B is in no contig; `reads_dropped` counts the nodes that had an edge in E* and have none now.
+ *   4. the contig graph: for oriented contigs X, Y with last node of X == first node of Y the edge (X -> Y, pos of that node in X), sorted by
+ *      (src, dst, offset).  In the GFA the overlap of a link is then the junction read's length.
+ * The result has the alga_unitigs layout and BECOMES the engine's current unitig result: valid until the next alga_unitigs_device or
+ * alga_contigs_device call on `e`; alga_unitig_consensus_device, alga_write_unitig_gfa_device and alga_write_consensus_fasta_device accept it as `u`
+ * (calls made with a real unitig result behave, and write bytes, as before).  The FASTA of a contig result names its records as
+ * OutputWriterNew::writeContigsNoFilter does: `>contig_id=<j>_length=<len>`, j counting the records written; the length rule is unchanged.
+ * `d_edges` may be the engine-owned result of the cut, the clip or the parallel-path step: the call reads it once, into E*, before anything else,
+ * and invalidates no earlier result but the unitigs and their consensus (the cut of H runs the cut's kernel on buffers of this call).
+ * Refusals (ALGA_ERR_INVALID_ARGUMENT, nothing written, the previous result stays valid): where alga_unitigs_device refuses, max_offset < 0, flags != 0.
+ * NOT reproduced (out of scope): filterContigs' share of new reads, the N4 trim of contig ends against each other (alga_contig_trim_host), the
+ * extension by paired connections (markReliablePredecessorsByPairedConnections), the reference's order-dependent replacement of parallel contracted
+ * paths, and its skipped last block in WorkloadManager::parallelBlockExecution.  The ABI number stays 7: the call only adds to the ABI. */
+#define ALGA_CONTIG_MAX_ROUNDS 64
+typedef struct {
+    uint64_t edges_in, edges_sym;  /* edges given / edges of E*                                                                      */
+    uint64_t rounds;               /* rounds run, the last one (which drops nothing) included                                        */
+    uint64_t chains[ALGA_CONTIG_MAX_ROUNDS];              /* per round, the first 64: chains of B (both orientations, closed included) */
+    uint64_t parallel_drops[ALGA_CONTIG_MAX_ROUNDS];      /* ... chains dropped by 2c                                                  */
+    uint64_t groups_cut[ALGA_CONTIG_MAX_ROUNDS];          /* ... groups whose own H edge the cut removed                               */
+    uint64_t base_edges_dropped[ALGA_CONTIG_MAX_ROUNDS];  /* ... edges that left B                                                     */
+    uint64_t final_edges;          /* edges of the final B                                                                           */
+    uint64_t path_nodes, junction_nodes;   /* of the final B: nodes in P / nodes with an edge that are not                           */
+    uint64_t cycles_cut, closed_chains;    /* of the final B; closed chains in both orientations                                     */
+    uint64_t reads_dropped;        /* nodes with an edge in E* and none in the final B                                               */
+    uint64_t longest_nodes, longest_bases, total_bases;   /* over the pairs                                                          */
+    int32_t  rank_rounds;          /* pointer-jumping rounds of all the list rankings                                                */
+    double   ms_sym, ms_rounds, ms_layout, ms_seq, ms_edges, ms_total;   /* device time per stage (HIP events) / wall time of the call */
+} alga_contig_info;
+int  alga_contigs_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset, int32_t flags /* 0 */,
+                         void *hip_stream, alga_unitigs *out, alga_contig_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
