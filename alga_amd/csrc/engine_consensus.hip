@@ -49,7 +49,7 @@ int consensus_impl(alga_engine *e, const alga_nodes *nodes, const alga_unitigs *
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
     }
     // the input is valid: from here on the previous consensus is rewritten
-    e->cs_valid = false;
+    e->cs_valid = false; e->fc_valid = false;
     const bool want_votes = flags & ALGA_CONSENSUS_VOTES;
     if ((rc = alga_ensure(e, e->cs_words, (size_t) (c.n_words + 4) * sizeof(uint32_t)))) return rc;      // (a 16-base fetch may touch the word behind a row)
     if ((rc = alga_ensure(e, e->cs_mask, (size_t) (c.n_words + 1) * sizeof(uint32_t)))) return rc;

@@ -38,10 +38,10 @@ struct GfaEvents {
     ~GfaEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
 };
 
-int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, int &fd) {
+int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, int &fd, const AlgaTextJob *job = nullptr) {
     hipStream_t s = e->own_stream;
     const uint64_t m = c.m;
-    const uint64_t N = c.n_seg + m;                                 // items: segment lines, then link lines
+    const uint64_t N = job ? job->items : c.n_seg + m;              // items: segment lines, then link lines (a job: its own items)
     int rc;
     GfaEvents evs;
     // [0, 1] checks .. scan, [2, 3] the copies' ends (one per pinned slot), [4 + 2 * (k % 4), 5 + 2 * (k % 4)] the formatting of chunk k
@@ -56,7 +56,7 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     unsigned long long *cnt = (unsigned long long *) e->counters.p, *off = (unsigned long long *) e->gfa_off.p;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, GFA_COUNTERS * sizeof(unsigned long long), s));
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
-    launch_gfa_check(c, cnt, s);
+    if (!job) launch_gfa_check(c, cnt, s);
     if ((rc = alga_check_launch(e, "k_gfa_check"))) return rc;
     HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -70,7 +70,8 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
         launch_edge_rowptr(c.e, m, c.n, (uint32_t *) e->gfa_rowptr.p, s);
         if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
     }
-    launch_gfa_sizes(c, (const uint32_t *) e->gfa_rowptr.p, (uint32_t *) e->gfa_sizes.p, cnt, s);
+    if (job) job->sizes((uint32_t *) e->gfa_sizes.p, cnt, s);
+    else launch_gfa_sizes(c, (const uint32_t *) e->gfa_rowptr.p, (uint32_t *) e->gfa_sizes.p, cnt, s);
     if ((rc = alga_check_launch(e, "k_gfa_sizes"))) return rc;
     launch_gfa_scan64((const uint32_t *) e->gfa_sizes.p, N, off, (unsigned long long *) e->gfa_tiles.p, s);
     if ((rc = alga_check_launch(e, "gfa scan"))) return rc;
@@ -130,7 +131,8 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
         if (!bytes) continue;
         // the formatting of chunk k runs behind the copy of chunk k - 1 (same stream, one device buffer)
         HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (4 + 2 * pair)], s));
-        launch_gfa_format(c, off, i0, i1, dbuf, s);
+        if (job) job->format(off, i0, i1, dbuf, s);
+        else launch_gfa_format(c, off, i0, i1, dbuf, s);
         if ((rc = alga_check_launch(e, "k_gfa_format"))) break;
         HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (5 + 2 * pair)], s));
         // ... wait for the write of the chunk two before (it read this pinned buffer) while the device formats
@@ -157,9 +159,9 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     return ALGA_OK;
 }
 
-int gfa_run(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, std::chrono::steady_clock::time_point t0) {
+int gfa_run(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, std::chrono::steady_clock::time_point t0, const AlgaTextJob *job = nullptr) {
     int fd = -1;
-    const int rc = gfa_impl(e, c, path, info, fd);
+    const int rc = gfa_impl(e, c, path, info, fd, job);
     if (rc != ALGA_OK) {
         (void) hipStreamSynchronize(e->own_stream);                 // nothing may still copy into the pinned buffers
         if (fd >= 0) { close(fd); unlink(path); }                  // no partial file is left behind
@@ -170,6 +172,12 @@ int gfa_run(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *in
 }
 
 }  // namespace
+
+int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info) {
+    GfaCfg c{nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 1};
+    c.fasta = 1;                                                     // no header line; the messages name a FASTA file
+    return gfa_run(e, c, path, info, std::chrono::steady_clock::now(), &job);
+}
 
 extern "C" int alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, const char *path, int32_t flags,
                                      alga_gfa_info *info) {

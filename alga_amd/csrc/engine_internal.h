@@ -153,6 +153,12 @@ struct alga_engine {
     DevBuf      cs_cnt, cs_words, cs_mask, cs_votes, cs_trim, cs_len, cs_changed;
     bool        cs_valid = false;                  // the buffers hold the consensus of the unitig result at hand
     bool        cs_has_votes = false;
+    // the final contig set (engine_final.hip): counters, the rank sort, the marks of the end reads, the two lists of undecided pairs, the accepted
+    // flags and their scan, the result arrays, the windows of the accepted pairs, and for the trim: the capped rows, their lengths, trim by id
+    DevBuf      fc_cnt, fc_keys[2], fc_vals, fc_first, fc_min, fc_list[2], fc_flag, fc_ids, fc_verdict, fc_rank, fc_id, fc_new, fc_trim, fc_begin, fc_len,
+                fc_order, fc_wbegin, fc_wlen, fc_rows, fc_rlen, fc_tid;
+    bool        fc_valid = false;                  // the buffers hold the final set of the unitig result and consensus at hand
+    uint64_t    fc_n_accepted = 0;
     int         opt_consensus_max_blocks = 0;      // option "consensus_max_blocks": cap on the grids of the consensus kernels (0: their own); tests lower it to make small inputs stride
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
@@ -274,6 +280,16 @@ int alga_ut_check(alga_engine *e, const alga_nodes *nodes, const alga::alga_edge
 int alga_ut_estar(alga_engine *e, const alga_nodes *nodes, const alga::alga_edge_dev *d_in, uint64_t m, unsigned long long *cnt, hipStream_t s, uint64_t *ms_out);
 int alga_ut_rank(alga_engine *e, const int32_t *len, int32_t n, int32_t *nxt, const int32_t *noff, int32_t *prv, unsigned long long *cnt, uint32_t *p_flag,
                  int &cur, int &rounds, hipStream_t s);
+
+// engine_gfa.hip: the chunk pipeline of the GFA export (sizes -> 64-bit scan -> chunks formatted on the device, copied down and written by a host
+// thread) over items that another file sizes and formats.  sizes: fill sizes[0 .. items) and counters[GFA_SEGMENTS] / [GFA_MAX_LINE] (zeroed);
+// format: the text of items [i0, i1) into buf, item i at byte off[i] - off[i0].  An error removes the partial file.
+struct AlgaTextJob {
+    uint64_t items;
+    std::function<void(uint32_t *sizes, unsigned long long *counters, hipStream_t s)> sizes;
+    std::function<void(const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s)> format;
+};
+int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info);
 
 inline int alga_check_launch(alga_engine *e, const char *what) {
     hipError_t err = hipGetLastError();

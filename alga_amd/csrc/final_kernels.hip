@@ -1,0 +1,410 @@
+// alga_amd/csrc/final_kernels.hip -- the final contig set on the GPU (include/alga_amd.h: alga_contig_trim_device, alga_final_contigs_device,
+// alga_write_final_fasta_device): what the reference does between ContigCreatorSinglePath::getAllContigs and its output FASTA
+// (OutputWriterNew::filterContigs, the trim of src/main.cpp:633-725, writeContigsNoFilter).
+//
+// Integer work and byte movement, and one IEEE double comparison per verdict.
+//   k_fc_len_check     lengths >= 0, the longest capped length
+//   k_fc_gather        ragged sequences (any base index as their start) -> rows of one stride in the cap form: one lane per output word, two source
+//                      words funnel-shifted by begin & 15; the seam at base 501 lies inside word 31 (501 = 31 * 16 + 5)
+//   k_fc_rank_keys     sort keys of the rank order (length descending; the stable sort keeps the pair order inside a length)
+//   k_fc_init          rank[], SHORT, and ACCEPTED for every pair that is accepted even when both its end reads are marked; the rest is undecided
+//   k_fc_round_min     every undecided pair registers its rank at its end reads (64-bit atomicMax on (round, ~rank): no clearing between rounds)
+//   k_fc_round_decide  a pair is decidable when each end read is marked by an accepted pair of smaller rank or has no undecided pair of smaller rank
+//   k_fc_accept_flags / k_fc_number   ids = exclusive scan of the accepted flags in rank order; new_reads from the final marks; the windows in id order
+//   k_fc_apply_trim    begin / len after the trim, TRIMMED_AWAY
+//   k_fc_fasta_sizes / k_fc_fasta_write   the records `>contig_id=<id>_length=<len>\n<window>\n`, one wave per record, 16-byte aligned stores
+// Only the first and the last path entry of a pair can be shared with another pair (the junction reads of a contig result; a unitig result shares
+// nothing), so the marks are kept for end entries alone.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "final_kernels.h"
+#include "gfa_kernels.h"
+
+namespace alga {
+
+namespace {
+
+constexpr int FC_BLOCK = 256;
+constexpr uint32_t FC_NONE = 0xFFFFFFFFu;
+
+__device__ __constant__ uint32_t kFcPow10[10] = {1u, 10u, 100u, 1000u, 10000u, 100000u, 1000000u, 10000000u, 100000000u, 1000000000u};
+
+__device__ __forceinline__ int fc_dec_width(uint32_t v) {
+    int w = 1;
+    while (w < 10 && v >= kFcPow10[w]) w++;
+    return w;
+}
+
+__device__ __forceinline__ unsigned long long fc_wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ unsigned long long fc_wave_max(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t > v ? t : v; }
+    return v;
+}
+
+// slot of this lane in a list that the whole wave appends to (every lane of the wave calls it)
+__device__ __forceinline__ uint32_t fc_wave_append(bool want, unsigned long long *counter) {
+    const unsigned long long m = __ballot(want);
+    if (!m) return 0;
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long) m) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long) __popcll(m));
+    base = __shfl(base, leader);
+    return (uint32_t) base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// OutputWriterNew::filterContig: 100 * ratio < NEW_READS_PER_CONTIG_PERCENTAGE with ratio = (double) new / all
+__device__ __forceinline__ bool fc_rejects(int64_t nw, int64_t all, int32_t percent) {
+    const double ratio = (double) nw / (double) all;
+    return 100.0 * ratio < (double) percent;
+}
+
+// 16 bases from base index q of the packed array; words behind `last_word` (the last word the sequence touches) are not read
+__device__ __forceinline__ uint32_t fc_fetch16(const uint32_t *__restrict__ words, uint64_t q, uint64_t last_word) {
+    const uint64_t w = q >> 4;
+    const uint32_t sh = (uint32_t) (q & 15);
+    const uint32_t lo = w <= last_word ? words[w] : 0u;
+    if (!sh) return lo;
+    const uint32_t hi = w + 1 <= last_word ? words[w + 1] : 0u;
+    return (uint32_t) ((((uint64_t) hi << 32) | lo) >> (2 * sh));
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_len_check(const int32_t *__restrict__ len, uint64_t n, unsigned long long *__restrict__ counters) {
+    unsigned long long bad = 0, mx = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) {
+        const int32_t L = len[i];
+        if (L < 0) bad = FC_BAD_LEN;
+        else { const unsigned long long c = (unsigned long long) (L < FC_CAP ? L : FC_CAP); mx = c > mx ? c : mx; }
+    }
+    bad = fc_wave_max(bad);
+    mx = fc_wave_max(mx);
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) atomicOr(&counters[FC_FLAGS], bad);
+        if (mx) atomicMax(&counters[FC_MAX_LEN], mx);
+    }
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_gather(const uint32_t *__restrict__ words, const unsigned long long *__restrict__ begin,
+                                                        const int32_t *__restrict__ len, uint64_t n, int32_t stride, uint32_t *__restrict__ rows,
+                                                        int32_t *__restrict__ rlen) {
+    const uint64_t total = n * (uint64_t) stride;
+    for (uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t) gridDim.x * blockDim.x) {
+        const uint64_t i = t / (uint64_t) stride;
+        const int32_t wq = (int32_t) (t - i * (uint64_t) stride);
+        const int32_t L = len[i], Lc = L < FC_CAP ? L : FC_CAP;
+        const int32_t j0 = 16 * wq;
+        uint32_t v = 0;
+        if (j0 < Lc) {
+            const uint64_t b = begin[i], last_word = (b + (uint64_t) L - 1) >> 4;
+            if (L <= FC_CAP || j0 + 16 <= FC_CAP_HALF) v = fc_fetch16(words, b + (uint64_t) j0, last_word);
+            else {
+                const uint64_t tail = b + (uint64_t) (L - FC_CAP);            // capped base j >= 501 is base tail + j of the array
+                if (j0 >= FC_CAP_HALF) v = fc_fetch16(words, tail + (uint64_t) j0, last_word);
+                else {                                                        // the seam: the first k bases from the head, the rest from the tail
+                    const int k = FC_CAP_HALF - j0;
+                    v = (fc_fetch16(words, b + (uint64_t) j0, last_word) & ((1u << (2 * k)) - 1u)) |
+                        (fc_fetch16(words, tail + (uint64_t) FC_CAP_HALF, last_word) << (2 * k));
+                }
+            }
+            const int32_t valid = Lc - j0;
+            if (valid < 16) v &= (1u << (2 * valid)) - 1u;
+        }
+        rows[t] = v;
+        if (wq == 0) rlen[i] = Lc;
+    }
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_rank_keys(const int32_t *__restrict__ cons_len, uint32_t P, uint32_t *__restrict__ keys) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < P) keys[k] = 0x7FFFFFFFu - (uint32_t) cons_len[k];
+}
+
+// the read indices of the end entries of pair k: one for a pair of one entry, else the first and the last (they may be the same read)
+__device__ __forceinline__ int fc_ends(const FcCfg &c, uint32_t k, int64_t &all, uint32_t r[2]) {
+    const unsigned long long a = c.path_off[k], b = c.path_off[k + 1];
+    all = (int64_t) (b - a);
+    if (all <= 0) return 0;
+    r[0] = (uint32_t) c.path_node[a] >> 1;
+    if (all == 1) return 1;
+    r[1] = (uint32_t) c.path_node[b - 1] >> 1;
+    return 2;
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_init(FcCfg c, uint32_t *__restrict__ list, unsigned long long *__restrict__ counters) {
+    const uint32_t rho = blockIdx.x * blockDim.x + threadIdx.x;
+    bool undecided = false;
+    uint32_t k = 0;
+    if (rho < c.P) {
+        k = c.by_rank[rho];
+        c.rank[k] = (int32_t) rho;
+        const int32_t L = c.cons_len[k];
+        uint8_t v = FC_V_UNDECIDED;
+        if (L < c.min_length || L == 0) v = FC_V_SHORT;
+        else {
+            int64_t all;
+            uint32_t r[2];
+            const int ne = fc_ends(c, k, all, r);
+            if (!fc_rejects(all - ne, all, c.percent)) {                      // accepted whatever came before
+                v = FC_V_ACCEPTED;
+                for (int j = 0; j < ne; j++) atomicMin(&c.first_acc[r[j]], rho);
+            } else undecided = true;
+        }
+        c.verdict[k] = v;
+    }
+    const uint32_t at = fc_wave_append(undecided, &counters[FC_UNDECIDED]);
+    if (undecided) list[at] = k;
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_round_min(FcCfg c, const uint32_t *__restrict__ list, uint32_t n_in, uint32_t round) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_in) return;
+    const uint32_t k = list[t], rho = (uint32_t) c.rank[k];
+    int64_t all;
+    uint32_t r[2];
+    const int ne = fc_ends(c, k, all, r);
+    const unsigned long long key = ((unsigned long long) round << 32) | (unsigned long long) (~rho);
+    for (int j = 0; j < ne; j++) atomicMax(&c.min_und[r[j]], key);
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_round_decide(FcCfg c, const uint32_t *__restrict__ list, uint32_t n_in, uint32_t round,
+                                                              uint32_t *__restrict__ list_out, unsigned long long *__restrict__ n_out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    bool again = false;
+    uint32_t k = 0;
+    if (t < n_in) {
+        k = list[t];
+        const uint32_t rho = (uint32_t) c.rank[k];
+        int64_t all;
+        uint32_t r[2];
+        const int ne = fc_ends(c, k, all, r);
+        int marked = 0;
+        bool settled = true;
+        for (int j = 0; j < ne; j++) {
+            // an accepted pair of smaller rank is final whenever it is seen; without one the read's state is final once no undecided pair of
+            // smaller rank touches it (this pair registered itself: the entry of this round exists)
+            const uint32_t fa = __hip_atomic_load(&c.first_acc[r[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (fa < rho) { marked++; continue; }
+            const unsigned long long mu = c.min_und[r[j]];
+            const uint32_t lowest = (uint32_t) (mu >> 32) == round ? ~(uint32_t) mu : FC_NONE;
+            if (lowest < rho) settled = false;
+        }
+        if (settled) {
+            const bool rej = fc_rejects(all - marked, all, c.percent);
+            c.verdict[k] = rej ? FC_V_REJECTED : FC_V_ACCEPTED;
+            if (!rej) for (int j = 0; j < ne; j++) atomicMin(&c.first_acc[r[j]], rho);
+        } else again = true;
+    }
+    const uint32_t at = fc_wave_append(again, n_out);
+    if (again) list_out[at] = k;
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_accept_flags(FcCfg c, uint32_t *__restrict__ flags) {
+    const uint32_t rho = blockIdx.x * blockDim.x + threadIdx.x;
+    if (rho <= c.P) flags[rho] = rho < c.P && c.verdict[c.by_rank[rho]] == FC_V_ACCEPTED;
+}
+
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_number(FcCfg c, const uint32_t *__restrict__ ids, unsigned long long *__restrict__ wbegin,
+                                                        int32_t *__restrict__ wlen, unsigned long long *__restrict__ counters) {
+    const uint32_t rho = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long n_short = 0, n_rej = 0, n_acc = 0, mx = 0;
+    if (rho < c.P) {
+        const uint32_t k = c.by_rank[rho];
+        const uint8_t v = c.verdict[k];
+        int32_t nw = -1, id = -1, begin = 0, L = 0;
+        if (v != FC_V_SHORT) {
+            int64_t all;
+            uint32_t r[2];
+            const int ne = fc_ends(c, k, all, r);
+            int marked = 0;
+            for (int j = 0; j < ne; j++) marked += c.first_acc[r[j]] < rho;
+            nw = (int32_t) (all - marked);
+        }
+        if (v == FC_V_ACCEPTED) {
+            id = (int32_t) ids[rho];
+            begin = c.cons_trim[k]; L = c.cons_len[k];
+            c.order[id] = (int32_t) k;
+            wbegin[id] = 16ull * c.word_off[k] + (unsigned long long) begin;
+            wlen[id] = L;
+            mx = (unsigned long long) (L < FC_CAP ? L : FC_CAP);
+            n_acc = 1;
+        } else if (v == FC_V_SHORT) n_short = 1;
+        else n_rej = 1;
+        c.id[k] = id; c.new_reads[k] = nw; c.trim_left[k] = 0; c.begin[k] = begin; c.len[k] = L;
+    }
+    n_short = fc_wave_sum(n_short); n_rej = fc_wave_sum(n_rej); n_acc = fc_wave_sum(n_acc); mx = fc_wave_max(mx);
+    if ((threadIdx.x & 63) == 0) {
+        if (n_short) atomicAdd(&counters[FC_SHORT], n_short);
+        if (n_rej) atomicAdd(&counters[FC_REJECTED], n_rej);
+        if (n_acc) atomicAdd(&counters[FC_ACCEPTED], n_acc);
+        if (mx) atomicMax(&counters[FC_MAX_LEN], mx);
+    }
+}
+
+// src/main.cpp:700-712 with trimRight = 0: the contig keeps s.substr(trimLeft) when trimLeft + 10 < |s|
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_apply_trim(FcCfg c, const int32_t *__restrict__ trim_by_id, uint32_t n_accepted,
+                                                            unsigned long long *__restrict__ counters) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long away = 0;
+    if (j < n_accepted) {
+        const uint32_t k = (uint32_t) c.order[j];
+        const int32_t t = trim_by_id[j], L = c.len[k];
+        c.trim_left[k] = t;
+        if (t + 10 < L) { c.begin[k] += t; c.len[k] = L - t; }
+        else { c.verdict[k] = FC_V_TRIMMED_AWAY; c.begin[k] = 0; c.len[k] = 0; away = 1; }
+    }
+    away = fc_wave_sum(away);
+    if ((threadIdx.x & 63) == 0 && away) atomicAdd(&counters[FC_TRIMMED_AWAY], away);
+}
+
+// ---- FASTA ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_fasta_sizes(FcFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long live = 0, bytes = 0;
+    if (j < f.n) {
+        const uint32_t k = (uint32_t) f.order[j];
+        if (f.verdict[k] == FC_V_ACCEPTED) {
+            const uint32_t L = (uint32_t) f.len[k];
+            // >contig_id= id _length= len \n seq \n
+            bytes = 11ull + fc_dec_width((uint32_t) j) + 8 + fc_dec_width(L) + 1 + L + 1;
+            live = 1;
+        }
+        sizes[j] = (uint32_t) bytes;
+    }
+    live = fc_wave_sum(live);
+    bytes = fc_wave_max(bytes);
+    if ((threadIdx.x & 63) == 0 && live) {
+        atomicAdd(&counters[GFA_SEGMENTS], live);
+        atomicMax(&counters[GFA_MAX_LINE], bytes);
+    }
+}
+
+struct FcRecord {
+    uint32_t id, L, hp;              // hp = bytes before the sequence
+    int wn, wl;
+    const uint32_t *row; uint32_t q0;
+    __device__ __forceinline__ char digit(uint32_t v, int w, int d) const { return (char) ('0' + (v / kFcPow10[w - 1 - d]) % 10); }
+    __device__ __forceinline__ char base(uint32_t q) const { q += q0; return (char) ((0x54474341u >> (8 * ((row[q >> 4] >> (2 * (q & 15))) & 3))) & 0xFF); }
+    __device__ char at(uint32_t p) const {
+        if (p < 11u) return ">contig_id="[p];
+        if (p < 11u + wn) return digit(id, wn, (int) (p - 11u));
+        if (p < 19u + wn) return "_length="[p - 11u - wn];
+        if (p + 1 < hp) return digit(L, wl, (int) (p - 19u - wn));
+        if (p < hp) return '\n';
+        return p - hp < L ? base(p - hp) : '\n';
+    }
+    // 16 bases from sequence index q (all inside the sequence) as 4 little-endian words of ASCII
+    __device__ __forceinline__ uint4 bases16(uint32_t q) const {
+        q += q0;
+        const uint32_t w = q >> 4, sh = q & 15;
+        uint32_t codes = row[w];
+        if (sh) codes = (uint32_t) ((((uint64_t) row[w + 1] << 32) | codes) >> (2 * sh));
+        uint32_t o[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) x |= ((0x54474341u >> (8 * ((codes >> (2 * (4 * k + b))) & 3))) & 0xFFu) << (8 * b);
+            o[k] = x;
+        }
+        return make_uint4(o[0], o[1], o[2], o[3]);
+    }
+};
+
+// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_fasta_write(FcFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
+                                                             char *__restrict__ buf) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t base = off[i0];
+    const uint64_t waves = (uint64_t) gridDim.x * (blockDim.x >> 6);
+    for (uint64_t j = i0 + (uint64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); j < i1; j += waves) {
+        const uint64_t l0 = off[j], l1 = off[j + 1];
+        if (l0 == l1) continue;
+        const uint32_t k = (uint32_t) f.order[j];
+        FcRecord s;
+        s.id = (uint32_t) j; s.L = (uint32_t) f.len[k]; s.wn = fc_dec_width(s.id); s.wl = fc_dec_width(s.L);
+        s.hp = 11u + s.wn + 8u + s.wl + 1u;
+        s.row = f.words + f.word_off[k]; s.q0 = (uint32_t) f.begin[k];
+        char *g0 = buf + (l0 - base), *g1 = buf + (l1 - base);
+        char *a0 = (char *) (((uintptr_t) g0 + 15) & ~(uintptr_t) 15), *a1 = (char *) ((uintptr_t) g1 & ~(uintptr_t) 15);
+        if (a0 >= a1) {                                               // no whole aligned block inside the record
+            for (char *p = g0 + lane; p < g1; p += 64) *p = s.at((uint32_t) (p - g0));
+            continue;
+        }
+        if (g0 + lane < a0) g0[lane] = s.at((uint32_t) lane);         // < 16 bytes before the first aligned block, < 16 after the last
+        if (a1 + lane < g1) a1[lane] = s.at((uint32_t) (a1 - g0) + lane);
+        const uint64_t nblk = (uint64_t) (a1 - a0) >> 4;
+        for (uint64_t q = lane; q < nblk; q += 64) {
+            const uint32_t p = (uint32_t) (a0 - g0) + (uint32_t) (q << 4);
+            uint4 v;
+            if (p >= s.hp && p + 16 <= s.hp + s.L) v = s.bases16(p - s.hp);
+            else {
+                uint32_t o[4];
+                for (int w = 0; w < 4; w++) {
+                    uint32_t x = 0;
+                    for (int b = 0; b < 4; b++) x |= (uint32_t) (uint8_t) s.at(p + 4 * w + b) << (8 * b);
+                    o[w] = x;
+                }
+                v = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+            *reinterpret_cast<uint4 *>(a0 + (q << 4)) = v;
+        }
+    }
+}
+
+inline unsigned fc_grid(uint64_t items, uint64_t cap = 1u << 20) {
+    const uint64_t g = (items + FC_BLOCK - 1) / FC_BLOCK;
+    return (unsigned) (g < cap ? g : cap);
+}
+
+}  // namespace
+
+void launch_fc_len_check(const int32_t *len, uint64_t n, unsigned long long *counters, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_fc_len_check, dim3(fc_grid(n, 4096)), dim3(FC_BLOCK), 0, s, len, n, counters);
+}
+
+void launch_fc_gather(const uint32_t *words, const unsigned long long *begin, const int32_t *len, uint64_t n, int32_t stride, uint32_t *rows, int32_t *rlen,
+                      hipStream_t s) {
+    if (n && stride > 0) hipLaunchKernelGGL(k_fc_gather, dim3(fc_grid(n * (uint64_t) stride)), dim3(FC_BLOCK), 0, s, words, begin, len, n, stride, rows, rlen);
+}
+
+void launch_fc_rank_keys(const int32_t *cons_len, uint32_t P, uint32_t *keys, hipStream_t s) {
+    if (P) hipLaunchKernelGGL(k_fc_rank_keys, dim3((P + FC_BLOCK - 1) / FC_BLOCK), dim3(FC_BLOCK), 0, s, cons_len, P, keys);
+}
+
+void launch_fc_init(const FcCfg &c, uint32_t *list, unsigned long long *counters, hipStream_t s) {
+    if (c.P) hipLaunchKernelGGL(k_fc_init, dim3((c.P + FC_BLOCK - 1) / FC_BLOCK), dim3(FC_BLOCK), 0, s, c, list, counters);
+}
+
+void launch_fc_round(const FcCfg &c, const uint32_t *list_in, uint32_t n_in, uint32_t round, uint32_t *list_out, unsigned long long *n_out, hipStream_t s) {
+    if (!n_in) return;
+    const dim3 grid((n_in + FC_BLOCK - 1) / FC_BLOCK);
+    hipLaunchKernelGGL(k_fc_round_min, grid, dim3(FC_BLOCK), 0, s, c, list_in, n_in, round);
+    hipLaunchKernelGGL(k_fc_round_decide, grid, dim3(FC_BLOCK), 0, s, c, list_in, n_in, round, list_out, n_out);
+}
+
+void launch_fc_accept_flags(const FcCfg &c, uint32_t *flags, hipStream_t s) {
+    hipLaunchKernelGGL(k_fc_accept_flags, dim3((c.P + 1 + FC_BLOCK - 1) / FC_BLOCK), dim3(FC_BLOCK), 0, s, c, flags);
+}
+
+void launch_fc_number(const FcCfg &c, const uint32_t *ids, unsigned long long *wbegin, int32_t *wlen, unsigned long long *counters, hipStream_t s) {
+    if (c.P) hipLaunchKernelGGL(k_fc_number, dim3((c.P + FC_BLOCK - 1) / FC_BLOCK), dim3(FC_BLOCK), 0, s, c, ids, wbegin, wlen, counters);
+}
+
+void launch_fc_apply_trim(const FcCfg &c, const int32_t *trim_by_id, uint32_t n_accepted, unsigned long long *counters, hipStream_t s) {
+    if (n_accepted) hipLaunchKernelGGL(k_fc_apply_trim, dim3((n_accepted + FC_BLOCK - 1) / FC_BLOCK), dim3(FC_BLOCK), 0, s, c, trim_by_id, n_accepted, counters);
+}
+
+void launch_fc_fasta_sizes(const FcFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
+    if (f.n) hipLaunchKernelGGL(k_fc_fasta_sizes, dim3((unsigned) ((f.n + FC_BLOCK - 1) / FC_BLOCK)), dim3(FC_BLOCK), 0, s, f, sizes, counters);
+}
+
+void launch_fc_fasta_write(const FcFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
+    if (i0 >= i1) return;
+    const uint64_t g = (i1 - i0 + FC_BLOCK / 64 - 1) / (FC_BLOCK / 64);
+    hipLaunchKernelGGL(k_fc_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(FC_BLOCK), 0, s, f, off, i0, i1, buf);
+}
+
+}  // namespace alga

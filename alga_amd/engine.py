@@ -160,7 +160,7 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
            "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
            "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device",
-           "alga_contigs_device"]
+           "alga_contigs_device", "alga_contig_trim_device", "alga_final_contigs_device", "alga_write_final_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -310,6 +310,49 @@ class Consensus:
                     votes=None if self.votes is None else h(self.votes), info=dict(self.info))
 
 
+FINAL_SHORT, FINAL_REJECTED, FINAL_ACCEPTED, FINAL_TRIMMED_AWAY = 0, 1, 2, 3     # ALGA_FINAL_*: alga_final_contigs.d_verdict
+
+
+class FinalContigsC(C.Structure):
+    """alga_final_contigs"""
+    _fields_ = [("n_pairs", C.c_int32), ("n_accepted", C.c_int32), ("n_written", C.c_int32), ("reserved", C.c_int32), ("d_verdict", C.c_void_p),
+                ("d_rank", C.c_void_p), ("d_id", C.c_void_p), ("d_new_reads", C.c_void_p), ("d_trim_left", C.c_void_p), ("d_begin", C.c_void_p),
+                ("d_len", C.c_void_p), ("d_order", C.c_void_p)]
+
+
+class FinalInfo(C.Structure):
+    """alga_final_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("pairs", "n_short", "rejected", "accepted", "trimmed_away", "filter_rounds", "trim_edges")] + \
+               [(k, C.c_double) for k in ("ms_filter", "ms_trim", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class FinalContigs:
+    """Result of Engine.final_contigs: zero-copy torch views of the engine's device memory (valid until the next Engine.unitigs, contigs,
+    unitig_consensus or final_contigs call on that engine; clone what has to live longer) -- verdict uint8 [n_pairs] (FINAL_*), rank / id /
+    new_reads / trim_left / begin / len int32 [n_pairs], order int32 [n_accepted] -- the counts n_accepted / n_written and .info (dict of
+    alga_final_info)."""
+    KEYS = ("verdict", "rank", "id", "new_reads", "trim_left", "begin", "len", "order")
+
+    def __init__(self, c, info, unitigs, consensus, device):
+        self._c, self.info, self.n_pairs, self.n_accepted, self.n_written = c, info, int(c.n_pairs), int(c.n_accepted), int(c.n_written)
+        self._unitigs, self._consensus = unitigs, consensus
+        P = self.n_pairs
+        dev = "cuda:%d" % device
+        self.verdict = device_view(c.d_verdict, (P,), dev, "|u1")
+        for k in self.KEYS[1:-1]:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (P,), dev))
+        self.order = device_view(c.d_order, (self.n_accepted,), dev)
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/final_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy() for k in self.KEYS}
+        d.update(n_pairs=self.n_pairs, n_accepted=self.n_accepted, n_written=self.n_written, info=dict(self.info))
+        return d
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -433,6 +476,10 @@ def load_library():
     lib.alga_unitig_consensus_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(UnitigsC), C.c_int32, C.c_int32, C.c_void_p,
                                                  C.POINTER(ConsensusC), C.POINTER(ConsensusInfo)]
     lib.alga_write_consensus_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.c_char_p, C.c_int32, C.POINTER(GfaInfo)]
+    lib.alga_contig_trim_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.alga_final_contigs_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.POINTER(FinalContigsC), C.POINTER(FinalInfo)]
+    lib.alga_write_final_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.POINTER(FinalContigsC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1160,6 +1207,50 @@ class Engine:
         info = GfaInfo()
         self._check(self._lib.alga_write_consensus_fasta_device(self._h, C.byref(unitigs._c), C.byref(consensus._c), os.fsencode(path), int(min_length),
                                                                 C.byref(info)))
+        return info.as_dict()
+
+    def contig_trim_device(self, words, begin, lens, threshold=25, stream=None):
+        """The trim of contig ends against each other (src/main.cpp:636-697) on ragged sequences in device memory (alga_contig_trim_device)
+        -> trim_left int32 [n], a torch device tensor.  words: the 2-bit packed array (int32 / uint32, any shape), begin int64 [n]: the base
+        index of each sequence's first base in it (any index), lens int32 [n]; torch device tensors (numpy arrays are uploaded first).
+        Sequences longer than 1002 nt enter the build as their first and last 501 nt: there is no length limit.  The call runs a build on
+        the engine (its last build result is gone); the current unitig, consensus and final results stay."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(words, np.ndarray):
+            words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(dev)
+        if isinstance(begin, np.ndarray):
+            begin = torch.from_numpy(np.ascontiguousarray(begin).astype(np.int64)).to(dev)
+        if isinstance(lens, np.ndarray):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+        assert begin.dtype == torch.int64 and lens.dtype == torch.int32 and begin.shape == lens.shape
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        n = int(lens.shape[0])
+        out = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        m = C.c_uint64()
+        self._check(self._lib.alga_contig_trim_device(self._h, _ptr(words), _ptr(begin), _ptr(lens), n, int(threshold), None, _ptr(out), C.byref(m)))
+        self.last_trim_edges = int(m.value)
+        return out
+
+    def final_contigs(self, unitigs, consensus, min_length=200, new_reads_percent=95, trim_threshold=25):
+        """The final contig set (alga_final_contigs_device: OutputWriterNew::filterContigs' length and new-read filter in longest-first order,
+        the numbering, the trim of the ends against each other; the definition is in include/alga_amd.h) -> FinalContigs.
+        unitigs / consensus: the results of the LAST Engine.contigs (or unitigs) and unitig_consensus calls.  trim_threshold 0: no trim."""
+        out, info = FinalContigsC(), FinalInfo()
+        self._check(self._lib.alga_final_contigs_device(self._h, C.byref(unitigs._c), C.byref(consensus._c), int(min_length), int(new_reads_percent),
+                                                        int(trim_threshold), 0, None, C.byref(out), C.byref(info)))
+        return FinalContigs(out, info.as_dict(), unitigs, consensus, self.device)
+
+    def write_final_fasta(self, path, final):
+        """The accepted contigs of the LAST Engine.final_contigs call as FASTA (alga_write_final_fasta_device) -> dict of alga_gfa_info
+        (segments = records): `>contig_id=<id>_length=<len>` and the window on one line, in id order."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_final_fasta_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
+                                                            os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

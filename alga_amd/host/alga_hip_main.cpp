@@ -5,6 +5,7 @@
 //            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1]
 //            [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200] [--consensus_min_votes=3]
 //            [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N]
+//            [--contigs_final=final.fasta] [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -41,6 +42,10 @@
 // record names (`>contig_id=<j>_length=<len>`) for the windows of at least --contigs_min_length bases (default max(200, int(1.75 * LEN)),
 // src/main.cpp:94); --contigs_gfa=PATH beside it: the contig graph with the spelled sequences.  No stock binary (--alga=) is needed for these
 // contigs.  None of the three options is passed through; every invocation without them behaves as before.
+// --contigs_final=PATH: the same chain through the contigs and their consensus (with or without --contigs=; it honours --contigs_min_length and
+// --consensus_min_votes), then the final set (alga_final_contigs_device: OutputWriterNew::filterContigs' length and new-read filter longest first with
+// --contigs_new_reads_percent, the numbering, the trim of the contig ends against each other at --contigs_trim_threshold, 0 = none), written as
+// FASTA in id order (alga_write_final_fasta_device).  None of the three options is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -65,10 +70,10 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 int main(int argc, char **argv) {
     using clk = std::chrono::steady_clock;
-    std::string file1, file2, output, alga_exe, gfa, unitigs, consensus, contigs, contigs_gfa, v;
+    std::string file1, file2, output, alga_exe, gfa, unitigs, consensus, contigs, contigs_gfa, contigs_final, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
-    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1;
+    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1, contigs_new_reads_percent = 95, contigs_trim_threshold = 25;
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -97,6 +102,9 @@ int main(int argc, char **argv) {
         else if (opt(a, "--contigs", v)) contigs = v;
         else if (opt(a, "--contigs_gfa", v)) contigs_gfa = v;
         else if (opt(a, "--contigs_min_length", v)) contigs_min_length = atoi(v.c_str());
+        else if (opt(a, "--contigs_final", v)) contigs_final = v;
+        else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
+        else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--consensus_min_length", v)) consensus_min_length = atoi(v.c_str());
         else if (opt(a, "--consensus_min_votes", v)) consensus_min_votes = atoi(v.c_str());
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
@@ -242,7 +250,7 @@ int main(int argc, char **argv) {
     if (n_final && alga_copy_to_host(engine, final_edges.data(), d_final, final_edges.size() * sizeof(alga_edge)) != ALGA_OK) { fprintf(stderr, "alga_amd: cannot read the edges back\n"); return 1; }
     fprintf(stderr, "Before first simplifier graph has %llu edges\n", (unsigned long long) n_final);
     const bool want_unitigs = !unitigs.empty() || !consensus.empty();
-    if (want_unitigs || !contigs.empty()) {                                    // the edges are on the host already: nothing below touches what is handed on
+    if (want_unitigs || !contigs.empty() || !contigs_final.empty()) {                                    // the edges are on the host already: nothing below touches what is handed on
         alga_nodes nd{nodes.d_words, nodes.stride_words, nodes.d_len, nodes.n, nullptr, nullptr};
         const int mopp = std::max(250, (int) (1.75 * parsed.LEN));            // Params::MAX_OFFSET_PARALLEL_PATHS, src/main.cpp:95
         const alga_edge *d_cut = nullptr;
@@ -313,7 +321,7 @@ int main(int argc, char **argv) {
                 (unsigned long long) ui.total_bases, (unsigned long long) n_removed, (unsigned long long) ui.isolated_skipped, ui.ms_sym, ui.ms_rank, ui.rank_rounds,
                 ui.ms_layout, ui.ms_seq, ui.ms_edges, ui.ms_total, (unsigned long long) gi.bytes, gi.ms_format, gi.ms_total);
         }
-        if (!contigs.empty()) {                                               // last: the contig result replaces the unitigs on the engine; d_cut stays valid
+        if (!contigs.empty() || !contigs_final.empty()) {                     // last: the contig result replaces the unitigs on the engine; d_cut stays valid
             alga_unitigs cu;
             alga_contig_info ki;
             alga_consensus cs;
@@ -323,8 +331,9 @@ int main(int argc, char **argv) {
             rc = alga_contigs_device(engine, &nd, d_cut, n_cut, mopp, 0, nullptr, &cu, &ki);
             if (rc == ALGA_OK && !contigs_gfa.empty()) rc = alga_write_unitig_gfa_device(engine, &cu, contigs_gfa.c_str(), ALGA_GFA_SEQUENCES, &cgi);
             if (rc == ALGA_OK) rc = alga_unitig_consensus_device(engine, &nd, &cu, consensus_min_votes, 0, nullptr, &cs, &ci);
-            if (rc == ALGA_OK) rc = alga_write_consensus_fasta_device(engine, &cu, &cs, contigs.c_str(), min_len, &fi);
-            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", contigs.c_str(), alga_last_error(engine), rc); return 1; }
+            if (rc == ALGA_OK && !contigs.empty()) rc = alga_write_consensus_fasta_device(engine, &cu, &cs, contigs.c_str(), min_len, &fi);
+            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", (contigs.empty() ? contigs_final : contigs).c_str(), alga_last_error(engine), rc); return 1; }
+            if (!contigs.empty())
             fprintf(stderr, "Contigs written -> %s: %llu records of %d contigs (min length %d), longest %llu nt (%llu reads); %llu rounds, %llu -> %llu edges, %llu reads "
                     "dropped, %llu path nodes, %llu junction nodes; device ms: edges %.3f rounds %.3f layout %.3f sequences %.3f contig graph %.3f, call %.1f ms "
                     "wall; consensus %.1f ms wall; FASTA %llu bytes, wall %.1f ms\n", contigs.c_str(), (unsigned long long) fi.segments, cu.n_pairs, min_len,
@@ -334,6 +343,19 @@ int main(int argc, char **argv) {
             if (!contigs_gfa.empty())
                 fprintf(stderr, "Contig graph written -> %s: %llu segments, %llu links, %llu bytes\n", contigs_gfa.c_str(), (unsigned long long) cgi.segments,
                         (unsigned long long) cgi.links, (unsigned long long) cgi.bytes);
+            if (!contigs_final.empty()) {
+                alga_final_contigs fc;
+                alga_final_info fci;
+                alga_gfa_info ffi;
+                rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
+                if (rc == ALGA_OK) rc = alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
+                if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", contigs_final.c_str(), alga_last_error(engine), rc); return 1; }
+                fprintf(stderr, "Final contigs written -> %s: %llu records of %d contigs (min length %d, new reads %d %%, trim threshold %d): %llu short, %llu rejected, "
+                        "%llu trimmed away; %llu filter rounds, %llu edges in the trim's build; device ms: filter %.3f trim %.3f, call %.1f ms wall; FASTA %llu bytes, "
+                        "wall %.1f ms\n", contigs_final.c_str(), (unsigned long long) ffi.segments, cu.n_pairs, min_len, contigs_new_reads_percent, contigs_trim_threshold,
+                        (unsigned long long) fci.n_short, (unsigned long long) fci.rejected, (unsigned long long) fci.trimmed_away, (unsigned long long) fci.filter_rounds,
+                        (unsigned long long) fci.trim_edges, fci.ms_filter, fci.ms_trim, fci.ms_total, (unsigned long long) ffi.bytes, ffi.ms_total);
+            }
         }
     }
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

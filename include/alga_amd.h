@@ -919,8 +919,8 @@ int  alga_write_consensus_fasta_device(alga_engine *e, const alga_unitigs *u, co
  * `d_edges` may be the engine-owned result of the cut, the clip or the parallel-path step: the call reads it once, into E*, before anything else,
  * and invalidates no earlier result but the unitigs and their consensus (the cut of H runs the cut's kernel on buffers of this call).
  * Refusals (ALGA_ERR_INVALID_ARGUMENT, nothing written, the previous result stays valid): where alga_unitigs_device refuses, max_offset < 0, flags != 0.
- * NOT reproduced (out of scope): filterContigs' share of new reads, the N4 trim of contig ends against each other (alga_contig_trim_host), the
- * extension by paired connections (markReliablePredecessorsByPairedConnections), the reference's order-dependent replacement of parallel contracted
+ * filterContigs' share of new reads and the N4 trim of contig ends against each other follow in alga_final_contigs_device below.
+ * NOT reproduced (out of scope): the extension by paired connections (markReliablePredecessorsByPairedConnections), the reference's order-dependent replacement of parallel contracted
  * paths, and its skipped last block in WorkloadManager::parallelBlockExecution.  The ABI number stays 7: the call only adds to the ABI. */
 #define ALGA_CONTIG_MAX_ROUNDS 64
 typedef struct {
@@ -940,6 +940,85 @@ typedef struct {
 } alga_contig_info;
 int  alga_contigs_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset, int32_t flags /* 0 */,
                          void *hip_stream, alga_unitigs *out, alga_contig_info *info /* may be NULL */);
+
+/* ---- the final contig set: new-read filter, numbering, end trim, FASTA (alga_amd/csrc/final_kernels.hip, engine_final.hip) ------------------------
+ * What the reference does between ContigCreatorSinglePath::getAllContigs and its output file: OutputWriterNew::filterContigs
+ * (src/IO/OutputWriterNew.cpp:93-125, 150-187), the trim of the contig ends against each other (src/main.cpp:633-725), writeContigsNoFilter.
+ *
+ * alga_contig_trim_device: alga_contig_trim_host on ragged sequences that are in device memory already.  Sequence i is the d_len[i] bases of the
+ * 2-bit packed array `d_words` from base index d_begin[i] on (any index: it need not be word-aligned); nodes 0 .. n-1 are the sequences,
+ * n .. 2n-1 their reverse complements, one PrefSuf build runs with min_overlap = rsoe_min_overlap = threshold (in [1, 501]) and the defaults
+ * otherwise, and d_trim_left[d] (device memory, n entries) = the largest len[i] - offset over the edges i -> d with i, d < n.  Overlap lengths
+ * stop at 501, so a sequence longer than 1002 nt enters the build as its first 501 nt followed by its last 501 nt: every overlap of up to 501 nt
+ * between the true sequences is one of the same length between the capped ones and the other way round, and a capped node cannot be the middle
+ * of a transitive triple (that needs len = ov1 + ov2 - ov3 <= 977).  The rows of the build are at most 63 words long whatever the lengths are:
+ * there is no length limit but int32.  A negative length answers ALGA_ERR_INVALID_ARGUMENT (checked on the device, nothing written).
+ * The call runs a build on the engine: it invalidates the engine's last build result (the edge list of alga_prefsuf_build_device and the like)
+ * and whatever the engine derived from a node set it was given before (keys, entry arrays, node statistics), as alga_contig_trim_host does.  It
+ * does not touch the engine's current unitig, consensus or final result.  `edges_out` (may be NULL): the edges of that build.
+ *
+ * alga_final_contigs_device: `u` is the engine's current unitig result (alga_unitigs_device or alga_contigs_device), `cons` its consensus.  The
+ * definition (tests/final_checker.py states it in Python; the device result equals it array for array):
+ *   order      the pairs are ranked by (cons.d_len[k] descending, k ascending); d_rank[k] = the rank.  (std::sort in the reference leaves the
+ *              order inside one length undefined; this is the order-free choice.)
+ *   verdict    the pairs in rank order, with an empty mark set over read indices v >> 1:
+ *                ALGA_FINAL_SHORT     cons.d_len[k] < min_length or cons.d_len[k] == 0.
+ *                otherwise            all = the path entries of k, new = those whose read index is unmarked (a read that occurs twice in a
+ *                                     closed chain counts twice);
+ *                ALGA_FINAL_REJECTED  100.0 * ((double) new / (double) all) < (double) new_reads_percent, in IEEE double as the reference
+ *                                     computes it (no fused or fast-math form);
+ *                ALGA_FINAL_ACCEPTED  else: all the pair's read indices become marked (so the read and its twin do).
+ *              d_id[k] = the number of accepted pairs ranked before k (-1: not accepted); d_new_reads[k] = new (-1: short);
+ *              d_order[id] = the pair.
+ *   trim       trim_threshold > 0: alga_contig_trim_device on the windows of the accepted pairs in id order, `+` orientation.  With t the value of
+ *              pair k: t + 10 < cons.d_len[k]: d_begin[k] = cons.d_trim_left[k] + t, d_len[k] = cons.d_len[k] - t; else the pair becomes
+ *              ALGA_FINAL_TRIMMED_AWAY (the reference writes the placeholder CCCC for such a contig; this engine leaves the record out and
+ *              counts it).  Ids keep the gap.  d_trim_left[k] = t.  trim_threshold == 0: no trim (t = 0).
+ *              Pairs that are not ACCEPTED in the end have d_begin = d_len = 0.
+ * n_accepted = ACCEPTED + TRIMMED_AWAY pairs (the ids), n_written = ACCEPTED pairs.
+ * Only the first and the last path entry of a pair can be shared with another pair (the junction reads of a contig result; a unitig result
+ * shares nothing).  A pair that is accepted even with both end reads marked needs no order; the rest is decided in rounds: a pair is decidable
+ * when each of its end reads either is marked by an accepted pair of smaller rank or has no undecided pair of smaller rank.  The undecided pair of
+ * the smallest rank always is: there is no cap on the rounds and no host fallback.  `filter_rounds` counts them; one count is read back per round.
+ * Refusals (ALGA_ERR_INVALID_ARGUMENT, nothing written, an earlier final result stays valid): `u` / `cons` are not the engine's current results,
+ * new_reads_percent outside 0 .. 100, min_length < 0, trim_threshold outside {0} and [1, 501], flags != 0.
+ * The result is engine-owned device memory, valid until the next alga_unitigs_device, alga_contigs_device, alga_unitig_consensus_device or
+ * alga_final_contigs_device call on `e`.  With trim_threshold > 0 the call invalidates what alga_contig_trim_device invalidates.
+ *
+ * alga_write_final_fasta_device: in id order, for every ALGA_FINAL_ACCEPTED pair, `>contig_id=<id>_length=<d_len>\n<ACGT of the window>\n`
+ * through the chunk pipeline of alga_write_gfa_device.  `fin` must be the engine's current final result.  info: segments = records written,
+ * bytes = size of the file.  No record: an empty file.  On an error the partial file is removed.  The ABI number stays 7: the calls only add. */
+#define ALGA_FINAL_SHORT        0
+#define ALGA_FINAL_REJECTED     1
+#define ALGA_FINAL_ACCEPTED     2
+#define ALGA_FINAL_TRIMMED_AWAY 3
+typedef struct {
+    int32_t        n_pairs;        /* u.n_pairs                                                                                       */
+    int32_t        n_accepted;     /* ids handed out: ACCEPTED + TRIMMED_AWAY pairs                                                   */
+    int32_t        n_written;      /* ACCEPTED pairs: the records of the FASTA                                                        */
+    int32_t        reserved;
+    const uint8_t *d_verdict;      /* n_pairs: ALGA_FINAL_*                                                                           */
+    const int32_t *d_rank;         /* n_pairs                                                                                         */
+    const int32_t *d_id;           /* n_pairs: -1 when not accepted                                                                   */
+    const int32_t *d_new_reads;    /* n_pairs: -1 when short                                                                          */
+    const int32_t *d_trim_left;    /* n_pairs: what the trim cuts off the window's left end                                           */
+    const int32_t *d_begin;        /* n_pairs: first column of the written window in the pair's consensus row                         */
+    const int32_t *d_len;          /* n_pairs: its length                                                                             */
+    const int32_t *d_order;        /* n_accepted: pair by id                                                                          */
+} alga_final_contigs;
+typedef struct {
+    uint64_t pairs, n_short, rejected, accepted, trimmed_away;   /* pairs per final verdict                                           */
+    uint64_t filter_rounds;        /* rounds of the filter's schedule                                                                 */
+    uint64_t trim_edges;           /* edges of the trim's build                                                                       */
+    double   ms_filter, ms_trim;   /* device time (HIP events)                                                                        */
+    double   ms_total;             /* wall time of the call                                                                           */
+} alga_final_info;
+int  alga_contig_trim_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n, int32_t threshold,
+                             void *hip_stream, int32_t *d_trim_left, uint64_t *edges_out /* may be NULL */);
+int  alga_final_contigs_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, int32_t min_length, int32_t new_reads_percent,
+                               int32_t trim_threshold, int32_t flags /* 0 */, void *hip_stream, alga_final_contigs *out, alga_final_info *info /* may be NULL */);
+int  alga_write_final_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin, const char *path,
+                                   alga_gfa_info *info /* may be NULL */);
 
 #ifdef __cplusplus
 }
