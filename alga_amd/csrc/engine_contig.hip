@@ -46,7 +46,7 @@ int contigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
     if ((rc = alga_ut_check(e, nodes, d_in, m, ucnt, s))) return rc;
     // the input is valid: from here on the previous result's buffers are rewritten
-    e->ut_valid = false; e->cs_valid = false; e->fc_valid = false; e->ut_is_contig = false;
+    e->ut_valid = false; e->cs_valid = false; e->fc_valid = false; e->ut_is_contig = false; e->ut_is_extended = false;
 
     // ---- E*: the input is consumed here, before anything else of this call runs
     uint64_t ms = 0;

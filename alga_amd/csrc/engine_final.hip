@@ -112,7 +112,8 @@ int final_impl(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons
     FcCfg c{u->d_path_node, (const unsigned long long *) u->d_path_off, (const unsigned long long *) u->d_word_off, cons->d_len, cons->d_trim_left, P, min_length,
             percent, (const uint32_t *) e->fc_vals.p, (uint8_t *) e->fc_verdict.p, (int32_t *) e->fc_rank.p, (int32_t *) e->fc_id.p, (int32_t *) e->fc_new.p,
             (int32_t *) e->fc_trim.p, (int32_t *) e->fc_begin.p, (int32_t *) e->fc_len.p, (int32_t *) e->fc_order.p, (uint32_t *) e->fc_first.p,
-            (unsigned long long *) e->fc_min.p};
+            (unsigned long long *) e->fc_min.p, e->ut_is_extended ? (const unsigned long long *) e->ex_seam_off.p : nullptr,
+            e->ut_is_extended ? (const int32_t *) e->ex_seam_entry.p : nullptr};
     launch_fc_init(c, (uint32_t *) e->fc_list[0].p, cnt, s);
     if ((rc = alga_check_launch(e, "k_fc_init"))) return rc;
     HIP_TRY(e, hipMemcpyAsync(&e->h_counters[0], cnt + FC_UNDECIDED, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

@@ -143,6 +143,12 @@ struct alga_engine {
     int32_t     ut_n_nodes = 0;                    // ... the n of the node set it was made from, the sum of its lengths
     uint64_t    ut_total_bases = 0;
     bool        ut_is_contig = false;              // the result at hand came from alga_contigs_device (the FASTA names its records contig_id=<j>)
+    // extension of contigs by paired connections (engine_extend.hip): counters, the contig graph's row pointers, per oriented contig its weight,
+    // entries, direct link, links of L*, the only one, head / bases / links before it on its path, new oriented id; the seam list; and the new
+    // result, built beside the one it is read from and swapped in at the end
+    DevBuf      ex_cnt, ex_rowptr, ex_w, ex_kcnt, ex_dlink, ex_outcnt, ex_sole, ex_xhead, ex_xbase, ex_xrank, ex_uid, ex_scnt, ex_seam_off,
+                ex_seam_entry, ex_pcnt, ex_uwords, ex_ulen, ex_ulen2, ex_path_off, ex_word_off, ex_path_node, ex_path_pos, ex_words, ex_edges;
+    bool        ut_is_extended = false;            // the result at hand came from alga_extend_contigs_device: ex_seam_off / ex_seam_entry describe it
     // contigs (engine_contig.hip): counters, the base graph B of a round (two buffers in turn) and its row pointers, P flags, per-run smallest read
     // index, the chain records and the chain that enters every run, drop marks, flags and their scan, the group sort, the per-group best
     // (weight, key), H with the triangle cut's workspaces, and for the contig graph: winners, pair numbers, oriented ids, their chains, degrees,

@@ -176,7 +176,7 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
     if ((rc = alga_ut_check(e, nodes, d_in, m, cnt, s))) return rc;
     // the input is valid: from here on the previous result's buffers are rewritten
-    e->ut_valid = false; e->cs_valid = false; e->fc_valid = false; e->ut_is_contig = false;
+    e->ut_valid = false; e->cs_valid = false; e->fc_valid = false; e->ut_is_contig = false; e->ut_is_extended = false;
     const size_t N = (size_t) n;
     for (int k = 0; k < 2; k++) if ((rc = alga_ensure(e, e->ut_rank[k], (N + 1) * sizeof(UtRank)))) return rc;
     if ((rc = alga_ensure(e, e->ut_nxt, (N + 1) * sizeof(int32_t)))) return rc;

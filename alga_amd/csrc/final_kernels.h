@@ -28,6 +28,8 @@ struct FcCfg {
     int32_t *rank, *id, *new_reads, *trim_left, *begin, *len, *order;
     uint32_t *first_acc;              // per read index: the smallest rank of an accepted pair that has it as an end entry (0xFFFFFFFF: none)
     unsigned long long *min_und;      // per read index: (round << 32) | ~(smallest rank of an undecided pair that has it as an end entry)
+    const unsigned long long *seam_off;   // an extended result: the end entries of pair k are its seam list seam_entry[seam_off[k] .. seam_off[k+1])
+    const int32_t *seam_entry;            // (indices into the pair's path entries); nullptr: the first and the last path entry
 };
 
 // lengths >= 0 (FC_BAD_LEN), the longest capped length into counters[FC_MAX_LEN]

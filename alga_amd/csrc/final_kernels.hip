@@ -14,7 +14,8 @@
 //   k_fc_apply_trim    begin / len after the trim, TRIMMED_AWAY
 //   k_fc_fasta_sizes / k_fc_fasta_write   the records `>contig_id=<id>_length=<len>\n<window>\n`, one wave per record, 16-byte aligned stores
 // Only the first and the last path entry of a pair can be shared with another pair (the junction reads of a contig result; a unitig result shares
-// nothing), so the marks are kept for end entries alone.
+// nothing), so the marks are kept for end entries alone.  Of an extended result (alga_extend_contigs_device) the junction reads inside a pair are
+// shared too: its end entries are its seam list.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -122,15 +123,18 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_rank_keys(const int32_t *__rest
     if (k < P) keys[k] = 0x7FFFFFFFu - (uint32_t) cons_len[k];
 }
 
-// the read indices of the end entries of pair k: one for a pair of one entry, else the first and the last (they may be the same read)
-__device__ __forceinline__ int fc_ends(const FcCfg &c, uint32_t k, int64_t &all, uint32_t r[2]) {
-    const unsigned long long a = c.path_off[k], b = c.path_off[k + 1];
-    all = (int64_t) (b - a);
+// the end entries of pair k, the ones another pair can share: one for a pair of one entry, else the first and the last (they may be the same
+// read); of an extended result the entries of its seam list.  -> their number; fc_end_read: the read index of end entry j
+__device__ __forceinline__ uint32_t fc_ends(const FcCfg &c, uint32_t k, int64_t &all) {
+    all = (int64_t) (c.path_off[k + 1] - c.path_off[k]);
     if (all <= 0) return 0;
-    r[0] = (uint32_t) c.path_node[a] >> 1;
-    if (all == 1) return 1;
-    r[1] = (uint32_t) c.path_node[b - 1] >> 1;
-    return 2;
+    if (c.seam_off) return (uint32_t) (c.seam_off[k + 1] - c.seam_off[k]);
+    return all == 1 ? 1u : 2u;
+}
+__device__ __forceinline__ uint32_t fc_end_read(const FcCfg &c, uint32_t k, uint32_t j) {
+    const unsigned long long a = c.path_off[k];
+    if (c.seam_off) return (uint32_t) c.path_node[a + (unsigned long long) c.seam_entry[c.seam_off[k] + j]] >> 1;
+    return (uint32_t) c.path_node[j ? c.path_off[k + 1] - 1 : a] >> 1;
 }
 
 __global__ void __launch_bounds__(FC_BLOCK) k_fc_init(FcCfg c, uint32_t *__restrict__ list, unsigned long long *__restrict__ counters) {
@@ -145,11 +149,10 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_init(FcCfg c, uint32_t *__restr
         if (L < c.min_length || L == 0) v = FC_V_SHORT;
         else {
             int64_t all;
-            uint32_t r[2];
-            const int ne = fc_ends(c, k, all, r);
+            const uint32_t ne = fc_ends(c, k, all);
             if (!fc_rejects(all - ne, all, c.percent)) {                      // accepted whatever came before
                 v = FC_V_ACCEPTED;
-                for (int j = 0; j < ne; j++) atomicMin(&c.first_acc[r[j]], rho);
+                for (uint32_t j = 0; j < ne; j++) atomicMin(&c.first_acc[fc_end_read(c, k, j)], rho);
             } else undecided = true;
         }
         c.verdict[k] = v;
@@ -163,10 +166,9 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_round_min(FcCfg c, const uint32
     if (t >= n_in) return;
     const uint32_t k = list[t], rho = (uint32_t) c.rank[k];
     int64_t all;
-    uint32_t r[2];
-    const int ne = fc_ends(c, k, all, r);
+    const uint32_t ne = fc_ends(c, k, all);
     const unsigned long long key = ((unsigned long long) round << 32) | (unsigned long long) (~rho);
-    for (int j = 0; j < ne; j++) atomicMax(&c.min_und[r[j]], key);
+    for (uint32_t j = 0; j < ne; j++) atomicMax(&c.min_und[fc_end_read(c, k, j)], key);
 }
 
 __global__ void __launch_bounds__(FC_BLOCK) k_fc_round_decide(FcCfg c, const uint32_t *__restrict__ list, uint32_t n_in, uint32_t round,
@@ -178,23 +180,23 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_round_decide(FcCfg c, const uin
         k = list[t];
         const uint32_t rho = (uint32_t) c.rank[k];
         int64_t all;
-        uint32_t r[2];
-        const int ne = fc_ends(c, k, all, r);
-        int marked = 0;
+        const uint32_t ne = fc_ends(c, k, all);
+        int64_t marked = 0;
         bool settled = true;
-        for (int j = 0; j < ne; j++) {
+        for (uint32_t j = 0; j < ne; j++) {
+            const uint32_t rd = fc_end_read(c, k, j);
             // an accepted pair of smaller rank is final whenever it is seen; without one the read's state is final once no undecided pair of
             // smaller rank touches it (this pair registered itself: the entry of this round exists)
-            const uint32_t fa = __hip_atomic_load(&c.first_acc[r[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t fa = __hip_atomic_load(&c.first_acc[rd], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (fa < rho) { marked++; continue; }
-            const unsigned long long mu = c.min_und[r[j]];
+            const unsigned long long mu = c.min_und[rd];
             const uint32_t lowest = (uint32_t) (mu >> 32) == round ? ~(uint32_t) mu : FC_NONE;
             if (lowest < rho) settled = false;
         }
         if (settled) {
             const bool rej = fc_rejects(all - marked, all, c.percent);
             c.verdict[k] = rej ? FC_V_REJECTED : FC_V_ACCEPTED;
-            if (!rej) for (int j = 0; j < ne; j++) atomicMin(&c.first_acc[r[j]], rho);
+            if (!rej) for (uint32_t j = 0; j < ne; j++) atomicMin(&c.first_acc[fc_end_read(c, k, j)], rho);
         } else again = true;
     }
     const uint32_t at = fc_wave_append(again, n_out);
@@ -216,10 +218,9 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_number(FcCfg c, const uint32_t 
         int32_t nw = -1, id = -1, begin = 0, L = 0;
         if (v != FC_V_SHORT) {
             int64_t all;
-            uint32_t r[2];
-            const int ne = fc_ends(c, k, all, r);
-            int marked = 0;
-            for (int j = 0; j < ne; j++) marked += c.first_acc[r[j]] < rho;
+            const uint32_t ne = fc_ends(c, k, all);
+            int64_t marked = 0;
+            for (uint32_t j = 0; j < ne; j++) marked += c.first_acc[fc_end_read(c, k, j)] < rho;
             nw = (int32_t) (all - marked);
         }
         if (v == FC_V_ACCEPTED) {

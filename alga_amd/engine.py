@@ -160,7 +160,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
            "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
            "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device",
-           "alga_contigs_device", "alga_contig_trim_device", "alga_final_contigs_device", "alga_write_final_fasta_device"]
+           "alga_contigs_device", "alga_contig_trim_device", "alga_final_contigs_device", "alga_write_final_fasta_device",
+           "alga_extend_contigs_device", "alga_extend_seams_get"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -240,6 +241,24 @@ class ContigInfo(C.Structure):
         for k in self._PER_ROUND:
             d[k] = list(getattr(self, k))[: min(int(self.rounds), CONTIG_MAX_ROUNDS)]
         return d
+
+
+EXTEND_HEAD_SLICE = 1024                                          # ALGA_EXTEND_HEAD_SLICE
+
+
+class ExtendInfo(C.Structure):
+    """alga_extend_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("candidates", "direct_links", "links", "joinable", "ambiguous", "cycles_cut", "pairs_in", "pairs_out", "head_max",
+                                          "head_passes", "longest_nodes", "longest_bases", "total_bases")] + [("rank_rounds", C.c_int32)] + \
+               [(k, C.c_double) for k in ("ms_count", "ms_paths", "ms_layout", "ms_seq", "ms_edges", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ExtendSeamsC(C.Structure):
+    """alga_extend_seams"""
+    _fields_ = [("d_seam_off", C.c_void_p), ("d_seam_entry", C.c_void_p), ("n_seams", C.c_uint64)]
 
 
 class Unitigs:
@@ -479,6 +498,9 @@ def load_library():
     lib.alga_contig_trim_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.alga_final_contigs_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.POINTER(FinalContigsC), C.POINTER(FinalInfo)]
+    lib.alga_extend_contigs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.POINTER(UnitigsC), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ExtendInfo)]
+    lib.alga_extend_seams_get.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ExtendSeamsC)]
     lib.alga_write_final_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.POINTER(FinalContigsC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
@@ -1170,6 +1192,37 @@ class Engine:
                                                   None, C.byref(out), C.byref(info)))
         del keep
         return Unitigs(out, info.as_dict(), self.device)
+
+    def extend_contigs(self, words, lens, pair_off, contigs, min_chain_weight, min_connections=5, max_insert=1000, stream=None):
+        """Contigs extended through junctions that paired reads support (alga_extend_contigs_device; the definition is in include/alga_amd.h)
+        -> Unitigs, with .info a dict of alga_extend_info and .seams = (seam_off int64 [n_pairs + 1], seam_entry int32), zero-copy views.
+        words / lens: the node set the LAST Engine.contigs call was made from, contigs: that call's result (no longer valid afterwards);
+        pair_off uint8 [n]: Global::pairedReadOffset per node (0 unpaired, 1: the mate is v + 2, 2: v - 2), None: no pairs.  The result becomes
+        the engine's current unitig result, as a contig result does.  The reference's min_chain_weight is int(2 * mean live read length)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if isinstance(words, np.ndarray):
+            words = torch.from_numpy(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32)).to(dev)
+        if isinstance(lens, np.ndarray):
+            lens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+        if isinstance(pair_off, np.ndarray):
+            pair_off = torch.from_numpy(np.ascontiguousarray(pair_off, dtype=np.uint8)).to(dev)
+        if pair_off is not None:
+            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == int(lens.shape[0])
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 else 1, _ptr(lens), int(lens.shape[0]), None, None)
+        out, info, seams = UnitigsC(), ExtendInfo(), ExtendSeamsC()
+        self._check(self._lib.alga_extend_contigs_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None),
+                                                         C.byref(contigs._c), int(min_chain_weight), int(min_connections), int(max_insert), 0, None,
+                                                         C.byref(out), C.byref(info)))
+        self._check(self._lib.alga_extend_seams_get(self._h, C.byref(out), C.byref(seams)))
+        res = Unitigs(out, info.as_dict(), self.device)
+        d = "cuda:%d" % self.device
+        res.seams = (device_view(seams.d_seam_off, (res.n_pairs + 1,), d, "<i8"), device_view(seams.d_seam_entry, (int(seams.n_seams),), d))
+        return res
 
     def write_unitig_gfa(self, path, unitigs, sequences=True, consensus=None):
         """The result of the LAST Engine.unitigs call as GFA 1.0 (alga_write_unitig_gfa_device) -> dict of alga_gfa_info: pair k is segment k,

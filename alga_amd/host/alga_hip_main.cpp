@@ -5,7 +5,7 @@
 //            [--device=K] [--gpus=N | --gpu-list=0,1,2,...] [--alga=/path/to/stock/ALGA] [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1]
 //            [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200] [--consensus_min_votes=3]
 //            [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N]
-//            [--contigs_final=final.fasta] [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25]
+//            [--contigs_final=final.fasta] [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -46,6 +46,9 @@
 // --consensus_min_votes), then the final set (alga_final_contigs_device: OutputWriterNew::filterContigs' length and new-read filter longest first with
 // --contigs_new_reads_percent, the numbering, the trim of the contig ends against each other at --contigs_trim_threshold, 0 = none), written as
 // FASTA in id order (alga_write_final_fasta_device).  None of the three options is passed through.
+// --paired_extend=1 (default 0; honoured by --contigs=, --contigs_gfa= and --contigs_final=; not passed through): with --file2 the contigs are
+// extended through the junctions that paired reads support (alga_extend_contigs_device: min_chain_weight = int(2 * mean length of the live reads),
+// 5 connections, inserts up to 1000) before the GFA, the consensus and the final set are made.  Without --file2 it changes nothing and says so.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -73,7 +76,7 @@ int main(int argc, char **argv) {
     std::string file1, file2, output, alga_exe, gfa, unitigs, consensus, contigs, contigs_gfa, contigs_final, v;
     alga_host::IngestParams ip;
     double error_rate = 0.0;
-    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1, contigs_new_reads_percent = 95, contigs_trim_threshold = 25;
+    int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1, contigs_new_reads_percent = 95, contigs_trim_threshold = 25, paired_extend = 0;
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -105,6 +108,7 @@ int main(int argc, char **argv) {
         else if (opt(a, "--contigs_final", v)) contigs_final = v;
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
+        else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
         else if (opt(a, "--consensus_min_length", v)) consensus_min_length = atoi(v.c_str());
         else if (opt(a, "--consensus_min_votes", v)) consensus_min_votes = atoi(v.c_str());
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
@@ -114,7 +118,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -256,21 +260,29 @@ int main(int argc, char **argv) {
         const alga_edge *d_cut = nullptr;
         uint64_t n_cut = 0, n_removed = 0;
         int rc = alga_cut_triangles_device(engine, nodes.n, d_final, n_final, mopp, nullptr, &d_cut, &n_cut, &n_removed);
+        // Global::calculateAvgReadLength: the mean length (a double) over the reads that are alive, i.e. have an edge in the graph at hand
+        // (Global::removeIsolatedReads).  A host pass over the lengths and the edge list, run only where an option asks for a bound made from it.
+        auto live_average = [&](const alga_edge *d_e, uint64_t n_e, double *avg) -> int {
+            std::vector<int32_t> hl((size_t) nodes.n);
+            std::vector<alga_edge> hc((size_t) n_e);
+            int r = ALGA_OK;
+            if (nodes.n) r = alga_copy_to_host(engine, hl.data(), nodes.d_len, hl.size() * sizeof(int32_t));
+            if (r == ALGA_OK && n_e) r = alga_copy_to_host(engine, hc.data(), d_e, hc.size() * sizeof(alga_edge));
+            std::vector<char> has_edge((size_t) nodes.n, 0);
+            for (const alga_edge &x : hc) { has_edge[(size_t) x.src] = 1; has_edge[(size_t) x.dst] = 1; }
+            double sum = 0; long long cnt = 0;
+            for (size_t k = 0; k < hl.size(); k++) if (hl[k] > 0 && has_edge[k]) { sum += hl[k]; cnt++; }
+            *avg = cnt ? sum / (double) cnt : 0.0;
+            return r;
+        };
         alga_unitigs u;
         alga_unitig_info ui;
         alga_gfa_info gi;
         if (rc == ALGA_OK && (clip_tips || parallel_paths)) {
             // Global::calculateAvgReadLength at src/GraphSimplifiers/GraphSimplifier.cpp:179: the mean (a double) over the reads alive after the cut,
             // i.e. without those the cut graph has no edge at (Global::removeIsolatedReads, :117)
-            std::vector<int32_t> hl((size_t) nodes.n);
-            std::vector<alga_edge> hc((size_t) n_cut);
-            if (nodes.n) rc = alga_copy_to_host(engine, hl.data(), nodes.d_len, hl.size() * sizeof(int32_t));
-            if (rc == ALGA_OK && n_cut) rc = alga_copy_to_host(engine, hc.data(), d_cut, hc.size() * sizeof(alga_edge));
-            std::vector<char> has_edge((size_t) nodes.n, 0);
-            for (const alga_edge &x : hc) { has_edge[(size_t) x.src] = 1; has_edge[(size_t) x.dst] = 1; }
-            double sum = 0; long long cnt = 0;
-            for (size_t k = 0; k < hl.size(); k++) if (hl[k] > 0 && has_edge[k]) { sum += hl[k]; cnt++; }
-            const double avg = cnt ? sum / (double) cnt : 0.0;
+            double avg = 0.0;
+            rc = live_average(d_cut, n_cut, &avg);
             const int bound = (int) (mopp * avg / (float) 100);                  // MAX_OFFSET_DANGLING_BRANCHES has MAX_OFFSET_PARALLEL_PATHS's value, src/main.cpp:95-96
             if (rc == ALGA_OK && parallel_paths) {
                 alga_mst_info mi;
@@ -329,6 +341,28 @@ int main(int argc, char **argv) {
             alga_gfa_info fi, cgi;
             const int min_len = contigs_min_length >= 0 ? contigs_min_length : std::max(200, (int) (1.75 * parsed.LEN));   // src/main.cpp:94
             rc = alga_contigs_device(engine, &nd, d_cut, n_cut, mopp, 0, nullptr, &cu, &ki);
+            if (rc == ALGA_OK && paired_extend && file2.empty()) fprintf(stderr, "--paired_extend=1 without --file2: there are no pairs, the contigs stay as they are\n");
+            if (rc == ALGA_OK && paired_extend && !file2.empty()) {
+                // Global::calculateAvgReadLength at ContigCreatorSinglePath.cpp:274: the mean over the reads that are alive, i.e. have an edge left
+                // d_cut is what the contigs were made from (after the parallel paths and the clip where they ran): the reads alive in it are the
+                // reference's at this call, its second one -- the first, for the clip's bound, sees the graph right after the cut
+                double avg = 0.0;
+                rc = live_average(d_cut, n_cut, &avg);
+                const int min_chain_weight = (int) (2 * avg);
+                alga_unitigs xu;
+                alga_extend_info xi;
+                if (rc == ALGA_OK) rc = alga_extend_contigs_device(engine, &nd, nodes.d_pair_off, &cu, min_chain_weight, 5, 1000, 0, nullptr, &xu, &xi);
+                if (rc == ALGA_OK) {
+                    cu = xu;
+                    fprintf(stderr, "Contigs extended by paired connections: %llu -> %llu contigs (min chain weight %d); %llu candidates, %llu direct links, %llu links, "
+                            "%llu joinable, %llu ambiguous, %llu cycles cut, largest head %llu entries (%llu passes), longest %llu nt (%llu reads); device ms: count %.3f "
+                            "paths %.3f layout %.3f sequences %.3f graph %.3f, call %.1f ms wall\n", (unsigned long long) xi.pairs_in, (unsigned long long) xi.pairs_out,
+                            min_chain_weight, (unsigned long long) xi.candidates, (unsigned long long) xi.direct_links, (unsigned long long) xi.links,
+                            (unsigned long long) xi.joinable, (unsigned long long) xi.ambiguous, (unsigned long long) xi.cycles_cut, (unsigned long long) xi.head_max,
+                            (unsigned long long) xi.head_passes, (unsigned long long) xi.longest_bases, (unsigned long long) xi.longest_nodes, xi.ms_count, xi.ms_paths,
+                            xi.ms_layout, xi.ms_seq, xi.ms_edges, xi.ms_total);
+                }
+            }
             if (rc == ALGA_OK && !contigs_gfa.empty()) rc = alga_write_unitig_gfa_device(engine, &cu, contigs_gfa.c_str(), ALGA_GFA_SEQUENCES, &cgi);
             if (rc == ALGA_OK) rc = alga_unitig_consensus_device(engine, &nd, &cu, consensus_min_votes, 0, nullptr, &cs, &ci);
             if (rc == ALGA_OK && !contigs.empty()) rc = alga_write_consensus_fasta_device(engine, &cu, &cs, contigs.c_str(), min_len, &fi);

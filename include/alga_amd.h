@@ -920,7 +920,8 @@ int  alga_write_consensus_fasta_device(alga_engine *e, const alga_unitigs *u, co
  * and invalidates no earlier result but the unitigs and their consensus (the cut of H runs the cut's kernel on buffers of this call).
  * Refusals (ALGA_ERR_INVALID_ARGUMENT, nothing written, the previous result stays valid): where alga_unitigs_device refuses, max_offset < 0, flags != 0.
  * filterContigs' share of new reads and the N4 trim of contig ends against each other follow in alga_final_contigs_device below.
- * NOT reproduced (out of scope): the extension by paired connections (markReliablePredecessorsByPairedConnections), the reference's order-dependent replacement of parallel contracted
+ * The extension by paired connections (markReliablePredecessorsByPairedConnections) follows in alga_extend_contigs_device below.
+ * NOT reproduced (out of scope): the reference's order-dependent replacement of parallel contracted
  * paths, and its skipped last block in WorkloadManager::parallelBlockExecution.  The ABI number stays 7: the call only adds to the ABI. */
 #define ALGA_CONTIG_MAX_ROUNDS 64
 typedef struct {
@@ -940,6 +941,67 @@ typedef struct {
 } alga_contig_info;
 int  alga_contigs_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, int32_t max_offset, int32_t flags /* 0 */,
                          void *hip_stream, alga_unitigs *out, alga_contig_info *info /* may be NULL */);
+
+/* ---- contigs extended through junctions that paired reads support (alga_amd/csrc/extend_kernels.hip, engine_extend.hip) ---------------------------
+ * What the reference does with the pairing between its contracted graph and its contigs (ContigCreatorSinglePath::
+ * markReliablePredecessorsByPairedConnections with countPairedConnections, and the walk of getContigOmitShortCyclesFrom through reliable
+ * predecessors), in an order-free, twin-symmetric form.  It is the only consumer of alga_device_node_set.d_pair_off.  Inputs: the node set (n, len),
+ * `d_pair_off` (n bytes of device memory, Global::pairedReadOffset: mate(v) = v, v + 2, v - 2 for the values 0, 1, 2; NULL: all zero), `u` = the
+ * engine's current result, which must come from alga_contigs_device, min_chain_weight (the reference: int(2 * mean length of the live reads)),
+ * min_connections (the reference: 5), max_insert (the reference: 1000), flags = 0.  The definition (tests/extend_checker.py states it in Python; the
+ * device result equals it array for array):
+ *   0. checks, on the device, nothing written on refusal (ALGA_ERR_INVALID_ARGUMENT): `u` is the current result and a contig result (not an
+ *      extended one); nodes->n is the n of that call; pair_off[v] <= 2 and pair_off[v] == pair_off[v ^ 1]; mate(v) is in range and points back
+ *      (1 <-> 2 at distance 2); min_chain_weight >= 0, max_insert >= 0, min_connections >= 1; flags == 0.
+ *   1. oriented contig c in [0, 2 P) (2k+1 = `+` of pair k, 2k = `-`) has the entries e_0 .. e_(k-1) at the positions p_0 = 0 .. p_(k-1); `-` is the
+ *      reversed chain of the twins: the entry made from v_i stands at L - p_i - len[v_i].  Its weight is w(c) = p_(k-1).
+ *   2. the head H(c) = the read indices e_i >> 1 for 1 <= i <= k-1 with p_(i-1) <= max_insert; the tail T(c) = the entries i with 1 <= i <= k-1 and
+ *      w(c) - p_i <= max_insert.  Entry 0 is in neither (the loops of countPairedConnections; the comparison is on the read index because the
+ *      reference asks for the mate or its twin).
+ *   3. for X, Y with last(X) == first(Y) =: a, cnt(X, Y) = the number of i in T(X) with pair_off[e_i] != 0 and mate(e_i) >> 1 in H(Y).
+ *   4. X -> Y is a DIRECT link when Y is the only oriented contig that starts at a, w(X) >= min_chain_weight, w(Y) >= min_chain_weight and
+ *      cnt(X, Y) >= min_connections.  L* = the direct links and their twins Y^1 -> X^1.
+ *   5. a link X -> Y of L* is JOINABLE when it is the only link of L* out of X, the only one into Y, Y != X and Y != X^1.  A cycle of joinable
+ *      links is opened as unitig step 4 opens it, over oriented contig ids (m = the smallest id over the cycle and its twin cycle; the link into m
+ *      and its twin go).  The extended contigs are the maximal paths of joinable links (an oriented contig without one: a path of one).  Of a path
+ *      and its twin the one whose first oriented contig has the smaller key c ^ 1 is `+`, and the pairs are numbered in ascending order of that key
+ *      (unitig step 6 over a key that puts `+` of a pair before its `-`: a contig that no link touches keeps its orientation and its place).
+ *   6. layout of a path X_1 .. X_m: the entries concatenated, a seam node once; base_1 = 0, base_(j+1) = base_j + w(X_j), position = base_j + p_i;
+ *      length = base_m + L(X_m), above 2^31 - 1: ALGA_ERR_CAPACITY.  Sequences follow unitig step 8 (ragged, tail bits zero).
+ *   7. the graph follows contig step 4 over the new oriented ids.
+ *   8. the seam list of pair k: the path indices of the first entry of every constituent chain, plus the last entry -- m + 1 indices,
+ *      d_seam_entry[d_seam_off[k] .. d_seam_off[k+1]) (alga_extend_seams_get).  These are the entries other pairs can share.
+ * With no link at all the arrays equal those of `u`.
+ * The result has the alga_unitigs layout and BECOMES the engine's current unitig result, as a contig result does (its FASTA names the records
+ * contig_id=<j>); `u` itself is no longer valid after a successful call.  alga_final_contigs_device keeps its marks per seam read for such a result.
+ * NOT reproduced: the reference extends one orientation only, emits every contig that starts in the middle of an extension as well and leaves
+ * those to the filter; where several predecessors of `a` qualify it emits one overlapping contig per predecessor and its filter drops the shorter
+ * ones whole -- here none is joined, and info.ambiguous counts the oriented contigs with more than one link of L* into them; an unpaired read
+ * does not count (the reference compares it with itself).  The ABI number stays 7: the calls only add. */
+#define ALGA_EXTEND_HEAD_SLICE 1024   /* head entries one pass of the count holds in its table */
+typedef struct {
+    uint64_t candidates;           /* oriented contigs X whose last node starts exactly one oriented contig                           */
+    uint64_t direct_links, links;  /* direct links / links of L*                                                                     */
+    uint64_t joinable;             /* joinable links, after the cycle cuts                                                           */
+    uint64_t ambiguous;            /* oriented contigs with more than one link of L* into them                                       */
+    uint64_t cycles_cut;           /* cycles of joinable links, a cycle and its twin cycle counted once                              */
+    uint64_t pairs_in, pairs_out;
+    uint64_t head_max, head_passes;   /* the largest head of a candidate that passed the weight test (entries; also without pairs) and the
+                                         passes over the tail it takes: ceil(head_max / ALGA_EXTEND_HEAD_SLICE)                       */
+    uint64_t longest_nodes, longest_bases, total_bases;   /* over the new pairs                                                      */
+    int32_t  rank_rounds;          /* pointer-jumping rounds of both list rankings                                                   */
+    double   ms_count, ms_paths, ms_layout, ms_seq, ms_edges, ms_total;   /* device time per stage (HIP events) / wall time of the call */
+} alga_extend_info;
+typedef struct {
+    const uint64_t *d_seam_off;    /* n_pairs + 1                                                                                    */
+    const int32_t  *d_seam_entry;  /* indices into the pair's own path entries (0 = its first entry)                                 */
+    uint64_t        n_seams;       /* d_seam_off[n_pairs]                                                                            */
+} alga_extend_seams;
+int  alga_extend_contigs_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_unitigs *u, int32_t min_chain_weight,
+                                int32_t min_connections, int32_t max_insert, int32_t flags /* 0 */, void *hip_stream, alga_unitigs *out,
+                                alga_extend_info *info /* may be NULL */);
+/* The seam list of `u`, which must be the engine's current result and come from alga_extend_contigs_device (else ALGA_ERR_INVALID_ARGUMENT). */
+int  alga_extend_seams_get(alga_engine *e, const alga_unitigs *u, alga_extend_seams *out);
 
 /* ---- the final contig set: new-read filter, numbering, end trim, FASTA (alga_amd/csrc/final_kernels.hip, engine_final.hip) ------------------------
  * What the reference does between ContigCreatorSinglePath::getAllContigs and its output file: OutputWriterNew::filterContigs
@@ -977,7 +1039,8 @@ int  alga_contigs_device(alga_engine *e, const alga_nodes *nodes, const alga_edg
  *              Pairs that are not ACCEPTED in the end have d_begin = d_len = 0.
  * n_accepted = ACCEPTED + TRIMMED_AWAY pairs (the ids), n_written = ACCEPTED pairs.
  * Only the first and the last path entry of a pair can be shared with another pair (the junction reads of a contig result; a unitig result
- * shares nothing).  A pair that is accepted even with both end reads marked needs no order; the rest is decided in rounds: a pair is decidable
+ * shares nothing); of an extended result (alga_extend_contigs_device) the entries of its seam list can, and "end reads" below are those.
+ * A pair that is accepted even with all its end reads marked needs no order; the rest is decided in rounds: a pair is decidable
  * when each of its end reads either is marked by an accepted pair of smaller rank or has no undecided pair of smaller rank.  The undecided pair of
  * the smallest rank always is: there is no cap on the rounds and no host fallback.  `filter_rounds` counts them; one count is read back per round.
  * Refusals (ALGA_ERR_INVALID_ARGUMENT, nothing written, an earlier final result stays valid): `u` / `cons` are not the engine's current results,
