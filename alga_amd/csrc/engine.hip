@@ -316,6 +316,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
     }
     const uint32_t big_list_cap = 1u << 20;
     if (local && (rc = alga_ensure(e, e->loc_big_list, big_list_cap * sizeof(int32_t)))) return rc;
+    bool pure_streamed = false;                            // a build of the pure pile form sent its handed-on sources through k_probe_stream as well (option pile_stream_by_id)
     for (int attempt = 0; attempt < 4; attempt++) {
         if (cap >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 overlap records; shard the input");
         if (local) HIP_TRY(e, hipMemsetAsync(e->outdeg.p, 0, (size_t) (n_src + 1) * sizeof(uint32_t), s));
@@ -366,11 +367,13 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                 if ((rc = alga_check_launch(e, "k_probe_stream"))) return rc;
                 if (piled) {
                     // the MIXED form (more than one irregular bucket in 250, not more than one in 20 -- the kernels read the sample's counters themselves):
-                    // what k_pile_probe handed on goes through the stream kernel, by list, before the general kernel gets what is left
+                    // what k_pile_probe handed on goes through the stream kernel, by list, before the general kernel gets what is left; the PURE form
+                    // too (option pile_stream_by_id), with the entries taken by id from the sorted (key, id) pairs -- it has no entry array
                     if ((rc = alga_ensure(e, e->cl_defer2, (size_t) (n_src + 64) * sizeof(int32_t)))) return rc;
-                    launch_probe_stream_list(nd, cfg, cc, pp.cluster_eq, e->cl_store.p, e->cl_dir.p, e->cl_runs.p, (const uint8_t *) e->cl_nruns.p, (int32_t *) e->cl_defer.p,
+                    pure_streamed = launch_probe_stream_list(nd, cfg, cc, pp.cluster_eq, e->cl_store.p, e->cl_dir.p, e->cl_runs.p, (const uint8_t *) e->cl_nruns.p, (int32_t *) e->cl_defer.p,
                                              (uint32_t) n_src, cnt, e->n_cu, (uint32_t *) e->outdeg.p, (unsigned long long *) e->loc_first.p,
-                                             (unsigned long long *) e->loc_second.p, (int32_t *) e->cl_defer2.p, (const unsigned long long *) e->cl_pile_cnt.p, s, slot_stride, src_begin);
+                                             (unsigned long long *) e->loc_second.p, (int32_t *) e->cl_defer2.p, (const unsigned long long *) e->cl_pile_cnt.p, s, slot_stride, src_begin,
+                                             (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, pp.uniform_len, e->opt_pile_stream_by_id != 0);
                     if ((rc = alga_check_launch(e, "k_probe_stream (list)"))) return rc;
                 }
                 HIP_TRY(e, hipEventRecord(e->ev[EV_PAIRS], s));
@@ -448,7 +451,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                 // array, and a later keys_shared = 2 build of this node set may use it
                 const bool kept = e->opt_pile == 2 || e->stats.pile_irregular * (uint64_t) ALGA_PILE_DECLINE_ONE_IN <= e->stats.pile_buckets;
                 e->stats.pile_mixed = kept && e->stats.pile_irregular * (uint64_t) ALGA_PILE_IRREGULAR_ONE_IN > e->stats.pile_buckets;
-                e->stats.pile_deferred = e->stats.pile_mixed ? e->h_counters[CNT_DEFERRED_PILE] : (kept ? e->h_counters[CNT_DEFERRED] : 0);
+                e->stats.pile_deferred = (e->stats.pile_mixed || (kept && pure_streamed)) ? e->h_counters[CNT_DEFERRED_PILE] : (kept ? e->h_counters[CNT_DEFERRED] : 0);
                 if (!kept || e->stats.pile_mixed || !e->opt_pile_skip_gather) e->store_n = nd.n;      // (the entry array was built: k_tgt_gather leaves only for a build of the pure pile form)
                 e->expect_pairwise = !kept;               // (how the NEXT build's key pass is laid out -- never what it computes)
                 e->pile_kept_pure = kept && !e->stats.pile_mixed && e->opt_pile_skip_gather != 0;
@@ -718,6 +721,8 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_pile_deg_fold = value != 0;
     } else if (!strcmp(name, "pile_probe_lean")) {
         e->opt_pile_probe_lean = value != 0;
+    } else if (!strcmp(name, "pile_stream_by_id")) {
+        e->opt_pile_stream_by_id = value != 0;
     } else if (!strcmp(name, "pile_check")) {
         e->opt_pile_check = value != 0;
     } else if (!strcmp(name, "pile_skip_gather")) {

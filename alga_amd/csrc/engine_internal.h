@@ -65,6 +65,7 @@ struct alga_engine {
     int    opt_pile_runs_list = 1;                          // option "pile_runs_list": 1 = k_pile_build lists its piles and k_pile_runs_consensus_list works through the lists (four waves per SIMD), 0 = k_pile_runs_consensus sweeps the side records for them (round 5)
     DevBuf cl_pile_list;                                    // the piles of every k_pile_build workgroup and their counts (pile_list_bytes)
     int    opt_pile_deg_fold = 1;                           // option "pile_deg_fold": 1 = the first pass of the out-degree scan moves the out-degrees k_pile_probe left in the slots (no k_pile_deg), 0 = k_pile_deg behind the probe
+    int    opt_pile_stream_by_id = 0;                       // option "pile_stream_by_id": 1 = a build kept in the pure pile form sends what k_pile_probe hands on through k_probe_stream (list mode, entries by id) before the general kernel, 0 = to the general kernel at once (the default until the pass is measured)
     int    opt_pile_probe_lean = 1;                         // option "pile_probe_lean": 1 = k_pile_probe<true> (the source's row taken in slot 0 only, no last-mismatch search past position 63), 0 = k_pile_probe<false> (round 5)
     bool   pile_deg_pending = false;                        // the last discovery left that move to finalize_local's scan
     int    opt_pile_check = 0;                              // option "pile_check" (tests): every node gets its own run list and every first-group member's is compared with its pile's clipped list (stats.pile_list_*)

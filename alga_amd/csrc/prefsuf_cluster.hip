@@ -335,6 +335,29 @@ struct ByIdEntries {
     uint32_t uniform_meta;                                 // len << 8 | CL_META_FROM
     const unsigned long long *pile_cnt;                    // null: the build has an entry array, no question
 };
+// The (key, id) pair of entry `ei` of the key order (the caller clamps ei); the id clamped: the row is fetched by it.
+__device__ __forceinline__ void by_id_pair(const ByIdEntries &by, size_t ei, uint32_t n_nodes, uint32_t &key, uint32_t &id) {
+    key = by.skeys[ei];
+    id = min(by.sids[ei], n_nodes - 1u);
+}
+// ... and the sixteen words the entry array would hold for it (EQ = 3: rows of nine words, all the pile path takes): the row from the node array --
+// two 16-byte loads and one word where the rows allow it (load_row9's rule, prefsuf_pile.hip), word by word otherwise --, the id, the key, and the
+// meta word the key and the one read length imply.  Used by k_probe_clustered<., ., ., ., true> and k_probe_stream<., ., ., ., ., true>.
+template <int EQ>
+__device__ __forceinline__ void entry_by_id(const NodesDev &nd, uint32_t uniform_meta, int fs, uint32_t key, uint32_t id, uint32_t (&ew)[4 * EQ]) {
+    static_assert(EQ == 3, "entries by id: rows of nine words");
+    const uint32_t *row = nd.words + (size_t) id * nd.stride;
+    if ((nd.stride & 3) == 0 && nd.stride >= 12 && ((uintptr_t) nd.words & 15u) == 0) {       // uniform
+        const uint4 v0 = reinterpret_cast<const uint4 *>(row)[0], v1 = reinterpret_cast<const uint4 *>(row)[1];
+        ew[0] = v0.x; ew[1] = v0.y; ew[2] = v0.z; ew[3] = v0.w; ew[4] = v1.x; ew[5] = v1.y; ew[6] = v1.z; ew[7] = v1.w;
+        ew[8] = row[8];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; k++) ew[k] = k < nd.stride ? row[k] : 0u;
+    }
+    ew[9] = id; ew[10] = key;
+    ew[11] = key != 0xFFFFFFFFu ? (uniform_meta | ((key >> fs) & ((1u << CL_MBITS) - 1u))) : 0u;      // (all ones: not a target -- never in a bucket)
+}
 template <bool STATS, int EQ, int KF, int SW = 1, bool BYID = false>
 __global__ void __launch_bounds__(PROBE_WAVES * 64, SW == 1 && EQ <= 4 ? CL_OCC : 4)
 k_probe_clustered(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__restrict__ store, const uint4 *__restrict__ dir,
@@ -433,17 +456,14 @@ k_probe_clustered(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__res
         const uint32_t j = k0 + ((uint32_t) lane & ((1u << gs) - 1u));
         ev = j < rp.w;
         ei = ev ? (size_t) min(rp.z + j, (uint32_t) nd.n - 1u) : (size_t) 0;   // lanes without an entry read entry 0 (unconditional loads: see index_loads); clamped: a corrupt directory must not fault
-        if (BYID) {
-            const uint32_t key = by.skeys[ei], id = min(by.sids[ei], (uint32_t) nd.n - 1u);
-            const uint32_t *row = nd.words + (size_t) id * nd.stride;
+        if constexpr (BYID) {
+            uint32_t key, id;
+            by_id_pair(by, ei, (uint32_t) nd.n, key, id);
+            entry_by_id<EQ>(nd, by.uniform_meta, cc.idx_shift - CL_MBITS, key, id, ew);
+        } else {
 #pragma unroll
-            for (int k = 0; k < WC; k++) ew[k] = k < nd.stride ? row[k] : 0u;
-            ew[4 * EQ - 3] = id; ew[4 * EQ - 2] = key;
-            ew[4 * EQ - 1] = key != 0xFFFFFFFFu ? (by.uniform_meta | ((key >> (cc.idx_shift - CL_MBITS)) & ((1u << CL_MBITS) - 1u))) : 0u;
-            return;
+            for (int c = 0; c < EQ; c++) { const uint4 v = store[ei * EQ + c]; ew[4 * c] = v.x; ew[4 * c + 1] = v.y; ew[4 * c + 2] = v.z; ew[4 * c + 3] = v.w; }
         }
-#pragma unroll
-        for (int c = 0; c < EQ; c++) { const uint4 v = store[ei * EQ + c]; ew[4 * c] = v.x; ew[4 * c + 1] = v.y; ew[4 * c + 2] = v.z; ew[4 * c + 3] = v.w; }
     };
 
     int B = 0, lenB = 0, nr = 0;
@@ -734,17 +754,23 @@ constexpr int clq_occ(int eq, int kf, bool bykey) { return (eq == 4 || (eq == 3 
 // LIST (round 5, the mixed form of a build the pile path keeps): the sources are the ids src_list[0 .. *src_count) -- what k_pile_probe handed
 // on, in about the order of the entry array -- rows and lengths by id; what this kernel cannot finish either goes on defer_list (a SECOND list,
 // counted in CNT_DEFERRED2).
-template <bool STATS, int EQ, int KF, bool BYKEY, bool LIST = false>
+// BYID (with LIST; option pile_stream_by_id): the same pass for a build the pile path keeps in its PURE form, which has no entry array: entry j of the
+// key order is taken by id as k_probe_clustered's BYID form takes it (by_id_pair, entry_by_id).  The (key, id) loads are issued where the entry
+// loads are issued otherwise; the row loads, which wait for the id, come behind the staging of the next quad -- one more dependent miss per round.
+// The mixed form keeps the entry-array instance: by id it would read ~17 random rows again per source for one source in eight.
+template <bool STATS, int EQ, int KF, bool BYKEY, bool LIST = false, bool BYID = false>
 __global__ void __launch_bounds__(PROBE_WAVES * 64, clq_occ(EQ, KF, BYKEY))
 k_probe_stream(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__restrict__ store, const uint4 *__restrict__ dir,
                const uint2 *__restrict__ runs, const uint8_t *__restrict__ nruns, int32_t src_begin_a, int32_t src_end_a, ProbeOut o,
                int32_t *__restrict__ defer_list, uint32_t defer_cap, const unsigned long long *__restrict__ pile_cnt,
-               const int32_t *__restrict__ src_list, const unsigned long long *__restrict__ src_count) {
+               const int32_t *__restrict__ src_list, const unsigned long long *__restrict__ src_count, ByIdEntries by) {
     static_assert(!(LIST && (BYKEY || STATS)), "list mode: ids from a list, no statistics build");
+    static_assert(!BYID || LIST, "entries by id: list mode only");
     // the pile kernel (prefsuf_pile.hip) was launched in front of this one and takes the build unless most buckets are irregular: the
     // same test on the same two counters, so exactly one of the two kernels does the work -- decided on the device, from this build's data
     if (!LIST && pile_cnt != nullptr && !pile_cnt_declines(pile_cnt)) return;
-    if (LIST && (pile_cnt == nullptr || !pile_cnt_mixed(pile_cnt))) return;
+    if (LIST && !BYID && (pile_cnt == nullptr || !pile_cnt_mixed(pile_cnt))) return;
+    if (BYID && (pile_cnt == nullptr || pile_cnt_declines(pile_cnt) || pile_cnt_mixed(pile_cnt))) return;       // the pure form only
     const int32_t src_begin = LIST ? 0 : src_begin_a;
     const int32_t src_end = LIST ? (int32_t) min(*src_count, (unsigned long long) src_end_a) : src_end_a;       // (list mode: src_end_a = the list's capacity)
     if (LIST && src_end <= 0) return;
@@ -993,13 +1019,18 @@ k_probe_stream(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__restri
         }
         const size_t ei = ev ? (size_t) min(rp.z + (uint32_t) hl, (uint32_t) nd.n - 1u) : (size_t) 0;      // clamped: a corrupt directory must not fault
         uint32_t ew[4 * EQ];
+        uint32_t e_key = 0u, e_id = 0u;
+        if constexpr (BYID) by_id_pair(by, ei, (uint32_t) nd.n, e_key, e_id);
+        else {
 #pragma unroll
-        for (int c = 0; c < EQ; c++) { const uint4 v = store[ei * EQ + c]; ew[4 * c] = v.x; ew[4 * c + 1] = v.y; ew[4 * c + 2] = v.z; ew[4 * c + 3] = v.w; }
+            for (int c = 0; c < EQ; c++) { const uint4 v = store[ei * EQ + c]; ew[4 * c] = v.x; ew[4 * c + 1] = v.y; ew[4 * c + 2] = v.z; ew[4 * c + 3] = v.w; }
+        }
         // ---- (3) the quad after quad 1: rows staged into the free buffer, index loads issued behind the entry loads ----
         uint32_t nbk = 0;
         uint4 nrec;
         if (have2) nbk = stage(b2, nB, nlenB, nnr_eff, nword0, nrun);
         index_loads(nbk, nrec);
+        if constexpr (BYID) entry_by_id<EQ>(nd, by.uniform_meta, cc.idx_shift - CL_MBITS, e_key, e_id, ew);      // (every lane, at its clamped id)
         // ---- (4) verify: one entry per lane ----
         const uint32_t id = ew[4 * EQ - 3], eh = ew[4 * EQ - 2], meta = ew[4 * EQ - 1];
         const int lenC = (int) ((meta >> 8) & 0xFFFu);
@@ -1045,6 +1076,10 @@ k_probe_stream(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__restri
                     const int t = min(max(ws - KF, 0), WC - KF);
 #pragma unroll
                     for (int k = 0; k < 5; k++) x[k] = ov[t + k];
+                } else if constexpr (BYID) {
+                    const uint32_t *er = nd.words + (size_t) id * nd.stride;                       // C's own row (no entry array)
+#pragma unroll
+                    for (int k = 0; k < 5; k++) x[k] = ws + k < nd.stride ? er[ws + k] : 0u;
                 } else {
                     const uint32_t *er = reinterpret_cast<const uint32_t *>(store + ei * EQ);
 #pragma unroll
@@ -1400,7 +1435,7 @@ void launch_probe_stream(const NodesDev &nd, const PrefSufCfg &cfg, const Cluste
     o.slot_stride = slot_stride;
     const uint4 *st = (const uint4 *) store;
 #define CLQ_LAUNCH(ST, E, K, BK) hipLaunchKernelGGL((k_probe_stream<ST, E, K, BK>), grid, block, 0, s, nd, cfg, cc, st, (const uint4 *) dir, (const uint2 *) runs, nruns, src_begin, src_end, o, defer_list, defer_cap, pile_cnt, \
-                                                    (const int32_t *) nullptr, (const unsigned long long *) nullptr)
+                                                    (const int32_t *) nullptr, (const unsigned long long *) nullptr, ByIdEntries{nullptr, nullptr, 0u, nullptr})
 #define CLQ_ORDER(ST, E, K) do { if (by_key) CLQ_LAUNCH(ST, E, K, true); else CLQ_LAUNCH(ST, E, K, false); } while (0)
 #define CLQ_STATS(E, K) do { if (cfg.stats) CLQ_ORDER(true, E, K); else CLQ_ORDER(false, E, K); } while (0)
     if (eq == 3 && kf == 5)      CLQ_STATS(3, 5);
@@ -1416,30 +1451,40 @@ void launch_probe_stream(const NodesDev &nd, const PrefSufCfg &cfg, const Cluste
 
 // The mixed form of a build the pile path keeps (prefsuf_cluster_device.h: pile_cnt_mixed): k_probe_stream over the sources k_pile_probe handed on
 // (src_list[0 .. *src_count), the count on the device); what it cannot finish goes on defer2 (counted in CNT_DEFERRED2), and k_defer_swap puts that
-// list and its count where the general kernel looks for its sources.  Both kernels leave at once for a build that is not of the mixed form.
+// list and its count where the general kernel looks for its sources.  The PURE form takes the same pass with the entries by id (by_id: option
+// pile_stream_by_id; it has no entry array) -- both instances are launched, the form is decided on the device, the one that does not apply and, for
+// a build the pile path declined, the swap leave at once.
 __global__ void __launch_bounds__(256) k_defer_swap(const unsigned long long *__restrict__ pile_cnt, unsigned long long *__restrict__ counters, const int32_t *__restrict__ list2,
-                                                     int32_t *__restrict__ list, uint32_t cap) {
-    if (!pile_cnt_mixed(pile_cnt)) return;
+                                                     int32_t *__restrict__ list, uint32_t cap, bool pure_too /* the by-id instance ran for the pure form */) {
+    if (!(pile_cnt_mixed(pile_cnt) || (pure_too && !pile_cnt_declines(pile_cnt)))) return;
     const uint64_t n2 = min(counters[CNT_DEFERRED2], (unsigned long long) cap);
     for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (uint64_t) gridDim.x * blockDim.x) list[i] = list2[i];
     if (blockIdx.x == 0 && threadIdx.x == 0) { counters[CNT_DEFERRED_PILE] = counters[CNT_DEFERRED]; counters[CNT_DEFERRED] = n2; }
 }
 
-void launch_probe_stream_list(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int eq, const void *store, const void *dir, const void *runs, const uint8_t *nruns,
+// skeys / sids / uniform_len: the sorted (key, id) pairs and the one read length, as launch_probe_clustered gets them; by_id = false (or no pairs):
+// the pure form keeps the general kernel alone.  Returns whether the by-id instance was launched (what the swap then did for a pure build).
+bool launch_probe_stream_list(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int eq, const void *store, const void *dir, const void *runs, const uint8_t *nruns,
                               int32_t *src_list, uint32_t list_cap, unsigned long long *counters, int n_cu, uint32_t *deg, unsigned long long *first,
-                              unsigned long long *second, int32_t *defer2, const unsigned long long *pile_cnt, hipStream_t s, uint32_t slot_stride, int32_t src_base) {
-    if (eq != 3 || list_cap == 0) return;                  // (the pile path takes entries of three pieces only: pile_plan)
+                              unsigned long long *second, int32_t *defer2, const unsigned long long *pile_cnt, hipStream_t s, uint32_t slot_stride, int32_t src_base,
+                              const uint32_t *skeys, const uint32_t *sids, int uniform_len, bool by_id) {
+    if (eq != 3 || list_cap == 0) return false;            // (the pile path takes entries of three pieces only: pile_plan)
     const int kf = (2 * cfg.Lmin) >> 5;
     const int kfs = (kf == 5 || kf == 3) ? kf : 0;
     const dim3 grid((unsigned) std::max(1, n_cu) * clq_occ(3, kfs, false)), block(PROBE_WAVES * 64);
     ProbeOut o{nullptr, nullptr, 0, counters, deg, first, src_base, second};       // (src_base: the listed ids are those of a rank's range, the slots count from its first)
     o.slot_stride = slot_stride;
-#define CLQ_LIST(K) hipLaunchKernelGGL((k_probe_stream<false, 3, K, false, true>), grid, block, 0, s, nd, cfg, cc, (const uint4 *) store, (const uint4 *) dir, (const uint2 *) runs, nruns, 0, \
-                                       (int32_t) std::min<uint32_t>(list_cap, 0x7FFFFFFFu), o, defer2, list_cap, pile_cnt, (const int32_t *) src_list, (const unsigned long long *) (counters + CNT_DEFERRED))
-    if (kf == 5) CLQ_LIST(5); else if (kf == 3) CLQ_LIST(3); else CLQ_LIST(0);
+    const bool pure_too = by_id && skeys && sids && uniform_len > 0 && nd.n > 0;
+    const ByIdEntries by{skeys, sids, uniform_len > 0 ? (((uint32_t) uniform_len << 8) | CL_META_FROM) : 0u, pile_cnt};
+#define CLQ_LIST(K, BI) hipLaunchKernelGGL((k_probe_stream<false, 3, K, false, true, BI>), grid, block, 0, s, nd, cfg, cc, (const uint4 *) store, (const uint4 *) dir, (const uint2 *) runs, nruns, 0, \
+                                           (int32_t) std::min<uint32_t>(list_cap, 0x7FFFFFFFu), o, defer2, list_cap, pile_cnt, (const int32_t *) src_list, (const unsigned long long *) (counters + CNT_DEFERRED), by)
+#define CLQ_BOTH(K) do { CLQ_LIST(K, false); if (pure_too) CLQ_LIST(K, true); } while (0)
+    if (kf == 5) CLQ_BOTH(5); else if (kf == 3) CLQ_BOTH(3); else CLQ_BOTH(0);
+#undef CLQ_BOTH
 #undef CLQ_LIST
     // the list the general kernel reads: (list2, CNT_DEFERRED2) -> (list, CNT_DEFERRED)
-    hipLaunchKernelGGL(k_defer_swap, dim3(1024), dim3(256), 0, s, pile_cnt, counters, (const int32_t *) defer2, src_list, list_cap);
+    hipLaunchKernelGGL(k_defer_swap, dim3(1024), dim3(256), 0, s, pile_cnt, counters, (const int32_t *) defer2, src_list, list_cap, pure_too);
+    return pure_too;
 }
 
 // src_list == null: the sources are the ids src_begin .. src_end - 1; else the ids src_list[src_begin .. src_end - 1]

@@ -81,13 +81,13 @@ enum Counter {
     CNT_LOCAL_OVERFLOW,    // sources with more raw overlaps than the source-side reduction holds (LDS; in the second pass: its global slice)
     CNT_LOCAL_GENERIC,     // sources that took the all-pairs path of the source-side reduction
     CNT_LOCAL_MAXITEMS,    // largest number of raw overlaps of one source seen by the source-side reduction
-    CNT_DEFERRED,          // clustered probe, pair kernel: sources handed to the general kernel
+    CNT_DEFERRED,          // clustered probe, pair kernel: sources handed to the general kernel (pile path: by k_pile_probe, until k_defer_swap puts the second list's count here)
     CNT_ROUNDS,            // clustered probe, quad kernel: rounds (wave iterations), statistics builds only
     CNT_PILE_BUCKETS,      // pile path: non-empty buckets of the entry array / those it does not take (copied from k_pile_build's counters by k_pile_probe)
     CNT_PILE_IRREGULAR,
     CNT_PILE_OWN,          // pile path: entries that read a run list of their own (the list-driven key pass behind k_pile_runs_consensus)
-    CNT_DEFERRED2,         // mixed form: sources k_probe_stream (list mode) handed on; k_defer_swap moves that list and count to the first list's place
-    CNT_DEFERRED_PILE,     // mixed form: sources k_pile_probe handed on (CNT_DEFERRED before the swap)
+    CNT_DEFERRED2,         // mixed form, and the pure form with option pile_stream_by_id: sources k_probe_stream (list mode) handed on; k_defer_swap moves that list and count to the first list's place
+    CNT_DEFERRED_PILE,     // the same forms: sources k_pile_probe handed on (CNT_DEFERRED before the swap)
     CNT_TOTAL = 24
 };
 constexpr int LOCAL_SLOTS_MAX = 4;                         // edges of a source k_probe_stream writes to slots itself (first[] + up to three in second[]: ProbeOut::slot_stride; eight measured no better)

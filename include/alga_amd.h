@@ -181,6 +181,11 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                pass of its own (k_pile_deg) right behind the probe (A/B and tests)
  *   "pile_probe_lean"            default 1: k_pile_probe takes a source's row from its home run in slot 0 only and looks for the last mismatch
  *                                below position 64 only (a mismatch from 64 on clears the whole offset set); 0: the round-5 kernel (A/B and tests)
+ *   "pile_stream_by_id"          1: a build the pile path keeps in its PURE form sends the sources k_pile_probe hands on through k_probe_stream (list
+ *                                mode) before the general kernel, as the mixed form does -- the entries taken by id from the sorted (key, id) pairs, since
+ *                                the pure form has no entry array; alga_prefsuf_stats.pile_deferred is then what the pile kernel handed on and
+ *                                deferred_sources what the general kernel was given; default 0 (until the pass has been measured on the GPU): the
+ *                                general kernel takes them all
  *   "pile_check"                 tests only.  != 0: every node gets its own run list as well and every first-group member's is compared with its pile's list
  *                                clipped to the member's windows (alga_prefsuf_stats.pile_list_checked / pile_list_mismatch)
  *   "pile_skip_gather"           default 1: a build the pile path keeps has no entry array (the rows in key order, 48 bytes per node: its kernels
