@@ -761,6 +761,12 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
     } else if (!strcmp(name, "unitig_ruling")) {
         if (value < -1 || value > 1) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option unitig_ruling: -1, 0 or 1");
         e->opt_unitig_ruling = (int) value;
+    } else if (!strcmp(name, "correct_slice_keys")) {
+        if (value < 1 || value > (1ll << 31)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option correct_slice_keys: 1 .. 2^31");
+        e->opt_correct_slice_keys = value;
+    } else if (!strcmp(name, "correct_dir_bits")) {
+        if (value < 0 || value > 28) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option correct_dir_bits: 0 (auto) or 1 .. 28");
+        e->opt_correct_dir_bits = (int) value;
     } else if (!strcmp(name, "auto_reduction_per_target")) {
         e->opt_force_per_target = value != 0;
     } else return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown option");

@@ -160,10 +160,9 @@ extern "C" int alga_preprocess_nodes(alga_engine *e, const alga_preprocess_input
 
 // Files -> node set resident in HBM: the host only maps the files and moves their bytes; line splitting, trimming, the N / STR
 // filters, packing, reverse complements (N2, parse_kernels.hip) and duplicate / prefix removal + compaction (N1) run on the GPU.
-extern "C" int alga_ingest_device(alga_engine *e, const char *file1, const char *file2, const alga_ingest_params *p, alga_device_node_set *out,
-                                  alga_ingest_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
+// cp != nullptr: the reads are corrected (engine_correct.hip) between the parse kernels and the removals
+static int ingest_impl(alga_engine *e, const char *file1, const char *file2, const alga_ingest_params *p, const alga_correct_params *cp, alga_device_node_set *out,
+                       alga_ingest_info *info, alga_correct_info *cinfo) {
     if (!file1 || !p || !out || !info) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "arguments must not be NULL");
     memset(out, 0, sizeof(*out));
     memset(info, 0, sizeof(*info));
@@ -266,11 +265,34 @@ extern "C" int alga_ingest_device(alga_engine *e, const char *file1, const char 
     }
     info->min_overlap = Lmin; info->rsoemo = rso; info->li_kmer_length = likl;
     info->paired = paired ? 1 : 0;
-    rc = preprocess_impl(e, (const uint32_t *) e->pp_rows.p, W, (int32_t *) e->pp_len.p, n, (int) hc[5], hc[6], p->remove_pref_reads, 3 + likl, s, out);
+    // a fix changes one base of a live pair: max_len and live stay what k_len_stats found (taken now: the correction reads its own counts back
+    // through the same pinned block)
+    const int max_len = (int) hc[5];
+    const uint64_t live = hc[6];
+    if (cp && (rc = alga_correct_impl(e, (uint32_t *) e->pp_rows.p, W, (const int32_t *) e->pp_len.p, (int64_t) n, cp, s, cinfo))) return rc;
+    const auto t1c = clk::now();
+    rc = preprocess_impl(e, (const uint32_t *) e->pp_rows.p, W, (int32_t *) e->pp_len.p, n, max_len, live, p->remove_pref_reads, 3 + likl, s, out);
     if (rc) return rc;
     const auto t2 = clk::now();
     info->ms_upload = ms_upload;
     info->ms_parse = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    info->ms_preprocess = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    info->ms_preprocess = std::chrono::duration<double, std::milli>(t2 - t1c).count();
     return ALGA_OK;
+}
+
+extern "C" int alga_ingest_device(alga_engine *e, const char *file1, const char *file2, const alga_ingest_params *p, alga_device_node_set *out,
+                                  alga_ingest_info *info) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    return ingest_impl(e, file1, file2, p, nullptr, out, info, nullptr);
+}
+
+extern "C" int alga_ingest_corrected_device(alga_engine *e, const char *file1, const char *file2, const alga_ingest_params *p, const alga_correct_params *cp,
+                                            alga_device_node_set *out, alga_ingest_info *info, alga_correct_info *cinfo) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    if (cinfo) *cinfo = alga_correct_info{};
+    int rc;
+    if ((rc = alga_correct_check_params(e, cp))) return rc;
+    return ingest_impl(e, file1, file2, p, cp, out, info, cinfo);
 }

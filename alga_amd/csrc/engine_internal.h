@@ -167,6 +167,11 @@ struct alga_engine {
     bool        fc_valid = false;                  // the buffers hold the final set of the unitig result and consensus at hand
     uint64_t    fc_n_accepted = 0;
     int         opt_consensus_max_blocks = 0;      // option "consensus_max_blocks": cap on the grids of the consensus kernels (0: their own); tests lower it to make small inputs stride
+    // read error correction (engine_correct.hip): counters, the per-block tables of the histogram / run-head / fix kernels, the column sums, a slice's
+    // keys before and after the sort, its solid flags and their scan, the solid keys of all slices, their directory
+    DevBuf      cr_cnt, cr_table, cr_hist, cr_keys[2], cr_flag, cr_pos, cr_solid, cr_dir;
+    int64_t     opt_correct_slice_keys = 1ll << 28;   // option "correct_slice_keys": occurrences a slice of the k-mer count holds (a single bin above it is a slice of its own)
+    int         opt_correct_dir_bits = 0;             // option "correct_dir_bits": bits of the solid keys' directory, 0 = about two keys per bucket (tests force long and empty buckets)
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;
@@ -297,6 +302,12 @@ struct AlgaTextJob {
     std::function<void(const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s)> format;
 };
 int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info);
+
+// engine_correct.hip: the correction of device-resident rows in the parser's layout, in place (what alga_correct_reads_device and the corrected
+// ingest share); the parameters are checked by the callers (alga_correct_check_params)
+int alga_correct_check_params(alga_engine *e, const alga_correct_params *p);
+int alga_correct_impl(alga_engine *e, uint32_t *d_rows, int32_t stride, const int32_t *d_len, int64_t n_nodes, const alga_correct_params *p, hipStream_t s,
+                      alga_correct_info *info);
 
 inline int alga_check_launch(alga_engine *e, const char *what) {
     hipError_t err = hipGetLastError();

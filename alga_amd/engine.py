@@ -98,6 +98,21 @@ class IngestInfo(C.Structure):
                 ("ms_preprocess", C.c_double), ("ms_upload", C.c_double)]
 
 
+class CorrectParams(C.Structure):
+    """alga_correct_params"""
+    _fields_ = [("k", C.c_int32), ("solid_min", C.c_int32), ("min_run", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CorrectInfo(C.Structure):
+    """alga_correct_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("reads", "kmers_total", "kmers_distinct", "kmers_solid", "runs", "runs_fixed", "runs_ambiguous",
+                                          "runs_no_candidate", "runs_skipped", "reads_changed", "slices")] + \
+               [(k, C.c_double) for k in ("ms_count", "ms_index", "ms_fix", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PkbParams(C.Structure):
     """alga_pkb_params"""
     _fields_ = [("min_overlap_area", C.c_int32), ("max_offset_pct", C.c_int32), ("min_identity_pct", C.c_int32),
@@ -161,7 +176,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
            "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device",
            "alga_contigs_device", "alga_contig_trim_device", "alga_final_contigs_device", "alga_write_final_fasta_device",
-           "alga_extend_contigs_device", "alga_extend_seams_get"]
+           "alga_extend_contigs_device", "alga_extend_seams_get",
+           "alga_correct_default_params", "alga_correct_reads_device", "alga_correct_parsed_reads", "alga_ingest_corrected_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -502,6 +518,12 @@ def load_library():
                                                C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ExtendInfo)]
     lib.alga_extend_seams_get.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ExtendSeamsC)]
     lib.alga_write_final_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.POINTER(FinalContigsC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_correct_default_params.argtypes = [C.POINTER(CorrectParams)]
+    lib.alga_correct_default_params.restype = None
+    lib.alga_correct_reads_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(CorrectParams), C.c_void_p, C.POINTER(CorrectInfo)]
+    lib.alga_correct_parsed_reads.argtypes = [C.c_void_p, C.POINTER(ParsedReads), C.POINTER(CorrectParams), C.POINTER(CorrectInfo)]
+    lib.alga_ingest_corrected_device.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(IngestParams), C.POINTER(CorrectParams), C.POINTER(DeviceNodeSet),
+                                                 C.POINTER(IngestInfo), C.POINTER(CorrectInfo)]
     _LIB = lib
     return lib
 
@@ -659,16 +681,58 @@ class Engine:
         self._check(self._lib.alga_preprocess_nodes(self._h, C.byref(inp), C.byref(out)))
         return out
 
-    def ingest_device(self, file1, file2=None, **kw):
+    def ingest_device(self, file1, file2=None, correct=None, **kw):
         """The whole input stage on the GPU (alga_ingest_device): files -> (DeviceNodeSet, info dict); raises AlgaError -7 for the
-        inputs that stage does not take (file types other than .fasta / .fastq / .fq, remove_reads_with_n = 0)."""
+        inputs that stage does not take (file types other than .fasta / .fastq / .fq, remove_reads_with_n = 0).
+        correct: a dict of k / solid_min / min_run (any subset; {} = the defaults) -- the reads are corrected between the parse kernels and
+        the removals (alga_ingest_corrected_device), and the info dict gets the correction's counters under "correct"."""
         p = IngestParams()
         self._lib.alga_ingest_default_params(C.byref(p))
         for k, v in kw.items():
             setattr(p, k, v)
         ds, info = DeviceNodeSet(), IngestInfo()
-        self._check(self._lib.alga_ingest_device(self._h, file1.encode(), (file2 or "").encode() or None, C.byref(p), C.byref(ds), C.byref(info)))
-        return ds, {k: getattr(info, k) for k, _ in IngestInfo._fields_}
+        f1, f2 = file1.encode(), (file2 or "").encode() or None
+        if correct is None:
+            self._check(self._lib.alga_ingest_device(self._h, f1, f2, C.byref(p), C.byref(ds), C.byref(info)))
+            return ds, {k: getattr(info, k) for k, _ in IngestInfo._fields_}
+        cp, ci = self.correct_params(**correct), CorrectInfo()
+        self._check(self._lib.alga_ingest_corrected_device(self._h, f1, f2, C.byref(p), C.byref(cp), C.byref(ds), C.byref(info), C.byref(ci)))
+        d = {k: getattr(info, k) for k, _ in IngestInfo._fields_}
+        d["correct"] = ci.as_dict()
+        return ds, d
+
+    # ---- read error correction by the k-mer spectrum (the definition: include/alga_amd.h) -----
+    @staticmethod
+    def correct_params(k=21, solid_min=3, min_run=1):
+        return CorrectParams(int(k), int(solid_min), int(min_run), 0)
+
+    def correct_reads(self, rows, lens, k=21, solid_min=3, min_run=1):
+        """rows[2R, stride] u32 / lens[2R] i32 in the parser's layout on the host (alga_correct_parsed_reads) -> (new rows, info dict);
+        the arguments are not modified."""
+        rows = np.array(rows, dtype=np.uint32, order="C", copy=True)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        n = int(lens.shape[0])
+        rows = rows.reshape(n, -1) if n else rows.reshape(0, rows.shape[1] if rows.ndim == 2 else 1)
+        pr = ParsedReads()
+        pr.n_nodes, pr.stride_words = n, int(rows.shape[1])
+        pr.rows = rows.ctypes.data_as(C.POINTER(C.c_uint32))
+        pr.len = lens.ctypes.data_as(C.POINTER(C.c_int32))
+        cp, ci = self.correct_params(k, solid_min, min_run), CorrectInfo()
+        self._check(self._lib.alga_correct_parsed_reads(self._h, C.byref(pr), C.byref(cp), C.byref(ci)))
+        return rows, ci.as_dict()
+
+    def correct_reads_device(self, rows_t, lens_t, k=21, solid_min=3, min_run=1, stream=None):
+        """rows_t int32 [2R, stride] / lens_t int32 [2R]: contiguous torch device tensors in the parser's layout, corrected in place
+        (alga_correct_reads_device) -> info dict"""
+        import torch
+        assert rows_t.dtype == torch.int32 and lens_t.dtype == torch.int32 and rows_t.is_contiguous() and lens_t.is_contiguous()
+        n = int(lens_t.shape[0])
+        assert rows_t.dim() == 2 and int(rows_t.shape[0]) == n
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+        cp, ci = self.correct_params(k, solid_min, min_run), CorrectInfo()
+        self._check(self._lib.alga_correct_reads_device(self._h, _ptr(rows_t), int(rows_t.shape[1]), _ptr(lens_t), n, C.byref(cp),
+                                                        C.c_void_p(stream) if stream else None, C.byref(ci)))
+        return ci.as_dict()
 
     # ---- host buffers in, edges out (the drop-in call) --------------------------------------
     def prefsuf_host(self, words, lens, min_overlap, rsoe_min_overlap, align_from=None, align_to=None, collect_stats=False,

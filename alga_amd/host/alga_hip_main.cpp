@@ -6,6 +6,7 @@
 //            [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200] [--consensus_min_votes=3]
 //            [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N]
 //            [--contigs_final=final.fasta] [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]
+//            [--correct_reads=0|1] [--correct_k=21] [--correct_solid=3] [--corrected_reads=reads.fasta]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -49,6 +50,11 @@
 // --paired_extend=1 (default 0; honoured by --contigs=, --contigs_gfa= and --contigs_final=; not passed through): with --file2 the contigs are
 // extended through the junctions that paired reads support (alga_extend_contigs_device: min_chain_weight = int(2 * mean length of the live reads),
 // 5 connections, inserts up to 1000) before the GFA, the consensus and the final set are made.  Without --file2 it changes nothing and says so.
+// --correct_reads=1 (default 0: every invocation without it behaves as before): the reads are parsed on the host cores, corrected on the GPU
+// (alga_correct_parsed_reads: k-mer spectrum with --correct_k, solid from --correct_solid occurrences on, one substitution per weak run) and join
+// the GPU again at the duplicate / prefix removal; the counters go to stderr.  --corrected_reads=PATH writes the corrected forward reads as
+// FASTA (from the rows the call brought back; the sequences are the trimmed ones: a run on that file needs --retl=0 --retr=0).  None of the four
+// is passed through, and with --alga= they are refused: stock ALGA would read the original files, whose nodes are not this graph's.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -65,6 +71,14 @@
 #include "GraphCreatorHIP.hpp"
 #include "ingest.hpp"
 
+static const char *USAGE =
+    "alga_hip --file1=reads.fasta [--file2=mates.fasta] --output=contigs.fasta [--threads=N] [--error_rate=R] [--serialize=1] [-l MINOVERLAP] [--rsoemo=N]\n"
+    "         [--scale=F] [--retl=N --retr=N] [--remove_reads_with_n=0|1] [--rna=0|1] [--device=K] [--gpus=N | --gpu-list=0,1,...] [--alga=/path/to/ALGA]\n"
+    "         [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1] [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200]\n"
+    "         [--consensus_min_votes=3] [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N] [--contigs_final=final.fasta]\n"
+    "         [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]\n"
+    "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n";
+
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
     if (strncmp(arg, name, n) == 0 && arg[n] == '=') { val = arg + n + 1; return true; }
@@ -77,6 +91,10 @@ int main(int argc, char **argv) {
     alga_host::IngestParams ip;
     double error_rate = 0.0;
     int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1, contigs_new_reads_percent = 95, contigs_trim_threshold = 25, paired_extend = 0;
+    int correct_reads = 0;
+    std::string corrected_reads;
+    alga_correct_params crp;
+    alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
     std::vector<std::string> passthrough;
     for (int i = 1; i < argc; i++) {
@@ -111,6 +129,11 @@ int main(int argc, char **argv) {
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
         else if (opt(a, "--consensus_min_length", v)) consensus_min_length = atoi(v.c_str());
         else if (opt(a, "--consensus_min_votes", v)) consensus_min_votes = atoi(v.c_str());
+        else if (opt(a, "--correct_reads", v)) correct_reads = atoi(v.c_str());
+        else if (opt(a, "--correct_k", v)) crp.k = atoi(v.c_str());
+        else if (opt(a, "--correct_solid", v)) crp.solid_min = atoi(v.c_str());
+        else if (opt(a, "--corrected_reads", v)) corrected_reads = v;
+        else if (!strcmp(a, "--help") || !strcmp(a, "-h")) { fprintf(stderr, "%s", USAGE); return 2; }
         else if (!strcmp(a, "-l") && i + 1 < argc) ip.min_overlap = atoi(argv[++i]);
         else { fprintf(stderr, "alga_hip: unrecognized option '%s'\n", a); return 2; }
         // the hand-off to stock ALGA drops the error-rate option: the supplement it switches on (src/Params.cpp:357-359) has
@@ -118,10 +141,17 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
+    if (crp.k < 5 || crp.k > 31 || !(crp.k & 1)) { fprintf(stderr, "alga_hip: --correct_k must be odd and in [5, 31] (got %d)\n", crp.k); return 2; }
+    if (crp.solid_min < 1) { fprintf(stderr, "alga_hip: --correct_solid must be >= 1 (got %d)\n", crp.solid_min); return 2; }
+    if (!correct_reads && !corrected_reads.empty()) { fprintf(stderr, "alga_hip: --corrected_reads= needs --correct_reads=1\n"); return 2; }
+    if (correct_reads && !alga_exe.empty()) {
+        fprintf(stderr, "alga_hip: --correct_reads=1 cannot be combined with --alga=: stock ALGA would read the original files, whose nodes are not the corrected graph's\n");
+        return 2;
+    }
     const std::string graph = alga_host::test_name(file1, ip.scale, ip.remove_reads_with_n) + "_beforeSimplifier.graph";
     if (!alga_exe.empty()) {
         // The hand-off is the dump: it is always written, and a file of that name left behind by an earlier run must not be
@@ -158,7 +188,8 @@ int main(int argc, char **argv) {
     std::vector<alga_device_node_set> rank_nodes((size_t) n_ranks);
     std::vector<alga_ingest_info> rank_info((size_t) n_ranks);
     std::vector<int> rank_rc((size_t) n_ranks, ALGA_OK);
-    {
+    if (correct_reads) rank_rc.assign((size_t) n_ranks, ALGA_ERR_UNSUPPORTED);       // the host parser, the correction, then the removals on every GPU
+    else {
         std::vector<std::thread> th;
         auto ingest = [&](int r) {
             alga_engine *er = multi ? alga_multi_engine(multi, r) : engine;
@@ -181,6 +212,32 @@ int main(int argc, char **argv) {
         std::string err = alga_host::parse(file1, file2, ip, parsed);
         if (!err.empty()) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
         t1 = clk::now();
+        if (correct_reads) {
+            alga_parsed_reads pr{};
+            pr.n_nodes = (int64_t) (2 * parsed.R); pr.stride_words = parsed.W; pr.rows = parsed.rows.data(); pr.len = parsed.len.data();
+            alga_correct_info ci;
+            if (alga_correct_parsed_reads(engine, &pr, &crp, &ci) != ALGA_OK) { fprintf(stderr, "%s\n", alga_last_error(engine)); return 1; }
+            fprintf(stderr, "Reads corrected (k %d, solid from %d): %llu reads, %llu k-mers (%llu distinct, %llu solid) in %llu slices; %llu weak runs: %llu fixed, "
+                    "%llu ambiguous, %llu without candidate, %llu skipped; %llu reads changed; device ms: count %.3f index %.3f fix %.3f, call %.1f ms wall\n", crp.k,
+                    crp.solid_min, (unsigned long long) ci.reads, (unsigned long long) ci.kmers_total, (unsigned long long) ci.kmers_distinct,
+                    (unsigned long long) ci.kmers_solid, (unsigned long long) ci.slices, (unsigned long long) ci.runs, (unsigned long long) ci.runs_fixed,
+                    (unsigned long long) ci.runs_ambiguous, (unsigned long long) ci.runs_no_candidate, (unsigned long long) ci.runs_skipped,
+                    (unsigned long long) ci.reads_changed, ci.ms_count, ci.ms_index, ci.ms_fix, ci.ms_total);
+            if (!corrected_reads.empty()) {                // not a hot path: the host writes from the rows that came back
+                FILE *f = fopen(corrected_reads.c_str(), "w");
+                if (!f) { fprintf(stderr, "alga_hip: cannot write %s\n", corrected_reads.c_str()); return 1; }
+                std::string seq;
+                for (size_t r = 0; r < parsed.R; r++) {
+                    const int32_t l = parsed.len[2 * r + 1];
+                    if (l <= 0) continue;
+                    const uint32_t *w = parsed.row(2 * r + 1);
+                    seq.resize((size_t) l);
+                    for (int32_t j = 0; j < l; j++) seq[(size_t) j] = "ACGT"[(w[j >> 4] >> ((j & 15) << 1)) & 3u];
+                    fprintf(f, ">read_%zu\n%s\n", r, seq.c_str());
+                }
+                if (fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", corrected_reads.c_str()); return 1; }
+            }
+        }
         alga_preprocess_input pin{parsed.rows.data(), parsed.W, parsed.len.data(), (int64_t) (2 * parsed.R), ip.remove_pref_reads, 3 + parsed.li_kmer_length};
         for (int r = 0; r < n_ranks; r++) {
             alga_engine *er = multi ? alga_multi_engine(multi, r) : engine;

@@ -195,6 +195,10 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *   "local_big_max"              largest per-wave item slice of the SOURCE_SIDE second pass (default -1 = built-in 4096); beyond it
  *                                the build takes PER_TARGET
  *   "auto_reduction_per_target"  != 0: alga_prefsuf_params.reduction == AUTO resolves to PER_TARGET
+ *   "correct_slice_keys"         1..2^31 (default 2^28): alga_correct_reads_device counts the k-mers in slices of the key space of at most this many
+ *                                occurrences (a single histogram bin above it is a slice of its own); tests lower it to run many slices
+ *   "correct_dir_bits"           0 (default: about two keys per bucket) or 1..28: bits of the directory over the solid k-mers; tests force long
+ *                                buckets and empty ones
  *   "gfa_chunk_mb"               1..4096 (default 256): alga_write_gfa_device formats the text in chunks of at most this many MB (one device buffer,
  *                                two pinned host buffers of that size; a chunk is never smaller than twice the longest line)
  *   "unitig_ruling"              default -1: the list ranking of alga_unitigs_device ranks a RULING SET first -- the heads and one node in 64 walk to the
@@ -1087,6 +1091,65 @@ int  alga_final_contigs_device(alga_engine *e, const alga_unitigs *u, const alga
                                int32_t trim_threshold, int32_t flags /* 0 */, void *hip_stream, alga_final_contigs *out, alga_final_info *info /* may be NULL */);
 int  alga_write_final_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin, const char *path,
                                    alga_gfa_info *info /* may be NULL */);
+
+/* ---- read error correction: k-mer spectrum, one substitution per weak run ---------------------------
+ * The stage between the parser and the duplicate / prefix removal.  A read with one wrong base has no exact overlap through that base; a base
+ * that a spectrum of the reads themselves decides is put right here, before anything is built on it.  (The reference's own corrector,
+ * src/Corrector/ReadCorrector.cpp, cannot be reached from its command line and its ties follow a hash map's iteration: this is a definition of
+ * its own, free of any order, and tests/correct_checker.py states it literally.)
+ *
+ * In: the parser's node layout (alga_parsed_reads): n_nodes (even) rows of 2-bit bases, LSB first, stride_words apart; node 2r + 1 is read r,
+ * node 2r its reverse complement.  A pair with len < k (-1 and 0 included) takes no part and stays as it is.
+ *   1. Spectrum.  The canonical form of a k-mer is the smaller of the k-mer and its reverse complement under any fixed injective encoding
+ *      (nothing observable depends on which).  count[x] = occurrences of x over all k-mers of all forward reads (odd nodes) with len >= k;
+ *      x is SOLID iff count[x] >= solid_min.  The spectrum is that of the reads as they came in: fixes do not feed back into it.
+ *   2. Weak runs.  Of a forward read of length l, nk = l - k + 1; k-mer i (bases i .. i + k - 1) is weak iff its canonical form is not solid.
+ *      Runs are the maximal intervals [a, b] of weak k-mers of the unmodified read, len = b - a + 1.
+ *   3. The suspected base p of a run:
+ *        whole read   a == 0 && b == nk - 1    skipped
+ *        interior     a > 0  && b <  nk - 1    p = b, only if len == k; otherwise skipped
+ *        left end     a == 0 && b <  nk - 1    p = b, only if b <= k - 1; otherwise skipped
+ *        right end    a > 0  && b == nk - 1    p = a + k - 1, only if len <= k; otherwise skipped
+ *      and len < min_run is skipped in every case.
+ *   4. Candidates.  A base x != read[p] WORKS iff every k-mer a .. b of the read with read[p] := x (all other bases as they came in) is solid.
+ *      Exactly one x works: fixed.  None: no_candidate.  Two or three: ambiguous.  Nothing is written for the last two.
+ *   5. Output.  All fixes of a read are applied together, row 2r becomes the reverse complement of the new row 2r + 1; lengths, tail bits (zero)
+ *      and every other node are untouched.
+ *   6. Counters: alga_correct_info.
+ * The rule is strand-symmetric (left-end and right-end runs map onto each other), and the runs of one read are independent: the k-mers of one
+ * run never contain the p of another.  Two errors closer than k + 1 apart make one run longer than k and stay: one base per run is the only
+ * fix a spectrum alone decides.
+ *
+ * Checked on the device before anything is written (ALGA_ERR_INVALID_ARGUMENT, rows untouched): row 2r is the reverse complement of row
+ * 2r + 1, len[2r] == len[2r + 1], blocks of len <= stride_words.  k even or outside 5 .. 31, solid_min < 1, min_run < 1, n_nodes odd: the same
+ * answer.  The k-mers are counted in slices of the (mixed) key space of at most "correct_slice_keys" occurrences each (alga_engine_set_option;
+ * default 2^28; a single bin of the 4096 above that is a slice of its own and the buffers follow the largest slice); the solid keys are looked
+ * up through a directory of "correct_dir_bits" bits (0 = about two keys per bucket).  Neither option changes a result. */
+typedef struct {
+    int32_t k;                       /* odd, 5 .. 31; default 21                                                                      */
+    int32_t solid_min;               /* >= 1; default 3                                                                               */
+    int32_t min_run;                 /* >= 1; default 1                                                                               */
+    int32_t reserved;                /* 0                                                                                             */
+} alga_correct_params;
+typedef struct {
+    uint64_t reads;                  /* forward reads with len >= k                                                                   */
+    uint64_t kmers_total, kmers_distinct, kmers_solid;
+    uint64_t runs, runs_fixed, runs_ambiguous, runs_no_candidate, runs_skipped;
+    uint64_t reads_changed;
+    uint64_t slices;                 /* slices the count ran in (depends on "correct_slice_keys" alone)                               */
+    double   ms_count, ms_index, ms_fix;   /* device time (HIP events): histogram + slices, directory, k_cr_fix                       */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_correct_info;
+void alga_correct_default_params(alga_correct_params *p);
+/* in place on caller-owned device arrays */
+int  alga_correct_reads_device(alga_engine *e, uint32_t *d_rows, int32_t stride_words, const int32_t *d_len, int64_t n_nodes, const alga_correct_params *p,
+                               void *hip_stream, alga_correct_info *info /* may be NULL */);
+/* host arrays up, corrected, down again: what sits between alga_parse_files and alga_preprocess_nodes.  On a refusal pr is untouched. */
+int  alga_correct_parsed_reads(alga_engine *e, alga_parsed_reads *pr, const alga_correct_params *p, alga_correct_info *info /* may be NULL */);
+/* alga_ingest_device with the correction between its parse kernels and the duplicate / prefix removal (fixes make new duplicates and prefix
+ * reads: that is why the stage sits in front of their removal) */
+int  alga_ingest_corrected_device(alga_engine *e, const char *file1, const char *file2 /* may be NULL */, const alga_ingest_params *p, const alga_correct_params *cp,
+                                  alga_device_node_set *out, alga_ingest_info *info, alga_correct_info *cinfo /* may be NULL */);
 
 #ifdef __cplusplus
 }
