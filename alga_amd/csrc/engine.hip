@@ -767,6 +767,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
     } else if (!strcmp(name, "correct_dir_bits")) {
         if (value < 0 || value > 28) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option correct_dir_bits: 0 (auto) or 1 .. 28");
         e->opt_correct_dir_bits = (int) value;
+    } else if (!strcmp(name, "place_dir_bits")) {
+        if (value < 0 || value > 26) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option place_dir_bits: 0 (auto) or 1 .. 26");
+        e->opt_place_dir_bits = (int) value;
     } else if (!strcmp(name, "auto_reduction_per_target")) {
         e->opt_force_per_target = value != 0;
     } else return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown option");

@@ -153,7 +153,7 @@ int final_impl(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons
     HIP_TRY(e, hipStreamSynchronize(s));
     if (trim_threshold > 0 && n_acc) away = e->h_counters[0];
 
-    e->fc_valid = true; e->fc_n_accepted = n_acc;
+    e->fc_valid = true; e->fc_n_accepted = n_acc; e->fc_epoch++;
     out->n_pairs = u->n_pairs; out->n_accepted = (int32_t) n_acc; out->n_written = (int32_t) (n_acc - away); out->reserved = 0;
     out->d_verdict = (const uint8_t *) e->fc_verdict.p; out->d_rank = c.rank; out->d_id = c.id; out->d_new_reads = c.new_reads; out->d_trim_left = c.trim_left;
     out->d_begin = c.begin; out->d_len = c.len; out->d_order = c.order;
@@ -168,6 +168,16 @@ int final_impl(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons
 }
 
 }  // namespace
+
+bool alga_final_is_current(const alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin, const char **why) {
+    if (!current_results(e, u, cons, why)) return false;
+    if (!e->fc_valid || fin->n_pairs != u->n_pairs || (uint64_t) fin->n_accepted != e->fc_n_accepted || fin->d_verdict != (const uint8_t *) e->fc_verdict.p ||
+        fin->d_order != (const int32_t *) e->fc_order.p || fin->d_begin != (const int32_t *) e->fc_begin.p || fin->d_len != (const int32_t *) e->fc_len.p) {
+        *why = "not the result of the last alga_final_contigs_device call on this engine";
+        return false;
+    }
+    return true;
+}
 
 extern "C" int alga_contig_trim_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n, int32_t threshold,
                                        void *hip_stream, int32_t *d_trim_left, uint64_t *edges_out) {
@@ -213,10 +223,7 @@ extern "C" int alga_write_final_fasta_device(alga_engine *e, const alga_unitigs 
     if (info) *info = alga_gfa_info{};
     if (!u || !cons || !fin || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs, consensus, final contigs and path must not be NULL");
     const char *why = nullptr;
-    if (!current_results(e, u, cons, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
-    if (!e->fc_valid || fin->n_pairs != u->n_pairs || (uint64_t) fin->n_accepted != e->fc_n_accepted || fin->d_verdict != (const uint8_t *) e->fc_verdict.p ||
-        fin->d_order != (const int32_t *) e->fc_order.p || fin->d_begin != (const int32_t *) e->fc_begin.p || fin->d_len != (const int32_t *) e->fc_len.p)
-        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_final_contigs_device call on this engine");
+    if (!alga_final_is_current(e, u, cons, fin, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
     HIP_TRY(e, hipSetDevice(e->device));
     const FcFasta f{cons->d_words, (const unsigned long long *) u->d_word_off, fin->d_verdict, fin->d_order, fin->d_begin, fin->d_len, (uint64_t) fin->n_accepted};
     AlgaTextJob job;

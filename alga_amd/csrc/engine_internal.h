@@ -172,6 +172,16 @@ struct alga_engine {
     DevBuf      cr_cnt, cr_table, cr_hist, cr_keys[2], cr_flag, cr_pos, cr_solid, cr_dir;
     int64_t     opt_correct_slice_keys = 1ll << 28;   // option "correct_slice_keys": occurrences a slice of the k-mer count holds (a single bin above it is a slice of its own)
     int         opt_correct_dir_bits = 0;             // option "correct_dir_bits": bits of the solid keys' directory, 0 = about two keys per bucket (tests force long and empty buckets)
+    // reads placed on sequences (engine_place.hip).  Workspaces: counters, the targets of a final result, the lengths' scan, the column array, the
+    // (k-mer, column) pairs before and after the sort, the directory, the per-wave seed masks, the difference array.  The result: per read target /
+    // pos / mm / hits / state, col_off, the scan of the differences (the cover is its entries from 1 on), the per-target sums, the histogram
+    DevBuf      pl_cnt, pl_fbegin, pl_flen, pl_scan, pl_cols, pl_keys[2], pl_vals[2], pl_dir, pl_ub, pl_diff;
+    DevBuf      pl_target, pl_pos, pl_mm, pl_hits, pl_state, pl_coloff, pl_cover, pl_tstat, pl_hist;
+    bool        pl_valid = false;                  // the result buffers hold a placement
+    uint64_t    pl_targets = 0, pl_reads = 0;      // ... of this many reads on this many targets
+    uint64_t    pl_final_epoch = 0;                // ... made on the final result of this epoch (0: on caller's targets)
+    uint64_t    fc_epoch = 0;                      // counts the alga_final_contigs_device calls that wrote a result
+    int         opt_place_dir_bits = 0;            // option "place_dir_bits": bits of the placement index's directory, 0 = about two positions per bucket
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;
@@ -308,6 +318,9 @@ int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, 
 int alga_correct_check_params(alga_engine *e, const alga_correct_params *p);
 int alga_correct_impl(alga_engine *e, uint32_t *d_rows, int32_t stride, const int32_t *d_len, int64_t n_nodes, const alga_correct_params *p, hipStream_t s,
                       alga_correct_info *info);
+
+// engine_final.hip: `u` / `cons` / `fin` are the engine's current unitig, consensus and final results (else *why says which is not)
+bool alga_final_is_current(const alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin, const char **why);
 
 inline int alga_check_launch(alga_engine *e, const char *what) {
     hipError_t err = hipGetLastError();

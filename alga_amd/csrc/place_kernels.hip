@@ -1,0 +1,506 @@
+// alga_amd/csrc/place_kernels.hip -- every read placed on a set of target sequences, the depth of every column, the pairs (include/alga_amd.h:
+// alga_place_reads_device; the definition is the comment there, host side in engine_place.hip).
+//
+// The targets are repacked into one 2-bit array in COLUMN space (column g in word g >> 4, g = col_off[t] + the base's index in t), so the
+// boundary problem is in one place: a base index anywhere else is a column.  (t, p) ascending is the column ascending, so a placement is its
+// first column and the tuple (mm, t, p, strand) one 64-bit key.
+//   k_pl_node_check     pair_off is well formed; the longest node
+//   k_pl_target_check   no negative target length; the columns (64-bit sum) and the indexed positions
+//   k_pl_final_targets  begin / length of the windows of a final result, by id
+//   k_pl_gather         the column array, one thread per word
+//   k_pl_keys           (k-mer, column) of every column; a column that is no indexed position gets a key above every k-mer
+//   k_pl_dir            directory of the sorted keys on the top bits of the k-mer, one thread per key (as k_cr_dir), and the distinct k-mers
+//   k_pl_place          one wave per read, both strands.  Lanes take seeds, 64 at a time: one directory read, a bisection to the lower bound, a
+//                       scan of at most max_occ + 1 equal keys.  The (seed, occurrence) candidates of the usable seeds go to the lanes in passes
+//                       of 64 (a wave scan of the occurrence counts, a bisection over it by cross-lane reads); a lane verifies its candidate by
+//                       XOR and popcount over funnel-shifted column words and leaves past max_mismatches.  A candidate found through seed j
+//                       counts only if no usable seed j' < j matches at that placement: no duplicates, no sort.  The minimum key and the number
+//                       of placements at its mm are reduced across the wave.  The rows are read from memory (every lane reads the same word):
+//                       there is no cap on the read length; a read with more than 64 seeds keeps the usable masks of its earlier seed chunks
+//                       in a per-wave piece of global scratch.
+//   k_pl_depth_add      +1 / -1 of every counting read into the difference array, the per-target sums: 32- and 64-bit integer atomics
+//   k_pl_uncovered      columns with cover 0 per target (the cover is one scan of the difference array over all columns: a read's +1 and -1
+//                       lie in one target, or the -1 on the first column of the next)
+//   k_pl_pairs          the verdict on every pair, the insert histogram (integer atomics on the global histogram: up to 2^20 + 1 bins)
+//   k_pl_fasta_sizes / k_pl_fasta_write   the records of the final FASTA with `_reads=<n>_depth=<q>.<dd>` in the header, one wave per record
+// Four waves per block; k_pl_place runs 8 blocks per CU (the lookups are dependent random reads: occupancy is what hides them).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "place_kernels.h"
+#include "gfa_kernels.h"
+#include "prefsuf_common.h"
+
+namespace alga {
+
+namespace {
+
+constexpr int PL_BLOCK = 256, PL_WAVES = PL_BLOCK / 64;
+constexpr uint8_t PL_ST_PLACED = 1, PL_ST_UNIQUE = 2, PL_ST_MINUS = 4;   // ALGA_PLACE_* of include/alga_amd.h (the bits of d_state)
+constexpr uint8_t PL_V_ACCEPTED = 2;                                   // ALGA_FINAL_ACCEPTED
+
+__device__ __forceinline__ unsigned long long pl_wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
+        v += ((unsigned long long) hi << 32) | lo;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long pl_wave_min(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
+        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// the target of column g < col_off[T]: the last t with col_off[t] <= g (it has a length: col_off[t + 1] > g)
+__device__ __forceinline__ uint32_t pl_target_of(const uint32_t *__restrict__ col_off, uint32_t T, uint32_t g) {
+    uint32_t lo = 0, hi = T;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (col_off[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the k-mer at column g of the column array (two words of padding behind the last column)
+__device__ __forceinline__ unsigned long long pl_col_kmer(const uint32_t *__restrict__ cols, uint32_t g, int k) {
+    const uint32_t w = g >> 4, sh = (g & 15u) << 1;
+    const unsigned long long lo = (unsigned long long) cols[w] | ((unsigned long long) cols[w + 1] << 32);
+    unsigned long long v = lo >> sh;
+    if (sh) v |= (unsigned long long) cols[w + 2] << (64 - sh);
+    return v & ((1ull << (2 * k)) - 1ull);
+}
+
+// the k-mer at base i of a row of nw words (i + k <= its length: nothing is read past word nw - 1)
+__device__ __forceinline__ unsigned long long pl_row_kmer(const uint32_t *__restrict__ row, int nw, int i, int k) {
+    const int w = i >> 4, sh = (i & 15) << 1;
+    const unsigned long long lo = (unsigned long long) row[w] | (w + 1 < nw ? (unsigned long long) row[w + 1] << 32 : 0ull);
+    unsigned long long v = lo >> sh;
+    if (sh && w + 2 < nw) v |= (unsigned long long) row[w + 2] << (64 - sh);
+    return v & ((1ull << (2 * k)) - 1ull);
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_node_check(const uint8_t *__restrict__ pair_off, const int32_t *__restrict__ len, uint64_t n,
+                                                            unsigned long long *__restrict__ counters) {
+    unsigned long long mx = 0;
+    bool bad = false;
+    for (uint64_t v = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; v < n; v += (uint64_t) gridDim.x * PL_BLOCK) {
+        const int32_t l = len[v];
+        if (l > 0 && (unsigned long long) l > mx) mx = (unsigned long long) l;
+        if (pair_off) {
+            const uint8_t po = pair_off[v];
+            if (po > 2 || po != pair_off[v ^ 1]) bad = true;
+            else if (po == 1 && (v + 2 >= n || pair_off[v + 2] != 2)) bad = true;
+            else if (po == 2 && (v < 2 || pair_off[v - 2] != 1)) bad = true;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long w = (unsigned long long) (uint32_t) __shfl_xor((int) (uint32_t) mx, o); mx = w > mx ? w : mx; }
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(&counters[PL_MAX_READ_LEN], mx);
+    if (bad) counters[PL_BAD_PAIR] = 1ull;
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_target_check(const int32_t *__restrict__ tlen, uint64_t T, int32_t k, unsigned long long *__restrict__ counters) {
+    unsigned long long sum = 0, idx = 0;
+    bool bad = false;
+    for (uint64_t t = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; t < T; t += (uint64_t) gridDim.x * PL_BLOCK) {
+        const int32_t l = tlen[t];
+        if (l < 0) { bad = true; continue; }
+        sum += (unsigned long long) l;
+        if (l >= k) idx += (unsigned long long) (l - k + 1);
+    }
+    sum = pl_wave_sum(sum); idx = pl_wave_sum(idx);
+    if ((threadIdx.x & 63) == 0) {
+        if (sum) atomicAdd(&counters[PL_COLUMNS], sum);
+        if (idx) atomicAdd(&counters[PL_INDEX_POS], idx);
+    }
+    if (bad) counters[PL_BAD_LEN] = 1ull;
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_final_targets(const unsigned long long *__restrict__ word_off, const uint8_t *__restrict__ verdict,
+                                                               const int32_t *__restrict__ order, const int32_t *__restrict__ begin, const int32_t *__restrict__ len,
+                                                               uint64_t n, unsigned long long *__restrict__ tbegin, int32_t *__restrict__ tlen) {
+    const uint64_t j = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t k = (uint32_t) order[j];
+    const bool live = verdict[k] == PL_V_ACCEPTED;
+    tbegin[j] = 16ull * word_off[k] + (unsigned long long) (live ? begin[k] : 0);
+    tlen[j] = live ? len[k] : 0;
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_gather(const uint32_t *__restrict__ words, const unsigned long long *__restrict__ begin, PlTargets t,
+                                                        uint32_t *__restrict__ cols) {
+    const uint64_t n_words = (t.columns + 15) >> 4;
+    for (uint64_t w = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * PL_BLOCK) {
+        const uint64_t g0 = w << 4;
+        uint32_t tt = pl_target_of(t.col_off, t.T, (uint32_t) g0), v = 0;
+        for (int j = 0; j < 16; j++) {
+            const uint64_t g = g0 + (uint64_t) j;
+            if (g >= t.columns) break;
+            while ((uint64_t) t.col_off[tt + 1] <= g) tt++;                  // (g < columns = col_off[T]: ends at a target that has a length)
+            const unsigned long long src = begin[tt] + (g - (uint64_t) t.col_off[tt]);
+            v |= ((words[src >> 4] >> ((src & 15ull) << 1)) & 3u) << (2 * j);
+        }
+        cols[w] = v;
+    }
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_keys(PlTargets t, int32_t k, unsigned long long *__restrict__ keys, uint32_t *__restrict__ vals) {
+    for (uint64_t g = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; g < t.columns; g += (uint64_t) gridDim.x * PL_BLOCK) {
+        const uint32_t tt = pl_target_of(t.col_off, t.T, (uint32_t) g);
+        const uint64_t q = g - (uint64_t) t.col_off[tt];
+        keys[g] = q + (uint64_t) k <= (uint64_t) t.tlen[tt] ? pl_col_kmer(t.cols, (uint32_t) g, k) : 1ull << (2 * k);      // above every k-mer, inside the 2k + 1 sorted bits
+        vals[g] = (uint32_t) g;
+    }
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_dir(const unsigned long long *__restrict__ keys, uint64_t n, int shift, uint32_t n_buckets, uint32_t *__restrict__ dir,
+                                                     unsigned long long *__restrict__ counters) {
+    const uint64_t j = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x;
+    unsigned long long head = 0;
+    if (j <= n) {
+        const uint32_t lo = j == 0 ? 0u : (uint32_t) (keys[j - 1] >> shift) + 1u;
+        const uint32_t hi = j < n ? (uint32_t) (keys[j] >> shift) : n_buckets;
+        for (uint32_t b = lo; b <= hi && b <= n_buckets; b++) dir[b] = (uint32_t) j;
+        head = j < n && (j == 0 || keys[j - 1] != keys[j]) ? 1ull : 0ull;
+    }
+    head = pl_wave_sum(head);
+    if ((threadIdx.x & 63) == 0 && head) atomicAdd(&counters[PL_DISTINCT], head);
+}
+
+// lower bound of x among the indexed keys and its occurrences, counted up to max_occ + 1
+__device__ __forceinline__ void pl_lookup(const PlIndex &x, unsigned long long kmer, uint32_t max_occ, uint32_t &lb, uint32_t &occ) {
+    const uint32_t b = (uint32_t) (kmer >> x.shift);
+    uint32_t lo = x.dir[b], hi = x.dir[b + 1];
+    const uint32_t end = hi;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (x.keys[mid] < kmer) lo = mid + 1; else hi = mid;
+    }
+    lb = lo;
+    uint32_t c = 0;
+    while (lo + c < end && c <= max_occ && x.keys[lo + c] == kmer) c++;
+    occ = c;
+}
+
+// Hamming distance between a row of L bases and the columns from gp on; stops past max_mm
+__device__ __forceinline__ uint32_t pl_verify(const uint32_t *__restrict__ row, int nw, int L, const uint32_t *__restrict__ cols, uint32_t gp, uint32_t max_mm) {
+    const uint32_t *tw = cols + (gp >> 4);
+    const uint32_t sh = (gp & 15u) << 1;
+    uint32_t mm = 0, prev = tw[0];
+    for (int w = 0; w < nw; w++) {
+        const uint32_t next = tw[w + 1];
+        uint32_t x = row[w] ^ __funnelshift_r(prev, next, sh);
+        prev = next;
+        if (w == nw - 1 && (L & 15)) x &= (1u << ((L & 15) << 1)) - 1u;
+        mm += (uint32_t) __popc((x | (x >> 1)) & 0x55555555u);
+        if (mm > max_mm) break;
+    }
+    return mm;
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_place(PlReads rd, PlTargets t, PlIndex x, int32_t k, uint32_t max_mm, uint32_t max_occ, PlOut o,
+                                                       unsigned long long *__restrict__ scratch, uint32_t scratch_words, unsigned long long *__restrict__ counters) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t) blockIdx.x * PL_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * PL_WAVES;
+    unsigned long long *ub = scratch + wave * (uint64_t) scratch_words;
+    unsigned long long n_placed = 0, n_unique = 0, n_sat = 0, n_seeds = 0, n_over = 0;       // wave-uniform
+    for (uint64_t r = wave; r < rd.R; r += n_waves) {
+        const int32_t L = rd.len[2 * r + 1];
+        unsigned long long best = ~0ull;                 // (mm << 33) | (first column << 1) | strand, of this lane's placements
+        uint32_t lane_mm = 0xFFFFFFFFu, lane_cnt = 0;    // the smallest mm among them and how many have it
+        if (L >= k) {
+            const int S = L / k, nw = blocks_of(L);
+            for (int strand = 0; strand < 2; strand++) {
+                const uint32_t *row = rd.rows + (2 * r + (strand == 0 ? 1u : 0u)) * (size_t) rd.stride;
+                for (int c0 = 0; c0 < S; c0 += 64) {
+                    const int j = c0 + lane;
+                    const bool act = j < S;
+                    uint32_t lb = 0, occ = 0;
+                    if (act) pl_lookup(x, pl_row_kmer(row, nw, j * k, k), max_occ, lb, occ);
+                    const bool usable = act && occ >= 1u && occ <= max_occ;
+                    const unsigned long long umask = __ballot(usable);
+                    n_seeds += (unsigned long long) __popcll(__ballot(act));
+                    n_over += (unsigned long long) __popcll(__ballot(act && occ > max_occ));
+                    if (S > 64) {                        // later chunks ask for this one's usable seeds
+                        if (lane == 0) __hip_atomic_store(&ub[c0 >> 6], umask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __threadfence();
+                    }
+                    const uint32_t mine = usable ? occ : 0u;
+                    uint32_t inc = mine;
+                    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t) __shfl_up((int) inc, d); if (lane >= d) inc += up; }
+                    const uint32_t C = (uint32_t) __shfl((int) inc, 63), exc = inc - mine;
+                    for (uint32_t p0 = 0; p0 < C; p0 += 64) {
+                        const bool cact = p0 + (uint32_t) lane < C;
+                        const uint32_t ci = cact ? p0 + (uint32_t) lane : C - 1u;
+                        int sl = 0;                      // the seed lane of candidate ci: the first with inc > ci
+                        for (int st = 32; st > 0; st >>= 1) if ((uint32_t) __shfl((int) inc, sl + st - 1) <= ci) sl += st;
+                        const uint32_t s_lb = (uint32_t) __shfl((int) lb, sl), s_exc = (uint32_t) __shfl((int) exc, sl);
+                        if (!cact) continue;
+                        const int js = c0 + sl;
+                        const uint32_t g = x.vals[s_lb + (ci - s_exc)];
+                        const uint32_t tt = pl_target_of(t.col_off, t.T, g);
+                        const long long p = (long long) g - (long long) t.col_off[tt] - (long long) js * k;
+                        if (p < 0 || p + (long long) L > (long long) t.tlen[tt]) continue;
+                        const uint32_t gp = g - (uint32_t) (js * k);
+                        const uint32_t mm = pl_verify(row, nw, L, t.cols, gp, max_mm);
+                        if (mm > max_mm) continue;
+                        bool dup = false;                // an earlier usable seed finds this placement too
+                        for (int j2 = 0; j2 < js && !dup; j2++) {
+                            const unsigned long long m = j2 >= c0 ? umask : __hip_atomic_load(&ub[j2 >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if ((m >> (j2 & 63)) & 1ull) dup = pl_row_kmer(row, nw, j2 * k, k) == pl_col_kmer(t.cols, gp + (uint32_t) (j2 * k), k);
+                        }
+                        if (dup) continue;
+                        const unsigned long long key = ((unsigned long long) mm << 33) | ((unsigned long long) gp << 1) | (unsigned long long) strand;
+                        best = key < best ? key : best;
+                        if (mm < lane_mm) { lane_mm = mm; lane_cnt = 1u; }
+                        else if (mm == lane_mm) lane_cnt++;
+                    }
+                }
+            }
+        }
+        const unsigned long long win = pl_wave_min(best);
+        int32_t tg = -1, ps = -1;
+        uint8_t mm8 = 0, hits8 = 0, st8 = 0;
+        if (win != ~0ull) {
+            const uint32_t bmm = (uint32_t) (win >> 33), gp = (uint32_t) (win >> 1);
+            const unsigned long long hits = pl_wave_sum(lane_mm == bmm ? (unsigned long long) lane_cnt : 0ull);
+            const uint32_t tt = pl_target_of(t.col_off, t.T, gp);
+            tg = (int32_t) tt; ps = (int32_t) (gp - t.col_off[tt]); mm8 = (uint8_t) bmm; hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
+            st8 = (uint8_t) (PL_ST_PLACED | (hits == 1ull ? PL_ST_UNIQUE : 0) | ((win & 1ull) ? PL_ST_MINUS : 0));
+            n_placed++; n_unique += hits == 1ull; n_sat += hits > 255ull;
+        }
+        if (lane == 0) { o.target[r] = tg; o.pos[r] = ps; o.mm[r] = mm8; o.hits[r] = hits8; o.state[r] = st8; }
+    }
+    if (lane == 0) {
+        if (n_placed) atomicAdd(&counters[PL_PLACED], n_placed);
+        if (n_unique) atomicAdd(&counters[PL_UNIQUE], n_unique);
+        if (n_sat) atomicAdd(&counters[PL_SATURATED], n_sat);
+        if (n_seeds) atomicAdd(&counters[PL_SEEDS], n_seeds);
+        if (n_over) atomicAdd(&counters[PL_SEEDS_OVER], n_over);
+    }
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_depth_add(PlReads rd, PlTargets t, PlOut o, int multi, uint32_t *__restrict__ diff, unsigned long long *__restrict__ tstat) {
+    for (uint64_t r = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; r < rd.R; r += (uint64_t) gridDim.x * PL_BLOCK) {
+        const uint8_t st = o.state[r];
+        if (!(st & (multi ? PL_ST_PLACED : PL_ST_UNIQUE))) continue;
+        const uint32_t tt = (uint32_t) o.target[r], L = (uint32_t) rd.len[2 * r + 1];
+        const uint32_t gp = t.col_off[tt] + (uint32_t) o.pos[r];
+        atomicAdd(&diff[gp], 1u);
+        atomicAdd(&diff[gp + L], 0xFFFFFFFFu);                                // gp + L <= col_off[tt + 1] <= columns: the array has columns + 1 entries
+        atomicAdd(&tstat[tt], 1ull);
+        atomicAdd(&tstat[(size_t) t.T + tt], (unsigned long long) L);
+        atomicAdd(&tstat[2 * (size_t) t.T + tt], (unsigned long long) o.mm[r]);
+    }
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_uncovered(PlTargets t, const uint32_t *__restrict__ cover, unsigned long long *__restrict__ tstat) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long *unc = tstat + 3 * (size_t) t.T;
+    for (uint64_t g0 = ((uint64_t) blockIdx.x * PL_BLOCK + (threadIdx.x & ~63u)); g0 < t.columns; g0 += (uint64_t) gridDim.x * PL_BLOCK) {
+        const uint64_t g = g0 + (uint64_t) lane;
+        const bool zero = g < t.columns && cover[g] == 0u;
+        const unsigned long long m = __ballot(zero);
+        if (!m) continue;
+        const uint64_t glast = g0 + 63 < t.columns ? g0 + 63 : t.columns - 1;
+        const uint32_t t0 = pl_target_of(t.col_off, t.T, (uint32_t) g0);
+        if ((uint64_t) t.col_off[t0 + 1] > glast) {                           // the wave's columns lie in one target
+            if (lane == 0) atomicAdd(&unc[t0], (unsigned long long) __popcll(m));
+        } else if (zero) atomicAdd(&unc[pl_target_of(t.col_off, t.T, (uint32_t) g)], 1ull);
+    }
+}
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_pairs(PlReads rd, const uint8_t *__restrict__ pair_off, PlOut o, int32_t max_insert, unsigned long long *__restrict__ hist,
+                                                       unsigned long long *__restrict__ counters) {
+    unsigned long long n_pairs = 0, n_proper = 0, n_improper = 0, n_split = 0, n_nu = 0, sum = 0;
+    for (uint64_t r = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; r < rd.R; r += (uint64_t) gridDim.x * PL_BLOCK) {
+        if (pair_off[2 * r + 1] != 1) continue;                                // the mate with the smaller index judges: its mate is read r + 1
+        const uint64_t r2 = r + 1;
+        const uint8_t s1 = o.state[r], s2 = o.state[r2];
+        n_pairs++;
+        if (!(s1 & PL_ST_UNIQUE) || !(s2 & PL_ST_UNIQUE)) { n_nu++; continue; }
+        if (o.target[r] != o.target[r2]) { n_split++; continue; }
+        if ((s1 & PL_ST_MINUS) == (s2 & PL_ST_MINUS)) { n_improper++; continue; }
+        const uint64_t rp = (s1 & PL_ST_MINUS) ? r2 : r, rm = (s1 & PL_ST_MINUS) ? r : r2;
+        const long long a = o.pos[rp], la = rd.len[2 * rp + 1], b = o.pos[rm], lb = rd.len[2 * rm + 1];
+        const long long ins = b + lb - a;
+        if (a <= b && a + la <= b + lb && ins <= (long long) max_insert) { n_proper++; sum += (unsigned long long) ins; atomicAdd(&hist[ins], 1ull); }
+        else n_improper++;
+    }
+    n_pairs = pl_wave_sum(n_pairs); n_proper = pl_wave_sum(n_proper); n_improper = pl_wave_sum(n_improper); n_split = pl_wave_sum(n_split);
+    n_nu = pl_wave_sum(n_nu); sum = pl_wave_sum(sum);
+    if ((threadIdx.x & 63) == 0 && n_pairs) {
+        atomicAdd(&counters[PL_PAIRS], n_pairs);
+        if (n_proper) { atomicAdd(&counters[PL_PROPER], n_proper); atomicAdd(&counters[PL_INSERT_SUM], sum); }
+        if (n_improper) atomicAdd(&counters[PL_IMPROPER], n_improper);
+        if (n_split) atomicAdd(&counters[PL_SPLIT], n_split);
+        if (n_nu) atomicAdd(&counters[PL_NOT_UNIQUE], n_nu);
+    }
+}
+
+// ---- FASTA with depth headers ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int pl_dec_width(unsigned long long v) {
+    int w = 1;
+    while (v >= 10ull) { v /= 10ull; w++; }
+    return w;
+}
+
+// `>contig_id=<id>_length=<L>_reads=<n>_depth=<q>.<dd>\n<window>\n`
+struct PlRecord {
+    unsigned long long id, L, reads, q, dd;
+    int w_id, w_len, w_reads, w_q;
+    uint32_t hp;                      // bytes before the sequence
+    const uint32_t *row; uint32_t q0;
+    __device__ void set(const PlFasta &f, uint64_t j) {
+        const uint32_t k = (uint32_t) f.order[j];
+        id = j; L = (unsigned long long) f.len[k]; reads = f.t_reads[j];
+        const unsigned long long bases = f.t_bases[j];
+        q = bases / L; dd = ((bases % L) * 100ull) / L;                        // floor(100 * bases / L) = 100 q + dd without a product above 2^64
+        w_id = pl_dec_width(id); w_len = pl_dec_width(L); w_reads = pl_dec_width(reads); w_q = pl_dec_width(q);
+        hp = 11u + w_id + 8u + w_len + 7u + w_reads + 7u + w_q + 3u + 1u;
+        row = f.words + f.word_off[k]; q0 = (uint32_t) f.begin[k];
+    }
+    __device__ static char digit(unsigned long long v, int w, int d) {
+        for (int i = w - 1 - d; i > 0; i--) v /= 10ull;
+        return (char) ('0' + (int) (v % 10ull));
+    }
+    __device__ char at(uint32_t p) const {
+        if (p >= hp) {
+            const uint32_t s = p - hp;
+            if (s >= L) return '\n';
+            const uint32_t c = s + q0;
+            return (char) ((0x54474341u >> (8 * ((row[c >> 4] >> (2 * (c & 15))) & 3))) & 0xFF);
+        }
+        uint32_t at0 = 0;
+        if (p < 11u) return ">contig_id="[p];
+        at0 = 11u;
+        if (p < at0 + w_id) return digit(id, w_id, (int) (p - at0));
+        at0 += w_id;
+        if (p < at0 + 8u) return "_length="[p - at0];
+        at0 += 8u;
+        if (p < at0 + w_len) return digit(L, w_len, (int) (p - at0));
+        at0 += w_len;
+        if (p < at0 + 7u) return "_reads="[p - at0];
+        at0 += 7u;
+        if (p < at0 + w_reads) return digit(reads, w_reads, (int) (p - at0));
+        at0 += w_reads;
+        if (p < at0 + 7u) return "_depth="[p - at0];
+        at0 += 7u;
+        if (p < at0 + w_q) return digit(q, w_q, (int) (p - at0));
+        at0 += w_q;
+        if (p == at0) return '.';
+        if (p < at0 + 3u) return digit(dd, 2, (int) (p - at0 - 1u));
+        return '\n';
+    }
+};
+
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_fasta_sizes(PlFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    const uint64_t j = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x;
+    unsigned long long live = 0, bytes = 0;
+    if (j < f.n) {
+        if (f.verdict[(uint32_t) f.order[j]] == PL_V_ACCEPTED) {
+            PlRecord s;
+            s.set(f, j);
+            bytes = (unsigned long long) s.hp + s.L + 1ull;
+            live = 1;
+        }
+        sizes[j] = (uint32_t) bytes;
+    }
+    live = pl_wave_sum(live);
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long w = (unsigned long long) (uint32_t) __shfl_xor((int) (uint32_t) bytes, o); bytes = w > bytes ? w : bytes; }
+    if ((threadIdx.x & 63) == 0 && live) {
+        atomicAdd(&counters[GFA_SEGMENTS], live);
+        atomicMax(&counters[GFA_MAX_LINE], bytes);
+    }
+}
+
+// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_fasta_write(PlFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1, char *__restrict__ buf) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t base = off[i0], waves = (uint64_t) gridDim.x * PL_WAVES;
+    for (uint64_t j = i0 + (uint64_t) blockIdx.x * PL_WAVES + (threadIdx.x >> 6); j < i1; j += waves) {
+        const uint64_t l0 = off[j], l1 = off[j + 1];
+        if (l0 == l1) continue;
+        PlRecord s;
+        s.set(f, j);
+        char *g0 = buf + (l0 - base);
+        for (uint64_t p = (uint64_t) lane; p < l1 - l0; p += 64) g0[p] = s.at((uint32_t) p);
+    }
+}
+
+inline unsigned pl_grid(uint64_t items, uint64_t cap = 1u << 16) {
+    const uint64_t g = (items + PL_BLOCK - 1) / PL_BLOCK;
+    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
+}
+
+}  // namespace
+
+void launch_pl_node_check(const uint8_t *pair_off, const int32_t *len, uint64_t n, unsigned long long *counters, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_pl_node_check, dim3(pl_grid(n, 4096)), dim3(PL_BLOCK), 0, s, pair_off, len, n, counters);
+}
+
+void launch_pl_target_check(const int32_t *tlen, uint64_t T, int32_t k, unsigned long long *counters, hipStream_t s) {
+    if (T) hipLaunchKernelGGL(k_pl_target_check, dim3(pl_grid(T, 4096)), dim3(PL_BLOCK), 0, s, tlen, T, k, counters);
+}
+
+void launch_pl_final_targets(const unsigned long long *word_off, const uint8_t *verdict, const int32_t *order, const int32_t *begin, const int32_t *len, uint64_t n,
+                             unsigned long long *tbegin, int32_t *tlen, hipStream_t s) {
+    if (n) hipLaunchKernelGGL(k_pl_final_targets, dim3((unsigned) ((n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, s, word_off, verdict, order, begin, len, n, tbegin, tlen);
+}
+
+void launch_pl_gather(const uint32_t *words, const unsigned long long *begin, const PlTargets &t, uint32_t *cols, hipStream_t s) {
+    if (t.columns) hipLaunchKernelGGL(k_pl_gather, dim3(pl_grid((t.columns + 15) >> 4)), dim3(PL_BLOCK), 0, s, words, begin, t, cols);
+}
+
+void launch_pl_keys(const PlTargets &t, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s) {
+    if (t.columns) hipLaunchKernelGGL(k_pl_keys, dim3(pl_grid(t.columns)), dim3(PL_BLOCK), 0, s, t, k, keys, vals);
+}
+
+void launch_pl_dir(const unsigned long long *keys, uint64_t n, int shift, int bits, uint32_t *dir, unsigned long long *counters, hipStream_t s) {
+    hipLaunchKernelGGL(k_pl_dir, dim3((unsigned) ((n + 1 + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, s, keys, n, shift, 1u << bits, dir, counters);
+}
+
+int pl_place_blocks(uint64_t R, int n_cu) {
+    return (int) std::max<uint64_t>(1, std::min<uint64_t>((R + PL_WAVES - 1) / PL_WAVES, (uint64_t) std::max(1, n_cu) * 8u));
+}
+
+size_t pl_place_scratch_words(int blocks, int64_t max_read_len, int32_t k) {
+    const size_t per_wave = (size_t) std::max<int64_t>(1, (max_read_len / k + 63) / 64);
+    return (size_t) blocks * PL_WAVES * per_wave;
+}
+
+void launch_pl_place(const PlReads &r, const PlTargets &t, const PlIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, const PlOut &o, unsigned long long *scratch,
+                     uint32_t scratch_words_per_wave, int blocks, unsigned long long *counters, hipStream_t s) {
+    if (r.R) hipLaunchKernelGGL(k_pl_place, dim3((unsigned) blocks), dim3(PL_BLOCK), 0, s, r, t, x, k, (uint32_t) max_mm, (uint32_t) max_occ, o, scratch, scratch_words_per_wave,
+                                counters);
+}
+
+void launch_pl_depth_add(const PlReads &r, const PlTargets &t, const PlOut &o, int multi, uint32_t *diff, unsigned long long *tstat, hipStream_t s) {
+    if (r.R && t.T) hipLaunchKernelGGL(k_pl_depth_add, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, t, o, multi, diff, tstat);
+}
+
+void launch_pl_uncovered(const PlTargets &t, const uint32_t *cover, unsigned long long *tstat, hipStream_t s) {
+    if (t.columns) hipLaunchKernelGGL(k_pl_uncovered, dim3(pl_grid(t.columns, 8192)), dim3(PL_BLOCK), 0, s, t, cover, tstat);
+}
+
+void launch_pl_pairs(const PlReads &r, const uint8_t *pair_off, const PlOut &o, int32_t max_insert, unsigned long long *hist, unsigned long long *counters, hipStream_t s) {
+    if (r.R && pair_off) hipLaunchKernelGGL(k_pl_pairs, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, pair_off, o, max_insert, hist, counters);
+}
+
+void launch_pl_fasta_sizes(const PlFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
+    if (f.n) hipLaunchKernelGGL(k_pl_fasta_sizes, dim3((unsigned) ((f.n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, s, f, sizes, counters);
+}
+
+void launch_pl_fasta_write(const PlFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
+    if (i0 >= i1) return;
+    const uint64_t g = (i1 - i0 + PL_WAVES - 1) / PL_WAVES;
+    hipLaunchKernelGGL(k_pl_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(PL_BLOCK), 0, s, f, off, i0, i1, buf);
+}
+
+}  // namespace alga

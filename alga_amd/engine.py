@@ -177,7 +177,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device",
            "alga_contigs_device", "alga_contig_trim_device", "alga_final_contigs_device", "alga_write_final_fasta_device",
            "alga_extend_contigs_device", "alga_extend_seams_get",
-           "alga_correct_default_params", "alga_correct_reads_device", "alga_correct_parsed_reads", "alga_ingest_corrected_device"]
+           "alga_correct_default_params", "alga_correct_reads_device", "alga_correct_parsed_reads", "alga_ingest_corrected_device",
+           "alga_place_default_params", "alga_place_reads_device", "alga_place_reads_on_final_device", "alga_write_final_fasta_depth_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -385,6 +386,57 @@ class FinalContigs:
         """numpy copies, in the dtypes of tests/final_checker.py"""
         d = {k: getattr(self, k).cpu().numpy().copy() for k in self.KEYS}
         d.update(n_pairs=self.n_pairs, n_accepted=self.n_accepted, n_written=self.n_written, info=dict(self.info))
+        return d
+
+
+PLACE_DEPTH_MULTI = 1                                            # alga_place_params.flags
+PLACE_PLACED, PLACE_UNIQUE, PLACE_MINUS = 1, 2, 4                # bits of Placements.state
+
+
+class PlaceParams(C.Structure):
+    """alga_place_params"""
+    _fields_ = [(k, C.c_int32) for k in ("k", "max_mismatches", "max_occ", "max_insert", "flags")] + [("reserved", C.c_int32 * 3)]
+
+
+class PlaceInfo(C.Structure):
+    """alga_place_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("reads", "placed", "unique", "multi", "unplaced", "hits_saturated", "seeds", "seeds_over_max_occ", "index_positions",
+                                          "index_distinct", "pairs", "pairs_proper", "pairs_improper", "pairs_split", "pairs_not_unique")] + \
+               [(k, C.c_int64) for k in ("insert_median", "insert_mean_x100")] + [(k, C.c_double) for k in ("ms_index", "ms_place", "ms_depth", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PlacementsC(C.Structure):
+    """alga_placements"""
+    _fields_ = [("n_reads", C.c_int64), ("n_targets", C.c_int64), ("n_columns", C.c_uint64), ("n_hist", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("d_target", "d_pos", "d_mm", "d_hits", "d_state", "d_col_off", "d_cover", "d_t_reads", "d_t_bases", "d_t_mismatches",
+                                          "d_t_uncovered", "d_insert_hist")]
+
+
+class Placements:
+    """Result of Engine.place_reads: zero-copy torch views of the engine's device memory (valid until the next Engine.place_reads call on that
+    engine; clone what has to live longer) -- target / pos int32 [n_reads], mm / hits / state uint8 [n_reads], col_off int32 [n_targets + 1]
+    and cover int32 [n_columns] (the bits of uint32), t_reads / t_bases / t_mismatches / t_uncovered int64 [n_targets], insert_hist int64
+    [max_insert + 1] -- and .info (dict of alga_place_info)."""
+    KEYS = (("target", "<i4", np.int32), ("pos", "<i4", np.int32), ("mm", "|u1", np.uint8), ("hits", "|u1", np.uint8), ("state", "|u1", np.uint8),
+            ("col_off", "<i4", np.uint32), ("cover", "<i4", np.uint32), ("t_reads", "<i8", np.uint64), ("t_bases", "<i8", np.uint64),
+            ("t_mismatches", "<i8", np.uint64), ("t_uncovered", "<i8", np.uint64), ("insert_hist", "<i8", np.uint64))
+
+    def __init__(self, c, info, device, final=None):
+        self._c, self.info, self._final = c, info, final
+        self.n_reads, self.n_targets, self.n_columns, self.n_hist = int(c.n_reads), int(c.n_targets), int(c.n_columns), int(c.n_hist)
+        dev = "cuda:%d" % device
+        shape = dict(target=self.n_reads, pos=self.n_reads, mm=self.n_reads, hits=self.n_reads, state=self.n_reads, col_off=self.n_targets + 1,
+                     cover=self.n_columns, insert_hist=self.n_hist)
+        for k, typestr, _ in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (shape.get(k, self.n_targets),), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/place_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt in self.KEYS}
+        d["info"] = dict(self.info)
         return d
 
 
@@ -1362,13 +1414,67 @@ class Engine:
                                                         int(trim_threshold), 0, None, C.byref(out), C.byref(info)))
         return FinalContigs(out, info.as_dict(), unitigs, consensus, self.device)
 
-    def write_final_fasta(self, path, final):
+    def write_final_fasta(self, path, final, placements=None):
         """The accepted contigs of the LAST Engine.final_contigs call as FASTA (alga_write_final_fasta_device) -> dict of alga_gfa_info
-        (segments = records): `>contig_id=<id>_length=<len>` and the window on one line, in id order."""
+        (segments = records): `>contig_id=<id>_length=<len>` and the window on one line, in id order.  placements: the result of the LAST
+        Engine.place_reads(final=final) call -- the headers then end in `_reads=<n>_depth=<q>.<dd>` (alga_write_final_fasta_depth_device)."""
         info = GfaInfo()
+        if placements is not None:
+            self._check(self._lib.alga_write_final_fasta_depth_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
+                                                                      C.byref(placements._c), os.fsencode(path), C.byref(info)))
+            return info.as_dict()
         self._check(self._lib.alga_write_final_fasta_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
                                                             os.fsencode(path), C.byref(info)))
         return info.as_dict()
+
+    # ---- reads placed on sequences: depth, pairs, inserts (the definition: include/alga_amd.h) -----
+    @staticmethod
+    def place_params(k=21, max_mismatches=4, max_occ=256, max_insert=1000, depth_multi=False, flags=None):
+        p = PlaceParams()
+        p.k, p.max_mismatches, p.max_occ, p.max_insert = int(k), int(max_mismatches), int(max_occ), int(max_insert)
+        p.flags = int(flags) if flags is not None else (PLACE_DEPTH_MULTI if depth_multi else 0)
+        return p
+
+    def place_reads(self, words, lens, targets=None, final=None, pair_off=None, stream=None, **params):
+        """Every read of a node set in twin layout placed on target sequences (alga_place_reads_device) -> Placements.  words [n, stride] /
+        lens [n]: node 2r + 1 is read r, node 2r its reverse complement; pair_off uint8 [n] or None.  targets = (packed words, begin int64 [T],
+        len int32 [T]): ragged sequences, sequence t from base index begin[t] on; or final = the result of the LAST Engine.final_contigs
+        call: target id == contig id (alga_place_reads_on_final_device).  Host arrays are uploaded first; tensors are used where they are and
+        left untouched.  params: k, max_mismatches, max_occ, max_insert, depth_multi."""
+        import torch
+        assert (targets is None) != (final is None), "give targets or final"
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if pair_off is not None:
+            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = self.place_params(**params), PlacementsC(), PlaceInfo()
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        if final is not None:
+            torch.cuda.current_stream(dev).synchronize()
+            self._check(self._lib.alga_place_reads_on_final_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(final._unitigs._c),
+                                                                   C.byref(final._consensus._c), C.byref(final._c), C.byref(pp), st, C.byref(out), C.byref(info)))
+        else:
+            twords, tbegin, tlen = targets
+            twords, tlen = up(twords, np.uint32, np.int32), up(tlen, np.int32)
+            if isinstance(tbegin, np.ndarray):
+                tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
+            assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
+            torch.cuda.current_stream(dev).synchronize()
+            self._check(self._lib.alga_place_reads_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.c_void_p(_ptr(twords) or None),
+                                                          C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(pp), st,
+                                                          C.byref(out), C.byref(info)))
+        return Placements(out, info.as_dict(), self.device, final)
 
     def write_graph(self, path, n_nodes, edges):
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)

@@ -7,6 +7,7 @@
 //            [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N]
 //            [--contigs_final=final.fasta] [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]
 //            [--correct_reads=0|1] [--correct_k=21] [--correct_solid=3] [--corrected_reads=reads.fasta]
+//            [--contigs_depth=0|1] [--placements=placements.tsv]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -55,6 +56,11 @@
 // the GPU again at the duplicate / prefix removal; the counters go to stderr.  --corrected_reads=PATH writes the corrected forward reads as
 // FASTA (from the rows the call brought back; the sequences are the trimmed ones: a run on that file needs --retl=0 --retr=0).  None of the four
 // is passed through, and with --alga= they are refused: stock ALGA would read the original files, whose nodes are not this graph's.
+// --contigs_depth=1 (default 0; needs --contigs_final=): every input read -- the files parsed again, corrected again with --correct_reads=1 -- is
+// placed on the final contigs (alga_place_reads_on_final_device), the FASTA headers end in `_reads=<n>_depth=<q>.<dd>` and one line on stderr
+// gives placed / unique / multi / unplaced reads, proper pairs and the median insert.  --placements=PATH (needs --contigs_final= too): one line
+// `read target pos strand mm hits` per read, tab separated, target -1 and strand `.` for an unplaced read.  With both off every file is what it
+// was without them; neither is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -77,7 +83,8 @@ static const char *USAGE =
     "         [--gfa=graph.gfa] [--unitigs=unitigs.gfa] [--clip_tips=0|1] [--parallel_paths=0|1] [--consensus=unitigs.fasta] [--consensus_min_length=200]\n"
     "         [--consensus_min_votes=3] [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N] [--contigs_final=final.fasta]\n"
     "         [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]\n"
-    "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n";
+    "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n"
+    "         [--contigs_depth=0|1] [--placements=placements.tsv]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -92,7 +99,8 @@ int main(int argc, char **argv) {
     double error_rate = 0.0;
     int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1, contigs_new_reads_percent = 95, contigs_trim_threshold = 25, paired_extend = 0;
     int correct_reads = 0;
-    std::string corrected_reads;
+    std::string corrected_reads, placements;
+    int contigs_depth = 0;
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -124,6 +132,8 @@ int main(int argc, char **argv) {
         else if (opt(a, "--contigs_gfa", v)) contigs_gfa = v;
         else if (opt(a, "--contigs_min_length", v)) contigs_min_length = atoi(v.c_str());
         else if (opt(a, "--contigs_final", v)) contigs_final = v;
+        else if (opt(a, "--contigs_depth", v)) contigs_depth = atoi(v.c_str());
+        else if (opt(a, "--placements", v)) placements = v;
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -141,13 +151,14 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
     if (crp.k < 5 || crp.k > 31 || !(crp.k & 1)) { fprintf(stderr, "alga_hip: --correct_k must be odd and in [5, 31] (got %d)\n", crp.k); return 2; }
     if (crp.solid_min < 1) { fprintf(stderr, "alga_hip: --correct_solid must be >= 1 (got %d)\n", crp.solid_min); return 2; }
     if (!correct_reads && !corrected_reads.empty()) { fprintf(stderr, "alga_hip: --corrected_reads= needs --correct_reads=1\n"); return 2; }
+    if ((contigs_depth || !placements.empty()) && contigs_final.empty()) { fprintf(stderr, "alga_hip: --contigs_depth=1 and --placements= need --contigs_final=\n"); return 2; }
     if (correct_reads && !alga_exe.empty()) {
         fprintf(stderr, "alga_hip: --correct_reads=1 cannot be combined with --alga=: stock ALGA would read the original files, whose nodes are not the corrected graph's\n");
         return 2;
@@ -439,6 +450,57 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty())) {
+                    // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
+                    alga_parsed_reads pr{};
+                    char perr[512] = {0};
+                    if (alga_parse_files(file1.c_str(), file2.empty() ? nullptr : file2.c_str(), &cp, &pr, perr, sizeof(perr)) != ALGA_OK) { fprintf(stderr, "%s\n", perr); return 1; }
+                    if (correct_reads && alga_correct_parsed_reads(engine, &pr, &crp, nullptr) != ALGA_OK) { fprintf(stderr, "%s\n", alga_last_error(engine)); return 1; }
+                    const size_t pn = (size_t) pr.n_nodes, row_bytes = pn * (size_t) pr.stride_words * sizeof(uint32_t);
+                    std::vector<uint8_t> po(pn, 0);
+                    if (pr.paired) for (size_t q = 0; q + 3 < pn; q += 4) { po[q] = po[q + 1] = 1; po[q + 2] = po[q + 3] = 2; }
+                    void *d_rows = nullptr, *d_plen = nullptr, *d_po = nullptr;
+                    rc = alga_device_alloc(engine, row_bytes + 16, &d_rows);
+                    if (rc == ALGA_OK) rc = alga_device_alloc(engine, pn * sizeof(int32_t) + 16, &d_plen);
+                    if (rc == ALGA_OK) rc = alga_device_alloc(engine, pn + 16, &d_po);
+                    if (rc == ALGA_OK && pn) rc = alga_copy_to_device(engine, d_rows, pr.rows, row_bytes);
+                    if (rc == ALGA_OK && pn) rc = alga_copy_to_device(engine, d_plen, pr.len, pn * sizeof(int32_t));
+                    if (rc == ALGA_OK && pn) rc = alga_copy_to_device(engine, d_po, po.data(), pn);
+                    const alga_nodes pnd{(const uint32_t *) d_rows, pr.stride_words, (const int32_t *) d_plen, (int32_t) pn, nullptr, nullptr};
+                    alga_place_params pp;
+                    alga_place_default_params(&pp);
+                    alga_placements pl;
+                    alga_place_info pi;
+                    if (rc == ALGA_OK) rc = alga_place_reads_on_final_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, &cu, &cs, &fc, &pp, nullptr, &pl, &pi);
+                    if (rc == ALGA_OK)
+                        fprintf(stderr, "Reads placed on the final contigs: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
+                                "median insert %lld; device ms: index %.3f place %.3f depth %.3f, call %.1f ms wall\n", (unsigned long long) pi.reads,
+                                (unsigned long long) pi.placed, (unsigned long long) pi.unique, (unsigned long long) pi.multi, (unsigned long long) pi.unplaced,
+                                (unsigned long long) pi.pairs_proper, (unsigned long long) pi.pairs, (long long) pi.insert_median, pi.ms_index, pi.ms_place, pi.ms_depth,
+                                pi.ms_total);
+                    if (rc == ALGA_OK && !placements.empty()) {            // not a hot path: the host formats from the arrays that came back
+                        const size_t nr = (size_t) pl.n_reads;
+                        std::vector<int32_t> tg(nr), ps(nr);
+                        std::vector<uint8_t> mm(nr), hits(nr), state(nr);
+                        if (nr) {
+                            rc = alga_copy_to_host(engine, tg.data(), pl.d_target, nr * sizeof(int32_t));
+                            if (rc == ALGA_OK) rc = alga_copy_to_host(engine, ps.data(), pl.d_pos, nr * sizeof(int32_t));
+                            if (rc == ALGA_OK) rc = alga_copy_to_host(engine, mm.data(), pl.d_mm, nr);
+                            if (rc == ALGA_OK) rc = alga_copy_to_host(engine, hits.data(), pl.d_hits, nr);
+                            if (rc == ALGA_OK) rc = alga_copy_to_host(engine, state.data(), pl.d_state, nr);
+                        }
+                        FILE *f = rc == ALGA_OK ? fopen(placements.c_str(), "w") : nullptr;
+                        if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", placements.c_str()); return 1; }
+                        for (size_t r = 0; f && r < nr; r++)
+                            fprintf(f, "%zu\t%d\t%d\t%c\t%d\t%d\n", r, tg[r], ps[r], !(state[r] & ALGA_PLACE_PLACED) ? '.' : (state[r] & ALGA_PLACE_MINUS) ? '-' : '+',
+                                    (int) mm[r], (int) hits[r]);
+                        if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", placements.c_str()); return 1; }
+                    }
+                    if (rc == ALGA_OK) rc = contigs_depth ? alga_write_final_fasta_depth_device(engine, &cu, &cs, &fc, &pl, contigs_final.c_str(), &ffi)
+                                                          : alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
+                    alga_device_free(engine, d_rows); alga_device_free(engine, d_plen); alga_device_free(engine, d_po);
+                    alga_free_parsed_reads(&pr);
+                } else
                 if (rc == ALGA_OK) rc = alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
                 if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", contigs_final.c_str(), alga_last_error(engine), rc); return 1; }
                 fprintf(stderr, "Final contigs written -> %s: %llu records of %d contigs (min length %d, new reads %d %%, trim threshold %d): %llu short, %llu rejected, "

@@ -199,6 +199,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                occurrences (a single histogram bin above it is a slice of its own); tests lower it to run many slices
  *   "correct_dir_bits"           0 (default: about two keys per bucket) or 1..28: bits of the directory over the solid k-mers; tests force long
  *                                buckets and empty ones
+ *   "place_dir_bits"             0 (default: about two positions per bucket) or 1..26 (never more than 2k): bits of the directory over the index
+ *                                of alga_place_reads_device; tests force long buckets and empty ones
  *   "gfa_chunk_mb"               1..4096 (default 256): alga_write_gfa_device formats the text in chunks of at most this many MB (one device buffer,
  *                                two pinned host buffers of that size; a chunk is never smaller than twice the longest line)
  *   "unitig_ruling"              default -1: the list ranking of alga_unitigs_device ranks a RULING SET first -- the heads and one node in 64 walk to the
@@ -1150,6 +1152,97 @@ int  alga_correct_parsed_reads(alga_engine *e, alga_parsed_reads *pr, const alga
  * reads: that is why the stage sits in front of their removal) */
 int  alga_ingest_corrected_device(alga_engine *e, const char *file1, const char *file2 /* may be NULL */, const alga_ingest_params *p, const alga_correct_params *cp,
                                   alga_device_node_set *out, alga_ingest_info *info, alga_correct_info *cinfo /* may be NULL */);
+
+/* ---- reads placed on sequences: depth, pairs, inserts (alga_amd/csrc/place_kernels.hip, engine_place.hip) -------------------------
+ * Every input read laid over a set of target sequences (the final contigs, or any ragged set): where it lies, how many reads cover every
+ * column, and what the pairs say about the library.  Substitutions only: no insertions, deletions or clipped ends.  The rule is free of any
+ * order (thread, slice, hash); tests/place_checker.py states it in Python and the device result equals it array for array.
+ *
+ * Targets.  T sequences; target t is the d_len[t] bases of the 2-bit packed array `d_words` from base index d_begin[t] on (any index, it
+ * need not be word-aligned: the form alga_contig_trim_device takes).  col_off[t] = the exclusive prefix sum of d_len (col_off[T] = the sum,
+ * the number of columns).  A sum above 2^32 - 2 answers ALGA_ERR_CAPACITY (before anything of that size is allocated), a negative length
+ * ALGA_ERR_INVALID_ARGUMENT (checked on the device, nothing written).
+ * Reads.  A node set in twin layout: n even, rows stride_words apart, d_len; node 2r + 1 is read r, node 2r its reverse complement (the
+ * parser's layout, where len -1 means removed, and alga_device_node_set).  d_pair_off: NULL (= all zero) or n bytes, mate(v) = v, v + 2,
+ * v - 2 for the values 0, 1, 2 as in alga_extend_contigs_device.  Checked on the device before anything is written
+ * (ALGA_ERR_INVALID_ARGUMENT): row 2r is the reverse complement of row 2r + 1, len[2r] == len[2r + 1], len <= 16 * stride_words;
+ * pair_off[v] <= 2, pair_off[v] == pair_off[v ^ 1], the mate is in range and points back.  A read with len < k takes no part: its state is 0.
+ * Parameters (alga_place_params; anything outside answers ALGA_ERR_INVALID_ARGUMENT): k 8 .. 31 (default 21), max_mismatches 0 .. 254 (4),
+ * max_occ 1 .. 65535 (256), max_insert 1 .. 2^20 (1000), flags ALGA_PLACE_DEPTH_MULTI or 0 (0).
+ *
+ *   1. Index.  Position (t, q) is indexed for 0 <= q <= len[t] - k; no k-mer spans two targets, also where the targets abut in d_words.
+ *      occ(x) = the number of indexed positions whose k-mer is x.
+ *   2. Seeds.  Node v of length L has S = floor(L / k) seeds, seed j = bases jk .. jk + k - 1.  A seed is USABLE iff
+ *      1 <= occ(its k-mer) <= max_occ.
+ *   3. Placement.  (t, p) is a placement of node v iff 0 <= p <= len[t] - L, the Hamming distance mm between v and t[p .. p + L) is
+ *      <= max_mismatches, and some usable seed j of v equals t[p + jk .. p + jk + k) exactly.  (With S > max_mismatches and no seed over
+ *      max_occ the third condition follows from the second by pigeonhole: "all placements within the bound".)  Placements of node 2r + 1 are
+ *      `+` placements of read r, those of node 2r `-` placements; p is always the leftmost column covered.  A placement is a distinct triple
+ *      (t, p, strand): several seeds hitting the same triple make one placement.
+ *   4. Per read.  best = the smallest (mm, t, p, strand) with + < -; hits = the number of placements with mm == best.mm, saturated at 255;
+ *      state bits ALGA_PLACE_PLACED, ALGA_PLACE_UNIQUE (hits == 1), ALGA_PLACE_MINUS.  d_target (-1 if not placed), d_pos (-1), d_mm (0),
+ *      d_hits (0), d_state (0), one entry per read.
+ *   5. Depth.  A read COUNTS iff it is UNIQUE; with ALGA_PLACE_DEPTH_MULTI iff it is PLACED, at its best placement.
+ *      d_cover[col_off[t] + j] = the number of counting reads whose best placement covers column j of t.  Per target: d_t_reads = the
+ *      counting reads, d_t_bases = the sum of their lengths, d_t_mismatches = the sum of their mm, d_t_uncovered = the columns with cover 0.
+ *   6. Pairs.  Each pair is judged once, from the mate with the smaller read index.  Not both UNIQUE: pairs_not_unique.  Both UNIQUE on
+ *      different targets: pairs_split.  Both UNIQUE on the same target: with a, la the position and length of the `+` read and b, lb of the
+ *      `-` read, the pair is PROPER iff the strands differ, a <= b, a + la <= b + lb and insert = b + lb - a <= max_insert; a proper pair
+ *      does d_insert_hist[insert]++ (max_insert + 1 bins); anything else on the same target is pairs_improper.  insert_median = the smallest i
+ *      whose cumulative count reaches (proper + 1) / 2 (computed on the host from the histogram; -1 without proper pairs);
+ *      insert_mean_x100 = floor(100 * sum of the inserts / proper) (-1 without proper pairs).
+ *   7. Counters (alga_place_info): reads = n / 2, placed, unique, multi = placed - unique, unplaced = reads - placed; hits_saturated = reads
+ *      with more than 255 placements at best.mm; seeds = the seeds of all nodes with len >= k (both strands), seeds_over_max_occ = those with
+ *      occ > max_occ; index_positions, index_distinct (distinct k-mers among them); pairs = pairs_proper + pairs_improper + pairs_split +
+ *      pairs_not_unique.
+ * The lookups go through a directory on the top "place_dir_bits" bits of the k-mer (alga_engine_set_option; 0 = about two positions per
+ * bucket): the option changes no result.  Three read-backs: the refusal flags with the column count, the counters, the histogram.
+ * The result is engine-owned device memory, valid until the next placement call on `e`; a refused call leaves an earlier result valid.
+ *
+ * alga_place_reads_on_final_device: target t is the window of the pair fin.d_order[t] (target id == contig id): it begins at base
+ * 16 * u.d_word_off[k] + fin.d_begin[k] of cons.d_words and has length fin.d_len[k]; a TRIMMED_AWAY pair is a target of length 0.  `u`,
+ * `cons` and `fin` must be the engine's current results (refused as alga_write_final_fasta_device refuses); the call does not invalidate them.
+ * alga_write_final_fasta_depth_device: the records and sequences of alga_write_final_fasta_device with the header
+ * `>contig_id=<id>_length=<len>_reads=<t_reads>_depth=<q>.<dd>`, <q>.<dd> = floor(100 * t_bases / len) in integers, two decimals, formatted on
+ * the device.  `placements` must be the engine's current result of alga_place_reads_on_final_device on `fin`.  ABI stays 7: the calls add. */
+#define ALGA_PLACE_DEPTH_MULTI 1     /* alga_place_params.flags                                                                       */
+#define ALGA_PLACE_PLACED 1          /* bits of d_state                                                                               */
+#define ALGA_PLACE_UNIQUE 2
+#define ALGA_PLACE_MINUS  4
+typedef struct {
+    int32_t k, max_mismatches, max_occ, max_insert, flags;
+    int32_t reserved[3];             /* 0                                                                                             */
+} alga_place_params;
+typedef struct {
+    int64_t         n_reads;         /* n / 2                                                                                         */
+    int64_t         n_targets;
+    uint64_t        n_columns;       /* col_off[n_targets]                                                                            */
+    int64_t         n_hist;          /* max_insert + 1                                                                                */
+    const int32_t  *d_target, *d_pos;                /* n_reads                                                                       */
+    const uint8_t  *d_mm, *d_hits, *d_state;         /* n_reads                                                                       */
+    const uint32_t *d_col_off;       /* n_targets + 1                                                                                 */
+    const uint32_t *d_cover;         /* n_columns                                                                                     */
+    const uint64_t *d_t_reads, *d_t_bases, *d_t_mismatches, *d_t_uncovered;   /* n_targets                                            */
+    const uint64_t *d_insert_hist;   /* n_hist                                                                                        */
+} alga_placements;
+typedef struct {
+    uint64_t reads, placed, unique, multi, unplaced;
+    uint64_t hits_saturated, seeds, seeds_over_max_occ;
+    uint64_t index_positions, index_distinct;
+    uint64_t pairs, pairs_proper, pairs_improper, pairs_split, pairs_not_unique;
+    int64_t  insert_median, insert_mean_x100;
+    double   ms_index, ms_place, ms_depth;           /* device time (HIP events): gather + index, the placement kernel, depth + pairs */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_place_info;
+void alga_place_default_params(alga_place_params *p);
+int  alga_place_reads_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off /* may be NULL */, const uint32_t *d_words,
+                             const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets, const alga_place_params *p, void *hip_stream,
+                             alga_placements *out, alga_place_info *info /* may be NULL */);
+int  alga_place_reads_on_final_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off /* may be NULL */, const alga_unitigs *u,
+                                      const alga_consensus *cons, const alga_final_contigs *fin, const alga_place_params *p, void *hip_stream,
+                                      alga_placements *out, alga_place_info *info /* may be NULL */);
+int  alga_write_final_fasta_depth_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin,
+                                         const alga_placements *placements, const char *path, alga_gfa_info *info /* may be NULL */);
 
 #ifdef __cplusplus
 }
