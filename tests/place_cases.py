@@ -178,9 +178,60 @@ def _empty_short():
     return _make([np.concatenate(t), t[0]], t, shifts=[0, 0, 0, 0], gaps=[True, False, False, False])
 
 
+def _mid(a, b):
+    """one substitution in the middle of each of the seeds a .. b - 1 (k = 21)"""
+    return [K * j + 10 for j in range(a, b)]
+
+
+def _many_seeds_parts():
+    rng = _rng(14)
+    X, W = _seq(rng, 2800), _seq(rng, 2800)
+    W[:1344] = 0                         # seeds 0 .. 63 of W are the poly-A 21-mer: 1324 occurrences, over max_occ
+    t0 = np.concatenate([_seq(rng, 137), X, _seq(rng, 211)])
+    t1 = np.concatenate([_seq(rng, 55), _sub(X, [1500, 2000, 2500]), _seq(rng, 19)])
+    t2 = np.concatenate([_seq(rng, 80), W, _seq(rng, 90)])
+    return X, W, [t0, t1, t2]
+
+
+def _many_seeds():
+    # 133 seeds: three chunks of 64 in k_pl_place.  Read 1 is found only from chunk 1, read 2 only from chunk 2 (its last five seeds), read 4 from
+    # no seed; read 5 through chunk 1 while all of chunk 0 matches and is over max_occ; reads 7 .. 10 (65, 64, 64, 65 seeds) lie on t0 and t1 at
+    # equal mm through one seed each: exactly two placements
+    X, W, targets = _many_seeds_parts()
+    r2, r7 = _sub(X, _mid(0, 128)), _sub(X[100:1465], _mid(0, 64))
+    reads = [X, _sub(X, _mid(0, 64)), r2, P.revcomp(r2), _sub(X, _mid(0, 133)), W, P.revcomp(W), r7, _sub(X[100:1464], _mid(0, 63)),
+             _sub(X[100:1444], _mid(1, 64)), P.revcomp(r7), _sub(targets[1][55:2855], _mid(0, 64))]
+    return _make(reads, targets, shifts=[3, 9, 14], max_mismatches=140, max_occ=8)
+
+
+def _mm_limit():
+    # the uint8 mm and the mm << 33 of the key at their limit: 254 substitutions (none in seed 0) are placed, 255 are not
+    X, _, targets = _many_seeds_parts()
+    at = [K + 10 * i for i in range(255)]
+    return _make([_sub(X, at[:254]), _sub(X, at), P.revcomp(_sub(X, at[:254]))], targets[:1], shifts=[3], max_mismatches=254, max_occ=8)
+
+
+TINY_LENS = [0, 21, 22, 37, 0, 0, 64, 65, 16, 100, 5, 48, 0, 20, 129, 1, 63, 0, 33]
+
+
+def _tiny_targets():
+    # 150 targets, 39 of them empty: several seams inside one word of k_pl_gather, one wave of k_pl_uncovered, and equal offsets in pl_target_of
+    rng = _rng(15)
+    targets = [_seq(rng, TINY_LENS[i % 19]) for i in range(150)]
+    reads = []
+    for i, t in enumerate(targets):
+        if len(t) >= K and i % 3 != 2:
+            reads.append(P.revcomp(t) if i & 1 else t)
+        if len(t) >= 40 and i % 2 == 0:
+            reads.append(t[-25:])
+        if len(t) >= 60 and i % 4 == 1:
+            reads.append(_sub(t[3:40], [30]))
+    return _make(reads, targets, shifts=[5 * i % 16 for i in range(150)], gaps=[i % 4 != 1 for i in range(150)])
+
+
 CASES = {"exact": _exact, "bound": _bound, "last_seed_only": _last_seed_only, "every_seed_hit": _every_seed_hit, "ends": _ends, "unaligned": _unaligned,
          "repeat": _repeat, "palindrome": _palindrome, "saturate": _saturate, "pairs": _pairs, "rand": _rand, "empty_targets": _empty_targets,
-         "empty_reads": _empty_reads, "empty_short": _empty_short}
+         "empty_reads": _empty_reads, "empty_short": _empty_short, "many_seeds": _many_seeds, "mm_limit": _mm_limit, "tiny_targets": _tiny_targets}
 
 
 @functools.lru_cache(maxsize=None)
@@ -194,6 +245,63 @@ def rand_cut():
     c = dict(case("rand"))
     c.update(rows=c["rows"][:400], lens=c["lens"][:400], pair_off=c["pair_off"][:400])
     return c
+
+
+@functools.lru_cache(maxsize=None)
+def many_reads(n):
+    """n short reads (21 .. 48 nt) on four targets, one of them empty, behind eight 1400-nt reads (67 seeds: the usable masks of two chunks stay
+    in the scratch of the waves that take a short read next); consecutive reads are mates.  Not in CASES: the GPU test sizes n by the device,
+    so that a wave of k_pl_place takes more than one read"""
+    assert n % 2 == 0 and n >= 8
+    rng = _rng(16)
+    targets = [_seq(rng, 700), _seq(rng, 0), _seq(rng, 333), _seq(rng, 1200), _seq(rng, 1600)]
+    reads = []
+    for i in range(n):
+        if i < 8:
+            p = int(rng.integers(0, 201))
+            r = targets[4][p:p + 1400]
+        else:
+            t = targets[(0, 2, 3)[i % 3]]
+            L = int(rng.integers(21, 49))
+            p = int(rng.integers(0, len(t) - L + 1))
+            r = t[p:p + L]
+            if i % 5 == 0:
+                r = _sub(r, [int(rng.integers(0, L))])
+            if i % 7 == 0:
+                r = _seq(rng, L)
+        reads.append(P.revcomp(r) if i & 1 else r)
+    return _make(reads, targets, shifts=[3, 0, 9, 14, 6], pair_off=[1, 1, 2, 2] * (n // 2))
+
+
+HEADER_LENS = [21, 40, 64, 99, 100, 333, 1000, 1200, 50, 75, 150, 480, 999, 1001]
+HEADER_ENDS = {1000: "_reads=11_depth=1.05", 40: "_reads=120_depth=120.00", 1200: "_reads=1000_depth=", 333: "_reads=11_depth=10.30", 1001: "_reads=1_depth=0.04",
+               99: "_reads=1_depth=0.33", 21: "_reads=1_depth=1.00", 480: "_reads=3_depth=0.56",
+               999: "_reads=0_depth=0.00", 150: "_reads=0_depth=0.00", 100: "_reads=0_depth=0.00", 75: "_reads=0_depth=0.00", 64: "_reads=0_depth=0.00", 50: "_reads=0_depth=0.00"}
+
+
+def header_nodes():
+    """one random read of every length in HEADER_LENS: without edges each becomes a contig of its own, numbered by descending length"""
+    rng = _rng(17)
+    return P.nodes_of([_seq(rng, n) for n in HEADER_LENS])
+
+
+def header_reads(contigs):
+    """reads for the depth headers of contigs with the lengths of HEADER_LENS (code arrays, any order): every width of id, length, reads and
+    depth the device formats, HEADER_ENDS by length"""
+    rng = _rng(18)
+    by = {len(c): c for c in contigs}
+    assert sorted(by) == sorted(HEADER_LENS)
+    c = by[1000]
+    reads = [c[p:p + 100] for p in range(0, 1000, 100)] + [c[475:525]]          # 1050 bases: 1.05, the leading zero of dd
+    reads += [by[40]] * 120                                                       # 120.00: q >= 100
+    for _ in range(1000):                                                         # four-digit reads
+        L = int(rng.integers(21, 61))
+        a = int(rng.integers(0, 1200 - L + 1))
+        reads.append(by[1200][a:a + L])
+    reads += [by[333]] * 10 + [by[333][200:300]]                                  # 3430 bases: 10.30
+    reads += [by[1001][900:950], by[99][50:83], by[21]]                           # 0.04, 0.33, 1.00
+    reads += [P.revcomp(by[480][a:a + 90]) for a in (0, 100, 390)]                # the minus strand only: 270 bases, 0.56
+    return reads                                                                  # 999, 150, 100, 75, 64, 50: no read
 
 
 def args(c):

@@ -1,7 +1,7 @@
 """The read placement on the GPU (alga_place_reads_device, alga_place_reads_on_final_device, alga_write_final_fasta_depth_device): every output
 array and every counter equal to the Python definition (tests/place_checker.py) on the cases of tests/place_cases.py, through host arrays and
-through tensors, whatever the directory; refusals leave an earlier result valid; the capacity bound; the whole chain on a genome with a repeat;
-the command line."""
+through tensors, whatever the directory; more reads than k_pl_place has waves; the caller's stream; refusals leave an earlier result valid;
+the capacity bound; the whole chain on a genome with a repeat; every width of the depth header; the command line."""
 import os
 import subprocess
 
@@ -58,7 +58,7 @@ def test_every_case_equals_the_checker(eng, name):
     print(name, pl.info)
 
 
-@pytest.mark.parametrize("name", ["rand", "repeat", "unaligned", "saturate"])
+@pytest.mark.parametrize("name", ["rand", "repeat", "unaligned", "saturate", "many_seeds", "tiny_targets"])
 def test_the_directory_changes_nothing(eng, name):
     c = PC.case(name)
     try:
@@ -71,6 +71,38 @@ def test_the_directory_changes_nothing(eng, name):
             assert_same(pl.to_host(), P.place(*PC.args(c), **dict(c["params"], k=k)), (name, "k", k))
     finally:
         eng.set_option("place_dir_bits", 0)
+
+
+def test_a_wave_takes_more_than_one_read(eng):
+    """k_pl_place runs at most 8 blocks of 4 waves per CU and a wave walks r += n_waves: with more reads than waves the state of a read (best,
+    lane_mm, lane_cnt, the usable masks that the 1400-nt reads 0 .. 7 left in the scratch of waves 0 .. 7) must not reach the wave's next one"""
+    import torch
+    waves = 32 * torch.cuda.get_device_properties(0).multi_processor_count
+    n = (waves + 808 + 1) // 2 * 2
+    assert n > waves
+    c = PC.many_reads(n)
+    want = P.place(*PC.args(c), **c["params"])
+    late = want["state"][waves:]
+    assert (late & P.PLACED).any() and (late == 0).any() and (late & P.MINUS).any()
+    assert (c["lens"][:16] // PC.K > 64).all() and want["info"]["pairs"] == n // 2
+    pl = eng.place_reads(c["rows"], c["lens"], targets=(c["twords"], c["tbegin"], c["tlen"]), pair_off=c["pair_off"], **c["params"])
+    assert_same(pl.to_host(), want, "many_reads(%d)" % n)
+    print(n, pl.info)
+
+
+def test_the_callers_stream(eng):
+    """tensors made on a stream of the caller's, the call on that stream; then a call on the engine's own stream"""
+    import torch
+    c = PC.case("pairs")
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        rows, lens, targets, po = device_args(c)
+    assert s.cuda_stream != 0 and s.cuda_stream != torch.cuda.current_stream().cuda_stream
+    pl = eng.place_reads(rows, lens, targets=targets, pair_off=po, stream=s.cuda_stream, **c["params"])
+    assert s.query()                                                             # the call returns with its work on the stream done
+    assert_same(pl.to_host(), PC.checked("pairs"), "on the caller's stream")
+    pl = eng.place_reads(rows, lens, targets=targets, pair_off=po, **c["params"])
+    assert_same(pl.to_host(), PC.checked("pairs"), "on the engine's stream afterwards")
 
 
 def test_refusals_leave_an_earlier_result_valid(eng):
@@ -176,6 +208,40 @@ def test_whole_chain_depth_of_the_final_contigs(eng, chain, tmp_path):
         eng.place_reads(r.words, r.lens, final=fin2)
     assert ei.value.code == -1
     assert c2.n_pairs == u.n_pairs
+
+
+def test_depth_header_widths(eng, tmp_path):
+    """`>contig_id=<id>_length=<L>_reads=<n>_depth=<q>.<dd>` is formatted on the device with widths computed by hand: ids of one and two digits,
+    lengths of two to four, reads of one to four (0 among them), q of one to three, dd below and above 10 (PC.HEADER_ENDS).  The contig set:
+    14 reads without an edge, every one a contig of its own (tests/test_place_cpu.py: what the checkers of those stages say)"""
+    words, lens = PC.header_nodes()
+    u = eng.unitigs(words, lens, np.zeros((0, 3), np.int32), skip_isolated=False)
+    c = eng.unitig_consensus(words, lens, u, min_votes=0)
+    fin = eng.final_contigs(u, c, 1, 95, 0)
+    uh, ch, fh = u.to_host(), c.to_host(), fin.to_host()
+    tw, tb, tl = final_targets(uh, ch, fh)
+    assert fin.n_accepted == 14 == fin.n_written and tl.tolist() == sorted(PC.HEADER_LENS, reverse=True)
+    rows, rlens = P.nodes_of(PC.header_reads([P.codes_of(tw, tb[j], int(tl[j])) for j in range(14)]))
+    pl = eng.place_reads(rows, rlens, final=fin)
+    want = P.place(rows, rlens, None, tw, tb, tl)
+    assert_same(pl.to_host(), want, "the header case")
+    plain, deep = str(tmp_path / "plain.fasta"), str(tmp_path / "depth.fasta")
+    eng.write_final_fasta(plain, fin)
+    info = eng.write_final_fasta(deep, fin, placements=pl)
+    a, b = open(plain).read().split("\n"), open(deep).read().split("\n")
+    assert len(a) == len(b) == 29 and a[-1] == b[-1] == "" and a[1::2] == b[1::2] and info["segments"] == 14 and info["bytes"] == os.path.getsize(deep)
+    assert b[0:28:2] == [P.depth_header(j, int(tl[j]), want["t_reads"][j], want["t_bases"][j]) for j in range(14)]
+    for j, h in enumerate(b[0:28:2]):
+        L = int(tl[j])
+        assert h.startswith(a[2 * j] + "_reads=") and a[2 * j] == ">contig_id=%d_length=%d" % (j, L) and len(b[2 * j + 1]) == L
+        assert h.endswith(PC.HEADER_ENDS[L]) if L != 1200 else PC.HEADER_ENDS[L] in h, h
+    heads = dict(zip(tl.tolist(), b[0:28:2]))
+    assert heads[1000] == ">contig_id=2_length=1000_reads=11_depth=1.05" and heads[40] == ">contig_id=12_length=40_reads=120_depth=120.00"
+    assert heads[999] == ">contig_id=3_length=999_reads=0_depth=0.00" and heads[50] == ">contig_id=11_length=50_reads=0_depth=0.00"
+    assert heads[1200].startswith(">contig_id=0_length=1200_reads=1000_depth=") and heads[21] == ">contig_id=13_length=21_reads=1_depth=1.00"
+    minus = (want["state"] & P.MINUS).astype(bool)
+    on480 = want["target"] == tl.tolist().index(480)
+    assert on480.sum() == 3 and minus[on480].all() and not minus[~on480].any() and int(want["t_reads"][0]) == 1000
 
 
 F_KEYS = ("verdict", "rank", "id", "new_reads", "trim_left", "begin", "len", "order")

@@ -10,8 +10,11 @@ import numpy as np
 import pytest
 
 import alga_amd
+import consensus_checker as S
+import final_checker as F
 import place_cases as PC
 import place_checker as P
+import unitig_checker as U
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ["k_pl_node_check", "k_pl_target_check", "k_pl_final_targets", "k_pl_gather", "k_pl_keys", "k_pl_dir", "k_pl_place", "k_pl_depth_add",
@@ -37,6 +40,16 @@ def test_the_two_statements_agree_on_a_cut_of_rand():
     got = P.place(*PC.args(c), **c["params"])
     assert_same(got, P.place_bruteforce(*PC.args(c), **c["params"]), "rand cut")
     assert got["info"]["multi"] > 0 and got["info"]["unplaced"] > 0 and got["info"]["pairs_proper"] > 0
+
+
+def test_the_two_statements_agree_on_many_reads():
+    c = PC.many_reads(600)
+    got = P.place(*PC.args(c), **c["params"])
+    assert_same(got, P.place_bruteforce(*PC.args(c), **c["params"]), "many_reads(600)")
+    assert got["state"][:8].tolist() == [3, 7] * 4 and (c["lens"][:16] == 1400).all() and c["lens"][16:].max() <= 48      # 67 seeds, then one or two
+    i, short = got["info"], got["state"][8:]
+    assert i["pairs"] == 300 and i["placed"] > 300 and (short == 0).sum() > 100 and (short & P.MINUS).astype(bool).sum() > 100
+    assert (got["t_reads"] > 0).tolist() == [True, False, True, True, True]
 
 
 def test_outcomes_the_cases_were_made_for():
@@ -67,6 +80,24 @@ def test_outcomes_the_cases_were_made_for():
     w = PC.checked("pairs")["info"]
     assert (w["pairs"], w["pairs_proper"], w["pairs_improper"], w["pairs_split"], w["pairs_not_unique"]) == (17, 9, 5, 1, 2)
     assert w["insert_median"] == 300 and PC.checked("pairs")["insert_hist"][400] == 1
+    w = PC.checked("many_seeds")                                                # 133 seeds: chunks of 64 seeds, see the case
+    assert w["target"].tolist() == [0, 0, 0, 0, -1, 2, 2, 0, 0, 0, 0, 1] and w["pos"].tolist() == [137, 137, 137, 137, -1, 80, 80, 237, 237, 237, 237, 55]
+    assert w["mm"].tolist() == [0, 64, 128, 128, 0, 0, 0, 64, 63, 63, 64, 64] and w["hits"].tolist() == [1, 1, 1, 1, 0, 1, 1, 2, 2, 2, 2, 1]
+    assert w["state"].tolist() == [3, 3, 3, 7, 0, 3, 7, 1, 1, 1, 5, 3] and w["info"]["seeds_over_max_occ"] == 128
+    assert (PC.case("many_seeds")["lens"][1::2] // PC.K).tolist() == [133, 133, 133, 133, 133, 133, 133, 65, 64, 64, 65, 133]
+    c = PC.case("many_seeds")
+    w = P.place(*PC.args(c), **dict(c["params"], k=8))                          # 350 seeds; read 4 has a seed left
+    assert w["state"].tolist() == [3, 3, 3, 7, 3, 3, 7, 1, 1, 1, 5, 3] and w["mm"][4] == 133 and w["hits"].tolist() == [1] * 7 + [2] * 4 + [1]
+    w = P.place(*PC.args(c), **dict(c["params"], k=31))
+    assert w["state"].tolist() == [3, 3, 3, 7, 0, 3, 7, 0, 1, 1, 0, 3]
+    w = PC.checked("mm_limit")
+    assert w["mm"].tolist() == [254, 0, 254] and w["state"].tolist() == [3, 0, 7] and w["hits"].tolist() == [1, 0, 1]
+    for flags in (0, P.DEPTH_MULTI):
+        w, tl = PC.checked("tiny_targets", flags), PC.case("tiny_targets")["tlen"]
+        un = w["t_uncovered"].astype(np.int64)
+        assert (w["info"]["reads"], w["info"]["unique"], len(w["cover"]), int(w["cover"].max())) == (87, 87, 4959, 2)
+        assert [int((tl > 0).sum()), int(((tl > 0) & (un == 0)).sum()), int(((un > 0) & (un < tl)).sum()), int(((tl > 0) & (un == tl)).sum())] == [111, 53, 10, 48]
+    assert P.place(*PC.args(PC.case("tiny_targets")), k=8)["info"]["index_positions"] > w["info"]["index_positions"]             # the 16- and 20-base targets
     for name in ("empty_targets", "empty_reads", "empty_short"):
         w = PC.checked(name)
         assert w["info"]["placed"] == 0 and w["info"]["index_positions"] == (250 if name == "empty_reads" else 0) and (w["cover"] == 0).all()
@@ -82,6 +113,31 @@ def test_sums_on_rand():
         assert int(w["t_reads"].sum()) == (i["placed"] if flags else i["unique"])
         assert i["multi"] > 20 and i["unplaced"] > 20 and 200 <= i["insert_median"] <= 500
     print(i)
+
+
+def test_depth_headers_the_header_case_was_made_for():
+    """the contig set of the GPU test's header case by the checkers of the earlier stages (every read its own accepted contig, ids by
+    descending length), and the header ends the reads of PC.header_reads were chosen for"""
+    words, lens = PC.header_nodes()
+    u = U.unitigs(words, lens, np.zeros((0, 3), np.int32), skip_isolated=False)
+    cons = S.consensus_pileup(words, lens, u, 0)
+    fin = F.final_contigs(u, cons, 1, 95, 0)
+    order = fin["order"].astype(np.int64)
+    assert fin["n_accepted"] == fin["n_written"] == 14 and fin["len"][order].tolist() == sorted(PC.HEADER_LENS, reverse=True)
+    begin = 16 * np.asarray(u["word_off"]).astype(np.int64)[order] + fin["begin"][order]
+    tlen = fin["len"][order].astype(np.int32)
+    contigs = [P.codes_of(cons["words"], begin[j], int(tlen[j])) for j in range(14)]
+    rows, rlens = P.nodes_of(PC.header_reads(contigs))
+    w = P.place(rows, rlens, None, cons["words"], begin, tlen)
+    assert w["info"]["unique"] == w["info"]["reads"] == len(rlens) // 2 == 11 + 120 + 1000 + 11 + 3 + 3
+    minus = (w["state"] & P.MINUS).astype(bool)
+    for j in range(14):
+        h = P.depth_header(j, int(tlen[j]), w["t_reads"][j], w["t_bases"][j])
+        assert h.startswith(">contig_id=%d_length=%d_reads=" % (j, tlen[j])) and PC.HEADER_ENDS[int(tlen[j])] in h, h
+        if tlen[j] != 1200:
+            assert h.endswith(PC.HEADER_ENDS[int(tlen[j])]), h
+        assert minus[w["target"] == j].all() == (tlen[j] == 480) or w["t_reads"][j] == 0
+    assert tlen[10:].tolist() == [64, 50, 40, 21]                                # the two-digit ids have two-digit lengths
 
 
 def test_refusals_of_the_checker():
