@@ -182,6 +182,14 @@ struct alga_engine {
     uint64_t    pl_final_epoch = 0;                // ... made on the final result of this epoch (0: on caller's targets)
     uint64_t    fc_epoch = 0;                      // counts the alga_final_contigs_device calls that wrote a result
     int         opt_place_dir_bits = 0;            // option "place_dir_bits": bits of the placement index's directory, 0 = about two positions per bucket
+    // the placed targets voted again (engine_polish.hip).  Workspaces: counters, the (first column, node) pairs before and after the sort, the
+    // per-word masks, their popcounts and the scan.  The result: its own copy of col_off, the polished column array, the change list, the
+    // per-target sums (changed, ambiguous), the optional counts
+    DevBuf      po_cnt, po_keys[2], po_vals[2], po_marks, po_pop, po_scan;
+    DevBuf      po_coloff, po_words, po_ccols, po_cbases, po_tstat, po_counts;
+    bool        po_valid = false;                  // the result buffers hold a polish
+    uint64_t    po_targets = 0, po_columns = 0;    // ... of this many targets and columns
+    uint64_t    po_final_epoch = 0;                // ... of a placement on the final result of this epoch (0: on caller's targets)
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

@@ -178,7 +178,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_contigs_device", "alga_contig_trim_device", "alga_final_contigs_device", "alga_write_final_fasta_device",
            "alga_extend_contigs_device", "alga_extend_seams_get",
            "alga_correct_default_params", "alga_correct_reads_device", "alga_correct_parsed_reads", "alga_ingest_corrected_device",
-           "alga_place_default_params", "alga_place_reads_device", "alga_place_reads_on_final_device", "alga_write_final_fasta_depth_device"]
+           "alga_place_default_params", "alga_place_reads_device", "alga_place_reads_on_final_device", "alga_write_final_fasta_depth_device",
+           "alga_polish_default_params", "alga_polish_placed_device", "alga_write_polished_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -440,6 +441,61 @@ class Placements:
         return d
 
 
+POLISH_MULTI, POLISH_COUNTS = 1, 2                               # alga_polish_params.flags
+
+
+class PolishParams(C.Structure):
+    """alga_polish_params"""
+    _fields_ = [(k, C.c_int32) for k in ("min_cover", "min_percent", "flags")] + [("reserved", C.c_int32 * 5)]
+
+
+class PolishInfo(C.Structure):
+    """alga_polish_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("columns", "voters", "votes", "voted_columns", "changed", "ambiguous", "max_cover")] + \
+               [(k, C.c_double) for k in ("ms_sort", "ms_vote", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PolishedC(C.Structure):
+    """alga_polished"""
+    _fields_ = [("n_targets", C.c_int64), ("n_columns", C.c_uint64), ("n_changed", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_col_off", "d_words", "d_changed_cols", "d_changed_bases", "d_t_changed", "d_t_ambiguous", "d_counts")]
+
+
+class Polished:
+    """Result of Engine.polish: zero-copy torch views of the engine's device memory (valid until the next Engine.polish call on that engine;
+    clone what has to live longer) -- col_off int32 [n_targets + 1], words int32 [(n_columns + 15) / 16 + 2] (the bits of uint32: column g
+    in word g >> 4 at bits 2 * (g & 15)), changed_cols int32 [n_changed] (the bits of uint32, ascending), changed_bases uint8 [n_changed]
+    (old | new << 2), t_changed / t_ambiguous int64 [n_targets], counts int32 [n_columns, 4] or None -- and .info (dict of alga_polish_info)."""
+    KEYS = (("col_off", "<i4", np.uint32), ("words", "<i4", np.uint32), ("changed_cols", "<i4", np.uint32), ("changed_bases", "|u1", np.uint8),
+            ("t_changed", "<i8", np.uint64), ("t_ambiguous", "<i8", np.uint64))
+
+    def __init__(self, c, info, device, placements=None):
+        self._c, self.info, self._placements = c, info, placements
+        self.n_targets, self.n_columns, self.n_changed = int(c.n_targets), int(c.n_columns), int(c.n_changed)
+        dev = "cuda:%d" % device
+        shape = dict(col_off=self.n_targets + 1, words=(self.n_columns + 15) // 16 + 2, changed_cols=self.n_changed, changed_bases=self.n_changed)
+        for k, typestr, _ in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (shape.get(k, self.n_targets),), dev, typestr))
+        self.counts = device_view(c.d_counts, (self.n_columns, 4), dev, "<i4") if c.d_counts else None
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/polish_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt in self.KEYS}
+        d["counts"] = None if self.counts is None else self.counts.cpu().numpy().copy().view(np.uint32)
+        d["info"] = dict(self.info)
+        return d
+
+    def targets(self):
+        """(words, begin int64 [T], len int32 [T]): the polished sequences as the ragged target set Engine.place_reads(targets=...) takes
+        (the words are the engine's; begin and len are new tensors)"""
+        import torch
+        off = self.col_off.to(torch.int64) & 0xFFFFFFFF
+        return self.words, off[:-1].contiguous(), (off[1:] - off[:-1]).to(torch.int32).contiguous()
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -576,6 +632,12 @@ def load_library():
     lib.alga_correct_parsed_reads.argtypes = [C.c_void_p, C.POINTER(ParsedReads), C.POINTER(CorrectParams), C.POINTER(CorrectInfo)]
     lib.alga_ingest_corrected_device.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(IngestParams), C.POINTER(CorrectParams), C.POINTER(DeviceNodeSet),
                                                  C.POINTER(IngestInfo), C.POINTER(CorrectInfo)]
+    lib.alga_polish_default_params.argtypes = [C.POINTER(PolishParams)]
+    lib.alga_polish_default_params.restype = None
+    lib.alga_polish_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(PlacementsC), C.POINTER(PolishParams), C.c_void_p, C.POINTER(PolishedC),
+                                              C.POINTER(PolishInfo)]
+    lib.alga_write_polished_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.POINTER(FinalContigsC), C.POINTER(PlacementsC),
+                                                     C.POINTER(PolishedC), C.c_int32, C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1414,11 +1476,18 @@ class Engine:
                                                         int(trim_threshold), 0, None, C.byref(out), C.byref(info)))
         return FinalContigs(out, info.as_dict(), unitigs, consensus, self.device)
 
-    def write_final_fasta(self, path, final, placements=None):
+    def write_final_fasta(self, path, final, placements=None, polished=None, depth=True):
         """The accepted contigs of the LAST Engine.final_contigs call as FASTA (alga_write_final_fasta_device) -> dict of alga_gfa_info
         (segments = records): `>contig_id=<id>_length=<len>` and the window on one line, in id order.  placements: the result of the LAST
-        Engine.place_reads(final=final) call -- the headers then end in `_reads=<n>_depth=<q>.<dd>` (alga_write_final_fasta_depth_device)."""
+        Engine.place_reads(final=final) call -- the headers then end in `_reads=<n>_depth=<q>.<dd>` (alga_write_final_fasta_depth_device).
+        polished: the result of the LAST Engine.polish of those placements -- the sequences are then the polished ones
+        (alga_write_polished_fasta_device), the headers with the depth iff `depth`."""
         info = GfaInfo()
+        if polished is not None:
+            assert placements is not None, "polished needs the placements it was made from"
+            self._check(self._lib.alga_write_polished_fasta_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
+                                                                   C.byref(placements._c), C.byref(polished._c), 1 if depth else 0, os.fsencode(path), C.byref(info)))
+            return info.as_dict()
         if placements is not None:
             self._check(self._lib.alga_write_final_fasta_depth_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
                                                                       C.byref(placements._c), os.fsencode(path), C.byref(info)))
@@ -1475,6 +1544,31 @@ class Engine:
                                                           C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(pp), st,
                                                           C.byref(out), C.byref(info)))
         return Placements(out, info.as_dict(), self.device, final)
+
+    def polish(self, words, lens, placements, min_cover=3, min_percent=60, multi=False, counts=False, stream=None):
+        """The placed targets voted again by every placed read (alga_polish_placed_device) -> Polished.  words / lens: the node set that was
+        placed; placements: the result of the LAST Engine.place_reads call.  A column changes to the base with the most votes iff its cover is
+        at least min_cover and that base has at least min_percent of it; multi: MULTI reads vote too; counts: keep the four counts per column."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = PolishParams(), PolishedC(), PolishInfo()
+        pp.min_cover, pp.min_percent, pp.flags = int(min_cover), int(min_percent), (POLISH_MULTI if multi else 0) | (POLISH_COUNTS if counts else 0)
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_polish_placed_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(pp), st, C.byref(out), C.byref(info)))
+        return Polished(out, info.as_dict(), self.device, placements)
 
     def write_graph(self, path, n_nodes, edges):
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)

@@ -7,7 +7,7 @@
 //            [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N]
 //            [--contigs_final=final.fasta] [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]
 //            [--correct_reads=0|1] [--correct_k=21] [--correct_solid=3] [--corrected_reads=reads.fasta]
-//            [--contigs_depth=0|1] [--placements=placements.tsv]
+//            [--contigs_depth=0|1] [--placements=placements.tsv] [--polish=0|1] [--polish_changes=changes.tsv]
 //
 // --gpus=N: the overlap graph on the GPUs K .. K+N-1 of this node (alga_multi_*, include/alga_amd.h: one host thread and one engine
 // per GPU, keys and edge lists exchanged over RCCL / xGMI) -- the counterpart of the reference's --threads for this stage
@@ -61,6 +61,11 @@
 // gives placed / unique / multi / unplaced reads, proper pairs and the median insert.  --placements=PATH (needs --contigs_final= too): one line
 // `read target pos strand mm hits` per read, tab separated, target -1 and strand `.` for an unplaced read.  With both off every file is what it
 // was without them; neither is passed through.
+// --polish=1 (default 0; needs --contigs_final= and implies the placement): every column of the final contigs is voted again by every uniquely
+// placed read (alga_polish_placed_device with its defaults: cover 3, 60 %) and the final FASTA holds the polished sequences
+// (alga_write_polished_fasta_device); its headers carry the depth iff --contigs_depth=1.  One line on stderr gives voters / voted columns /
+// changed / ambiguous.  --polish_changes=PATH (needs --polish=1): one line `contig pos old new A C G T` per changed column, tab separated, no
+// header line, the four counts of the column behind the bases.  Neither is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -84,7 +89,7 @@ static const char *USAGE =
     "         [--consensus_min_votes=3] [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N] [--contigs_final=final.fasta]\n"
     "         [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]\n"
     "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n"
-    "         [--contigs_depth=0|1] [--placements=placements.tsv]\n";
+    "         [--contigs_depth=0|1] [--placements=placements.tsv] [--polish=0|1] [--polish_changes=changes.tsv]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -99,8 +104,8 @@ int main(int argc, char **argv) {
     double error_rate = 0.0;
     int device = 0, serialize = 1, gpus = 1, clip_tips = 0, parallel_paths = 0, consensus_min_length = 200, consensus_min_votes = 3, contigs_min_length = -1, contigs_new_reads_percent = 95, contigs_trim_threshold = 25, paired_extend = 0;
     int correct_reads = 0;
-    std::string corrected_reads, placements;
-    int contigs_depth = 0;
+    std::string corrected_reads, placements, polish_changes;
+    int contigs_depth = 0, polish = 0;
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -134,6 +139,8 @@ int main(int argc, char **argv) {
         else if (opt(a, "--contigs_final", v)) contigs_final = v;
         else if (opt(a, "--contigs_depth", v)) contigs_depth = atoi(v.c_str());
         else if (opt(a, "--placements", v)) placements = v;
+        else if (opt(a, "--polish", v)) polish = atoi(v.c_str());
+        else if (opt(a, "--polish_changes", v)) polish_changes = v;
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -151,7 +158,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -159,6 +166,8 @@ int main(int argc, char **argv) {
     if (crp.solid_min < 1) { fprintf(stderr, "alga_hip: --correct_solid must be >= 1 (got %d)\n", crp.solid_min); return 2; }
     if (!correct_reads && !corrected_reads.empty()) { fprintf(stderr, "alga_hip: --corrected_reads= needs --correct_reads=1\n"); return 2; }
     if ((contigs_depth || !placements.empty()) && contigs_final.empty()) { fprintf(stderr, "alga_hip: --contigs_depth=1 and --placements= need --contigs_final=\n"); return 2; }
+    if (polish && contigs_final.empty()) { fprintf(stderr, "alga_hip: --polish=1 needs --contigs_final=\n"); return 2; }
+    if (!polish && !polish_changes.empty()) { fprintf(stderr, "alga_hip: --polish_changes= needs --polish=1\n"); return 2; }
     if (correct_reads && !alga_exe.empty()) {
         fprintf(stderr, "alga_hip: --correct_reads=1 cannot be combined with --alga=: stock ALGA would read the original files, whose nodes are not the corrected graph's\n");
         return 2;
@@ -450,7 +459,7 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
-                if (rc == ALGA_OK && (contigs_depth || !placements.empty())) {
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish)) {
                     // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
                     alga_parsed_reads pr{};
                     char perr[512] = {0};
@@ -496,8 +505,39 @@ int main(int argc, char **argv) {
                                     (int) mm[r], (int) hits[r]);
                         if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", placements.c_str()); return 1; }
                     }
-                    if (rc == ALGA_OK) rc = contigs_depth ? alga_write_final_fasta_depth_device(engine, &cu, &cs, &fc, &pl, contigs_final.c_str(), &ffi)
-                                                          : alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
+                    alga_polished pol{};
+                    if (rc == ALGA_OK && polish) {
+                        alga_polish_params qp;
+                        alga_polish_default_params(&qp);
+                        if (!polish_changes.empty()) qp.flags |= ALGA_POLISH_COUNTS;
+                        alga_polish_info qi;
+                        rc = alga_polish_placed_device(engine, &pnd, &pl, &qp, nullptr, &pol, &qi);
+                        if (rc == ALGA_OK)
+                            fprintf(stderr, "Final contigs polished (cover %d, %d %%): %llu voters, %llu voted columns of %llu, %llu changed, %llu ambiguous, cover up to %llu; "
+                                    "device ms: sort %.3f vote %.3f, call %.1f ms wall\n", qp.min_cover, qp.min_percent, (unsigned long long) qi.voters,
+                                    (unsigned long long) qi.voted_columns, (unsigned long long) qi.columns, (unsigned long long) qi.changed,
+                                    (unsigned long long) qi.ambiguous, (unsigned long long) qi.max_cover, qi.ms_sort, qi.ms_vote, qi.ms_total);
+                    }
+                    if (rc == ALGA_OK && polish && !polish_changes.empty()) {   // not a hot path: the host formats from the arrays that came back
+                        const size_t nc = (size_t) pol.n_changed, nt = (size_t) pol.n_targets, ncol = (size_t) pol.n_columns;
+                        std::vector<uint32_t> cols(nc), off(nt + 1), counts(4 * ncol);
+                        std::vector<uint8_t> bases(nc);
+                        rc = alga_copy_to_host(engine, off.data(), pol.d_col_off, (nt + 1) * sizeof(uint32_t));
+                        if (rc == ALGA_OK && nc) rc = alga_copy_to_host(engine, cols.data(), pol.d_changed_cols, nc * sizeof(uint32_t));
+                        if (rc == ALGA_OK && nc) rc = alga_copy_to_host(engine, bases.data(), pol.d_changed_bases, nc);
+                        if (rc == ALGA_OK && ncol) rc = alga_copy_to_host(engine, counts.data(), pol.d_counts, 4 * ncol * sizeof(uint32_t));
+                        FILE *f = rc == ALGA_OK ? fopen(polish_changes.c_str(), "w") : nullptr;
+                        if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", polish_changes.c_str()); return 1; }
+                        for (size_t i = 0; f && i < nc; i++) {
+                            const size_t t = (size_t) (std::upper_bound(off.begin(), off.end(), cols[i]) - off.begin()) - 1;
+                            const uint32_t *c4 = &counts[4 * (size_t) cols[i]];
+                            fprintf(f, "%zu\t%u\t%c\t%c\t%u\t%u\t%u\t%u\n", t, cols[i] - off[t], "ACGT"[bases[i] & 3], "ACGT"[(bases[i] >> 2) & 3], c4[0], c4[1], c4[2], c4[3]);
+                        }
+                        if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", polish_changes.c_str()); return 1; }
+                    }
+                    if (rc == ALGA_OK) rc = polish ? alga_write_polished_fasta_device(engine, &cu, &cs, &fc, &pl, &pol, contigs_depth, contigs_final.c_str(), &ffi)
+                                        : contigs_depth ? alga_write_final_fasta_depth_device(engine, &cu, &cs, &fc, &pl, contigs_final.c_str(), &ffi)
+                                                        : alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
                     alga_device_free(engine, d_rows); alga_device_free(engine, d_plen); alga_device_free(engine, d_po);
                     alga_free_parsed_reads(&pr);
                 } else

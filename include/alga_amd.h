@@ -1244,6 +1244,74 @@ int  alga_place_reads_on_final_device(alga_engine *e, const alga_nodes *nodes, c
 int  alga_write_final_fasta_depth_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin,
                                          const alga_placements *placements, const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- the placed targets polished: every column voted again by every placed read (alga_amd/csrc/polish_kernels.hip, engine_polish.hip) ----
+ * The consensus decides a column from the reads of the contig's PATH; after the placement every input read lies over the final sequences,
+ * also those the graph stages dropped.  This stage lets them all vote.  Substitutions only, integers only, free of any order (thread, sort);
+ * tests/polish_checker.py states the rule twice in Python and the device result equals it array for array.
+ *
+ * Inputs: the node set that was placed (twin layout), the engine's current placement result `pl` (from either placement call), and
+ * alga_polish_params: min_cover 1 .. 2^31 - 1 (default 3), min_percent 1 .. 100 (60), flags ALGA_POLISH_MULTI | ALGA_POLISH_COUNTS (0);
+ * anything else answers ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Voters.  Read r votes iff its state has ALGA_PLACE_UNIQUE; with ALGA_POLISH_MULTI iff it has ALGA_PLACE_PLACED; at its best placement.
+ *      Its voting node is v = 2r if ALGA_PLACE_MINUS, else 2r + 1.  With L = len[v] and g0 = col_off[target[r]] + pos[r], base i of v gives
+ *      one vote for its code at column g0 + i, 0 <= i < L.
+ *   2. Counts.  count[g][b] = the votes for base b at column g, exact up to 2^32 - 1; cover[g] = their sum over b.  (Where the placement's
+ *      depth mode agrees with the flag, cover[g] == pl.d_cover[g].)
+ *   3. Decision.  cur = the base of the placed target at column g, read from the column array the placement call kept (the caller does not
+ *      pass the targets again).  w = the base with the largest count; a tie goes to cur if it is among the tied bases, else to the smallest
+ *      code.  Column g CHANGES to w iff w != cur, cover[g] >= min_cover and 100 * count[g][w] >= min_percent * cover[g] (64-bit products);
+ *      it is AMBIGUOUS iff w != cur, cover[g] >= min_cover and the percentage test fails; every other column keeps cur.
+ *   4. Result (alga_polished; engine-owned, valid until the next polish call on `e`: a later placement call does not invalidate it, a refused
+ *      call leaves an earlier result valid).  n_targets, n_columns, d_col_off (a copy of the placement's); d_words: the polished targets in
+ *      column space, column g in word g >> 4 at bits 2 * (g & 15), (n_columns + 15) / 16 + 2 words, the bits past n_columns zero; n_changed,
+ *      d_changed_cols (uint32, ascending), d_changed_bases (uint8, old | new << 2); d_t_changed, d_t_ambiguous (uint64 per target); with
+ *      ALGA_POLISH_COUNTS d_counts, uint32 [4 * n_columns], the count of base b of column g at 4 * g + b, else NULL.
+ *      (d_words, begin[t] = col_off[t], len[t] = col_off[t + 1] - col_off[t]) is a ragged target set as alga_place_reads_device takes it:
+ *      a second round is place -> polish on the first round's output.  The polish reads cur from the placement's copy, so it may overwrite
+ *      the buffer its own targets came from.
+ *   5. Counters (alga_polish_info): columns, voters, votes (the sum of their lengths), voted_columns (cover >= min_cover), changed,
+ *      ambiguous, max_cover; ms_sort, ms_vote (HIP events), ms_total (wall).
+ *   6. Refusals, all checked on the device before anything of the result is written (ALGA_ERR_INVALID_ARGUMENT): `pl` is not the engine's
+ *      current placement result; nodes->n / 2 != pl.n_reads; a voter with len < 1 or len > 16 * stride_words; a voter with its target
+ *      outside [0, n_targets), pos < 0 or pos + len > len[target].  The last check is what keeps a wrong node set from writing outside the
+ *      arrays: the vote kernel relies on it and on nothing else.  An allocation that fails answers ALGA_ERR_OUT_OF_MEMORY (d_counts takes
+ *      16 bytes per column).
+ * The voters are sorted by first column with the engine's radix sort; every output word is then GATHERED by one lane (no atomic per base),
+ * bit-sliced counters up to a cover of 255 and 32-bit counters above.  One read-back for the checks, one for the counters.
+ *
+ * alga_write_polished_fasta_device: the records of alga_write_final_fasta_device (depth_header == 0) or of
+ * alga_write_final_fasta_depth_device (!= 0) -- same ids, lengths and order -- with the sequence taken from pol.d_words.  `pl` must be the
+ * engine's current result of alga_place_reads_on_final_device on `fin`, `pol` the current polish of it.  ABI stays 7: the calls add. */
+#define ALGA_POLISH_MULTI  1         /* alga_polish_params.flags                                                                      */
+#define ALGA_POLISH_COUNTS 2
+typedef struct {
+    int32_t min_cover, min_percent, flags;
+    int32_t reserved[5];             /* 0                                                                                             */
+} alga_polish_params;
+typedef struct {
+    int64_t         n_targets;
+    uint64_t        n_columns;
+    uint64_t        n_changed;
+    const uint32_t *d_col_off;       /* n_targets + 1                                                                                 */
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+    const uint32_t *d_changed_cols;  /* n_changed                                                                                     */
+    const uint8_t  *d_changed_bases; /* n_changed                                                                                     */
+    const uint64_t *d_t_changed, *d_t_ambiguous;     /* n_targets                                                                     */
+    const uint32_t *d_counts;        /* 4 * n_columns, or NULL                                                                        */
+} alga_polished;
+typedef struct {
+    uint64_t columns, voters, votes, voted_columns, changed, ambiguous, max_cover;
+    double   ms_sort, ms_vote;       /* device time (HIP events): keys + sort, the votes + the change list                            */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_polish_info;
+void alga_polish_default_params(alga_polish_params *p);
+int  alga_polish_placed_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polish_params *p,
+                               void *hip_stream, alga_polished *out, alga_polish_info *info /* may be NULL */);
+int  alga_write_polished_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin,
+                                      const alga_placements *pl, const alga_polished *pol, int32_t depth_header, const char *path,
+                                      alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
