@@ -190,6 +190,17 @@ struct alga_engine {
     bool        po_valid = false;                  // the result buffers hold a polish
     uint64_t    po_targets = 0, po_columns = 0;    // ... of this many targets and columns
     uint64_t    po_final_epoch = 0;                // ... of a placement on the final result of this epoch (0: on caller's targets)
+    uint64_t    pl_serial = 0, po_pl_serial = 0;   // counts the placement results written; the one the polish at hand was made from
+    // scaffolds from split pairs (engine_scaffold.hip).  Workspaces: counters, the link keys / judging reads before and after the sort, the spans,
+    // the heads and their scan, the first link of every bundle, best / second / choice / partner / join bundle per end, the two sets of list
+    // records, head / first / members per contig and their scans.  The result: the bundle arrays, the end states, the per-contig and
+    // per-scaffold arrays
+    DevBuf      sc_cnt, sc_keys[2], sc_vals[2], sc_span, sc_heads, sc_pos, sc_bstart, sc_best, sc_choice, sc_partner, sc_lists[2], sc_head, sc_first, sc_scan;
+    DevBuf      sc_ba, sc_bb, sc_blinks, sc_bspan, sc_bgap, sc_bstate, sc_estate, sc_scaffold, sc_rank, sc_orient, sc_start, sc_gapafter, sc_jlinks, sc_soff,
+                sc_smembers, sc_slen;
+    bool        sc_valid = false;                  // the result buffers hold scaffolds
+    uint64_t    sc_targets = 0, sc_scaffolds = 0, sc_longest = 0;   // ... of this many targets, this many of them, the longest with its gaps
+    uint64_t    sc_pl_serial = 0;                  // ... made from this placement result
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

@@ -73,7 +73,7 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     if (columns > 0xFFFFFFFEull) return alga_fail(e, ALGA_ERR_CAPACITY, "placement: the targets hold more than 2^32 - 2 bases");
 
     // from here on the result is rewritten
-    e->pl_valid = false;
+    e->pl_valid = false; e->pl_serial++;
     const size_t col_words = (size_t) ((columns + 15) >> 4) + 2, n_hist = (size_t) p->max_insert + 1;
     const int blocks = pl_place_blocks(R, e->n_cu);
     const size_t ub_words = pl_place_scratch_words(blocks, max_read_len, p->k);

@@ -111,7 +111,7 @@ int polish_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
     HIP_TRY(e, hipStreamSynchronize(s));
 
-    e->po_valid = true; e->po_targets = T; e->po_columns = columns; e->po_final_epoch = e->pl_final_epoch;
+    e->po_valid = true; e->po_targets = T; e->po_columns = columns; e->po_final_epoch = e->pl_final_epoch; e->po_pl_serial = e->pl_serial;
     out->n_targets = (int64_t) T; out->n_columns = columns; out->n_changed = n_changed;
     out->d_col_off = col_off; out->d_words = words; out->d_changed_cols = (const uint32_t *) e->po_ccols.p; out->d_changed_bases = (const uint8_t *) e->po_cbases.p;
     out->d_t_changed = (const uint64_t *) tstat; out->d_t_ambiguous = (const uint64_t *) (tstat + T);

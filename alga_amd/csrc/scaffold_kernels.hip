@@ -1,0 +1,498 @@
+// alga_amd/csrc/scaffold_kernels.hip -- scaffolds from the pairs the placement split over two targets (include/alga_amd.h:
+// alga_scaffold_placed_device; the definition is the comment there, host side in engine_scaffold.hip).
+//
+// Integer work only, wave-64, nothing depends on thread order or on the sort's order among equal keys: counts and sums are integer adds, the
+// best and second-best bundle of an end are 64-bit atomicMax on links << 32 | ~partner (distinct per end: the partners differ).
+//   k_sc_check        pair_off as the placement checks it, every UNIQUE read as the polish checks a voter -> the refusal flags
+//   k_sc_links        one thread per read: the judge of a split pair writes (a << 32 | b, span), every other read a sentinel above every key
+//   k_sc_heads        first link of every key among the sorted links; their count
+//   k_sc_bundle_fill  the first link of every bundle at the place the scan of the heads gives, the spans added (one atomic per wave where
+//                     the wave's links are of one bundle: a bundle over several blocks is a few adds)
+//   k_sc_bundles      a, b, links, gap, SUPPORTED; best[end]       k_sc_second   second[end]
+//   k_sc_choice       AMBIGUOUS and choice per end                 k_sc_joins    JOIN where both ends chose each other; partner[end]
+//   k_sc_cycle_init / _jump / _drop   pointer jumping over the 2T states with the smallest contig id carried along: a state that still has a
+//                     successor after ceil(log2(2T)) + 1 doublings is on a cycle, and the contig that is its own minimum drops the join at 2c
+//   k_sc_rank_init / _jump            the same jumps over the paths that are left: states to the end, bases and gaps to the end, the last state
+//   k_sc_place        per contig the direction item 7 chooses (the list whose first contig has the smaller id), rank, orientation, start
+//   k_sc_layout       scaffold ids and the member lists from the scans over "is the first contig" and "members of the scaffold it starts"
+//   k_sc_fasta_sizes / k_sc_fasta_write   one record per scaffold, one wave per record; a byte finds its contig by bisection over the starts
+// Block 256 and the grid caps are picked, not tuned.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "scaffold_kernels.h"
+#include "gfa_kernels.h"
+
+namespace alga {
+
+namespace {
+
+constexpr int SC_BLOCK = 256, SC_WAVES = SC_BLOCK / 64;
+constexpr uint8_t SC_ST_UNIQUE = 2, SC_ST_MINUS = 4;                    // ALGA_PLACE_UNIQUE, ALGA_PLACE_MINUS
+
+__device__ __forceinline__ unsigned long long sc_wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
+        v += ((unsigned long long) hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long sc_wave_max(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
+        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
+        v = w > v ? w : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t sc_wave_or(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t) __shfl_xor((int) v, o);
+    return v;
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_check(ScReads r, ScTargets t, unsigned long long *__restrict__ counters) {
+    uint32_t bad = 0;
+    const uint64_t n = 2 * r.R, step = (uint64_t) gridDim.x * SC_BLOCK;
+    if (r.pair_off)
+        for (uint64_t v = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; v < n; v += step) {
+            const uint8_t po = r.pair_off[v];
+            if (po > 2 || po != r.pair_off[v ^ 1]) bad |= SC_BAD_PAIR;
+            else if (po == 1 && (v + 2 >= n || r.pair_off[v + 2] != 2)) bad |= SC_BAD_PAIR;
+            else if (po == 2 && (v < 2 || r.pair_off[v - 2] != 1)) bad |= SC_BAD_PAIR;
+        }
+    for (uint64_t i = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; i < r.R; i += step) {
+        if (!(r.state[i] & SC_ST_UNIQUE)) continue;
+        const int32_t L = r.len[2 * i + 1];
+        if (L < 1 || (int64_t) L > 16ll * r.stride) { bad |= SC_BAD_LEN; continue; }
+        const int32_t tt = r.target[i], p = r.pos[i];
+        if (tt < 0 || (uint32_t) tt >= t.T || p < 0 || (int64_t) p + L > (int64_t) t.col_off[tt + 1] - (int64_t) t.col_off[tt]) bad |= SC_BAD_PLACE;
+    }
+    bad = sc_wave_or(bad);
+    if ((threadIdx.x & 63) == 0 && bad) atomicOr(&counters[SC_BAD], (unsigned long long) bad);
+}
+
+// (after the check: every UNIQUE read lies inside its target, a judge's mate is read r + 1 < R)
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_links(ScReads r, ScTargets t, int32_t max_insert, unsigned long long sentinel, unsigned long long *__restrict__ keys,
+                                                       uint32_t *__restrict__ vals, uint32_t *__restrict__ span, unsigned long long *__restrict__ counters) {
+    unsigned long long n_split = 0, n_links = 0, n_far = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; i < r.R; i += (uint64_t) gridDim.x * SC_BLOCK) {
+        unsigned long long key = sentinel;
+        uint32_t sp = 0;
+        if (r.pair_off[2 * i + 1] == 1) {
+            const uint64_t j = i + 1;
+            const uint8_t s1 = r.state[i], s2 = r.state[j];
+            const int32_t t1 = r.target[i], t2 = r.target[j];
+            if ((s1 & SC_ST_UNIQUE) && (s2 & SC_ST_UNIQUE) && t1 != t2) {
+                n_split++;
+                const long long l1 = (long long) t.col_off[t1 + 1] - (long long) t.col_off[t1], l2 = (long long) t.col_off[t2 + 1] - (long long) t.col_off[t2];
+                const long long d1 = (s1 & SC_ST_MINUS) ? (long long) r.pos[i] + r.len[2 * i + 1] : l1 - r.pos[i];
+                const long long d2 = (s2 & SC_ST_MINUS) ? (long long) r.pos[j] + r.len[2 * j + 1] : l2 - r.pos[j];
+                if (d1 + d2 <= (long long) max_insert) {
+                    const uint32_t x1 = 2u * (uint32_t) t1 + ((s1 & SC_ST_MINUS) ? 0u : 1u), x2 = 2u * (uint32_t) t2 + ((s2 & SC_ST_MINUS) ? 0u : 1u);
+                    const uint32_t a = x1 < x2 ? x1 : x2, b = x1 < x2 ? x2 : x1;
+                    key = ((unsigned long long) a << 32) | b;
+                    sp = (uint32_t) (d1 + d2);
+                    n_links++;
+                } else n_far++;
+            }
+        }
+        keys[i] = key; vals[i] = (uint32_t) i; span[i] = sp;
+    }
+    n_split = sc_wave_sum(n_split); n_links = sc_wave_sum(n_links); n_far = sc_wave_sum(n_far);
+    if ((threadIdx.x & 63) == 0 && n_split) {
+        atomicAdd(&counters[SC_SPLIT], n_split);
+        if (n_links) atomicAdd(&counters[SC_LINKS], n_links);
+        if (n_far) atomicAdd(&counters[SC_TOO_FAR], n_far);
+    }
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_heads(const unsigned long long *__restrict__ keys, uint64_t n_links, uint32_t *__restrict__ heads,
+                                                       unsigned long long *__restrict__ counters) {
+    unsigned long long n = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; i < n_links; i += (uint64_t) gridDim.x * SC_BLOCK) {
+        const uint32_t h = i == 0 || keys[i] != keys[i - 1];
+        heads[i] = h; n += h;
+    }
+    n = sc_wave_sum(n);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[SC_BUNDLES], n);
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_bundle_fill(const uint32_t *__restrict__ vals, const uint32_t *__restrict__ span, const uint32_t *__restrict__ heads,
+                                                             const uint32_t *__restrict__ pos, uint64_t n_links, uint64_t n_bundles, uint32_t *__restrict__ b_start,
+                                                             unsigned long long *__restrict__ b_span) {
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x == 0) b_start[n_bundles] = (uint32_t) n_links;
+    // whole waves stride: lane l of a pass holds link base + l
+    for (uint64_t base = (uint64_t) blockIdx.x * SC_BLOCK + (threadIdx.x & ~63); base < n_links; base += (uint64_t) gridDim.x * SC_BLOCK) {
+        const uint64_t i = base + (uint64_t) lane;
+        const bool active = i < n_links;
+        uint32_t bid = 0;
+        unsigned long long sp = 0;
+        if (active) {
+            const uint32_t h = heads[i];
+            bid = pos[i] + h - 1u;
+            if (h) b_start[bid] = (uint32_t) i;
+            sp = span[vals[i]];
+        }
+        const uint32_t bid0 = (uint32_t) __shfl((int) bid, 0);            // lane 0 is active wherever a lane of the pass is
+        if (__all(!active || bid == bid0)) {
+            sp = sc_wave_sum(sp);
+            if (lane == 0) atomicAdd(&b_span[bid0], sp);
+        } else if (active) atomicAdd(&b_span[bid], sp);
+    }
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_bundles(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ b_start, ScBundles b, ScParams p,
+                                                         unsigned long long *__restrict__ best, unsigned long long *__restrict__ counters) {
+    unsigned long long n_sup = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; i < b.n; i += (uint64_t) gridDim.x * SC_BLOCK) {
+        const uint32_t i0 = b_start[i], n = b_start[i + 1] - i0;
+        const unsigned long long key = keys[i0];
+        const uint32_t ea = (uint32_t) (key >> 32), eb = (uint32_t) key;
+        const bool sup = (unsigned long long) n >= (unsigned long long) p.min_links;
+        b.a[i] = ea; b.b[i] = eb; b.links[i] = n;
+        b.gap[i] = (int32_t) ((long long) p.insert - (long long) (b.span[i] / (unsigned long long) n));
+        b.state[i] = sup ? SC_B_SUPPORTED : (uint8_t) 0;
+        if (sup) {
+            n_sup++;
+            atomicMax(&best[ea], ((unsigned long long) n << 32) | (uint32_t) ~eb);
+            atomicMax(&best[eb], ((unsigned long long) n << 32) | (uint32_t) ~ea);
+        }
+    }
+    n_sup = sc_wave_sum(n_sup);
+    if ((threadIdx.x & 63) == 0 && n_sup) atomicAdd(&counters[SC_SUPPORTED], n_sup);
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_second(ScBundles b, const unsigned long long *__restrict__ best, unsigned long long *__restrict__ second) {
+    for (uint64_t i = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; i < b.n; i += (uint64_t) gridDim.x * SC_BLOCK) {
+        if (!(b.state[i] & SC_B_SUPPORTED)) continue;
+        const uint32_t ea = b.a[i], eb = b.b[i];
+        const unsigned long long n = b.links[i], pa = (n << 32) | (uint32_t) ~eb, pb = (n << 32) | (uint32_t) ~ea;
+        if (pa != best[ea]) atomicMax(&second[ea], pa);
+        if (pb != best[eb]) atomicMax(&second[eb], pb);
+    }
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_choice(const unsigned long long *__restrict__ best, const unsigned long long *__restrict__ second, uint64_t n_ends,
+                                                        int32_t max_second_percent, uint32_t *__restrict__ choice, uint8_t *__restrict__ end_state,
+                                                        unsigned long long *__restrict__ counters) {
+    unsigned long long n_amb = 0;
+    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_ends; x += (uint64_t) gridDim.x * SC_BLOCK) {
+        const unsigned long long b1 = best[x], b2 = second[x];
+        uint8_t st = 0;
+        uint32_t ch = SC_NONE;
+        if (b1) {
+            st = SC_E_SUPPORTED;
+            const bool amb = b2 && 100ull * (b2 >> 32) >= (unsigned long long) max_second_percent * (b1 >> 32);
+            if (amb) { st |= SC_E_AMBIGUOUS; n_amb++; }
+            else ch = ~(uint32_t) b1;
+        }
+        choice[x] = ch; end_state[x] = st;
+    }
+    n_amb = sc_wave_sum(n_amb);
+    if ((threadIdx.x & 63) == 0 && n_amb) atomicAdd(&counters[SC_AMBIGUOUS], n_amb);
+}
+
+// (an end is joined by at most one bundle: its choice is one end, and only the bundle of that key can name it)
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_joins(ScBundles b, const uint32_t *__restrict__ choice, uint32_t *__restrict__ partner, uint32_t *__restrict__ join_bundle) {
+    for (uint64_t i = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; i < b.n; i += (uint64_t) gridDim.x * SC_BLOCK) {
+        if (!(b.state[i] & SC_B_SUPPORTED)) continue;
+        const uint32_t ea = b.a[i], eb = b.b[i];
+        if (choice[ea] != eb || choice[eb] != ea) continue;
+        b.state[i] = SC_B_SUPPORTED | SC_B_JOIN;
+        partner[ea] = eb; partner[eb] = ea;
+        join_bundle[ea] = (uint32_t) i; join_bundle[eb] = (uint32_t) i;
+    }
+}
+
+// state x = 2c + e: contig c entered at end e, left at e ^ 1 through that end's join into the partner end's contig
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_init(const uint32_t *__restrict__ partner, uint64_t n_states, ScLists l) {
+    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_states; x += (uint64_t) gridDim.x * SC_BLOCK) {
+        l.nxt[x] = partner[x ^ 1]; l.aux[x] = (uint32_t) (x >> 1);
+    }
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_jump(uint64_t n_states, ScLists from, ScLists to) {
+    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_states; x += (uint64_t) gridDim.x * SC_BLOCK) {
+        const uint32_t y = from.nxt[x];
+        uint32_t m = from.aux[x], z = SC_NONE;
+        if (y != SC_NONE) { const uint32_t my = from.aux[y]; m = my < m ? my : m; z = from.nxt[y]; }
+        to.nxt[x] = z; to.aux[x] = m;
+    }
+}
+
+// one thread per contig; only the smallest contig of a cycle writes, and only the two ends of the join at its left end
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_drop(ScLists l, uint32_t T, uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
+                                                            uint8_t *__restrict__ b_state, unsigned long long *__restrict__ counters) {
+    unsigned long long n = 0;
+    for (uint64_t c = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; c < T; c += (uint64_t) gridDim.x * SC_BLOCK) {
+        if (l.nxt[2 * c] == SC_NONE || l.aux[2 * c] != (uint32_t) c) continue;
+        const uint32_t y = partner[2 * c];
+        partner[2 * c] = SC_NONE; partner[y] = SC_NONE;
+        b_state[join_bundle[2 * c]] = SC_B_SUPPORTED | SC_B_JOIN | SC_B_DROPPED;
+        n++;
+    }
+    n = sc_wave_sum(n);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[SC_DROPPED], n);
+}
+
+__device__ __forceinline__ uint32_t sc_gap_behind(const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle, const int32_t *__restrict__ b_gap,
+                                                  int32_t min_gap, uint32_t end) {
+    if (partner[end] == SC_NONE) return 0u;
+    const int32_t g = b_gap[join_bundle[end]];
+    return (uint32_t) (g > min_gap ? g : min_gap);
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_rank_init(ScTargets t, const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
+                                                           const int32_t *__restrict__ b_gap, int32_t min_gap, ScLists l) {
+    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < 2ull * t.T; x += (uint64_t) gridDim.x * SC_BLOCK) {
+        const uint32_t c = (uint32_t) (x >> 1);
+        l.nxt[x] = partner[x ^ 1]; l.aux[x] = 1u; l.tail[x] = (uint32_t) x;
+        l.wsum[x] = (unsigned long long) (t.col_off[c + 1] - t.col_off[c]) + sc_gap_behind(partner, join_bundle, b_gap, min_gap, (uint32_t) (x ^ 1));
+    }
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_rank_jump(uint64_t n_states, ScLists from, ScLists to) {
+    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_states; x += (uint64_t) gridDim.x * SC_BLOCK) {
+        const uint32_t y = from.nxt[x];
+        uint32_t d = from.aux[x], tl = from.tail[x], z = SC_NONE;
+        unsigned long long w = from.wsum[x];
+        if (y != SC_NONE) { d += from.aux[y]; w += from.wsum[y]; tl = from.tail[y]; z = from.nxt[y]; }
+        to.nxt[x] = z; to.aux[x] = d; to.tail[x] = tl; to.wsum[x] = w;
+    }
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_place(ScTargets t, ScLists l, const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
+                                                       const int32_t *__restrict__ b_gap, const uint32_t *__restrict__ b_links, int32_t min_gap, ScLayout o,
+                                                       uint32_t *__restrict__ head, uint32_t *__restrict__ first, uint32_t *__restrict__ members,
+                                                       unsigned long long *__restrict__ counters) {
+    unsigned long long n_joins = 0;
+    for (uint64_t c = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; c <= t.T; c += (uint64_t) gridDim.x * SC_BLOCK) {
+        if (c == t.T) { first[c] = 0; members[c] = 0; continue; }               // the place of the scans' totals
+        const uint32_t len = t.col_off[c + 1] - t.col_off[c];
+        o.end_state[2 * c] |= partner[2 * c] != SC_NONE ? SC_E_JOINED : (uint8_t) 0;
+        o.end_state[2 * c + 1] |= partner[2 * c + 1] != SC_NONE ? SC_E_JOINED : (uint8_t) 0;
+        if (len == 0) {                                                        // in no scaffold (nothing is placed on it: it has no join)
+            o.scaffold[c] = -1; o.rank[c] = -1; o.orient[c] = 0; o.start[c] = 0; o.gap_after[c] = 0; o.join_links[c] = 0;
+            head[c] = (uint32_t) c; first[c] = 0; members[c] = 0;
+            continue;
+        }
+        // the list of state 2c + e begins at the contig the other direction ends at
+        const uint32_t f0 = l.tail[2 * c + 1] >> 1, l0 = l.tail[2 * c] >> 1;   // first and last contig of the direction that enters c at end 0
+        const uint32_t e = (f0 < l0 || f0 == l0) ? 0u : 1u;                    // (f0 == l0: a path of one contig, orientation +)
+        const uint32_t x = 2 * (uint32_t) c + e;
+        const uint32_t m = l.aux[x] + l.aux[x ^ 1] - 1u, rank = m - l.aux[x];
+        const uint32_t hx = l.tail[x ^ 1] ^ 1u;                                // the state of the first contig in this direction
+        const uint32_t out = x ^ 1u;                                           // c is left at this end
+        const bool joined = partner[out] != SC_NONE;
+        o.rank[c] = (int32_t) rank; o.orient[c] = (uint8_t) e;
+        o.start[c] = l.wsum[hx] - l.wsum[x];
+        o.gap_after[c] = (int32_t) sc_gap_behind(partner, join_bundle, b_gap, min_gap, out);
+        o.join_links[c] = joined ? b_links[join_bundle[out]] : 0u;
+        n_joins += joined;
+        head[c] = hx >> 1; first[c] = rank == 0; members[c] = rank == 0 ? m : 0u;
+    }
+    n_joins = sc_wave_sum(n_joins);
+    if ((threadIdx.x & 63) == 0 && n_joins) atomicAdd(&counters[SC_JOINS], n_joins);
+}
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_layout(ScTargets t, ScLists l, const uint32_t *__restrict__ head, const uint32_t *__restrict__ first_scan,
+                                                        const uint32_t *__restrict__ members_scan, ScLayout o, unsigned long long *__restrict__ counters) {
+    unsigned long long n_sc = 0, n_multi = 0, n_mem = 0, longest = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) o.s_off[first_scan[t.T]] = members_scan[t.T];
+    for (uint64_t c = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; c < t.T; c += (uint64_t) gridDim.x * SC_BLOCK) {
+        const int32_t rank = o.rank[c];
+        if (rank < 0) continue;
+        const uint32_t h = head[c], sid = first_scan[h], at = members_scan[h];
+        o.scaffold[c] = (int32_t) sid;
+        o.s_members[at + (uint32_t) rank] = (int32_t) c;
+        if (rank == 0) {
+            const uint32_t x = 2 * (uint32_t) c + o.orient[c];
+            const unsigned long long bases = l.wsum[x];
+            o.s_off[sid] = at; o.s_len[sid] = bases;
+            n_sc++; n_multi += l.aux[x] > 1u; n_mem += l.aux[x];
+            longest = bases > longest ? bases : longest;
+        }
+    }
+    n_sc = sc_wave_sum(n_sc); n_multi = sc_wave_sum(n_multi); n_mem = sc_wave_sum(n_mem); longest = sc_wave_max(longest);
+    if ((threadIdx.x & 63) == 0 && n_sc) {
+        atomicAdd(&counters[SC_SCAFFOLDS], n_sc); atomicAdd(&counters[SC_MEMBERS], n_mem); atomicMax(&counters[SC_LONGEST], longest);
+        if (n_multi) atomicAdd(&counters[SC_MULTI], n_multi);
+    }
+}
+
+// ---- FASTA of the scaffolds ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int sc_dec_width(unsigned long long v) {
+    int w = 1;
+    while (v >= 10ull) { v /= 10ull; w++; }
+    return w;
+}
+
+// `>scaffold_id=<j>_length=<s_len>_contigs=<m>\n<sequence>\n`
+struct ScRecord {
+    unsigned long long id, L, m;
+    int w_id, w_len, w_m;
+    uint32_t hp;                      // bytes before the sequence
+    const int32_t *mem;               // the scaffold's contigs
+    const unsigned long long *start;
+    const uint32_t *col_off, *words;
+    const uint8_t *orient;
+    __device__ void set(const ScFasta &ff, uint64_t j) {
+        start = ff.start; col_off = ff.col_off; words = ff.words; orient = ff.orient; id = j; L = ff.s_len[j]; m = ff.s_off[j + 1] - ff.s_off[j]; mem = ff.s_members + ff.s_off[j];
+        w_id = sc_dec_width(id); w_len = sc_dec_width(L); w_m = sc_dec_width(m);
+        hp = 13u + w_id + 8u + w_len + 9u + w_m + 1u;
+    }
+    __device__ static char digit(unsigned long long v, int w, int d) {
+        for (int i = w - 1 - d; i > 0; i--) v /= 10ull;
+        return (char) ('0' + (int) (v % 10ull));
+    }
+    __device__ char at(uint64_t p) const {
+        if (p >= hp) {
+            const unsigned long long q = p - hp;
+            if (q >= L) return '\n';
+            uint32_t lo = 0, hi = (uint32_t) m;                                 // the last member that starts at or before q
+            while (hi - lo > 1) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (start[mem[mid]] <= q) lo = mid; else hi = mid;
+            }
+            const uint32_t c = (uint32_t) mem[lo], c0 = col_off[c], len = col_off[c + 1] - c0;
+            const unsigned long long k = q - start[c];
+            if (k >= len) return 'N';
+            const bool minus = orient[c] != 0;
+            const uint32_t g = minus ? c0 + len - 1u - (uint32_t) k : c0 + (uint32_t) k;
+            const uint32_t code = (words[g >> 4] >> (2 * (g & 15))) & 3u;
+            return (char) ((0x54474341u >> (8 * (minus ? 3u - code : code))) & 0xFF);
+        }
+        if (p < 13u) return ">scaffold_id="[p];
+        uint32_t at0 = 13u;
+        if (p < at0 + w_id) return digit(id, w_id, (int) (p - at0));
+        at0 += w_id;
+        if (p < at0 + 8u) return "_length="[p - at0];
+        at0 += 8u;
+        if (p < at0 + w_len) return digit(L, w_len, (int) (p - at0));
+        at0 += w_len;
+        if (p < at0 + 9u) return "_contigs="[p - at0];
+        at0 += 9u;
+        if (p < at0 + w_m) return digit(m, w_m, (int) (p - at0));
+        return '\n';
+    }
+};
+
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_fasta_sizes(ScFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    const uint64_t j = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x;
+    unsigned long long live = 0, bytes = 0;
+    if (j < f.n) {
+        ScRecord s;
+        s.set(f, j);
+        bytes = (unsigned long long) s.hp + s.L + 1ull;
+        live = 1;
+        sizes[j] = (uint32_t) bytes;
+    }
+    live = sc_wave_sum(live);
+    bytes = sc_wave_max(bytes);
+    if ((threadIdx.x & 63) == 0 && live) {
+        atomicAdd(&counters[GFA_SEGMENTS], live);
+        atomicMax(&counters[GFA_MAX_LINE], bytes);
+    }
+}
+
+// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_fasta_write(ScFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1, char *__restrict__ buf) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t base = off[i0], waves = (uint64_t) gridDim.x * SC_WAVES;
+    for (uint64_t j = i0 + (uint64_t) blockIdx.x * SC_WAVES + (threadIdx.x >> 6); j < i1; j += waves) {
+        const uint64_t l0 = off[j], l1 = off[j + 1];
+        if (l0 == l1) continue;
+        ScRecord s;
+        s.set(f, j);
+        char *g0 = buf + (l0 - base);
+        for (uint64_t p = (uint64_t) lane; p < l1 - l0; p += 64) g0[p] = s.at(p);
+    }
+}
+
+inline unsigned sc_grid(uint64_t items, uint64_t cap = 8192) {
+    const uint64_t g = (items + SC_BLOCK - 1) / SC_BLOCK;
+    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
+}
+
+}  // namespace
+
+void launch_sc_check(const ScReads &r, const ScTargets &t, unsigned long long *counters, hipStream_t s) {
+    if (r.R) hipLaunchKernelGGL(k_sc_check, dim3(sc_grid(2 * r.R, 4096)), dim3(SC_BLOCK), 0, s, r, t, counters);
+}
+
+void launch_sc_links(const ScReads &r, const ScTargets &t, int32_t max_insert, unsigned long long sentinel, unsigned long long *keys, uint32_t *vals, uint32_t *span,
+                     unsigned long long *counters, hipStream_t s) {
+    if (r.R && r.pair_off) hipLaunchKernelGGL(k_sc_links, dim3(sc_grid(r.R)), dim3(SC_BLOCK), 0, s, r, t, max_insert, sentinel, keys, vals, span, counters);
+}
+
+void launch_sc_heads(const unsigned long long *keys, uint64_t n_links, uint32_t *heads, unsigned long long *counters, hipStream_t s) {
+    if (n_links) hipLaunchKernelGGL(k_sc_heads, dim3(sc_grid(n_links)), dim3(SC_BLOCK), 0, s, keys, n_links, heads, counters);
+}
+
+void launch_sc_bundle_fill(const uint32_t *vals, const uint32_t *span, const uint32_t *heads, const uint32_t *pos, uint64_t n_links, uint64_t n_bundles, uint32_t *b_start,
+                           unsigned long long *b_span, hipStream_t s) {
+    if (n_links) hipLaunchKernelGGL(k_sc_bundle_fill, dim3(sc_grid(n_links)), dim3(SC_BLOCK), 0, s, vals, span, heads, pos, n_links, n_bundles, b_start, b_span);
+}
+
+void launch_sc_bundles(const unsigned long long *keys, const uint32_t *b_start, const ScBundles &b, const ScParams &p, unsigned long long *best, unsigned long long *counters,
+                       hipStream_t s) {
+    if (b.n) hipLaunchKernelGGL(k_sc_bundles, dim3(sc_grid(b.n)), dim3(SC_BLOCK), 0, s, keys, b_start, b, p, best, counters);
+}
+
+void launch_sc_second(const ScBundles &b, const unsigned long long *best, unsigned long long *second, hipStream_t s) {
+    if (b.n) hipLaunchKernelGGL(k_sc_second, dim3(sc_grid(b.n)), dim3(SC_BLOCK), 0, s, b, best, second);
+}
+
+void launch_sc_choice(const unsigned long long *best, const unsigned long long *second, uint64_t n_ends, int32_t max_second_percent, uint32_t *choice, uint8_t *end_state,
+                      unsigned long long *counters, hipStream_t s) {
+    if (n_ends) hipLaunchKernelGGL(k_sc_choice, dim3(sc_grid(n_ends)), dim3(SC_BLOCK), 0, s, best, second, n_ends, max_second_percent, choice, end_state, counters);
+}
+
+void launch_sc_joins(const ScBundles &b, const uint32_t *choice, uint32_t *partner, uint32_t *join_bundle, hipStream_t s) {
+    if (b.n) hipLaunchKernelGGL(k_sc_joins, dim3(sc_grid(b.n)), dim3(SC_BLOCK), 0, s, b, choice, partner, join_bundle);
+}
+
+void launch_sc_cycle_init(const uint32_t *partner, uint64_t n_states, const ScLists &l, hipStream_t s) {
+    if (n_states) hipLaunchKernelGGL(k_sc_cycle_init, dim3(sc_grid(n_states)), dim3(SC_BLOCK), 0, s, partner, n_states, l);
+}
+
+void launch_sc_cycle_jump(uint64_t n_states, const ScLists &from, const ScLists &to, hipStream_t s) {
+    if (n_states) hipLaunchKernelGGL(k_sc_cycle_jump, dim3(sc_grid(n_states)), dim3(SC_BLOCK), 0, s, n_states, from, to);
+}
+
+void launch_sc_cycle_drop(const ScLists &l, uint32_t T, uint32_t *partner, const uint32_t *join_bundle, uint8_t *b_state, unsigned long long *counters, hipStream_t s) {
+    if (T) hipLaunchKernelGGL(k_sc_cycle_drop, dim3(sc_grid(T)), dim3(SC_BLOCK), 0, s, l, T, partner, join_bundle, b_state, counters);
+}
+
+void launch_sc_rank_init(const ScTargets &t, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, int32_t min_gap, const ScLists &l, hipStream_t s) {
+    if (t.T) hipLaunchKernelGGL(k_sc_rank_init, dim3(sc_grid(2ull * t.T)), dim3(SC_BLOCK), 0, s, t, partner, join_bundle, b_gap, min_gap, l);
+}
+
+void launch_sc_rank_jump(uint64_t n_states, const ScLists &from, const ScLists &to, hipStream_t s) {
+    if (n_states) hipLaunchKernelGGL(k_sc_rank_jump, dim3(sc_grid(n_states)), dim3(SC_BLOCK), 0, s, n_states, from, to);
+}
+
+void launch_sc_place(const ScTargets &t, const ScLists &l, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, const uint32_t *b_links, int32_t min_gap,
+                     const ScLayout &o, uint32_t *head, uint32_t *first, uint32_t *members, unsigned long long *counters, hipStream_t s) {
+    hipLaunchKernelGGL(k_sc_place, dim3(sc_grid((uint64_t) t.T + 1)), dim3(SC_BLOCK), 0, s, t, l, partner, join_bundle, b_gap, b_links, min_gap, o, head, first, members, counters);
+}
+
+void launch_sc_layout(const ScTargets &t, const ScLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const ScLayout &o,
+                      unsigned long long *counters, hipStream_t s) {
+    hipLaunchKernelGGL(k_sc_layout, dim3(sc_grid((uint64_t) t.T + 1)), dim3(SC_BLOCK), 0, s, t, l, head, first_scan, members_scan, o, counters);
+}
+
+void launch_sc_fasta_sizes(const ScFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
+    if (f.n) hipLaunchKernelGGL(k_sc_fasta_sizes, dim3((unsigned) ((f.n + SC_BLOCK - 1) / SC_BLOCK)), dim3(SC_BLOCK), 0, s, f, sizes, counters);
+}
+
+void launch_sc_fasta_write(const ScFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
+    if (i0 >= i1) return;
+    const uint64_t g = (i1 - i0 + SC_WAVES - 1) / SC_WAVES;
+    hipLaunchKernelGGL(k_sc_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(SC_BLOCK), 0, s, f, off, i0, i1, buf);
+}
+
+}  // namespace alga

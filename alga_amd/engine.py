@@ -179,7 +179,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_extend_contigs_device", "alga_extend_seams_get",
            "alga_correct_default_params", "alga_correct_reads_device", "alga_correct_parsed_reads", "alga_ingest_corrected_device",
            "alga_place_default_params", "alga_place_reads_device", "alga_place_reads_on_final_device", "alga_write_final_fasta_depth_device",
-           "alga_polish_default_params", "alga_polish_placed_device", "alga_write_polished_fasta_device"]
+           "alga_polish_default_params", "alga_polish_placed_device", "alga_write_polished_fasta_device",
+           "alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -496,6 +497,81 @@ class Polished:
         return self.words, off[:-1].contiguous(), (off[1:] - off[:-1]).to(torch.int32).contiguous()
 
 
+SCAFFOLD_BUNDLE_SUPPORTED, SCAFFOLD_BUNDLE_JOIN, SCAFFOLD_BUNDLE_DROPPED_CYCLE = 1, 2, 4     # bits of Scaffolds.b_state
+SCAFFOLD_END_HAS_SUPPORTED, SCAFFOLD_END_AMBIGUOUS, SCAFFOLD_END_JOINED = 1, 2, 4         # bits of Scaffolds.end_state
+
+
+class ScaffoldParams(C.Structure):
+    """alga_scaffold_params"""
+    _fields_ = [(k, C.c_int32) for k in ("insert", "max_insert", "min_links", "max_second_percent", "min_gap", "flags")] + [("reserved", C.c_int32 * 2)]
+
+
+class ScaffoldInfo(C.Structure):
+    """alga_scaffold_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("pairs_split", "links", "links_too_far", "bundles", "bundles_supported", "ends_ambiguous", "joins", "joins_dropped_cycle",
+                                          "scaffolds", "scaffolds_multi", "longest", "n50_targets", "n50_scaffolds")] + \
+               [(k, C.c_double) for k in ("ms_links", "ms_chain", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ScaffoldsC(C.Structure):
+    """alga_scaffolds"""
+    _fields_ = [(k, C.c_int64) for k in ("n_targets", "n_bundles", "n_scaffolds", "n_members")] + \
+               [(k, C.c_void_p) for k in ("d_b_a", "d_b_b", "d_b_links", "d_b_span", "d_b_gap", "d_b_state", "d_end_state", "d_scaffold", "d_rank", "d_orient", "d_start",
+                                          "d_gap_after", "d_join_links", "d_s_off", "d_s_members", "d_s_len")]
+
+
+class Scaffolds:
+    """Result of Engine.scaffold: zero-copy torch views of the engine's device memory (valid until the next Engine.scaffold call on that engine;
+    clone what has to live longer) -- per bundle b_a / b_b / b_links int32 (the bits of uint32), b_span int64, b_gap int32, b_state uint8; end_state
+    uint8 [2 * n_targets]; per target scaffold / rank int32, orient uint8, start int64, gap_after int32, join_links int32; s_off int32
+    [n_scaffolds + 1], s_members int32 [n_members], s_len int64 [n_scaffolds] -- and .info (dict of alga_scaffold_info)."""
+    KEYS = (("b_a", "<i4", np.uint32, "b"), ("b_b", "<i4", np.uint32, "b"), ("b_links", "<i4", np.uint32, "b"), ("b_span", "<i8", np.uint64, "b"),
+            ("b_gap", "<i4", np.int32, "b"), ("b_state", "|u1", np.uint8, "b"), ("end_state", "|u1", np.uint8, "e"), ("scaffold", "<i4", np.int32, "t"),
+            ("rank", "<i4", np.int32, "t"), ("orient", "|u1", np.uint8, "t"), ("start", "<i8", np.uint64, "t"), ("gap_after", "<i4", np.int32, "t"),
+            ("join_links", "<i4", np.uint32, "t"), ("s_off", "<i4", np.uint32, "s1"), ("s_members", "<i4", np.int32, "m"), ("s_len", "<i8", np.uint64, "s"))
+
+    def __init__(self, c, info, device, placements=None):
+        self._c, self.info, self._placements = c, info, placements
+        self.n_targets, self.n_bundles, self.n_scaffolds, self.n_members = int(c.n_targets), int(c.n_bundles), int(c.n_scaffolds), int(c.n_members)
+        dev = "cuda:%d" % device
+        size = dict(b=self.n_bundles, e=2 * self.n_targets, t=self.n_targets, s1=self.n_scaffolds + 1, m=self.n_members, s=self.n_scaffolds)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/scaffold_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+    def layout_tsv(self, host=None):
+        """one line per member contig in (scaffold, rank) order: scaffold, rank, contig, orient (+/-), start, length, gap_after, links (tabs);
+        the text alga_hip --scaffold_layout= writes"""
+        return layout_tsv(host if host is not None else self.to_host())
+
+
+def layout_tsv(h, tlen=None):
+    """the layout of a scaffold result read back (Scaffolds.to_host()).  tlen: the targets' lengths; by default they are taken from the
+    result itself (a member ends where the next one starts less its gap, the last one at s_len), so the placement need not be at hand"""
+    lines = []
+    if tlen is None:
+        tlen = np.zeros(len(h["rank"]), dtype=np.int64)
+        for j in range(len(h["s_len"])):
+            mem = [int(c) for c in h["s_members"][int(h["s_off"][j]):int(h["s_off"][j + 1])]]
+            ends = [int(h["start"][c]) for c in mem[1:]] + [int(h["s_len"][j])]
+            for c, e in zip(mem, ends):
+                tlen[c] = e - int(h["start"][c]) - int(h["gap_after"][c])
+    for j in range(len(h["s_len"])):
+        for c in h["s_members"][int(h["s_off"][j]):int(h["s_off"][j + 1])]:
+            c = int(c)
+            lines.append("%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\n" % (j, int(h["rank"][c]), c, "-" if h["orient"][c] else "+", int(h["start"][c]), int(tlen[c]),
+                                                              int(h["gap_after"][c]), int(h["join_links"][c])))
+    return "".join(lines)
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -638,6 +714,11 @@ def load_library():
                                               C.POINTER(PolishInfo)]
     lib.alga_write_polished_fasta_device.argtypes = [C.c_void_p, C.POINTER(UnitigsC), C.POINTER(ConsensusC), C.POINTER(FinalContigsC), C.POINTER(PlacementsC),
                                                      C.POINTER(PolishedC), C.c_int32, C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_scaffold_default_params.argtypes = [C.POINTER(ScaffoldParams)]
+    lib.alga_scaffold_default_params.restype = None
+    lib.alga_scaffold_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.POINTER(PlacementsC), C.POINTER(ScaffoldParams), C.c_void_p,
+                                                C.POINTER(ScaffoldsC), C.POINTER(ScaffoldInfo)]
+    lib.alga_write_scaffold_fasta_device.argtypes = [C.c_void_p, C.POINTER(PlacementsC), C.POINTER(ScaffoldsC), C.POINTER(PolishedC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1569,6 +1650,48 @@ class Engine:
         torch.cuda.current_stream(dev).synchronize()
         self._check(self._lib.alga_polish_placed_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(pp), st, C.byref(out), C.byref(info)))
         return Polished(out, info.as_dict(), self.device, placements)
+
+    def scaffold(self, words, lens, pair_off, placements, insert=None, max_insert=1000, min_links=5, max_second_percent=50, min_gap=10, stream=None):
+        """Scaffolds from the pairs the placement split over two targets (alga_scaffold_placed_device) -> Scaffolds.  words / lens / pair_off:
+        the node set that was placed and its pairing (None: no pairs); placements: the result of the LAST Engine.place_reads call.  insert: the
+        library's insert size, by default the placement's insert_median (refused where that is -1: no proper pair was seen).  Two ends are joined
+        iff each is the other's only choice: at least min_links links within max_insert, and no second bundle with max_second_percent of them."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if insert is None:
+            insert = int(placements.info["insert_median"])
+            if insert < 0:
+                raise AlgaError(-1, "Engine.scaffold: the placement saw no proper pair (insert_median -1): give insert")
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if pair_off is not None:
+            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = ScaffoldParams(), ScaffoldsC(), ScaffoldInfo()
+        pp.insert, pp.max_insert, pp.min_links, pp.max_second_percent, pp.min_gap = int(insert), int(max_insert), int(min_links), int(max_second_percent), int(min_gap)
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_scaffold_placed_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(placements._c), C.byref(pp), st, C.byref(out),
+                                                          C.byref(info)))
+        return Scaffolds(out, info.as_dict(), self.device, placements)
+
+    def write_scaffold_fasta(self, path, placements, scaffolds, polished=None):
+        """The scaffolds of the LAST Engine.scaffold call as FASTA (alga_write_scaffold_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>scaffold_id=<j>_length=<len>_contigs=<m>` and the contigs with their gaps as runs of N on one line, in id order.  polished:
+        the result of the LAST Engine.polish of those placements -- the bases are then the polished ones."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_scaffold_fasta_device(self._h, C.byref(placements._c), C.byref(scaffolds._c),
+                                                               C.byref(polished._c) if polished is not None else None, os.fsencode(path), C.byref(info)))
+        return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)

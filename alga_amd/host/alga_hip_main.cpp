@@ -66,6 +66,13 @@
 // (alga_write_polished_fasta_device); its headers carry the depth iff --contigs_depth=1.  One line on stderr gives voters / voted columns /
 // changed / ambiguous.  --polish_changes=PATH (needs --polish=1): one line `contig pos old new A C G T` per changed column, tab separated, no
 // header line, the four counts of the column behind the bases.  Neither is passed through.
+// --scaffolds=PATH (needs --contigs_final= and --file2=; implies the placement): the final contigs joined through the pairs whose mates lie on two
+// of them (alga_scaffold_placed_device: insert = the placement's median, max_insert the placement's; --scaffold_min_links= (5), --scaffold_min_gap= (10),
+// --scaffold_max_second_percent= (50)), one record `>scaffold_id=<j>_length=<len>_contigs=<m>` per scaffold with the gaps as runs of N
+// (alga_write_scaffold_fasta_device); with --polish=1 the bases are the polished ones.  --scaffold_layout=PATH (needs --scaffolds=): one line
+// `scaffold rank contig orient(+/-) start length gap_after links` per member contig, tab separated.  One line on stderr gives links / bundles
+// supported / joins / scaffolds / N50 of the contigs -> N50 of the scaffolds.  Without a proper pair (no median) the scaffolding is skipped with a
+// message and every contig is its own scaffold in the FASTA.  None is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -89,7 +96,8 @@ static const char *USAGE =
     "         [--consensus_min_votes=3] [--contigs=contigs.fasta] [--contigs_gfa=contigs.gfa] [--contigs_min_length=N] [--contigs_final=final.fasta]\n"
     "         [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]\n"
     "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n"
-    "         [--contigs_depth=0|1] [--placements=placements.tsv] [--polish=0|1] [--polish_changes=changes.tsv]\n";
+    "         [--contigs_depth=0|1] [--placements=placements.tsv] [--polish=0|1] [--polish_changes=changes.tsv]\n"
+    "         [--scaffolds=scaffolds.fasta] [--scaffold_layout=layout.tsv] [--scaffold_min_links=5] [--scaffold_min_gap=10] [--scaffold_max_second_percent=50]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -106,6 +114,9 @@ int main(int argc, char **argv) {
     int correct_reads = 0;
     std::string corrected_reads, placements, polish_changes;
     int contigs_depth = 0, polish = 0;
+    std::string scaffolds, scaffold_layout;
+    alga_scaffold_params scp;
+    alga_scaffold_default_params(&scp);
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -141,6 +152,11 @@ int main(int argc, char **argv) {
         else if (opt(a, "--placements", v)) placements = v;
         else if (opt(a, "--polish", v)) polish = atoi(v.c_str());
         else if (opt(a, "--polish_changes", v)) polish_changes = v;
+        else if (opt(a, "--scaffolds", v)) scaffolds = v;
+        else if (opt(a, "--scaffold_layout", v)) scaffold_layout = v;
+        else if (opt(a, "--scaffold_min_links", v)) scp.min_links = atoi(v.c_str());
+        else if (opt(a, "--scaffold_min_gap", v)) scp.min_gap = atoi(v.c_str());
+        else if (opt(a, "--scaffold_max_second_percent", v)) scp.max_second_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -158,7 +174,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -168,6 +184,12 @@ int main(int argc, char **argv) {
     if ((contigs_depth || !placements.empty()) && contigs_final.empty()) { fprintf(stderr, "alga_hip: --contigs_depth=1 and --placements= need --contigs_final=\n"); return 2; }
     if (polish && contigs_final.empty()) { fprintf(stderr, "alga_hip: --polish=1 needs --contigs_final=\n"); return 2; }
     if (!polish && !polish_changes.empty()) { fprintf(stderr, "alga_hip: --polish_changes= needs --polish=1\n"); return 2; }
+    if (!scaffolds.empty() && (contigs_final.empty() || file2.empty())) { fprintf(stderr, "alga_hip: --scaffolds= needs --contigs_final= and --file2=\n"); return 2; }
+    if (scaffolds.empty() && !scaffold_layout.empty()) { fprintf(stderr, "alga_hip: --scaffold_layout= needs --scaffolds=\n"); return 2; }
+    if (scp.min_links < 1 || scp.min_gap < 1 || scp.min_gap > (1 << 20) || scp.max_second_percent < 1 || scp.max_second_percent > 100) {
+        fprintf(stderr, "alga_hip: --scaffold_min_links must be >= 1, --scaffold_min_gap in [1, 2^20], --scaffold_max_second_percent in [1, 100]\n");
+        return 2;
+    }
     if (correct_reads && !alga_exe.empty()) {
         fprintf(stderr, "alga_hip: --correct_reads=1 cannot be combined with --alga=: stock ALGA would read the original files, whose nodes are not the corrected graph's\n");
         return 2;
@@ -459,7 +481,7 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
-                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish)) {
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty())) {
                     // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
                     alga_parsed_reads pr{};
                     char perr[512] = {0};
@@ -538,6 +560,49 @@ int main(int argc, char **argv) {
                     if (rc == ALGA_OK) rc = polish ? alga_write_polished_fasta_device(engine, &cu, &cs, &fc, &pl, &pol, contigs_depth, contigs_final.c_str(), &ffi)
                                         : contigs_depth ? alga_write_final_fasta_depth_device(engine, &cu, &cs, &fc, &pl, contigs_final.c_str(), &ffi)
                                                         : alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
+                    if (rc == ALGA_OK && !scaffolds.empty()) {
+                        const bool have = pr.paired && pi.insert_median >= 0;
+                        if (!have) fprintf(stderr, "Scaffolding skipped: the placement saw no proper pair, so there is no insert size; every contig is its own scaffold\n");
+                        scp.insert = have ? (int32_t) pi.insert_median : 0;
+                        scp.max_insert = pp.max_insert;
+                        alga_scaffolds sc;
+                        alga_scaffold_info si;
+                        alga_gfa_info sgi;
+                        rc = alga_scaffold_placed_device(engine, &pnd, have ? (const uint8_t *) d_po : nullptr, &pl, &scp, nullptr, &sc, &si);
+                        if (rc == ALGA_OK) rc = alga_write_scaffold_fasta_device(engine, &pl, &sc, polish ? &pol : nullptr, scaffolds.c_str(), &sgi);
+                        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", scaffolds.c_str(), alga_last_error(engine), rc); return 1; }
+                        fprintf(stderr, "Scaffolds: %llu links, %llu bundles supported, %llu joins, %llu scaffolds (%llu of several contigs), N50 %llu -> %llu; insert %d, "
+                                "%llu split pairs (%llu too far), %llu bundles, %llu ambiguous ends, %llu joins dropped for cycles, longest %llu; device ms: links %.3f "
+                                "chain %.3f, call %.1f ms wall; -> %s: %llu bytes\n", (unsigned long long) si.links, (unsigned long long) si.bundles_supported,
+                                (unsigned long long) si.joins, (unsigned long long) si.scaffolds, (unsigned long long) si.scaffolds_multi, (unsigned long long) si.n50_targets,
+                                (unsigned long long) si.n50_scaffolds, scp.insert, (unsigned long long) si.pairs_split, (unsigned long long) si.links_too_far,
+                                (unsigned long long) si.bundles, (unsigned long long) si.ends_ambiguous, (unsigned long long) si.joins_dropped_cycle,
+                                (unsigned long long) si.longest, si.ms_links, si.ms_chain, si.ms_total, scaffolds.c_str(), (unsigned long long) sgi.bytes);
+                        if (!scaffold_layout.empty()) {                      // not a hot path: the host formats from the arrays that came back
+                            const size_t nt = (size_t) sc.n_targets, ns = (size_t) sc.n_scaffolds, nm = (size_t) sc.n_members;
+                            std::vector<uint32_t> off(nt + 1), s_off(ns + 1), links(nt);
+                            std::vector<int32_t> members(nm), rank(nt), gap(nt);
+                            std::vector<uint8_t> orient(nt);
+                            std::vector<uint64_t> start(nt);
+                            rc = alga_copy_to_host(engine, off.data(), pl.d_col_off, (nt + 1) * sizeof(uint32_t));
+                            if (rc == ALGA_OK) rc = alga_copy_to_host(engine, s_off.data(), sc.d_s_off, (ns + 1) * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nm) rc = alga_copy_to_host(engine, members.data(), sc.d_s_members, nm * sizeof(int32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, rank.data(), sc.d_rank, nt * sizeof(int32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, gap.data(), sc.d_gap_after, nt * sizeof(int32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, links.data(), sc.d_join_links, nt * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, orient.data(), sc.d_orient, nt);
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, start.data(), sc.d_start, nt * sizeof(uint64_t));
+                            FILE *f = rc == ALGA_OK ? fopen(scaffold_layout.c_str(), "w") : nullptr;
+                            if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", scaffold_layout.c_str()); return 1; }
+                            for (size_t j = 0; f && j < ns; j++)
+                                for (uint32_t k = s_off[j]; k < s_off[j + 1]; k++) {
+                                    const size_t c = (size_t) members[k];
+                                    fprintf(f, "%zu\t%d\t%zu\t%c\t%llu\t%u\t%d\t%u\n", j, rank[c], c, orient[c] ? '-' : '+', (unsigned long long) start[c], off[c + 1] - off[c],
+                                            gap[c], links[c]);
+                                }
+                            if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", scaffold_layout.c_str()); return 1; }
+                        }
+                    }
                     alga_device_free(engine, d_rows); alga_device_free(engine, d_plen); alga_device_free(engine, d_po);
                     alga_free_parsed_reads(&pr);
                 } else

@@ -1312,6 +1312,105 @@ int  alga_write_polished_fasta_device(alga_engine *e, const alga_unitigs *u, con
                                       const alga_placements *pl, const alga_polished *pol, int32_t depth_header, const char *path,
                                       alga_gfa_info *info /* may be NULL */);
 
+/* ---- scaffolds from split pairs: links, joins, order, gaps, FASTA (alga_amd/csrc/scaffold_kernels.hip, engine_scaffold.hip) ---------------
+ * alga_extend_contigs_device joins contigs only through junctions of the overlap graph.  A pair whose mates are both uniquely placed on
+ * DIFFERENT targets (the placement's pairs_split) says that two targets lie near each other although no edge joins them; this stage turns
+ * those pairs into scaffolds.  Integers only, free of any order (thread, sort); tests/scaffold_checker.py states the rule twice in Python
+ * and the device result equals it array for array.  The library is forward-reverse, as the placement's PROPER rule assumes.
+ *
+ * Inputs: the node set that was placed (twin layout), d_pair_off as alga_place_reads_device takes it (NULL = no pairs), the engine's
+ * current placement result `pl` (from either placement call), and alga_scaffold_params: insert 0 .. 2^20 (no default: the library's insert
+ * size, usually the placement's insert_median), max_insert 1 .. 2^20 (default 1000), min_links 1 .. 2^31 - 1 (5, the default of the
+ * extension's min_connections), max_second_percent 1 .. 100 (50), min_gap 1 .. 2^20 (10), flags 0, reserved 0; anything else answers
+ * ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Ends and reach.  Target t has a left end x = 2t and a right end x = 2t + 1.  A UNIQUE read r lies on target t at p with length
+ *      L = len[2r + 1].  A `+` placement (no ALGA_PLACE_MINUS) points out of the right end: e(r) = 1, d(r) = len[t] - p; a `-` placement
+ *      out of the left end: e(r) = 0, d(r) = p + L.  The read's end is x(r) = 2t + e(r).
+ *   2. Links.  Pairs are judged as in the placement: by the mate with the smaller read index (pair_off[2r + 1] == 1), its mate is r + 1.
+ *      A pair takes part iff both mates are UNIQUE and on different targets (pairs_split: it equals the placement's).  span = d(r) +
+ *      d(r + 1).  The pair is a LINK between x(r) and x(r + 1) iff span <= max_insert, else it counts in links_too_far.  A link's key is
+ *      (a, b) = (min, max) of its two ends.
+ *   3. Bundles.  A bundle is all the links of one key: n links, S the 64-bit sum of their spans, gap = insert - floor(S / n) (int32, may be
+ *      negative).  It is SUPPORTED iff n >= min_links.  The bundles are listed in ascending (a, b).
+ *   4. Choice per end.  Among the SUPPORTED bundles at end x, ordered by (n descending, partner end ascending), n1 is the first and n2 the
+ *      second if there is one.  x is AMBIGUOUS iff a second exists and 100 * n2 >= max_second_percent * n1 (64-bit products).  choice(x) =
+ *      the first bundle's partner iff x has a supported bundle and is not ambiguous; else x has no choice.
+ *   5. Joins.  A bundle (a, b) is a JOIN iff choice(a) == b and choice(b) == a.  Every end then has at most one join: the targets form
+ *      paths and cycles (two bundles between the same two contigs at different ends make a ring of two).
+ *   6. Cycles.  A cycle is opened at its smallest contig id c: the join at end 2c is dropped.  Its bundle keeps SUPPORTED | JOIN and gets
+ *      DROPPED_CYCLE; it counts in joins_dropped_cycle and not in joins, and its two ends are not JOINED.
+ *   7. Scaffolds.  A target of length 0 belongs to no scaffold (scaffold = rank = -1, everything else 0).  Every other target belongs to
+ *      exactly one scaffold, a path of at least one contig.  A path of one contig has orientation +.  A longer path starts at whichever
+ *      of its two terminal contigs has the smaller id; the start contig is entered at its free end.  A contig entered at end e has
+ *      orientation + (d_orient 0) iff e == 0, else - (1, reverse-complemented); it is left at e ^ 1, through that end's join, into the
+ *      partner end's contig.  Scaffolds are numbered by ascending id of their first contig; rank counts from 0 along the path.
+ *   8. Layout.  gap_after[c] = max(gap of the join by which c is left, min_gap), 0 for the last contig of a scaffold; join_links[c] = that
+ *      join's n, 0 for the last.  start[c] = the uint64 sum of the lengths and gap_after of the contigs before c in its scaffold; s_len =
+ *      the scaffold's length with its gaps.
+ *   9. Result (alga_scaffolds; engine-owned, valid until the next scaffold call on `e`: a later placement or polish call does not
+ *      invalidate it, a refused call leaves an earlier result valid).  d_s_off[j] .. d_s_off[j + 1] are the places of scaffold j's contigs
+ *      in d_s_members (contig ids in scaffold order); n_members = the targets with a length.
+ *  10. Counters (alga_scaffold_info): pairs_split, links, links_too_far; bundles, bundles_supported; ends_ambiguous; joins,
+ *      joins_dropped_cycle; scaffolds, scaffolds_multi (more than one contig); longest (the largest s_len); n50_targets, n50_scaffolds
+ *      (host, from the lengths read back: the N50, the largest length l such that the sequences of length >= l hold at least half of all
+ *      bases, 0 for an empty set; the scaffolds with their gaps); ms_links (links + sort + bundles), ms_chain (choice, joins, ranking, layout)
+ *      (HIP events), ms_total (wall).
+ *  11. Refusals, all before anything of the result is written (ALGA_ERR_INVALID_ARGUMENT).  On the host: `pl` is not the engine's current
+ *      placement result; nodes->n / 2 != pl.n_reads.  On the device (k_sc_check, one read-back): pair_off is malformed (the placement's
+ *      check, repeated because the array is passed again); a UNIQUE read with len < 1 or len > 16 * stride_words, its target outside
+ *      [0, n_targets), pos < 0 or pos + len > len[target].  An allocation that fails, on the device or for the host copies of the lengths,
+ *      answers ALGA_ERR_OUT_OF_MEMORY.  "Current" is judged as the polish judges it, by the struct's buffers and sizes: a struct kept from
+ *      an earlier placement call of the same shapes names the same engine buffers and is taken for the current one -- what is read is
+ *      then the current placement's data.  (Which placement a scaffold or polish RESULT was made from is tracked by a serial number inside
+ *      the engine, so alga_write_scaffold_fasta_device cannot be given a scaffold or polish of an earlier placement.)
+ * The links are sorted by a << 32 | b with sort_u64_u32 (the value is the judging read); a scan over the heads numbers the bundles, whose
+ * arrays are allocated at their size after the count comes back.  Contig c entered at end e is state 2c + e with succ = the partner of the
+ * join at the other end: pointer jumping over the 2T states finds the cycles (the smallest id rides along), then ranks the paths and sums
+ * their lengths and gaps in the same jumps.  Nothing walks on the host.
+ *
+ * alga_write_scaffold_fasta_device: one record per scaffold in id order, `>scaffold_id=<j>_length=<s_len>_contigs=<m>`, then its contigs
+ * (reverse-complemented where d_orient is 1) with gap_after `N`s behind each but the last, on one line.  The bases come from the column
+ * array the placement kept, or from pol->d_words.  `pl` must be the engine's current placement, `scaf` its current scaffold result and
+ * made from `pl`, `pol` (may be NULL) the current polish of `pl`; otherwise the call is refused.  ABI stays 7: the calls add. */
+#define ALGA_SCAFFOLD_BUNDLE_SUPPORTED     1   /* bits of d_b_state                                                                   */
+#define ALGA_SCAFFOLD_BUNDLE_JOIN          2
+#define ALGA_SCAFFOLD_BUNDLE_DROPPED_CYCLE 4
+#define ALGA_SCAFFOLD_END_HAS_SUPPORTED    1   /* bits of d_end_state                                                                 */
+#define ALGA_SCAFFOLD_END_AMBIGUOUS        2
+#define ALGA_SCAFFOLD_END_JOINED           4
+typedef struct {
+    int32_t insert, max_insert, min_links, max_second_percent, min_gap, flags;
+    int32_t reserved[2];             /* 0                                                                                             */
+} alga_scaffold_params;
+typedef struct {
+    int64_t         n_targets, n_bundles, n_scaffolds, n_members;
+    const uint32_t *d_b_a, *d_b_b, *d_b_links;       /* n_bundles                                                                     */
+    const uint64_t *d_b_span;
+    const int32_t  *d_b_gap;
+    const uint8_t  *d_b_state;
+    const uint8_t  *d_end_state;     /* 2 * n_targets                                                                                 */
+    const int32_t  *d_scaffold, *d_rank;             /* n_targets                                                                     */
+    const uint8_t  *d_orient;
+    const uint64_t *d_start;
+    const int32_t  *d_gap_after;
+    const uint32_t *d_join_links;
+    const uint32_t *d_s_off;         /* n_scaffolds + 1                                                                               */
+    const int32_t  *d_s_members;     /* n_members                                                                                     */
+    const uint64_t *d_s_len;         /* n_scaffolds                                                                                   */
+} alga_scaffolds;
+typedef struct {
+    uint64_t pairs_split, links, links_too_far, bundles, bundles_supported, ends_ambiguous, joins, joins_dropped_cycle;
+    uint64_t scaffolds, scaffolds_multi, longest, n50_targets, n50_scaffolds;
+    double   ms_links, ms_chain;     /* device time (HIP events): links + sort + bundles; choice, joins, ranking, layout              */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_scaffold_info;
+void alga_scaffold_default_params(alga_scaffold_params *p);   /* insert is left 0: the caller sets it                                 */
+int  alga_scaffold_placed_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off /* may be NULL */, const alga_placements *pl,
+                                 const alga_scaffold_params *p, void *hip_stream, alga_scaffolds *out, alga_scaffold_info *info /* may be NULL */);
+int  alga_write_scaffold_fasta_device(alga_engine *e, const alga_placements *pl, const alga_scaffolds *scaf, const alga_polished *pol /* may be NULL */,
+                                      const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
