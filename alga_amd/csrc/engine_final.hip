@@ -226,9 +226,5 @@ extern "C" int alga_write_final_fasta_device(alga_engine *e, const alga_unitigs 
     if (!alga_final_is_current(e, u, cons, fin, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
     HIP_TRY(e, hipSetDevice(e->device));
     const FcFasta f{cons->d_words, (const unsigned long long *) u->d_word_off, fin->d_verdict, fin->d_order, fin->d_begin, fin->d_len, (uint64_t) fin->n_accepted};
-    AlgaTextJob job;
-    job.items = f.n;
-    job.sizes = [f](uint32_t *sizes, unsigned long long *counters, hipStream_t s) { launch_fc_fasta_sizes(f, sizes, counters, s); };
-    job.format = [f](const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) { launch_fc_fasta_write(f, off, i0, i1, buf, s); };
-    return alga_text_job_run(e, job, path, info);
+    return alga_text_records(e, f, launch_fc_fasta_sizes, launch_fc_fasta_write, path, info);
 }

@@ -10,6 +10,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <cstring>
 #include <future>
 #include <vector>
 
@@ -38,10 +39,9 @@ struct GfaEvents {
     ~GfaEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
 };
 
-int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, int &fd, const AlgaTextJob *job = nullptr) {
+int gfa_impl(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info, int &fd) {
     hipStream_t s = e->own_stream;
-    const uint64_t m = c.m;
-    const uint64_t N = job ? job->items : c.n_seg + m;              // items: segment lines, then link lines (a job: its own items)
+    const uint64_t N = job.items;
     int rc;
     GfaEvents evs;
     // [0, 1] checks .. scan, [2, 3] the copies' ends (one per pinned slot), [4 + 2 * (k % 4), 5 + 2 * (k % 4)] the formatting of chunk k
@@ -49,29 +49,14 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     evs.ev.assign(12, nullptr);
     for (int k = 0; k < 12; k++) HIP_TRY(e, hipEventCreate(&evs.ev[(size_t) k]));
     if ((rc = alga_ensure(e, e->counters, GFA_COUNTERS * sizeof(unsigned long long)))) return rc;
-    if ((rc = alga_ensure(e, e->gfa_rowptr, ((size_t) c.n + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_sizes, (size_t) (N + 1) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_off, (size_t) (N + 1) * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_tiles, (gfa_scan_tiles(N) + 1) * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->counters.p, *off = (unsigned long long *) e->gfa_off.p;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, GFA_COUNTERS * sizeof(unsigned long long), s));
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
-    if (!job) launch_gfa_check(c, cnt, s);
-    if ((rc = alga_check_launch(e, "k_gfa_check"))) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    if (const unsigned long long bad = e->h_counters[GFA_FLAGS]) {
-        const char *why = (bad & GFA_BAD_ID) ? "edge endpoint outside [0, n)" : (bad & GFA_BAD_ORDER) ? "edges must be sorted by (src, dst, offset)"
-                        : (bad & GFA_BAD_LEN) ? "negative node length" : "ALGA_GFA_TWINS: len[2k] != len[2k + 1]";
-        return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
-    }
-    // the list is valid: per-source rows, line sizes, byte offsets
-    if (m) {
-        launch_edge_rowptr(c.e, m, c.n, (uint32_t *) e->gfa_rowptr.p, s);
-        if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
-    }
-    if (job) job->sizes((uint32_t *) e->gfa_sizes.p, cnt, s);
-    else launch_gfa_sizes(c, (const uint32_t *) e->gfa_rowptr.p, (uint32_t *) e->gfa_sizes.p, cnt, s);
+    if (job.prepare && (rc = job.prepare(cnt, s))) return rc;
+    job.sizes((uint32_t *) e->gfa_sizes.p, cnt, s);
     if ((rc = alga_check_launch(e, "k_gfa_sizes"))) return rc;
     launch_gfa_scan64((const uint32_t *) e->gfa_sizes.p, N, off, (unsigned long long *) e->gfa_tiles.p, s);
     if ((rc = alga_check_launch(e, "gfa scan"))) return rc;
@@ -82,10 +67,10 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     float ms = 0.0f;
     HIP_TRY(e, hipEventElapsedTime(&ms, evs.ev[0], evs.ev[1]));
     double ms_format = ms;
-    const uint64_t total = e->h_counters[GFA_COUNTERS], max_line = e->h_counters[GFA_MAX_LINE];
+    const uint64_t total = e->h_counters[GFA_COUNTERS], max_line = e->h_counters[GFA_MAX_LINE], head = strlen(job.head);
     if (info) {
         info->segments = e->h_counters[GFA_SEGMENTS]; info->links = e->h_counters[GFA_LINKS]; info->links_merged = e->h_counters[GFA_MERGED];
-        info->bytes = (c.fasta ? 0 : sizeof(kGfaHeader) - 1) + total;
+        info->bytes = head + total;
     }
     // chunks: step = cap - longest line, so that no chunk exceeds cap and each ends at a line boundary
     uint64_t cap = (uint64_t) e->opt_gfa_chunk_mb << 20;
@@ -107,9 +92,9 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
         }
     }
     fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return alga_fail(e, ALGA_ERR_IO, c.fasta ? "cannot create the FASTA file" : "cannot create the GFA file");
-    const uint64_t head = c.fasta ? 0 : sizeof(kGfaHeader) - 1;       // (a FASTA file has no header line)
-    if (head && !write_all(fd, kGfaHeader, head, 0)) return alga_fail(e, ALGA_ERR_IO, "cannot write the GFA file");
+    auto io_fail = [&](const char *verb) { return alga_fail(e, ALGA_ERR_IO, (std::string("cannot ") + verb + " the " + job.kind + " file").c_str()); };
+    if (fd < 0) return io_fail("create");
+    if (head && !write_all(fd, job.head, head, 0)) return io_fail("write");
     std::future<bool> writer[2];
     int pending_fmt[2] = {-1, -1};                                 // event pair of the chunk the slot holds, -1 none
     bool io_ok = true;
@@ -131,8 +116,7 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
         if (!bytes) continue;
         // the formatting of chunk k runs behind the copy of chunk k - 1 (same stream, one device buffer)
         HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (4 + 2 * pair)], s));
-        if (job) job->format(off, i0, i1, dbuf, s);
-        else launch_gfa_format(c, off, i0, i1, dbuf, s);
+        job.format(off, i0, i1, dbuf, s);
         if ((rc = alga_check_launch(e, "k_gfa_format"))) break;
         HIP_TRY(e, hipEventRecord(evs.ev[(size_t) (5 + 2 * pair)], s));
         // ... wait for the write of the chunk two before (it read this pinned buffer) while the device formats
@@ -152,16 +136,46 @@ int gfa_impl(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *i
     for (int k = 0; k < 2; k++) { const int r = finish_slot(k); if (rc == ALGA_OK) rc = r; }
     if (rc != ALGA_OK) return rc;
     HIP_TRY(e, hipStreamSynchronize(s));
-    if (!io_ok) return alga_fail(e, ALGA_ERR_IO, c.fasta ? "cannot write the FASTA file" : "cannot write the GFA file");
-    if (close(fd) != 0) { fd = -1; return alga_fail(e, ALGA_ERR_IO, c.fasta ? "cannot close the FASTA file" : "cannot close the GFA file"); }
+    if (!io_ok) return io_fail("write");
+    if (close(fd) != 0) { fd = -1; return io_fail("close"); }
     fd = -1;
     if (info) info->ms_format = ms_format;
     return ALGA_OK;
 }
 
-int gfa_run(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, std::chrono::steady_clock::time_point t0, const AlgaTextJob *job = nullptr) {
+// The GFA of a node set and its edge list: the device's verdict on the input and the per-source rows come before the sizes
+int gfa_export(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *info, std::chrono::steady_clock::time_point t0) {
+    AlgaTextJob job;
+    job.items = c.n_seg + c.m;                                       // segment lines, then link lines
+    job.kind = "GFA"; job.head = kGfaHeader;
+    job.prepare = [e, c](unsigned long long *cnt, hipStream_t s) -> int {
+        int rc;
+        if ((rc = alga_ensure(e, e->gfa_rowptr, ((size_t) c.n + 2) * sizeof(uint32_t)))) return rc;
+        launch_gfa_check(c, cnt, s);
+        if ((rc = alga_check_launch(e, "k_gfa_check"))) return rc;
+        HIP_TRY(e, hipMemcpyAsync(e->h_counters, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIP_TRY(e, hipStreamSynchronize(s));
+        if (const unsigned long long bad = e->h_counters[GFA_FLAGS]) {
+            const char *why = (bad & GFA_BAD_ID) ? "edge endpoint outside [0, n)" : (bad & GFA_BAD_ORDER) ? "edges must be sorted by (src, dst, offset)"
+                            : (bad & GFA_BAD_LEN) ? "negative node length" : "ALGA_GFA_TWINS: len[2k] != len[2k + 1]";
+            return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
+        }
+        if (c.m) {                                                   // the list is valid: per-source rows
+            launch_edge_rowptr(c.e, c.m, c.n, (uint32_t *) e->gfa_rowptr.p, s);
+            if ((rc = alga_check_launch(e, "k_edge_rowptr"))) return rc;
+        }
+        return ALGA_OK;
+    };
+    job.sizes = [e, c](uint32_t *sizes, unsigned long long *cnt, hipStream_t s) { launch_gfa_sizes(c, (const uint32_t *) e->gfa_rowptr.p, sizes, cnt, s); };
+    job.format = [c](const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) { launch_gfa_format(c, off, i0, i1, buf, s); };
+    return alga_text_job_run(e, job, path, info, t0);
+}
+
+}  // namespace
+
+int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info, std::chrono::steady_clock::time_point t0) {
     int fd = -1;
-    const int rc = gfa_impl(e, c, path, info, fd, job);
+    const int rc = gfa_impl(e, job, path, info, fd);
     if (rc != ALGA_OK) {
         (void) hipStreamSynchronize(e->own_stream);                 // nothing may still copy into the pinned buffers
         if (fd >= 0) { close(fd); unlink(path); }                  // no partial file is left behind
@@ -169,14 +183,6 @@ int gfa_run(alga_engine *e, const GfaCfg &c, const char *path, alga_gfa_info *in
     }
     if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return ALGA_OK;
-}
-
-}  // namespace
-
-int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info) {
-    GfaCfg c{nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 1};
-    c.fasta = 1;                                                     // no header line; the messages name a FASTA file
-    return gfa_run(e, c, path, info, std::chrono::steady_clock::now(), &job);
 }
 
 extern "C" int alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, const alga_edge *d_edges, uint64_t n_edges, const char *path, int32_t flags,
@@ -196,7 +202,7 @@ extern "C" int alga_write_gfa_device(alga_engine *e, const alga_nodes *nodes, co
     const bool twins = flags & ALGA_GFA_TWINS;
     GfaCfg c{nodes->words, nodes->stride_words, nodes->len, nodes->n, (const alga_edge_dev *) d_edges, n_edges, twins ? (uint64_t) nodes->n / 2 : (uint64_t) nodes->n,
              twins ? 1 : 0, (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
-    return gfa_run(e, c, path, info, t0);
+    return gfa_export(e, c, path, info, t0);
 }
 
 // The unitig graph as GFA: the same kernels over the ragged rows (GfaCfg::row_off); pair k is segment k, oriented unitig 2k+1 is `+`.
@@ -218,10 +224,10 @@ extern "C" int alga_write_unitig_gfa_device(alga_engine *e, const alga_unitigs *
     GfaCfg c{(flags & ALGA_GFA_CONSENSUS) ? (const uint32_t *) e->cs_words.p : u->d_words, 0, (const int32_t *) e->ut_ulen2.p, 2 * u->n_pairs,
              (const alga_edge_dev *) u->d_edges, u->n_edges, (uint64_t) u->n_pairs, 1, (flags & ALGA_GFA_SEQUENCES) ? 1 : 0};
     c.row_off = (const unsigned long long *) u->d_word_off;
-    return gfa_run(e, c, path, info, t0);
+    return gfa_export(e, c, path, info, t0);
 }
 
-// The consensus windows as FASTA: the same pipeline with one item per pair and no links (GfaCfg::fasta)
+// The consensus windows as FASTA: one record per pair that is long enough
 extern "C" int alga_write_consensus_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const char *path, int32_t min_length,
                                                  alga_gfa_info *info) {
     if (!e) return ALGA_ERR_INVALID_ARGUMENT;
@@ -235,9 +241,7 @@ extern "C" int alga_write_consensus_fasta_device(alga_engine *e, const alga_unit
         cons->d_trim_left != (const int32_t *) e->cs_trim.p)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_unitig_consensus_device call on this engine");
     HIP_TRY(e, hipSetDevice(e->device));
-    GfaCfg c{cons->d_words, 0, cons->d_len, u->n_pairs, nullptr, 0, (uint64_t) u->n_pairs, 0, 1};
-    c.row_off = (const unsigned long long *) u->d_word_off;
-    c.fasta = 1; c.min_length = min_length; c.seq_off = cons->d_trim_left;
+    GfaFasta f{cons->d_words, (const unsigned long long *) u->d_word_off, cons->d_len, cons->d_trim_left, nullptr, (uint64_t) u->n_pairs, min_length};
     if (e->ut_is_contig) {                                           // the records are numbered as they are written: a scan of the selection
         const uint64_t P = (uint64_t) u->n_pairs;
         int rc;
@@ -247,7 +251,7 @@ extern "C" int alga_write_consensus_fasta_device(alga_engine *e, const alga_unit
         launch_ct_fasta_select(cons->d_len, P, min_length, sel, e->own_stream);
         launch_exclusive_scan(sel, P, rank, (uint64_t *) e->scan_scratch.p, e->own_stream);
         if ((rc = alga_check_launch(e, "scan(fasta records)"))) return rc;
-        c.rec_rank = rank;
+        f.rec_rank = rank;
     }
-    return gfa_run(e, c, path, info, t0);
+    return alga_text_records(e, f, launch_gfa_fasta_sizes, launch_gfa_fasta_write, path, info, t0);
 }

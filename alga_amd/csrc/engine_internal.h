@@ -304,6 +304,7 @@ inline void alga_release(DevBuf &b) {
     b.p = nullptr; b.cap = 0;
 }
 
+#include <chrono>
 #include <functional>
 typedef std::function<void(void * /* pinned chunk */, size_t /* byte offset of the chunk */, size_t /* bytes */)> AlgaStageFill;
 int  alga_staged_h2d(alga_engine *e, void *d_dst, const void *h_src, size_t bytes);   // staging.hip: blocking
@@ -322,15 +323,31 @@ int alga_ut_estar(alga_engine *e, const alga_nodes *nodes, const alga::alga_edge
 int alga_ut_rank(alga_engine *e, const int32_t *len, int32_t n, int32_t *nxt, const int32_t *noff, int32_t *prv, unsigned long long *cnt, uint32_t *p_flag,
                  int &cur, int &rounds, hipStream_t s);
 
-// engine_gfa.hip: the chunk pipeline of the GFA export (sizes -> 64-bit scan -> chunks formatted on the device, copied down and written by a host
-// thread) over items that another file sizes and formats.  sizes: fill sizes[0 .. items) and counters[GFA_SEGMENTS] / [GFA_MAX_LINE] (zeroed);
+// engine_gfa.hip: the chunk pipeline of every text output (sizes -> 64-bit scan -> chunks formatted on the device, copied down and written by a
+// host thread) over items that another file sizes and formats.  sizes: fill sizes[0 .. items) and counters[GFA_SEGMENTS] / [GFA_MAX_LINE] (zeroed);
 // format: the text of items [i0, i1) into buf, item i at byte off[i] - off[i0].  An error removes the partial file.
 struct AlgaTextJob {
     uint64_t items;
     std::function<void(uint32_t *sizes, unsigned long long *counters, hipStream_t s)> sizes;
     std::function<void(const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s)> format;
+    const char *kind = "FASTA";       // what the I/O error messages call the file
+    const char *head = "";            // the text before the first item
+    // optional: what has to hold or exist before the sizes (the device's verdict on the input, tables); an error code ends the job
+    std::function<int(unsigned long long *counters, hipStream_t s)> prepare;
 };
-int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info);
+int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info,
+                      std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now());
+
+// the job of records that a launch_*_sizes / launch_*_write pair formats from one struct `f` (f.n items)
+template <class F> int alga_text_records(alga_engine *e, const F &f, void (*sizes)(const F &, uint32_t *, unsigned long long *, hipStream_t),
+                                         void (*write)(const F &, const unsigned long long *, uint64_t, uint64_t, char *, hipStream_t), const char *path,
+                                         alga_gfa_info *info, std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now()) {
+    AlgaTextJob job;
+    job.items = f.n;
+    job.sizes = [f, sizes](uint32_t *out, unsigned long long *counters, hipStream_t s) { sizes(f, out, counters, s); };
+    job.format = [f, write](const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) { write(f, off, i0, i1, buf, s); };
+    return alga_text_job_run(e, job, path, info, t0);
+}
 
 // engine_correct.hip: the correction of device-resident rows in the parser's layout, in place (what alga_correct_reads_device and the corrected
 // ingest share); the parameters are checked by the callers (alga_correct_check_params)

@@ -176,9 +176,5 @@ extern "C" int alga_write_polished_fasta_device(alga_engine *e, const alga_uniti
     HIP_TRY(e, hipSetDevice(e->device));
     const PoFasta f{pol->d_words, pol->d_col_off, fin->d_verdict, fin->d_order, (const unsigned long long *) pl->d_t_reads, (const unsigned long long *) pl->d_t_bases,
                     (uint64_t) fin->n_accepted, depth_header};
-    AlgaTextJob job;
-    job.items = f.n;
-    job.sizes = [f](uint32_t *sizes, unsigned long long *counters, hipStream_t s) { launch_po_fasta_sizes(f, sizes, counters, s); };
-    job.format = [f](const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) { launch_po_fasta_write(f, off, i0, i1, buf, s); };
-    return alga_text_job_run(e, job, path, info);
+    return alga_text_records(e, f, launch_po_fasta_sizes, launch_po_fasta_write, path, info);
 }

@@ -271,9 +271,5 @@ extern "C" int alga_write_scaffold_fasta_device(alga_engine *e, const alga_place
     HIP_TRY(e, hipSetDevice(e->device));
     const ScFasta f{pol ? pol->d_words : (const uint32_t *) e->pl_cols.p, pl->d_col_off, scaf->d_s_off, scaf->d_s_members, (const unsigned long long *) scaf->d_s_len,
                     (const unsigned long long *) scaf->d_start, scaf->d_orient, (uint64_t) scaf->n_scaffolds};
-    AlgaTextJob job;
-    job.items = f.n;
-    job.sizes = [f](uint32_t *sizes, unsigned long long *counters, hipStream_t s) { launch_sc_fasta_sizes(f, sizes, counters, s); };
-    job.format = [f](const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) { launch_sc_fasta_write(f, off, i0, i1, buf, s); };
-    return alga_text_job_run(e, job, path, info);
+    return alga_text_records(e, f, launch_sc_fasta_sizes, launch_sc_fasta_write, path, info);
 }

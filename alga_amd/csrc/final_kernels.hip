@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "final_kernels.h"
-#include "gfa_kernels.h"
+#include "text_record.h"
 
 namespace alga {
 
@@ -28,23 +28,6 @@ namespace {
 
 constexpr int FC_BLOCK = 256;
 constexpr uint32_t FC_NONE = 0xFFFFFFFFu;
-
-__device__ __constant__ uint32_t kFcPow10[10] = {1u, 10u, 100u, 1000u, 10000u, 100000u, 1000000u, 10000000u, 100000000u, 1000000000u};
-
-__device__ __forceinline__ int fc_dec_width(uint32_t v) {
-    int w = 1;
-    while (w < 10 && v >= kFcPow10[w]) w++;
-    return w;
-}
-
-__device__ __forceinline__ unsigned long long fc_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long fc_wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
 
 // slot of this lane in a list that the whole wave appends to (every lane of the wave calls it)
 __device__ __forceinline__ uint32_t fc_wave_append(bool want, unsigned long long *counter) {
@@ -80,8 +63,8 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_len_check(const int32_t *__rest
         if (L < 0) bad = FC_BAD_LEN;
         else { const unsigned long long c = (unsigned long long) (L < FC_CAP ? L : FC_CAP); mx = c > mx ? c : mx; }
     }
-    bad = fc_wave_max(bad);
-    mx = fc_wave_max(mx);
+    bad = wave_max(bad);
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) {
         if (bad) atomicOr(&counters[FC_FLAGS], bad);
         if (mx) atomicMax(&counters[FC_MAX_LEN], mx);
@@ -235,7 +218,7 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_number(FcCfg c, const uint32_t 
         else n_rej = 1;
         c.id[k] = id; c.new_reads[k] = nw; c.trim_left[k] = 0; c.begin[k] = begin; c.len[k] = L;
     }
-    n_short = fc_wave_sum(n_short); n_rej = fc_wave_sum(n_rej); n_acc = fc_wave_sum(n_acc); mx = fc_wave_max(mx);
+    n_short = wave_sum(n_short); n_rej = wave_sum(n_rej); n_acc = wave_sum(n_acc); mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) {
         if (n_short) atomicAdd(&counters[FC_SHORT], n_short);
         if (n_rej) atomicAdd(&counters[FC_REJECTED], n_rej);
@@ -256,103 +239,28 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_apply_trim(FcCfg c, const int32
         if (t + 10 < L) { c.begin[k] += t; c.len[k] = L - t; }
         else { c.verdict[k] = FC_V_TRIMMED_AWAY; c.begin[k] = 0; c.len[k] = 0; away = 1; }
     }
-    away = fc_wave_sum(away);
+    away = wave_sum(away);
     if ((threadIdx.x & 63) == 0 && away) atomicAdd(&counters[FC_TRIMMED_AWAY], away);
 }
 
 // ---- FASTA ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(FC_BLOCK) k_fc_fasta_sizes(FcFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
-    const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long live = 0, bytes = 0;
-    if (j < f.n) {
+// `>contig_id=<id>_length=<len>\n<window>\n` of the accepted pair of id j
+struct FcRecord : FastaRecord<PackedSeq> {
+    __device__ __forceinline__ bool set(const FcFasta &f, uint64_t j) {
         const uint32_t k = (uint32_t) f.order[j];
-        if (f.verdict[k] == FC_V_ACCEPTED) {
-            const uint32_t L = (uint32_t) f.len[k];
-            // >contig_id= id _length= len \n seq \n
-            bytes = 11ull + fc_dec_width((uint32_t) j) + 8 + fc_dec_width(L) + 1 + L + 1;
-            live = 1;
-        }
-        sizes[j] = (uint32_t) bytes;
-    }
-    live = fc_wave_sum(live);
-    bytes = fc_wave_max(bytes);
-    if ((threadIdx.x & 63) == 0 && live) {
-        atomicAdd(&counters[GFA_SEGMENTS], live);
-        atomicMax(&counters[GFA_MAX_LINE], bytes);
-    }
-}
-
-struct FcRecord {
-    uint32_t id, L, hp;              // hp = bytes before the sequence
-    int wn, wl;
-    const uint32_t *row; uint32_t q0;
-    __device__ __forceinline__ char digit(uint32_t v, int w, int d) const { return (char) ('0' + (v / kFcPow10[w - 1 - d]) % 10); }
-    __device__ __forceinline__ char base(uint32_t q) const { q += q0; return (char) ((0x54474341u >> (8 * ((row[q >> 4] >> (2 * (q & 15))) & 3))) & 0xFF); }
-    __device__ char at(uint32_t p) const {
-        if (p < 11u) return ">contig_id="[p];
-        if (p < 11u + wn) return digit(id, wn, (int) (p - 11u));
-        if (p < 19u + wn) return "_length="[p - 11u - wn];
-        if (p + 1 < hp) return digit(L, wl, (int) (p - 19u - wn));
-        if (p < hp) return '\n';
-        return p - hp < L ? base(p - hp) : '\n';
-    }
-    // 16 bases from sequence index q (all inside the sequence) as 4 little-endian words of ASCII
-    __device__ __forceinline__ uint4 bases16(uint32_t q) const {
-        q += q0;
-        const uint32_t w = q >> 4, sh = q & 15;
-        uint32_t codes = row[w];
-        if (sh) codes = (uint32_t) ((((uint64_t) row[w + 1] << 32) | codes) >> (2 * sh));
-        uint32_t o[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++) x |= ((0x54474341u >> (8 * ((codes >> (2 * (4 * k + b))) & 3))) & 0xFFu) << (8 * b);
-            o[k] = x;
-        }
-        return make_uint4(o[0], o[1], o[2], o[3]);
+        if (f.verdict[k] != FC_V_ACCEPTED) return false;
+        contig_head(j, (uint32_t) f.len[k]); seal();
+        seq.row = f.words + f.word_off[k]; seq.q0 = (uint32_t) f.begin[k];
+        return true;
     }
 };
 
-// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
+__global__ void __launch_bounds__(FC_BLOCK) k_fc_fasta_sizes(FcFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    text_sizes_body<FcRecord>(f, f.n, sizes, counters);
+}
 __global__ void __launch_bounds__(FC_BLOCK) k_fc_fasta_write(FcFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
                                                              char *__restrict__ buf) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t base = off[i0];
-    const uint64_t waves = (uint64_t) gridDim.x * (blockDim.x >> 6);
-    for (uint64_t j = i0 + (uint64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); j < i1; j += waves) {
-        const uint64_t l0 = off[j], l1 = off[j + 1];
-        if (l0 == l1) continue;
-        const uint32_t k = (uint32_t) f.order[j];
-        FcRecord s;
-        s.id = (uint32_t) j; s.L = (uint32_t) f.len[k]; s.wn = fc_dec_width(s.id); s.wl = fc_dec_width(s.L);
-        s.hp = 11u + s.wn + 8u + s.wl + 1u;
-        s.row = f.words + f.word_off[k]; s.q0 = (uint32_t) f.begin[k];
-        char *g0 = buf + (l0 - base), *g1 = buf + (l1 - base);
-        char *a0 = (char *) (((uintptr_t) g0 + 15) & ~(uintptr_t) 15), *a1 = (char *) ((uintptr_t) g1 & ~(uintptr_t) 15);
-        if (a0 >= a1) {                                               // no whole aligned block inside the record
-            for (char *p = g0 + lane; p < g1; p += 64) *p = s.at((uint32_t) (p - g0));
-            continue;
-        }
-        if (g0 + lane < a0) g0[lane] = s.at((uint32_t) lane);         // < 16 bytes before the first aligned block, < 16 after the last
-        if (a1 + lane < g1) a1[lane] = s.at((uint32_t) (a1 - g0) + lane);
-        const uint64_t nblk = (uint64_t) (a1 - a0) >> 4;
-        for (uint64_t q = lane; q < nblk; q += 64) {
-            const uint32_t p = (uint32_t) (a0 - g0) + (uint32_t) (q << 4);
-            uint4 v;
-            if (p >= s.hp && p + 16 <= s.hp + s.L) v = s.bases16(p - s.hp);
-            else {
-                uint32_t o[4];
-                for (int w = 0; w < 4; w++) {
-                    uint32_t x = 0;
-                    for (int b = 0; b < 4; b++) x |= (uint32_t) (uint8_t) s.at(p + 4 * w + b) << (8 * b);
-                    o[w] = x;
-                }
-                v = make_uint4(o[0], o[1], o[2], o[3]);
-            }
-            *reinterpret_cast<uint4 *>(a0 + (q << 4)) = v;
-        }
-    }
+    text_write_body<FcRecord>(f, off, i0, i1, buf);
 }
 
 inline unsigned fc_grid(uint64_t items, uint64_t cap = 1u << 20) {

@@ -19,15 +19,21 @@ struct GfaCfg {
     // optional: ragged rows (the unitig graph).  Non-null: the row of node v starts at words + row_off[v >> 1] (one row per twin pair, read
     // through its odd node; `stride` is not used); null: at words + v * stride
     const unsigned long long *row_off = nullptr;
-    // optional: FASTA records instead of segment lines (the consensus windows; twins == 0, m == 0, one ragged row per item): item j is
-    // `>unitig_<j>_length=<len[j]>\n<bases seq_off[j] .. seq_off[j] + len[j] of its row>\n`, written when len[j] >= min_length and len[j] > 0
-    int32_t fasta = 0, min_length = 0;
-    const int32_t *seq_off = nullptr;
-    // optional, FASTA only: the records of a contig result, `>contig_id=<rec_rank[j]>_length=<len[j]>` (rec_rank[j] = records written before item j)
-    const uint32_t *rec_rank = nullptr;
     __host__ __device__ __forceinline__ const uint32_t *row(uint64_t node) const {
         return row_off ? words + row_off[twins ? node >> 1 : node] : words + node * (uint64_t) stride;
     }
+};
+
+// The consensus windows as FASTA (one ragged row per item): item j is `>unitig_<j>_length=<len[j]>\n<bases seq_off[j] .. seq_off[j] + len[j] of its
+// row>\n`, written when len[j] >= min_length and len[j] > 0.  rec_rank non-null: the records of a contig result,
+// `>contig_id=<rec_rank[j]>_length=<len[j]>` (rec_rank[j] = records written before item j)
+struct GfaFasta {
+    const uint32_t *words;
+    const unsigned long long *row_off;
+    const int32_t *len, *seq_off;
+    const uint32_t *rec_rank;
+    uint64_t n;
+    int32_t min_length;
 };
 
 // counters[] (unsigned long long) the kernels fill
@@ -45,5 +51,7 @@ void   launch_gfa_scan64(const uint32_t *sizes, uint64_t n, unsigned long long *
 void   launch_gfa_bounds(const unsigned long long *off, uint64_t n, uint64_t step, uint64_t K, unsigned long long *bounds, hipStream_t s);
 // the lines of items [i0, i1) into buf, item i at byte off[i] - off[i0]
 void   launch_gfa_format(const GfaCfg &c, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s);
+void   launch_gfa_fasta_sizes(const GfaFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s);
+void   launch_gfa_fasta_write(const GfaFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s);
 
 }  // namespace alga

@@ -11,10 +11,13 @@
 //   k_gfa_seg_write  one wave per segment line: 16-byte aligned stores of the ASCII bases (2-bit codes A C G T = 0..3, 16 codes per
 //                    word, low bits first), byte stores for the partial 16-byte blocks at the two ends of the line (neighbouring lines)
 //   k_gfa_link_write one thread per kept edge: its own integer-to-decimal conversion
+//   k_gfa_fasta_sizes / k_gfa_fasta_write   the consensus windows as FASTA records (GfaFasta), through the same scan and bounds
+// A segment line and a FASTA record are record types of text_record.h: the sizes and write kernels are its two bodies.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gfa_kernels.h"
+#include "text_record.h"
 
 namespace alga {
 
@@ -23,18 +26,7 @@ namespace {
 constexpr int GFA_BLOCK = 256;
 constexpr int SCAN_T = 256, SCAN_K = 8, SCAN_TILE64 = SCAN_T * SCAN_K;
 
-__device__ __constant__ uint64_t kPow10[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull,
-                                               1000000000ull, 10000000000ull, 100000000000ull, 1000000000000ull, 10000000000000ull,
-                                               100000000000000ull, 1000000000000000ull, 10000000000000000ull, 100000000000000000ull,
-                                               1000000000000000000ull, 10000000000000000000ull};
-
-// decimal width of a non-negative value
-__device__ __forceinline__ int dec_width(uint64_t v) {
-    int w = 1;
-    while (w < 20 && v >= kPow10[w]) w++;
-    return w;
-}
-// ... of a signed one (a minus sign counts)
+// decimal width of a signed value (a minus sign counts)
 __device__ __forceinline__ int sdec_width(int64_t v) { return v < 0 ? 1 + dec_width((uint64_t) (-v)) : dec_width((uint64_t) v); }
 
 __device__ __forceinline__ char *put_sdec(char *p, int64_t v) {
@@ -45,27 +37,8 @@ __device__ __forceinline__ char *put_sdec(char *p, int64_t v) {
     return p + w;
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
-
 __device__ __forceinline__ bool edge_less(const alga_edge_dev &x, const alga_edge_dev &y) {
     return x.src < y.src || (x.src == y.src && (x.dst < y.dst || (x.dst == y.dst && x.offset < y.offset)));
-}
-
-__device__ __forceinline__ uint64_t seg_line_bytes(uint64_t name, int32_t L, int seqs) {
-    // S \t name \t seq \t LN:i: len \n
-    return L > 0 ? 2 + dec_width(name) + 1 + (seqs ? (uint64_t) L : 1) + 6 + dec_width((uint64_t) L) + 1 : 0;
-}
-
-// > unitig_ name _length= len \n seq \n  (prefix: 8 bytes, or the 11 of ">contig_id=")
-__device__ __forceinline__ uint64_t fasta_record_bytes(uint64_t name, int32_t L, int32_t min_length, uint32_t prefix) {
-    return L > 0 && L >= min_length ? prefix + dec_width(name) + 8 + dec_width((uint64_t) L) + 1 + (uint64_t) L + 1 : 0;
 }
 
 __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_check(GfaCfg c, unsigned long long *__restrict__ counters) {
@@ -84,23 +57,6 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_check(GfaCfg c, unsigned long
         }
     }
     if (bad) atomicOr(&counters[GFA_FLAGS], bad);
-}
-
-__global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_sizes(GfaCfg c, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
-    const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long live = 0, bytes = 0;
-    if (j < c.n_seg) {
-        const int32_t L = c.len[c.twins ? 2 * j + 1 : j];
-        bytes = c.fasta ? fasta_record_bytes(c.rec_rank ? c.rec_rank[j] : j, L, c.min_length, c.rec_rank ? 11u : 8u) : seg_line_bytes(j, L, c.seqs);
-        live = bytes > 0;
-        sizes[j] = (uint32_t) bytes;
-    }
-    live = wave_sum(live);
-    bytes = wave_max(bytes);
-    if ((threadIdx.x & 63) == 0 && live) {
-        atomicAdd(&counters[GFA_SEGMENTS], live);
-        atomicMax(&counters[GFA_MAX_LINE], bytes);
-    }
 }
 
 __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_link_sizes(GfaCfg c, const uint32_t *__restrict__ rowptr, uint32_t *__restrict__ sizes,
@@ -219,89 +175,71 @@ __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_bounds(const unsigned long lo
     bounds[K + 1 + k] = off[b];
 }
 
-// byte p of a segment line: "S\t" name "\t" seq "\tLN:i:" len "\n"; of a FASTA record: ">unitig_" name "_length=" len "\n" seq "\n"
-// CONTIG: the FASTA of a contig result (">contig_id=" and the record's rank as its name); false: the code as it was before that form existed
-template <bool CONTIG> struct SegLine {
-    uint64_t name; int32_t L; int wn, wl; uint32_t hp, sl;           // hp = bytes before the sequence, sl = bytes of the sequence field
-    const uint32_t *row; int seqs;
-    int fasta; uint32_t q0;                                           // FASTA: the sequence starts at base q0 of the row
-    __device__ __forceinline__ char digit(uint64_t v, int w, int d) const { return (char) ('0' + (v / kPow10[w - 1 - d]) % 10); }
-    __device__ __forceinline__ char base(uint32_t q) const { q += q0; return (char) ((0x54474341u >> (8 * ((row[q >> 4] >> (2 * (q & 15))) & 3))) & 0xFF); }
-    __device__ char at(uint32_t p) const {
-        if (fasta) {
-            constexpr uint32_t fp = CONTIG ? 11u : 8u;
-            if (p < fp) return CONTIG ? ">contig_id="[p] : ">unitig_"[p];
-            if (p < fp + wn) return digit(name, wn, (int) (p - fp));
-            if (p < fp + 8u + wn) return "_length="[p - fp - wn];
-            if (p + 1 < hp) return digit((uint64_t) L, wl, (int) (p - fp - 8 - wn));
-            if (p < hp) return '\n';
-            return p - hp < sl ? base(p - hp) : '\n';
-        }
-        if (p < hp) return p < 2 ? (p == 0 ? 'S' : '\t') : (p < 2u + wn ? digit(name, wn, (int) p - 2) : '\t');
-        const uint32_t q = p - hp;
-        if (q < sl) return seqs ? base(q) : '*';
-        const uint32_t r = q - sl;
-        if (r < 6) return "\tLN:i:"[r];
-        return r < 6u + wl ? digit((uint64_t) L, wl, (int) r - 6) : '\n';
+// "S\t" name "\t" seq "\tLN:i:" len "\n"; seq is `*` without ALGA_GFA_SEQUENCES
+struct SegLine {
+    static constexpr bool kPacked = true, kAligned = true;
+    TextHeader<2> h; TextHeader<1> t;                                 // before and after the sequence (h's newline is never reached)
+    uint32_t hp, sl; int seqs;                                        // hp = bytes before the sequence, sl = bytes of the sequence field
+    PackedSeq seq;
+    __device__ __forceinline__ bool set(const GfaCfg &c, uint64_t j) {
+        const uint64_t node = c.twins ? 2 * j + 1 : j;
+        const int32_t L = c.len[node];
+        if (L <= 0) return false;
+        h.f[0] = text_field("S\t", j); h.f[1] = text_lit("\t"); t.f[0] = text_field("\tLN:i:", (uint64_t) L);
+        hp = h.bytes() - 1u; seqs = c.seqs; sl = seqs ? (uint32_t) L : 1u;
+        seq.row = c.row(node); seq.q0 = 0;
+        return true;
     }
-    // 16 bases from sequence index q (all inside the sequence) as 4 little-endian words of ASCII
-    __device__ __forceinline__ uint4 bases16(uint32_t q) const {
-        q += q0;
-        const uint32_t w = q >> 4, sh = q & 15;
-        uint32_t codes = row[w];
-        if (sh) codes = (uint32_t) ((((uint64_t) row[w + 1] << 32) | codes) >> (2 * sh));
-        uint32_t o[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++) x |= ((0x54474341u >> (8 * ((codes >> (2 * (4 * k + b))) & 3))) & 0xFFu) << (8 * b);
-            o[k] = x;
-        }
-        return make_uint4(o[0], o[1], o[2], o[3]);
+    __device__ __forceinline__ uint32_t bytes() const { return hp + sl + t.bytes(); }
+    __device__ __forceinline__ char at(uint32_t p) const {
+        if (p < hp) return h.at(p);
+        const uint32_t q = p - hp;
+        if (q < sl) return seqs ? seq.base(q) : '*';
+        return t.at(q - sl);
+    }
+    __device__ __forceinline__ uint32_t packed() const { return seqs ? sl : 0u; }
+    __device__ __forceinline__ uint4 bases16(uint32_t q) const { return seq.bases16(q); }
+};
+
+// `>unitig_<j>_length=<len>` or, of a contig result, `>contig_id=<rank>_length=<len>`, then the window of row j
+struct WindowRecord : FastaRecord<PackedSeq> {
+    __device__ __forceinline__ bool window(const GfaFasta &f, uint64_t j) {
+        const int32_t len = f.len[j];
+        seq.row = f.words + f.row_off[j]; seq.q0 = (uint32_t) f.seq_off[j];
+        L = (uint32_t) len;
+        return len > 0 && len >= f.min_length;
+    }
+};
+struct UnitigRecord : WindowRecord {
+    __device__ __forceinline__ bool set(const GfaFasta &f, uint64_t j) {
+        if (!window(f, j)) return false;
+        head(">unitig_", j, L); seal();
+        return true;
+    }
+};
+struct ContigRecord : WindowRecord {
+    __device__ __forceinline__ bool set(const GfaFasta &f, uint64_t j) {
+        if (!window(f, j)) return false;
+        contig_head(f.rec_rank[j], L); seal();
+        return true;
     }
 };
 
-// one wave per segment item in [i0, i1) (items below n_seg); buf + off[j] - base is the line's first byte
-template <bool CONTIG> __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
+__global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_sizes(GfaCfg c, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    text_sizes_body<SegLine>(c, c.n_seg, sizes, counters);
+}
+// items in [i0, i1) (items below n_seg)
+__global__ void __launch_bounds__(GFA_BLOCK) k_gfa_seg_write(GfaCfg c, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
                                                              char *__restrict__ buf) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t base = off[i0];
-    const uint64_t waves = (uint64_t) gridDim.x * (blockDim.x >> 6);
-    for (uint64_t j = i0 + (uint64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); j < i1; j += waves) {
-        const uint64_t l0 = off[j], l1 = off[j + 1];
-        if (l0 == l1) continue;
-        const uint64_t node = c.twins ? 2 * j + 1 : j;
-        SegLine<CONTIG> s;
-        s.name = CONTIG ? c.rec_rank[j] : j; s.L = c.len[node]; s.wn = dec_width(s.name); s.wl = dec_width((uint64_t) s.L);
-        s.hp = c.fasta ? (CONTIG ? 11 : 8) + s.wn + 8 + s.wl + 1 : 2 + s.wn + 1; s.sl = c.seqs ? (uint32_t) s.L : 1u;
-        s.row = c.row(node); s.seqs = c.seqs;
-        s.fasta = c.fasta; s.q0 = c.fasta ? (uint32_t) c.seq_off[j] : 0u;
-        char *g0 = buf + (l0 - base), *g1 = buf + (l1 - base);
-        char *a0 = (char *) (((uintptr_t) g0 + 15) & ~(uintptr_t) 15), *a1 = (char *) ((uintptr_t) g1 & ~(uintptr_t) 15);
-        if (a0 >= a1) {                                               // no whole aligned block inside the line
-            for (char *p = g0 + lane; p < g1; p += 64) *p = s.at((uint32_t) (p - g0));
-            continue;
-        }
-        if (g0 + lane < a0) g0[lane] = s.at((uint32_t) lane);         // < 16 bytes before the first aligned block, < 16 after the last
-        if (a1 + lane < g1) a1[lane] = s.at((uint32_t) (a1 - g0) + lane);
-        const uint64_t nblk = (uint64_t) (a1 - a0) >> 4;
-        for (uint64_t q = lane; q < nblk; q += 64) {
-            const uint32_t p = (uint32_t) (a0 - g0) + (uint32_t) (q << 4);
-            uint4 v;
-            if (s.seqs && p >= s.hp && p + 16 <= s.hp + s.sl) v = s.bases16(p - s.hp);
-            else {
-                uint32_t o[4];
-                for (int k = 0; k < 4; k++) {
-                    uint32_t x = 0;
-                    for (int b = 0; b < 4; b++) x |= (uint32_t) (uint8_t) s.at(p + 4 * k + b) << (8 * b);
-                    o[k] = x;
-                }
-                v = make_uint4(o[0], o[1], o[2], o[3]);
-            }
-            *reinterpret_cast<uint4 *>(a0 + (q << 4)) = v;
-        }
-    }
+    text_write_body<SegLine>(c, off, i0, i1, buf);
+}
+
+template <class R> __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_fasta_sizes(GfaFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    text_sizes_body<R>(f, f.n, sizes, counters);
+}
+template <class R> __global__ void __launch_bounds__(GFA_BLOCK) k_gfa_fasta_write(GfaFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1,
+                                                                                  char *__restrict__ buf) {
+    text_write_body<R>(f, off, i0, i1, buf);
 }
 
 // one thread per link item in [i0, i1) (items from n_seg on)
@@ -356,14 +294,27 @@ void launch_gfa_format(const GfaCfg &c, const unsigned long long *off, uint64_t 
     const uint64_t s1 = i1 < c.n_seg ? i1 : c.n_seg;
     if (i0 < s1) {
         const uint64_t g = grid_of(s1 - i0, GFA_BLOCK / 64);
-        if (c.fasta && c.rec_rank) hipLaunchKernelGGL(k_gfa_seg_write<true>, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
-        else hipLaunchKernelGGL(k_gfa_seg_write<false>, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
+        hipLaunchKernelGGL(k_gfa_seg_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
     }
     const uint64_t l0 = i0 > c.n_seg ? i0 : c.n_seg;
     if (l0 < i1) {
         // the chunk's bytes start at off[i0]: its link lines are placed relative to that
         hipLaunchKernelGGL(k_gfa_link_write, dim3(grid_of(i1 - l0, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, c, off, i0, l0, i1, buf);
     }
+}
+
+void launch_gfa_fasta_sizes(const GfaFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
+    if (!f.n) return;
+    if (f.rec_rank) hipLaunchKernelGGL(k_gfa_fasta_sizes<ContigRecord>, dim3(grid_of(f.n, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, f, sizes, counters);
+    else hipLaunchKernelGGL(k_gfa_fasta_sizes<UnitigRecord>, dim3(grid_of(f.n, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, f, sizes, counters);
+}
+
+void launch_gfa_fasta_write(const GfaFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
+    if (i0 >= i1) return;
+    const uint64_t g = grid_of(i1 - i0, GFA_BLOCK / 64);
+    const dim3 grid((unsigned) (g < 16384 ? g : 16384));
+    if (f.rec_rank) hipLaunchKernelGGL(k_gfa_fasta_write<ContigRecord>, grid, dim3(GFA_BLOCK), 0, s, f, off, i0, i1, buf);
+    else hipLaunchKernelGGL(k_gfa_fasta_write<UnitigRecord>, grid, dim3(GFA_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -30,7 +30,7 @@
 #include <algorithm>
 
 #include "place_kernels.h"
-#include "gfa_kernels.h"
+#include "text_record.h"
 #include "prefsuf_common.h"
 
 namespace alga {
@@ -40,14 +40,6 @@ namespace {
 constexpr int PL_BLOCK = 256, PL_WAVES = PL_BLOCK / 64;
 constexpr uint8_t PL_ST_PLACED = 1, PL_ST_UNIQUE = 2, PL_ST_MINUS = 4;   // ALGA_PLACE_* of include/alga_amd.h (the bits of d_state)
 constexpr uint8_t PL_V_ACCEPTED = 2;                                   // ALGA_FINAL_ACCEPTED
-
-__device__ __forceinline__ unsigned long long pl_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        v += ((unsigned long long) hi << 32) | lo;
-    }
-    return v;
-}
 
 __device__ __forceinline__ unsigned long long pl_wave_min(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -114,7 +106,7 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_target_check(const int32_t *__r
         sum += (unsigned long long) l;
         if (l >= k) idx += (unsigned long long) (l - k + 1);
     }
-    sum = pl_wave_sum(sum); idx = pl_wave_sum(idx);
+    sum = wave_sum(sum); idx = wave_sum(idx);
     if ((threadIdx.x & 63) == 0) {
         if (sum) atomicAdd(&counters[PL_COLUMNS], sum);
         if (idx) atomicAdd(&counters[PL_INDEX_POS], idx);
@@ -169,7 +161,7 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_dir(const unsigned long long *_
         for (uint32_t b = lo; b <= hi && b <= n_buckets; b++) dir[b] = (uint32_t) j;
         head = j < n && (j == 0 || keys[j - 1] != keys[j]) ? 1ull : 0ull;
     }
-    head = pl_wave_sum(head);
+    head = wave_sum(head);
     if ((threadIdx.x & 63) == 0 && head) atomicAdd(&counters[PL_DISTINCT], head);
 }
 
@@ -269,7 +261,7 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_place(PlReads rd, PlTargets t, 
         uint8_t mm8 = 0, hits8 = 0, st8 = 0;
         if (win != ~0ull) {
             const uint32_t bmm = (uint32_t) (win >> 33), gp = (uint32_t) (win >> 1);
-            const unsigned long long hits = pl_wave_sum(lane_mm == bmm ? (unsigned long long) lane_cnt : 0ull);
+            const unsigned long long hits = wave_sum(lane_mm == bmm ? (unsigned long long) lane_cnt : 0ull);
             const uint32_t tt = pl_target_of(t.col_off, t.T, gp);
             tg = (int32_t) tt; ps = (int32_t) (gp - t.col_off[tt]); mm8 = (uint8_t) bmm; hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
             st8 = (uint8_t) (PL_ST_PLACED | (hits == 1ull ? PL_ST_UNIQUE : 0) | ((win & 1ull) ? PL_ST_MINUS : 0));
@@ -333,8 +325,8 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_pairs(PlReads rd, const uint8_t
         if (a <= b && a + la <= b + lb && ins <= (long long) max_insert) { n_proper++; sum += (unsigned long long) ins; atomicAdd(&hist[ins], 1ull); }
         else n_improper++;
     }
-    n_pairs = pl_wave_sum(n_pairs); n_proper = pl_wave_sum(n_proper); n_improper = pl_wave_sum(n_improper); n_split = pl_wave_sum(n_split);
-    n_nu = pl_wave_sum(n_nu); sum = pl_wave_sum(sum);
+    n_pairs = wave_sum(n_pairs); n_proper = wave_sum(n_proper); n_improper = wave_sum(n_improper); n_split = wave_sum(n_split);
+    n_nu = wave_sum(n_nu); sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0 && n_pairs) {
         atomicAdd(&counters[PL_PAIRS], n_pairs);
         if (n_proper) { atomicAdd(&counters[PL_PROPER], n_proper); atomicAdd(&counters[PL_INSERT_SUM], sum); }
@@ -345,93 +337,23 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_pairs(PlReads rd, const uint8_t
 }
 
 // ---- FASTA with depth headers ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int pl_dec_width(unsigned long long v) {
-    int w = 1;
-    while (v >= 10ull) { v /= 10ull; w++; }
-    return w;
-}
-
 // `>contig_id=<id>_length=<L>_reads=<n>_depth=<q>.<dd>\n<window>\n`
-struct PlRecord {
-    unsigned long long id, L, reads, q, dd;
-    int w_id, w_len, w_reads, w_q;
-    uint32_t hp;                      // bytes before the sequence
-    const uint32_t *row; uint32_t q0;
-    __device__ void set(const PlFasta &f, uint64_t j) {
+struct PlRecord : FastaRecord<PackedSeq> {
+    static constexpr bool kAligned = false;
+    __device__ __forceinline__ bool set(const PlFasta &f, uint64_t j) {
         const uint32_t k = (uint32_t) f.order[j];
-        id = j; L = (unsigned long long) f.len[k]; reads = f.t_reads[j];
-        const unsigned long long bases = f.t_bases[j];
-        q = bases / L; dd = ((bases % L) * 100ull) / L;                        // floor(100 * bases / L) = 100 q + dd without a product above 2^64
-        w_id = pl_dec_width(id); w_len = pl_dec_width(L); w_reads = pl_dec_width(reads); w_q = pl_dec_width(q);
-        hp = 11u + w_id + 8u + w_len + 7u + w_reads + 7u + w_q + 3u + 1u;
-        row = f.words + f.word_off[k]; q0 = (uint32_t) f.begin[k];
-    }
-    __device__ static char digit(unsigned long long v, int w, int d) {
-        for (int i = w - 1 - d; i > 0; i--) v /= 10ull;
-        return (char) ('0' + (int) (v % 10ull));
-    }
-    __device__ char at(uint32_t p) const {
-        if (p >= hp) {
-            const uint32_t s = p - hp;
-            if (s >= L) return '\n';
-            const uint32_t c = s + q0;
-            return (char) ((0x54474341u >> (8 * ((row[c >> 4] >> (2 * (c & 15))) & 3))) & 0xFF);
-        }
-        uint32_t at0 = 0;
-        if (p < 11u) return ">contig_id="[p];
-        at0 = 11u;
-        if (p < at0 + w_id) return digit(id, w_id, (int) (p - at0));
-        at0 += w_id;
-        if (p < at0 + 8u) return "_length="[p - at0];
-        at0 += 8u;
-        if (p < at0 + w_len) return digit(L, w_len, (int) (p - at0));
-        at0 += w_len;
-        if (p < at0 + 7u) return "_reads="[p - at0];
-        at0 += 7u;
-        if (p < at0 + w_reads) return digit(reads, w_reads, (int) (p - at0));
-        at0 += w_reads;
-        if (p < at0 + 7u) return "_depth="[p - at0];
-        at0 += 7u;
-        if (p < at0 + w_q) return digit(q, w_q, (int) (p - at0));
-        at0 += w_q;
-        if (p == at0) return '.';
-        if (p < at0 + 3u) return digit(dd, 2, (int) (p - at0 - 1u));
-        return '\n';
+        if (f.verdict[k] != PL_V_ACCEPTED) return false;
+        contig_head(j, (uint32_t) f.len[k]); depth(f.t_reads[j], f.t_bases[j]); seal();
+        seq.row = f.words + f.word_off[k]; seq.q0 = (uint32_t) f.begin[k];
+        return true;
     }
 };
 
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_fasta_sizes(PlFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
-    const uint64_t j = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x;
-    unsigned long long live = 0, bytes = 0;
-    if (j < f.n) {
-        if (f.verdict[(uint32_t) f.order[j]] == PL_V_ACCEPTED) {
-            PlRecord s;
-            s.set(f, j);
-            bytes = (unsigned long long) s.hp + s.L + 1ull;
-            live = 1;
-        }
-        sizes[j] = (uint32_t) bytes;
-    }
-    live = pl_wave_sum(live);
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long w = (unsigned long long) (uint32_t) __shfl_xor((int) (uint32_t) bytes, o); bytes = w > bytes ? w : bytes; }
-    if ((threadIdx.x & 63) == 0 && live) {
-        atomicAdd(&counters[GFA_SEGMENTS], live);
-        atomicMax(&counters[GFA_MAX_LINE], bytes);
-    }
+    text_sizes_body<PlRecord>(f, f.n, sizes, counters);
 }
-
-// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_fasta_write(PlFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1, char *__restrict__ buf) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t base = off[i0], waves = (uint64_t) gridDim.x * PL_WAVES;
-    for (uint64_t j = i0 + (uint64_t) blockIdx.x * PL_WAVES + (threadIdx.x >> 6); j < i1; j += waves) {
-        const uint64_t l0 = off[j], l1 = off[j + 1];
-        if (l0 == l1) continue;
-        PlRecord s;
-        s.set(f, j);
-        char *g0 = buf + (l0 - base);
-        for (uint64_t p = (uint64_t) lane; p < l1 - l0; p += 64) g0[p] = s.at((uint32_t) p);
-    }
+    text_write_body<PlRecord>(f, off, i0, i1, buf);
 }
 
 inline unsigned pl_grid(uint64_t items, uint64_t cap = 1u << 16) {

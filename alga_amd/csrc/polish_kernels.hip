@@ -25,7 +25,7 @@
 #include <algorithm>
 
 #include "polish_kernels.h"
-#include "gfa_kernels.h"
+#include "text_record.h"
 
 namespace alga {
 
@@ -35,13 +35,6 @@ constexpr int PO_BLOCK = 256, PO_WAVES = PO_BLOCK / 64;
 constexpr uint8_t PO_ST_MINUS = 4;                                      // ALGA_PLACE_MINUS
 constexpr uint8_t PO_V_ACCEPTED = 2;                                    // ALGA_FINAL_ACCEPTED
 
-__device__ __forceinline__ unsigned long long po_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        v += ((unsigned long long) hi << 32) | lo;
-    }
-    return v;
-}
 __device__ __forceinline__ uint32_t po_wave_sum32(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v += (uint32_t) __shfl_xor((int) v, o);
     return v;
@@ -79,7 +72,7 @@ __global__ void __launch_bounds__(PO_BLOCK) k_po_check(PoReads r, PoTargets t, u
         voters++; votes += (unsigned long long) L;
         mx = (uint32_t) L > mx ? (uint32_t) L : mx;
     }
-    voters = po_wave_sum(voters); votes = po_wave_sum(votes); mx = po_wave_max(mx); bad = po_wave_or(bad);
+    voters = wave_sum(voters); votes = wave_sum(votes); mx = po_wave_max(mx); bad = po_wave_or(bad);
     if ((threadIdx.x & 63) == 0) {
         if (voters) { atomicAdd(&counters[PO_VOTERS], voters); atomicAdd(&counters[PO_VOTES], votes); atomicMax(&counters[PO_MAX_LEN], (unsigned long long) mx); }
         if (bad) atomicOr(&counters[PO_BAD], (unsigned long long) bad);
@@ -294,102 +287,25 @@ __global__ void __launch_bounds__(PO_BLOCK) k_po_changes(PoTargets t, const uint
 }
 
 // ---- FASTA of the polished sequences ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int po_dec_width(unsigned long long v) {
-    int w = 1;
-    while (v >= 10ull) { v /= 10ull; w++; }
-    return w;
-}
-
 // `>contig_id=<id>_length=<L>[_reads=<n>_depth=<q>.<dd>]\n<columns col_off[id] .. col_off[id + 1])>\n`
-struct PoRecord {
-    unsigned long long id, L, reads, q, dd;
-    int w_id, w_len, w_reads, w_q;
-    uint32_t hp, c0;                  // bytes before the sequence, its first column
-    bool depth;
-    const uint32_t *words;
-    __device__ void set(const PoFasta &f, uint64_t j) {
-        id = j; c0 = f.col_off[j]; L = (unsigned long long) (f.col_off[j + 1] - c0); words = f.words; depth = f.depth != 0;
-        w_id = po_dec_width(id); w_len = po_dec_width(L);
-        hp = 11u + w_id + 8u + w_len + 1u;
-        reads = q = dd = 0; w_reads = w_q = 0;
-        if (depth) {
-            reads = f.t_reads[j];
-            const unsigned long long bases = f.t_bases[j];
-            q = bases / L; dd = ((bases % L) * 100ull) / L;
-            w_reads = po_dec_width(reads); w_q = po_dec_width(q);
-            hp += 7u + w_reads + 7u + w_q + 3u;
-        }
-    }
-    __device__ static char digit(unsigned long long v, int w, int d) {
-        for (int i = w - 1 - d; i > 0; i--) v /= 10ull;
-        return (char) ('0' + (int) (v % 10ull));
-    }
-    __device__ char at(uint32_t p) const {
-        if (p >= hp) {
-            const uint32_t s = p - hp;
-            if (s >= L) return '\n';
-            const uint32_t c = s + c0;
-            return (char) ((0x54474341u >> (8 * ((words[c >> 4] >> (2 * (c & 15))) & 3))) & 0xFF);
-        }
-        if (p < 11u) return ">contig_id="[p];
-        uint32_t at0 = 11u;
-        if (p < at0 + w_id) return digit(id, w_id, (int) (p - at0));
-        at0 += w_id;
-        if (p < at0 + 8u) return "_length="[p - at0];
-        at0 += 8u;
-        if (p < at0 + w_len) return digit(L, w_len, (int) (p - at0));
-        at0 += w_len;
-        if (!depth) return '\n';
-        if (p < at0 + 7u) return "_reads="[p - at0];
-        at0 += 7u;
-        if (p < at0 + w_reads) return digit(reads, w_reads, (int) (p - at0));
-        at0 += w_reads;
-        if (p < at0 + 7u) return "_depth="[p - at0];
-        at0 += 7u;
-        if (p < at0 + w_q) return digit(q, w_q, (int) (p - at0));
-        at0 += w_q;
-        if (p == at0) return '.';
-        if (p < at0 + 3u) return digit(dd, 2, (int) (p - at0 - 1u));
-        return '\n';
+struct PoRecord : FastaRecord<PackedSeq> {
+    static constexpr bool kAligned = false;
+    __device__ __forceinline__ bool set(const PoFasta &f, uint64_t j) {
+        const uint32_t c0 = f.col_off[j], len = f.col_off[j + 1] - c0;
+        if (f.verdict[(uint32_t) f.order[j]] != PO_V_ACCEPTED || !len) return false;
+        contig_head(j, len);
+        if (f.depth) depth(f.t_reads[j], f.t_bases[j]);
+        seal();
+        seq.row = f.words; seq.q0 = c0;
+        return true;
     }
 };
 
-__device__ __forceinline__ bool po_live(const PoFasta &f, uint64_t j) {
-    return f.verdict[(uint32_t) f.order[j]] == PO_V_ACCEPTED && f.col_off[j + 1] > f.col_off[j];
-}
-
 __global__ void __launch_bounds__(PO_BLOCK) k_po_fasta_sizes(PoFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
-    const uint64_t j = (uint64_t) blockIdx.x * PO_BLOCK + threadIdx.x;
-    unsigned long long live = 0, bytes = 0;
-    if (j < f.n) {
-        if (po_live(f, j)) {
-            PoRecord s;
-            s.set(f, j);
-            bytes = (unsigned long long) s.hp + s.L + 1ull;
-            live = 1;
-        }
-        sizes[j] = (uint32_t) bytes;
-    }
-    live = po_wave_sum(live);
-    bytes = (unsigned long long) po_wave_max((uint32_t) bytes);
-    if ((threadIdx.x & 63) == 0 && live) {
-        atomicAdd(&counters[GFA_SEGMENTS], live);
-        atomicMax(&counters[GFA_MAX_LINE], bytes);
-    }
+    text_sizes_body<PoRecord>(f, f.n, sizes, counters);
 }
-
-// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
 __global__ void __launch_bounds__(PO_BLOCK) k_po_fasta_write(PoFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1, char *__restrict__ buf) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t base = off[i0], waves = (uint64_t) gridDim.x * PO_WAVES;
-    for (uint64_t j = i0 + (uint64_t) blockIdx.x * PO_WAVES + (threadIdx.x >> 6); j < i1; j += waves) {
-        const uint64_t l0 = off[j], l1 = off[j + 1];
-        if (l0 == l1) continue;
-        PoRecord s;
-        s.set(f, j);
-        char *g0 = buf + (l0 - base);
-        for (uint64_t p = (uint64_t) lane; p < l1 - l0; p += 64) g0[p] = s.at((uint32_t) p);
-    }
+    text_write_body<PoRecord>(f, off, i0, i1, buf);
 }
 
 inline unsigned po_grid(uint64_t items, uint64_t cap = 1u << 16) {

@@ -23,7 +23,7 @@
 #include <algorithm>
 
 #include "scaffold_kernels.h"
-#include "gfa_kernels.h"
+#include "text_record.h"
 
 namespace alga {
 
@@ -32,21 +32,6 @@ namespace {
 constexpr int SC_BLOCK = 256, SC_WAVES = SC_BLOCK / 64;
 constexpr uint8_t SC_ST_UNIQUE = 2, SC_ST_MINUS = 4;                    // ALGA_PLACE_UNIQUE, ALGA_PLACE_MINUS
 
-__device__ __forceinline__ unsigned long long sc_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        v += ((unsigned long long) hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned long long sc_wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
-        v = w > v ? w : v;
-    }
-    return v;
-}
 __device__ __forceinline__ uint32_t sc_wave_or(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v |= (uint32_t) __shfl_xor((int) v, o);
     return v;
@@ -100,7 +85,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_links(ScReads r, ScTargets t, i
         }
         keys[i] = key; vals[i] = (uint32_t) i; span[i] = sp;
     }
-    n_split = sc_wave_sum(n_split); n_links = sc_wave_sum(n_links); n_far = sc_wave_sum(n_far);
+    n_split = wave_sum(n_split); n_links = wave_sum(n_links); n_far = wave_sum(n_far);
     if ((threadIdx.x & 63) == 0 && n_split) {
         atomicAdd(&counters[SC_SPLIT], n_split);
         if (n_links) atomicAdd(&counters[SC_LINKS], n_links);
@@ -115,7 +100,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_heads(const unsigned long long 
         const uint32_t h = i == 0 || keys[i] != keys[i - 1];
         heads[i] = h; n += h;
     }
-    n = sc_wave_sum(n);
+    n = wave_sum(n);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[SC_BUNDLES], n);
 }
 
@@ -138,7 +123,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_bundle_fill(const uint32_t *__r
         }
         const uint32_t bid0 = (uint32_t) __shfl((int) bid, 0);            // lane 0 is active wherever a lane of the pass is
         if (__all(!active || bid == bid0)) {
-            sp = sc_wave_sum(sp);
+            sp = wave_sum(sp);
             if (lane == 0) atomicAdd(&b_span[bid0], sp);
         } else if (active) atomicAdd(&b_span[bid], sp);
     }
@@ -161,7 +146,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_bundles(const unsigned long lon
             atomicMax(&best[eb], ((unsigned long long) n << 32) | (uint32_t) ~ea);
         }
     }
-    n_sup = sc_wave_sum(n_sup);
+    n_sup = wave_sum(n_sup);
     if ((threadIdx.x & 63) == 0 && n_sup) atomicAdd(&counters[SC_SUPPORTED], n_sup);
 }
 
@@ -191,7 +176,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_choice(const unsigned long long
         }
         choice[x] = ch; end_state[x] = st;
     }
-    n_amb = sc_wave_sum(n_amb);
+    n_amb = wave_sum(n_amb);
     if ((threadIdx.x & 63) == 0 && n_amb) atomicAdd(&counters[SC_AMBIGUOUS], n_amb);
 }
 
@@ -234,7 +219,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_drop(ScLists l, uint32_t 
         b_state[join_bundle[2 * c]] = SC_B_SUPPORTED | SC_B_JOIN | SC_B_DROPPED;
         n++;
     }
-    n = sc_wave_sum(n);
+    n = wave_sum(n);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[SC_DROPPED], n);
 }
 
@@ -294,7 +279,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_place(ScTargets t, ScLists l, c
         n_joins += joined;
         head[c] = hx >> 1; first[c] = rank == 0; members[c] = rank == 0 ? m : 0u;
     }
-    n_joins = sc_wave_sum(n_joins);
+    n_joins = wave_sum(n_joins);
     if ((threadIdx.x & 63) == 0 && n_joins) atomicAdd(&counters[SC_JOINS], n_joins);
 }
 
@@ -316,7 +301,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_layout(ScTargets t, ScLists l, 
             longest = bases > longest ? bases : longest;
         }
     }
-    n_sc = sc_wave_sum(n_sc); n_multi = sc_wave_sum(n_multi); n_mem = sc_wave_sum(n_mem); longest = sc_wave_max(longest);
+    n_sc = wave_sum(n_sc); n_multi = wave_sum(n_multi); n_mem = wave_sum(n_mem); longest = wave_max(longest);
     if ((threadIdx.x & 63) == 0 && n_sc) {
         atomicAdd(&counters[SC_SCAFFOLDS], n_sc); atomicAdd(&counters[SC_MEMBERS], n_mem); atomicMax(&counters[SC_LONGEST], longest);
         if (n_multi) atomicAdd(&counters[SC_MULTI], n_multi);
@@ -324,92 +309,46 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_layout(ScTargets t, ScLists l, 
 }
 
 // ---- FASTA of the scaffolds ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int sc_dec_width(unsigned long long v) {
-    int w = 1;
-    while (v >= 10ull) { v /= 10ull; w++; }
-    return w;
-}
-
-// `>scaffold_id=<j>_length=<s_len>_contigs=<m>\n<sequence>\n`
-struct ScRecord {
-    unsigned long long id, L, m;
-    int w_id, w_len, w_m;
-    uint32_t hp;                      // bytes before the sequence
+// the sequence of a scaffold: its contigs in their orientation, `N` between them
+struct ScSeq {
+    static constexpr bool kPacked = false;
+    uint32_t m;
     const int32_t *mem;               // the scaffold's contigs
     const unsigned long long *start;
     const uint32_t *col_off, *words;
     const uint8_t *orient;
-    __device__ void set(const ScFasta &ff, uint64_t j) {
-        start = ff.start; col_off = ff.col_off; words = ff.words; orient = ff.orient; id = j; L = ff.s_len[j]; m = ff.s_off[j + 1] - ff.s_off[j]; mem = ff.s_members + ff.s_off[j];
-        w_id = sc_dec_width(id); w_len = sc_dec_width(L); w_m = sc_dec_width(m);
-        hp = 13u + w_id + 8u + w_len + 9u + w_m + 1u;
-    }
-    __device__ static char digit(unsigned long long v, int w, int d) {
-        for (int i = w - 1 - d; i > 0; i--) v /= 10ull;
-        return (char) ('0' + (int) (v % 10ull));
-    }
-    __device__ char at(uint64_t p) const {
-        if (p >= hp) {
-            const unsigned long long q = p - hp;
-            if (q >= L) return '\n';
-            uint32_t lo = 0, hi = (uint32_t) m;                                 // the last member that starts at or before q
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (start[mem[mid]] <= q) lo = mid; else hi = mid;
-            }
-            const uint32_t c = (uint32_t) mem[lo], c0 = col_off[c], len = col_off[c + 1] - c0;
-            const unsigned long long k = q - start[c];
-            if (k >= len) return 'N';
-            const bool minus = orient[c] != 0;
-            const uint32_t g = minus ? c0 + len - 1u - (uint32_t) k : c0 + (uint32_t) k;
-            const uint32_t code = (words[g >> 4] >> (2 * (g & 15))) & 3u;
-            return (char) ((0x54474341u >> (8 * (minus ? 3u - code : code))) & 0xFF);
+    __device__ char base(uint32_t q) const {
+        uint32_t lo = 0, hi = m;                                            // the last member that starts at or before q
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (start[mem[mid]] <= q) lo = mid; else hi = mid;
         }
-        if (p < 13u) return ">scaffold_id="[p];
-        uint32_t at0 = 13u;
-        if (p < at0 + w_id) return digit(id, w_id, (int) (p - at0));
-        at0 += w_id;
-        if (p < at0 + 8u) return "_length="[p - at0];
-        at0 += 8u;
-        if (p < at0 + w_len) return digit(L, w_len, (int) (p - at0));
-        at0 += w_len;
-        if (p < at0 + 9u) return "_contigs="[p - at0];
-        at0 += 9u;
-        if (p < at0 + w_m) return digit(m, w_m, (int) (p - at0));
-        return '\n';
+        const uint32_t c = (uint32_t) mem[lo], c0 = col_off[c], len = col_off[c + 1] - c0;
+        const unsigned long long k = q - start[c];
+        if (k >= len) return 'N';
+        const bool minus = orient[c] != 0;
+        const uint32_t g = minus ? c0 + len - 1u - (uint32_t) k : c0 + (uint32_t) k;
+        const uint32_t code = (words[g >> 4] >> (2 * (g & 15))) & 3u;
+        return (char) ((0x54474341u >> (8 * (minus ? 3u - code : code))) & 0xFF);
+    }
+};
+
+// `>scaffold_id=<j>_length=<s_len>_contigs=<m>\n<sequence>\n`
+struct ScRecord : FastaRecord<ScSeq> {
+    static constexpr bool kAligned = false;
+    __device__ __forceinline__ bool set(const ScFasta &f, uint64_t j) {
+        seq.m = f.s_off[j + 1] - f.s_off[j]; seq.mem = f.s_members + f.s_off[j];
+        seq.start = f.start; seq.col_off = f.col_off; seq.words = f.words; seq.orient = f.orient;
+        head(">scaffold_id=", j, (uint32_t) f.s_len[j]); h.f[2] = text_field("_contigs=", seq.m); seal();
+        return true;
     }
 };
 
 __global__ void __launch_bounds__(SC_BLOCK) k_sc_fasta_sizes(ScFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
-    const uint64_t j = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x;
-    unsigned long long live = 0, bytes = 0;
-    if (j < f.n) {
-        ScRecord s;
-        s.set(f, j);
-        bytes = (unsigned long long) s.hp + s.L + 1ull;
-        live = 1;
-        sizes[j] = (uint32_t) bytes;
-    }
-    live = sc_wave_sum(live);
-    bytes = sc_wave_max(bytes);
-    if ((threadIdx.x & 63) == 0 && live) {
-        atomicAdd(&counters[GFA_SEGMENTS], live);
-        atomicMax(&counters[GFA_MAX_LINE], bytes);
-    }
+    text_sizes_body<ScRecord>(f, f.n, sizes, counters);
 }
-
-// one wave per record in [i0, i1); buf + off[j] - off[i0] is the record's first byte
 __global__ void __launch_bounds__(SC_BLOCK) k_sc_fasta_write(ScFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1, char *__restrict__ buf) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t base = off[i0], waves = (uint64_t) gridDim.x * SC_WAVES;
-    for (uint64_t j = i0 + (uint64_t) blockIdx.x * SC_WAVES + (threadIdx.x >> 6); j < i1; j += waves) {
-        const uint64_t l0 = off[j], l1 = off[j + 1];
-        if (l0 == l1) continue;
-        ScRecord s;
-        s.set(f, j);
-        char *g0 = buf + (l0 - base);
-        for (uint64_t p = (uint64_t) lane; p < l1 - l0; p += 64) g0[p] = s.at(p);
-    }
+    text_write_body<ScRecord>(f, off, i0, i1, buf);
 }
 
 inline unsigned sc_grid(uint64_t items, uint64_t cap = 8192) {
