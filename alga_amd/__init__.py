@@ -6,4 +6,5 @@ the tests, bench.py and the multi-GPU driver; torch supplies device memory, stre
 torch.distributed only.  There is no CPU fallback: importing works anywhere, computing needs the GPU.
 """
 from .engine import (Engine, MultiEngine, AlgaError, PrefSufParams, load_library, library_path, pack_reads, derive_params, ingest_files, parse_files,  # noqa: F401
-                     EDGE_DTYPE, PolishParams, PolishInfo, PolishedC, Polished, ScaffoldParams, ScaffoldInfo, ScaffoldsC, Scaffolds)
+                     EDGE_DTYPE, PolishParams, PolishInfo, PolishedC, Polished, ScaffoldParams, ScaffoldInfo, ScaffoldsC, Scaffolds,
+                     BreakParams, BreakInfo, BrokenC, Broken)

@@ -179,6 +179,7 @@ struct alga_engine {
     DevBuf      pl_target, pl_pos, pl_mm, pl_hits, pl_state, pl_coloff, pl_cover, pl_tstat, pl_hist;
     bool        pl_valid = false;                  // the result buffers hold a placement
     uint64_t    pl_targets = 0, pl_reads = 0;      // ... of this many reads on this many targets
+    uint64_t    pl_ncolumns = 0, pl_nhist = 0;      // ... its col_off[pl_targets] and the bins of its insert histogram (max_insert + 1)
     uint64_t    pl_final_epoch = 0;                // ... made on the final result of this epoch (0: on caller's targets)
     uint64_t    fc_epoch = 0;                      // counts the alga_final_contigs_device calls that wrote a result
     int         opt_place_dir_bits = 0;            // option "place_dir_bits": bits of the placement index's directory, 0 = about two positions per bucket
@@ -201,6 +202,13 @@ struct alga_engine {
     bool        sc_valid = false;                  // the result buffers hold scaffolds
     uint64_t    sc_targets = 0, sc_scaffolds = 0, sc_longest = 0;   // ... of this many targets, this many of them, the longest with its gaps
     uint64_t    sc_pl_serial = 0;                  // ... made from this placement result
+    // contigs broken where no proper pair spans them (engine_break.hip).  Workspaces: counters, the difference array, the run starts and their
+    // scan, the marks per column, first / last / closed per run and the scan of the closed ones.  The result: the span (entry g + 1 of the scan
+    // of the differences), the cuts, the cuts per target, the piece arrays, the result's own copy of the bases
+    DevBuf      br_cnt, br_diff, br_starts, br_rpos, br_marks, br_rfirst, br_rlast, br_closed, br_cpos;
+    DevBuf      br_span, br_ccols, br_cfirst, br_clast, br_tcuts, br_poff, br_begin, br_len, br_ptarget, br_pstart, br_words;
+    bool        br_valid = false;                  // the result buffers hold a break result
+    uint64_t    br_targets = 0, br_pieces = 0, br_cuts = 0, br_columns = 0, br_longest = 0;   // ... of this many targets, pieces, cuts, columns; the longest piece
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

@@ -143,7 +143,7 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     HIP_TRY(e, hipMemcpyAsync(h.data(), hist, n_hist * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
 
-    e->pl_valid = true; e->pl_targets = T; e->pl_reads = R; e->pl_final_epoch = final_epoch;
+    e->pl_valid = true; e->pl_targets = T; e->pl_reads = R; e->pl_ncolumns = columns; e->pl_nhist = n_hist; e->pl_final_epoch = final_epoch;
     out->n_reads = (int64_t) R; out->n_targets = (int64_t) T; out->n_columns = columns; out->n_hist = (int64_t) n_hist;
     out->d_target = po.target; out->d_pos = po.pos; out->d_mm = po.mm; out->d_hits = po.hits; out->d_state = po.state;
     out->d_col_off = col_off; out->d_cover = scan + 1;

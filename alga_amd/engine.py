@@ -180,7 +180,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_correct_default_params", "alga_correct_reads_device", "alga_correct_parsed_reads", "alga_ingest_corrected_device",
            "alga_place_default_params", "alga_place_reads_device", "alga_place_reads_on_final_device", "alga_write_final_fasta_depth_device",
            "alga_polish_default_params", "alga_polish_placed_device", "alga_write_polished_fasta_device",
-           "alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device"]
+           "alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device",
+           "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -572,6 +573,71 @@ def layout_tsv(h, tlen=None):
     return "".join(lines)
 
 
+class BreakParams(C.Structure):
+    """alga_break_params"""
+    _fields_ = [(k, C.c_int32) for k in ("min_span", "inset", "margin", "flags")] + [("reserved", C.c_int32 * 4)]
+
+
+class BreakInfo(C.Structure):
+    """alga_break_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("pairs_proper", "pairs_spanning", "candidate_columns", "weak_columns", "runs", "runs_open", "cuts", "targets_cut", "pieces",
+                                          "max_span", "longest_piece", "n50_targets", "n50_pieces")] + \
+               [(k, C.c_double) for k in ("ms_span", "ms_cut", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BrokenC(C.Structure):
+    """alga_broken"""
+    _fields_ = [(k, C.c_int64) for k in ("n_targets", "n_pieces", "n_cuts")] + [("n_columns", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_span", "d_cut_cols", "d_cut_first", "d_cut_last", "d_t_cuts", "d_piece_off", "d_begin", "d_len", "d_piece_target",
+                                          "d_piece_start", "d_words")]
+
+
+class Broken:
+    """Result of Engine.break_contigs: zero-copy torch views of the engine's device memory (valid until the next Engine.break_contigs call on
+    that engine; clone what has to live longer) -- span int32 [n_columns] (the bits of uint32), cut_cols / cut_first / cut_last int32 [n_cuts]
+    (column space), t_cuts int32 [n_targets], piece_off int32 [n_pieces + 1], begin int64, len int32, piece_target int32, piece_start int32
+    [n_pieces], words int32 [(n_columns + 15) / 16 + 2] (the result's own copy of the bases) -- and .info (dict of alga_break_info)."""
+    KEYS = (("span", "<i4", np.uint32, "c"), ("cut_cols", "<i4", np.uint32, "k"), ("cut_first", "<i4", np.uint32, "k"), ("cut_last", "<i4", np.uint32, "k"),
+            ("t_cuts", "<i4", np.uint32, "t"), ("piece_off", "<i4", np.uint32, "p1"), ("begin", "<i8", np.uint64, "p"), ("len", "<i4", np.int32, "p"),
+            ("piece_target", "<i4", np.int32, "p"), ("piece_start", "<i4", np.uint32, "p"), ("words", "<i4", np.uint32, "w"))
+
+    def __init__(self, c, info, device, placements=None):
+        self._c, self.info, self._placements = c, info, placements
+        self.n_targets, self.n_pieces, self.n_cuts, self.n_columns = int(c.n_targets), int(c.n_pieces), int(c.n_cuts), int(c.n_columns)
+        dev = "cuda:%d" % device
+        size = dict(c=self.n_columns, k=self.n_cuts, t=self.n_targets, p1=self.n_pieces + 1, p=self.n_pieces, w=(self.n_columns + 15) // 16 + 2)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/break_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+    def targets(self):
+        """(words, begin int64 [n_pieces], len int32 [n_pieces]): the pieces as the ragged target set Engine.place_reads(targets=...) takes;
+        piece j is target j of that placement (the tensors are the engine's)"""
+        return self.words, self.begin, self.len
+
+    def cuts_tsv(self, host=None):
+        """one line per cut: contig, cut, run_first, run_last (tabs) in target-local columns; the text alga_hip --break_cuts= writes"""
+        return cuts_tsv(host if host is not None else self.to_host())
+
+
+def cuts_tsv(h):
+    """the cuts of a break result read back (Broken.to_host()): the piece behind cut i is the i-th piece that starts inside its target"""
+    lines = []
+    behind = np.nonzero(np.asarray(h["piece_start"]) > 0)[0]
+    for i, j in enumerate(behind):
+        base = int(h["piece_off"][j]) - int(h["piece_start"][j])
+        lines.append("%d\t%d\t%d\t%d\n" % (int(h["piece_target"][j]), int(h["cut_cols"][i]) - base, int(h["cut_first"][i]) - base, int(h["cut_last"][i]) - base))
+    return "".join(lines)
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -719,6 +785,11 @@ def load_library():
     lib.alga_scaffold_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.POINTER(PlacementsC), C.POINTER(ScaffoldParams), C.c_void_p,
                                                 C.POINTER(ScaffoldsC), C.POINTER(ScaffoldInfo)]
     lib.alga_write_scaffold_fasta_device.argtypes = [C.c_void_p, C.POINTER(PlacementsC), C.POINTER(ScaffoldsC), C.POINTER(PolishedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_break_default_params.argtypes = [C.POINTER(BreakParams)]
+    lib.alga_break_default_params.restype = None
+    lib.alga_break_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.POINTER(PlacementsC), C.POINTER(PolishedC), C.POINTER(BreakParams), C.c_void_p,
+                                             C.POINTER(BrokenC), C.POINTER(BreakInfo)]
+    lib.alga_write_broken_fasta_device.argtypes = [C.c_void_p, C.POINTER(BrokenC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1691,6 +1762,48 @@ class Engine:
         info = GfaInfo()
         self._check(self._lib.alga_write_scaffold_fasta_device(self._h, C.byref(placements._c), C.byref(scaffolds._c),
                                                                C.byref(polished._c) if polished is not None else None, os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    def break_contigs(self, words, lens, pair_off, placements, polished=None, margin=None, min_span=1, inset=21, stream=None):
+        """The placed targets cut where no proper pair spans them (alga_break_placed_device) -> Broken.  words / lens / pair_off: the node set
+        that was placed and its pairing (None: no pairs, nothing is cut); placements: the result of the LAST Engine.place_reads call; polished:
+        the result of the LAST Engine.polish of those placements -- the pieces then carry the polished bases.  A pair spans the columns from
+        inset behind its first to inset before its last; a stretch of columns spanned by fewer than min_span pairs, at least margin columns
+        from both ends of its target and with spanned columns on both sides, is cut in its middle.  margin: by default the placement's
+        insert_median (refused where that is -1: no proper pair was seen)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if margin is None:
+            margin = int(placements.info["insert_median"])
+            if margin < 0:
+                raise AlgaError(-1, "Engine.break_contigs: the placement saw no proper pair (insert_median -1): give margin")
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if pair_off is not None:
+            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = BreakParams(), BrokenC(), BreakInfo()
+        pp.min_span, pp.inset, pp.margin = int(min_span), int(inset), int(margin)
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_break_placed_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(placements._c),
+                                                       C.byref(polished._c) if polished is not None else None, C.byref(pp), st, C.byref(out), C.byref(info)))
+        return Broken(out, info.as_dict(), self.device, placements)
+
+    def write_broken_fasta(self, path, broken):
+        """The pieces of the LAST Engine.break_contigs call as FASTA (alga_write_broken_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>contig_id=<j>_length=<len>_from=<t>_start=<s>` per piece with a length, j the piece id."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_broken_fasta_device(self._h, C.byref(broken._c), os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

@@ -73,6 +73,14 @@
 // `scaffold rank contig orient(+/-) start length gap_after links` per member contig, tab separated.  One line on stderr gives links / bundles
 // supported / joins / scaffolds / N50 of the contigs -> N50 of the scaffolds.  Without a proper pair (no median) the scaffolding is skipped with a
 // message and every contig is its own scaffold in the FASTA.  None is passed through.
+// --break_misjoins=1 (default 0; needs --contigs_final= and --file2=; implies the placement): the final contigs are cut where no proper pair spans
+// them (alga_break_placed_device: --break_min_span= (1), --break_inset= (21), --break_margin= (the placement's median insert)).  --broken=PATH: the
+// pieces as FASTA, `>contig_id=<j>_length=<len>_from=<t>_start=<s>` (alga_write_broken_fasta_device); --break_cuts=PATH: one line
+// `contig cut run_first run_last` per cut, tab separated, in the contig's own columns (both need --break_misjoins=1).  One line on stderr gives
+// proper and spanning pairs, weak columns, runs with the open ones, cuts, contigs cut, pieces, N50 of the contigs -> N50 of the pieces.  With
+// --polish=1 the pieces carry the polished bases.  With --scaffolds= the same reads are placed a second time, on the pieces, and the scaffolds and
+// their layout come from that placement (contig ids there are piece ids).  Without a proper pair nothing is cut, with a message: every contig is
+// one piece.  Without --break_misjoins=1 every file is what it was.  None is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -97,7 +105,8 @@ static const char *USAGE =
     "         [--contigs_new_reads_percent=95] [--contigs_trim_threshold=25] [--paired_extend=0|1]\n"
     "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n"
     "         [--contigs_depth=0|1] [--placements=placements.tsv] [--polish=0|1] [--polish_changes=changes.tsv]\n"
-    "         [--scaffolds=scaffolds.fasta] [--scaffold_layout=layout.tsv] [--scaffold_min_links=5] [--scaffold_min_gap=10] [--scaffold_max_second_percent=50]\n";
+    "         [--scaffolds=scaffolds.fasta] [--scaffold_layout=layout.tsv] [--scaffold_min_links=5] [--scaffold_min_gap=10] [--scaffold_max_second_percent=50]\n"
+    "         [--break_misjoins=0|1] [--break_min_span=1] [--break_inset=21] [--break_margin=N] [--broken=pieces.fasta] [--break_cuts=cuts.tsv]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -117,6 +126,11 @@ int main(int argc, char **argv) {
     std::string scaffolds, scaffold_layout;
     alga_scaffold_params scp;
     alga_scaffold_default_params(&scp);
+    int break_misjoins = 0, break_margin = 0;
+    bool break_margin_given = false;
+    std::string broken, break_cuts;
+    alga_break_params brp;
+    alga_break_default_params(&brp);
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -157,6 +171,12 @@ int main(int argc, char **argv) {
         else if (opt(a, "--scaffold_min_links", v)) scp.min_links = atoi(v.c_str());
         else if (opt(a, "--scaffold_min_gap", v)) scp.min_gap = atoi(v.c_str());
         else if (opt(a, "--scaffold_max_second_percent", v)) scp.max_second_percent = atoi(v.c_str());
+        else if (opt(a, "--break_misjoins", v)) break_misjoins = atoi(v.c_str());
+        else if (opt(a, "--break_min_span", v)) brp.min_span = atoi(v.c_str());
+        else if (opt(a, "--break_inset", v)) brp.inset = atoi(v.c_str());
+        else if (opt(a, "--break_margin", v)) { break_margin = atoi(v.c_str()); break_margin_given = true; }
+        else if (opt(a, "--broken", v)) broken = v;
+        else if (opt(a, "--break_cuts", v)) break_cuts = v;
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -174,7 +194,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && strncmp(a, "--break_", 8) && strncmp(a, "--broken=", 9) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -188,6 +208,12 @@ int main(int argc, char **argv) {
     if (scaffolds.empty() && !scaffold_layout.empty()) { fprintf(stderr, "alga_hip: --scaffold_layout= needs --scaffolds=\n"); return 2; }
     if (scp.min_links < 1 || scp.min_gap < 1 || scp.min_gap > (1 << 20) || scp.max_second_percent < 1 || scp.max_second_percent > 100) {
         fprintf(stderr, "alga_hip: --scaffold_min_links must be >= 1, --scaffold_min_gap in [1, 2^20], --scaffold_max_second_percent in [1, 100]\n");
+        return 2;
+    }
+    if (break_misjoins && (contigs_final.empty() || file2.empty())) { fprintf(stderr, "alga_hip: --break_misjoins=1 needs --contigs_final= and --file2=\n"); return 2; }
+    if (!break_misjoins && (!broken.empty() || !break_cuts.empty())) { fprintf(stderr, "alga_hip: --broken= and --break_cuts= need --break_misjoins=1\n"); return 2; }
+    if (brp.min_span < 1 || brp.inset < 0 || brp.inset > (1 << 20) || break_margin < 0 || break_margin > (1 << 20)) {
+        fprintf(stderr, "alga_hip: --break_min_span must be >= 1, --break_inset and --break_margin in [0, 2^20]\n");
         return 2;
     }
     if (correct_reads && !alga_exe.empty()) {
@@ -481,7 +507,7 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
-                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty())) {
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins)) {
                     // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
                     alga_parsed_reads pr{};
                     char perr[512] = {0};
@@ -560,7 +586,62 @@ int main(int argc, char **argv) {
                     if (rc == ALGA_OK) rc = polish ? alga_write_polished_fasta_device(engine, &cu, &cs, &fc, &pl, &pol, contigs_depth, contigs_final.c_str(), &ffi)
                                         : contigs_depth ? alga_write_final_fasta_depth_device(engine, &cu, &cs, &fc, &pl, contigs_final.c_str(), &ffi)
                                                         : alga_write_final_fasta_device(engine, &cu, &cs, &fc, contigs_final.c_str(), &ffi);
+                    // what the scaffolder works on: the placement on the contigs, or with --break_misjoins=1 a second one on the pieces
+                    const alga_placements *spl = &pl;
+                    const alga_place_info *spi = &pi;
+                    const alga_polished *spol = polish ? &pol : nullptr;
+                    alga_placements pl2;
+                    alga_place_info pi2;
+                    if (rc == ALGA_OK && break_misjoins) {
+                        const bool have = pr.paired && pi.insert_median >= 0;
+                        if (!have) fprintf(stderr, "Breaking skipped: the placement saw no proper pair, so nothing can span a column; every contig is one piece\n");
+                        brp.margin = !have ? 0 : break_margin_given ? break_margin : (int32_t) std::min<long long>(pi.insert_median, 1 << 20);
+                        alga_broken bk;
+                        alga_break_info bi;
+                        rc = alga_break_placed_device(engine, &pnd, have ? (const uint8_t *) d_po : nullptr, &pl, polish ? &pol : nullptr, &brp, nullptr, &bk, &bi);
+                        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot break the contigs: %s (status %d)\n", alga_last_error(engine), rc); return 1; }
+                        fprintf(stderr, "Contigs broken: %llu proper pairs (%llu spanning), %llu weak columns, %llu runs (%llu open), %llu cuts, %llu contigs cut, %llu pieces, "
+                                "N50 %llu -> %llu; min span %d, inset %d, margin %d, %llu candidate columns, span up to %llu, longest piece %llu; device ms: span %.3f "
+                                "cut %.3f, call %.1f ms wall\n", (unsigned long long) bi.pairs_proper, (unsigned long long) bi.pairs_spanning,
+                                (unsigned long long) bi.weak_columns, (unsigned long long) bi.runs, (unsigned long long) bi.runs_open, (unsigned long long) bi.cuts,
+                                (unsigned long long) bi.targets_cut, (unsigned long long) bi.pieces, (unsigned long long) bi.n50_targets, (unsigned long long) bi.n50_pieces,
+                                brp.min_span, brp.inset, brp.margin, (unsigned long long) bi.candidate_columns, (unsigned long long) bi.max_span,
+                                (unsigned long long) bi.longest_piece, bi.ms_span, bi.ms_cut, bi.ms_total);
+                        if (!broken.empty()) {
+                            alga_gfa_info bgi;
+                            rc = alga_write_broken_fasta_device(engine, &bk, broken.c_str(), &bgi);
+                            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", broken.c_str(), alga_last_error(engine), rc); return 1; }
+                            fprintf(stderr, "Pieces written -> %s: %llu records, %llu bytes\n", broken.c_str(), (unsigned long long) bgi.segments, (unsigned long long) bgi.bytes);
+                        }
+                        if (!break_cuts.empty()) {                           // not a hot path: the host formats from the arrays that came back
+                            const size_t nc = (size_t) bk.n_cuts, nt = (size_t) bk.n_targets;
+                            std::vector<uint32_t> off(nt + 1), cols(nc), first(nc), last(nc);
+                            rc = alga_copy_to_host(engine, off.data(), pl.d_col_off, (nt + 1) * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nc) rc = alga_copy_to_host(engine, cols.data(), bk.d_cut_cols, nc * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nc) rc = alga_copy_to_host(engine, first.data(), bk.d_cut_first, nc * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nc) rc = alga_copy_to_host(engine, last.data(), bk.d_cut_last, nc * sizeof(uint32_t));
+                            FILE *f = rc == ALGA_OK ? fopen(break_cuts.c_str(), "w") : nullptr;
+                            if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", break_cuts.c_str()); return 1; }
+                            for (size_t i = 0; f && i < nc; i++) {
+                                const size_t t = (size_t) (std::upper_bound(off.begin(), off.end(), cols[i]) - off.begin()) - 1;
+                                fprintf(f, "%zu\t%u\t%u\t%u\n", t, cols[i] - off[t], first[i] - off[t], last[i] - off[t]);
+                            }
+                            if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", break_cuts.c_str()); return 1; }
+                        }
+                        if (rc == ALGA_OK && !scaffolds.empty() && have) {    // the same reads on the pieces (the break result keeps its own copy of the bases)
+                            rc = alga_place_reads_device(engine, &pnd, (const uint8_t *) d_po, bk.d_words, bk.d_begin, bk.d_len, (int32_t) bk.n_pieces, &pp, nullptr, &pl2, &pi2);
+                            if (rc == ALGA_OK) {
+                                fprintf(stderr, "Reads placed on the pieces: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
+                                        "median insert %lld; call %.1f ms wall\n", (unsigned long long) pi2.reads, (unsigned long long) pi2.placed, (unsigned long long) pi2.unique,
+                                        (unsigned long long) pi2.multi, (unsigned long long) pi2.unplaced, (unsigned long long) pi2.pairs_proper, (unsigned long long) pi2.pairs,
+                                        (long long) pi2.insert_median, pi2.ms_total);
+                                spl = &pl2; spi = &pi2; spol = nullptr;         // (a polish is already in the pieces' bases)
+                            }
+                        }
+                    }
                     if (rc == ALGA_OK && !scaffolds.empty()) {
+                        const alga_placements &pl = *spl;                    // (shadows: from here on the placement the scaffolds are made from)
+                        const alga_place_info &pi = *spi;
                         const bool have = pr.paired && pi.insert_median >= 0;
                         if (!have) fprintf(stderr, "Scaffolding skipped: the placement saw no proper pair, so there is no insert size; every contig is its own scaffold\n");
                         scp.insert = have ? (int32_t) pi.insert_median : 0;
@@ -569,7 +650,7 @@ int main(int argc, char **argv) {
                         alga_scaffold_info si;
                         alga_gfa_info sgi;
                         rc = alga_scaffold_placed_device(engine, &pnd, have ? (const uint8_t *) d_po : nullptr, &pl, &scp, nullptr, &sc, &si);
-                        if (rc == ALGA_OK) rc = alga_write_scaffold_fasta_device(engine, &pl, &sc, polish ? &pol : nullptr, scaffolds.c_str(), &sgi);
+                        if (rc == ALGA_OK) rc = alga_write_scaffold_fasta_device(engine, &pl, &sc, spol, scaffolds.c_str(), &sgi);
                         if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", scaffolds.c_str(), alga_last_error(engine), rc); return 1; }
                         fprintf(stderr, "Scaffolds: %llu links, %llu bundles supported, %llu joins, %llu scaffolds (%llu of several contigs), N50 %llu -> %llu; insert %d, "
                                 "%llu split pairs (%llu too far), %llu bundles, %llu ambiguous ends, %llu joins dropped for cycles, longest %llu; device ms: links %.3f "

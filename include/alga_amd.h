@@ -1411,6 +1411,85 @@ int  alga_scaffold_placed_device(alga_engine *e, const alga_nodes *nodes, const 
 int  alga_write_scaffold_fasta_device(alga_engine *e, const alga_placements *pl, const alga_scaffolds *scaf, const alga_polished *pol /* may be NULL */,
                                       const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- contigs broken where no read pair spans them (alga_amd/csrc/break_kernels.hip, engine_break.hip) -------------------------------------
+ * Every stage after the graph keeps a contig whole or joins contigs.  The placement holds the evidence against a contig: for every uniquely
+ * placed pair the target, both positions and both strands.  A column that no proper pair's fragment spans, while columns on both sides of it
+ * are spanned, is a join that no clone of the library supports; the contig is cut there.  Integers only, free of any order (thread, atomics);
+ * tests/break_checker.py states the rule twice in Python and the device result equals it array for array.  place -> [polish] -> break ->
+ * place on the pieces -> scaffold.
+ *
+ * Inputs: the node set that was placed (twin layout), d_pair_off as alga_place_reads_device takes it (NULL = no pairs), the engine's
+ * current placement result `pl` (from either placement call), optionally the current polish `pol` of that placement, and alga_break_params:
+ * min_span 1 .. 2^31 - 1 (default 1), inset 0 .. 2^20 (21), margin 0 .. 2^20 (no default: the caller sets it, usually the placement's
+ * insert_median), flags 0, reserved 0; anything else answers ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Proper pairs.  A pair is PROPER exactly as item 6 of the placement defines it, with max_insert = pl.n_hist - 1.  Each pair is judged
+ *      once, from the mate with the smaller read index.  pairs_proper of this call equals the placement's.
+ *   2. Span.  A proper pair has its `+` read at a and its `-` read at b, lengths la and lb.  It SPANS column j of its target iff
+ *      a + inset <= j < b + lb - inset.  A pair with b + lb - a <= 2 * inset spans nothing (it still counts in pairs_proper); the pairs that
+ *      span something count in pairs_spanning.  span[g] = the number of proper pairs that span column g, in column space, uint32.
+ *      (inset is part of the rule: with up to max_mismatches substitutions tolerated, a read may overhang a misjoin by a few columns.)
+ *   3. Candidates.  Column j of target t is a CANDIDATE iff margin <= j < len[t] - margin.  A candidate is WEAK iff span < min_span.
+ *   4. Runs.  A run is a maximal stretch of consecutive weak candidates of one target; it never crosses a target boundary, also where
+ *      targets abut.
+ *   5. Closed and open.  A run s .. e is CLOSED iff columns s - 1 and e + 1 are both candidates of the same target (they are then not weak).
+ *      Every other run is OPEN and cuts nothing: a whole target with no pair on it, single-end data, a run that touches the margin.
+ *   6. Cuts.  Every closed run makes one cut, at column c = floor((s + e + 1) / 2): the pieces are [.., c) and [c, ..).  Nothing is removed.
+ *   7. Pieces, numbered in column order; a target of length 0 stays one piece of length 0 in its place.  n_pieces = n_targets + n_cuts;
+ *      piece j is the columns d_piece_off[j] .. d_piece_off[j + 1]; d_piece_target[j] its source target, d_piece_start[j] its offset there.
+ *   8. Result (alga_broken; engine-owned, valid until the next break call on `e`: a later placement, polish or scaffold call does not
+ *      invalidate it, a refused call leaves an earlier result valid).  d_span [n_columns]; d_cut_cols (ascending, column space), d_cut_first,
+ *      d_cut_last (the run of each cut) [n_cuts]; d_t_cuts uint32 [n_targets]; d_piece_off [n_pieces + 1]; d_begin uint64, d_len int32,
+ *      d_piece_target, d_piece_start [n_pieces]; d_words: the result's OWN copy of the bases in column space (the polish's layout,
+ *      (n_columns + 15) / 16 + 2 words, the bits past n_columns zero), taken from the column array the placement kept or from pol->d_words.
+ *      (d_words, d_begin, d_len, n_pieces) is a target set as alga_place_reads_device takes it; the copy is what lets the next placement,
+ *      which overwrites its own column array, read it.
+ *   9. Counters (alga_break_info): pairs_proper, pairs_spanning; candidate_columns, weak_columns; runs, runs_open; cuts, targets_cut, pieces;
+ *      max_span (over all columns), longest_piece; n50_targets, n50_pieces (the scaffold's N50, on the host from lengths read back only when
+ *      `info` is given); ms_span (the check, the pair pass, the scan), ms_cut (flags, compaction, pieces, the copy) (HIP events), ms_total (wall).
+ *  10. Refusals, all before anything of the result is written (ALGA_ERR_INVALID_ARGUMENT).  On the host: `pl` is not the engine's current
+ *      placement result, judged by its buffers and by ALL its sizes (n_reads, n_targets, n_columns, n_hist: a struct kept from an earlier
+ *      placement of the same reads on other targets is refused, since n_columns sizes every column array and n_hist - 1 is max_insert);
+ *      nodes->n / 2 != pl.n_reads; `pol` is given but is not the current polish of this placement.  On the device
+ *      (k_br_check, one read-back): pl.n_columns != col_off[n_targets]; pair_off fails the placement's test; a UNIQUE read with len < 1 or len > 16 * stride_words, its target
+ *      outside [0, n_targets), pos < 0 or pos + len > len[target].  The column check and the last read check are what the pair kernel's
+ *      writes into the difference array rely on.
+ * One pass over the reads (integer atomics on a difference array of n_columns + 1 entries), a scan, one pass over the columns, and two
+ * compactions by scan: of the runs (the i-th start belongs to the i-th end), then of the closed ones.  Read-backs: the refusal flags, the run
+ * count, the cut count (the run, cut and piece arrays are allocated at their size), the counters.
+ *
+ * alga_write_broken_fasta_device: one record per piece with a length, in piece order, `>contig_id=<j>_length=<len>_from=<t>_start=<s>`: j is
+ * the piece id (the target id of a later placement on the pieces), t and s its source target and offset.  `brk` must be the engine's
+ * current break result.  ABI stays 7: the calls add. */
+typedef struct {
+    int32_t min_span, inset, margin, flags;
+    int32_t reserved[4];             /* 0                                                                                             */
+} alga_break_params;
+typedef struct {
+    int64_t         n_targets, n_pieces, n_cuts;
+    uint64_t        n_columns;
+    const uint32_t *d_span;          /* n_columns                                                                                     */
+    const uint32_t *d_cut_cols, *d_cut_first, *d_cut_last;   /* n_cuts                                                                */
+    const uint32_t *d_t_cuts;        /* n_targets                                                                                     */
+    const uint32_t *d_piece_off;     /* n_pieces + 1                                                                                  */
+    const uint64_t *d_begin;         /* n_pieces                                                                                      */
+    const int32_t  *d_len;
+    const int32_t  *d_piece_target;
+    const uint32_t *d_piece_start;
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+} alga_broken;
+typedef struct {
+    uint64_t pairs_proper, pairs_spanning, candidate_columns, weak_columns, runs, runs_open, cuts, targets_cut, pieces, max_span, longest_piece;
+    uint64_t n50_targets, n50_pieces;
+    double   ms_span, ms_cut;        /* device time (HIP events): check + pair pass + scan; flags, compaction, pieces, copy          */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_break_info;
+void alga_break_default_params(alga_break_params *p);         /* margin is left 0: the caller sets it                                 */
+int  alga_break_placed_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off /* may be NULL */, const alga_placements *pl,
+                              const alga_polished *pol /* may be NULL */, const alga_break_params *p, void *hip_stream, alga_broken *out,
+                              alga_break_info *info /* may be NULL */);
+int  alga_write_broken_fasta_device(alga_engine *e, const alga_broken *brk, const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
