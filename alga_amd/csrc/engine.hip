@@ -233,10 +233,19 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
             HIP_TRY(e, hipEventRecord(e->ev[EV_KEYS], s));
             e->keyed_n = -1;                               // the sort below may reuse the key buffers: one build per key pass
             e->store_n = -1;
-            HIP_TRY(e, launch_cluster_store(nd, cc, (uint32_t *) e->cl_keys[0].p, (uint32_t *) e->cl_vals[0].p, (uint32_t *) e->cl_keys[1].p,
-                                            (uint32_t *) e->cl_vals[1].p, e->sort_temp.p, cluster_sort_temp_bytes((uint64_t) nd.n), e->cl_dir.p, pp.keys_shared == 1 || !need_vals,
-                                            e->ev[EV_SORT], cnt + CNT_TOTAL + 1, e->opt_test_unsorted_index != 0, s, e->opt_own_sort != 0));
-            HIP_TRY(e, hipEventRecord(e->ev[EV_DIR], s));
+            HIP_TRY(e, launch_cluster_sort(nd, cc, (uint32_t *) e->cl_keys[0].p, (uint32_t *) e->cl_vals[0].p, (uint32_t *) e->cl_keys[1].p,
+                                           (uint32_t *) e->cl_vals[1].p, e->sort_temp.p, cluster_sort_temp_bytes((uint64_t) nd.n), pp.keys_shared == 1 || !need_vals,
+                                           e->ev[EV_SORT], e->opt_test_unsorted_index != 0, s, e->opt_own_sort != 0));
+            // The bucket directory.  With option pile_dir >= 1 the pile path's sample does not read it and comes first; with pile_dir = 2 the fill and
+            // k_tgt_dir then read the sample's verdict and leave at once for a build the path keeps in its pure form: its pile kernels take the bucket
+            // records from the keys, the pairwise kernels behind them (the by-id instances, which alone run for that form) from the piles' table
+            // (bucket_record).  That needs every pairwise kernel of such a build to be a by-id instance: pile_skip_gather, no statistics build.
+            const bool dir_late = pile && e->opt_pile_dir >= 1;
+            e->dir_late = dir_late;
+            if (!dir_late) {
+                HIP_TRY(e, launch_cluster_dir(nd, cc, (const uint32_t *) e->cl_keys[1].p, e->cl_dir.p, cnt + CNT_TOTAL + 1, nullptr, s));
+                HIP_TRY(e, hipEventRecord(e->ev[EV_DIR], s));
+            }
             e->pile_n = -1;
             if (pile) {
                 // piles of the key order: belong to the index (a function of the targets alone), read by k_pile_probe.  The sample first: a
@@ -262,8 +271,15 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
             }
             if (pile) {
                 launch_pile_sample(nd, cc, pp.uniform_len, (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, e->cl_dir.p,
-                                   (unsigned long long *) e->cl_pile_cnt.p, e->opt_pile >= 2 ? e->opt_pile - 1 : 0, s);
+                                   (unsigned long long *) e->cl_pile_cnt.p, e->opt_pile >= 2 ? e->opt_pile - 1 : 0, s, e->opt_pile_dir >= 1);
                 if ((rc = alga_check_launch(e, "k_pile_build<sample>"))) return rc;
+            }
+            e->pile_tab_index = pile && e->opt_pile_dir >= 2 && e->opt_pile_skip_gather && !cfg.stats;
+            if (dir_late) {
+                HIP_TRY(e, hipEventRecord(e->ev[EV_SAMPLE], s));
+                HIP_TRY(e, launch_cluster_dir(nd, cc, (const uint32_t *) e->cl_keys[1].p, e->cl_dir.p, cnt + CNT_TOTAL + 1,
+                                              e->pile_tab_index ? (const unsigned long long *) e->cl_pile_cnt.p : nullptr, s));
+                HIP_TRY(e, hipEventRecord(e->ev[EV_DIR], s));
             }
             HIP_TRY(e, launch_cluster_gather(nd, cc, pp.cluster_eq, (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, (const uint32_t *) e->cl_meta.p,
                                              pp.uniform_len, e->cl_store.p, (pile && e->opt_pile_skip_gather) ? (const unsigned long long *) e->cl_pile_cnt.p : nullptr, s));
@@ -277,7 +293,8 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                 const bool from_consensus = e->opt_pile_runs != 0;
                 launch_pile_build(nd, cfg, cc, pp.uniform_len, (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, e->cl_dir.p, e->cl_pile_rec.p, e->cl_pile_rec2.p, e->cl_pile_tab.p,
                                   e->pile_epoch, e->cl_pile_succ.p, e->cl_runs.p, pp.uniform_len - cfg.Lmin + 1, (const unsigned long long *) e->cl_pile_cnt.p,
-                                  from_consensus ? (uint32_t *) e->cl_pile_own.p : nullptr, (from_consensus && e->opt_pile_runs_list) ? e->cl_pile_list.p : nullptr, s);
+                                  from_consensus ? (uint32_t *) e->cl_pile_own.p : nullptr, (from_consensus && e->opt_pile_runs_list) ? e->cl_pile_list.p : nullptr, s,
+                                  e->opt_pile_dir >= 1, cnt + CNT_TOTAL + 1, e->pile_tab_index);
                 if ((rc = alga_check_launch(e, "k_pile_build"))) return rc;
                 if (keys_only) {
                     // own run lists of the entries outside a first group (6 % at the north-star size) ...
@@ -373,7 +390,8 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                     pure_streamed = launch_probe_stream_list(nd, cfg, cc, pp.cluster_eq, e->cl_store.p, e->cl_dir.p, e->cl_runs.p, (const uint8_t *) e->cl_nruns.p, (int32_t *) e->cl_defer.p,
                                              (uint32_t) n_src, cnt, e->n_cu, (uint32_t *) e->outdeg.p, (unsigned long long *) e->loc_first.p,
                                              (unsigned long long *) e->loc_second.p, (int32_t *) e->cl_defer2.p, (const unsigned long long *) e->cl_pile_cnt.p, s, slot_stride, src_begin,
-                                             (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, pp.uniform_len, e->opt_pile_stream_by_id != 0);
+                                             (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, pp.uniform_len, e->opt_pile_stream_by_id != 0,
+                                             e->pile_tab_index ? e->cl_pile_tab.p : nullptr, e->pile_epoch);
                     if ((rc = alga_check_launch(e, "k_probe_stream (list)"))) return rc;
                 }
                 HIP_TRY(e, hipEventRecord(e->ev[EV_PAIRS], s));
@@ -382,7 +400,8 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                                        (int32_t) n_src, (const int32_t *) e->cl_defer.p, src_begin, (uint32_t *) e->rec_dst.p, (unsigned long long *) e->rec_val.p,
                                        cap, cnt, e->n_cu, (uint32_t *) e->outdeg.p, (unsigned long long *) e->loc_first.p, &big, cnt + CNT_DEFERRED, 1, s,
                                        (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, pp.uniform_len,
-                                       (piled && e->opt_pile_skip_gather) ? (const unsigned long long *) e->cl_pile_cnt.p : nullptr);
+                                       (piled && e->opt_pile_skip_gather) ? (const unsigned long long *) e->cl_pile_cnt.p : nullptr,
+                                       (piled && e->pile_tab_index) ? e->cl_pile_tab.p : nullptr, e->pile_epoch);
                 // the out-degrees k_pile_probe left in the slots: moved to outdeg by the first pass of finalize_local's scan (option pile_deg_fold), or here
                 e->pile_deg_pending = piled && e->opt_pile_deg_fold != 0;
                 if (piled && !e->pile_deg_pending) launch_pile_deg((int32_t) n_src, (unsigned long long *) e->loc_first.p, (uint32_t *) e->outdeg.p, (const unsigned long long *) e->cl_pile_cnt.p, s);
@@ -607,8 +626,9 @@ void store_phase_stats(alga_engine *e) {
     if (!e->store_timed) return;
     e->stats.ms_keys = ev_ms(e, EV_START, EV_KEYS);
     e->stats.ms_sort = ev_ms(e, EV_KEYS, EV_SORT);
-    e->stats.ms_dir = ev_ms(e, EV_SORT, EV_DIR);
-    e->stats.ms_gather = ev_ms(e, EV_DIR, EV_GATHER);      // (with the pile path's sample in front of k_tgt_gather: all there is of this phase when that path keeps the build)
+    // (option pile_dir >= 1: the sample runs between the sort and the directory pass; it stays with the gather phase)
+    e->stats.ms_dir = ev_ms(e, e->dir_late ? EV_SAMPLE : EV_SORT, EV_DIR);
+    e->stats.ms_gather = ev_ms(e, EV_DIR, EV_GATHER) + (e->dir_late ? ev_ms(e, EV_SORT, EV_SAMPLE) : 0.0);      // (with the pile path's sample in front of k_tgt_gather: all there is of this phase when that path keeps the build)
     e->stats.ms_pile = e->pile_timed ? ev_ms(e, EV_GATHER, EV_SEED) : 0.0;
 }
 
@@ -717,6 +737,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_pile_runs = value != 0;
     } else if (!strcmp(name, "pile_runs_list")) {
         e->opt_pile_runs_list = value != 0;
+    } else if (!strcmp(name, "pile_dir")) {
+        if (value < 0 || value > 2) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option pile_dir: 0 directory records, 1 k_pile_build from the keys, 2 ... and no directory for a pure pile build");
+        e->opt_pile_dir = (int) value;
     } else if (!strcmp(name, "pile_deg_fold")) {
         e->opt_pile_deg_fold = value != 0;
     } else if (!strcmp(name, "pile_probe_lean")) {

@@ -18,7 +18,7 @@ struct DevBuf {
     size_t cap = 0;
 };
 
-enum { EV_START = 0, EV_SEED, EV_PROBE, EV_GROUP, EV_REDUCE, EV_EMIT, EV_PAIRS, EV_KEYS, EV_SORT, EV_GATHER, EV_DIR, EV_COUNT };
+enum { EV_START = 0, EV_SEED, EV_PROBE, EV_GROUP, EV_REDUCE, EV_EMIT, EV_PAIRS, EV_KEYS, EV_SORT, EV_GATHER, EV_DIR, EV_SAMPLE, EV_COUNT };
 constexpr int ALGA_STAGE_THREADS = 8;      // worker threads (pinned buffer pairs, streams) of the staged host <-> HBM copies
 
 struct alga_engine {
@@ -65,6 +65,9 @@ struct alga_engine {
     int    opt_pile_runs_list = 1;                          // option "pile_runs_list": 1 = k_pile_build lists its piles and k_pile_runs_consensus_list works through the lists (four waves per SIMD), 0 = k_pile_runs_consensus sweeps the side records for them (round 5)
     DevBuf cl_pile_list;                                    // the piles of every k_pile_build workgroup and their counts (pile_list_bytes)
     int    opt_pile_deg_fold = 1;                           // option "pile_deg_fold": 1 = the first pass of the out-degree scan moves the out-degrees k_pile_probe left in the slots (no k_pile_deg), 0 = k_pile_deg behind the probe
+    int    opt_pile_dir = 2;                                // option "pile_dir": 0 = k_pile_build reads the bucket directory (until round 7), 1 = it takes bucket starts, counts and class offsets from the sorted keys and never reads cl_dir, 2 = ... and a build of the pure pile form has no directory at all
+    bool   dir_late = false;                                // the last index build ran the pile path's sample in front of the directory pass (EV_SAMPLE was recorded)
+    bool   pile_tab_index = false;                          // the last index build made the directory only for a build the pile path did not keep pure: the pairwise kernels of a pure build read the piles' table (bucket_record)
     int    opt_pile_stream_by_id = 0;                       // option "pile_stream_by_id": 1 = a build kept in the pure pile form sends what k_pile_probe hands on through k_probe_stream (list mode, entries by id) before the general kernel, 0 = to the general kernel at once (the default until the pass is measured)
     int    opt_pile_probe_lean = 1;                         // option "pile_probe_lean": 1 = k_pile_probe<true> (the source's row taken in slot 0 only, no last-mismatch search past position 63), 0 = k_pile_probe<false> (round 5)
     bool   pile_deg_pending = false;                        // the last discovery left that move to finalize_local's scan

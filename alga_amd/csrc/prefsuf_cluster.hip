@@ -219,7 +219,9 @@ __global__ void __launch_bounds__(256) k_tgt_gather(NodesDev nd, uint64_t count 
 constexpr int TD_TILE = 256, TD_HALO = 96;                 // entries per tile (512 and 1024 measure the same); entries staged past it
 __global__ void __launch_bounds__(TD_TILE) k_tgt_dir(const uint32_t *__restrict__ keys, uint64_t n, int shift, uint32_t n_buckets /* of this directory */,
                                                      uint32_t bucket_base /* first bucket of this directory: 0, or the start of a rank's bucket range (every key lies in it) */, uint4 *__restrict__ dir,
-                                                     unsigned long long *__restrict__ bad /* set when the keys are not in (bucket, m_C class) order: the build fails with ALGA_ERR_HIP */) {
+                                                     unsigned long long *__restrict__ bad /* set when the keys are not in (bucket, m_C class) order: the build fails with ALGA_ERR_HIP */,
+                                                     const unsigned long long *__restrict__ pile_cnt /* null, or the pile path's sample (option pile_dir = 2): no directory for a build it keeps in its pure form -- k_pile_build carries the order check there */) {
+    if (pile_cnt && pile_cnt_pure(pile_cnt)) return;
     __shared__ uint32_t sb[TD_TILE + TD_HALO + 1];         // (bucket << 3 | m_C class) of the entries base - 1 .. base + TD_TILE + TD_HALO - 1
     const uint64_t base = (uint64_t) blockIdx.x * TD_TILE;
     const uint32_t nb3 = n_buckets << 3;
@@ -334,6 +336,7 @@ struct ByIdEntries {
     const uint32_t *skeys, *sids;                          // the sorted (key, id) pairs
     uint32_t uniform_meta;                                 // len << 8 | CL_META_FROM
     const unsigned long long *pile_cnt;                    // null: the build has an entry array, no question
+    BucketIndex bx;                                        // tab != null (option pile_dir = 2): a build of the pure form has no directory either -- the by-id instances take the bucket records from the piles' table
 };
 // The (key, id) pair of entry `ei` of the key order (the caller clamps ei); the id clamped: the row is fetched by it.
 __device__ __forceinline__ void by_id_pair(const ByIdEntries &by, size_t ei, uint32_t n_nodes, uint32_t &key, uint32_t &id) {
@@ -436,7 +439,8 @@ k_probe_clustered(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__res
     // The index loads of stage 1 are issued by EVERY lane and outside any branch: a load under a branch leaves the number of
     // loads in flight unknown to the compiler, which then drains ALL of them where the entries are first used -- and that
     // serialises the two stages of the pipeline.
-    auto index_loads = [&](uint32_t bucket, uint4 &rec) { rec = dir[bucket]; };
+    const bool from_tab = BYID && by.bx.tab != nullptr;    // (the by-id instance runs for the pure form alone: bucket_record, prefsuf_cluster_device.h)
+    auto index_loads = [&](uint32_t bucket, uint4 &rec) { rec = bucket_record<BYID>(dir, by.bx, from_tab, bucket); };
     // resolved run list -> LDS; returns the largest entry count of the source's runs (uniform)
     auto finish_runs = [&](int buf, int nr, const uint2 &run, const uint4 &rec) -> uint32_t {
         uint32_t e0, cnt;
@@ -665,7 +669,7 @@ k_probe_clustered(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__res
                     wave_lds_fence();
                     uint32_t cnt = 0u;
                     if (start && rank >= rb && rank < rb + CL_RMAX) {
-                        const uint4 rec = dir[key >> cc.idx_shift];
+                        const uint4 rec = bucket_record<BYID>(dir, by.bx, from_tab, key >> cc.idx_shift);
                         const uint32_t ry = (wm & 255u) | ((uint32_t) wl << 8) | ((uint32_t) p1 << 16);
                         uint32_t e0;
                         run_slice(rec, ry, e0, cnt);
@@ -904,7 +908,8 @@ k_probe_stream(NodesDev nd, PrefSufCfg cfg, ClusterCfg cc, const uint4 *__restri
         if (gl == 0) sSrc[wave][4 * qb + g] = make_uint2((uint32_t) id, (uint32_t) lenB);
         return gl < nr_eff ? run.x >> cc.idx_shift : 0u;
     };
-    auto index_loads = [&](uint32_t bucket, uint4 &rec) { rec = dir[bucket]; };   // every lane, no branch
+    const bool from_tab = BYID && by.bx.tab != nullptr;
+    auto index_loads = [&](uint32_t bucket, uint4 &rec) { rec = bucket_record<BYID>(dir, by.bx, from_tab, bucket); };   // every lane, no branch
     auto finish_runs = [&](int qb, int nr_eff, const uint2 &run, const uint4 &rec) -> uint32_t {
         uint32_t e0, cnt;
         run_slice(rec, run.y, e0, cnt);
@@ -1341,6 +1346,12 @@ __global__ void __launch_bounds__(256) k_iota(uint32_t *__restrict__ v, uint32_t
 hipError_t launch_cluster_store(const NodesDev &nd, const ClusterCfg &cc, uint32_t *keys, uint32_t *vals, uint32_t *keys2, uint32_t *vals2,
                                 void *sort_temp, size_t sort_temp_bytes, void *dir, bool fill_vals,
                                 hipEvent_t ev_sorted, unsigned long long *bad_flag, bool test_skip_sort, hipStream_t s, bool own_sort) {
+    const hipError_t err = launch_cluster_sort(nd, cc, keys, vals, keys2, vals2, sort_temp, sort_temp_bytes, fill_vals, ev_sorted, test_skip_sort, s, own_sort);
+    return err != hipSuccess ? err : launch_cluster_dir(nd, cc, keys2, dir, bad_flag, nullptr, s);
+}
+
+hipError_t launch_cluster_sort(const NodesDev &nd, const ClusterCfg &cc, uint32_t *keys, uint32_t *vals, uint32_t *keys2, uint32_t *vals2, void *sort_temp, size_t sort_temp_bytes,
+                               bool fill_vals, hipEvent_t ev_sorted, bool test_skip_sort, hipStream_t s, bool own_sort) {
     if (nd.n <= 0) return hipSuccess;
     const uint64_t n = (uint64_t) nd.n;
     // (the sort payload is the node id = the position: the engine's own sort makes it up in its first pass; the library's wants the array)
@@ -1355,11 +1366,38 @@ hipError_t launch_cluster_store(const NodesDev &nd, const ClusterCfg &cc, uint32
     } else err = sort_u32_pairs(sort_temp, sort_temp_bytes, keys, keys2, own_sort ? (const uint32_t *) nullptr : vals, vals2, n, cc.idx_shift - 3, s, own_sort);
     if (err != hipSuccess) return err;
     if (ev_sorted) (void) hipEventRecord(ev_sorted, s);
+    return hipSuccess;
+}
+
+// The directory's zero fill as a kernel: a memset cannot be made to depend on what the device knows.  16-byte stores, grid-stride over pieces of
+// DF_UNROLL * 256 records (16 KB, every wave's store a contiguous kilobyte); at the north-star size a block takes one piece.
+constexpr int DF_UNROLL = 4;
+__global__ void __launch_bounds__(256) k_dir_fill(uint4 *__restrict__ dir, uint64_t n_rec, const unsigned long long *__restrict__ pile_cnt) {
+    if (pile_cnt && pile_cnt_pure(pile_cnt)) return;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (uint64_t p = (uint64_t) blockIdx.x * (256u * DF_UNROLL); p < n_rec; p += (uint64_t) gridDim.x * (256u * DF_UNROLL)) {
+#pragma unroll
+        for (int u = 0; u < DF_UNROLL; u++) {
+            const uint64_t i = p + (uint64_t) u * 256u + threadIdx.x;
+            if (i < n_rec) dir[i] = z;
+        }
+    }
+}
+
+hipError_t launch_cluster_dir(const NodesDev &nd, const ClusterCfg &cc, const uint32_t *keys2, void *dir, unsigned long long *bad_flag, const unsigned long long *only_if_no_pure_piles,
+                              hipStream_t s) {
+    if (nd.n <= 0) return hipSuccess;
+    const uint64_t n = (uint64_t) nd.n, n_rec = (uint64_t) cc.n_buckets + 2;
     // (measured and rejected: zero-filling the directory as a side job of the VALU-bound k_node_runs -- that kernel got slower by what
     // the fill costs on its own, 0.24 ms)
-    err = hipMemsetAsync(dir, 0, ((size_t) cc.n_buckets + 2) * 16, s);
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(k_tgt_dir, dim3((unsigned) ((n + 1 + TD_TILE - 1) / TD_TILE)), dim3(TD_TILE), 0, s, (const uint32_t *) keys2, n, cc.idx_shift, cc.n_buckets, 0u, (uint4 *) dir, bad_flag);
+    if (only_if_no_pure_piles)
+        hipLaunchKernelGGL(k_dir_fill, dim3((unsigned) std::min<uint64_t>((n_rec + 256 * DF_UNROLL - 1) / (256 * DF_UNROLL), 1u << 17)), dim3(256), 0, s, (uint4 *) dir, n_rec,
+                           only_if_no_pure_piles);
+    else {
+        const hipError_t err = hipMemsetAsync(dir, 0, n_rec * 16, s);
+        if (err != hipSuccess) return err;
+    }
+    hipLaunchKernelGGL(k_tgt_dir, dim3((unsigned) ((n + 1 + TD_TILE - 1) / TD_TILE)), dim3(TD_TILE), 0, s, keys2, n, cc.idx_shift, cc.n_buckets, 0u, (uint4 *) dir, bad_flag, only_if_no_pure_piles);
     return hipGetLastError();
 }
 
@@ -1408,7 +1446,7 @@ hipError_t launch_cluster_store_slice(const NodesDev &nd, const ClusterCfg &cc, 
 #undef TG_EQ
 #undef TG_LAUNCH
     hipLaunchKernelGGL(k_tgt_dir, dim3((unsigned) ((n + 1 + TD_TILE - 1) / TD_TILE)), dim3(TD_TILE), 0, s, (const uint32_t *) keys2, n, cc.idx_shift, n_buckets_local, bucket_base,
-                       (uint4 *) dir, bad_flag);
+                       (uint4 *) dir, bad_flag, (const unsigned long long *) nullptr);
     return hipGetLastError();
 }
 
@@ -1435,7 +1473,7 @@ void launch_probe_stream(const NodesDev &nd, const PrefSufCfg &cfg, const Cluste
     o.slot_stride = slot_stride;
     const uint4 *st = (const uint4 *) store;
 #define CLQ_LAUNCH(ST, E, K, BK) hipLaunchKernelGGL((k_probe_stream<ST, E, K, BK>), grid, block, 0, s, nd, cfg, cc, st, (const uint4 *) dir, (const uint2 *) runs, nruns, src_begin, src_end, o, defer_list, defer_cap, pile_cnt, \
-                                                    (const int32_t *) nullptr, (const unsigned long long *) nullptr, ByIdEntries{nullptr, nullptr, 0u, nullptr})
+                                                    (const int32_t *) nullptr, (const unsigned long long *) nullptr, ByIdEntries{nullptr, nullptr, 0u, nullptr, BucketIndex{nullptr, 0u}})
 #define CLQ_ORDER(ST, E, K) do { if (by_key) CLQ_LAUNCH(ST, E, K, true); else CLQ_LAUNCH(ST, E, K, false); } while (0)
 #define CLQ_STATS(E, K) do { if (cfg.stats) CLQ_ORDER(true, E, K); else CLQ_ORDER(false, E, K); } while (0)
     if (eq == 3 && kf == 5)      CLQ_STATS(3, 5);
@@ -1467,7 +1505,7 @@ __global__ void __launch_bounds__(256) k_defer_swap(const unsigned long long *__
 bool launch_probe_stream_list(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int eq, const void *store, const void *dir, const void *runs, const uint8_t *nruns,
                               int32_t *src_list, uint32_t list_cap, unsigned long long *counters, int n_cu, uint32_t *deg, unsigned long long *first,
                               unsigned long long *second, int32_t *defer2, const unsigned long long *pile_cnt, hipStream_t s, uint32_t slot_stride, int32_t src_base,
-                              const uint32_t *skeys, const uint32_t *sids, int uniform_len, bool by_id) {
+                              const uint32_t *skeys, const uint32_t *sids, int uniform_len, bool by_id, const void *tab, uint32_t epoch) {
     if (eq != 3 || list_cap == 0) return false;            // (the pile path takes entries of three pieces only: pile_plan)
     const int kf = (2 * cfg.Lmin) >> 5;
     const int kfs = (kf == 5 || kf == 3) ? kf : 0;
@@ -1475,7 +1513,7 @@ bool launch_probe_stream_list(const NodesDev &nd, const PrefSufCfg &cfg, const C
     ProbeOut o{nullptr, nullptr, 0, counters, deg, first, src_base, second};       // (src_base: the listed ids are those of a rank's range, the slots count from its first)
     o.slot_stride = slot_stride;
     const bool pure_too = by_id && skeys && sids && uniform_len > 0 && nd.n > 0;
-    const ByIdEntries by{skeys, sids, uniform_len > 0 ? (((uint32_t) uniform_len << 8) | CL_META_FROM) : 0u, pile_cnt};
+    const ByIdEntries by{skeys, sids, uniform_len > 0 ? (((uint32_t) uniform_len << 8) | CL_META_FROM) : 0u, pile_cnt, BucketIndex{(const uint4 *) tab, epoch}};
 #define CLQ_LIST(K, BI) hipLaunchKernelGGL((k_probe_stream<false, 3, K, false, true, BI>), grid, block, 0, s, nd, cfg, cc, (const uint4 *) store, (const uint4 *) dir, (const uint2 *) runs, nruns, 0, \
                                            (int32_t) std::min<uint32_t>(list_cap, 0x7FFFFFFFu), o, defer2, list_cap, pile_cnt, (const int32_t *) src_list, (const unsigned long long *) (counters + CNT_DEFERRED), by)
 #define CLQ_BOTH(K) do { CLQ_LIST(K, false); if (pure_too) CLQ_LIST(K, true); } while (0)
@@ -1493,7 +1531,7 @@ void launch_probe_clustered(const NodesDev &nd, const PrefSufCfg &cfg, const Clu
                             uint32_t *rec_dst, unsigned long long *rec_val, uint64_t rec_cap,
                             unsigned long long *counters, int n_cu, uint32_t *deg, unsigned long long *first, const ProbeBig *big,
                             const unsigned long long *list_count, int sw /* 1 | 2: words per offset mask of the source-side form */, hipStream_t s,
-                            const uint32_t *skeys, const uint32_t *sids, int uniform_len, const unsigned long long *pile_cnt) {
+                            const uint32_t *skeys, const uint32_t *sids, int uniform_len, const unsigned long long *pile_cnt, const void *tab, uint32_t epoch) {
     const int64_t ns = (int64_t) src_end - src_begin;
     if (ns <= 0) return;
     dim3 grid((unsigned) cluster_probe_blocks(n_cu, (uint64_t) ns)), block(PROBE_WAVES * 64);
@@ -1502,7 +1540,7 @@ void launch_probe_clustered(const NodesDev &nd, const PrefSufCfg &cfg, const Clu
     const uint4 *st = (const uint4 *) store;
     // pile_cnt: the build may have no entry array (decided on the device): the form that reads the rows by id is launched beside the usual one
     const bool maybe_by_id = pile_cnt && skeys && sids && uniform_len > 0 && eq == 3 && sw == 1 && !cfg.stats;
-    const ByIdEntries by{skeys, sids, uniform_len > 0 ? (((uint32_t) uniform_len << 8) | CL_META_FROM) : 0u, maybe_by_id ? pile_cnt : nullptr};
+    const ByIdEntries by{skeys, sids, uniform_len > 0 ? (((uint32_t) uniform_len << 8) | CL_META_FROM) : 0u, maybe_by_id ? pile_cnt : nullptr, BucketIndex{(const uint4 *) tab, epoch}};
     // KF = (2 * Lmin) >> 5 as a compile-time constant for the shapes ALGA's defaults produce (150-bp reads: Lmin 82, rows of 9
     // words; 100-bp reads: Lmin 55, rows of 6 words); 0 = any shape
     const int kf = (2 * cfg.Lmin) >> 5;

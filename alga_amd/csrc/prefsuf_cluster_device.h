@@ -84,6 +84,34 @@ constexpr unsigned long long PILE_DECLINE_ONE_IN = ALGA_PILE_DECLINE_ONE_IN;
 // needs the entry array, so k_tgt_gather runs) before the general kernel sees what is left; else the pile kernels and the general kernel alone.
 __device__ __forceinline__ bool pile_cnt_declines(const unsigned long long *c) { return c[1] * PILE_DECLINE_ONE_IN > c[0]; }
 __device__ __forceinline__ bool pile_cnt_mixed(const unsigned long long *c) { return !pile_cnt_declines(c) && c[1] * PILE_IRREGULAR_ONE_IN > c[0]; }
+__device__ __forceinline__ bool pile_cnt_pure(const unsigned long long *c) { return !pile_cnt_declines(c) && !pile_cnt_mixed(c); }
+// Where the record of a bucket lives.  The pairwise and the mixed form: in the directory (k_tgt_dir).  A build the pile path keeps in its PURE form
+// with option pile_dir = 2 has no directory: k_pile_build left {entries, first entry, class offsets} in words 16 .. 19 of the bucket's line of `tab`
+// (prefsuf_pile.hip), valid when the line carries the build's epoch (word 15, bits 23 ..; a line of another epoch is an empty bucket), and for a
+// bucket of more than 64 entries (word 16 says 127) the full count in word 20.
+struct BucketIndex {
+    const uint4 *tab;                                      // null: the directory, whatever the form
+    uint32_t epoch;
+};
+// MAYBE_TAB: an instance that runs for the pure form alone (the by-id kernels); the others read the directory and nothing else.  from_tab: uniform.
+// All loads are issued by every lane and outside any branch (k_probe_clustered: index_loads).
+template <bool MAYBE_TAB>
+__device__ __forceinline__ uint4 bucket_record(const uint4 *__restrict__ dir, const BucketIndex &bx, bool from_tab, uint32_t bucket) {
+    if constexpr (!MAYBE_TAB) return dir[bucket];
+    else {
+        const uint4 *line = bx.tab + (size_t) bucket * 8;
+        const uint4 *pr = from_tab ? line + 4 : dir + bucket;
+        const uint32_t *pt = from_tab ? reinterpret_cast<const uint32_t *>(line + 3) + 3 : reinterpret_cast<const uint32_t *>(pr);
+        const uint32_t *pf = from_tab ? reinterpret_cast<const uint32_t *>(line + 5) : reinterpret_cast<const uint32_t *>(pr);
+        const uint4 r = *pr;
+        const uint32_t tag = *pt, full = *pf;
+        if (!from_tab) return r;
+        const uint32_t n = r.x & 255u;
+        const bool valid = (tag >> 23) == bx.epoch;
+        return valid ? make_uint4(r.y, n == 127u ? full : n, r.z, r.w) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
 __device__ __forceinline__ void run_slice(const uint4 &rec, uint32_t run_y, uint32_t &e0, uint32_t &cnt) {
     const int q = (int) (run_y & 255u), p0 = (int) ((run_y >> 8) & 255u), p1 = (int) ((run_y >> 16) & 255u);
     int mlo = q - p1 + 1, mhi = q - p0;

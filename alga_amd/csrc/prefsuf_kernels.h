@@ -54,6 +54,12 @@ hipError_t launch_cluster_store(const NodesDev &nd, const ClusterCfg &cc, uint32
                                 size_t sort_temp_bytes, void *dir, bool fill_vals, hipEvent_t ev_sorted /* may be null */,
                                 unsigned long long *bad_flag /* device: set when the sorted keys are not in order */,
                                 bool test_skip_sort /* tests: build the index over UNSORTED keys */, hipStream_t s, bool own_sort = true);      // sort + directory
+// ... and its two halves: the sort of the (key, id) pairs, and the bucket directory over the sorted keys.  only_if_no_pure_piles: null, or the counters of
+// the pile path's sample -- the fill and k_tgt_dir then leave at once for a build that path keeps in its pure form (decided on the device)
+hipError_t launch_cluster_sort(const NodesDev &nd, const ClusterCfg &cc, uint32_t *keys, uint32_t *vals, uint32_t *keys2, uint32_t *vals2, void *sort_temp, size_t sort_temp_bytes,
+                               bool fill_vals, hipEvent_t ev_sorted, bool test_skip_sort, hipStream_t s, bool own_sort = true);
+hipError_t launch_cluster_dir(const NodesDev &nd, const ClusterCfg &cc, const uint32_t *keys2, void *dir, unsigned long long *bad_flag, const unsigned long long *only_if_no_pure_piles,
+                              hipStream_t s);
 hipError_t launch_cluster_gather(const NodesDev &nd, const ClusterCfg &cc, int eq, const uint32_t *keys2, const uint32_t *vals2, const uint32_t *meta,
                                  int uniform_len /* > 0: all live nodes have this length, no alignFrom mask */, void *store,
                                  const unsigned long long *pile_cnt /* null, or the pile path's sample counters: no entry array for a build it keeps */, hipStream_t s);
@@ -64,7 +70,8 @@ void       launch_probe_clustered(const NodesDev &nd, const PrefSufCfg &cfg, con
                                   const unsigned long long *list_count /* device, may be null: list mode ends at min(src_end, *list_count) */,
                                   int sw /* 1 | 2: 64-bit words per offset mask (sources of up to 64 | 128 suffix windows) */, hipStream_t s,
                                   const uint32_t *skeys = nullptr, const uint32_t *sids = nullptr, int uniform_len = 0,
-                                  const unsigned long long *pile_cnt = nullptr /* the pile path's sample: the build may have no entry array -- then the sorted (key, id) pairs stand in for it */);
+                                  const unsigned long long *pile_cnt = nullptr /* the pile path's sample: the build may have no entry array -- then the sorted (key, id) pairs stand in for it */,
+                                  const void *tab = nullptr /* option pile_dir = 2: ... and no directory -- then the bucket records come from the piles' table */, uint32_t epoch = 0);
 void       launch_probe_stream(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int eq, const void *store, const void *dir,
                                const void *runs, const uint8_t *nruns, int32_t src_begin, int32_t src_end, bool by_key /* the range is one of entry-array positions */,
                                unsigned long long *counters, int n_cu, uint32_t *deg, unsigned long long *first, unsigned long long *second, int32_t *defer_list,
@@ -76,14 +83,17 @@ bool       pile_plan(const PrefSufCfg &cfg, const ClusterCfg &cc, int eq, int un
 size_t     pile_record_bytes(uint64_t n);
 size_t     pile_table_bytes(uint32_t n_buckets);
 void       launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys /* sorted keys */, const uint32_t *sids /* their node ids */, const void *dir,
-                              unsigned long long *pile_cnt /* of the sample: [0] buckets (raised to entries / 8), [1] irregular buckets, [2] entries */, int no_sample, hipStream_t s);
+                              unsigned long long *pile_cnt /* of the sample: [0] buckets (raised to entries / 8), [1] irregular buckets, [2] entries */, int no_sample, hipStream_t s,
+                              bool from_keys = false /* option pile_dir >= 1: bucket starts, counts and class offsets from the keys, dir is not read */);
 constexpr int PILE_CNT_WORDS = 6;      // {sampled buckets, irregular ones, sampled entries, own-list ids, members checked, members whose lists differ}
 size_t     pile_own_mask_bytes(uint64_t n);
 size_t     pile_list_bytes(uint64_t n);
 void       launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys, const uint32_t *sids, const void *dir, void *rec,
                              void *rec2 /* run lists of the further groups, at the groups' slots */, void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt,
                              uint32_t *own_mask /* null: the piles' run lists from their outer members' own lists (round 4) */,
-                             void *plist /* null: k_pile_runs_consensus finds the piles in the side records; else pile_list_bytes(n) of scratch */, hipStream_t s);
+                             void *plist /* null: k_pile_runs_consensus finds the piles in the side records; else pile_list_bytes(n) of scratch */, hipStream_t s,
+                             bool from_keys = false /* as for the sample; the kernel then carries k_tgt_dir's order check */, unsigned long long *bad_flag = nullptr,
+                             bool full_record = false /* option pile_dir = 2: the records of the buckets of more than 64 entries complete (count, class offsets): a pure build has no directory */);
 void       launch_pile_own_ids(const uint32_t *own_mask, const uint32_t *sids, uint64_t n_entries, int32_t *list, uint32_t cap, unsigned long long *pile_cnt, hipStream_t s);
 void       launch_pile_check(const void *side, uint64_t n_entries, uint32_t n_buckets, const void *tab, const void *rec2, uint32_t epoch, const void *runs, int n_nodes, int nwin,
                              unsigned long long *pile_cnt, hipStream_t s);
@@ -93,7 +103,8 @@ bool       launch_probe_stream_list(const NodesDev &nd, const PrefSufCfg &cfg, c
                                     int32_t *src_list, uint32_t list_cap, unsigned long long *counters, int n_cu, uint32_t *deg, unsigned long long *first,
                                     unsigned long long *second, int32_t *defer2, const unsigned long long *pile_cnt, hipStream_t s, uint32_t slot_stride = 0,
                                     int32_t src_base = 0 /* the slot arrays count from this id (a rank's range) */,
-                                    const uint32_t *skeys = nullptr, const uint32_t *sids = nullptr, int uniform_len = 0, bool by_id = false);
+                                    const uint32_t *skeys = nullptr, const uint32_t *sids = nullptr, int uniform_len = 0, bool by_id = false,
+                                    const void *tab = nullptr /* as for launch_probe_clustered */, uint32_t epoch = 0);
 void       launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const void *tab, uint32_t epoch, const void *rec, const void *rec2, const void *side,
                              const void *runs, unsigned long long *counters, uint32_t *deg, unsigned long long *first, unsigned long long *second, int32_t *defer_list,
                              uint32_t defer_cap, const unsigned long long *pile_cnt, int n_cu, hipStream_t s, int32_t src_begin, int32_t src_end,

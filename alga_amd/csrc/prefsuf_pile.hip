@@ -52,7 +52,9 @@ constexpr int PILE_EQ = 3;                     // entry size this path takes: ro
 //               the record (bits 23..31, never 0: the table is not cleared between builds, a record of another epoch is an empty bucket)
 //   -- the first 64 bytes are all the run loop reads (the kernel is bound by the number of 64-byte requests that miss its L1) --
 //   w[16]       entries (127: more than 64) | runs of the pile's run list << 8 (0: none -- its members read their own lists) | end of the last run's
-//               windows (+ 64) << 16;  w[17] first entry of the bucket;  w[18], w[19] the directory's class offsets (k_tgt_dir): the look-up of a target
+//               windows (+ 64) << 16;  w[17] first entry of the bucket;  w[18], w[19] the directory's class offsets (k_tgt_dir's, or the same bytes made
+//               from the keys: option pile_dir): the look-up of a target.  A bucket of more than 64 entries has no pile and no list: with pile_dir = 2
+//               its w[18], w[19] and its full count in w[20] serve the pairwise kernels of a build without a directory (bucket_record)
 //   w[20 .. 31] the pile's run list (k_pile_runs_consensus): up to EIGHT runs, windows ascending and contiguous on the pile's axis: w[20 .. 27] their
 //               cluster keys, w[28 .. 31] per run (k-mer position + 64) | (first window + 64) << 8 in 16 bits (a run ends where the next begins).
 //               A pile's extent holds ~5.4 minimizers at 30x (one per 32 positions of ~174): with six slots one pile in four had no list
@@ -89,11 +91,16 @@ __device__ __forceinline__ void load_row9(const NodesDev &nd, uint32_t id, uint3
     }
 }
 
-template <bool SAMPLE>
+// KEYS (engine option "pile_dir" >= 1): where a bucket starts and ends, its entry count and its class offsets come from the tile's own keys
+// and one key on each side -- the keys are sorted by (bucket, m_C >> 3), the directory record says nothing they do not.  The kernel then never
+// reads `dir`: no 16-byte record per entry streamed through it, and no global round trip between an entry's key and its random row fetch
+// (the row's address needs sids[j] alone; the fetch is what the workgroup waits for).  false: the records of k_tgt_dir, as until round 7.
+template <bool SAMPLE, bool KEYS>
 __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const uint32_t *__restrict__ skeys, const uint32_t *__restrict__ sids, uint64_t n_entries, const uint4 *__restrict__ dir, ClusterCfg cc, int U,
                                                            uint4 *__restrict__ rec, uint4 *__restrict__ tab, uint32_t epoch,
                                                            uint4 *__restrict__ side, unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask,
-                                                           uint32_t *__restrict__ plist, uint32_t *__restrict__ pcount) {
+                                                           uint32_t *__restrict__ plist, uint32_t *__restrict__ pcount, unsigned long long *__restrict__ bad,
+                                                           uint32_t full_record) {
     if (!SAMPLE && pile_declines(pile_cnt)) return;
     const int idx_shift = cc.idx_shift, kk = cc.kk;
     __shared__ uint32_t sRow[PB_THREADS][PILE_SW];         // the entry's row on the pile's axis, masked to its extent (odd stride: conflict-free)
@@ -105,6 +112,8 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
     __shared__ uint8_t sTag[PB_THREADS];                   // per leader
     __shared__ uint32_t sCount[3];                         // buckets, irregular buckets, entries of buckets that begin in the tile (sample only)
     __shared__ uint32_t sPiles;                            // piles this workgroup put on its list (plist)
+    __shared__ unsigned long long sMask[KEYS ? PB_THREADS / 64 : 1][8];   // KEYS, per wave: [0] bit l = lane l's entry is the first of its bucket; [c], c = 1 .. 7: its m_C class is below c
+    __shared__ uint32_t sPrev;                             // KEYS: entries of the bucket of entry base - 1 among the 64 entries in front of the tile
     const int t = (int) threadIdx.x;
     const uint64_t base = (uint64_t) blockIdx.x * PB_TILE;
     const uint64_t j = base + (uint64_t) t;
@@ -115,18 +124,57 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
     const uint32_t key = skeys[jc], node_id = min(sids[jc], (uint32_t) nd.n - 1u);
     const uint32_t meta = key >> (cc.idx_shift - CL_MBITS);       // low bits: m_C (a target's sort key holds it under the bucket)
     const bool tgt = have && key != 0xFFFFFFFFu;
+    // (bucket << 3 | m_C class) as k_tgt_dir sees an entry: the non-targets (all-ones keys) and what lies past the end count as bucket n_buckets
+    const uint32_t nb3 = cc.n_buckets << 3;
+    auto tagged = [&](uint32_t x) -> uint32_t { return x == 0xFFFFFFFFu ? nb3 : x >> (idx_shift - 3); };
     uint4 drec = make_uint4(0u, 0u, 0u, 0u);
-    if (tgt) drec = dir[key >> idx_shift];
-    const uint64_t e0 = drec.x;
-    const uint32_t cnt = drec.y;
-    const bool owned = tgt && e0 >= base && e0 < base + PB_TILE && e0 <= j && j - e0 < (uint64_t) cnt;
-    const int s = owned ? (int) (e0 - base) : 0;           // thread of the bucket's first entry
-    const int i = owned ? (int) (j - e0) : 0;              // index of this entry in its bucket
-    const bool part = owned && cnt <= 64u;
+    uint32_t tg_own = 0u, tg_before = 0u, tg_look = 0u, bk_before = 0u;
+    bool pre = false;                                      // KEYS: the row is fetched (the entry's bucket begins in the tile proper, from the two boundary keys)
+    if (KEYS) {
+        // the key in front of mine (one more coalesced load of the lines the wave has just read), and for the first wave the 64 keys in front
+        // of the tile; the tile's two boundary keys are uniform loads
+        tg_own = have ? tagged(key) : nb3;
+        tg_before = j == 0 ? 0xFFFFFFFFu : (j - 1 < n_entries ? tagged(skeys[j - 1]) : nb3);        // "entry -1": a bucket no entry has
+        if (t < 64 && base >= 64u) tg_look = tagged(skeys[min(base - 64u + (uint64_t) t, n_entries - 1)]);
+        const uint64_t jl = min(base + (uint64_t) (PB_TILE - 1), n_entries - 1);
+        bk_before = base == 0 ? 0x1FFFFFFFu : tagged(skeys[min(base - 1, n_entries - 1)]) >> 3;
+        const uint32_t bk_last = tagged(skeys[jl]) >> 3;
+        pre = tgt && (tg_own >> 3) != bk_before && (tg_own >> 3) <= bk_last;
+    } else if (tgt) drec = dir[key >> idx_shift];
     // (only the thread that WORKS on an entry reads its row: the entries of a bucket that began in the tile before are that tile's halo, and a
-    // halo thread whose bucket begins behind the tile has nothing to do -- one random row read per entry, none for the overlap of the tiles)
+    // halo thread whose bucket begins behind the tile has nothing to do -- one random row read per entry, none for the overlap of the tiles.
+    // KEYS: issued straight behind the key and the id, for every entry of a bucket that begins in the tile proper -- also where the bucket
+    // turns out to hold more than 64 entries)
     uint32_t row[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (part) load_row9(nd, node_id, row);
+    if (KEYS && pre) load_row9(nd, node_id, row);
+    uint64_t e0 = drec.x;
+    uint32_t cnt = drec.y;
+    bool owned = tgt && e0 >= base && e0 < base + PB_TILE && e0 <= j && j - e0 < (uint64_t) cnt;
+    int s = owned ? (int) (e0 - base) : 0;                 // thread of the bucket's first entry
+    int i = owned ? (int) (j - e0) : 0;                    // index of this entry in its bucket
+    bool part = owned && cnt <= 64u;
+    bool regular = tgt && cnt <= 64u;                      // an entry of a bucket of at most 64 entries, wherever that begins
+    if (!KEYS && part) load_row9(nd, node_id, row);
+    if (KEYS) {
+        const int wv = t >> 6;
+        const bool first = tg_own >> 3 != tg_before >> 3;
+        // fail closed (k_tgt_dir's check, for the build that has no directory pass): keys that are not in (bucket, m_C class) order.  Everything
+        // below is bounded by the tile whatever the keys say
+        if (!SAMPLE && t < PB_TILE && j >= 1 && j < n_entries && tg_own < tg_before) atomicOr(bad, 1ull);
+        const unsigned long long mf = __ballot(first);
+        unsigned long long mc[7];
+#pragma unroll
+        for (int c = 1; c <= 7; c++) mc[c - 1] = __ballot((tg_own & 7u) < (uint32_t) c);
+        if ((t & 63) == 0) {
+            sMask[wv][0] = mf;
+#pragma unroll
+            for (int c = 1; c <= 7; c++) sMask[wv][c] = mc[c - 1];
+        }
+        if (t < 64) {
+            const unsigned long long ml = __ballot(base >= 64u && (tg_look >> 3) == bk_before);
+            if (t == 0) sPrev = (uint32_t) __popcll(ml);
+        }
+    }
     sLead[t] = 0ull; sRm[t] = 0ull; sMin[t] = 0xFFFFFFFFu; sMax[t] = 0u; sBad[t] = 0u;
     if (t < 3) sCount[t] = 0u;
     if (t == 0) sPiles = 0u;
@@ -160,6 +208,44 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
 #pragma unroll
     for (int k = 0; k < PILE_SW; k++) sRow[t][k] = A[k];
     __syncthreads();
+    if (KEYS) {
+        // my bucket begins at the last bucket start at or before my thread and ends in front of the next one: from the waves' ballots.  A bucket that
+        // begins in the tile proper and holds at most 64 entries ends inside tile + halo; one whose end is not seen there holds more
+        const int wv = t >> 6, ln = t & 63;
+        int sk = -1, ek = PB_THREADS;
+        {
+            const unsigned long long own = sMask[wv][0];
+            const unsigned long long at = own & (~0ull >> (63 - ln)), after = ln == 63 ? 0ull : own & (~0ull << (ln + 1));
+            if (at) sk = wv * 64 + 63 - __clzll((long long) at);
+            if (after) ek = wv * 64 + __builtin_ctzll(after);
+#pragma unroll
+            for (int v = 1; v < PB_THREADS / 64; v++) {
+                if (sk < 0 && wv - v >= 0) { const unsigned long long mv = sMask[wv - v][0]; if (mv) sk = (wv - v) * 64 + 63 - __clzll((long long) mv); }
+                if (ek == PB_THREADS && wv + v < PB_THREADS / 64) { const unsigned long long mv = sMask[wv + v][0]; if (mv) ek = (wv + v) * 64 + __builtin_ctzll(mv); }
+            }
+        }
+        owned = tgt && sk >= 0 && sk < PB_TILE;
+        s = owned ? sk : 0;
+        i = owned ? t - sk : 0;
+        cnt = owned ? (uint32_t) (ek - sk) : 0u;           // (exact up to 64; a larger bucket: at least 65)
+        e0 = base + (uint64_t) s;
+        part = owned && pre && cnt <= 64u;
+        // (an entry of the tile proper whose bucket began in front of the tile: that bucket's entries there + those up to the tile's first start)
+        regular = tgt && (sk >= 0 ? cnt <= 64u : sPrev + (uint32_t) ek <= 64u);
+        drec.x = (uint32_t) e0;
+    }
+    // KEYS: the class offsets of a bucket of at most 64 entries (threads s .. s + cnt - 1: two waves at most) as k_tgt_dir's tally makes them:
+    // byte c = entries of the bucket with an m_C class below c, c = 1 .. 7 (byte 0: zero)
+    auto class_offsets = [&]() -> unsigned long long {
+        const int last = s + (int) cnt - 1, w0 = s >> 6, w1 = last >> 6;
+        const unsigned long long r0 = (~0ull << (s & 63)) & (w1 == w0 ? ~0ull >> (63 - (last & 63)) : ~0ull);
+        const unsigned long long r1 = w1 == w0 ? 0ull : ~0ull >> (63 - (last & 63));
+        unsigned long long acc = 0ull;
+#pragma unroll
+        for (int c = 1; c <= 7; c++)
+            acc |= (unsigned long long) (__popcll(sMask[KEYS ? w0 : 0][c] & r0) + __popcll(sMask[KEYS ? w1 : 0][c] & r1)) << (8 * c);
+        return acc;
+    };
     int L = t;                                             // leader: the first entry of the bucket with this k-mer
     if (part) {
         for (int u = 0; u < i; u++) if (sKm[s + u] == kmer) { L = s + u; break; }
@@ -212,7 +298,30 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
         uint4 *line = tab + (size_t) (key >> idx_shift) * 8;                        // the bucket's 128-byte record
         if (!part) {
             if (i == 0) {                                  // more than 64 entries: not for this path
-                if (!SAMPLE) { line[3] = make_uint4(0u, 0u, 0u, (1u << 22) | (epoch << 23)); line[4] = make_uint4(127u, drec.x, drec.z, drec.w); }
+                // (KEYS: the record's class offsets stay zero and its count says no more than "127".  No pile kernel behind this one reads either of an
+                //  irregular bucket: k_pile_probe's lookup serves sources it did not hand on, and a run in a bucket with bit 22 set hands its source on;
+                //  k_pile_runs* and k_pile_list_check take the piles of regular buckets only.  full_record -- option pile_dir = 2, a build without a
+                //  directory: the pairwise kernels read the bucket's record from here (bucket_record), so this lane finds the bucket's end and its seven
+                //  class boundaries by bisection in the keys: exact, and rare in a build the sample keeps.  The full count goes to word 20)
+                if (!SAMPLE) {
+                    uint32_t cz = drec.z, cw = drec.w;
+                    if (KEYS && full_record) {
+                        const uint32_t b3 = tg_own & ~7u;
+                        auto lower = [&](uint64_t lo, uint64_t hi, uint32_t tv) -> uint64_t {      // the first entry of [lo, hi) at or above tv
+                            while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (tagged(skeys[mid]) < tv) lo = mid + 1; else hi = mid; }
+                            return lo;
+                        };
+                        uint64_t hi = min(j + 256u, n_entries);
+                        while (hi < n_entries && tagged(skeys[hi]) < b3 + 8u) hi = min(j + 2u * (hi - j), n_entries);
+                        const uint64_t end = lower(j + 1u, hi, b3 + 8u);
+                        unsigned long long co = 0ull;      // byte c: entries with an m_C class below c, saturating (run_slice takes the whole of a bucket of more than 255)
+                        for (uint32_t c = 1; c <= 7u; c++) co |= (unsigned long long) min(lower(j, end, b3 + c) - j, (uint64_t) 255u) << (8u * c);
+                        cz = (uint32_t) co; cw = (uint32_t) (co >> 32);
+                        line[5] = make_uint4((uint32_t) min(end - j, (uint64_t) 0xFFFFFFFFu), 0u, 0u, 0u);
+                    }
+                    line[3] = make_uint4(0u, 0u, 0u, (1u << 22) | (epoch << 23));
+                    line[4] = make_uint4(127u, drec.x, cz, cw);
+                }
                 atomicAdd(&sCount[0], 1u); atomicAdd(&sCount[1], 1u);
             }
         } else {
@@ -271,13 +380,14 @@ __global__ void __launch_bounds__(PB_THREADS, 6) k_pile_build(NodesDev nd, const
             if (!SAMPLE && L == s && t == (int) (sMax[s] & 0xFFFFu)) {
                 // T0 of the first group (the member that starts leftmost): the second half of the bucket's record -- no run list yet (k_pile_runs), and
                 // who T1 is (the member that starts rightmost: the lowest slot of the group's dense stretch): its id and its m_C
+                if (KEYS) { const unsigned long long co = class_offsets(); drec.z = (uint32_t) co; drec.w = (uint32_t) (co >> 32); }
                 line[4] = make_uint4(cnt, drec.x, drec.z, drec.w);
                 line[5] = make_uint4(sSlot[s], sMin[s] >> 16, 0u, 0u);
             }
         }
     }
     // entries of no regular bucket (non-targets, buckets of more than 64 entries): written by the thread of the tile proper
-    if (!SAMPLE && have && t < PB_TILE && !(tgt && cnt <= 64u)) {
+    if (!SAMPLE && have && t < PB_TILE && !regular) {
         side[j] = make_uint4(node_id, 0xFFFFFFFFu, 0u, 0u);
         if (own_mask) atomicOr(&own_mask[j >> 5], 1u << (j & 31u));
     }
@@ -1116,8 +1226,9 @@ __global__ void k_pile_sample_close(unsigned long long *__restrict__ pile_cnt) {
 // array -- its kernels take the rows by id -- and that kernel, like the pairwise probes, reads the two counters and leaves at once.
 __global__ void k_pile_sample_force(unsigned long long *__restrict__ pile_cnt, unsigned long long buckets, unsigned long long irregular) { pile_cnt[0] = buckets; pile_cnt[1] = irregular; }
 
+// from_keys (option "pile_dir" >= 1): k_pile_build<., true> -- `dir` is not read (and need not be built yet)
 void launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys, const uint32_t *sids, const void *dir, unsigned long long *pile_cnt,
-                        int no_sample, hipStream_t s) {
+                        int no_sample, hipStream_t s, bool from_keys) {
     (void) hipMemsetAsync(pile_cnt, 0, PILE_CNT_WORDS * sizeof(unsigned long long), s);
     const uint64_t n_entries = nd.n > 0 ? (uint64_t) nd.n : 0;
     // (no_sample -- tests only: 1: the two counters stay zero and the pile kernels take the build whatever its buckets look like; 2: counters that say "mixed form")
@@ -1125,8 +1236,8 @@ void launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int uniform_le
     if (n_entries == 0 || no_sample) return;
     const uint64_t tiles = (n_entries + PB_TILE - 1) / PB_TILE;
     const dim3 sample((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::max<uint64_t>(64, tiles / 32)))), block(PB_THREADS);
-    hipLaunchKernelGGL((k_pile_build<true>), sample, block, 0, s, nd, skeys, sids, n_entries, (const uint4 *) dir, cc, uniform_len, (uint4 *) nullptr, (uint4 *) nullptr, 0u, (uint4 *) nullptr, pile_cnt,
-                       (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr);
+    hipLaunchKernelGGL((from_keys ? k_pile_build<true, true> : k_pile_build<true, false>), sample, block, 0, s, nd, skeys, sids, n_entries, (const uint4 *) dir, cc, uniform_len, (uint4 *) nullptr,
+                       (uint4 *) nullptr, 0u, (uint4 *) nullptr, pile_cnt, (uint32_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, (unsigned long long *) nullptr, 0u);
     hipLaunchKernelGGL(k_pile_sample_close, dim3(1), dim3(1), 0, s, pile_cnt);
 }
 
@@ -1135,15 +1246,17 @@ void launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int uniform_le
 // must have its run list then)
 // plist != null (with own_mask): k_pile_build lists its piles per workgroup and k_pile_runs_consensus_list takes them from there (pile_list_bytes)
 void launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys, const uint32_t *sids, const void *dir, void *rec, void *rec2,
-                       void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt, uint32_t *own_mask, void *plist, hipStream_t s) {
+                       void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt, uint32_t *own_mask, void *plist, hipStream_t s,
+                       bool from_keys, unsigned long long *bad_flag, bool full_record) {
     const uint64_t n_entries = nd.n > 0 ? (uint64_t) nd.n : 0;
     if (n_entries == 0) return;
     const uint64_t tiles = (n_entries + PB_TILE - 1) / PB_TILE;
     if (!own_mask) plist = nullptr;
     uint32_t *pl = (uint32_t *) plist, *pc = pl ? pl + tiles * PB_THREADS : nullptr;
     if (own_mask) (void) hipMemsetAsync(own_mask, 0, pile_own_mask_bytes(n_entries), s);
-    hipLaunchKernelGGL((k_pile_build<false>), dim3((unsigned) tiles), dim3(PB_THREADS), 0, s, nd, skeys, sids, n_entries, (const uint4 *) dir, cc, uniform_len, (uint4 *) rec, (uint4 *) tab, epoch,
-                       (uint4 *) side, const_cast<unsigned long long *>(pile_cnt), own_mask, pl, pc);
+    // (from_keys: the kernel carries k_tgt_dir's order check -- bad_flag is the word that kernel sets)
+    hipLaunchKernelGGL((from_keys ? k_pile_build<false, true> : k_pile_build<false, false>), dim3((unsigned) tiles), dim3(PB_THREADS), 0, s, nd, skeys, sids, n_entries, (const uint4 *) dir, cc, uniform_len,
+                       (uint4 *) rec, (uint4 *) tab, epoch, (uint4 *) side, const_cast<unsigned long long *>(pile_cnt), own_mask, pl, pc, bad_flag, full_record ? 1u : 0u);
     if (pl)
         hipLaunchKernelGGL(k_pile_runs_consensus_list, dim3((unsigned) ((tiles + PR_SEGS - 1) / PR_SEGS)), dim3(TK_ROWS), 0, s, (const uint32_t *) pl, (const uint32_t *) pc, (uint32_t) tiles,
                            (const uint4 *) side, n_entries, (uint4 *) tab, (const uint4 *) rec, (uint4 *) rec2, cc, uniform_len, cfg.Lmin, pile_cnt, own_mask);

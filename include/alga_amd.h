@@ -177,6 +177,13 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                node its own list, a pile's list joined from its two outer members')
  *   "pile_runs_list"             default 1: k_pile_build lists the piles of each of its workgroups and k_pile_runs_consensus_list takes the piles from
  *                                those lists (four waves per SIMD); 0: k_pile_runs_consensus sweeps the side records for them (round 5; A/B and tests)
+ *   "pile_dir"                   where the pile path takes a bucket's record {first entry, entries, class offsets} from.  0: k_pile_build reads the bucket
+ *                                directory k_tgt_dir made (until round 7; A/B and tests).  1: k_pile_build (the sample and the build) takes bucket
+ *                                starts, counts of at most 64 and the class offsets from the sorted keys of its tile and never reads the directory;
+ *                                the sample then runs in front of the directory pass.  2 (default): ... and a build the pile path keeps in its PURE
+ *                                form neither fills nor builds the directory (decided on the device, from the sample's counters): the pairwise
+ *                                kernels behind the pile kernels read the bucket records from the piles' table.  Declined and mixed builds, "pile" 0,
+ *                                a statistics build and "pile_skip_gather" 0 build the directory as before
  *   "pile_deg_fold"              default 1: the first pass of the out-degree scan moves the out-degrees k_pile_probe left in the sources' slots; 0: a
  *                                pass of its own (k_pile_deg) right behind the probe (A/B and tests)
  *   "pile_probe_lean"            default 1: k_pile_probe takes a source's row from its home run in slot 0 only and looks for the last mismatch
