@@ -574,21 +574,25 @@ int finalize_local(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_
     if ((rc = alga_ensure(e, e->out_cnt, (size_t) (n_src + 1) * sizeof(uint32_t)))) return rc;
     HIP_TRY(e, hipEventRecord(e->ev[EV_GROUP], s));
     HIP_TRY(e, hipEventRecord(e->ev[EV_REDUCE], s));
-    if (e->pile_deg_pending)
-        launch_exclusive_scan_pile_deg((uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, (unsigned long long *) e->loc_first.p,
-                                       (const unsigned long long *) e->cl_pile_cnt.p, s);
-    else
-        launch_exclusive_scan((const uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, s);
+    // option emit_fused: the scan and the slot edges in two passes over the slots (launch_local_emit); 0: the scan first, as until round 8
+    const bool fused = e->opt_emit_fused != 0;
+    const unsigned long long *pile_cnt = e->pile_deg_pending ? (const unsigned long long *) e->cl_pile_cnt.p : nullptr;      // (not pending: k_pile_deg has moved the out-degrees, or no pile kernel ran)
+    if (!fused) {
+        if (e->pile_deg_pending)
+            launch_exclusive_scan_pile_deg((uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, (unsigned long long *) e->loc_first.p, pile_cnt, s);
+        else
+            launch_exclusive_scan((const uint32_t *) e->outdeg.p, n_src, (uint32_t *) e->out_rowptr.p, (uint64_t *) e->scan_scratch.p, s);
+        if ((rc = alga_check_launch(e, "scan(outdeg)"))) return rc;
+    }
     e->pile_deg_pending = false;
-    if ((rc = alga_check_launch(e, "scan(outdeg)"))) return rc;
     const uint64_t E = e->stats.records;                                   // CNT_VALID_RECORDS of the probe == sum of the out-degrees (launch_local_emit zeroes the cursors it needs)
     if (E >= (1ull << 32) - 16) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 edges; shard the input");
     if ((rc = alga_ensure(e, e->edges, (size_t) (E + 1) * sizeof(alga_edge_dev)))) return rc;
     launch_local_emit(src_begin, (int32_t) n_src, (const uint32_t *) e->outdeg.p, (const unsigned long long *) e->loc_first.p,
-                      e->loc_second_used ? (const unsigned long long *) e->loc_second.p : nullptr, (const uint32_t *) e->rec_dst.p, (const unsigned long long *) e->rec_val.p, n_rec, (const uint32_t *) e->out_rowptr.p,
+                      e->loc_second_used ? (const unsigned long long *) e->loc_second.p : nullptr, (const uint32_t *) e->rec_dst.p, (const unsigned long long *) e->rec_val.p, n_rec, (uint32_t *) e->out_rowptr.p,
                       (uint32_t *) e->out_cnt.p, (alga_edge_dev *) e->edges.p,
                       e->defer_list_valid ? (const int32_t *) e->cl_defer.p : nullptr, (const unsigned long long *) e->counters.p + CNT_DEFERRED, (uint32_t) n_src, s,
-                      e->loc_second_used ? e->loc_slot_stride : 0u);
+                      e->loc_second_used ? e->loc_slot_stride : 0u, fused ? (uint64_t *) e->scan_scratch.p : nullptr, fused ? pile_cnt : nullptr);
     if ((rc = alga_check_launch(e, "k_local_emit"))) return rc;
     HIP_TRY(e, hipEventRecord(e->ev[EV_EMIT], s));
     uint64_t *d_total = (uint64_t *) e->scan_scratch.p + scan_total_index(n_src);
@@ -742,6 +746,8 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_pile_dir = (int) value;
     } else if (!strcmp(name, "pile_deg_fold")) {
         e->opt_pile_deg_fold = value != 0;
+    } else if (!strcmp(name, "emit_fused")) {
+        e->opt_emit_fused = value != 0;
     } else if (!strcmp(name, "pile_probe_lean")) {
         e->opt_pile_probe_lean = value != 0;
     } else if (!strcmp(name, "pile_stream_by_id")) {

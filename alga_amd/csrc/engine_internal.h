@@ -65,6 +65,7 @@ struct alga_engine {
     int    opt_pile_runs_list = 1;                          // option "pile_runs_list": 1 = k_pile_build lists its piles and k_pile_runs_consensus_list works through the lists (four waves per SIMD), 0 = k_pile_runs_consensus sweeps the side records for them (round 5)
     DevBuf cl_pile_list;                                    // the piles of every k_pile_build workgroup and their counts (pile_list_bytes)
     int    opt_pile_deg_fold = 1;                           // option "pile_deg_fold": 1 = the first pass of the out-degree scan moves the out-degrees k_pile_probe left in the slots (no k_pile_deg), 0 = k_pile_deg behind the probe
+    int    opt_emit_fused = 1;                              // option "emit_fused": 1 = finalize_local sums the out-degrees per tile and one pass writes row pointers and slot edges (k_emit_tile_sums, k_emit_scan_tiles: nothing moved to deg[], no row pointer read back), 0 = scan of deg[] first, k_local_emit_first behind it (until round 8)
     int    opt_pile_dir = 2;                                // option "pile_dir": 0 = k_pile_build reads the bucket directory (until round 7), 1 = it takes bucket starts, counts and class offsets from the sorted keys and never reads cl_dir, 2 = ... and a build of the pure pile form has no directory at all
     bool   dir_late = false;                                // the last index build ran the pile path's sample in front of the directory pass (EV_SAMPLE was recorded)
     bool   pile_tab_index = false;                          // the last index build made the directory only for a build the pile path did not keep pure: the pairwise kernels of a pure build read the piles' table (bucket_record)

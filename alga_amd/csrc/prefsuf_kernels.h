@@ -37,9 +37,13 @@ uint64_t probe_record_slack(int n_cu, uint64_t n_src, bool local);
 // source-side reduction: adjacency lists from the probe's out-degrees (rowptr = their scan), one-edge slots and record list
 // record_sources (device, may be null: every row is sorted): the ids of the only sources whose rows were filled from records, their number at
 // *record_sources_count (device), at most record_sources_cap
+// fused_scratch (option emit_fused; scan_scratch_bytes(n_src)): rowptr is not an input but made here -- the out-degrees are summed per tile, the tile sums
+// scanned (the 64-bit total at fused_scratch[scan_total_index(n_src)]) and one pass writes the row pointers and the slot edges; the out-degree of a source is
+// deg[i], or -- in a build the pile path kept (pile_cnt, may be null) -- what k_pile_probe left in bit 8 of first[i].  Null: rowptr is the scan of deg[]
 void launch_local_emit(int32_t src_base, int32_t n_src, const uint32_t *deg, const unsigned long long *first, const unsigned long long *second,
-                       const uint32_t *rec_dst, const unsigned long long *rec_val, uint64_t n_rec, const uint32_t *rowptr, uint32_t *cursor,
-                       alga_edge_dev *edges, const int32_t *record_sources, const unsigned long long *record_sources_count, uint32_t record_sources_cap, hipStream_t s, uint32_t slot_stride = 0);
+                       const uint32_t *rec_dst, const unsigned long long *rec_val, uint64_t n_rec, uint32_t *rowptr, uint32_t *cursor,
+                       alga_edge_dev *edges, const int32_t *record_sources, const unsigned long long *record_sources_count, uint32_t record_sources_cap, hipStream_t s, uint32_t slot_stride = 0,
+                       uint64_t *fused_scratch = nullptr, const unsigned long long *pile_cnt = nullptr);
 
 // clustered minimizer join (prefsuf_cluster.hip): source-side form with one-word offset masks (max_len - Lmin <= 63)
 bool       cluster_plan(const PrefSufCfg &cfg, int max_len, uint64_t live, int bucket_log2_bias, ClusterCfg *c, int *eq);   // false: this probe does not take the input

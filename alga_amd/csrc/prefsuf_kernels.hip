@@ -1029,31 +1029,24 @@ __global__ void __launch_bounds__(256) k_keys_to_edges(const unsigned long long 
 // clustered probe finishes two-edge sources in slots too); k_sort_rows orders the two.
 // slot_stride != 0 (round 5): a source with out-degree 3 .. LOCAL_SLOTS_MAX whose first slot is set has its further edges in second[(k - 2) * slot_stride + i]
 // (k_probe_stream finishes sources with up to that many standing items).
-__global__ void __launch_bounds__(256) k_local_emit_first(int32_t src_base, int32_t n_src, const uint32_t *__restrict__ deg,
-                                                           const unsigned long long *__restrict__ first, const unsigned long long *__restrict__ second,
-                                                           const uint32_t *__restrict__ rowptr, alga_edge_dev *__restrict__ edges, uint32_t slot_stride) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_src) return;
-    const uint32_t dg = deg[i];
-    if (dg == 0) return;
-    const unsigned long long f = first[i];
-    if (f == LOCAL_FIRST_NONE) return;
+// the edges of source i (out-degree dg, first slot f != LOCAL_FIRST_NONE) into its row edges[at ..), in (dst, offset) order
+__device__ __forceinline__ void local_emit_slots(int32_t src, size_t i, uint32_t dg, unsigned long long f, const unsigned long long *__restrict__ second,
+                                                 uint32_t at, alga_edge_dev *__restrict__ edges, uint32_t slot_stride) {
     alga_edge_dev e;
-    e.src = src_base + i; e.dst = (int32_t) (uint32_t) (f >> 32); e.offset = (int32_t) (uint32_t) f;
-    const uint32_t at = rowptr[i];
+    e.src = src; e.dst = (int32_t) (uint32_t) (f >> 32); e.offset = (int32_t) (uint32_t) f;
     edges[at] = e;
     if (dg >= 3u && dg <= (uint32_t) LOCAL_SLOTS_MAX && second != nullptr && slot_stride != 0u) {      // up to LOCAL_SLOTS_MAX slots: left in (dst, offset) order as well
         unsigned long long k[LOCAL_SLOTS_MAX];
         k[0] = f;
 #pragma unroll
-        for (int q = 1; q < LOCAL_SLOTS_MAX; q++) k[q] = (uint32_t) q < dg ? second[(size_t) (q - 1) * slot_stride + (size_t) i] : ~0ull;   // (dst in the high half: order by (dst, offset) == by value)
+        for (int q = 1; q < LOCAL_SLOTS_MAX; q++) k[q] = (uint32_t) q < dg ? second[(size_t) (q - 1) * slot_stride + i] : ~0ull;   // (dst in the high half: order by (dst, offset) == by value)
 #pragma unroll
         for (int a = 0; a < LOCAL_SLOTS_MAX; a++)          // odd-even transposition
 #pragma unroll
             for (int b = (a & 1); b + 1 < LOCAL_SLOTS_MAX; b += 2) { const unsigned long long lo = min(k[b], k[b + 1]), hi = max(k[b], k[b + 1]); k[b] = lo; k[b + 1] = hi; }
 #pragma unroll
         for (int q = 0; q < LOCAL_SLOTS_MAX; q++)
-            if ((uint32_t) q < dg) { alga_edge_dev x; x.src = src_base + i; x.dst = (int32_t) (uint32_t) (k[q] >> 32); x.offset = (int32_t) (uint32_t) k[q]; edges[at + q] = x; }
+            if ((uint32_t) q < dg) { alga_edge_dev x; x.src = src; x.dst = (int32_t) (uint32_t) (k[q] >> 32); x.offset = (int32_t) (uint32_t) k[q]; edges[at + q] = x; }
         return;
     }
     if (dg == 2u && second != nullptr) {                   // both slots: left in (dst, offset) order, so that such a row needs no k_sort_rows
@@ -1063,6 +1056,133 @@ __global__ void __launch_bounds__(256) k_local_emit_first(int32_t src_base, int3
         if (e2.dst < e.dst || (e2.dst == e.dst && e2.offset < e.offset)) { edges[at] = e2; e2 = e; }
         edges[at + 1] = e2;
     }
+}
+
+__global__ void __launch_bounds__(256) k_local_emit_first(int32_t src_base, int32_t n_src, const uint32_t *__restrict__ deg,
+                                                           const unsigned long long *__restrict__ first, const unsigned long long *__restrict__ second,
+                                                           const uint32_t *__restrict__ rowptr, alga_edge_dev *__restrict__ edges, uint32_t slot_stride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_src) return;
+    const uint32_t dg = deg[i];
+    if (dg == 0) return;
+    const unsigned long long f = first[i];
+    if (f == LOCAL_FIRST_NONE) return;
+    local_emit_slots(src_base + i, (size_t) i, dg, f, second, rowptr[i], edges, slot_stride);
+}
+
+// ------------------------------------------------------------------------------------------
+// The same rows in two passes over the slots (option emit_fused): nothing is moved to deg[] and no row pointer is read back.
+//   k_emit_tile_sums    the out-degrees of a tile of SCAN_TILE sources, summed
+//   k_scan_spine_serial exclusive prefix of the tile sums
+//   k_emit_scan_tiles   the tile's out-degrees again, their prefix = out_rowptr[], and the slot edges written where the prefix says
+// The out-degree of source i is a function of deg[i] and first[i] alone (k_pile_deg's rule, read instead of applied): a build the pile path
+// kept (pile_cnt: the sample's verdict, read on the device) has the out-degree of a source k_pile_probe finished in bit 8 of its slot, and
+// bit 8 stays there -- a pile slot's offset is its low byte.  Where the sample declined, or the build is not the piles' (pile_cnt null),
+// the slot of a source with deg[i] == 0 is stale and is not looked at.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t source_degree(uint32_t dg, bool piled, unsigned long long f) {
+    if (dg != 0u) return dg;                               // a source the pairwise kernels finished (deg and slot are theirs)
+    if (!piled || f == LOCAL_FIRST_NONE) return 0u;
+    return 1u + (uint32_t) ((f >> 8) & 1ull);
+}
+
+__global__ void __launch_bounds__(SCAN_BLOCK) k_emit_tile_sums(const uint32_t *__restrict__ deg, const unsigned long long *__restrict__ first, uint64_t n,
+                                                                const unsigned long long *__restrict__ pile_cnt, uint64_t *__restrict__ tile_sums) {
+    __shared__ uint32_t lds[8];
+    const bool piled = pile_cnt != nullptr && !pile_cnt_declines(pile_cnt);
+    const uint64_t base = (uint64_t) blockIdx.x * SCAN_TILE;
+    uint32_t s = 0;
+    if (base + SCAN_TILE <= n && (reinterpret_cast<uintptr_t>(deg) & 15u) == 0 && (reinterpret_cast<uintptr_t>(first) & 15u) == 0) {
+        constexpr int G = SCAN_ITEMS / 4;                  // 16-byte groups of deg[] per thread, two of first[] each
+        const uint4 *d4 = reinterpret_cast<const uint4 *>(deg + base);
+        const ulonglong2 *f2 = reinterpret_cast<const ulonglong2 *>(first + base);
+        uint4 v[G];
+#pragma unroll
+        for (int k = 0; k < G; k++) v[k] = d4[k * SCAN_BLOCK + threadIdx.x];
+#pragma unroll
+        for (int k = 0; k < G; k++) {
+            const int g = 2 * (k * SCAN_BLOCK + (int) threadIdx.x);
+            ulonglong2 a = make_ulonglong2(LOCAL_FIRST_NONE, LOCAL_FIRST_NONE), b = a;
+            if (piled && (v[k].x == 0u || v[k].y == 0u)) a = f2[g];
+            if (piled && (v[k].z == 0u || v[k].w == 0u)) b = f2[g + 1];
+            s += source_degree(v[k].x, piled, a.x) + source_degree(v[k].y, piled, a.y) + source_degree(v[k].z, piled, b.x) + source_degree(v[k].w, piled, b.y);
+        }
+    } else {
+        for (int k = 0; k < SCAN_ITEMS; k++) {
+            const uint64_t i = base + (uint64_t) k * SCAN_BLOCK + threadIdx.x;
+            if (i < n) { const uint32_t dg = deg[i]; s += source_degree(dg, piled, (piled && dg == 0u) ? first[i] : LOCAL_FIRST_NONE); }
+        }
+    }
+    uint32_t tot;
+    block_exclusive_scan(s, &tot, lds);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
+}
+
+// single workgroup: exclusive scan of the tile sums (64-bit), total written to tile_sums[n_tiles].  Every thread sums a contiguous stretch
+// of the tile sums, one block scan of the 1024 stretch sums, every thread writes the prefixes of its stretch.
+__global__ void __launch_bounds__(1024) k_scan_spine_serial(uint64_t *tile_sums, uint32_t n_tiles) {
+    __shared__ uint64_t lds[16];
+    const int lane = lane_id(), wave = (int) (threadIdx.x >> 6);
+    const uint64_t per = ((uint64_t) n_tiles + 1023u) / 1024u;
+    const uint64_t beg = min((uint64_t) threadIdx.x * per, (uint64_t) n_tiles), end = min(beg + per, (uint64_t) n_tiles);
+    uint64_t sum = 0;
+    for (uint64_t i = beg; i < end; i++) sum += tile_sums[i];
+    uint64_t inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t lo = (uint32_t) __shfl_up((int) (uint32_t) inc, o), hi = (uint32_t) __shfl_up((int) (uint32_t) (inc >> 32), o);
+        if (lane >= o) inc += ((uint64_t) hi << 32) | lo;
+    }
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    uint64_t run = inc - sum;
+    for (int w = 0; w < wave; w++) run += lds[w];
+    for (uint64_t i = beg; i < end; i++) { const uint64_t v = tile_sums[i]; tile_sums[i] = run; run += v; }
+    if (threadIdx.x == 1023) tile_sums[n_tiles] = run;      // (the last thread's stretch ends the array, or is empty behind it)
+}
+
+// A wave owns 64 * SCAN_ITEMS consecutive sources and walks them one source per lane and step: edges[at] of neighbouring lanes are neighbours.
+// out[n] = total (low 32 bits).
+__global__ void __launch_bounds__(SCAN_BLOCK) k_emit_scan_tiles(int32_t src_base, uint64_t n, const uint32_t *__restrict__ deg, const unsigned long long *__restrict__ first,
+                                                                 const unsigned long long *__restrict__ second, const unsigned long long *__restrict__ pile_cnt,
+                                                                 const uint64_t *__restrict__ tile_sums, uint32_t *__restrict__ out, alga_edge_dev *__restrict__ edges,
+                                                                 uint32_t slot_stride) {
+    __shared__ uint32_t lds[8];
+    const bool piled = pile_cnt != nullptr && !pile_cnt_declines(pile_cnt);
+    const int lane = lane_id(), wave = (int) (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t) blockIdx.x * SCAN_TILE + (uint64_t) wave * (64 * SCAN_ITEMS) + (uint64_t) lane;
+    uint32_t d[SCAN_ITEMS];                                // out-degrees
+    unsigned long long f[SCAN_ITEMS];                      // first slots, a pile slot's without its bit 8; "none" where nothing is written from the slots
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; k++) { const uint64_t i = wbase + 64u * k; d[k] = i < n ? deg[i] : 0u; }
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; k++) { const uint64_t i = wbase + 64u * k; f[k] = (i < n && (piled || d[k] != 0u)) ? first[i] : LOCAL_FIRST_NONE; }
+    uint32_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; k++) {
+        const uint32_t dk = source_degree(d[k], piled, f[k]);
+        if (d[k] == 0u && dk != 0u) f[k] &= 0xFFFFFFFF000000FFull;
+        d[k] = dk; sum += dk;
+    }
+    sum = (uint32_t) wave_sum_u64(sum);
+    if (lane == 0) lds[wave] = sum;
+    __syncthreads();
+    uint32_t run = (uint32_t) tile_sums[blockIdx.x];       // sources before step k of this wave
+    for (int w = 0; w < wave; w++) run += lds[w];
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; k++) {
+        const uint64_t i = wbase + 64u * k;
+        uint32_t inc = d[k];
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = (uint32_t) __shfl_up((int) inc, o); if (lane >= o) inc += t; }
+        const uint32_t at = run + inc - d[k];
+        run += (uint32_t) __shfl((int) inc, 63);
+        if (i < n) {
+            out[i] = at;
+            if (d[k] != 0u && f[k] != LOCAL_FIRST_NONE) local_emit_slots(src_base + (int32_t) i, (size_t) i, d[k], f[k], second, at, edges, slot_stride);
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = (uint32_t) tile_sums[gridDim.x];
 }
 
 // cursor[id - src_base] = 0 for the sources of a list (its length read from the device): the only cursors k_local_emit_records will touch
@@ -1312,15 +1432,24 @@ void launch_probe(const NodesDev &nd, const PrefSufCfg &cfg, const unsigned long
 }
 
 void launch_local_emit(int32_t src_base, int32_t n_src, const uint32_t *deg, const unsigned long long *first, const unsigned long long *second,
-                       const uint32_t *rec_dst, const unsigned long long *rec_val, uint64_t n_rec, const uint32_t *rowptr, uint32_t *cursor,
+                       const uint32_t *rec_dst, const unsigned long long *rec_val, uint64_t n_rec, uint32_t *rowptr, uint32_t *cursor,
                        alga_edge_dev *edges, const int32_t *record_sources, const unsigned long long *record_sources_count, uint32_t record_sources_cap, hipStream_t s,
-                       uint32_t slot_stride) {
-    if (n_src <= 0) return;
+                       uint32_t slot_stride, uint64_t *fused_scratch, const unsigned long long *pile_cnt) {
+    if (n_src <= 0) {
+        if (fused_scratch) launch_exclusive_scan(deg, 0, rowptr, fused_scratch, s);
+        return;
+    }
     // the cursors of the record rows start at zero: all of them, or those of the listed sources alone
     if (record_sources) hipLaunchKernelGGL(k_zero_cursors_list, dim3(std::min<unsigned>(grid_for((uint64_t) record_sources_cap, 256), 2048u)), dim3(256), 0, s, record_sources, record_sources_count,
                                            record_sources_cap, src_base, cursor);
     else (void) hipMemsetAsync(cursor, 0, (size_t) (n_src + 1) * sizeof(uint32_t), s);
-    hipLaunchKernelGGL(k_local_emit_first, dim3(grid_for((uint64_t) n_src, 256)), dim3(256), 0, s, src_base, n_src, deg, first, second, rowptr, edges, slot_stride);
+    if (fused_scratch) {
+        const uint32_t tiles = (uint32_t) (((uint64_t) n_src + SCAN_TILE - 1) / SCAN_TILE);
+        hipLaunchKernelGGL(k_emit_tile_sums, dim3(tiles), dim3(SCAN_BLOCK), 0, s, deg, first, (uint64_t) n_src, pile_cnt, fused_scratch);
+        hipLaunchKernelGGL(k_scan_spine_serial, dim3(1), dim3(1024), 0, s, fused_scratch, tiles);
+        hipLaunchKernelGGL(k_emit_scan_tiles, dim3(tiles), dim3(SCAN_BLOCK), 0, s, src_base, (uint64_t) n_src, deg, first, second, pile_cnt, (const uint64_t *) fused_scratch, rowptr, edges,
+                           slot_stride);
+    } else hipLaunchKernelGGL(k_local_emit_first, dim3(grid_for((uint64_t) n_src, 256)), dim3(256), 0, s, src_base, n_src, deg, first, second, (const uint32_t *) rowptr, edges, slot_stride);
     if (n_rec) {
         unsigned g = std::min<unsigned>(grid_for(n_rec, 256), 4096u);
         hipLaunchKernelGGL(k_local_emit_records, dim3(std::max(1u, g)), dim3(256), 0, s, src_base, rec_dst, rec_val, n_rec, rowptr, cursor, edges);

@@ -186,6 +186,10 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                a statistics build and "pile_skip_gather" 0 build the directory as before
  *   "pile_deg_fold"              default 1: the first pass of the out-degree scan moves the out-degrees k_pile_probe left in the sources' slots; 0: a
  *                                pass of its own (k_pile_deg) right behind the probe (A/B and tests)
+ *   "emit_fused"                 default 1: the source-side emit makes its rows in two passes over the out-degrees and slots (k_emit_tile_sums sums the
+ *                                out-degrees of a tile, k_emit_scan_tiles forms their prefix and writes row pointers and slot edges from it); an
+ *                                out-degree k_pile_probe left in a slot is read there and never moved to the out-degree array; 0: the scan of the
+ *                                out-degree array first, k_local_emit_first behind it (until round 8; A/B and tests)
  *   "pile_probe_lean"            default 1: k_pile_probe takes a source's row from its home run in slot 0 only and looks for the last mismatch
  *                                below position 64 only (a mismatch from 64 on clears the whole offset set); 0: the round-5 kernel (A/B and tests)
  *   "pile_stream_by_id"          1: a build the pile path keeps in its PURE form sends the sources k_pile_probe hands on through k_probe_stream (list
