@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "prefsuf_shard.h"
 
 using namespace alga;
 
@@ -763,7 +764,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
     } else if (!strcmp(name, "shard_bucket_max")) {
         e->opt_shard_dmax = (int) std::max<int64_t>(1, std::min<int64_t>(value, 4096));
     } else if (!strcmp(name, "rsort_variant")) {
-        rsort_set_variant((int) value);                    // tuning only (process-wide): tile shape of radix_sort.hip
+        // tuning only, and PROCESS-WIDE (not per engine): the tile shape of radix_sort.hip's (u32, u32) sort for every engine of this process
+        if (value < 0 || value > 1) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option rsort_variant: 0 tiles of 8192 pairs, 1 tiles of 16384 pairs");
+        rsort_set_variant((int) value);
     } else if (!strcmp(name, "stream_slots")) {
         e->opt_stream_slots = value >= 4 ? 4 : 2;
     } else if (!strcmp(name, "pile_range")) {
@@ -1406,14 +1409,16 @@ int alga_sort_edges_device(alga_engine *e, const alga_edge *d_edges, uint64_t n_
     return ALGA_OK;
 }
 
-// the (u32 key, u32 value) sort of the index build on its own (tests / tools): stable on the key bits [begin_bit, 32)
+// the (u32 key, u32 value) sort of the index build on its own (tests / tools): stable on the key bits [begin_bit, 32).  d_vals == NULL with own != 0:
+// the values are 0, 1, 2, ... (the index build's, the final-contig filter's and the supplement's form of the call)
 int alga_sort_u32_pairs_device(alga_engine *e, const uint32_t *d_keys, const uint32_t *d_vals, uint64_t n, int32_t begin_bit, int32_t own, int32_t repeat,
                                void *hip_stream, const uint32_t **d_keys_sorted, const uint32_t **d_vals_sorted, double *ms_best) {
     if (!e) return ALGA_ERR_INVALID_ARGUMENT;
     e->err.clear();
     if (!d_keys_sorted || !d_vals_sorted) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "output pointers must not be NULL");
     *d_keys_sorted = nullptr; *d_vals_sorted = nullptr;
-    if (n && (!d_keys || !d_vals)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "key / value arrays must not be NULL");
+    if (n && !d_keys) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "key / value arrays must not be NULL");
+    if (n && !d_vals && !own) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "value array must not be NULL for the library's sort (own = 0)");
     if (begin_bit < 0 || begin_bit > 31) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "begin_bit must be in [0, 31]");
     if (n >= (1ull << 32) - (1u << 16)) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 pairs");
     DeviceGuard guard;
@@ -1471,6 +1476,39 @@ int alga_sort_u64_pairs_device(alga_engine *e, const uint64_t *d_keys, const uin
     }
     if (ms_best) *ms_best = best;
     *d_keys_sorted = (const uint64_t *) e->pk_keys2.p; *d_vals_sorted = (const uint64_t *) e->pk_vals2.p;
+    return ALGA_OK;
+}
+
+// the (u32 key, u64 value) sort of the sharded build's run descriptors on its own (tests / tools): stable on the key bits [begin_bit, end_bit);
+// a window that is not one is [0, 32) (sort_desc)
+int alga_sort_desc_device(alga_engine *e, const uint32_t *d_keys, const uint64_t *d_vals, uint64_t n, int32_t begin_bit, int32_t end_bit, int32_t own, int32_t repeat,
+                          void *hip_stream, const uint32_t **d_keys_sorted, const uint64_t **d_vals_sorted, double *ms_best) {
+    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
+    e->err.clear();
+    if (!d_keys_sorted || !d_vals_sorted) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "output pointers must not be NULL");
+    *d_keys_sorted = nullptr; *d_vals_sorted = nullptr;
+    if (n && (!d_keys || !d_vals)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "key / value arrays must not be NULL");
+    if (n >= (1ull << 32) - (1u << 16)) return alga_fail(e, ALGA_ERR_CAPACITY, "more than 2^32 records");
+    DeviceGuard guard;
+    HIP_TRY(e, hipSetDevice(e->device));
+    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
+    int rc;
+    const size_t temp_bytes = sort_desc_temp_bytes(n);
+    if ((rc = alga_ensure(e, e->pk_keys2, (size_t) (n + 1) * sizeof(unsigned long long)))) return rc;      // (the buffers of alga_sort_u64_pairs_device)
+    if ((rc = alga_ensure(e, e->pk_vals2, (size_t) (n + 1) * sizeof(unsigned long long)))) return rc;
+    if ((rc = alga_ensure(e, e->sort_temp, temp_bytes))) return rc;
+    double best = 0.0;
+    for (int it = 0; it < std::max(1, repeat); it++) {
+        HIP_TRY(e, hipEventRecord(e->ev[EV_START], s));
+        HIP_TRY(e, sort_desc(e->sort_temp.p, temp_bytes, d_keys, (uint32_t *) e->pk_keys2.p, (const unsigned long long *) d_vals, (unsigned long long *) e->pk_vals2.p, n,
+                             begin_bit, end_bit, s, own != 0));
+        HIP_TRY(e, hipEventRecord(e->ev[EV_SORT], s));
+        HIP_TRY(e, hipStreamSynchronize(s));
+        const double ms = ev_ms(e, EV_START, EV_SORT);
+        best = it == 0 ? ms : std::min(best, ms);
+    }
+    if (ms_best) *ms_best = best;
+    *d_keys_sorted = (const uint32_t *) e->pk_keys2.p; *d_vals_sorted = (const uint64_t *) e->pk_vals2.p;
     return ALGA_OK;
 }
 

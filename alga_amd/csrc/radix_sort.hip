@@ -46,7 +46,7 @@ struct RsPlan {
     int tile = 8192;
 };
 
-int g_rs_variant = 0;                                      // tuning only (engine option "rsort_variant"): 0 = tiles of 8192 pairs (512 threads), 1 = 16384 (1024 threads)
+int g_rs_variant = 0;                                      // tuning only, process-wide (engine option "rsort_variant"): 0 = tiles of 8192 pairs (512 threads), 1 = 16384 (1024 threads)
 
 RsPlan rs_plan(uint64_t n, int begin_bit, int end_bit, int variant) {
     RsPlan p;
@@ -441,7 +441,9 @@ size_t rsort_u32_pairs_temp_bytes(uint64_t n) {
            2 * rs_align(RS_MAX_DIGITS * 4);
 }
 
-void rsort_set_variant(int v) { g_rs_variant = v; }
+// process-wide, tuning only.  Anything but 0 and 1 is ignored: rs_plan's variant 2 is the internal code of the 4096-record tiles, and rsort_u32_pairs
+// would plan those tiles (twice the tile_pref rows its temp reserves) while launching the 16384-pair kernels
+void rsort_set_variant(int v) { if (v == 0 || v == 1) g_rs_variant = v; }
 
 // stable sort of (key, value) on the key bits [begin_bit, 32); keys_in / vals_in are left untouched.  vals_in == nullptr: the values are 0, 1, 2, ...
 // (the sort of (key, id) pairs of the index build: 4 bytes per pair less to read in the first pass, and nobody has to write them)

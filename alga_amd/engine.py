@@ -171,7 +171,7 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_multi_create", "alga_multi_destroy", "alga_multi_last_error", "alga_multi_engine", "alga_multi_prefsuf_build_host", "alga_multi_prefsuf_build_device",
            "alga_multi_free_edges", "alga_multi_last_stats", "alga_multi_set_option", "alga_upload_twin_nodes",
            "alga_shard_index_device", "alga_shard_join_device", "alga_shard_small_keys_device", "alga_shard_resolve_device", "alga_shard_place_device",
-           "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
+           "alga_shard_last_stats", "alga_sort_u32_pairs_device", "alga_sort_u64_pairs_device", "alga_sort_desc_device", "alga_multi_pkb_supplement_device", "alga_pkb_shard_begin", "alga_pkb_shard_round", "alga_pkb_shard_merge", "alga_pkb_shard_end",
            "alga_prefsuf_build_host_compact", "alga_download_edges_compact", "alga_free_compact_edges", "alga_host_alloc", "alga_host_free",
            "alga_write_gfa_device", "alga_unitigs_device", "alga_write_unitig_gfa_device", "alga_remove_dangling_branches_device",
            "alga_remove_short_parallel_paths_device", "alga_unitig_consensus_device", "alga_write_consensus_fasta_device",
@@ -721,6 +721,8 @@ def load_library():
                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_double)]
     lib.alga_sort_u32_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_double)]
+    lib.alga_sort_desc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_double)]
     lib.alga_pkb_shard_begin.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(PkbParams), C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p]
     lib.alga_pkb_shard_round.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     lib.alga_pkb_shard_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -1233,10 +1235,11 @@ class Engine:
 
     def sort_u32_pairs_device(self, keys, vals, begin_bit=0, own=True, repeat=1, stream=None):
         """alga_sort_u32_pairs_device: (key, value) int32 / uint32 tensors on this device, stable on the key bits [begin_bit, 32) ->
-        (keys ptr, vals ptr, best ms).  own: the engine's radix sort (radix_sort.hip), else rocPRIM's."""
+        (keys ptr, vals ptr, best ms).  own: the engine's radix sort (radix_sort.hip), else rocPRIM's.  vals None (own only): the values are
+        0, 1, 2, ..."""
         n = int(keys.shape[0])
         ko, vo, ms = C.c_void_p(), C.c_void_p(), C.c_double()
-        self._check(self._lib.alga_sort_u32_pairs_device(self._h, keys.data_ptr() if n else None, vals.data_ptr() if n else None, n, int(begin_bit), int(bool(own)),
+        self._check(self._lib.alga_sort_u32_pairs_device(self._h, keys.data_ptr() if n else None, vals.data_ptr() if n and vals is not None else None, n, int(begin_bit), int(bool(own)),
                                                          int(repeat), C.c_void_p(stream or 0), C.byref(ko), C.byref(vo), C.byref(ms)))
         return ko.value, vo.value, ms.value
 
@@ -1246,6 +1249,15 @@ class Engine:
         ko, vo, ms = C.c_void_p(), C.c_void_p(), C.c_double()
         self._check(self._lib.alga_sort_u64_pairs_device(self._h, keys.data_ptr() if n else None, vals.data_ptr() if n else None, n, int(bits), int(bool(own)),
                                                          int(repeat), C.c_void_p(stream or 0), C.byref(ko), C.byref(vo), C.byref(ms)))
+        return ko.value, vo.value, ms.value
+
+    def sort_desc_device(self, keys, vals, begin_bit, end_bit, own=True, repeat=1, stream=None):
+        """alga_sort_desc_device: int32 / uint32 keys and int64 values on this device, stable on the key bits [begin_bit, end_bit) (a window that is
+        not one: [0, 32)) -> (keys ptr, vals ptr, best ms)"""
+        n = int(keys.shape[0])
+        ko, vo, ms = C.c_void_p(), C.c_void_p(), C.c_double()
+        self._check(self._lib.alga_sort_desc_device(self._h, keys.data_ptr() if n else None, vals.data_ptr() if n else None, n, int(begin_bit), int(end_bit),
+                                                    int(bool(own)), int(repeat), C.c_void_p(stream or 0), C.byref(ko), C.byref(vo), C.byref(ms)))
         return ko.value, vo.value, ms.value
 
     def sort_edges_device(self, edges, n_edges, n_nodes, stream=None):

@@ -477,13 +477,21 @@ int  alga_sort_records_device(alga_engine *e, const uint32_t *d_dst, const uint6
 /* The (u32 key, u32 value) sort of the index build on its own (tests and tools): stable on the key bits [begin_bit, 32).  own != 0: the
  * engine's radix sort (alga_amd/csrc/radix_sort.hip), 0: rocPRIM's.  For n < 2^22 the library path sorts on all 32 bits (its merge-sort path
  * compares the wrong bits for a partial key); the engine's own sort looks at [begin_bit, 32) whatever n is.  The sorted arrays are engine-owned
- * (valid until the next call on e); *ms_best = the fastest of `repeat` runs by HIP events. */
+ * (valid until the next call on e); *ms_best = the fastest of `repeat` runs by HIP events.  d_vals == NULL with own != 0: the values are the
+ * positions 0, 1, 2, ... (how the index build, the final-contig filter and the supplement call the sort); with own == 0 a NULL value array is
+ * ALGA_ERR_INVALID_ARGUMENT (rocPRIM needs values). */
 int  alga_sort_u32_pairs_device(alga_engine *e, const uint32_t *d_keys, const uint32_t *d_vals, uint64_t n, int32_t begin_bit, int32_t own, int32_t repeat,
                                 void *hip_stream, const uint32_t **d_keys_sorted, const uint32_t **d_vals_sorted, double *ms_best);
 /* The (u64 key, u64 value) sort of the supplement's k-mer entries on its own (tests and tools): stable on the key bits [0, bits); own != 0: the
  * engine's radix sort (bits <= 50), 0: rocPRIM's.  Replaces the std::sort of the reference's k-mer buckets (src/GraphCreators/GraphCreatorKmerBased.cpp:94-106). */
 int  alga_sort_u64_pairs_device(alga_engine *e, const uint64_t *d_keys, const uint64_t *d_vals, uint64_t n, int32_t bits, int32_t own, int32_t repeat,
                                 void *hip_stream, const uint64_t **d_keys_sorted, const uint64_t **d_vals_sorted, double *ms_best);
+/* The (u32 key, u64 value) sort of the bucket-sharded build's run descriptors on its own (tests and tools): stable on the key bits
+ * [begin_bit, end_bit); a window that is not one (begin_bit < 0, end_bit > 32, end_bit <= begin_bit) is [0, 32).  own != 0: the engine's radix sort
+ * (12-byte records, alga_amd/csrc/radix_sort.hip), 0: rocPRIM's, which for n < 2^22 sorts on all 32 bits (see alga_sort_u32_pairs_device).  The
+ * inputs are left untouched; the sorted arrays are engine-owned (valid until the next call on e). */
+int  alga_sort_desc_device(alga_engine *e, const uint32_t *d_keys, const uint64_t *d_vals, uint64_t n, int32_t begin_bit, int32_t end_bit, int32_t own,
+                           int32_t repeat, void *hip_stream, const uint32_t **d_keys_sorted, const uint64_t **d_vals_sorted, double *ms_best);
 int  alga_sort_edges_device(alga_engine *e, const alga_edge *d_edges, uint64_t n_edges, int32_t n_nodes,
                             void *hip_stream, const alga_edge **d_sorted);
 
