@@ -295,7 +295,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                 launch_pile_build(nd, cfg, cc, pp.uniform_len, (const uint32_t *) e->cl_keys[1].p, (const uint32_t *) e->cl_vals[1].p, e->cl_dir.p, e->cl_pile_rec.p, e->cl_pile_rec2.p, e->cl_pile_tab.p,
                                   e->pile_epoch, e->cl_pile_succ.p, e->cl_runs.p, pp.uniform_len - cfg.Lmin + 1, (const unsigned long long *) e->cl_pile_cnt.p,
                                   from_consensus ? (uint32_t *) e->cl_pile_own.p : nullptr, (from_consensus && e->opt_pile_runs_list) ? e->cl_pile_list.p : nullptr, s,
-                                  e->opt_pile_dir >= 1, cnt + CNT_TOTAL + 1, e->pile_tab_index);
+                                  e->opt_pile_dir >= 1, cnt + CNT_TOTAL + 1, e->pile_tab_index, e->opt_pile_runs_ahead != 0);
                 if ((rc = alga_check_launch(e, "k_pile_build"))) return rc;
                 if (keys_only) {
                     // own run lists of the entries outside a first group (6 % at the north-star size) ...
@@ -370,7 +370,7 @@ int discover_impl(alga_engine *e, const Prepared &pp, int32_t src_begin, int32_t
                     launch_pile_probe(nd, cfg, cc, pp.uniform_len, e->cl_pile_tab.p, e->pile_epoch, e->cl_pile_rec.p, e->cl_pile_rec2.p, e->cl_pile_succ.p,
                                       e->cl_runs.p, cnt, (uint32_t *) e->outdeg.p, (unsigned long long *) e->loc_first.p, (unsigned long long *) e->loc_second.p,
                                       (int32_t *) e->cl_defer.p, (uint32_t) n_src, (const unsigned long long *) e->cl_pile_cnt.p, e->n_cu, s, src_begin, src_end,
-                                      e->cl_pile_side_r.p, (unsigned long long *) e->cl_pile_cursor.p, e->opt_pile_probe_lean != 0);
+                                      e->cl_pile_side_r.p, (unsigned long long *) e->cl_pile_cursor.p, e->opt_pile_probe_lean != 0, e->opt_pile_probe_tail != 0);
                     if ((rc = alga_check_launch(e, "k_pile_probe"))) return rc;
                     // the sources it handed on have no run list of their own yet (the general kernel reads it): a list-driven key pass over the
                     // defer list, whose length the device knows
@@ -751,6 +751,10 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
         e->opt_emit_fused = value != 0;
     } else if (!strcmp(name, "pile_probe_lean")) {
         e->opt_pile_probe_lean = value != 0;
+    } else if (!strcmp(name, "pile_probe_tail")) {
+        e->opt_pile_probe_tail = value != 0;
+    } else if (!strcmp(name, "pile_runs_ahead")) {
+        e->opt_pile_runs_ahead = value != 0;
     } else if (!strcmp(name, "pile_stream_by_id")) {
         e->opt_pile_stream_by_id = value != 0;
     } else if (!strcmp(name, "pile_check")) {

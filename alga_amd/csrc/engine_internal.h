@@ -71,7 +71,9 @@ struct alga_engine {
     bool   pile_tab_index = false;                          // the last index build made the directory only for a build the pile path did not keep pure: the pairwise kernels of a pure build read the piles' table (bucket_record)
     int    opt_pile_stream_by_id = 0;                       // option "pile_stream_by_id": 1 = a build kept in the pure pile form sends what k_pile_probe hands on through k_probe_stream (list mode, entries by id) before the general kernel, 0 = to the general kernel at once (the default until the pass is measured)
     int    opt_pile_probe_lean = 1;                         // option "pile_probe_lean": 1 = k_pile_probe<true> (the source's row taken in slot 0 only, no last-mismatch search past position 63), 0 = k_pile_probe<false> (round 5)
-    bool   pile_deg_pending = false;                        // the last discovery left that move to finalize_local's scan
+    int    opt_pile_probe_tail = 1;                         // option "pile_probe_tail" (with pile_probe_lean): 1 = k_pile_probe<true, true> (the look-ups of a tile's one or two targets batched, the further groups' bucket words read an iteration ahead), 0 = the serial tail
+    int    opt_pile_runs_ahead = 0;                         // option "pile_runs_ahead": 1 = k_pile_runs_consensus_list reads its piles' records a round ahead of the work on them, 0 = round by round (the default: the look-ahead measured no gain)
+    bool   pile_deg_pending = false;                       // the last discovery left that move to finalize_local's scan
     int    opt_pile_check = 0;                              // option "pile_check" (tests): every node gets its own run list and every first-group member's is compared with its pile's clipped list (stats.pile_list_*)
     bool   expect_pairwise = false;                         // the pile path declined the build before this one: the next key pass makes every run list up front
     DevBuf cl_pile_side_r, cl_pile_cursor;                  // the side records of a source id range (k_pile_side_range), its block cursor

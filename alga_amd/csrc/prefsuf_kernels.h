@@ -97,7 +97,8 @@ void       launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const Cl
                              uint32_t *own_mask /* null: the piles' run lists from their outer members' own lists (round 4) */,
                              void *plist /* null: k_pile_runs_consensus finds the piles in the side records; else pile_list_bytes(n) of scratch */, hipStream_t s,
                              bool from_keys = false /* as for the sample; the kernel then carries k_tgt_dir's order check */, unsigned long long *bad_flag = nullptr,
-                             bool full_record = false /* option pile_dir = 2: the records of the buckets of more than 64 entries complete (count, class offsets): a pure build has no directory */);
+                             bool full_record = false /* option pile_dir = 2: the records of the buckets of more than 64 entries complete (count, class offsets): a pure build has no directory */,
+                             bool runs_ahead = false /* option pile_runs_ahead: k_pile_runs_consensus_list reads its piles' records a round ahead */);
 void       launch_pile_own_ids(const uint32_t *own_mask, const uint32_t *sids, uint64_t n_entries, int32_t *list, uint32_t cap, unsigned long long *pile_cnt, hipStream_t s);
 void       launch_pile_check(const void *side, uint64_t n_entries, uint32_t n_buckets, const void *tab, const void *rec2, uint32_t epoch, const void *runs, int n_nodes, int nwin,
                              unsigned long long *pile_cnt, hipStream_t s);
@@ -113,7 +114,7 @@ void       launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const Cl
                              const void *runs, unsigned long long *counters, uint32_t *deg, unsigned long long *first, unsigned long long *second, int32_t *defer_list,
                              uint32_t defer_cap, const unsigned long long *pile_cnt, int n_cu, hipStream_t s, int32_t src_begin, int32_t src_end,
                              void *side_range /* a range that is not all nodes: (src_end - src_begin + 64) * 16 B of scratch */, unsigned long long *cursor /* ... and a word */,
-                             bool lean = true /* option pile_probe_lean */);
+                             bool lean = true /* option pile_probe_lean */, bool tail = false /* option pile_probe_tail (with lean) */);
 
 // radix_sort.hip: the engine's own stable LSD radix sort of (u32 key, u32 value) pairs on the key bits [begin_bit, 32)
 size_t     rsort_u32_pairs_temp_bytes(uint64_t n);

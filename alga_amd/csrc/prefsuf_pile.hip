@@ -499,22 +499,31 @@ constexpr int PR_TKW = 21;
 constexpr int PR_RCAP = 14;                                // raw runs of a pile's extent (the eight a list holds after the seams are merged + a run per seam)
 constexpr int PR_SEGS = 32;                                // k_pile_build workgroups (their pile lists) per block of k_pile_runs_consensus_list (~1000 piles at 30x: eight rounds of 128)
 
-// pile `who` (a bucket, or a further group's slot | bit 31; `in`: the thread has one) -> its run list.  row: the thread's row in LDS, word k at row[k * RS]
-// (RW > 0: RW words, node_runs_core reads the rest as zero)
+// pile `who` (a bucket, or a further group's slot | bit 31; `in`: the thread has one) -> its run list, in two parts: what is READ of the pile
+// (pile_consensus_load: the four 16-byte words of its consensus with the mirrored offset set, and word 16 of a first group's line -- nothing this
+// kernel writes for ANOTHER pile, so the list-driven kernel may ask for it a round ahead), and the list made of it and stored
+// (pile_consensus_make).  row: the thread's row in LDS, word k at row[k * RS] (RW > 0: RW words, node_runs_core reads the rest as zero)
+__device__ __forceinline__ void pile_consensus_load(uint32_t who, const uint4 *__restrict__ tab, const uint4 *__restrict__ rec, uint4 &l0, uint4 &l1, uint4 &l2, uint4 &l3, uint32_t &w16) {
+    const bool further = (who >> 31) != 0u;                // a further group of its bucket: consensus in rec
+    const uint4 *src = further ? rec + (size_t) (who & 0x7FFFFFFFu) * 4 : tab + (size_t) who * 8;
+    l0 = src[0]; l1 = src[1]; l2 = src[2]; l3 = src[3];
+    // (entries | ...: pile_list_store keeps its low byte.  One unconditional load -- a further group reads word 0 of its record once more and
+    // never looks at it -- and nothing computed from it here: a branch or a select at this point waits for the loads just issued)
+    w16 = reinterpret_cast<const uint32_t *>(src)[further ? 0 : 16];
+}
+
 template <int RS, int RW>
-__device__ __forceinline__ void pile_consensus_one(uint32_t who, bool in, uint32_t *row, uint32_t (*stk)[TK_ROWS], uint16_t (*rbuf)[TK_ROWS], int t, const uint4 *__restrict__ side,
-                                                   uint64_t n_entries, uint4 *__restrict__ tab, const uint4 *__restrict__ rec, uint4 *__restrict__ rec2, const ClusterCfg &cc, int U,
-                                                   int Lmin, uint32_t *__restrict__ own_mask) {
+__device__ __forceinline__ void pile_consensus_make(uint32_t who, bool in, const uint4 l0, const uint4 l1, const uint4 l2, const uint4 l3, const uint32_t w16, uint32_t *row, uint32_t (*stk)[TK_ROWS], uint16_t (*rbuf)[TK_ROWS], int t,
+                                                    const uint4 *__restrict__ side, uint64_t n_entries, uint4 *__restrict__ tab, uint4 *__restrict__ rec2, const ClusterCfg &cc, int U,
+                                                    int Lmin, uint32_t *__restrict__ own_mask) {
     const int fs = cc.idx_shift - CL_MBITS;
     const int step = max(16, min(64, cc.w) & ~15);         // windows per piece of the sweep: no more than w, whole row words (w >= 16 for every shape pile_plan takes)
     const bool further = (who >> 31) != 0u;                // a further group of its bucket: consensus in rec, list into rec2
     const uint32_t slot = who & 0x7FFFFFFFu;
     uint4 *line = tab + (size_t) (further ? 0u : who) * 8;
-    const uint4 *src = further ? rec + (size_t) slot * 4 : (const uint4 *) line;
     uint32_t S[PILE_SW + 1];
     unsigned long long rm = 0ull;
     {
-        const uint4 l0 = src[0], l1 = src[1], l2 = src[2], l3 = src[3];
         S[0] = l0.x; S[1] = l0.y; S[2] = l0.z; S[3] = l0.w; S[4] = l1.x; S[5] = l1.y; S[6] = l1.z; S[7] = l1.w;
         S[8] = l2.x; S[9] = l2.y; S[10] = l2.z; S[11] = l2.w; S[12] = l3.x; S[13] = 0u;
         rm = !in ? 0ull : (further ? (((unsigned long long) l3.w << 32) | l3.z) : (((unsigned long long) l3.z << 32) | l3.y));
@@ -584,13 +593,14 @@ __device__ __forceinline__ void pile_consensus_one(uint32_t who, bool in, uint32
         }
     } else if (in) {
         uint32_t *lw = reinterpret_cast<uint32_t *>(line);
-        pile_list_store(line, lw[16], ok, n, key_, kc_, (uint32_t) (nwin - m_max + 64));
+        uint32_t entries = w16;
+        asm volatile("" : "+v"(entries));                  // (looked at HERE: computed from where it was loaded, the word read a round ahead is waited for at once)
+        pile_list_store(line, entries, ok, n, key_, kc_, (uint32_t) (nwin - m_max + 64));
         if (!ok) {
             // no list (3 piles in 1000: a window without a class-0 k-mer somewhere on the extent, mostly): the members probe with their OWN
             // lists, as the entries outside a first group do -- noted in own_mask for the list-driven key pass that follows.  (Marking the
             // bucket irregular instead sent every source with a run in it to the general kernel: 1.7 M more sources at the north-star size.)
-            lw[16] = lw[16] & 255u;
-            const uint32_t cntb = min(lw[16] & 255u, 64u), e0b = lw[17];
+            const uint32_t cntb = min(entries & 255u, 64u), e0b = lw[17];           // (pile_list_store left entries & 255 in word 16)
             for (uint32_t i2 = 0; i2 < cntb; i2++) {
                 const uint64_t j2 = (uint64_t) e0b + i2;
                 if (j2 < n_entries) { const uint4 s2 = side[j2]; if ((s2.z >> 31) && ((s2.z >> 16) & 3u) == 0u) atomicOr(&own_mask[j2 >> 5], 1u << (j2 & 31u)); }
@@ -625,14 +635,19 @@ __global__ void __launch_bounds__(TK_ROWS) k_pile_runs_consensus(const uint4 *__
     const int np = (int) sN;
     for (int c0 = 0; c0 < np; c0 += TK_ROWS) {             // uniform
         const bool in = c0 + t < np;
-        pile_consensus_one<1, 0>(sList[in ? c0 + t : 0], in, s[t], stk, rbuf, t, side, n_entries, tab, rec, rec2, cc, U, Lmin, own_mask);
+        const uint32_t who = sList[in ? c0 + t : 0];
+        uint4 l0, l1, l2, l3;
+        uint32_t w16;
+        pile_consensus_load(who, tab, rec, l0, l1, l2, l3, w16);
+        pile_consensus_make<1, 0>(who, in, l0, l1, l2, l3, w16, s[t], stk, rbuf, t, side, n_entries, tab, rec2, cc, U, Lmin, own_mask);
     }
 }
 
 // the piles k_pile_build listed: workgroup b of that kernel left its own in plist[b * PB_THREADS ..] and their number in pcount[b]
 __global__ void __launch_bounds__(TK_ROWS) k_pile_runs_consensus_list(const uint32_t *__restrict__ plist, const uint32_t *__restrict__ pcount, uint32_t n_segs, const uint4 *__restrict__ side,
                                                                       uint64_t n_entries, uint4 *__restrict__ tab, const uint4 *__restrict__ rec, uint4 *__restrict__ rec2, ClusterCfg cc,
-                                                                      int U, int Lmin, const unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask) {
+                                                                      int U, int Lmin, const unsigned long long *__restrict__ pile_cnt, uint32_t *__restrict__ own_mask,
+                                                                      int ahead /* option pile_runs_ahead */) {
     if (pile_declines(pile_cnt)) return;
     __shared__ uint32_t s[PILE_SW][TK_ROWS];               // word-major: thread t's row is s[.][t] (conflict-free without padding)
     __shared__ uint32_t stk[2 * (NR_STACK + 1)][TK_ROWS];
@@ -650,14 +665,41 @@ __global__ void __launch_bounds__(TK_ROWS) k_pile_runs_consensus_list(const uint
     }
     __syncthreads();
     const int np = (int) sOff[PR_SEGS];
-    for (int c0 = 0; c0 < np; c0 += TK_ROWS) {             // uniform
+    auto who_of = [&](int c0) -> uint32_t {                // the pile of this thread in the round that starts at c0 (0: none)
         const int i = c0 + t;
-        const bool in = i < np;
         int g = 0;                                         // the segment that holds pile i: the last g with sOff[g] <= i
 #pragma unroll
         for (int b = PR_SEGS / 2; b >= 1; b >>= 1) g += (g + b <= PR_SEGS - 1 && (int) sOff[g + b] <= i) ? b : 0;
-        const uint32_t who = in ? plist[(size_t) (seg0 + (uint32_t) g) * PB_THREADS + (uint32_t) (i - (int) sOff[g])] : 0u;
-        pile_consensus_one<TK_ROWS, PILE_SW>(who, in, &s[0][t], stk, rbuf, t, side, n_entries, tab, rec, rec2, cc, U, Lmin, own_mask);
+        return i < np ? plist[(size_t) (seg0 + (uint32_t) g) * PB_THREADS + (uint32_t) (i - (int) sOff[g])] : 0u;
+    };
+    if (!ahead) {                                          // uniform: every round reads its piles, then works on them
+        for (int c0 = 0; c0 < np; c0 += TK_ROWS) {         // uniform
+            const uint32_t who = who_of(c0);
+            uint4 l0, l1, l2, l3;
+            uint32_t w16;
+            pile_consensus_load(who, tab, rec, l0, l1, l2, l3, w16);
+            pile_consensus_make<TK_ROWS, PILE_SW>(who, c0 + t < np, l0, l1, l2, l3, w16, &s[0][t], stk, rbuf, t, side, n_entries, tab, rec2, cc, U, Lmin, own_mask);
+        }
+        return;
+    }
+    // A round's chain is plist -> the pile's record (a random 128-byte line) -> ~2000 vector instructions -> the store, and with nothing of the
+    // next round on its way a wave waits out both reads every round.  One round of look-ahead in registers: before round r is worked on, the
+    // list entry of round r + 2 and the records of round r + 1 are asked for (`who` two rounds ahead, or plist -> record stays a chain).
+    // What is read ahead are words 0 .. 16 of OTHER piles' lines -- k_pile_build wrote them, and word 16 of a line changes only in the hands of
+    // the thread that owns the pile, later; this kernel writes words 16 .. 31 of its own piles' lines, and rec2.
+    if (np <= 0) return;
+    uint32_t who1 = who_of(0), who2 = who_of(TK_ROWS);
+    uint4 n0, n1, n2, n3;                                  // the record of the round to come
+    uint32_t nw;
+    pile_consensus_load(who1, tab, rec, n0, n1, n2, n3, nw);
+    for (int c0 = 0; c0 < np; c0 += TK_ROWS) {             // uniform
+        const uint32_t who = who1;
+        const uint4 l0 = n0, l1 = n1, l2 = n2, l3 = n3;
+        const uint32_t w16 = nw;
+        who1 = who2;                                       // (asked for a round ago: the records first, so that they do not wait for the list entry behind them)
+        if (c0 + TK_ROWS < np) pile_consensus_load(who1, tab, rec, n0, n1, n2, n3, nw);     // uniform (a thread without a pile in that round: line 0, unused)
+        if (c0 + 2 * TK_ROWS < np) who2 = who_of(c0 + 2 * TK_ROWS);            // uniform
+        pile_consensus_make<TK_ROWS, PILE_SW>(who, c0 + t < np, l0, l1, l2, l3, w16, &s[0][t], stk, rbuf, t, side, n_entries, tab, rec2, cc, U, Lmin, own_mask);
     }
 }
 
@@ -772,7 +814,16 @@ constexpr bool PP_HOME_ANY_SLOT = true;                    // (slots not shifted
 #else
 constexpr bool PP_HOME_ANY_SLOT = false;
 #endif
-template <bool LEAN>
+// TAIL (engine option "pile_probe_tail", with LEAN) changes WHEN the end of a tile asks for memory, nothing it decides.  A wave's tile is a
+// chain of dependent round trips, and two stretches of it ran load by load under divergence:
+//   * the look-up of the one or two targets that stand (a bucket line's second half, then the side records of the offset's m_C >> 3 class one
+//     at a time, and all of it again for a second item): both items' runs are picked in one pass over the slots, both bucket lines are asked
+//     for back to back by the whole wave (a lane without a look-up reads the sentinel line), and the first PP_TAIL_K candidates of both classes
+//     in one batch -- two round trips; a class of more entries (regular at 120x) takes further batches in a wave-uniform loop;
+//   * the further groups of a run's tag: the bucket's first entry (word 17 of its line) and then the group's record were two round trips per
+//     iteration; the word of a lane's next pending (slot, group) is asked for an iteration ahead, the first one beside the next tile's run lists.
+constexpr int PP_TAIL_K = 4;                               // candidates of a class per batch and item
+template <bool LEAN, bool TAIL>
 __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg cfg, ClusterCfg cc, int U, NodesDev nd, uint64_t n_entries, uint64_t n_mine, int n_nodes,
                                                                  const uint4 *__restrict__ tab, uint32_t epoch, const uint4 *__restrict__ rec, const uint4 *__restrict__ rec2,
                                                                  const uint4 *__restrict__ side, const uint4 *__restrict__ side_src, const uint2 *__restrict__ runs, ProbeOut o,
@@ -1074,15 +1125,26 @@ __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg
         got_row = got_row || home;
         take_record(li * PP_LSTRIDE, ((unsigned long long) R3.z << 32) | R3.y, a, 0u, ry[a], on, home);
     }
+    dfr = dfr || (active && !got_row);                     // (cannot happen: a first-group member's home run wants its bucket's first group)
+    // the further groups that share a run's tag (another k-mer of the bucket with the same tag, or the run's own k-mer when it is not the
+    // bucket's first): at most one of a slot's groups holds the source's k-mer
+    more = dfr ? 0u : more;
+    // (TAIL) the first entry of the bucket of a lane's first pending (slot, group) in `m`; a lane with none reads the sentinel line
+    auto first_entry_of = [&](uint32_t m) -> uint32_t {
+        const int a = m != 0u ? __builtin_ctz(m) >> 2 : 0;
+        uint32_t ka = 0u;                                  // (OR of masked words: as a chain of selects this becomes an indexed array in scratch)
+#pragma unroll
+        for (int k = 0; k < CL_RMAX; k++) ka |= rk[k] & (0u - (uint32_t) (a == k));
+        return reinterpret_cast<const uint32_t *>(tab)[(size_t) (m != 0u ? min(ka >> cc.idx_shift, cc.n_buckets) : cc.n_buckets) * 32 + 17];
+    };
+    // (no branch around either of these loads: behind a join the compiler's wait for ANY load waits for all of them)
+    uint32_t xa_next = 0u;
+    if constexpr (TAIL) xa_next = first_entry_of(more);
     {                                                      // the next tile's run lists: on their way while this tile's targets are looked up
         const uint4 *rp = run_list_of(next_side);
 #pragma unroll
         for (int c = 0; c < CL_RMAX / 2; c++) Qr[c] = rp[c];
     }
-    dfr = dfr || (active && !got_row);                     // (cannot happen: a first-group member's home run wants its bucket's first group)
-    // the further groups that share a run's tag (another k-mer of the bucket with the same tag, or the run's own k-mer when it is not the
-    // bucket's first): at most one of a slot's groups holds the source's k-mer
-    more = dfr ? 0u : more;
     while (__ballot(more != 0u) != 0ull) {                 // uniform
         const bool on = more != 0u;
         const int bit = on ? __builtin_ctz(more) : 0;
@@ -1092,9 +1154,10 @@ __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg
         uint32_t ya = ry[0], ka = rk[0];
 #pragma unroll
         for (int k = 1; k < CL_RMAX; k++) { ya = a == k ? ry[k] : ya; ka = a == k ? rk[k] : ka; }
-        const uint32_t xa = reinterpret_cast<const uint32_t *>(tab)[(size_t) min(ka >> cc.idx_shift, cc.n_buckets) * 32 + 17];      // first entry of the bucket
+        const uint32_t xa = TAIL ? xa_next : reinterpret_cast<const uint32_t *>(tab)[(size_t) min(ka >> cc.idx_shift, cc.n_buckets) * 32 + 17];      // first entry of the bucket
         const uint64_t se = min((uint64_t) xa + g, last);  // (clamped: a corrupt record must not fault)
         const uint4 Q0 = rec[se * 4], Q1 = rec[se * 4 + 1], Q2 = rec[se * 4 + 2], Q3 = rec[se * 4 + 3];
+        if constexpr (TAIL) xa_next = first_entry_of(more);                            // the next iteration's, behind this one's record in the queue
         uint4 *mine = reinterpret_cast<uint4 *>(sl + lane * PP_LSTRIDE);              // (the slot loop is done with the records in LDS)
         mine[0] = Q0; mine[1] = Q1; mine[2] = Q2; mine[3] = Q3;
         wave_lds_fence();
@@ -1128,6 +1191,60 @@ __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg
     };
     // every source position writes its slot exactly once (no fill in front of this kernel): the edge(s), or "none" -- also for a source that
     // goes to the general kernel, which overwrites it if the source has edges
+    uint32_t lk_id1 = 0xFFFFFFFFu, lk_id2 = 0xFFFFFFFFu;   // (TAIL) what lookup() gives for the first and the second item
+    if constexpr (TAIL) {
+        const bool fin = active && !dfr && nkept > 0;
+        const int d1 = fin ? __builtin_ctzll(kept) : 0, d2 = (fin && nkept == 2) ? 63 - __clzll((long long) kept) : 0;
+        // which items need a look-up (the first unless it is the member k_pile_build noted: by_succ below), and their runs in one pass over the slots
+        uint32_t y1 = 0u, k1 = 0u, g1 = 0u, y2 = 0u, k2 = 0u, g2 = 0u;
+        int p1_home = 0;
+#pragma unroll
+        for (int k = 0; k < CL_RMAX; k++) {
+            const bool v = ((vmask >> k) & 1u) != 0u;
+            const int p0 = (int) ((ry[k] >> 8) & 255u), p1 = (int) ((ry[k] >> 16) & 255u);
+            const uint32_t gk = (grp >> (2 * k)) & 3u;
+            p1_home = (v && p0 == 0) ? p1 : p1_home;
+            const bool in1 = v && d1 >= p0 && d1 < p1, in2 = v && d2 >= p0 && d2 < p1;
+            y1 = in1 ? ry[k] : y1; k1 = in1 ? rk[k] : k1; g1 = in1 ? gk : g1;
+            y2 = in2 ? ry[k] : y2; k2 = in2 ? rk[k] : k2; g2 = in2 ? gk : g2;
+        }
+        const bool need1 = fin && !(d1 < p1_home && (int) (my.z & 255u) == d1 && my.y != 0xFFFFFFFFu), need2 = fin && nkept == 2;
+        if (__ballot(need1 || need2) != 0ull) {            // uniform: the whole wave takes part, a lane without a look-up on the sentinel line
+            uint4 dd1 = tab[(size_t) (need1 ? min(k1 >> cc.idx_shift, cc.n_buckets) : cc.n_buckets) * 8 + 4];      // {entries | ..., first entry, class offsets}
+            uint4 dd2 = tab[(size_t) (need2 ? min(k2 >> cc.idx_shift, cc.n_buckets) : cc.n_buckets) * 8 + 4];
+            // (opaque: left to itself the compiler moves the load of a word behind the branch that uses it -- a round trip of its own again)
+            asm volatile("" : "+v"(dd1.x), "+v"(dd1.y), "+v"(dd1.z), "+v"(dd1.w), "+v"(dd2.x), "+v"(dd2.y), "+v"(dd2.z), "+v"(dd2.w));
+            // the member with m_C == q - d among the entries [b0, min(b1, 64)) of its m_C >> 3 class
+            auto class_of = [&](const uint4 &dd, int mm, bool need, uint32_t &b0, uint32_t &b1) {
+                const int cl = (mm >> 3) & 7;
+                b0 = ((cl < 4 ? dd.z : dd.w) >> (8 * (cl & 3))) & 255u;
+                b1 = cl >= 7 ? (dd.x & 127u) : ((((cl + 1) < 4 ? dd.z : dd.w) >> (8 * ((cl + 1) & 3))) & 255u);
+                b1 = need ? min(b1, 64u) : 0u;
+                b0 = need ? b0 : 0u;
+            };
+            const int mm1 = (int) (y1 & 255u) - d1, mm2 = (int) (y2 & 255u) - d2;
+            uint32_t e1, e1_end, e2, e2_end;
+            class_of(dd1, mm1, need1, e1, e1_end);
+            class_of(dd2, mm2, need2, e2, e2_end);
+            do {                                           // uniform: batches of PP_TAIL_K candidates of both items (the last match wins, as in lookup)
+                uint32_t cx1[PP_TAIL_K], cz1[PP_TAIL_K], cx2[PP_TAIL_K], cz2[PP_TAIL_K];
+#pragma unroll
+                for (int i = 0; i < PP_TAIL_K; i++) {      // (clamped: a load for nothing hits the entry array)
+                    const uint4 *c1 = side + min((uint64_t) dd1.y + e1 + (uint32_t) i, last), *c2 = side + min((uint64_t) dd2.y + e2 + (uint32_t) i, last);
+                    cx1[i] = c1->x; cz1[i] = c1->z; cx2[i] = c2->x; cz2[i] = c2->z;
+                }
+                static_assert(PP_TAIL_K == 4, "the batch is pinned word by word");
+                asm volatile("" : "+v"(cx1[0]), "+v"(cz1[0]), "+v"(cx1[1]), "+v"(cz1[1]), "+v"(cx1[2]), "+v"(cz1[2]), "+v"(cx1[3]), "+v"(cz1[3]),
+                                  "+v"(cx2[0]), "+v"(cz2[0]), "+v"(cx2[1]), "+v"(cz2[1]), "+v"(cx2[2]), "+v"(cz2[2]), "+v"(cx2[3]), "+v"(cz2[3]));
+#pragma unroll
+                for (int i = 0; i < PP_TAIL_K; i++) {
+                    if (e1 + (uint32_t) i < e1_end && (int) ((cz1[i] >> 8) & 63u) == mm1 && ((cz1[i] >> 16) & 3u) == g1) lk_id1 = cx1[i];
+                    if (e2 + (uint32_t) i < e2_end && (int) ((cz2[i] >> 8) & 63u) == mm2 && ((cz2[i] >> 16) & 3u) == g2) lk_id2 = cx2[i];
+                }
+                e1 += PP_TAIL_K; e2 += PP_TAIL_K;
+            } while (__ballot(e1 < e1_end || e2 < e2_end) != 0ull);
+        }
+    }
     unsigned long long slot_val = LOCAL_FIRST_NONE;
     if (active && !dfr && nkept > 0) {
         const int d1 = __builtin_ctzll(kept);
@@ -1137,25 +1254,13 @@ __global__ void __launch_bounds__(PP_WAVES * 64, PP_OCC) k_pile_probe(PrefSufCfg
 #pragma unroll
         for (int k = 0; k < CL_RMAX; k++) p1_home = (((vmask >> k) & 1u) != 0u && ((ry[k] >> 8) & 255u) == 0u) ? (int) ((ry[k] >> 16) & 255u) : p1_home;
         const bool by_succ = d1 < p1_home && (int) (my.z & 255u) == d1 && my.y != 0xFFFFFFFFu;
-#ifdef PP_LK
-        const int d2 = nkept == 2 ? 63 - __clzll((long long) kept) : -1;
-        const int dA = by_succ ? d2 : d1, dB = by_succ ? -1 : d2;
-        uint32_t idA = 0xFFFFFFFFu, idB = 0xFFFFFFFFu;
-        if (dA >= 0) idA = lookup(dA);
-        if (dB >= 0) idB = lookup(dB);
-        const uint32_t id1 = by_succ ? my.y : idA;
-        const uint32_t id2 = by_succ ? idA : idB;
-        bool two = false;
-        if (nkept == 2) {
-#else
-        const uint32_t id1 = by_succ ? my.y : lookup(d1);
+        const uint32_t id1 = by_succ ? my.y : (TAIL ? lk_id1 : lookup(d1));
         uint32_t id2 = 0u;
         int d2 = 0;
         bool two = false;
         if (nkept == 2) {
             d2 = 63 - __clzll((long long) kept);
-            id2 = lookup(d2);
-#endif
+            id2 = TAIL ? lk_id2 : lookup(d2);
             // the cap of three small overlaps per source: the second item stands if it is big or fewer than three small items lie before it
             const int ds0 = U - cfg.rsoemo + 1;
             const unsigned long long lowm = ds0 <= 0 ? 0ull : (ds0 >= 64 ? ~0ull : ((1ull << ds0) - 1ull));
@@ -1247,7 +1352,7 @@ void launch_pile_sample(const NodesDev &nd, const ClusterCfg &cc, int uniform_le
 // plist != null (with own_mask): k_pile_build lists its piles per workgroup and k_pile_runs_consensus_list takes them from there (pile_list_bytes)
 void launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const uint32_t *skeys, const uint32_t *sids, const void *dir, void *rec, void *rec2,
                        void *tab, uint32_t epoch, void *side, const void *runs, int nwin, const unsigned long long *pile_cnt, uint32_t *own_mask, void *plist, hipStream_t s,
-                       bool from_keys, unsigned long long *bad_flag, bool full_record) {
+                       bool from_keys, unsigned long long *bad_flag, bool full_record, bool runs_ahead) {
     const uint64_t n_entries = nd.n > 0 ? (uint64_t) nd.n : 0;
     if (n_entries == 0) return;
     const uint64_t tiles = (n_entries + PB_TILE - 1) / PB_TILE;
@@ -1259,7 +1364,7 @@ void launch_pile_build(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterC
                        (uint4 *) rec, (uint4 *) tab, epoch, (uint4 *) side, const_cast<unsigned long long *>(pile_cnt), own_mask, pl, pc, bad_flag, full_record ? 1u : 0u);
     if (pl)
         hipLaunchKernelGGL(k_pile_runs_consensus_list, dim3((unsigned) ((tiles + PR_SEGS - 1) / PR_SEGS)), dim3(TK_ROWS), 0, s, (const uint32_t *) pl, (const uint32_t *) pc, (uint32_t) tiles,
-                           (const uint4 *) side, n_entries, (uint4 *) tab, (const uint4 *) rec, (uint4 *) rec2, cc, uniform_len, cfg.Lmin, pile_cnt, own_mask);
+                           (const uint4 *) side, n_entries, (uint4 *) tab, (const uint4 *) rec, (uint4 *) rec2, cc, uniform_len, cfg.Lmin, pile_cnt, own_mask, runs_ahead ? 1 : 0);
     else if (own_mask)
         hipLaunchKernelGGL(k_pile_runs_consensus, dim3((unsigned) ((n_entries + PR_TILE - 1) / PR_TILE)), dim3(TK_ROWS), 0, s, (const uint4 *) side, n_entries, cc.n_buckets, (uint4 *) tab,
                            (const uint4 *) rec, (uint4 *) rec2, cc, uniform_len, cfg.Lmin, pile_cnt, own_mask);
@@ -1333,7 +1438,7 @@ __global__ void __launch_bounds__(256) k_pile_side_range(const uint4 *__restrict
 void launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterCfg &cc, int uniform_len, const void *tab, uint32_t epoch, const void *rec, const void *rec2,
                        const void *side, const void *runs, unsigned long long *counters, uint32_t *deg, unsigned long long *first, unsigned long long *second,
                        int32_t *defer_list, uint32_t defer_cap, const unsigned long long *pile_cnt, int n_cu, hipStream_t s, int32_t src_begin, int32_t src_end,
-                       void *side_range, unsigned long long *cursor, bool lean) {
+                       void *side_range, unsigned long long *cursor, bool lean, bool tail) {
     const uint64_t n_entries = nd.n > 0 ? (uint64_t) nd.n : 0;
     if (n_entries == 0 || src_end <= src_begin) return;
     ProbeOut o{};
@@ -1349,7 +1454,7 @@ void launch_pile_probe(const NodesDev &nd, const PrefSufCfg &cfg, const ClusterC
     }
     const uint64_t tiles = (n_mine + PP_WAVES * 64 - 1) / (PP_WAVES * 64);
     const dim3 grid((unsigned) std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t) std::max(1, n_cu) * (PP_OCC * 4 / PP_WAVES)))), block(PP_WAVES * 64);      // PP_OCC waves per SIMD, four SIMDs per CU
-    hipLaunchKernelGGL(lean ? k_pile_probe<true> : k_pile_probe<false>, grid, block, 0, s, cfg, cc, uniform_len, nd, n_entries, n_mine, nd.n, (const uint4 *) tab, epoch, (const uint4 *) rec, (const uint4 *) rec2,
+    hipLaunchKernelGGL((lean ? (tail ? k_pile_probe<true, true> : k_pile_probe<true, false>) : k_pile_probe<false, false>), grid, block, 0, s, cfg, cc, uniform_len, nd, n_entries, n_mine, nd.n, (const uint4 *) tab, epoch, (const uint4 *) rec, (const uint4 *) rec2,
                        (const uint4 *) side, (const uint4 *) side_src, (const uint2 *) runs, o, defer_list, defer_cap, pile_cnt);
 }
 

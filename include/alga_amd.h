@@ -192,6 +192,13 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                out-degree array first, k_local_emit_first behind it (until round 8; A/B and tests)
  *   "pile_probe_lean"            default 1: k_pile_probe takes a source's row from its home run in slot 0 only and looks for the last mismatch
  *                                below position 64 only (a mismatch from 64 on clears the whole offset set); 0: the round-5 kernel (A/B and tests)
+ *   "pile_probe_tail"            default 1 (with "pile_probe_lean" 1): the end of a tile of k_pile_probe asks for memory in batches -- the look-ups of a
+ *                                source's one or two standing targets share two round trips (both bucket lines, then four candidates of both m_C
+ *                                classes; further batches while a class has more), and the first entry of a further group's bucket is read an
+ *                                iteration ahead of the group's record; 0: load by load, as until round 9 (A/B and tests).  Decides nothing
+ *   "pile_runs_ahead"            1: k_pile_runs_consensus_list asks for the records of its next round of piles (and the list entries of the
+ *                                round after) before it works on the round at hand; default 0: every round reads its piles, then works on them -- at the
+ *                                north-star size the look-ahead changed the kernel's time by less than the spread of two runs.  Computes nothing else
  *   "pile_stream_by_id"          1: a build the pile path keeps in its PURE form sends the sources k_pile_probe hands on through k_probe_stream (list
  *                                mode) before the general kernel, as the mixed form does -- the entries taken by id from the sorted (key, id) pairs, since
  *                                the pure form has no entry array; alga_prefsuf_stats.pile_deferred is then what the pile kernel handed on and
