@@ -215,6 +215,15 @@ struct alga_engine {
     DevBuf      br_span, br_ccols, br_cfirst, br_clast, br_tcuts, br_poff, br_begin, br_len, br_ptarget, br_pstart, br_words;
     bool        br_valid = false;                  // the result buffers hold a break result
     uint64_t    br_targets = 0, br_pieces = 0, br_cuts = 0, br_columns = 0, br_longest = 0;   // ... of this many targets, pieces, cuts, columns; the longest piece
+    // contig ends grown with the reads that hang over them (engine_grow.hip).  Workspaces: counters, the candidate flags, their scan and the
+    // list, the end lengths and their scan, the end sequences, the (k-mer, end column) pairs before and after the sort, the directory, the
+    // per-wave seed masks, the growth per end and its bases.  The result, twice: a call writes the set that is not the current one and
+    // swaps it in at its end, so a call that fails anywhere leaves the earlier result as it was
+    DevBuf      gr_cnt, gr_flag, gr_pos, gr_cand, gr_elen, gr_eoff, gr_ecols, gr_keys[2], gr_vals[2], gr_dir, gr_ub, gr_x, gr_g;
+    struct GrowSet { DevBuf end, over, mm, hits, state, count, estop, evoters, left, right, len, coloff, begin, words; } gr_set[2];
+    int         gr_cur = 0;                        // the set that holds the result
+    bool        gr_valid = false;
+    uint64_t    gr_reads = 0, gr_targets = 0, gr_columns = 0, gr_longest = 0;   // ... of this many reads, targets and columns; the longest grown target
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

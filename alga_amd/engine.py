@@ -181,7 +181,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_place_default_params", "alga_place_reads_device", "alga_place_reads_on_final_device", "alga_write_final_fasta_depth_device",
            "alga_polish_default_params", "alga_polish_placed_device", "alga_write_polished_fasta_device",
            "alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device",
-           "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device"]
+           "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device",
+           "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -638,6 +639,73 @@ def cuts_tsv(h):
     return "".join(lines)
 
 
+GROW_OVERHANGS, GROW_VOTES, GROW_MINUS = 1, 2, 4                   # bits of Grown.state
+
+
+class GrowParams(C.Structure):
+    """alga_grow_params"""
+    _fields_ = [(k, C.c_int32) for k in ("k", "max_mismatches", "max_occ", "min_anchor", "min_cover", "min_percent", "max_grow", "flags")] + [("reserved", C.c_int32 * 4)]
+
+
+class GrowInfo(C.Structure):
+    """alga_grow_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("candidates", "overhanging", "voting", "multi", "hits_saturated", "seeds", "seeds_over_max_occ", "index_positions",
+                                          "ends_with_voters", "ends_grown", "bases_added", "longest_growth", "stops_cover", "stops_percent", "stops_max",
+                                          "columns_before", "columns_after", "n50_before", "n50_after")] + \
+               [(k, C.c_double) for k in ("ms_index", "ms_place", "ms_build", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GrownC(C.Structure):
+    """alga_grown"""
+    _fields_ = [(k, C.c_int64) for k in ("n_reads", "n_targets", "max_grow")] + [("n_columns", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_end", "d_over", "d_mm", "d_hits", "d_state", "d_count", "d_e_stop", "d_e_voters", "d_left", "d_right", "d_len", "d_col_off",
+                                          "d_begin", "d_words")]
+
+
+class Grown:
+    """Result of Engine.grow_ends: zero-copy torch views of the engine's device memory (valid until the next Engine.grow_ends call on that
+    engine; clone what has to live longer) -- per read end / over int32, mm / hits / state uint8; count int32 [2 * n_targets * max_grow * 4] (the
+    bits of uint32); e_stop uint8, e_voters int32 [2 * n_targets]; left / right / len int32 [n_targets], col_off int32 [n_targets + 1], begin
+    int64 [n_targets], words int32 [(n_columns + 15) / 16 + 2] (the result's own copy of the bases) -- and .info (dict of alga_grow_info)."""
+    KEYS = (("end", "<i4", np.int32, "r"), ("over", "<i4", np.int32, "r"), ("mm", "|u1", np.uint8, "r"), ("hits", "|u1", np.uint8, "r"), ("state", "|u1", np.uint8, "r"),
+            ("count", "<i4", np.uint32, "c"), ("e_stop", "|u1", np.uint8, "e"), ("e_voters", "<i4", np.uint32, "e"), ("left", "<i4", np.uint32, "t"),
+            ("right", "<i4", np.uint32, "t"), ("len", "<i4", np.int32, "t"), ("col_off", "<i4", np.uint32, "t1"), ("begin", "<i8", np.uint64, "t"),
+            ("words", "<i4", np.uint32, "w"))
+
+    def __init__(self, c, info, device, placements=None):
+        self._c, self.info, self._placements = c, info, placements
+        self.n_reads, self.n_targets, self.max_grow, self.n_columns = int(c.n_reads), int(c.n_targets), int(c.max_grow), int(c.n_columns)
+        dev = "cuda:%d" % device
+        size = dict(r=self.n_reads, c=8 * self.n_targets * self.max_grow, e=2 * self.n_targets, t=self.n_targets, t1=self.n_targets + 1,
+                    w=(self.n_columns + 15) // 16 + 2)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/grow_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+    def targets(self):
+        """(words, begin int64 [n_targets], len int32 [n_targets]): the grown targets as the ragged target set Engine.place_reads(targets=...)
+        takes (the tensors are the engine's)"""
+        return self.words, self.begin, self.len
+
+    def grow_tsv(self, host=None):
+        """one line per target: contig, left, right, voters_left, voters_right, stop_left, stop_right (tabs); the text alga_hip --grow_layout= writes"""
+        return grow_tsv(host if host is not None else self.to_host())
+
+
+def grow_tsv(h):
+    """the growth of a grow result read back (Grown.to_host())"""
+    return "".join("%d\t%d\t%d\t%d\t%d\t%d\t%d\n" % (t, int(h["left"][t]), int(h["right"][t]), int(h["e_voters"][2 * t]), int(h["e_voters"][2 * t + 1]),
+                                                       int(h["e_stop"][2 * t]), int(h["e_stop"][2 * t + 1])) for t in range(len(h["len"])))
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -792,6 +860,11 @@ def load_library():
     lib.alga_break_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.POINTER(PlacementsC), C.POINTER(PolishedC), C.POINTER(BreakParams), C.c_void_p,
                                              C.POINTER(BrokenC), C.POINTER(BreakInfo)]
     lib.alga_write_broken_fasta_device.argtypes = [C.c_void_p, C.POINTER(BrokenC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_grow_default_params.argtypes = [C.POINTER(GrowParams)]
+    lib.alga_grow_default_params.restype = None
+    lib.alga_grow_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(PlacementsC), C.POINTER(PolishedC), C.POINTER(GrowParams), C.c_void_p,
+                                            C.POINTER(GrownC), C.POINTER(GrowInfo)]
+    lib.alga_write_grown_fasta_device.argtypes = [C.c_void_p, C.POINTER(GrownC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1816,6 +1889,45 @@ class Engine:
         records): `>contig_id=<j>_length=<len>_from=<t>_start=<s>` per piece with a length, j the piece id."""
         info = GfaInfo()
         self._check(self._lib.alga_write_broken_fasta_device(self._h, C.byref(broken._c), os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    def grow_ends(self, words, lens, placements, polished=None, stream=None, **params):
+        """The ends of the placed targets grown with the unplaced reads that hang over them (alga_grow_placed_device) -> Grown.  words / lens:
+        the node set that was placed; placements: the result of the LAST Engine.place_reads call; polished: the result of the LAST
+        Engine.polish of those placements -- the grown targets then carry the polished bases.  params: k, max_mismatches, max_occ, min_anchor,
+        min_cover, min_percent, max_grow (the fields of alga_grow_params; the library's defaults where not given).  A further round is a
+        placement on Grown.targets() and a further call."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = GrowParams(), GrownC(), GrowInfo()
+        self._lib.alga_grow_default_params(C.byref(pp))
+        for k, v in params.items():
+            if k not in ("k", "max_mismatches", "max_occ", "min_anchor", "min_cover", "min_percent", "max_grow", "flags"):
+                raise TypeError("Engine.grow_ends: unknown parameter %r" % k)
+            setattr(pp, k, int(v))
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_grow_placed_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(polished._c) if polished is not None else None,
+                                                      C.byref(pp), st, C.byref(out), C.byref(info)))
+        return Grown(out, info.as_dict(), self.device, placements)
+
+    def write_grown_fasta(self, path, grown):
+        """The grown targets of the LAST Engine.grow_ends call as FASTA (alga_write_grown_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>contig_id=<t>_length=<len>_left=<xl>_right=<xr>` per target with a length."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_grown_fasta_device(self._h, C.byref(grown._c), os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

@@ -81,6 +81,16 @@
 // --polish=1 the pieces carry the polished bases.  With --scaffolds= the same reads are placed a second time, on the pieces, and the scaffolds and
 // their layout come from that placement (contig ids there are piece ids).  Without a proper pair nothing is cut, with a message: every contig is
 // one piece.  Without --break_misjoins=1 every file is what it was.  None is passed through.
+// --grow_ends=N (rounds, 0 .. 16, default 0; needs --contigs_final=; implies the placement): the ends of the contigs (with --break_misjoins=1: of
+// the pieces, on which the reads are then placed also without --scaffolds=) grow with the unplaced reads that hang over them (alga_grow_placed_device:
+// --grow_min_anchor= (63), --grow_max_mismatches= (2), --grow_min_cover= (3), --grow_min_percent= (80), --grow_max= (64)).  A round is a grow on
+// the current placement and then a placement of the same reads on the grown contigs; the rounds end early when one adds no base.  They run
+// behind the break and before the scaffolder: the scaffolds and their layout come from the last placement.  With --polish=1 the first round
+// takes the polished bases (unless the break already carried them into the pieces); later rounds grow what the round before left.
+// --grown=PATH: the contigs after the last round that ran, `>contig_id=<t>_length=<len>_left=<xl>_right=<xr>` with xl / xr that round's growth
+// (alga_write_grown_fasta_device); --grow_layout=PATH: one line `contig left right voters_left voters_right stop_left stop_right` per contig of
+// that round, tab separated (both need --grow_ends >= 1).  One line on stderr per round gives candidates / voting reads / ends grown / bases
+// added / N50 before -> after.  Without --grow_ends every file is what it was.  None is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -106,7 +116,9 @@ static const char *USAGE =
     "         [--correct_reads=0|1] [--correct_k=21 (odd, 5 .. 31)] [--correct_solid=3] [--corrected_reads=reads.fasta]\n"
     "         [--contigs_depth=0|1] [--placements=placements.tsv] [--polish=0|1] [--polish_changes=changes.tsv]\n"
     "         [--scaffolds=scaffolds.fasta] [--scaffold_layout=layout.tsv] [--scaffold_min_links=5] [--scaffold_min_gap=10] [--scaffold_max_second_percent=50]\n"
-    "         [--break_misjoins=0|1] [--break_min_span=1] [--break_inset=21] [--break_margin=N] [--broken=pieces.fasta] [--break_cuts=cuts.tsv]\n";
+    "         [--break_misjoins=0|1] [--break_min_span=1] [--break_inset=21] [--break_margin=N] [--broken=pieces.fasta] [--break_cuts=cuts.tsv]\n"
+    "         [--grow_ends=N] [--grown=grown.fasta] [--grow_layout=grow.tsv] [--grow_min_anchor=63] [--grow_max_mismatches=2] [--grow_min_cover=3]\n"
+    "         [--grow_min_percent=80] [--grow_max=64]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -131,6 +143,10 @@ int main(int argc, char **argv) {
     std::string broken, break_cuts;
     alga_break_params brp;
     alga_break_default_params(&brp);
+    int grow_ends = 0;
+    std::string grown, grow_layout;
+    alga_grow_params grp;
+    alga_grow_default_params(&grp);
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -177,6 +193,14 @@ int main(int argc, char **argv) {
         else if (opt(a, "--break_margin", v)) { break_margin = atoi(v.c_str()); break_margin_given = true; }
         else if (opt(a, "--broken", v)) broken = v;
         else if (opt(a, "--break_cuts", v)) break_cuts = v;
+        else if (opt(a, "--grow_ends", v)) grow_ends = atoi(v.c_str());
+        else if (opt(a, "--grown", v)) grown = v;
+        else if (opt(a, "--grow_layout", v)) grow_layout = v;
+        else if (opt(a, "--grow_min_anchor", v)) grp.min_anchor = atoi(v.c_str());
+        else if (opt(a, "--grow_max_mismatches", v)) grp.max_mismatches = atoi(v.c_str());
+        else if (opt(a, "--grow_min_cover", v)) grp.min_cover = atoi(v.c_str());
+        else if (opt(a, "--grow_min_percent", v)) grp.min_percent = atoi(v.c_str());
+        else if (opt(a, "--grow_max", v)) grp.max_grow = atoi(v.c_str());
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -194,7 +218,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && strncmp(a, "--break_", 8) && strncmp(a, "--broken=", 9) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && strncmp(a, "--break_", 8) && strncmp(a, "--broken=", 9) && strncmp(a, "--grow", 6) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -214,6 +238,15 @@ int main(int argc, char **argv) {
     if (!break_misjoins && (!broken.empty() || !break_cuts.empty())) { fprintf(stderr, "alga_hip: --broken= and --break_cuts= need --break_misjoins=1\n"); return 2; }
     if (brp.min_span < 1 || brp.inset < 0 || brp.inset > (1 << 20) || break_margin < 0 || break_margin > (1 << 20)) {
         fprintf(stderr, "alga_hip: --break_min_span must be >= 1, --break_inset and --break_margin in [0, 2^20]\n");
+        return 2;
+    }
+    if (grow_ends < 0 || grow_ends > 16) { fprintf(stderr, "alga_hip: --grow_ends must be in [0, 16] (got %d)\n", grow_ends); return 2; }
+    if (grow_ends && contigs_final.empty()) { fprintf(stderr, "alga_hip: --grow_ends= needs --contigs_final=\n"); return 2; }
+    if (!grow_ends && (!grown.empty() || !grow_layout.empty())) { fprintf(stderr, "alga_hip: --grown= and --grow_layout= need --grow_ends >= 1\n"); return 2; }
+    if (grp.min_anchor < grp.k || grp.min_anchor > (1 << 20) || grp.max_mismatches < 0 || grp.max_mismatches > 254 || grp.min_cover < 1 || grp.min_percent < 51 ||
+        grp.min_percent > 100 || grp.max_grow < 1 || grp.max_grow > 4096) {
+        fprintf(stderr, "alga_hip: --grow_min_anchor must be in [21, 2^20], --grow_max_mismatches in [0, 254], --grow_min_cover >= 1, --grow_min_percent in [51, 100], "
+                        "--grow_max in [1, 4096]\n");
         return 2;
     }
     if (correct_reads && !alga_exe.empty()) {
@@ -507,7 +540,7 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
-                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins)) {
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins || grow_ends)) {
                     // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
                     alga_parsed_reads pr{};
                     char perr[512] = {0};
@@ -628,7 +661,7 @@ int main(int argc, char **argv) {
                             }
                             if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", break_cuts.c_str()); return 1; }
                         }
-                        if (rc == ALGA_OK && !scaffolds.empty() && have) {    // the same reads on the pieces (the break result keeps its own copy of the bases)
+                        if (rc == ALGA_OK && (!scaffolds.empty() || grow_ends) && have) {    // the same reads on the pieces (the break result keeps its own copy of the bases)
                             rc = alga_place_reads_device(engine, &pnd, (const uint8_t *) d_po, bk.d_words, bk.d_begin, bk.d_len, (int32_t) bk.n_pieces, &pp, nullptr, &pl2, &pi2);
                             if (rc == ALGA_OK) {
                                 fprintf(stderr, "Reads placed on the pieces: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
@@ -637,6 +670,56 @@ int main(int argc, char **argv) {
                                         (long long) pi2.insert_median, pi2.ms_total);
                                 spl = &pl2; spi = &pi2; spol = nullptr;         // (a polish is already in the pieces' bases)
                             }
+                        }
+                    }
+                    alga_placements pl3;
+                    alga_place_info pi3;
+                    if (rc == ALGA_OK && grow_ends) {
+                        alga_grown gw{};
+                        for (int round = 1; round <= grow_ends; round++) {
+                            alga_grow_info gi;
+                            rc = alga_grow_placed_device(engine, &pnd, spl, spol, &grp, nullptr, &gw, &gi);
+                            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot grow the contig ends: %s (status %d)\n", alga_last_error(engine), rc); return 1; }
+                            fprintf(stderr, "Contig ends grown, round %d: %llu candidates, %llu voting, %llu ends grown, %llu bases added, N50 %llu -> %llu; %llu overhanging "
+                                    "(%llu at several places), %llu ends with voters, stops: %llu cover %llu percent %llu max, longest growth %llu, %llu -> %llu columns; "
+                                    "device ms: index %.3f place %.3f build %.3f, call %.1f ms wall\n", round, (unsigned long long) gi.candidates,
+                                    (unsigned long long) gi.voting, (unsigned long long) gi.ends_grown, (unsigned long long) gi.bases_added, (unsigned long long) gi.n50_before,
+                                    (unsigned long long) gi.n50_after, (unsigned long long) gi.overhanging, (unsigned long long) gi.multi, (unsigned long long) gi.ends_with_voters,
+                                    (unsigned long long) gi.stops_cover, (unsigned long long) gi.stops_percent, (unsigned long long) gi.stops_max,
+                                    (unsigned long long) gi.longest_growth, (unsigned long long) gi.columns_before, (unsigned long long) gi.columns_after, gi.ms_index, gi.ms_place,
+                                    gi.ms_build, gi.ms_total);
+                            if (!gi.bases_added) break;                         // the contigs are what the current placement was made on
+                            // the same reads on the grown contigs (the grow result keeps its own copy of the bases)
+                            rc = alga_place_reads_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, gw.d_words, gw.d_begin, gw.d_len, (int32_t) gw.n_targets, &pp,
+                                                         nullptr, &pl3, &pi3);
+                            if (rc != ALGA_OK) break;
+                            fprintf(stderr, "Reads placed on the grown contigs: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
+                                    "median insert %lld; call %.1f ms wall\n", (unsigned long long) pi3.reads, (unsigned long long) pi3.placed, (unsigned long long) pi3.unique,
+                                    (unsigned long long) pi3.multi, (unsigned long long) pi3.unplaced, (unsigned long long) pi3.pairs_proper, (unsigned long long) pi3.pairs,
+                                    (long long) pi3.insert_median, pi3.ms_total);
+                            spl = &pl3; spi = &pi3; spol = nullptr;             // (a polish is already in the grown bases)
+                        }
+                        if (rc == ALGA_OK && !grown.empty()) {
+                            alga_gfa_info ggi;
+                            rc = alga_write_grown_fasta_device(engine, &gw, grown.c_str(), &ggi);
+                            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", grown.c_str(), alga_last_error(engine), rc); return 1; }
+                            fprintf(stderr, "Grown contigs written -> %s: %llu records, %llu bytes\n", grown.c_str(), (unsigned long long) ggi.segments, (unsigned long long) ggi.bytes);
+                        }
+                        if (rc == ALGA_OK && !grow_layout.empty()) {         // not a hot path: the host formats from the arrays that came back
+                            const size_t nt = (size_t) gw.n_targets;
+                            std::vector<uint32_t> left(nt), right(nt), voters(2 * nt);
+                            std::vector<uint8_t> stop(2 * nt);
+                            if (nt) {
+                                rc = alga_copy_to_host(engine, left.data(), gw.d_left, nt * sizeof(uint32_t));
+                                if (rc == ALGA_OK) rc = alga_copy_to_host(engine, right.data(), gw.d_right, nt * sizeof(uint32_t));
+                                if (rc == ALGA_OK) rc = alga_copy_to_host(engine, voters.data(), gw.d_e_voters, 2 * nt * sizeof(uint32_t));
+                                if (rc == ALGA_OK) rc = alga_copy_to_host(engine, stop.data(), gw.d_e_stop, 2 * nt);
+                            }
+                            FILE *f = rc == ALGA_OK ? fopen(grow_layout.c_str(), "w") : nullptr;
+                            if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", grow_layout.c_str()); return 1; }
+                            for (size_t t = 0; f && t < nt; t++)
+                                fprintf(f, "%zu\t%u\t%u\t%u\t%u\t%d\t%d\n", t, left[t], right[t], voters[2 * t], voters[2 * t + 1], (int) stop[2 * t], (int) stop[2 * t + 1]);
+                            if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", grow_layout.c_str()); return 1; }
                         }
                     }
                     if (rc == ALGA_OK && !scaffolds.empty()) {

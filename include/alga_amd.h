@@ -1516,6 +1516,95 @@ int  alga_break_placed_device(alga_engine *e, const alga_nodes *nodes, const uin
                               alga_break_info *info /* may be NULL */);
 int  alga_write_broken_fasta_device(alga_engine *e, const alga_broken *brk, const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- contig ends grown with the reads that hang over them (alga_amd/csrc/grow_kernels.hip, engine_grow.hip) ---------------------------------
+ * Every stage after the consensus keeps, joins, cuts or orders contigs; none adds a base.  The placement rule has 0 <= p <= len[t] - L, so a
+ * read that hangs over a contig end comes out unplaced.  Here the unplaced reads are laid over the contig ends, the columns beyond each end
+ * are voted, and each end grows while the vote is clear.  No mates, no joining.  Integers only, free of any order (thread, atomics, sort);
+ * tests/grow_checker.py states the rule twice in Python and the device result equals it array for array.  place -> [polish] -> [break ->
+ * place] -> grow -> place on the grown targets -> scaffold; a further round is a further call.
+ *
+ * Inputs: the node set that was placed (twin layout: node 2r + 1 is read r, node 2r its reverse complement), the engine's current placement
+ * result `pl` (from either placement call), optionally the current polish `pol` of that placement (the bases are then pol->d_words instead of
+ * the column array the placement kept), and alga_grow_params: k 8 .. 31 (default 21), max_mismatches 0 .. 254 (2), max_occ 1 .. 65535 (256),
+ * min_anchor k .. 2^20 (63 = k * (max_mismatches + 1): by pigeonhole the seed condition of item 4 then follows from the Hamming bound),
+ * min_cover 1 .. 2^31 - 1 (3), min_percent 51 .. 100 (80: above 50, so the winning base is unique), max_grow 1 .. 4096 (64), flags 0,
+ * reserved 0; anything else answers ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. End sequences.  Lmax is the largest len over all nodes (0 where none has a length).  Target t of length n has two ends, e = 2t (left)
+ *      and e = 2t + 1 (right); W_e = max(0, min(n, Lmax - 1)).  E_{2t+1} is the last W_e bases of t, E_{2t} the reverse complement of the
+ *      first W_e bases of t: in both the contig end is at the right.  A left overhang of a node is by definition the right overhang of its
+ *      twin on E_{2t}; both nodes of every read are tried, so every physical alignment appears exactly once.
+ *   2. Index.  Position q of E_e is indexed for 0 <= q <= W_e - k; no k-mer spans two end sequences.  occ(x) = the number of indexed
+ *      positions over all ends whose k-mer is x.
+ *   3. Candidates.  Read r is a CANDIDATE iff its state in `pl` lacks ALGA_PLACE_PLACED and len >= min_anchor + 1.
+ *   4. Overhang placements.  For node v of a candidate, of length L, (e, h) is an overhang placement iff, with a = L - h: h >= 1 and
+ *      min_anchor <= a <= W_e; mm, the Hamming distance between v[0 .. a) and the last a bases of E_e, is <= max_mismatches; some seed j of v
+ *      (bases jk .. jk + k - 1) with (j + 1) k <= a is USABLE (1 <= occ <= max_occ) and equals the corresponding k-mer of E_e exactly.  A
+ *      placement is a distinct triple (e, h, strand), strand 0 for node 2r + 1 and 1 for node 2r.
+ *   5. Per read.  best = the smallest (mm, e, h, strand); hits = the number of placements with mm == best.mm, saturated at 255.  d_state:
+ *      ALGA_GROW_OVERHANGS, ALGA_GROW_VOTES (iff hits == 1), ALGA_GROW_MINUS (best.strand); d_end (-1 where the read does not overhang),
+ *      d_over (h, else 0), d_mm, d_hits.
+ *   6. Votes.  A voting read with best (e, h) on node v gives base v[a + i] one vote at growth column i of end e, 0 <= i < min(h, max_grow):
+ *      d_count[(e * max_grow + i) * 4 + b], uint32.  cover = the sum over b.
+ *   7. Decision.  x_e = the number of leading columns i = 0, 1, .. that PASS: cover >= min_cover and 100 * count[w] >= min_percent * cover
+ *      (64-bit products), w the base with the largest count; g_e[i] = w.  d_e_stop[e] says why column x_e failed: 0 = no further column or
+ *      cover below min_cover (an end without any voter has 0), 1 = the percentage (a disagreement: a branch, a second haplotype),
+ *      2 = x_e == max_grow.  d_e_voters[e] = the reads voting at end e.
+ *   8. Grown targets.  Target t becomes the reverse complement of g_{2t}[0 .. x_{2t}), then t, then g_{2t+1}[0 .. x_{2t+1}).  A target
+ *      shorter than min_anchor, an empty one too, never grows (item 4).  d_left[t] = x_{2t} (where old column 0 now lies), d_right[t] =
+ *      x_{2t+1}, d_len[t] the new length, d_col_off [n_targets + 1] their exclusive scan, d_begin[t] = col_off[t], d_words the result's OWN
+ *      copy in column space (the polish's layout, (n_columns + 15) / 16 + 2 words, the bits past n_columns zero).  (d_words, d_begin, d_len,
+ *      n_targets) is a target set as alga_place_reads_device takes it.  ALGA_ERR_CAPACITY, before anything of that size is allocated: more
+ *      than 2^32 - 2 new columns, a new length above 2^31 - 1, 2 * n_targets * max_grow > 2^30, more than 2^32 - 2 bases in the end sequences.
+ *   9. Counters (alga_grow_info): candidates, overhanging, voting, multi (= overhanging - voting), hits_saturated; seeds (of the candidates'
+ *      nodes: the j with (j + 1) k <= L - 1), seeds_over_max_occ, index_positions; ends_with_voters, ends_grown, bases_added, longest_growth;
+ *      stops_cover, stops_percent, stops_max (the ends by d_e_stop: they sum to 2 * n_targets); columns_before, columns_after; n50_before,
+ *      n50_after (the scaffold's N50, on the host from lengths read back only when `info` is given); ms_index (check, candidates, end
+ *      sequences, keys, sort, directory), ms_place (k_gr_place), ms_build (votes, decision, scan, build) (HIP events), ms_total (wall).
+ *  10. Result (alga_grown; engine-owned, valid until the next grow call on `e`: a later placement, polish, break or scaffold call does not
+ *      invalidate it, a refused call leaves an earlier result valid: a call writes a second set of buffers and swaps it in at its end).
+ *      Refusals, all before anything of the result is written.  On the host, as alga_break_placed_device: `pl` is not the engine's current
+ *      placement result, judged by its buffers and all its sizes; nodes->n / 2 != pl.n_reads; `pol` is given but is not the current polish of
+ *      this placement.  On the device (k_gr_check, one read-back): the twin property fails or a len > 16 * stride_words; pl.n_columns !=
+ *      col_off[n_targets].  The write kernels rely on these checks and on nothing else.
+ * Read-backs: the refusal flags with Lmax; the candidate count, the bases and indexed positions of the end sequences (the sort and the
+ * directory are sized by them); the new column count (d_words is allocated at its size); the counters.
+ *
+ * alga_write_grown_fasta_device: one record per target with a length, in target order, `>contig_id=<t>_length=<len>_left=<xl>_right=<xr>`.
+ * `grown` must be the engine's current grow result.  ABI stays 7: the calls add. */
+#define ALGA_GROW_OVERHANGS 1
+#define ALGA_GROW_VOTES     2
+#define ALGA_GROW_MINUS     4
+typedef struct {
+    int32_t k, max_mismatches, max_occ, min_anchor, min_cover, min_percent, max_grow, flags;
+    int32_t reserved[4];             /* 0                                                                                             */
+} alga_grow_params;
+typedef struct {
+    int64_t         n_reads, n_targets, max_grow;
+    uint64_t        n_columns;       /* of the grown targets: d_col_off[n_targets]                                                    */
+    const int32_t  *d_end, *d_over;  /* n_reads                                                                                       */
+    const uint8_t  *d_mm, *d_hits, *d_state;
+    const uint32_t *d_count;         /* 2 * n_targets * max_grow * 4                                                                  */
+    const uint8_t  *d_e_stop;        /* 2 * n_targets                                                                                 */
+    const uint32_t *d_e_voters;
+    const uint32_t *d_left, *d_right;   /* n_targets                                                                                  */
+    const int32_t  *d_len;
+    const uint32_t *d_col_off;       /* n_targets + 1                                                                                 */
+    const uint64_t *d_begin;         /* n_targets                                                                                     */
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+} alga_grown;
+typedef struct {
+    uint64_t candidates, overhanging, voting, multi, hits_saturated, seeds, seeds_over_max_occ, index_positions, ends_with_voters, ends_grown, bases_added,
+             longest_growth, stops_cover, stops_percent, stops_max, columns_before, columns_after;
+    uint64_t n50_before, n50_after;
+    double   ms_index, ms_place, ms_build;   /* device time (HIP events)                                                              */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_grow_info;
+void alga_grow_default_params(alga_grow_params *p);
+int  alga_grow_placed_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polished *pol /* may be NULL */,
+                             const alga_grow_params *p, void *hip_stream, alga_grown *out, alga_grow_info *info /* may be NULL */);
+int  alga_write_grown_fasta_device(alga_engine *e, const alga_grown *grown, const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
