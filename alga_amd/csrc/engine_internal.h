@@ -224,6 +224,14 @@ struct alga_engine {
     int         gr_cur = 0;                        // the set that holds the result
     bool        gr_valid = false;
     uint64_t    gr_reads = 0, gr_targets = 0, gr_columns = 0, gr_longest = 0;   // ... of this many reads, targets and columns; the longest grown target
+    // contigs whose ends overlap merged into one sequence (engine_merge.hip).  Workspaces: counters, the end lengths, their padded lengths and
+    // the scan, the end sequences and their reverse complements, the (k-mer, end column) pairs before and after the sort, the directory, the
+    // join of every end, the lists over the 2T states (twice), head / first / members and their scans.  The result, twice, as for the grow
+    DevBuf      mg_cnt, mg_elen, mg_epad, mg_eoff, mg_ecols, mg_pcols, mg_keys[2], mg_vals[2], mg_dir, mg_join, mg_lists[2], mg_head, mg_first, mg_scan;
+    struct MergeSet { DevBuf partner, olen, mm, hits, estate, merged, rank, orient, start, ovafter, moff, mmembers, len, coloff, begin, words; } mg_set[2];
+    int         mg_cur = 0;                        // the set that holds the result
+    bool        mg_valid = false;
+    uint64_t    mg_targets = 0, mg_merged = 0, mg_columns = 0, mg_longest = 0;   // ... of this many targets, merged contigs and columns; the longest merged contig
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

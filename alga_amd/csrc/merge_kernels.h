@@ -1,0 +1,99 @@
+// alga_amd/csrc/merge_kernels.h -- launchers of merge_kernels.hip: contigs whose ends overlap merged into one sequence
+// (include/alga_amd.h: alga_merge_targets_device)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace alga {
+
+// counters[] (unsigned long long): the refusal flags and the sizes, then what the kernels count
+enum { MG_BAD = 0, MG_COLUMNS, MG_END_COLUMNS, MG_INDEX_POS, MG_ENDS, MG_SEEDS, MG_SEEDS_OVER, MG_WITH_OVERLAP, MG_AMBIGUOUS, MG_SATURATED, MG_JOINS, MG_DROPPED, MG_JOIN_MM,
+       MG_REMOVED, MG_LONGEST_OVERLAP, MG_MERGED, MG_MULTI, MG_MEMBERS, MG_LONGEST, MG_COLUMNS_AFTER, MG_BAD_MERGED_LEN, MG_COUNTERS };
+constexpr uint32_t MG_BAD_LEN = 1;                                       // bit of counters[MG_BAD]
+constexpr uint8_t  MG_E_HAS_OVERLAP = 1, MG_E_AMBIGUOUS = 2, MG_E_JOINED = 4, MG_E_DROPPED_CYCLE = 8;   // ALGA_MERGE_END_* of include/alga_amd.h
+constexpr uint32_t MG_NONE = 0xFFFFFFFFu;
+constexpr int32_t  MG_MAX_OVERLAP = 4096;
+
+// a ragged target set as the placement takes it
+struct MgTargets {
+    const uint32_t *words;
+    const unsigned long long *begin;  // T: base index of the first base
+    const int32_t *len;               // T
+    uint32_t T;
+};
+// the 2T end sequences in a column space of their own: end x is the columns end_off[x] .. end_off[x] + elen[x], end_off[x] a multiple of 16
+struct MgEnds {
+    const uint32_t *end_off;          // 2T + 1
+    const int32_t *elen;              // 2T: W_x
+    uint32_t E;                       // 2T
+    uint64_t columns;                 // end_off[2T]
+    const uint32_t *cols;             // E_x: the contig end at the right; two words of padding behind the last column
+    const uint32_t *pcols;            // P_x = the reverse complement of E_x, at the same columns
+};
+struct MgIndex {
+    const unsigned long long *keys;   // sorted; the first n are k-mers
+    const uint32_t *vals;             // their end columns
+    const uint32_t *dir;
+    int shift;
+    uint32_t n;
+};
+struct MgEndOut {
+    int32_t *partner, *olen;
+    uint8_t *mm, *hits, *state;
+};
+// the lists over the 2T states (contig, entry end), twice: a jump reads one set and writes the other
+struct MgLists {
+    unsigned long long *wsum;
+    uint32_t *nxt, *aux, *tail;
+};
+struct MgLayout {
+    int32_t *merged, *rank;
+    uint8_t *orient;
+    uint32_t *start;
+    int32_t *overlap_after;
+    uint32_t *m_off;                  // n_merged + 1
+    int32_t *m_members;               // n_members
+    int32_t *m_len;                   // n_merged (+ 1: a 0 for the scan)
+};
+
+// a negative length -> counters[MG_BAD]; counters[MG_COLUMNS] += len
+void launch_mg_check(const MgTargets &t, unsigned long long *counters, hipStream_t s);
+// elen[x] = W_x, epad[x] = W_x rounded up to 16 (2T + 1 entries each, the last 0); counters[MG_END_COLUMNS], [MG_INDEX_POS], [MG_ENDS]
+void launch_mg_end_lens(const MgTargets &t, int32_t max_overlap, int32_t min_overlap, int32_t k, int32_t *elen, uint32_t *epad, unsigned long long *counters, hipStream_t s);
+// E_x and P_x, one thread per word: the left ends complemented and mirrored
+void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32_t *pcols, hipStream_t s);
+// (k-mer, end column) of every end column; a column that is no indexed position gets a key above every k-mer
+void launch_mg_keys(const MgEnds &e, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s);
+// one wave per end
+int  mg_overlap_blocks(uint64_t n_ends, int n_cu);
+void launch_mg_overlap(const MgEnds &e, const MgIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
+                       unsigned long long *counters, hipStream_t s);
+// one thread per end: join[x] = the end x is joined with, MG_NONE without; JOINED into the end's state
+void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, hipStream_t s);
+// pointer jumping over the 2T states with the smallest contig id riding along; the smallest contig of a cycle drops the join at its left end
+void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, hipStream_t s);
+void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s);
+void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, hipStream_t s);
+// the same jumps over the paths that are left: states, len - overlap and the last state to the end of the path
+void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const MgLists &l, hipStream_t s);
+void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s);
+// per contig: rank, orientation, start, overlap_after; head / first / members (T + 1 entries of the last two) for the scans; the join counters
+void launch_mg_place(const MgTargets &t, const MgLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
+                     unsigned long long *counters, hipStream_t s);
+// merged ids, the member lists, the merged lengths; counters[MG_MERGED], [MG_MULTI], [MG_MEMBERS], [MG_LONGEST], [MG_COLUMNS_AFTER], [MG_BAD_MERGED_LEN]
+void launch_mg_layout(const MgTargets &t, const MgLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
+                      unsigned long long *counters, hipStream_t s);
+// the merged contigs' column array, one thread per word; begin[j] = col_off[j]
+void launch_mg_build(const MgTargets &t, const MgLayout &lo, const uint32_t *col_off, uint32_t n_merged, uint64_t columns, uint32_t *words, unsigned long long *begin,
+                     hipStream_t s);
+
+// `>contig_id=<j>_length=<len>_contigs=<m>\n<merged contig>\n`, one record per merged contig
+struct MgFasta {
+    const uint32_t *words, *col_off, *m_off;
+    const int32_t *len;
+    uint64_t n;
+};
+void launch_mg_fasta_sizes(const MgFasta &f, uint32_t *sizes, unsigned long long *counters /* GFA_SEGMENTS / GFA_MAX_LINE of gfa_kernels.h */, hipStream_t s);
+void launch_mg_fasta_write(const MgFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s);
+
+}  // namespace alga

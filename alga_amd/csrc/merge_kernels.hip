@@ -1,0 +1,509 @@
+// alga_amd/csrc/merge_kernels.hip -- contigs whose ends overlap merged into one sequence (include/alga_amd.h: alga_merge_targets_device; the
+// definition is the comment there, host side in engine_merge.hip).
+//
+// The 2T end sequences are gathered into one padded 2-bit array in a column space of their own (end x at end_off[x], a multiple of 16, the
+// contig end at the right: the left ends complemented and mirrored), and next to it their reverse complements P_x at the same columns: an
+// overlap of o bases is P_x[0 .. o) laid on the last o columns of E_y, whatever the pairing of left and right ends.  Integer work only,
+// wave-64, nothing depends on thread order or on the sort's order among equal keys.
+//   k_mg_check        a negative length -> the refusal flag; the column sum
+//   k_mg_end_lens     W_x of every end, W_x rounded up to a word, the indexed positions; (scan): end_off
+//   k_mg_ends         E_x and P_x, one thread per word
+//   k_mg_keys         (k-mer, end column) of every end column; a column that is no indexed position gets a key above every k-mer
+//   k_mg_overlap      one wave per end.  The lanes take the at most 64 seeds of P_x: directory read, bisection, a scan of at most max_occ + 1
+//                     equal keys; the (seed, occurrence) candidates go to the lanes in passes of 64.  A hit of seed j at position q of E_y gives
+//                     o = W_y - q + j k.  A lane verifies the o bases only: XOR and popcount over funnel-shifted words, the last partial word
+//                     masked, nothing read past the two words of padding.  A candidate found through seed j counts only if no usable seed
+//                     j' < j matches there (the usable seeds are one 64-bit ballot), so every (y, o) counts once.  The minimum key
+//                     (mm, y, o descending) and the number of (y, o) are reduced across the wave.
+//   k_mg_joins        one thread per end: joined where both ends have one overlap, each other, at one o
+//   k_mg_cycle_init / _jump / _drop   pointer jumping over the 2T states (contig, entry end) with the smallest contig id carried along: a state
+//                     that still has a successor after ceil(log2(2T)) + 1 doublings is on a cycle, and the contig that is its own minimum drops
+//                     the join at its left end
+//   k_mg_rank_init / _jump            the same jumps over the paths that are left: states, len - overlap and the last state to the end
+//   k_mg_place        per contig the direction whose first contig has the smaller id, rank, orientation, start, overlap_after
+//   k_mg_layout       merged ids, member lists and merged lengths from the scans over "is the first contig" and "members of what it starts"
+//   k_mg_build        every output word gathered by one lane: a column finds its member by bisection over the starts, an overlapped column is
+//                     the earlier contig's; minus-oriented members complemented and mirrored
+//   k_mg_fasta_sizes / k_mg_fasta_write   one record per merged contig, one wave per record
+// No LDS.  Block 256 and the grid caps are picked, not tuned; k_mg_overlap runs 8 blocks per CU like k_gr_place.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "merge_kernels.h"
+#include "text_record.h"
+#include "prefsuf_common.h"
+
+namespace alga {
+
+namespace {
+
+constexpr int MG_BLOCK = 256, MG_WAVES = MG_BLOCK / 64;
+
+__device__ __forceinline__ unsigned long long mg_wave_min(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
+        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// the item of position g < off[n]: the last i with off[i] <= g (it has a length: off[i + 1] > g)
+__device__ __forceinline__ uint32_t mg_item_of(const uint32_t *__restrict__ off, uint32_t n, uint32_t g) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint32_t mg_base(const uint32_t *__restrict__ words, uint64_t g) { return (words[g >> 4] >> ((g & 15ull) << 1)) & 3u; }
+
+// the k-mer at column g of a column array (two words of padding behind the last column)
+__device__ __forceinline__ unsigned long long mg_col_kmer(const uint32_t *__restrict__ cols, uint32_t g, int k) {
+    const uint32_t w = g >> 4, sh = (g & 15u) << 1;
+    const unsigned long long lo = (unsigned long long) cols[w] | ((unsigned long long) cols[w + 1] << 32);
+    unsigned long long v = lo >> sh;
+    if (sh) v |= (unsigned long long) cols[w + 2] << (64 - sh);
+    return v & ((1ull << (2 * k)) - 1ull);
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_check(MgTargets t, unsigned long long *__restrict__ counters) {
+    unsigned long long sum = 0, bad = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; i < t.T; i += (uint64_t) gridDim.x * MG_BLOCK) {
+        const int32_t n = t.len[i];
+        if (n < 0) bad = MG_BAD_LEN; else sum += (unsigned long long) n;
+    }
+    sum = wave_sum(sum); bad = wave_max(bad);
+    if ((threadIdx.x & 63) == 0) {
+        if (sum) atomicAdd(&counters[MG_COLUMNS], sum);
+        if (bad) atomicOr(&counters[MG_BAD], bad);
+    }
+}
+
+// (after the check: no length is negative)
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_end_lens(MgTargets t, int32_t max_overlap, int32_t min_overlap, int32_t k, int32_t *__restrict__ elen,
+                                                          uint32_t *__restrict__ epad, unsigned long long *__restrict__ counters) {
+    unsigned long long idx = 0, sum = 0, ends = 0;
+    const uint64_t E = 2ull * t.T;
+    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x <= E; x += (uint64_t) gridDim.x * MG_BLOCK) {
+        int32_t w = 0;
+        if (x < E) {
+            w = std::min(t.len[x >> 1] >> 1, max_overlap);
+            if (w >= k) idx += (unsigned long long) (w - k + 1);
+            ends += w >= min_overlap;
+        }
+        const uint32_t pad = ((uint32_t) w + 15u) & ~15u;
+        elen[x] = w; epad[x] = pad;                                           // entry 2T: the place of the scan's total
+        sum += pad;
+    }
+    idx = wave_sum(idx); sum = wave_sum(sum); ends = wave_sum(ends);
+    if ((threadIdx.x & 63) == 0 && sum) {
+        atomicAdd(&counters[MG_END_COLUMNS], sum);
+        if (idx) atomicAdd(&counters[MG_INDEX_POS], idx);
+        if (ends) atomicAdd(&counters[MG_ENDS], ends);
+    }
+}
+
+// (every end begins a word, so a word lies in one end; W_x <= len / 2: every source base lies in its target)
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_ends(MgTargets t, MgEnds e, uint32_t *__restrict__ ecols, uint32_t *__restrict__ pcols) {
+    const uint64_t n_words = e.columns >> 4;
+    for (uint64_t w = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * MG_BLOCK) {
+        const uint32_t g0 = (uint32_t) (w << 4), x = mg_item_of(e.end_off, e.E, g0), tt = x >> 1, q0 = g0 - e.end_off[x], W = (uint32_t) e.elen[x];
+        const uint64_t b0 = t.begin[tt], n = (uint64_t) t.len[tt];
+        uint32_t ve = 0, vp = 0;
+        for (uint32_t j = 0; j < 16 && q0 + j < W; j++) {
+            const uint32_t q = q0 + j;
+            uint32_t be, bp;
+            if (x & 1u) { be = mg_base(t.words, b0 + n - W + q); bp = 3u - mg_base(t.words, b0 + n - 1u - q); }          // the last W bases
+            else { be = 3u - mg_base(t.words, b0 + (W - 1u - q)); bp = mg_base(t.words, b0 + q); }                       // the first W, complemented and mirrored
+            ve |= be << (2 * j); vp |= bp << (2 * j);
+        }
+        ecols[w] = ve; pcols[w] = vp;
+    }
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_keys(MgEnds e, int32_t k, unsigned long long *__restrict__ keys, uint32_t *__restrict__ vals) {
+    for (uint64_t g = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; g < e.columns; g += (uint64_t) gridDim.x * MG_BLOCK) {
+        const uint32_t x = mg_item_of(e.end_off, e.E, (uint32_t) g);
+        const uint64_t q = g - (uint64_t) e.end_off[x];
+        keys[g] = q + (uint64_t) k <= (uint64_t) e.elen[x] ? mg_col_kmer(e.cols, (uint32_t) g, k) : 1ull << (2 * k);   // above every k-mer, inside the 2k + 1 sorted bits
+        vals[g] = (uint32_t) g;
+    }
+}
+
+// lower bound of x among the indexed keys and its occurrences, counted up to max_occ + 1
+__device__ __forceinline__ void mg_lookup(const MgIndex &x, unsigned long long kmer, uint32_t max_occ, uint32_t &lb, uint32_t &occ) {
+    const uint32_t b = (uint32_t) (kmer >> x.shift);
+    uint32_t lo = x.dir[b], hi = x.dir[b + 1];
+    const uint32_t end = hi;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (x.keys[mid] < kmer) lo = mid + 1; else hi = mid;
+    }
+    lb = lo;
+    uint32_t c = 0;
+    while (lo + c < end && c <= max_occ && x.keys[lo + c] == kmer) c++;
+    occ = c;
+}
+
+// Hamming distance between the first o bases of a word-aligned row and the o columns from gp on; stops past max_mm.  Words 0 .. blocks_of(o) - 1
+// of the row and up to one word more of the columns are read (gp + o <= the columns: inside the padding); the bases from o on are masked away
+__device__ __forceinline__ uint32_t mg_verify(const uint32_t *__restrict__ row, int o, const uint32_t *__restrict__ cols, uint32_t gp, uint32_t max_mm) {
+    const uint32_t *tw = cols + (gp >> 4);
+    const uint32_t sh = (gp & 15u) << 1;
+    const int nw = blocks_of(o);
+    uint32_t mm = 0, prev = tw[0];
+    for (int w = 0; w < nw; w++) {
+        const uint32_t next = tw[w + 1];
+        uint32_t x = row[w] ^ __funnelshift_r(prev, next, sh);
+        prev = next;
+        if (w == nw - 1 && (o & 15)) x &= (1u << ((o & 15) << 1)) - 1u;
+        mm += (uint32_t) __popc((x | (x >> 1)) & 0x55555555u);
+        if (mm > max_mm) break;
+    }
+    return mm;
+}
+
+// the key of an overlap: (mm, y, o descending); o <= 4096
+__device__ __forceinline__ unsigned long long mg_key(uint32_t mm, uint32_t y, uint32_t o) {
+    return ((unsigned long long) mm << 45) | ((unsigned long long) y << 13) | (unsigned long long) ((uint32_t) MG_MAX_OVERLAP - o);
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_overlap(MgEnds en, MgIndex ix, int32_t k, uint32_t max_mm, uint32_t max_occ, int32_t min_overlap, MgEndOut out,
+                                                         unsigned long long *__restrict__ counters) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t) blockIdx.x * MG_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * MG_WAVES;
+    unsigned long long n_with = 0, n_amb = 0, n_sat = 0, n_seeds = 0, n_over = 0;            // wave-uniform
+    for (uint64_t x = wave; x < en.E; x += n_waves) {
+        const int32_t W = en.elen[x];
+        unsigned long long best = ~0ull;
+        uint32_t lane_cnt = 0;
+        if (W >= min_overlap) {                              // (wave-uniform) a shorter end has no overlap: o <= W
+            const uint32_t x0 = en.end_off[x];
+            const uint32_t *row = en.pcols + (x0 >> 4);      // P_x begins a word
+            const int S = W / k;                             // the seeds with (j + 1) k <= W: at most 64
+            const bool act = lane < S;
+            uint32_t lb = 0, occ = 0;
+            if (act) mg_lookup(ix, mg_col_kmer(en.pcols, x0 + (uint32_t) (lane * k), k), max_occ, lb, occ);
+            const bool usable = act && occ >= 1u && occ <= max_occ;
+            const unsigned long long umask = __ballot(usable);
+            n_seeds += (unsigned long long) S;
+            n_over += (unsigned long long) __popcll(__ballot(act && occ > max_occ));
+            const uint32_t mine = usable ? occ : 0u;
+            uint32_t inc = mine;
+            for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t) __shfl_up((int) inc, d); if (lane >= d) inc += up; }
+            const uint32_t C = (uint32_t) __shfl((int) inc, 63), exc = inc - mine;
+            for (uint32_t p0 = 0; p0 < C; p0 += 64) {
+                const bool cact = p0 + (uint32_t) lane < C;
+                const uint32_t ci = cact ? p0 + (uint32_t) lane : C - 1u;
+                int sl = 0;                                  // the seed lane of candidate ci: the first with inc > ci
+                for (int st = 32; st > 0; st >>= 1) if ((uint32_t) __shfl((int) inc, sl + st - 1) <= ci) sl += st;
+                const uint32_t s_lb = (uint32_t) __shfl((int) lb, sl), s_exc = (uint32_t) __shfl((int) exc, sl);
+                if (!cact) continue;
+                const uint32_t g = ix.vals[s_lb + (ci - s_exc)];                // an indexed position: q + k <= W_y
+                const uint32_t y = mg_item_of(en.end_off, en.E, g);
+                if ((y >> 1) == (uint32_t) (x >> 1)) continue;                   // the same target: no overlap here
+                const int32_t Wy = en.elen[y], q = (int32_t) (g - en.end_off[y]);
+                const int32_t o = Wy - q + sl * k;                               // P_x[sl k] lies on E_y[q]; the overlap ends with E_y
+                if (o < min_overlap || o > W || o > Wy) continue;
+                const uint32_t gp = g - (uint32_t) (sl * k);                     // = end_off[y] + W_y - o >= end_off[y]
+                const uint32_t mm = mg_verify(row, o, en.cols, gp, max_mm);
+                if (mm > max_mm) continue;
+                bool dup = false;                            // an earlier usable seed finds this overlap too (it lies inside it: j2 < sl)
+                for (int j2 = 0; j2 < sl && !dup; j2++)
+                    if ((umask >> j2) & 1ull) dup = mg_col_kmer(en.pcols, x0 + (uint32_t) (j2 * k), k) == mg_col_kmer(en.cols, gp + (uint32_t) (j2 * k), k);
+                if (dup) continue;
+                const unsigned long long key = mg_key(mm, y, (uint32_t) o);
+                best = key < best ? key : best;
+                lane_cnt++;
+            }
+        }
+        const unsigned long long win = mg_wave_min(best);
+        int32_t y_out = -1, o_out = 0;
+        uint8_t mm8 = 0, hits8 = 0, st8 = 0;
+        if (win != ~0ull) {
+            const unsigned long long hits = wave_sum((unsigned long long) lane_cnt);
+            y_out = (int32_t) (uint32_t) (win >> 13); o_out = MG_MAX_OVERLAP - (int32_t) (win & 8191ull); mm8 = (uint8_t) (win >> 45);
+            hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
+            st8 = (uint8_t) (MG_E_HAS_OVERLAP | (hits > 1ull ? MG_E_AMBIGUOUS : 0));
+            n_with++; n_amb += hits > 1ull; n_sat += hits > 255ull;
+        }
+        if (lane == 0) { out.partner[x] = y_out; out.olen[x] = o_out; out.mm[x] = mm8; out.hits[x] = hits8; out.state[x] = st8; }
+    }
+    if (lane == 0) {
+        if (n_with) atomicAdd(&counters[MG_WITH_OVERLAP], n_with);
+        if (n_amb) atomicAdd(&counters[MG_AMBIGUOUS], n_amb);
+        if (n_sat) atomicAdd(&counters[MG_SATURATED], n_sat);
+        if (n_seeds) atomicAdd(&counters[MG_SEEDS], n_seeds);
+        if (n_over) atomicAdd(&counters[MG_SEEDS_OVER], n_over);
+    }
+}
+
+// (a thread writes its own end only; partner[x] < 2T wherever hits[x] > 0)
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_joins(MgEndOut o, uint32_t E, uint32_t *__restrict__ join) {
+    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
+        uint32_t j = MG_NONE;
+        if (o.hits[x] == 1) {
+            const uint32_t y = (uint32_t) o.partner[x];
+            if (o.hits[y] == 1 && (uint32_t) o.partner[y] == (uint32_t) x && o.olen[y] == o.olen[x]) j = y;
+        }
+        join[x] = j;
+        if (j != MG_NONE) o.state[x] |= MG_E_JOINED;
+    }
+}
+
+// state x = 2c + e: contig c entered at end e, left at e ^ 1 through that end's join into the partner end's contig
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_init(const uint32_t *__restrict__ join, uint32_t E, MgLists l) {
+    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
+        l.nxt[x] = join[x ^ 1]; l.aux[x] = (uint32_t) (x >> 1);
+    }
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_jump(uint32_t E, MgLists from, MgLists to) {
+    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
+        const uint32_t y = from.nxt[x];
+        uint32_t m = from.aux[x], z = MG_NONE;
+        if (y != MG_NONE) { const uint32_t my = from.aux[y]; m = my < m ? my : m; z = from.nxt[y]; }
+        to.nxt[x] = z; to.aux[x] = m;
+    }
+}
+
+// one thread per contig; only the smallest contig of a cycle writes, and only the two ends of the join at its left end
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_drop(MgLists l, uint32_t T, uint32_t *__restrict__ join, uint8_t *__restrict__ end_state,
+                                                            unsigned long long *__restrict__ counters) {
+    unsigned long long n = 0;
+    for (uint64_t c = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; c < T; c += (uint64_t) gridDim.x * MG_BLOCK) {
+        if (l.nxt[2 * c] == MG_NONE || l.aux[2 * c] != (uint32_t) c) continue;
+        const uint32_t y = join[2 * c];
+        join[2 * c] = MG_NONE; join[y] = MG_NONE;
+        end_state[2 * c] = (uint8_t) ((end_state[2 * c] & ~MG_E_JOINED) | MG_E_DROPPED_CYCLE);
+        end_state[y] = (uint8_t) ((end_state[y] & ~MG_E_JOINED) | MG_E_DROPPED_CYCLE);
+        n++;
+    }
+    n = wave_sum(n);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[MG_DROPPED], n);
+}
+
+// (a joined end has 42 <= olen <= len / 2: len - olen > 0)
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_rank_init(MgTargets t, const uint32_t *__restrict__ join, const int32_t *__restrict__ olen, MgLists l) {
+    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < 2ull * t.T; x += (uint64_t) gridDim.x * MG_BLOCK) {
+        const uint32_t out = (uint32_t) (x ^ 1);
+        l.nxt[x] = join[out]; l.aux[x] = 1u; l.tail[x] = (uint32_t) x;
+        l.wsum[x] = (unsigned long long) (t.len[x >> 1] - (join[out] != MG_NONE ? olen[out] : 0));
+    }
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_rank_jump(uint32_t E, MgLists from, MgLists to) {
+    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
+        const uint32_t y = from.nxt[x];
+        uint32_t d = from.aux[x], tl = from.tail[x], z = MG_NONE;
+        unsigned long long w = from.wsum[x];
+        if (y != MG_NONE) { d += from.aux[y]; w += from.wsum[y]; tl = from.tail[y]; z = from.nxt[y]; }
+        to.nxt[x] = z; to.aux[x] = d; to.tail[x] = tl; to.wsum[x] = w;
+    }
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_place(MgTargets t, MgLists l, const uint32_t *__restrict__ join, MgEndOut eo, MgLayout o, uint32_t *__restrict__ head,
+                                                       uint32_t *__restrict__ first, uint32_t *__restrict__ members, unsigned long long *__restrict__ counters) {
+    unsigned long long n_joins = 0, n_mm = 0, n_removed = 0, longest = 0;
+    for (uint64_t c = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; c <= t.T; c += (uint64_t) gridDim.x * MG_BLOCK) {
+        if (c == t.T) { first[c] = 0; members[c] = 0; continue; }               // the place of the scans' totals
+        if (t.len[c] == 0) {                                                   // in no merged contig (it has no end sequence: no join)
+            o.merged[c] = -1; o.rank[c] = -1; o.orient[c] = 0; o.start[c] = 0; o.overlap_after[c] = 0;
+            head[c] = (uint32_t) c; first[c] = 0; members[c] = 0;
+            continue;
+        }
+        // the list of state 2c + e begins at the contig the other direction ends at
+        const uint32_t f0 = l.tail[2 * c + 1] >> 1, l0 = l.tail[2 * c] >> 1;   // first and last contig of the direction that enters c at end 0
+        const uint32_t e = f0 <= l0 ? 0u : 1u;                                 // (f0 == l0: a path of one contig, orientation +)
+        const uint32_t x = 2 * (uint32_t) c + e;
+        const uint32_t m = l.aux[x] + l.aux[x ^ 1] - 1u, rank = m - l.aux[x];
+        const uint32_t hx = l.tail[x ^ 1] ^ 1u;                                // the state of the first contig in this direction
+        const uint32_t out = x ^ 1u;                                           // c is left at this end
+        const bool joined = join[out] != MG_NONE;
+        const uint32_t ov = joined ? (uint32_t) eo.olen[out] : 0u;
+        o.rank[c] = (int32_t) rank; o.orient[c] = (uint8_t) e;
+        o.start[c] = (uint32_t) (l.wsum[hx] - l.wsum[x]);
+        o.overlap_after[c] = (int32_t) ov;
+        if (joined) { n_joins++; n_mm += eo.mm[out]; n_removed += ov; longest = ov > longest ? ov : longest; }
+        head[c] = hx >> 1; first[c] = rank == 0; members[c] = rank == 0 ? m : 0u;
+    }
+    n_joins = wave_sum(n_joins); n_mm = wave_sum(n_mm); n_removed = wave_sum(n_removed); longest = wave_max(longest);
+    if ((threadIdx.x & 63) == 0 && n_joins) {
+        atomicAdd(&counters[MG_JOINS], n_joins); atomicAdd(&counters[MG_REMOVED], n_removed); atomicMax(&counters[MG_LONGEST_OVERLAP], longest);
+        if (n_mm) atomicAdd(&counters[MG_JOIN_MM], n_mm);
+    }
+}
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_layout(MgTargets t, MgLists l, const uint32_t *__restrict__ head, const uint32_t *__restrict__ first_scan,
+                                                        const uint32_t *__restrict__ members_scan, MgLayout o, unsigned long long *__restrict__ counters) {
+    unsigned long long n_mg = 0, n_multi = 0, n_mem = 0, longest = 0, sum = 0, bad = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) o.m_off[first_scan[t.T]] = members_scan[t.T];
+    for (uint64_t c = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; c < t.T; c += (uint64_t) gridDim.x * MG_BLOCK) {
+        const int32_t rank = o.rank[c];
+        if (rank < 0) continue;
+        const uint32_t h = head[c], mid = first_scan[h], at = members_scan[h];
+        o.merged[c] = (int32_t) mid;
+        o.m_members[at + (uint32_t) rank] = (int32_t) c;
+        if (rank == 0) {
+            const uint32_t x = 2 * (uint32_t) c + o.orient[c];
+            unsigned long long bases = l.wsum[x];
+            if (bases > 0x7FFFFFFFull) { bad = 1; bases = 0; }
+            o.m_off[mid] = at; o.m_len[mid] = (int32_t) bases;
+            n_mg++; n_multi += l.aux[x] > 1u; n_mem += l.aux[x]; sum += bases;
+            longest = bases > longest ? bases : longest;
+        }
+    }
+    n_mg = wave_sum(n_mg); n_multi = wave_sum(n_multi); n_mem = wave_sum(n_mem); longest = wave_max(longest); sum = wave_sum(sum); bad = wave_max(bad);
+    if ((threadIdx.x & 63) == 0 && n_mg) {
+        atomicAdd(&counters[MG_MERGED], n_mg); atomicAdd(&counters[MG_MEMBERS], n_mem); atomicMax(&counters[MG_LONGEST], longest);
+        atomicAdd(&counters[MG_COLUMNS_AFTER], sum);
+        if (n_multi) atomicAdd(&counters[MG_MULTI], n_multi);
+        if (bad) atomicMax(&counters[MG_BAD_MERGED_LEN], bad);
+    }
+}
+
+// (col_off is the scan of the merged lengths, columns its total; every merged contig has a length and at least one member; a column of a member
+// lies in that member's target: p - start < len)
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_build(MgTargets t, MgLayout o, const uint32_t *__restrict__ col_off, uint32_t n_merged, uint64_t columns,
+                                                       uint32_t *__restrict__ words, unsigned long long *__restrict__ begin) {
+    const uint64_t n_words = ((columns + 15) >> 4) + 2, step = (uint64_t) gridDim.x * MG_BLOCK;
+    for (uint64_t i = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; i < n_merged; i += step) begin[i] = col_off[i];
+    for (uint64_t w = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; w < n_words; w += step) {
+        const uint64_t g0 = w << 4;
+        uint32_t v = 0;
+        if (g0 < columns) {
+            uint32_t j = mg_item_of(col_off, n_merged, (uint32_t) g0);
+            for (int b = 0; b < 16; b++) {
+                const uint64_t gg = g0 + (uint64_t) b;
+                if (gg >= columns) break;
+                while ((uint64_t) col_off[j + 1] <= gg) j++;                 // (gg < columns = col_off[n_merged]: ends at a merged contig)
+                const uint32_t p = (uint32_t) (gg - col_off[j]), m0 = o.m_off[j], m = o.m_off[j + 1] - m0;
+                const int32_t *mem = o.m_members + m0;
+                uint32_t lo = 0, hi = m;                                     // the member of largest rank that starts at or before p
+                while (hi - lo > 1) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    if (o.start[mem[mid]] <= p) lo = mid; else hi = mid;
+                }
+                uint32_t c = (uint32_t) mem[lo];
+                if (lo > 0) {                                                // an overlapped column is the earlier contig's
+                    const uint32_t cp = (uint32_t) mem[lo - 1];
+                    if (p < o.start[cp] + (uint32_t) t.len[cp]) c = cp;
+                }
+                const uint32_t q = p - o.start[c], n = (uint32_t) t.len[c];
+                const uint32_t code = o.orient[c] ? 3u - mg_base(t.words, t.begin[c] + (n - 1u - q)) : mg_base(t.words, t.begin[c] + q);
+                v |= code << (2 * b);
+            }
+        }
+        words[w] = v;
+    }
+}
+
+// ---- FASTA of the merged contigs -------------------------------------------------------------------------------------------------------
+// `>contig_id=<j>_length=<len>_contigs=<m>\n<merged contig>\n`
+struct MgRecord : FastaRecord<PackedSeq> {
+    static constexpr bool kAligned = false;
+    __device__ __forceinline__ bool set(const MgFasta &f, uint64_t j) {
+        const int32_t len = f.len[j];
+        if (len <= 0) return false;
+        contig_head(j, (uint32_t) len);
+        h.f[2] = text_field("_contigs=", (uint64_t) (f.m_off[j + 1] - f.m_off[j])); seal();
+        seq.row = f.words; seq.q0 = f.col_off[j];
+        return true;
+    }
+};
+
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_fasta_sizes(MgFasta f, uint32_t *__restrict__ sizes, unsigned long long *__restrict__ counters) {
+    text_sizes_body<MgRecord>(f, f.n, sizes, counters);
+}
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_fasta_write(MgFasta f, const unsigned long long *__restrict__ off, uint64_t i0, uint64_t i1, char *__restrict__ buf) {
+    text_write_body<MgRecord>(f, off, i0, i1, buf);
+}
+
+inline unsigned mg_grid(uint64_t items, uint64_t cap = 8192) {
+    const uint64_t g = (items + MG_BLOCK - 1) / MG_BLOCK;
+    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
+}
+
+}  // namespace
+
+void launch_mg_check(const MgTargets &t, unsigned long long *counters, hipStream_t s) {
+    if (t.T) hipLaunchKernelGGL(k_mg_check, dim3(mg_grid(t.T, 4096)), dim3(MG_BLOCK), 0, s, t, counters);
+}
+
+void launch_mg_end_lens(const MgTargets &t, int32_t max_overlap, int32_t min_overlap, int32_t k, int32_t *elen, uint32_t *epad, unsigned long long *counters, hipStream_t s) {
+    hipLaunchKernelGGL(k_mg_end_lens, dim3(mg_grid(2ull * t.T + 1)), dim3(MG_BLOCK), 0, s, t, max_overlap, min_overlap, k, elen, epad, counters);
+}
+
+void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32_t *pcols, hipStream_t s) {
+    if (e.columns) hipLaunchKernelGGL(k_mg_ends, dim3(mg_grid(e.columns >> 4)), dim3(MG_BLOCK), 0, s, t, e, ecols, pcols);
+}
+
+void launch_mg_keys(const MgEnds &e, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s) {
+    if (e.columns) hipLaunchKernelGGL(k_mg_keys, dim3(mg_grid(e.columns, 1u << 16)), dim3(MG_BLOCK), 0, s, e, k, keys, vals);
+}
+
+int mg_overlap_blocks(uint64_t n_ends, int n_cu) {
+    return (int) std::max<uint64_t>(1, std::min<uint64_t>((n_ends + MG_WAVES - 1) / MG_WAVES, (uint64_t) std::max(1, n_cu) * 8u));
+}
+
+void launch_mg_overlap(const MgEnds &e, const MgIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
+                       unsigned long long *counters, hipStream_t s) {
+    if (e.E) hipLaunchKernelGGL(k_mg_overlap, dim3((unsigned) blocks), dim3(MG_BLOCK), 0, s, e, x, k, (uint32_t) max_mm, (uint32_t) max_occ, min_overlap, o, counters);
+}
+
+void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_joins, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, o, E, join);
+}
+
+void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_cycle_init, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, join, E, l);
+}
+
+void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_cycle_jump, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, E, from, to);
+}
+
+void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, hipStream_t s) {
+    if (T) hipLaunchKernelGGL(k_mg_cycle_drop, dim3(mg_grid(T)), dim3(MG_BLOCK), 0, s, l, T, join, end_state, counters);
+}
+
+void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const MgLists &l, hipStream_t s) {
+    if (t.T) hipLaunchKernelGGL(k_mg_rank_init, dim3(mg_grid(2ull * t.T)), dim3(MG_BLOCK), 0, s, t, join, olen, l);
+}
+
+void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_rank_jump, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, E, from, to);
+}
+
+void launch_mg_place(const MgTargets &t, const MgLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
+                     unsigned long long *counters, hipStream_t s) {
+    hipLaunchKernelGGL(k_mg_place, dim3(mg_grid((uint64_t) t.T + 1)), dim3(MG_BLOCK), 0, s, t, l, join, o, lo, head, first, members, counters);
+}
+
+void launch_mg_layout(const MgTargets &t, const MgLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
+                      unsigned long long *counters, hipStream_t s) {
+    hipLaunchKernelGGL(k_mg_layout, dim3(mg_grid((uint64_t) t.T + 1)), dim3(MG_BLOCK), 0, s, t, l, head, first_scan, members_scan, lo, counters);
+}
+
+void launch_mg_build(const MgTargets &t, const MgLayout &lo, const uint32_t *col_off, uint32_t n_merged, uint64_t columns, uint32_t *words, unsigned long long *begin,
+                     hipStream_t s) {
+    const uint64_t n_words = ((columns + 15) >> 4) + 2;
+    hipLaunchKernelGGL(k_mg_build, dim3(mg_grid(std::max<uint64_t>(n_words, n_merged))), dim3(MG_BLOCK), 0, s, t, lo, col_off, n_merged, columns, words, begin);
+}
+
+void launch_mg_fasta_sizes(const MgFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
+    if (f.n) hipLaunchKernelGGL(k_mg_fasta_sizes, dim3((unsigned) ((f.n + MG_BLOCK - 1) / MG_BLOCK)), dim3(MG_BLOCK), 0, s, f, sizes, counters);
+}
+
+void launch_mg_fasta_write(const MgFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
+    if (i0 >= i1) return;
+    const uint64_t g = (i1 - i0 + MG_WAVES - 1) / MG_WAVES;
+    hipLaunchKernelGGL(k_mg_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(MG_BLOCK), 0, s, f, off, i0, i1, buf);
+}
+
+}  // namespace alga

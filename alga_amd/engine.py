@@ -182,7 +182,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_polish_default_params", "alga_polish_placed_device", "alga_write_polished_fasta_device",
            "alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device",
            "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device",
-           "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device"]
+           "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device",
+           "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -706,6 +707,82 @@ def grow_tsv(h):
                                                        int(h["e_stop"][2 * t]), int(h["e_stop"][2 * t + 1])) for t in range(len(h["len"])))
 
 
+MERGE_END_HAS_OVERLAP, MERGE_END_AMBIGUOUS, MERGE_END_JOINED, MERGE_END_DROPPED_CYCLE = 1, 2, 4, 8   # bits of Merged.end_state
+
+
+class MergeParams(C.Structure):
+    """alga_merge_params"""
+    _fields_ = [(k, C.c_int32) for k in ("k", "max_mismatches", "max_occ", "min_overlap", "max_overlap", "flags")] + [("reserved", C.c_int32 * 2)]
+
+
+class MergeInfo(C.Structure):
+    """alga_merge_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("ends", "index_positions", "seeds", "seeds_over_max_occ", "ends_with_overlap", "ends_ambiguous", "hits_saturated", "joins",
+                                          "joins_dropped_cycle", "join_mismatches", "bases_removed", "longest_overlap", "merged", "merged_multi", "longest",
+                                          "columns_before", "columns_after", "n50_before", "n50_after")] + \
+               [(k, C.c_double) for k in ("ms_index", "ms_overlap", "ms_build", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MergedC(C.Structure):
+    """alga_merged"""
+    _fields_ = [(k, C.c_int64) for k in ("n_targets", "n_merged", "n_members")] + [("n_columns", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_partner", "d_olen", "d_mm", "d_hits", "d_end_state", "d_merged", "d_rank", "d_orient", "d_start", "d_overlap_after", "d_m_off",
+                                          "d_m_members", "d_len", "d_col_off", "d_begin", "d_words")]
+
+
+class Merged:
+    """Result of Engine.merge_ends: zero-copy torch views of the engine's device memory (valid until the next Engine.merge_ends call on that
+    engine; clone what has to live longer) -- per end partner / olen int32, mm / hits / end_state uint8 [2 * n_targets]; per target merged /
+    rank int32, orient uint8, start int32 (the bits of uint32), overlap_after int32; m_off int32 [n_merged + 1], m_members int32 [n_members];
+    len int32 [n_merged], col_off int32 [n_merged + 1], begin int64 [n_merged], words int32 [(n_columns + 15) / 16 + 2] (the result's own copy
+    of the bases) -- and .info (dict of alga_merge_info)."""
+    KEYS = (("partner", "<i4", np.int32, "e"), ("olen", "<i4", np.int32, "e"), ("mm", "|u1", np.uint8, "e"), ("hits", "|u1", np.uint8, "e"),
+            ("end_state", "|u1", np.uint8, "e"), ("merged", "<i4", np.int32, "t"), ("rank", "<i4", np.int32, "t"), ("orient", "|u1", np.uint8, "t"),
+            ("start", "<i4", np.uint32, "t"), ("overlap_after", "<i4", np.int32, "t"), ("m_off", "<i4", np.uint32, "m1"), ("m_members", "<i4", np.int32, "mm"),
+            ("len", "<i4", np.int32, "m"), ("col_off", "<i4", np.uint32, "m1"), ("begin", "<i8", np.uint64, "m"), ("words", "<i4", np.uint32, "w"))
+
+    def __init__(self, c, info, device, source=None):
+        self._c, self.info, self._source = c, info, source                 # source: the tensors the targets came from, kept alive with the result
+        self.n_targets, self.n_merged, self.n_members, self.n_columns = int(c.n_targets), int(c.n_merged), int(c.n_members), int(c.n_columns)
+        dev = "cuda:%d" % device
+        size = dict(e=2 * self.n_targets, t=self.n_targets, m=self.n_merged, m1=self.n_merged + 1, mm=self.n_members, w=(self.n_columns + 15) // 16 + 2)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/merge_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+    def targets(self):
+        """(words, begin int64 [n_merged], len int32 [n_merged]): the merged contigs as the ragged target set Engine.place_reads(targets=...) and
+        Engine.merge_ends take (the tensors are the engine's)"""
+        return self.words, self.begin, self.len
+
+    def merge_tsv(self, tlen=None, host=None):
+        """one line per member in (merged, rank) order: merged, rank, contig, orient, start, length, overlap_after, mm (tabs); tlen: the lengths
+        of the targets that were merged (by default read back from the targets of the call); the text alga_hip --merge_layout= writes"""
+        if tlen is None:
+            tlen = self._source[2].cpu().numpy()
+        return merge_tsv(host if host is not None else self.to_host(), tlen)
+
+
+def merge_tsv(h, tlen):
+    """the layout of a merge result read back (Merged.to_host())"""
+    lines = []
+    for j in range(len(h["len"])):
+        for c in h["m_members"][int(h["m_off"][j]):int(h["m_off"][j + 1])]:
+            c = int(c)
+            out = 2 * c + (int(h["orient"][c]) ^ 1)
+            lines.append("%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\n" % (j, int(h["rank"][c]), c, "-" if h["orient"][c] else "+", int(h["start"][c]), int(tlen[c]),
+                                                             int(h["overlap_after"][c]), int(h["mm"][out]) if h["overlap_after"][c] else 0))
+    return "".join(lines)
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -865,6 +942,11 @@ def load_library():
     lib.alga_grow_placed_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(PlacementsC), C.POINTER(PolishedC), C.POINTER(GrowParams), C.c_void_p,
                                             C.POINTER(GrownC), C.POINTER(GrowInfo)]
     lib.alga_write_grown_fasta_device.argtypes = [C.c_void_p, C.POINTER(GrownC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_merge_default_params.argtypes = [C.POINTER(MergeParams)]
+    lib.alga_merge_default_params.restype = None
+    lib.alga_merge_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MergeParams), C.c_void_p, C.POINTER(MergedC),
+                                              C.POINTER(MergeInfo)]
+    lib.alga_write_merged_fasta_device.argtypes = [C.c_void_p, C.POINTER(MergedC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -1928,6 +2010,46 @@ class Engine:
         records): `>contig_id=<t>_length=<len>_left=<xl>_right=<xr>` per target with a length."""
         info = GfaInfo()
         self._check(self._lib.alga_write_grown_fasta_device(self._h, C.byref(grown._c), os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    def merge_ends(self, targets, stream=None, **params):
+        """Contigs whose ends overlap merged into one sequence (alga_merge_targets_device) -> Merged.  targets = (packed words, begin int64 [T],
+        len int32 [T]): ragged sequences as Engine.place_reads takes them, for instance Grown.targets() or the Merged.targets() of the call
+        before.  Host arrays are uploaded first; tensors are used where they are and left untouched.  params: k, max_mismatches, max_occ,
+        min_overlap, max_overlap (the fields of alga_merge_params; the library's defaults where not given)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        twords, tbegin, tlen = targets
+        twords, tlen = up(twords, np.uint32, np.int32), up(tlen, np.int32)
+        if isinstance(tbegin, np.ndarray):
+            tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
+        assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
+        assert twords.is_contiguous()
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        pp, out, info = MergeParams(), MergedC(), MergeInfo()
+        self._lib.alga_merge_default_params(C.byref(pp))
+        for k, v in params.items():
+            if k not in ("k", "max_mismatches", "max_occ", "min_overlap", "max_overlap", "flags"):
+                raise TypeError("Engine.merge_ends: unknown parameter %r" % k)
+            setattr(pp, k, int(v))
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_merge_targets_device(self._h, C.c_void_p(_ptr(twords) or None), C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None),
+                                                        int(tlen.shape[0]), C.byref(pp), st, C.byref(out), C.byref(info)))
+        return Merged(out, info.as_dict(), self.device, (twords, tbegin, tlen))
+
+    def write_merged_fasta(self, path, merged):
+        """The merged contigs of the LAST Engine.merge_ends call as FASTA (alga_write_merged_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>contig_id=<j>_length=<len>_contigs=<m>` per merged contig."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_merged_fasta_device(self._h, C.byref(merged._c), os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

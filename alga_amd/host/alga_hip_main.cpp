@@ -91,6 +91,12 @@
 // (alga_write_grown_fasta_device); --grow_layout=PATH: one line `contig left right voters_left voters_right stop_left stop_right` per contig of
 // that round, tab separated (both need --grow_ends >= 1).  One line on stderr per round gives candidates / voting reads / ends grown / bases
 // added / N50 before -> after.  Without --grow_ends every file is what it was.  None is passed through.
+// --merge_ends=1 (default 0; needs --grow_ends >= 1): after the last grow round the grown contigs whose ends overlap are merged into one
+// (alga_merge_targets_device: --merge_min_overlap= (42), --merge_max_mismatches= (1)), the reads are placed again on the merged contigs, and the
+// scaffolds and their layout come from that placement (contig ids there are merged ids).  --merged=PATH: the merged contigs,
+// `>contig_id=<j>_length=<len>_contigs=<m>` (alga_write_merged_fasta_device); --merge_layout=PATH: one line `merged rank contig orient start
+// length overlap_after mm` per member, tab separated (both need --merge_ends=1).  One line on stderr gives overlaps / ambiguous ends / joins /
+// bases removed / N50 before -> after.  Without --merge_ends=1 every file is what it was.  None is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -118,7 +124,8 @@ static const char *USAGE =
     "         [--scaffolds=scaffolds.fasta] [--scaffold_layout=layout.tsv] [--scaffold_min_links=5] [--scaffold_min_gap=10] [--scaffold_max_second_percent=50]\n"
     "         [--break_misjoins=0|1] [--break_min_span=1] [--break_inset=21] [--break_margin=N] [--broken=pieces.fasta] [--break_cuts=cuts.tsv]\n"
     "         [--grow_ends=N] [--grown=grown.fasta] [--grow_layout=grow.tsv] [--grow_min_anchor=63] [--grow_max_mismatches=2] [--grow_min_cover=3]\n"
-    "         [--grow_min_percent=80] [--grow_max=64]\n";
+    "         [--grow_min_percent=80] [--grow_max=64]\n"
+    "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -147,6 +154,10 @@ int main(int argc, char **argv) {
     std::string grown, grow_layout;
     alga_grow_params grp;
     alga_grow_default_params(&grp);
+    int merge_ends = 0;
+    std::string merged_path, merge_layout;
+    alga_merge_params mgp;
+    alga_merge_default_params(&mgp);
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -201,6 +212,11 @@ int main(int argc, char **argv) {
         else if (opt(a, "--grow_min_cover", v)) grp.min_cover = atoi(v.c_str());
         else if (opt(a, "--grow_min_percent", v)) grp.min_percent = atoi(v.c_str());
         else if (opt(a, "--grow_max", v)) grp.max_grow = atoi(v.c_str());
+        else if (opt(a, "--merge_ends", v)) merge_ends = atoi(v.c_str());
+        else if (opt(a, "--merged", v)) merged_path = v;
+        else if (opt(a, "--merge_layout", v)) merge_layout = v;
+        else if (opt(a, "--merge_min_overlap", v)) mgp.min_overlap = atoi(v.c_str());
+        else if (opt(a, "--merge_max_mismatches", v)) mgp.max_mismatches = atoi(v.c_str());
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -247,6 +263,13 @@ int main(int argc, char **argv) {
         grp.min_percent > 100 || grp.max_grow < 1 || grp.max_grow > 4096) {
         fprintf(stderr, "alga_hip: --grow_min_anchor must be in [21, 2^20], --grow_max_mismatches in [0, 254], --grow_min_cover >= 1, --grow_min_percent in [51, 100], "
                         "--grow_max in [1, 4096]\n");
+        return 2;
+    }
+    if (merge_ends != 0 && merge_ends != 1) { fprintf(stderr, "alga_hip: --merge_ends must be 0 or 1 (got %d)\n", merge_ends); return 2; }
+    if (merge_ends && !grow_ends) { fprintf(stderr, "alga_hip: --merge_ends=1 needs --grow_ends >= 1\n"); return 2; }
+    if (!merge_ends && (!merged_path.empty() || !merge_layout.empty())) { fprintf(stderr, "alga_hip: --merged= and --merge_layout= need --merge_ends=1\n"); return 2; }
+    if (mgp.min_overlap < mgp.k || mgp.min_overlap > mgp.max_overlap || mgp.max_mismatches < 0 || mgp.max_mismatches > 254) {
+        fprintf(stderr, "alga_hip: --merge_min_overlap must be in [21, 512], --merge_max_mismatches in [0, 254]\n");
         return 2;
     }
     if (correct_reads && !alga_exe.empty()) {
@@ -720,6 +743,60 @@ int main(int argc, char **argv) {
                             for (size_t t = 0; f && t < nt; t++)
                                 fprintf(f, "%zu\t%u\t%u\t%u\t%u\t%d\t%d\n", t, left[t], right[t], voters[2 * t], voters[2 * t + 1], (int) stop[2 * t], (int) stop[2 * t + 1]);
                             if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", grow_layout.c_str()); return 1; }
+                        }
+                        if (rc == ALGA_OK && merge_ends) {                   // the grown contigs whose ends overlap become one, and the reads are placed on those
+                            alga_merged mg{};
+                            alga_merge_info mi;
+                            rc = alga_merge_targets_device(engine, gw.d_words, gw.d_begin, gw.d_len, (int32_t) gw.n_targets, &mgp, nullptr, &mg, &mi);
+                            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot merge the contig ends: %s (status %d)\n", alga_last_error(engine), rc); return 1; }
+                            fprintf(stderr, "Contig ends merged: %llu ends with an overlap, %llu ambiguous, %llu joins, %llu bases removed, N50 %llu -> %llu; %llu ends of "
+                                    "%llu contigs, %llu joins dropped for cycles, %llu mismatches in the joins, longest overlap %llu, %llu merged contigs (%llu of several), "
+                                    "%llu -> %llu columns; device ms: index %.3f overlap %.3f build %.3f, call %.1f ms wall\n", (unsigned long long) mi.ends_with_overlap,
+                                    (unsigned long long) mi.ends_ambiguous, (unsigned long long) mi.joins, (unsigned long long) mi.bases_removed, (unsigned long long) mi.n50_before,
+                                    (unsigned long long) mi.n50_after, (unsigned long long) mi.ends, (unsigned long long) mg.n_targets, (unsigned long long) mi.joins_dropped_cycle,
+                                    (unsigned long long) mi.join_mismatches, (unsigned long long) mi.longest_overlap, (unsigned long long) mi.merged,
+                                    (unsigned long long) mi.merged_multi, (unsigned long long) mi.columns_before, (unsigned long long) mi.columns_after, mi.ms_index, mi.ms_overlap,
+                                    mi.ms_build, mi.ms_total);
+                            if (!merged_path.empty()) {
+                                alga_gfa_info mgi;
+                                rc = alga_write_merged_fasta_device(engine, &mg, merged_path.c_str(), &mgi);
+                                if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", merged_path.c_str(), alga_last_error(engine), rc); return 1; }
+                                fprintf(stderr, "Merged contigs written -> %s: %llu records, %llu bytes\n", merged_path.c_str(), (unsigned long long) mgi.segments,
+                                        (unsigned long long) mgi.bytes);
+                            }
+                            if (!merge_layout.empty()) {                     // not a hot path: the host formats from the arrays that came back
+                                const size_t nt = (size_t) mg.n_targets, nj = (size_t) mg.n_merged, nm = (size_t) mg.n_members;
+                                std::vector<uint32_t> m_off(nj + 1), start(nt);
+                                std::vector<int32_t> members(nm), rank(nt), ov(nt), tlen(nt);
+                                std::vector<uint8_t> orient(nt), mm(2 * nt);
+                                rc = alga_copy_to_host(engine, m_off.data(), mg.d_m_off, (nj + 1) * sizeof(uint32_t));
+                                if (rc == ALGA_OK && nm) rc = alga_copy_to_host(engine, members.data(), mg.d_m_members, nm * sizeof(int32_t));
+                                if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, rank.data(), mg.d_rank, nt * sizeof(int32_t));
+                                if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, ov.data(), mg.d_overlap_after, nt * sizeof(int32_t));
+                                if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, tlen.data(), gw.d_len, nt * sizeof(int32_t));
+                                if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, start.data(), mg.d_start, nt * sizeof(uint32_t));
+                                if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, orient.data(), mg.d_orient, nt);
+                                if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, mm.data(), mg.d_mm, 2 * nt);
+                                FILE *f = rc == ALGA_OK ? fopen(merge_layout.c_str(), "w") : nullptr;
+                                if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", merge_layout.c_str()); return 1; }
+                                for (size_t j = 0; f && j < nj; j++)
+                                    for (uint32_t k = m_off[j]; k < m_off[j + 1]; k++) {
+                                        const size_t c = (size_t) members[k];
+                                        fprintf(f, "%zu\t%d\t%zu\t%c\t%u\t%d\t%d\t%d\n", j, rank[c], c, orient[c] ? '-' : '+', start[c], tlen[c], ov[c],
+                                                ov[c] ? (int) mm[2 * c + (orient[c] ^ 1)] : 0);
+                                    }
+                                if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", merge_layout.c_str()); return 1; }
+                            }
+                            // the same reads on the merged contigs (the merge result keeps its own copy of the bases)
+                            if (rc == ALGA_OK) rc = alga_place_reads_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, mg.d_words, mg.d_begin, mg.d_len,
+                                                                            (int32_t) mg.n_merged, &pp, nullptr, &pl3, &pi3);
+                            if (rc == ALGA_OK) {
+                                fprintf(stderr, "Reads placed on the merged contigs: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
+                                        "median insert %lld; call %.1f ms wall\n", (unsigned long long) pi3.reads, (unsigned long long) pi3.placed, (unsigned long long) pi3.unique,
+                                        (unsigned long long) pi3.multi, (unsigned long long) pi3.unplaced, (unsigned long long) pi3.pairs_proper, (unsigned long long) pi3.pairs,
+                                        (long long) pi3.insert_median, pi3.ms_total);
+                                spl = &pl3; spi = &pi3; spol = nullptr;
+                            }
                         }
                     }
                     if (rc == ALGA_OK && !scaffolds.empty()) {

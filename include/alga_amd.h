@@ -1605,6 +1605,103 @@ int  alga_grow_placed_device(alga_engine *e, const alga_nodes *nodes, const alga
                              const alga_grow_params *p, void *hip_stream, alga_grown *out, alga_grow_info *info /* may be NULL */);
 int  alga_write_grown_fasta_device(alga_engine *e, const alga_grown *grown, const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- contigs whose ends overlap merged into one sequence (alga_amd/csrc/merge_kernels.hip, engine_merge.hip) ----------------------------------
+ * The grow stage stops where two grown ends overlap: they stay two contigs, and the scaffolder can only put min_gap Ns between them.  Here the
+ * ends of different targets are compared with each other, ends that choose each other unambiguously are joined, the paths are ordered and
+ * oriented, and the merged contigs come out as a new target set with its own copy of the bases.  No reads, no placement, nothing of the
+ * engine's state but the stage's own result.  Integers only, free of any order (thread, atomics, sort); tests/merge_checker.py states the rule
+ * twice in Python and the device result equals it array for array.  place -> [polish] -> [break -> place] -> grow -> merge -> place on the
+ * merged contigs -> scaffold; a further round is a further call.
+ *
+ * Inputs: a ragged target set as alga_place_reads_device takes it (d_words, d_begin uint64 base index, d_len int32, n_targets = T; a negative
+ * length answers ALGA_ERR_INVALID_ARGUMENT, checked on the device before anything is written; a column sum above 2^32 - 2 or more than 2^30
+ * targets answers ALGA_ERR_CAPACITY), and alga_merge_params: k 8 .. 31 (default 21), max_mismatches 0 .. 254 (1), max_occ 1 .. 65535 (256),
+ * min_overlap k .. max_overlap (42 = k * (max_mismatches + 1): by pigeonhole the seed condition of item 3 then follows from the Hamming bound
+ * wherever no seed is over max_occ), max_overlap min_overlap .. min(4096, 64 k) (512; an end has at most 64 seeds: one wave holds them all),
+ * flags 0, reserved 0; anything else answers ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Ends.  Target t of n bases has two ends, x = 2t (left) and x = 2t + 1 (right); W_x = min(n >> 1, max_overlap).  E_{2t+1} is the last
+ *      W_x bases of t, E_{2t} the reverse complement of the first W_x bases: in both the contig end is at the right (the grow stage's
+ *      convention).  P_x is the reverse complement of E_x: the first W_x bases read inward from end x.  Because W_x <= n / 2 the two windows of
+ *      a target never share a column, an overlap never contains a whole target, and the two overlaps of a doubly joined target never exceed
+ *      its length.
+ *   2. Index.  Position q of E_x is indexed for 0 <= q <= W_x - k; no k-mer spans two end sequences.  occ(v) = the number of indexed
+ *      positions over all ends whose k-mer is v.
+ *   3. Overlaps.  (x, y, o) is an overlap at end x iff x and y are ends of DIFFERENT targets; min_overlap <= o <= min(W_x, W_y); mm, the
+ *      Hamming distance between P_x[0 .. o) and the last o bases of E_y, is <= max_mismatches; some seed j of P_x (bases jk .. jk + k - 1) with
+ *      (j + 1) k <= o is USABLE (1 <= occ <= max_occ) and equals E_y[W_y - o + jk ..) exactly.  mm is the same seen from y; the seed condition
+ *      need not be, and that is part of the rule.  An overlap of a target's end with that target's own other end (a ring of one) is no
+ *      overlap here and counts nowhere.
+ *   4. Per end.  hits[x] = the number of distinct (y, o), saturated at 255; best = the smallest (mm, y, o descending).  d_partner[x] = best.y
+ *      (-1 without an overlap), d_olen[x] = best.o, d_mm[x], d_hits[x]; d_end_state: ALGA_MERGE_END_HAS_OVERLAP, ALGA_MERGE_END_AMBIGUOUS
+ *      (hits > 1), ALGA_MERGE_END_JOINED, ALGA_MERGE_END_DROPPED_CYCLE.
+ *   5. Joins.  Ends x and y are joined iff hits[x] == 1 and hits[y] == 1, partner[x] == y and partner[y] == x, olen[x] == olen[y].  Any second
+ *      overlap within the bound stops the join: another partner, or the same partner at another o (a periodic end).  An end has at most one
+ *      join.
+ *   6. Cycles, paths, orientation, numbering: items 6 and 7 of the scaffold definition.  A cycle is opened at its smallest contig id c: the
+ *      join at end 2c is dropped, both of its ends get DROPPED_CYCLE and lose JOINED, it counts in joins_dropped_cycle.  A path starts at its
+ *      terminal contig of smaller id, entered at its free end; a contig entered at end 0 has orientation + (d_orient 0), else - (1).  Merged
+ *      contigs are numbered by the ascending id of their first contig.  A target of length 0 belongs to none (d_merged = d_rank = -1).
+ *   7. Layout.  d_overlap_after[c] = the o of the join by which c is left, 0 for the last contig of a path; d_start[c] = the sum of
+ *      len - overlap_after over the contigs before c; the merged length = start[last] + len[last].  A merged length above 2^31 - 1 answers
+ *      ALGA_ERR_CAPACITY, before d_words is allocated.
+ *   8. Bases.  Column p of merged contig j belongs to the member m of largest rank with start[m] <= p, unless m has a predecessor and
+ *      p < start[prev] + len[prev]: then to the predecessor (the overlapped bases are the earlier contig's).  At most two members cover a
+ *      column (item 1).  The base is that of the oriented contig at p - start.
+ *   9. Result (alga_merged; engine-owned, valid until the next merge call on `e`: no other call invalidates it; kept twice and swapped at the
+ *      end of a call, so a refused or failed call leaves the earlier result valid and a call may take its targets from the previous merge
+ *      result).  Per end (2T): d_partner, d_olen, d_mm, d_hits, d_end_state.  Per target (T): d_merged, d_rank, d_orient, d_start,
+ *      d_overlap_after.  d_m_off [n_merged + 1] and d_m_members [n_members]: the members in rank order.  d_len [n_merged], d_col_off
+ *      [n_merged + 1], d_begin [n_merged] (= col_off), d_words: the result's OWN copy in column space (the polish's layout,
+ *      (n_columns + 15) / 16 + 2 words, the bits past n_columns zero).  (d_words, d_begin, d_len, n_merged) is a target set as
+ *      alga_place_reads_device takes it.
+ *  10. Counters (alga_merge_info): ends (those with W_x >= min_overlap: no other can overlap), index_positions, seeds (of those ends: the j
+ *      with (j + 1) k <= W_x), seeds_over_max_occ, ends_with_overlap, ends_ambiguous, hits_saturated; joins (the kept ones),
+ *      joins_dropped_cycle, join_mismatches (the sum of mm over the kept joins), bases_removed (the sum of their o), longest_overlap (their
+ *      largest o); merged, merged_multi, longest, columns_before, columns_after; n50_before, n50_after (the scaffold's N50, on the host from
+ *      lengths read back only when `info` is given); ms_index (check, end sequences, keys, sort, directory), ms_overlap (k_mg_overlap),
+ *      ms_build (joins, cycles, ranks, layout, scan, build) (HIP events), ms_total (wall).
+ * Read-backs: the refusal flag with the column sum; the padded end columns and the indexed positions (the sort and the directory are sized by
+ * them); the merged contigs, members and columns (d_words is allocated at its size); the lengths for the N50s.
+ *
+ * alga_write_merged_fasta_device: one record per merged contig, in id order, `>contig_id=<j>_length=<len>_contigs=<m>`.  `merged` must be the
+ * engine's current merge result.  ABI stays 7: the calls add. */
+#define ALGA_MERGE_END_HAS_OVERLAP   1
+#define ALGA_MERGE_END_AMBIGUOUS     2
+#define ALGA_MERGE_END_JOINED        4
+#define ALGA_MERGE_END_DROPPED_CYCLE 8
+typedef struct {
+    int32_t k, max_mismatches, max_occ, min_overlap, max_overlap, flags;
+    int32_t reserved[2];             /* 0                                                                                             */
+} alga_merge_params;
+typedef struct {
+    int64_t         n_targets, n_merged, n_members;
+    uint64_t        n_columns;       /* of the merged contigs: d_col_off[n_merged]                                                    */
+    const int32_t  *d_partner, *d_olen;   /* 2 * n_targets                                                                            */
+    const uint8_t  *d_mm, *d_hits, *d_end_state;
+    const int32_t  *d_merged, *d_rank;    /* n_targets                                                                                */
+    const uint8_t  *d_orient;
+    const uint32_t *d_start;
+    const int32_t  *d_overlap_after;
+    const uint32_t *d_m_off;         /* n_merged + 1                                                                                  */
+    const int32_t  *d_m_members;     /* n_members                                                                                     */
+    const int32_t  *d_len;           /* n_merged                                                                                      */
+    const uint32_t *d_col_off;       /* n_merged + 1                                                                                  */
+    const uint64_t *d_begin;         /* n_merged                                                                                      */
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+} alga_merged;
+typedef struct {
+    uint64_t ends, index_positions, seeds, seeds_over_max_occ, ends_with_overlap, ends_ambiguous, hits_saturated, joins, joins_dropped_cycle, join_mismatches,
+             bases_removed, longest_overlap, merged, merged_multi, longest, columns_before, columns_after;
+    uint64_t n50_before, n50_after;
+    double   ms_index, ms_overlap, ms_build;   /* device time (HIP events)                                                            */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_merge_info;
+void alga_merge_default_params(alga_merge_params *p);
+int  alga_merge_targets_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
+                               const alga_merge_params *p, void *hip_stream, alga_merged *out, alga_merge_info *info /* may be NULL */);
+int  alga_write_merged_fasta_device(alga_engine *e, const alga_merged *merged, const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
