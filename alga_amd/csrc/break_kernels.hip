@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "break_kernels.h"
+#include "seed_device.h"
 #include "text_record.h"
 
 namespace alga {
@@ -34,16 +35,6 @@ constexpr uint8_t BR_ST_UNIQUE = 2, BR_ST_MINUS = 4;                    // ALGA_
 __device__ __forceinline__ uint32_t br_wave_or(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v |= (uint32_t) __shfl_xor((int) v, o);
     return v;
-}
-
-// the target of column g < col_off[T]: the last t with col_off[t] <= g (it has a length: col_off[t + 1] > g)
-__device__ __forceinline__ uint32_t br_target_of(const uint32_t *__restrict__ col_off, uint32_t T, uint32_t g) {
-    uint32_t lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (col_off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(BR_BLOCK) k_br_check(BrReads r, BrTargets t, unsigned long long *__restrict__ counters) {
@@ -110,8 +101,8 @@ __global__ void __launch_bounds__(BR_BLOCK) k_br_flags(BrTargets t, const uint32
         const uint64_t g = g0 + (uint64_t) lane;
         if (g >= t.columns) continue;
         const uint64_t glast = g0 + 63 < t.columns ? g0 + 63 : t.columns - 1;
-        uint32_t tt = br_target_of(t.col_off, t.T, (uint32_t) g0);               // the same in all lanes
-        if ((uint64_t) t.col_off[tt + 1] <= glast) tt = br_target_of(t.col_off, t.T, (uint32_t) g);   // the wave's columns lie in several targets
+        uint32_t tt = item_of(t.col_off, t.T, (uint32_t) g0);               // the same in all lanes
+        if ((uint64_t) t.col_off[tt + 1] <= glast) tt = item_of(t.col_off, t.T, (uint32_t) g);   // the wave's columns lie in several targets
         const uint32_t c0 = t.col_off[tt];
         const long long j = (long long) g - c0, hi = (long long) t.col_off[tt + 1] - c0 - (long long) margin;   // candidates: margin <= j < hi
         const uint32_t sp = span[g];
@@ -171,7 +162,7 @@ __global__ void __launch_bounds__(BR_BLOCK) k_br_cuts(BrTargets t, const uint32_
         if (at >= c.n) continue;                                                // (cannot be: the count came from closed[])
         const uint32_t s = run_first[i], e = run_last[i];
         c.cols[at] = (uint32_t) (((uint64_t) s + e + 1) >> 1); c.first[at] = s; c.last[at] = e;
-        atomicAdd(&c.t_cuts[br_target_of(t.col_off, t.T, s)], 1u);
+        atomicAdd(&c.t_cuts[item_of(t.col_off, t.T, s)], 1u);
     }
 }
 
@@ -192,7 +183,7 @@ __global__ void __launch_bounds__(BR_BLOCK) k_br_pieces(BrTargets t, BrCuts c, B
             n_tcut += lo < c.n && c.cols[lo] < t.col_off[tt + 1];
         } else {
             const uint64_t i = x - t.T;
-            col = c.cols[i]; tt = br_target_of(t.col_off, t.T, col);
+            col = c.cols[i]; tt = item_of(t.col_off, t.T, col);
             id = i + (uint64_t) tt + 1; next_cut = (uint32_t) (i + 1);
         }
         const uint32_t end_t = t.col_off[tt + 1];

@@ -43,16 +43,6 @@ bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
            pl->n_columns <= 0xFFFFFFFEull && pl->n_hist >= 1 && (uint64_t) pl->n_hist == e->pl_nhist;
 }
 
-// the largest length l such that the sequences of length >= l hold at least half of all bases (the scaffold's N50)
-uint64_t n50_of(std::vector<uint64_t> v) {
-    std::sort(v.begin(), v.end(), [](uint64_t a, uint64_t b) { return a > b; });
-    unsigned __int128 total = 0, cum = 0;
-    for (uint64_t x : v) total += x;
-    if (total == 0) return 0;
-    for (uint64_t x : v) { cum += x; if (2 * cum >= total) return x; }
-    return 0;
-}
-
 int break_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_polished *pol, const alga_break_params *p,
                hipStream_t s, alga_broken *out, alga_break_info *info) {
     const auto t0 = std::chrono::steady_clock::now();

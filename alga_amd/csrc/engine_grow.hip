@@ -3,7 +3,7 @@
 //
 // Host side: the check runs on a workspace and ends in one read-back (the refusal flags, the longest node).  Then, still on workspaces: the
 // candidate flags, their scan and the list; W_e of every end and the scan; a read-back of the candidate count, the end columns and the indexed
-// positions (they size the sort and the directory); the end sequences, their (k-mer, column) pairs sorted on 2k + 1 bits, the directory.  The
+// positions (they size the sort and the directory); the end sequences, the seed index over them (alga_seed_index).  The
 // result is written into the set of buffers that does NOT hold the current result: k_gr_place, the votes, the decision, the new lengths; a
 // read-back of the counters (the new column count sizes the result's bases, and is the last refusal); the scan and the build.  The sets are
 // swapped at the end, so a call that is refused or fails anywhere leaves an earlier result as it was.  The lengths for the N50s come back only
@@ -19,7 +19,6 @@
 #include "correct_kernels.h"
 #include "gfa_kernels.h"
 #include "ingest_kernels.h"
-#include "place_kernels.h"
 #include "grow_kernels.h"
 
 using namespace alga;
@@ -52,16 +51,6 @@ bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
            pl->n_columns <= 0xFFFFFFFEull && pl->n_hist >= 1 && (uint64_t) pl->n_hist == e->pl_nhist;
 }
 
-// the largest length l such that the sequences of length >= l hold at least half of all bases (the scaffold's N50)
-uint64_t n50_of(std::vector<uint64_t> v) {
-    std::sort(v.begin(), v.end(), [](uint64_t a, uint64_t b) { return a > b; });
-    unsigned __int128 total = 0, cum = 0;
-    for (uint64_t x : v) total += x;
-    if (total == 0) return 0;
-    for (uint64_t x : v) { cum += x; if (2 * cum >= total) return x; }
-    return 0;
-}
-
 int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polished *pol, const alga_grow_params *p, hipStream_t s, alga_grown *out,
               alga_grow_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -70,11 +59,10 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     int rc;
     GrEvents evs;
     for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
-    // (the directory fill of the placement counts the distinct k-mers into a counter block of its own layout: it gets the words behind ours)
-    if ((rc = alga_ensure(e, e->gr_cnt, (GR_COUNTERS + PL_COUNTERS) * sizeof(unsigned long long)))) return rc;
+    if ((rc = alga_ensure(e, e->gr_cnt, GR_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->gr_cnt.p, *hc = e->h_counters;
-    HIP_TRY(e, hipMemsetAsync(cnt, 0, (GR_COUNTERS + PL_COUNTERS) * sizeof(unsigned long long), s));
-    const GrReads rd{nodes->words, nodes->stride_words, nodes->len, R};
+    HIP_TRY(e, hipMemsetAsync(cnt, 0, GR_COUNTERS * sizeof(unsigned long long), s));
+    const SeedReads rd{nodes->words, nodes->stride_words, nodes->len, R};
     const GrTargets tg{pl->d_col_off, (uint32_t) T, C, pol ? pol->d_words : (const uint32_t *) e->pl_cols.p};
 
     // the check: nothing of the result is written before its verdict
@@ -118,21 +106,11 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
 
     // the list, the end sequences, the index
     const size_t ec_words = (size_t) ((EC + 15) >> 4) + 2;
-    const int blocks = gr_place_blocks(n_cand, e->n_cu);
-    const size_t ub_words = gr_place_scratch_words(blocks, max_len, p->k);
-    int bits = e->opt_place_dir_bits;
-    if (bits <= 0) { bits = 1; while (bits < PL_DIR_BITS_MAX && (n_index >> bits) > 2) bits++; }
-    bits = std::min(bits, 2 * p->k);
+    const int blocks = seed_blocks(n_cand, e->n_cu);
+    const size_t ub_words = seed_scratch_words(blocks, max_len, p->k);
     if ((rc = alga_ensure(e, e->gr_cand, (n_cand + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gr_ecols, ec_words * sizeof(uint32_t)))) return rc;
-    for (int j = 0; j < 2; j++) {
-        if ((rc = alga_ensure(e, e->gr_keys[j], (EC + 2) * sizeof(unsigned long long)))) return rc;
-        if ((rc = alga_ensure(e, e->gr_vals[j], (EC + 2) * sizeof(uint32_t)))) return rc;
-    }
-    if ((rc = alga_ensure(e, e->gr_dir, (((size_t) 1 << bits) + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->gr_ub, ub_words * sizeof(unsigned long long)))) return rc;
-    const size_t temp = sort_u64_u32_temp_bytes(EC);
-    if ((rc = alga_ensure(e, e->sort_temp, temp))) return rc;
+    if ((rc = alga_ensure(e, e->seed_ub, ub_words * sizeof(unsigned long long)))) return rc;
     uint32_t *cand = (uint32_t *) e->gr_cand.p, *ecols = (uint32_t *) e->gr_ecols.p;
     launch_gr_compact(flag, pos, R, cand, s);
     if ((rc = alga_check_launch(e, "k_gr_compact"))) return rc;
@@ -140,13 +118,8 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     HIP_TRY(e, hipMemsetAsync(ecols, 0, ec_words * sizeof(uint32_t), s));
     launch_gr_ends(tg, en, ecols, s);
     if ((rc = alga_check_launch(e, "k_gr_ends"))) return rc;
-    launch_gr_keys(en, p->k, (unsigned long long *) e->gr_keys[0].p, (uint32_t *) e->gr_vals[0].p, s);
-    if ((rc = alga_check_launch(e, "k_gr_keys"))) return rc;
-    if (EC) HIP_TRY(e, sort_u64_u32(e->sort_temp.p, temp, (const unsigned long long *) e->gr_keys[0].p, (unsigned long long *) e->gr_keys[1].p, (const uint32_t *) e->gr_vals[0].p,
-                                    (uint32_t *) e->gr_vals[1].p, EC, 2 * p->k + 1, s));
-    const GrIndex ix{(const unsigned long long *) e->gr_keys[1].p, (const uint32_t *) e->gr_vals[1].p, (const uint32_t *) e->gr_dir.p, 2 * p->k - bits, (uint32_t) n_index};
-    launch_pl_dir(ix.keys, n_index, ix.shift, bits, (uint32_t *) e->gr_dir.p, cnt + GR_COUNTERS, s);
-    if ((rc = alga_check_launch(e, "k_pl_dir"))) return rc;
+    SeedIndex ix;
+    if ((rc = alga_seed_index(e, en, p->k, n_index, nullptr, s, &ix))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
     // the result, into the set that is not the current one
@@ -170,8 +143,8 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     HIP_TRY(e, hipMemsetAsync(count, 0, count_bytes + 16, s));
     HIP_TRY(e, hipMemsetAsync(voters, 0, (E + 2) * sizeof(uint32_t), s));
     HIP_TRY(e, hipMemsetAsync(new_off, 0, (T + 2) * sizeof(uint32_t), s));
-    launch_gr_place(rd, cand, n_cand, en, ix, p->k, p->max_mismatches, p->max_occ, p->min_anchor, go, (unsigned long long *) e->gr_ub.p,
-                    (uint32_t) (ub_words / ((size_t) blocks * 4)), blocks, cnt, s);
+    launch_gr_place(rd, cand, n_cand, en, ix, p->k, p->max_mismatches, p->max_occ, p->min_anchor, go, (unsigned long long *) e->seed_ub.p,
+                    (uint32_t) (ub_words / ((size_t) blocks * SEED_WAVES)), blocks, cnt, s);
     if ((rc = alga_check_launch(e, "k_gr_place"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 

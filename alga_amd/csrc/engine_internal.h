@@ -178,17 +178,20 @@ struct alga_engine {
     DevBuf      cr_cnt, cr_table, cr_hist, cr_keys[2], cr_flag, cr_pos, cr_solid, cr_dir;
     int64_t     opt_correct_slice_keys = 1ll << 28;   // option "correct_slice_keys": occurrences a slice of the k-mer count holds (a single bin above it is a slice of its own)
     int         opt_correct_dir_bits = 0;             // option "correct_dir_bits": bits of the solid keys' directory, 0 = about two keys per bucket (tests force long and empty buckets)
+    // the seed index of the call at hand (seed_index.hip; the placement, the grow and the merge build theirs here, and none reads an earlier
+    // call's): the (k-mer, column) pairs before and after the sort, the directory, the per-wave usable-seed masks of the kernel that seeds from it
+    DevBuf      seed_keys[2], seed_vals[2], seed_dir, seed_ub;
     // reads placed on sequences (engine_place.hip).  Workspaces: counters, the targets of a final result, the lengths' scan, the column array, the
-    // (k-mer, column) pairs before and after the sort, the directory, the per-wave seed masks, the difference array.  The result: per read target /
-    // pos / mm / hits / state, col_off, the scan of the differences (the cover is its entries from 1 on), the per-target sums, the histogram
-    DevBuf      pl_cnt, pl_fbegin, pl_flen, pl_scan, pl_cols, pl_keys[2], pl_vals[2], pl_dir, pl_ub, pl_diff;
+    // difference array.  The result: per read target / pos / mm / hits / state, col_off, the scan of the differences (the cover is its entries
+    // from 1 on), the per-target sums, the histogram
+    DevBuf      pl_cnt, pl_fbegin, pl_flen, pl_scan, pl_cols, pl_diff;
     DevBuf      pl_target, pl_pos, pl_mm, pl_hits, pl_state, pl_coloff, pl_cover, pl_tstat, pl_hist;
     bool        pl_valid = false;                  // the result buffers hold a placement
     uint64_t    pl_targets = 0, pl_reads = 0;      // ... of this many reads on this many targets
     uint64_t    pl_ncolumns = 0, pl_nhist = 0;      // ... its col_off[pl_targets] and the bins of its insert histogram (max_insert + 1)
     uint64_t    pl_final_epoch = 0;                // ... made on the final result of this epoch (0: on caller's targets)
     uint64_t    fc_epoch = 0;                      // counts the alga_final_contigs_device calls that wrote a result
-    int         opt_place_dir_bits = 0;            // option "place_dir_bits": bits of the placement index's directory, 0 = about two positions per bucket
+    int         opt_place_dir_bits = 0;            // option "place_dir_bits": bits of the seed index's directory, 0 = about two positions per bucket
     // the placed targets voted again (engine_polish.hip).  Workspaces: counters, the (first column, node) pairs before and after the sort, the
     // per-word masks, their popcounts and the scan.  The result: its own copy of col_off, the polished column array, the change list, the
     // per-target sums (changed, ambiguous), the optional counts
@@ -216,18 +219,17 @@ struct alga_engine {
     bool        br_valid = false;                  // the result buffers hold a break result
     uint64_t    br_targets = 0, br_pieces = 0, br_cuts = 0, br_columns = 0, br_longest = 0;   // ... of this many targets, pieces, cuts, columns; the longest piece
     // contig ends grown with the reads that hang over them (engine_grow.hip).  Workspaces: counters, the candidate flags, their scan and the
-    // list, the end lengths and their scan, the end sequences, the (k-mer, end column) pairs before and after the sort, the directory, the
-    // per-wave seed masks, the growth per end and its bases.  The result, twice: a call writes the set that is not the current one and
-    // swaps it in at its end, so a call that fails anywhere leaves the earlier result as it was
-    DevBuf      gr_cnt, gr_flag, gr_pos, gr_cand, gr_elen, gr_eoff, gr_ecols, gr_keys[2], gr_vals[2], gr_dir, gr_ub, gr_x, gr_g;
+    // list, the end lengths and their scan, the end sequences, the growth per end and its bases.  The result, twice: a call writes the set
+    // that is not the current one and swaps it in at its end, so a call that fails anywhere leaves the earlier result as it was
+    DevBuf      gr_cnt, gr_flag, gr_pos, gr_cand, gr_elen, gr_eoff, gr_ecols, gr_x, gr_g;
     struct GrowSet { DevBuf end, over, mm, hits, state, count, estop, evoters, left, right, len, coloff, begin, words; } gr_set[2];
     int         gr_cur = 0;                        // the set that holds the result
     bool        gr_valid = false;
     uint64_t    gr_reads = 0, gr_targets = 0, gr_columns = 0, gr_longest = 0;   // ... of this many reads, targets and columns; the longest grown target
     // contigs whose ends overlap merged into one sequence (engine_merge.hip).  Workspaces: counters, the end lengths, their padded lengths and
-    // the scan, the end sequences and their reverse complements, the (k-mer, end column) pairs before and after the sort, the directory, the
-    // join of every end, the lists over the 2T states (twice), head / first / members and their scans.  The result, twice, as for the grow
-    DevBuf      mg_cnt, mg_elen, mg_epad, mg_eoff, mg_ecols, mg_pcols, mg_keys[2], mg_vals[2], mg_dir, mg_join, mg_lists[2], mg_head, mg_first, mg_scan;
+    // the scan, the end sequences and their reverse complements, the join of every end, the lists over the 2T states (twice), head / first /
+    // members and their scans.  The result, twice, as for the grow
+    DevBuf      mg_cnt, mg_elen, mg_epad, mg_eoff, mg_ecols, mg_pcols, mg_join, mg_lists[2], mg_head, mg_first, mg_scan;
     struct MergeSet { DevBuf partner, olen, mm, hits, estate, merged, rank, orient, start, ovafter, moff, mmembers, len, coloff, begin, words; } mg_set[2];
     int         mg_cur = 0;                        // the set that holds the result
     bool        mg_valid = false;
@@ -328,6 +330,16 @@ inline int alga_ensure(alga_engine *e, DevBuf &b, size_t bytes) {
 inline void alga_forget_node_set(alga_engine *e) {
     e->keyed_n = -1; e->store_n = -1; e->pile_n = -1;
     e->stat_len = nullptr; e->stat_from = nullptr; e->stat_to = nullptr;
+}
+
+// the largest length l such that the sequences of length >= l hold at least half of all bases
+inline uint64_t n50_of(std::vector<uint64_t> v) {
+    std::sort(v.begin(), v.end(), [](uint64_t a, uint64_t b) { return a > b; });
+    unsigned __int128 total = 0, cum = 0;
+    for (uint64_t x : v) total += x;
+    if (total == 0) return 0;
+    for (uint64_t x : v) { cum += x; if (2 * cum >= total) return x; }
+    return 0;
 }
 
 inline void alga_release(DevBuf &b) {

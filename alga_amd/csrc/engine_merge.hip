@@ -3,7 +3,7 @@
 //
 // Host side: the check runs on a workspace and ends in one read-back (the refusal flag, the column sum).  Then, still on workspaces: W_x of
 // every end and the scan; a read-back of the end columns and the indexed positions (they size the sort and the directory); the end sequences,
-// their (k-mer, column) pairs sorted on 2k + 1 bits, the directory.  The result is written into the set of buffers that does NOT hold the
+// the seed index over them (alga_seed_index).  The result is written into the set of buffers that does NOT hold the
 // current result: k_mg_overlap, the joins, the cycles, the ranks, the layout; a read-back of the counters (the merged contigs, their members and
 // columns size what follows, and the longest merged contig is the last refusal); the scan and the build.  The sets are swapped at the end, so a
 // call that is refused or fails anywhere leaves an earlier result as it was, and a call may take its targets from that result.  The lengths
@@ -18,7 +18,6 @@
 #include "engine_internal.h"
 #include "gfa_kernels.h"
 #include "ingest_kernels.h"
-#include "place_kernels.h"
 #include "merge_kernels.h"
 
 using namespace alga;
@@ -41,16 +40,6 @@ int check_params(alga_engine *e, const alga_merge_params *p) {
     return ALGA_OK;
 }
 
-// the largest length l such that the sequences of length >= l hold at least half of all bases (the scaffold's N50)
-uint64_t n50_of(std::vector<uint64_t> v) {
-    std::sort(v.begin(), v.end(), [](uint64_t a, uint64_t b) { return a > b; });
-    unsigned __int128 total = 0, cum = 0;
-    for (uint64_t x : v) total += x;
-    if (total == 0) return 0;
-    for (uint64_t x : v) { cum += x; if (2 * cum >= total) return x; }
-    return 0;
-}
-
 int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long *d_begin, const int32_t *d_len, int32_t n_targets, const alga_merge_params *p, hipStream_t s,
                alga_merged *out, alga_merge_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -58,10 +47,9 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     int rc;
     MgEvents evs;
     for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
-    // (the directory fill of the placement counts the distinct k-mers into a counter block of its own layout: it gets the words behind ours)
-    if ((rc = alga_ensure(e, e->mg_cnt, (MG_COUNTERS + PL_COUNTERS) * sizeof(unsigned long long)))) return rc;
+    if ((rc = alga_ensure(e, e->mg_cnt, MG_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->mg_cnt.p, *hc = e->h_counters;
-    HIP_TRY(e, hipMemsetAsync(cnt, 0, (MG_COUNTERS + PL_COUNTERS) * sizeof(unsigned long long), s));
+    HIP_TRY(e, hipMemsetAsync(cnt, 0, MG_COUNTERS * sizeof(unsigned long long), s));
     const MgTargets tg{d_words, d_begin, d_len, (uint32_t) T};
 
     // the check: nothing of the result is written before its verdict
@@ -92,31 +80,16 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
 
     // the end sequences, the index
     const size_t ec_words = (size_t) (EC >> 4) + 2;
-    int bits = e->opt_place_dir_bits;
-    if (bits <= 0) { bits = 1; while (bits < PL_DIR_BITS_MAX && (n_index >> bits) > 2) bits++; }
-    bits = std::min(bits, 2 * p->k);
     if ((rc = alga_ensure(e, e->mg_ecols, ec_words * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->mg_pcols, ec_words * sizeof(uint32_t)))) return rc;
-    for (int j = 0; j < 2; j++) {
-        if ((rc = alga_ensure(e, e->mg_keys[j], (EC + 2) * sizeof(unsigned long long)))) return rc;
-        if ((rc = alga_ensure(e, e->mg_vals[j], (EC + 2) * sizeof(uint32_t)))) return rc;
-    }
-    if ((rc = alga_ensure(e, e->mg_dir, (((size_t) 1 << bits) + 2) * sizeof(uint32_t)))) return rc;
-    const size_t temp = sort_u64_u32_temp_bytes(EC);
-    if ((rc = alga_ensure(e, e->sort_temp, temp))) return rc;
     uint32_t *ecols = (uint32_t *) e->mg_ecols.p, *pcols = (uint32_t *) e->mg_pcols.p;
-    const MgEnds en{eoff, elen, (uint32_t) E, EC, ecols, pcols};
+    const MgEnds en{{eoff, elen, (uint32_t) E, EC, ecols}, pcols};
     HIP_TRY(e, hipMemsetAsync(ecols, 0, ec_words * sizeof(uint32_t), s));
     HIP_TRY(e, hipMemsetAsync(pcols, 0, ec_words * sizeof(uint32_t), s));
     launch_mg_ends(tg, en, ecols, pcols, s);
     if ((rc = alga_check_launch(e, "k_mg_ends"))) return rc;
-    launch_mg_keys(en, p->k, (unsigned long long *) e->mg_keys[0].p, (uint32_t *) e->mg_vals[0].p, s);
-    if ((rc = alga_check_launch(e, "k_mg_keys"))) return rc;
-    if (EC) HIP_TRY(e, sort_u64_u32(e->sort_temp.p, temp, (const unsigned long long *) e->mg_keys[0].p, (unsigned long long *) e->mg_keys[1].p, (const uint32_t *) e->mg_vals[0].p,
-                                    (uint32_t *) e->mg_vals[1].p, EC, 2 * p->k + 1, s));
-    const MgIndex ix{(const unsigned long long *) e->mg_keys[1].p, (const uint32_t *) e->mg_vals[1].p, (const uint32_t *) e->mg_dir.p, 2 * p->k - bits, (uint32_t) n_index};
-    launch_pl_dir(ix.keys, n_index, ix.shift, bits, (uint32_t *) e->mg_dir.p, cnt + MG_COUNTERS, s);
-    if ((rc = alga_check_launch(e, "k_pl_dir"))) return rc;
+    SeedIndex ix;
+    if ((rc = alga_seed_index(e, en, p->k, n_index, nullptr, s, &ix))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
     // the result, into the set that is not the current one
@@ -134,7 +107,7 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     if ((rc = alga_ensure(e, e->mg_scan, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                     // their scans
     const MgEndOut eo{(int32_t *) rs.partner.p, (int32_t *) rs.olen.p, (uint8_t *) rs.mm.p, (uint8_t *) rs.hits.p, (uint8_t *) rs.estate.p};
     uint32_t *join = (uint32_t *) e->mg_join.p, *col_off = (uint32_t *) rs.coloff.p;
-    launch_mg_overlap(en, ix, p->k, p->max_mismatches, p->max_occ, p->min_overlap, eo, mg_overlap_blocks(E, e->n_cu), cnt, s);
+    launch_mg_overlap(en, ix, p->k, p->max_mismatches, p->max_occ, p->min_overlap, eo, seed_blocks(E, e->n_cu), cnt, s);
     if ((rc = alga_check_launch(e, "k_mg_overlap"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 

@@ -3,7 +3,7 @@
 //
 // Host side: the checks run on workspaces and end in one read-back (the refusal flags, the number of columns and of indexed positions, the
 // longest read); only then are the result buffers touched, so a refused call leaves an earlier result as it was.  Then: scan of the target
-// lengths, the column array, (k-mer, column) of every column sorted on 2k + 1 bits, the directory, k_pl_place, the difference array and its
+// lengths, the column array, the seed index over it (alga_seed_index), k_pl_place, the difference array and its
 // scan, the per-target sums, the pairs; the counters and the histogram come back at the end.
 #include <hip/hip_runtime.h>
 
@@ -75,11 +75,8 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     // from here on the result is rewritten
     e->pl_valid = false; e->pl_serial++;
     const size_t col_words = (size_t) ((columns + 15) >> 4) + 2, n_hist = (size_t) p->max_insert + 1;
-    const int blocks = pl_place_blocks(R, e->n_cu);
-    const size_t ub_words = pl_place_scratch_words(blocks, max_read_len, p->k);
-    int bits = e->opt_place_dir_bits;
-    if (bits <= 0) { bits = 1; while (bits < PL_DIR_BITS_MAX && (n_index >> bits) > 2) bits++; }
-    bits = std::min(bits, 2 * p->k);
+    const int blocks = seed_blocks(R, e->n_cu);
+    const size_t ub_words = seed_scratch_words(blocks, max_read_len, p->k);
     for (DevBuf *b : {&e->pl_target, &e->pl_pos}) if ((rc = alga_ensure(e, *b, (R + 1) * sizeof(int32_t)))) return rc;
     for (DevBuf *b : {&e->pl_mm, &e->pl_hits, &e->pl_state}) if ((rc = alga_ensure(e, *b, R + 16))) return rc;
     if ((rc = alga_ensure(e, e->pl_coloff, (T + 2) * sizeof(uint32_t)))) return rc;
@@ -88,14 +85,7 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     if ((rc = alga_ensure(e, e->pl_tstat, (4 * T + 1) * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->pl_hist, n_hist * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->pl_cols, col_words * sizeof(uint32_t)))) return rc;
-    for (int j = 0; j < 2; j++) {
-        if ((rc = alga_ensure(e, e->pl_keys[j], (columns + 2) * sizeof(unsigned long long)))) return rc;
-        if ((rc = alga_ensure(e, e->pl_vals[j], (columns + 2) * sizeof(uint32_t)))) return rc;
-    }
-    if ((rc = alga_ensure(e, e->pl_dir, (((size_t) 1 << bits) + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->pl_ub, ub_words * sizeof(unsigned long long)))) return rc;
-    const size_t temp = sort_u64_u32_temp_bytes(columns);
-    if ((rc = alga_ensure(e, e->sort_temp, temp))) return rc;
+    if ((rc = alga_ensure(e, e->seed_ub, ub_words * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(std::max<uint64_t>(T + 1, columns + 1))))) return rc;
     uint32_t *col_off = (uint32_t *) e->pl_coloff.p, *cols = (uint32_t *) e->pl_cols.p, *scan = (uint32_t *) e->pl_cover.p, *diff = (uint32_t *) e->pl_diff.p;
     unsigned long long *tstat = (unsigned long long *) e->pl_tstat.p, *hist = (unsigned long long *) e->pl_hist.p;
@@ -109,18 +99,13 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     HIP_TRY(e, hipMemsetAsync(cols, 0, col_words * sizeof(uint32_t), s));
     launch_pl_gather(d_words, d_begin, tg, cols, s);
     if ((rc = alga_check_launch(e, "k_pl_gather"))) return rc;
-    launch_pl_keys(tg, p->k, (unsigned long long *) e->pl_keys[0].p, (uint32_t *) e->pl_vals[0].p, s);
-    if ((rc = alga_check_launch(e, "k_pl_keys"))) return rc;
-    HIP_TRY(e, sort_u64_u32(e->sort_temp.p, temp, (const unsigned long long *) e->pl_keys[0].p, (unsigned long long *) e->pl_keys[1].p, (const uint32_t *) e->pl_vals[0].p,
-                            (uint32_t *) e->pl_vals[1].p, columns, 2 * p->k + 1, s));
-    const PlIndex ix{(const unsigned long long *) e->pl_keys[1].p, (const uint32_t *) e->pl_vals[1].p, (const uint32_t *) e->pl_dir.p, 2 * p->k - bits, (uint32_t) n_index};
-    launch_pl_dir(ix.keys, n_index, ix.shift, bits, (uint32_t *) e->pl_dir.p, cnt, s);
-    if ((rc = alga_check_launch(e, "k_pl_dir"))) return rc;
+    SeedIndex ix;
+    if ((rc = alga_seed_index(e, tg, p->k, n_index, cnt + PL_DISTINCT, s, &ix))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
-    const PlReads rd{nodes->words, nodes->stride_words, nodes->len, R};
+    const SeedReads rd{nodes->words, nodes->stride_words, nodes->len, R};
     const PlOut po{(int32_t *) e->pl_target.p, (int32_t *) e->pl_pos.p, (uint8_t *) e->pl_mm.p, (uint8_t *) e->pl_hits.p, (uint8_t *) e->pl_state.p};
-    launch_pl_place(rd, tg, ix, p->k, p->max_mismatches, p->max_occ, po, (unsigned long long *) e->pl_ub.p, (uint32_t) (ub_words / ((size_t) blocks * 4)), blocks, cnt, s);
+    launch_pl_place(rd, tg, ix, p->k, p->max_mismatches, p->max_occ, po, (unsigned long long *) e->seed_ub.p, (uint32_t) (ub_words / ((size_t) blocks * SEED_WAVES)), blocks, cnt, s);
     if ((rc = alga_check_launch(e, "k_pl_place"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 

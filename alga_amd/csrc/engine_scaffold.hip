@@ -45,16 +45,6 @@ bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
            pl->d_col_off == (const uint32_t *) e->pl_coloff.p && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p;
 }
 
-// the largest length l such that the sequences of length >= l hold at least half of all bases
-uint64_t n50_of(std::vector<uint64_t> v) {
-    std::sort(v.begin(), v.end(), [](uint64_t a, uint64_t b) { return a > b; });
-    unsigned __int128 total = 0, cum = 0;
-    for (uint64_t x : v) total += x;
-    if (total == 0) return 0;
-    for (uint64_t x : v) { cum += x; if (2 * cum >= total) return x; }
-    return 0;
-}
-
 int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_scaffold_params *p, hipStream_t s,
                   alga_scaffolds *out, alga_scaffold_info *info) {
     const auto t0 = std::chrono::steady_clock::now();

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seed_index.h"
+
 namespace alga {
 
 // counters[] (unsigned long long): the refusal flags, then what the kernels count
@@ -13,12 +15,6 @@ enum { GR_BAD = 0, GR_BAD_TWIN /* a 32-bit flag of k_cr_twin */, GR_MAX_LEN, GR_
 constexpr uint32_t GR_BAD_LEN = 1, GR_BAD_COLUMNS = 2;                 // bits of counters[GR_BAD]
 constexpr uint8_t  GR_ST_OVERHANGS = 1, GR_ST_VOTES = 2, GR_ST_MINUS = 4;   // ALGA_GROW_* of include/alga_amd.h
 
-struct GrReads {
-    const uint32_t *rows;
-    int32_t stride;
-    const int32_t *len;               // 2R
-    uint64_t R;
-};
 // the placed targets in the placement's column space
 struct GrTargets {
     const uint32_t *col_off;          // T + 1
@@ -26,46 +22,30 @@ struct GrTargets {
     uint64_t columns;                 // col_off[T]
     const uint32_t *cols;             // their bases: the placement's column array or the polish's
 };
-// the 2T end sequences in a column space of their own: end e is the columns end_off[e] .. end_off[e] + elen[e], the contig end at the right
-struct GrEnds {
-    const uint32_t *end_off;          // 2T + 1
-    const int32_t *elen;              // 2T: W_e
-    uint32_t E;                       // 2T
-    uint64_t columns;                 // end_off[2T]
-    const uint32_t *cols;             // two words of padding behind the last column
-};
-struct GrIndex {
-    const unsigned long long *keys;   // sorted; the first n are k-mers
-    const uint32_t *vals;             // their end columns
-    const uint32_t *dir;
-    int shift;
-    uint32_t n;
-};
+// the 2T end sequences in a column space of their own, the space their index is built over (alga_seed_index): end e is the columns
+// off[e] .. off[e] + len[e] (len[e] = W_e), the contig end at the right; n = 2T
+typedef SeedSpace GrEnds;
 struct GrOut {
     int32_t *end, *over;
     uint8_t *mm, *hits, *state;
 };
 
 // every len <= 16 * stride, columns == col_off[T] (the flags of counters[GR_BAD]); counters[GR_MAX_LEN] = the longest node
-void launch_gr_check(const GrReads &r, const GrTargets &t, unsigned long long *counters, hipStream_t s);
+void launch_gr_check(const SeedReads &r, const GrTargets &t, unsigned long long *counters, hipStream_t s);
 // flag[r] = 1 where read r lacks PLACED and has len >= min_anchor + 1 (R + 1 entries, the last 0)
-void launch_gr_candidates(const GrReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, hipStream_t s);
+void launch_gr_candidates(const SeedReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, hipStream_t s);
 // the candidates' ids at the places the scan of flag[] gives
 void launch_gr_compact(const uint32_t *flag, const uint32_t *pos, uint64_t R, uint32_t *cand, hipStream_t s);
 // elen[e] = W_e (2T + 1 entries, the last 0); counters[GR_END_COLUMNS] += W_e, [GR_INDEX_POS] += max(0, W_e - k + 1)
 void launch_gr_end_lens(const GrTargets &t, int32_t max_len, int32_t k, int32_t *elen, unsigned long long *counters, hipStream_t s);
 // the end sequences, one thread per word: the right ends copied, the left ones complemented and mirrored
 void launch_gr_ends(const GrTargets &t, const GrEnds &e, uint32_t *ecols, hipStream_t s);
-// (k-mer, end column) of every end column; a column that is no indexed position gets a key above every k-mer
-void launch_gr_keys(const GrEnds &e, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s);
-// one wave per candidate, both nodes
-int    gr_place_blocks(uint64_t n_cand, int n_cu);
-size_t gr_place_scratch_words(int blocks, int64_t max_read_len, int32_t k);
-void launch_gr_place(const GrReads &r, const uint32_t *cand, uint64_t n_cand, const GrEnds &e, const GrIndex &x, int32_t k, int32_t max_mm, int32_t max_occ,
+// one wave per candidate, both nodes (blocks: seed_blocks(n_cand), the scratch: seed_scratch_words)
+void launch_gr_place(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ,
                      int32_t min_anchor, const GrOut &o, unsigned long long *scratch, uint32_t scratch_words_per_wave, int blocks, unsigned long long *counters,
                      hipStream_t s);
 // one wave per candidate that votes: count[(e * max_grow + i) * 4 + base]++, voters[e]++
-void launch_gr_vote(const GrReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, hipStream_t s);
+void launch_gr_vote(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, hipStream_t s);
 // one thread per end: x[e] = the leading passing columns, g[e * max_grow + i] their bases, stop[e]; the counters of the ends
 void launch_gr_decide(const uint32_t *count, const uint32_t *voters, uint32_t E, int32_t max_grow, int32_t min_cover, int32_t min_percent, uint32_t *x, uint8_t *g,
                       uint8_t *stop, unsigned long long *counters, hipStream_t s);

@@ -10,25 +10,24 @@
 //                     spends no wave on a placed read
 //   k_gr_end_lens     W_e of every end and the indexed positions; (scan): end_off
 //   k_gr_ends         the end sequences, one thread per word
-//   k_gr_keys         (k-mer, end column) of every end column; a column that is no indexed position gets a key above every k-mer
-//   k_gr_place        one wave per candidate, both nodes.  Lanes take seeds, 64 at a time, as in k_pl_place; a (seed j, occurrence at position q
-//                     of end e) gives a = W_e - q + j k and h = L - a.  A lane verifies the anchored part only: XOR and popcount over
-//                     funnel-shifted words of the end columns, the last partial word masked; the overhanging bases are never compared and
-//                     nothing is read past the two words of padding.  A candidate found through seed j counts only if no usable seed
-//                     j' < j matches there.  The minimum key and the number of placements at its mm are reduced across the wave.  The rows
-//                     are read from memory: no cap on the read length.
+//   (the index over the end columns: alga_seed_index, seed_index.hip)
+//   k_gr_place        one wave per candidate, both nodes: seed_and_verify (seed_device.h) once per node over the seeds with (j + 1) k <= L - 1.
+//                     A (seed j, occurrence at position q of end e) gives a = W_e - q + j k and h = L - a; only the anchored part is
+//                     verified, the overhanging bases are never compared.  The minimum key and the number of placements at its mm are
+//                     reduced across the wave.
 //   k_gr_vote         one wave per candidate, a lane a growth column: 32-bit integer atomics into count
 //   k_gr_decide       one thread per end: the leading run of passing columns, their bases, the stop reason, the counters
 //   k_gr_lens         left / right / new length per target; (scan): the new col_off
 //   k_gr_build        every output word gathered by one lane, from the old column array or from the growth
 //   k_gr_fasta_sizes / k_gr_fasta_write   one record per target with a length, one wave per record, a lane a byte
-// Block 256 and the grid caps are picked, not tuned; k_gr_place runs 8 blocks per CU like k_pl_place.
+// Block 256 and the grid caps are picked, not tuned.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "grow_kernels.h"
+#include "seed_device.h"
 #include "text_record.h"
 #include "prefsuf_common.h"
 
@@ -39,46 +38,7 @@ namespace {
 constexpr int GR_BLOCK = 256, GR_WAVES = GR_BLOCK / 64;
 constexpr uint8_t GR_PL_PLACED = 1;                                    // ALGA_PLACE_PLACED
 
-__device__ __forceinline__ unsigned long long gr_wave_min(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-// the item of position g < off[n]: the last i with off[i] <= g (it has a length: off[i + 1] > g)
-__device__ __forceinline__ uint32_t gr_item_of(const uint32_t *__restrict__ off, uint32_t n, uint32_t g) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t gr_base(const uint32_t *__restrict__ cols, uint64_t g) { return (cols[g >> 4] >> ((g & 15ull) << 1)) & 3u; }
-
-// the k-mer at column g of a column array (two words of padding behind the last column)
-__device__ __forceinline__ unsigned long long gr_col_kmer(const uint32_t *__restrict__ cols, uint32_t g, int k) {
-    const uint32_t w = g >> 4, sh = (g & 15u) << 1;
-    const unsigned long long lo = (unsigned long long) cols[w] | ((unsigned long long) cols[w + 1] << 32);
-    unsigned long long v = lo >> sh;
-    if (sh) v |= (unsigned long long) cols[w + 2] << (64 - sh);
-    return v & ((1ull << (2 * k)) - 1ull);
-}
-
-// the k-mer at base i of a row of nw words (i + k <= its length: nothing is read past word nw - 1)
-__device__ __forceinline__ unsigned long long gr_row_kmer(const uint32_t *__restrict__ row, int nw, int i, int k) {
-    const int w = i >> 4, sh = (i & 15) << 1;
-    const unsigned long long lo = (unsigned long long) row[w] | (w + 1 < nw ? (unsigned long long) row[w + 1] << 32 : 0ull);
-    unsigned long long v = lo >> sh;
-    if (sh && w + 2 < nw) v |= (unsigned long long) row[w + 2] << (64 - sh);
-    return v & ((1ull << (2 * k)) - 1ull);
-}
-
-__global__ void __launch_bounds__(GR_BLOCK) k_gr_check(GrReads r, GrTargets t, unsigned long long *__restrict__ counters) {
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_check(SeedReads r, GrTargets t, unsigned long long *__restrict__ counters) {
     unsigned long long mx = 0;
     uint32_t bad = 0;
     // every column array of the stage is sized from the caller's `columns`: it has to be the placement's
@@ -96,7 +56,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_check(GrReads r, GrTargets t, u
     }
 }
 
-__global__ void __launch_bounds__(GR_BLOCK) k_gr_candidates(GrReads r, const uint8_t *__restrict__ pl_state, int32_t min_anchor, uint32_t *__restrict__ flag) {
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_candidates(SeedReads r, const uint8_t *__restrict__ pl_state, int32_t min_anchor, uint32_t *__restrict__ flag) {
     for (uint64_t i = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; i <= r.R; i += (uint64_t) gridDim.x * GR_BLOCK)
         flag[i] = i < r.R && !(pl_state[i] & GR_PL_PLACED) && r.len[2 * i + 1] > min_anchor ? 1u : 0u;   // entry R: the place of the scan's total
 }
@@ -131,64 +91,39 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_ends(GrTargets t, GrEnds e, uin
     const uint64_t n_words = (e.columns + 15) >> 4;
     for (uint64_t w = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * GR_BLOCK) {
         const uint64_t g0 = w << 4;
-        uint32_t ee = gr_item_of(e.end_off, e.E, (uint32_t) g0), v = 0;
+        uint32_t ee = item_of(e.off, e.n, (uint32_t) g0), v = 0;
         for (int j = 0; j < 16; j++) {
             const uint64_t g = g0 + (uint64_t) j;
             if (g >= e.columns) break;
-            while ((uint64_t) e.end_off[ee + 1] <= g) ee++;                  // (g < columns = end_off[2T]: ends at an end that has a length)
-            const uint32_t tt = ee >> 1, q = (uint32_t) (g - e.end_off[ee]), W = (uint32_t) e.elen[ee];
+            while ((uint64_t) e.off[ee + 1] <= g) ee++;                  // (g < columns = end_off[2T]: ends at an end that has a length)
+            const uint32_t tt = ee >> 1, q = (uint32_t) (g - e.off[ee]), W = (uint32_t) e.len[ee];
             uint32_t b;
-            if (ee & 1u) b = gr_base(t.cols, (uint64_t) t.col_off[tt + 1] - W + q);            // the last W bases
-            else b = 3u - gr_base(t.cols, (uint64_t) t.col_off[tt] + (W - 1u - q));            // the first W, complemented and mirrored
+            if (ee & 1u) b = base_at(t.cols, (uint64_t) t.col_off[tt + 1] - W + q);            // the last W bases
+            else b = 3u - base_at(t.cols, (uint64_t) t.col_off[tt] + (W - 1u - q));            // the first W, complemented and mirrored
             v |= b << (2 * j);
         }
         ecols[w] = v;
     }
 }
 
-__global__ void __launch_bounds__(GR_BLOCK) k_gr_keys(GrEnds e, int32_t k, unsigned long long *__restrict__ keys, uint32_t *__restrict__ vals) {
-    for (uint64_t g = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; g < e.columns; g += (uint64_t) gridDim.x * GR_BLOCK) {
-        const uint32_t ee = gr_item_of(e.end_off, e.E, (uint32_t) g);
-        const uint64_t q = g - (uint64_t) e.end_off[ee];
-        keys[g] = q + (uint64_t) k <= (uint64_t) e.elen[ee] ? gr_col_kmer(e.cols, (uint32_t) g, k) : 1ull << (2 * k);   // above every k-mer, inside the 2k + 1 sorted bits
-        vals[g] = (uint32_t) g;
+// Geometry of a read of L bases on the ends: seed js at position q of end e puts v[js k] on E[q], so v[a], a = W_e - q + js k, is the first
+// base behind the end; the anchored part begins at column end_off[e] + W_e - a >= end_off[e]
+struct GrGeometry {
+    static constexpr int kMmShift = 33;              // the key: (mm << 33) | (first end column of the anchored part << 1) | strand
+    const GrEnds &en;
+    int k, L, min_anchor, strand;
+    __device__ __forceinline__ bool operator()(int js, uint32_t g, uint32_t &gp, int &n, unsigned long long &low) const {
+        const uint32_t ee = item_of(en.off, en.n, g);
+        const long long W = en.len[ee], q = (long long) g - (long long) en.off[ee];
+        const long long a = W - q + (long long) js * k;
+        if (a > W || a < (long long) min_anchor || a > (long long) L - 1) return false;
+        gp = g - (uint32_t) (js * k); n = (int) a;
+        low = ((unsigned long long) gp << 1) | (unsigned long long) strand;
+        return true;
     }
-}
+};
 
-// lower bound of x among the indexed keys and its occurrences, counted up to max_occ + 1
-__device__ __forceinline__ void gr_lookup(const GrIndex &x, unsigned long long kmer, uint32_t max_occ, uint32_t &lb, uint32_t &occ) {
-    const uint32_t b = (uint32_t) (kmer >> x.shift);
-    uint32_t lo = x.dir[b], hi = x.dir[b + 1];
-    const uint32_t end = hi;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (x.keys[mid] < kmer) lo = mid + 1; else hi = mid;
-    }
-    lb = lo;
-    uint32_t c = 0;
-    while (lo + c < end && c <= max_occ && x.keys[lo + c] == kmer) c++;
-    occ = c;
-}
-
-// Hamming distance between the first a bases of a row and the a columns from gp on; stops past max_mm.  Words 0 .. blocks_of(a) - 1 of the
-// row and up to one word more of the columns are read (gp + a <= the columns: inside the padding); the bases from a on are masked away
-__device__ __forceinline__ uint32_t gr_verify(const uint32_t *__restrict__ row, int a, const uint32_t *__restrict__ cols, uint32_t gp, uint32_t max_mm) {
-    const uint32_t *tw = cols + (gp >> 4);
-    const uint32_t sh = (gp & 15u) << 1;
-    const int nw = blocks_of(a);
-    uint32_t mm = 0, prev = tw[0];
-    for (int w = 0; w < nw; w++) {
-        const uint32_t next = tw[w + 1];
-        uint32_t x = row[w] ^ __funnelshift_r(prev, next, sh);
-        prev = next;
-        if (w == nw - 1 && (a & 15)) x &= (1u << ((a & 15) << 1)) - 1u;
-        mm += (uint32_t) __popc((x | (x >> 1)) & 0x55555555u);
-        if (mm > max_mm) break;
-    }
-    return mm;
-}
-
-__global__ void __launch_bounds__(GR_BLOCK) k_gr_place(GrReads rd, const uint32_t *__restrict__ cand, uint64_t n_cand, GrEnds en, GrIndex x, int32_t k, uint32_t max_mm,
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_place(SeedReads rd, const uint32_t *__restrict__ cand, uint64_t n_cand, GrEnds en, SeedIndex x, int32_t k, uint32_t max_mm,
                                                        uint32_t max_occ, int32_t min_anchor, GrOut o, unsigned long long *__restrict__ scratch, uint32_t scratch_words,
                                                        unsigned long long *__restrict__ counters) {
     const int lane = threadIdx.x & 63;
@@ -198,65 +133,21 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_place(GrReads rd, const uint32_
     for (uint64_t ci0 = wave; ci0 < n_cand; ci0 += n_waves) {
         const uint64_t r = cand[ci0];
         const int32_t L = rd.len[2 * r + 1];                 // >= min_anchor + 1 >= k + 1
-        unsigned long long best = ~0ull;                     // (mm << 33) | (first end column of the anchored part << 1) | strand, of this lane's placements
-        uint32_t lane_mm = 0xFFFFFFFFu, lane_cnt = 0;        // the smallest mm among them and how many have it
-        const int S = (L - 1) / k, nw = blocks_of(L);        // the seeds with (j + 1) k <= L - 1: no other lies in an anchored part
+        unsigned long long best = ~0ull;                     // of this lane's placements
+        MinMmTally tally;
         for (int strand = 0; strand < 2; strand++) {
-            const uint32_t *row = rd.rows + (2 * r + (strand == 0 ? 1u : 0u)) * (size_t) rd.stride;
-            for (int c0 = 0; c0 < S; c0 += 64) {
-                const int j = c0 + lane;
-                const bool act = j < S;
-                uint32_t lb = 0, occ = 0;
-                if (act) gr_lookup(x, gr_row_kmer(row, nw, j * k, k), max_occ, lb, occ);
-                const bool usable = act && occ >= 1u && occ <= max_occ;
-                const unsigned long long umask = __ballot(usable);
-                n_seeds += (unsigned long long) __popcll(__ballot(act));
-                n_over += (unsigned long long) __popcll(__ballot(act && occ > max_occ));
-                if (S > 64) {                                // later chunks ask for this one's usable seeds
-                    if (lane == 0) __hip_atomic_store(&ub[c0 >> 6], umask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __threadfence();
-                }
-                const uint32_t mine = usable ? occ : 0u;
-                uint32_t inc = mine;
-                for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t) __shfl_up((int) inc, d); if (lane >= d) inc += up; }
-                const uint32_t C = (uint32_t) __shfl((int) inc, 63), exc = inc - mine;
-                for (uint32_t p0 = 0; p0 < C; p0 += 64) {
-                    const bool cact = p0 + (uint32_t) lane < C;
-                    const uint32_t ci = cact ? p0 + (uint32_t) lane : C - 1u;
-                    int sl = 0;                              // the seed lane of candidate ci: the first with inc > ci
-                    for (int st = 32; st > 0; st >>= 1) if ((uint32_t) __shfl((int) inc, sl + st - 1) <= ci) sl += st;
-                    const uint32_t s_lb = (uint32_t) __shfl((int) lb, sl), s_exc = (uint32_t) __shfl((int) exc, sl);
-                    if (!cact) continue;
-                    const int js = c0 + sl;
-                    const uint32_t g = x.vals[s_lb + (ci - s_exc)];            // an indexed position: q + k <= W_e
-                    const uint32_t ee = gr_item_of(en.end_off, en.E, g);
-                    const long long W = en.elen[ee], q = (long long) g - (long long) en.end_off[ee];
-                    const long long a = W - q + (long long) js * k;            // v[js k] lies on E[q]; v[a] is the first base behind the end
-                    if (a > W || a < (long long) min_anchor || a > (long long) L - 1) continue;
-                    const uint32_t gp = g - (uint32_t) (js * k);               // = end_off[e] + W - a >= end_off[e]
-                    const uint32_t mm = gr_verify(row, (int) a, en.cols, gp, max_mm);
-                    if (mm > max_mm) continue;
-                    bool dup = false;                        // an earlier usable seed finds this placement too (it lies in the anchored part: j2 < js)
-                    for (int j2 = 0; j2 < js && !dup; j2++) {
-                        const unsigned long long m = j2 >= c0 ? umask : __hip_atomic_load(&ub[j2 >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if ((m >> (j2 & 63)) & 1ull) dup = gr_row_kmer(row, nw, j2 * k, k) == gr_col_kmer(en.cols, gp + (uint32_t) (j2 * k), k);
-                    }
-                    if (dup) continue;
-                    const unsigned long long key = ((unsigned long long) mm << 33) | ((unsigned long long) gp << 1) | (unsigned long long) strand;
-                    best = key < best ? key : best;
-                    if (mm < lane_mm) { lane_mm = mm; lane_cnt = 1u; }
-                    else if (mm == lane_mm) lane_cnt++;
-                }
-            }
+            const RowQuery q{rd.rows + (2 * r + (strand == 0 ? 1u : 0u)) * (size_t) rd.stride, blocks_of(L), k};
+            // the seeds with (j + 1) k <= L - 1: no other lies in an anchored part
+            seed_and_verify(x, en.cols, k, max_mm, max_occ, (L - 1) / k, q, GrGeometry{en, k, L, min_anchor, strand}, ub, best, tally, n_seeds, n_over);
         }
-        const unsigned long long win = gr_wave_min(best);
+        const unsigned long long win = wave_min_u64(best);
         int32_t e_out = -1, h_out = 0;
         uint8_t mm8 = 0, hits8 = 0, st8 = 0;
         if (win != ~0ull) {
             const uint32_t bmm = (uint32_t) (win >> 33), gp = (uint32_t) (win >> 1);
-            const unsigned long long hits = wave_sum(lane_mm == bmm ? (unsigned long long) lane_cnt : 0ull);
-            const uint32_t ee = gr_item_of(en.end_off, en.E, gp);
-            const int32_t a = (int32_t) (en.end_off[ee] + (uint32_t) en.elen[ee] - gp);
+            const unsigned long long hits = wave_sum(tally.mm == bmm ? (unsigned long long) tally.cnt : 0ull);
+            const uint32_t ee = item_of(en.off, en.n, gp);
+            const int32_t a = (int32_t) (en.off[ee] + (uint32_t) en.len[ee] - gp);
             e_out = (int32_t) ee; h_out = L - a; mm8 = (uint8_t) bmm; hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
             st8 = (uint8_t) (GR_ST_OVERHANGS | (hits == 1ull ? GR_ST_VOTES : 0) | ((win & 1ull) ? GR_ST_MINUS : 0));
             n_hang++; n_vote += hits == 1ull; n_sat += hits > 255ull;
@@ -273,7 +164,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_place(GrReads rd, const uint32_
 }
 
 // (a voting read has 1 <= h <= L - min_anchor and its end e < 2T from k_gr_place: base L - h + i < L lies in its row, the count entry in end e's slice)
-__global__ void __launch_bounds__(GR_BLOCK) k_gr_vote(GrReads rd, const uint32_t *__restrict__ cand, uint64_t n_cand, GrOut o, int32_t max_grow, uint32_t *__restrict__ count,
+__global__ void __launch_bounds__(GR_BLOCK) k_gr_vote(SeedReads rd, const uint32_t *__restrict__ cand, uint64_t n_cand, GrOut o, int32_t max_grow, uint32_t *__restrict__ count,
                                                       uint32_t *__restrict__ voters) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t) blockIdx.x * GR_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * GR_WAVES;
@@ -285,7 +176,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_vote(GrReads rd, const uint32_t
         const uint64_t e = (uint64_t) o.end[r];
         const uint32_t *row = rd.rows + (2 * r + ((st & GR_ST_MINUS) ? 0u : 1u)) * (size_t) rd.stride;
         if (lane == 0) atomicAdd(&voters[e], 1u);
-        for (int32_t i = lane; i < n; i += 64) atomicAdd(&count[(e * (uint64_t) max_grow + (uint64_t) i) * 4ull + gr_base(row, (uint64_t) (L - h + i))], 1u);
+        for (int32_t i = lane; i < n; i += 64) atomicAdd(&count[(e * (uint64_t) max_grow + (uint64_t) i) * 4ull + base_at(row, (uint64_t) (L - h + i))], 1u);
     }
 }
 
@@ -355,7 +246,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_build(GrTargets t, const uint32
         const uint64_t g0 = w << 4;
         uint32_t v = 0;
         if (g0 < new_columns) {
-            uint32_t tt = gr_item_of(new_off, t.T, (uint32_t) g0);
+            uint32_t tt = item_of(new_off, t.T, (uint32_t) g0);
             for (int j = 0; j < 16; j++) {
                 const uint64_t gg = g0 + (uint64_t) j;
                 if (gg >= new_columns) break;
@@ -363,7 +254,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_build(GrTargets t, const uint32
                 const uint64_t q = gg - new_off[tt], l = left[tt], n = (uint64_t) t.col_off[tt + 1] - t.col_off[tt];
                 uint32_t b;
                 if (q < l) b = 3u - g[(2ull * tt) * (uint64_t) max_grow + (l - 1 - q)];
-                else if (q < l + n) b = gr_base(t.cols, (uint64_t) t.col_off[tt] + (q - l));
+                else if (q < l + n) b = base_at(t.cols, (uint64_t) t.col_off[tt] + (q - l));
                 else b = g[(2ull * tt + 1) * (uint64_t) max_grow + (q - l - n)];
                 v |= b << (2 * j);
             }
@@ -400,11 +291,11 @@ inline unsigned gr_grid(uint64_t items, uint64_t cap = 8192) {
 
 }  // namespace
 
-void launch_gr_check(const GrReads &r, const GrTargets &t, unsigned long long *counters, hipStream_t s) {
+void launch_gr_check(const SeedReads &r, const GrTargets &t, unsigned long long *counters, hipStream_t s) {
     hipLaunchKernelGGL(k_gr_check, dim3(gr_grid(2 * r.R, 4096)), dim3(GR_BLOCK), 0, s, r, t, counters);
 }
 
-void launch_gr_candidates(const GrReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, hipStream_t s) {
+void launch_gr_candidates(const SeedReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, hipStream_t s) {
     hipLaunchKernelGGL(k_gr_candidates, dim3(gr_grid(r.R + 1)), dim3(GR_BLOCK), 0, s, r, pl_state, min_anchor, flag);
 }
 
@@ -420,27 +311,14 @@ void launch_gr_ends(const GrTargets &t, const GrEnds &e, uint32_t *ecols, hipStr
     if (e.columns) hipLaunchKernelGGL(k_gr_ends, dim3(gr_grid((e.columns + 15) >> 4)), dim3(GR_BLOCK), 0, s, t, e, ecols);
 }
 
-void launch_gr_keys(const GrEnds &e, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s) {
-    if (e.columns) hipLaunchKernelGGL(k_gr_keys, dim3(gr_grid(e.columns, 1u << 16)), dim3(GR_BLOCK), 0, s, e, k, keys, vals);
-}
-
-int gr_place_blocks(uint64_t n_cand, int n_cu) {
-    return (int) std::max<uint64_t>(1, std::min<uint64_t>((n_cand + GR_WAVES - 1) / GR_WAVES, (uint64_t) std::max(1, n_cu) * 8u));
-}
-
-size_t gr_place_scratch_words(int blocks, int64_t max_read_len, int32_t k) {
-    const size_t per_wave = (size_t) std::max<int64_t>(1, (max_read_len / k + 63) / 64);
-    return (size_t) blocks * GR_WAVES * per_wave;
-}
-
-void launch_gr_place(const GrReads &r, const uint32_t *cand, uint64_t n_cand, const GrEnds &e, const GrIndex &x, int32_t k, int32_t max_mm, int32_t max_occ,
+void launch_gr_place(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ,
                      int32_t min_anchor, const GrOut &o, unsigned long long *scratch, uint32_t scratch_words_per_wave, int blocks, unsigned long long *counters,
                      hipStream_t s) {
     if (n_cand) hipLaunchKernelGGL(k_gr_place, dim3((unsigned) blocks), dim3(GR_BLOCK), 0, s, r, cand, n_cand, e, x, k, (uint32_t) max_mm, (uint32_t) max_occ, min_anchor, o,
                                    scratch, scratch_words_per_wave, counters);
 }
 
-void launch_gr_vote(const GrReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, hipStream_t s) {
+void launch_gr_vote(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, hipStream_t s) {
     if (n_cand) hipLaunchKernelGGL(k_gr_vote, dim3(gr_grid(n_cand * 64)), dim3(GR_BLOCK), 0, s, r, cand, n_cand, o, max_grow, count, voters);
 }
 

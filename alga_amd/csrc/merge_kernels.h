@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seed_index.h"
+
 namespace alga {
 
 // counters[] (unsigned long long): the refusal flags and the sizes, then what the kernels count
@@ -21,21 +23,10 @@ struct MgTargets {
     const int32_t *len;               // T
     uint32_t T;
 };
-// the 2T end sequences in a column space of their own: end x is the columns end_off[x] .. end_off[x] + elen[x], end_off[x] a multiple of 16
-struct MgEnds {
-    const uint32_t *end_off;          // 2T + 1
-    const int32_t *elen;              // 2T: W_x
-    uint32_t E;                       // 2T
-    uint64_t columns;                 // end_off[2T]
-    const uint32_t *cols;             // E_x: the contig end at the right; two words of padding behind the last column
+// the 2T end sequences in a column space of their own, the space their index is built over (alga_seed_index): end x is the columns
+// off[x] .. off[x] + len[x] (len[x] = W_x), off[x] a multiple of 16; cols holds E_x, the contig end at the right; n = 2T
+struct MgEnds : SeedSpace {
     const uint32_t *pcols;            // P_x = the reverse complement of E_x, at the same columns
-};
-struct MgIndex {
-    const unsigned long long *keys;   // sorted; the first n are k-mers
-    const uint32_t *vals;             // their end columns
-    const uint32_t *dir;
-    int shift;
-    uint32_t n;
 };
 struct MgEndOut {
     int32_t *partner, *olen;
@@ -62,11 +53,8 @@ void launch_mg_check(const MgTargets &t, unsigned long long *counters, hipStream
 void launch_mg_end_lens(const MgTargets &t, int32_t max_overlap, int32_t min_overlap, int32_t k, int32_t *elen, uint32_t *epad, unsigned long long *counters, hipStream_t s);
 // E_x and P_x, one thread per word: the left ends complemented and mirrored
 void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32_t *pcols, hipStream_t s);
-// (k-mer, end column) of every end column; a column that is no indexed position gets a key above every k-mer
-void launch_mg_keys(const MgEnds &e, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s);
-// one wave per end
-int  mg_overlap_blocks(uint64_t n_ends, int n_cu);
-void launch_mg_overlap(const MgEnds &e, const MgIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
+// one wave per end (blocks: seed_blocks(2T))
+void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
                        unsigned long long *counters, hipStream_t s);
 // one thread per end: join[x] = the end x is joined with, MG_NONE without; JOINED into the end's state
 void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, hipStream_t s);

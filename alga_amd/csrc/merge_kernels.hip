@@ -8,12 +8,9 @@
 //   k_mg_check        a negative length -> the refusal flag; the column sum
 //   k_mg_end_lens     W_x of every end, W_x rounded up to a word, the indexed positions; (scan): end_off
 //   k_mg_ends         E_x and P_x, one thread per word
-//   k_mg_keys         (k-mer, end column) of every end column; a column that is no indexed position gets a key above every k-mer
-//   k_mg_overlap      one wave per end.  The lanes take the at most 64 seeds of P_x: directory read, bisection, a scan of at most max_occ + 1
-//                     equal keys; the (seed, occurrence) candidates go to the lanes in passes of 64.  A hit of seed j at position q of E_y gives
-//                     o = W_y - q + j k.  A lane verifies the o bases only: XOR and popcount over funnel-shifted words, the last partial word
-//                     masked, nothing read past the two words of padding.  A candidate found through seed j counts only if no usable seed
-//                     j' < j matches there (the usable seeds are one 64-bit ballot), so every (y, o) counts once.  The minimum key
+//   (the index over the end columns: alga_seed_index, seed_index.hip)
+//   k_mg_overlap      one wave per end: seed_and_verify (seed_device.h) over the at most 64 seeds of P_x, one chunk.  A hit of seed j at position q
+//                     of E_y gives o = W_y - q + j k; the o bases only are verified, so every (y, o) counts once.  The minimum key
 //                     (mm, y, o descending) and the number of (y, o) are reduced across the wave.
 //   k_mg_joins        one thread per end: joined where both ends have one overlap, each other, at one o
 //   k_mg_cycle_init / _jump / _drop   pointer jumping over the 2T states (contig, entry end) with the smallest contig id carried along: a state
@@ -25,13 +22,14 @@
 //   k_mg_build        every output word gathered by one lane: a column finds its member by bisection over the starts, an overlapped column is
 //                     the earlier contig's; minus-oriented members complemented and mirrored
 //   k_mg_fasta_sizes / k_mg_fasta_write   one record per merged contig, one wave per record
-// No LDS.  Block 256 and the grid caps are picked, not tuned; k_mg_overlap runs 8 blocks per CU like k_gr_place.
+// No LDS.  Block 256 and the grid caps are picked, not tuned.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "merge_kernels.h"
+#include "seed_device.h"
 #include "text_record.h"
 #include "prefsuf_common.h"
 
@@ -40,36 +38,6 @@ namespace alga {
 namespace {
 
 constexpr int MG_BLOCK = 256, MG_WAVES = MG_BLOCK / 64;
-
-__device__ __forceinline__ unsigned long long mg_wave_min(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-// the item of position g < off[n]: the last i with off[i] <= g (it has a length: off[i + 1] > g)
-__device__ __forceinline__ uint32_t mg_item_of(const uint32_t *__restrict__ off, uint32_t n, uint32_t g) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t mg_base(const uint32_t *__restrict__ words, uint64_t g) { return (words[g >> 4] >> ((g & 15ull) << 1)) & 3u; }
-
-// the k-mer at column g of a column array (two words of padding behind the last column)
-__device__ __forceinline__ unsigned long long mg_col_kmer(const uint32_t *__restrict__ cols, uint32_t g, int k) {
-    const uint32_t w = g >> 4, sh = (g & 15u) << 1;
-    const unsigned long long lo = (unsigned long long) cols[w] | ((unsigned long long) cols[w + 1] << 32);
-    unsigned long long v = lo >> sh;
-    if (sh) v |= (unsigned long long) cols[w + 2] << (64 - sh);
-    return v & ((1ull << (2 * k)) - 1ull);
-}
 
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_check(MgTargets t, unsigned long long *__restrict__ counters) {
     unsigned long long sum = 0, bad = 0;
@@ -112,121 +80,74 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_end_lens(MgTargets t, int32_t m
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_ends(MgTargets t, MgEnds e, uint32_t *__restrict__ ecols, uint32_t *__restrict__ pcols) {
     const uint64_t n_words = e.columns >> 4;
     for (uint64_t w = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * MG_BLOCK) {
-        const uint32_t g0 = (uint32_t) (w << 4), x = mg_item_of(e.end_off, e.E, g0), tt = x >> 1, q0 = g0 - e.end_off[x], W = (uint32_t) e.elen[x];
+        const uint32_t g0 = (uint32_t) (w << 4), x = item_of(e.off, e.n, g0), tt = x >> 1, q0 = g0 - e.off[x], W = (uint32_t) e.len[x];
         const uint64_t b0 = t.begin[tt], n = (uint64_t) t.len[tt];
         uint32_t ve = 0, vp = 0;
         for (uint32_t j = 0; j < 16 && q0 + j < W; j++) {
             const uint32_t q = q0 + j;
             uint32_t be, bp;
-            if (x & 1u) { be = mg_base(t.words, b0 + n - W + q); bp = 3u - mg_base(t.words, b0 + n - 1u - q); }          // the last W bases
-            else { be = 3u - mg_base(t.words, b0 + (W - 1u - q)); bp = mg_base(t.words, b0 + q); }                       // the first W, complemented and mirrored
+            if (x & 1u) { be = base_at(t.words, b0 + n - W + q); bp = 3u - base_at(t.words, b0 + n - 1u - q); }          // the last W bases
+            else { be = 3u - base_at(t.words, b0 + (W - 1u - q)); bp = base_at(t.words, b0 + q); }                       // the first W, complemented and mirrored
             ve |= be << (2 * j); vp |= bp << (2 * j);
         }
         ecols[w] = ve; pcols[w] = vp;
     }
 }
 
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_keys(MgEnds e, int32_t k, unsigned long long *__restrict__ keys, uint32_t *__restrict__ vals) {
-    for (uint64_t g = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; g < e.columns; g += (uint64_t) gridDim.x * MG_BLOCK) {
-        const uint32_t x = mg_item_of(e.end_off, e.E, (uint32_t) g);
-        const uint64_t q = g - (uint64_t) e.end_off[x];
-        keys[g] = q + (uint64_t) k <= (uint64_t) e.elen[x] ? mg_col_kmer(e.cols, (uint32_t) g, k) : 1ull << (2 * k);   // above every k-mer, inside the 2k + 1 sorted bits
-        vals[g] = (uint32_t) g;
+// Query: P_x, which begins a word of pcols at column x0
+struct MgQuery {
+    const uint32_t *pcols, *row;
+    uint32_t x0;
+    int k;
+    __device__ __forceinline__ unsigned long long kmer(int j) const { return col_kmer(pcols, x0 + (uint32_t) (j * k), k); }
+};
+
+// Geometry of P_x on the ends: seed js at position q of E_y puts P_x[js k] on E_y[q], and the overlap of o = W_y - q + js k bases ends with
+// E_y: it begins at column end_off[y] + W_y - o >= end_off[y]
+struct MgGeometry {
+    static constexpr int kMmShift = 45;              // the key: (mm, y, o descending); o <= 4096
+    const MgEnds &en;
+    uint32_t x;
+    int k, W, min_overlap;
+    __device__ __forceinline__ bool operator()(int js, uint32_t g, uint32_t &gp, int &n, unsigned long long &low) const {
+        const uint32_t y = item_of(en.off, en.n, g);
+        if ((y >> 1) == (x >> 1)) return false;              // the same target: no overlap here
+        const int32_t Wy = en.len[y], q = (int32_t) (g - en.off[y]);
+        const int32_t o = Wy - q + js * k;
+        if (o < min_overlap || o > W || o > Wy) return false;
+        gp = g - (uint32_t) (js * k); n = o;
+        low = ((unsigned long long) y << 13) | (unsigned long long) ((uint32_t) MG_MAX_OVERLAP - (uint32_t) o);
+        return true;
     }
-}
+};
 
-// lower bound of x among the indexed keys and its occurrences, counted up to max_occ + 1
-__device__ __forceinline__ void mg_lookup(const MgIndex &x, unsigned long long kmer, uint32_t max_occ, uint32_t &lb, uint32_t &occ) {
-    const uint32_t b = (uint32_t) (kmer >> x.shift);
-    uint32_t lo = x.dir[b], hi = x.dir[b + 1];
-    const uint32_t end = hi;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (x.keys[mid] < kmer) lo = mid + 1; else hi = mid;
-    }
-    lb = lo;
-    uint32_t c = 0;
-    while (lo + c < end && c <= max_occ && x.keys[lo + c] == kmer) c++;
-    occ = c;
-}
+// Tally: every (y, o) of the lane
+struct MgTally {
+    uint32_t cnt = 0;
+    __device__ __forceinline__ void add(uint32_t) { cnt++; }
+};
 
-// Hamming distance between the first o bases of a word-aligned row and the o columns from gp on; stops past max_mm.  Words 0 .. blocks_of(o) - 1
-// of the row and up to one word more of the columns are read (gp + o <= the columns: inside the padding); the bases from o on are masked away
-__device__ __forceinline__ uint32_t mg_verify(const uint32_t *__restrict__ row, int o, const uint32_t *__restrict__ cols, uint32_t gp, uint32_t max_mm) {
-    const uint32_t *tw = cols + (gp >> 4);
-    const uint32_t sh = (gp & 15u) << 1;
-    const int nw = blocks_of(o);
-    uint32_t mm = 0, prev = tw[0];
-    for (int w = 0; w < nw; w++) {
-        const uint32_t next = tw[w + 1];
-        uint32_t x = row[w] ^ __funnelshift_r(prev, next, sh);
-        prev = next;
-        if (w == nw - 1 && (o & 15)) x &= (1u << ((o & 15) << 1)) - 1u;
-        mm += (uint32_t) __popc((x | (x >> 1)) & 0x55555555u);
-        if (mm > max_mm) break;
-    }
-    return mm;
-}
-
-// the key of an overlap: (mm, y, o descending); o <= 4096
-__device__ __forceinline__ unsigned long long mg_key(uint32_t mm, uint32_t y, uint32_t o) {
-    return ((unsigned long long) mm << 45) | ((unsigned long long) y << 13) | (unsigned long long) ((uint32_t) MG_MAX_OVERLAP - o);
-}
-
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_overlap(MgEnds en, MgIndex ix, int32_t k, uint32_t max_mm, uint32_t max_occ, int32_t min_overlap, MgEndOut out,
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_overlap(MgEnds en, SeedIndex ix, int32_t k, uint32_t max_mm, uint32_t max_occ, int32_t min_overlap, MgEndOut out,
                                                          unsigned long long *__restrict__ counters) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t) blockIdx.x * MG_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * MG_WAVES;
     unsigned long long n_with = 0, n_amb = 0, n_sat = 0, n_seeds = 0, n_over = 0;            // wave-uniform
-    for (uint64_t x = wave; x < en.E; x += n_waves) {
-        const int32_t W = en.elen[x];
+    for (uint64_t x = wave; x < en.n; x += n_waves) {
+        const int32_t W = en.len[x];
         unsigned long long best = ~0ull;
-        uint32_t lane_cnt = 0;
+        MgTally tally;
         if (W >= min_overlap) {                              // (wave-uniform) a shorter end has no overlap: o <= W
-            const uint32_t x0 = en.end_off[x];
-            const uint32_t *row = en.pcols + (x0 >> 4);      // P_x begins a word
-            const int S = W / k;                             // the seeds with (j + 1) k <= W: at most 64
-            const bool act = lane < S;
-            uint32_t lb = 0, occ = 0;
-            if (act) mg_lookup(ix, mg_col_kmer(en.pcols, x0 + (uint32_t) (lane * k), k), max_occ, lb, occ);
-            const bool usable = act && occ >= 1u && occ <= max_occ;
-            const unsigned long long umask = __ballot(usable);
-            n_seeds += (unsigned long long) S;
-            n_over += (unsigned long long) __popcll(__ballot(act && occ > max_occ));
-            const uint32_t mine = usable ? occ : 0u;
-            uint32_t inc = mine;
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t) __shfl_up((int) inc, d); if (lane >= d) inc += up; }
-            const uint32_t C = (uint32_t) __shfl((int) inc, 63), exc = inc - mine;
-            for (uint32_t p0 = 0; p0 < C; p0 += 64) {
-                const bool cact = p0 + (uint32_t) lane < C;
-                const uint32_t ci = cact ? p0 + (uint32_t) lane : C - 1u;
-                int sl = 0;                                  // the seed lane of candidate ci: the first with inc > ci
-                for (int st = 32; st > 0; st >>= 1) if ((uint32_t) __shfl((int) inc, sl + st - 1) <= ci) sl += st;
-                const uint32_t s_lb = (uint32_t) __shfl((int) lb, sl), s_exc = (uint32_t) __shfl((int) exc, sl);
-                if (!cact) continue;
-                const uint32_t g = ix.vals[s_lb + (ci - s_exc)];                // an indexed position: q + k <= W_y
-                const uint32_t y = mg_item_of(en.end_off, en.E, g);
-                if ((y >> 1) == (uint32_t) (x >> 1)) continue;                   // the same target: no overlap here
-                const int32_t Wy = en.elen[y], q = (int32_t) (g - en.end_off[y]);
-                const int32_t o = Wy - q + sl * k;                               // P_x[sl k] lies on E_y[q]; the overlap ends with E_y
-                if (o < min_overlap || o > W || o > Wy) continue;
-                const uint32_t gp = g - (uint32_t) (sl * k);                     // = end_off[y] + W_y - o >= end_off[y]
-                const uint32_t mm = mg_verify(row, o, en.cols, gp, max_mm);
-                if (mm > max_mm) continue;
-                bool dup = false;                            // an earlier usable seed finds this overlap too (it lies inside it: j2 < sl)
-                for (int j2 = 0; j2 < sl && !dup; j2++)
-                    if ((umask >> j2) & 1ull) dup = mg_col_kmer(en.pcols, x0 + (uint32_t) (j2 * k), k) == mg_col_kmer(en.cols, gp + (uint32_t) (j2 * k), k);
-                if (dup) continue;
-                const unsigned long long key = mg_key(mm, y, (uint32_t) o);
-                best = key < best ? key : best;
-                lane_cnt++;
-            }
+            const uint32_t x0 = en.off[x];
+            const int S = W / k;                             // the seeds with (j + 1) k <= W
+            __builtin_assume(S >= 1 && S <= 64);             // (k <= min_overlap <= W <= max_overlap <= 64 k: one chunk, the scratch is never touched)
+            seed_and_verify(ix, en.cols, k, max_mm, max_occ, S, MgQuery{en.pcols, en.pcols + (x0 >> 4), x0, k}, MgGeometry{en, (uint32_t) x, k, W, min_overlap}, nullptr,
+                            best, tally, n_seeds, n_over);
         }
-        const unsigned long long win = mg_wave_min(best);
+        const unsigned long long win = wave_min_u64(best);
         int32_t y_out = -1, o_out = 0;
         uint8_t mm8 = 0, hits8 = 0, st8 = 0;
         if (win != ~0ull) {
-            const unsigned long long hits = wave_sum((unsigned long long) lane_cnt);
+            const unsigned long long hits = wave_sum((unsigned long long) tally.cnt);
             y_out = (int32_t) (uint32_t) (win >> 13); o_out = MG_MAX_OVERLAP - (int32_t) (win & 8191ull); mm8 = (uint8_t) (win >> 45);
             hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
             st8 = (uint8_t) (MG_E_HAS_OVERLAP | (hits > 1ull ? MG_E_AMBIGUOUS : 0));
@@ -377,7 +298,7 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_build(MgTargets t, MgLayout o, 
         const uint64_t g0 = w << 4;
         uint32_t v = 0;
         if (g0 < columns) {
-            uint32_t j = mg_item_of(col_off, n_merged, (uint32_t) g0);
+            uint32_t j = item_of(col_off, n_merged, (uint32_t) g0);
             for (int b = 0; b < 16; b++) {
                 const uint64_t gg = g0 + (uint64_t) b;
                 if (gg >= columns) break;
@@ -395,7 +316,7 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_build(MgTargets t, MgLayout o, 
                     if (p < o.start[cp] + (uint32_t) t.len[cp]) c = cp;
                 }
                 const uint32_t q = p - o.start[c], n = (uint32_t) t.len[c];
-                const uint32_t code = o.orient[c] ? 3u - mg_base(t.words, t.begin[c] + (n - 1u - q)) : mg_base(t.words, t.begin[c] + q);
+                const uint32_t code = o.orient[c] ? 3u - base_at(t.words, t.begin[c] + (n - 1u - q)) : base_at(t.words, t.begin[c] + q);
                 v |= code << (2 * b);
             }
         }
@@ -443,17 +364,9 @@ void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32
     if (e.columns) hipLaunchKernelGGL(k_mg_ends, dim3(mg_grid(e.columns >> 4)), dim3(MG_BLOCK), 0, s, t, e, ecols, pcols);
 }
 
-void launch_mg_keys(const MgEnds &e, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s) {
-    if (e.columns) hipLaunchKernelGGL(k_mg_keys, dim3(mg_grid(e.columns, 1u << 16)), dim3(MG_BLOCK), 0, s, e, k, keys, vals);
-}
-
-int mg_overlap_blocks(uint64_t n_ends, int n_cu) {
-    return (int) std::max<uint64_t>(1, std::min<uint64_t>((n_ends + MG_WAVES - 1) / MG_WAVES, (uint64_t) std::max(1, n_cu) * 8u));
-}
-
-void launch_mg_overlap(const MgEnds &e, const MgIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
+void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
                        unsigned long long *counters, hipStream_t s) {
-    if (e.E) hipLaunchKernelGGL(k_mg_overlap, dim3((unsigned) blocks), dim3(MG_BLOCK), 0, s, e, x, k, (uint32_t) max_mm, (uint32_t) max_occ, min_overlap, o, counters);
+    if (e.n) hipLaunchKernelGGL(k_mg_overlap, dim3((unsigned) blocks), dim3(MG_BLOCK), 0, s, e, x, k, (uint32_t) max_mm, (uint32_t) max_occ, min_overlap, o, counters);
 }
 
 void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, hipStream_t s) {

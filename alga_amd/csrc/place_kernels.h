@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seed_index.h"
+
 namespace alga {
 
 // counters[] (unsigned long long): the refusal flags and what the checks measure, then what the kernels count
 enum { PL_BAD_TWIN = 0, PL_BAD_PAIR, PL_BAD_LEN, PL_COLUMNS, PL_INDEX_POS, PL_MAX_READ_LEN, PL_DISTINCT, PL_PLACED, PL_UNIQUE, PL_SATURATED, PL_SEEDS,
        PL_SEEDS_OVER, PL_PAIRS, PL_PROPER, PL_IMPROPER, PL_SPLIT, PL_NOT_UNIQUE, PL_INSERT_SUM, PL_COUNTERS };
-constexpr int PL_DIR_BITS_MAX = 26;
 
 // pair_off (may be null): values <= 2, equal on a node and its twin, the mate in range and pointing back (*bad_pair = 1 otherwise);
 // counters[PL_MAX_READ_LEN] = the longest node
@@ -20,52 +21,25 @@ void launch_pl_target_check(const int32_t *tlen, uint64_t T, int32_t k, unsigned
 void launch_pl_final_targets(const unsigned long long *word_off, const uint8_t *verdict, const int32_t *order, const int32_t *begin, const int32_t *len, uint64_t n,
                              unsigned long long *tbegin, int32_t *tlen, hipStream_t s);
 
-// the targets in column space and their index
-struct PlTargets {
-    const uint32_t *col_off;          // T + 1
-    const int32_t *tlen;
-    uint32_t T;
-    uint64_t columns;                 // col_off[T]
-    const uint32_t *cols;             // column g in word g >> 4; two zero words behind the last
-};
+// the targets in column space, the space their index is built over (alga_seed_index): off = col_off (T + 1), len = the target lengths, n = T
+typedef SeedSpace PlTargets;
 // cols: the ragged targets repacked (the buffer is zeroed by the caller)
 void launch_pl_gather(const uint32_t *words, const unsigned long long *begin, const PlTargets &t, uint32_t *cols, hipStream_t s);
-// keys[g] = the k-mer at column g where (t, q) is indexed, 2^(2k) elsewhere (above every k-mer: sorted on 2k + 1 bits, the indexed
-// positions are the head of the sorted keys); vals[g] = g
-void launch_pl_keys(const PlTargets &t, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s);
-// dir[b] = the first of the n sorted keys with (key >> shift) >= b, b = 0 .. 2^bits; counters[PL_DISTINCT] += distinct keys
-void launch_pl_dir(const unsigned long long *keys, uint64_t n, int shift, int bits, uint32_t *dir, unsigned long long *counters, hipStream_t s);
 
-struct PlReads {
-    const uint32_t *rows;
-    int32_t stride;
-    const int32_t *len;
-    uint64_t R;
-};
-struct PlIndex {
-    const unsigned long long *keys;   // sorted; the first n are k-mers
-    const uint32_t *vals;             // their columns
-    const uint32_t *dir;
-    int32_t shift;                    // bucket = k-mer >> shift
-    uint32_t n;
-};
 struct PlOut {
     int32_t *target, *pos;
     uint8_t *mm, *hits, *state;
 };
-int  pl_place_blocks(uint64_t R, int n_cu);
-// words of the per-wave scratch (usable-seed masks of a read with more than 64 seeds): blocks * waves a block * ceil(max seeds / 64)
-size_t pl_place_scratch_words(int blocks, int64_t max_read_len, int32_t k);
-// the placement itself: one wave per read, both strands
-void launch_pl_place(const PlReads &r, const PlTargets &t, const PlIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, const PlOut &o, unsigned long long *scratch,
+// the placement itself: one wave per read, both strands (blocks: seed_blocks(R), the scratch: seed_scratch_words)
+void launch_pl_place(const SeedReads &r, const PlTargets &t, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, const PlOut &o, unsigned long long *scratch,
                      uint32_t scratch_words_per_wave, int blocks, unsigned long long *counters, hipStream_t s);
 
 // +1 / -1 of every counting read into diff[] (columns + 1 entries, zeroed), the per-target sums into tstat[4][T] (reads, bases, mismatches, uncovered)
-void launch_pl_depth_add(const PlReads &r, const PlTargets &t, const PlOut &o, int multi, uint32_t *diff, unsigned long long *tstat, hipStream_t s);
+void launch_pl_depth_add(const SeedReads &r, const PlTargets &t, const PlOut &o, int multi, uint32_t *diff, unsigned long long *tstat, hipStream_t s);
 // tstat[3][t] += columns of t with cover 0
 void launch_pl_uncovered(const PlTargets &t, const uint32_t *cover, unsigned long long *tstat, hipStream_t s);
 // the pairs: counters[PL_PAIRS ..], hist[max_insert + 1] (zeroed)
-void launch_pl_pairs(const PlReads &r, const uint8_t *pair_off, const PlOut &o, int32_t max_insert, unsigned long long *hist, unsigned long long *counters, hipStream_t s);
+void launch_pl_pairs(const SeedReads &r, const uint8_t *pair_off, const PlOut &o, int32_t max_insert, unsigned long long *hist, unsigned long long *counters, hipStream_t s);
 
 // the FASTA of a final result with depth headers: record j is the accepted pair of id j = target j
 struct PlFasta {

@@ -8,16 +8,10 @@
 //   k_pl_target_check   no negative target length; the columns (64-bit sum) and the indexed positions
 //   k_pl_final_targets  begin / length of the windows of a final result, by id
 //   k_pl_gather         the column array, one thread per word
-//   k_pl_keys           (k-mer, column) of every column; a column that is no indexed position gets a key above every k-mer
-//   k_pl_dir            directory of the sorted keys on the top bits of the k-mer, one thread per key (as k_cr_dir), and the distinct k-mers
-//   k_pl_place          one wave per read, both strands.  Lanes take seeds, 64 at a time: one directory read, a bisection to the lower bound, a
-//                       scan of at most max_occ + 1 equal keys.  The (seed, occurrence) candidates of the usable seeds go to the lanes in passes
-//                       of 64 (a wave scan of the occurrence counts, a bisection over it by cross-lane reads); a lane verifies its candidate by
-//                       XOR and popcount over funnel-shifted column words and leaves past max_mismatches.  A candidate found through seed j
-//                       counts only if no usable seed j' < j matches at that placement: no duplicates, no sort.  The minimum key and the number
-//                       of placements at its mm are reduced across the wave.  The rows are read from memory (every lane reads the same word):
-//                       there is no cap on the read length; a read with more than 64 seeds keeps the usable masks of its earlier seed chunks
-//                       in a per-wave piece of global scratch.
+//   (the index over the columns: alga_seed_index, seed_index.hip)
+//   k_pl_place          one wave per read, both strands: seed_and_verify (seed_device.h) once per strand over the read's L / k seeds.  A seed at
+//                       column g stands for the placement at g - j k where that lies in g's target with all L bases; the whole read is
+//                       verified.  The minimum key and the number of placements at its mm are reduced across the wave.
 //   k_pl_depth_add      +1 / -1 of every counting read into the difference array, the per-target sums: 32- and 64-bit integer atomics
 //   k_pl_uncovered      columns with cover 0 per target (the cover is one scan of the difference array over all columns: a read's +1 and -1
 //                       lie in one target, or the -1 on the first column of the next)
@@ -30,6 +24,7 @@
 #include <algorithm>
 
 #include "place_kernels.h"
+#include "seed_device.h"
 #include "text_record.h"
 #include "prefsuf_common.h"
 
@@ -40,43 +35,6 @@ namespace {
 constexpr int PL_BLOCK = 256, PL_WAVES = PL_BLOCK / 64;
 constexpr uint8_t PL_ST_PLACED = 1, PL_ST_UNIQUE = 2, PL_ST_MINUS = 4;   // ALGA_PLACE_* of include/alga_amd.h (the bits of d_state)
 constexpr uint8_t PL_V_ACCEPTED = 2;                                   // ALGA_FINAL_ACCEPTED
-
-__device__ __forceinline__ unsigned long long pl_wave_min(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) v, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), o);
-        const unsigned long long w = ((unsigned long long) hi << 32) | lo;
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-// the target of column g < col_off[T]: the last t with col_off[t] <= g (it has a length: col_off[t + 1] > g)
-__device__ __forceinline__ uint32_t pl_target_of(const uint32_t *__restrict__ col_off, uint32_t T, uint32_t g) {
-    uint32_t lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (col_off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the k-mer at column g of the column array (two words of padding behind the last column)
-__device__ __forceinline__ unsigned long long pl_col_kmer(const uint32_t *__restrict__ cols, uint32_t g, int k) {
-    const uint32_t w = g >> 4, sh = (g & 15u) << 1;
-    const unsigned long long lo = (unsigned long long) cols[w] | ((unsigned long long) cols[w + 1] << 32);
-    unsigned long long v = lo >> sh;
-    if (sh) v |= (unsigned long long) cols[w + 2] << (64 - sh);
-    return v & ((1ull << (2 * k)) - 1ull);
-}
-
-// the k-mer at base i of a row of nw words (i + k <= its length: nothing is read past word nw - 1)
-__device__ __forceinline__ unsigned long long pl_row_kmer(const uint32_t *__restrict__ row, int nw, int i, int k) {
-    const int w = i >> 4, sh = (i & 15) << 1;
-    const unsigned long long lo = (unsigned long long) row[w] | (w + 1 < nw ? (unsigned long long) row[w + 1] << 32 : 0ull);
-    unsigned long long v = lo >> sh;
-    if (sh && w + 2 < nw) v |= (unsigned long long) row[w + 2] << (64 - sh);
-    return v & ((1ull << (2 * k)) - 1ull);
-}
 
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_node_check(const uint8_t *__restrict__ pair_off, const int32_t *__restrict__ len, uint64_t n,
                                                             unsigned long long *__restrict__ counters) {
@@ -130,73 +88,34 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_gather(const uint32_t *__restri
     const uint64_t n_words = (t.columns + 15) >> 4;
     for (uint64_t w = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * PL_BLOCK) {
         const uint64_t g0 = w << 4;
-        uint32_t tt = pl_target_of(t.col_off, t.T, (uint32_t) g0), v = 0;
+        uint32_t tt = item_of(t.off, t.n, (uint32_t) g0), v = 0;
         for (int j = 0; j < 16; j++) {
             const uint64_t g = g0 + (uint64_t) j;
             if (g >= t.columns) break;
-            while ((uint64_t) t.col_off[tt + 1] <= g) tt++;                  // (g < columns = col_off[T]: ends at a target that has a length)
-            const unsigned long long src = begin[tt] + (g - (uint64_t) t.col_off[tt]);
+            while ((uint64_t) t.off[tt + 1] <= g) tt++;                  // (g < columns = col_off[T]: ends at a target that has a length)
+            const unsigned long long src = begin[tt] + (g - (uint64_t) t.off[tt]);
             v |= ((words[src >> 4] >> ((src & 15ull) << 1)) & 3u) << (2 * j);
         }
         cols[w] = v;
     }
 }
 
-__global__ void __launch_bounds__(PL_BLOCK) k_pl_keys(PlTargets t, int32_t k, unsigned long long *__restrict__ keys, uint32_t *__restrict__ vals) {
-    for (uint64_t g = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; g < t.columns; g += (uint64_t) gridDim.x * PL_BLOCK) {
-        const uint32_t tt = pl_target_of(t.col_off, t.T, (uint32_t) g);
-        const uint64_t q = g - (uint64_t) t.col_off[tt];
-        keys[g] = q + (uint64_t) k <= (uint64_t) t.tlen[tt] ? pl_col_kmer(t.cols, (uint32_t) g, k) : 1ull << (2 * k);      // above every k-mer, inside the 2k + 1 sorted bits
-        vals[g] = (uint32_t) g;
+// Geometry of a read of L bases on the targets: (seed js, column g) is the placement at g - js k where it lies in g's target
+struct PlGeometry {
+    static constexpr int kMmShift = 33;              // the key: (mm << 33) | (first column << 1) | strand
+    const PlTargets &t;
+    int k, L, strand;
+    __device__ __forceinline__ bool operator()(int js, uint32_t g, uint32_t &gp, int &n, unsigned long long &low) const {
+        const uint32_t tt = item_of(t.off, t.n, g);
+        const long long p = (long long) g - (long long) t.off[tt] - (long long) js * k;
+        if (p < 0 || p + (long long) L > (long long) t.len[tt]) return false;
+        gp = g - (uint32_t) (js * k); n = L;
+        low = ((unsigned long long) gp << 1) | (unsigned long long) strand;
+        return true;
     }
-}
+};
 
-__global__ void __launch_bounds__(PL_BLOCK) k_pl_dir(const unsigned long long *__restrict__ keys, uint64_t n, int shift, uint32_t n_buckets, uint32_t *__restrict__ dir,
-                                                     unsigned long long *__restrict__ counters) {
-    const uint64_t j = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x;
-    unsigned long long head = 0;
-    if (j <= n) {
-        const uint32_t lo = j == 0 ? 0u : (uint32_t) (keys[j - 1] >> shift) + 1u;
-        const uint32_t hi = j < n ? (uint32_t) (keys[j] >> shift) : n_buckets;
-        for (uint32_t b = lo; b <= hi && b <= n_buckets; b++) dir[b] = (uint32_t) j;
-        head = j < n && (j == 0 || keys[j - 1] != keys[j]) ? 1ull : 0ull;
-    }
-    head = wave_sum(head);
-    if ((threadIdx.x & 63) == 0 && head) atomicAdd(&counters[PL_DISTINCT], head);
-}
-
-// lower bound of x among the indexed keys and its occurrences, counted up to max_occ + 1
-__device__ __forceinline__ void pl_lookup(const PlIndex &x, unsigned long long kmer, uint32_t max_occ, uint32_t &lb, uint32_t &occ) {
-    const uint32_t b = (uint32_t) (kmer >> x.shift);
-    uint32_t lo = x.dir[b], hi = x.dir[b + 1];
-    const uint32_t end = hi;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (x.keys[mid] < kmer) lo = mid + 1; else hi = mid;
-    }
-    lb = lo;
-    uint32_t c = 0;
-    while (lo + c < end && c <= max_occ && x.keys[lo + c] == kmer) c++;
-    occ = c;
-}
-
-// Hamming distance between a row of L bases and the columns from gp on; stops past max_mm
-__device__ __forceinline__ uint32_t pl_verify(const uint32_t *__restrict__ row, int nw, int L, const uint32_t *__restrict__ cols, uint32_t gp, uint32_t max_mm) {
-    const uint32_t *tw = cols + (gp >> 4);
-    const uint32_t sh = (gp & 15u) << 1;
-    uint32_t mm = 0, prev = tw[0];
-    for (int w = 0; w < nw; w++) {
-        const uint32_t next = tw[w + 1];
-        uint32_t x = row[w] ^ __funnelshift_r(prev, next, sh);
-        prev = next;
-        if (w == nw - 1 && (L & 15)) x &= (1u << ((L & 15) << 1)) - 1u;
-        mm += (uint32_t) __popc((x | (x >> 1)) & 0x55555555u);
-        if (mm > max_mm) break;
-    }
-    return mm;
-}
-
-__global__ void __launch_bounds__(PL_BLOCK) k_pl_place(PlReads rd, PlTargets t, PlIndex x, int32_t k, uint32_t max_mm, uint32_t max_occ, PlOut o,
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_place(SeedReads rd, PlTargets t, SeedIndex x, int32_t k, uint32_t max_mm, uint32_t max_occ, PlOut o,
                                                        unsigned long long *__restrict__ scratch, uint32_t scratch_words, unsigned long long *__restrict__ counters) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t) blockIdx.x * PL_WAVES + (threadIdx.x >> 6), n_waves = (uint64_t) gridDim.x * PL_WAVES;
@@ -204,66 +123,22 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_place(PlReads rd, PlTargets t, 
     unsigned long long n_placed = 0, n_unique = 0, n_sat = 0, n_seeds = 0, n_over = 0;       // wave-uniform
     for (uint64_t r = wave; r < rd.R; r += n_waves) {
         const int32_t L = rd.len[2 * r + 1];
-        unsigned long long best = ~0ull;                 // (mm << 33) | (first column << 1) | strand, of this lane's placements
-        uint32_t lane_mm = 0xFFFFFFFFu, lane_cnt = 0;    // the smallest mm among them and how many have it
+        unsigned long long best = ~0ull;                 // of this lane's placements
+        MinMmTally tally;
         if (L >= k) {
-            const int S = L / k, nw = blocks_of(L);
             for (int strand = 0; strand < 2; strand++) {
-                const uint32_t *row = rd.rows + (2 * r + (strand == 0 ? 1u : 0u)) * (size_t) rd.stride;
-                for (int c0 = 0; c0 < S; c0 += 64) {
-                    const int j = c0 + lane;
-                    const bool act = j < S;
-                    uint32_t lb = 0, occ = 0;
-                    if (act) pl_lookup(x, pl_row_kmer(row, nw, j * k, k), max_occ, lb, occ);
-                    const bool usable = act && occ >= 1u && occ <= max_occ;
-                    const unsigned long long umask = __ballot(usable);
-                    n_seeds += (unsigned long long) __popcll(__ballot(act));
-                    n_over += (unsigned long long) __popcll(__ballot(act && occ > max_occ));
-                    if (S > 64) {                        // later chunks ask for this one's usable seeds
-                        if (lane == 0) __hip_atomic_store(&ub[c0 >> 6], umask, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __threadfence();
-                    }
-                    const uint32_t mine = usable ? occ : 0u;
-                    uint32_t inc = mine;
-                    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = (uint32_t) __shfl_up((int) inc, d); if (lane >= d) inc += up; }
-                    const uint32_t C = (uint32_t) __shfl((int) inc, 63), exc = inc - mine;
-                    for (uint32_t p0 = 0; p0 < C; p0 += 64) {
-                        const bool cact = p0 + (uint32_t) lane < C;
-                        const uint32_t ci = cact ? p0 + (uint32_t) lane : C - 1u;
-                        int sl = 0;                      // the seed lane of candidate ci: the first with inc > ci
-                        for (int st = 32; st > 0; st >>= 1) if ((uint32_t) __shfl((int) inc, sl + st - 1) <= ci) sl += st;
-                        const uint32_t s_lb = (uint32_t) __shfl((int) lb, sl), s_exc = (uint32_t) __shfl((int) exc, sl);
-                        if (!cact) continue;
-                        const int js = c0 + sl;
-                        const uint32_t g = x.vals[s_lb + (ci - s_exc)];
-                        const uint32_t tt = pl_target_of(t.col_off, t.T, g);
-                        const long long p = (long long) g - (long long) t.col_off[tt] - (long long) js * k;
-                        if (p < 0 || p + (long long) L > (long long) t.tlen[tt]) continue;
-                        const uint32_t gp = g - (uint32_t) (js * k);
-                        const uint32_t mm = pl_verify(row, nw, L, t.cols, gp, max_mm);
-                        if (mm > max_mm) continue;
-                        bool dup = false;                // an earlier usable seed finds this placement too
-                        for (int j2 = 0; j2 < js && !dup; j2++) {
-                            const unsigned long long m = j2 >= c0 ? umask : __hip_atomic_load(&ub[j2 >> 6], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if ((m >> (j2 & 63)) & 1ull) dup = pl_row_kmer(row, nw, j2 * k, k) == pl_col_kmer(t.cols, gp + (uint32_t) (j2 * k), k);
-                        }
-                        if (dup) continue;
-                        const unsigned long long key = ((unsigned long long) mm << 33) | ((unsigned long long) gp << 1) | (unsigned long long) strand;
-                        best = key < best ? key : best;
-                        if (mm < lane_mm) { lane_mm = mm; lane_cnt = 1u; }
-                        else if (mm == lane_mm) lane_cnt++;
-                    }
-                }
+                const RowQuery q{rd.rows + (2 * r + (strand == 0 ? 1u : 0u)) * (size_t) rd.stride, blocks_of(L), k};
+                seed_and_verify(x, t.cols, k, max_mm, max_occ, L / k, q, PlGeometry{t, k, L, strand}, ub, best, tally, n_seeds, n_over);
             }
         }
-        const unsigned long long win = pl_wave_min(best);
+        const unsigned long long win = wave_min_u64(best);
         int32_t tg = -1, ps = -1;
         uint8_t mm8 = 0, hits8 = 0, st8 = 0;
         if (win != ~0ull) {
             const uint32_t bmm = (uint32_t) (win >> 33), gp = (uint32_t) (win >> 1);
-            const unsigned long long hits = wave_sum(lane_mm == bmm ? (unsigned long long) lane_cnt : 0ull);
-            const uint32_t tt = pl_target_of(t.col_off, t.T, gp);
-            tg = (int32_t) tt; ps = (int32_t) (gp - t.col_off[tt]); mm8 = (uint8_t) bmm; hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
+            const unsigned long long hits = wave_sum(tally.mm == bmm ? (unsigned long long) tally.cnt : 0ull);
+            const uint32_t tt = item_of(t.off, t.n, gp);
+            tg = (int32_t) tt; ps = (int32_t) (gp - t.off[tt]); mm8 = (uint8_t) bmm; hits8 = (uint8_t) (hits > 255ull ? 255ull : hits);
             st8 = (uint8_t) (PL_ST_PLACED | (hits == 1ull ? PL_ST_UNIQUE : 0) | ((win & 1ull) ? PL_ST_MINUS : 0));
             n_placed++; n_unique += hits == 1ull; n_sat += hits > 255ull;
         }
@@ -278,37 +153,37 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_place(PlReads rd, PlTargets t, 
     }
 }
 
-__global__ void __launch_bounds__(PL_BLOCK) k_pl_depth_add(PlReads rd, PlTargets t, PlOut o, int multi, uint32_t *__restrict__ diff, unsigned long long *__restrict__ tstat) {
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_depth_add(SeedReads rd, PlTargets t, PlOut o, int multi, uint32_t *__restrict__ diff, unsigned long long *__restrict__ tstat) {
     for (uint64_t r = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; r < rd.R; r += (uint64_t) gridDim.x * PL_BLOCK) {
         const uint8_t st = o.state[r];
         if (!(st & (multi ? PL_ST_PLACED : PL_ST_UNIQUE))) continue;
         const uint32_t tt = (uint32_t) o.target[r], L = (uint32_t) rd.len[2 * r + 1];
-        const uint32_t gp = t.col_off[tt] + (uint32_t) o.pos[r];
+        const uint32_t gp = t.off[tt] + (uint32_t) o.pos[r];
         atomicAdd(&diff[gp], 1u);
         atomicAdd(&diff[gp + L], 0xFFFFFFFFu);                                // gp + L <= col_off[tt + 1] <= columns: the array has columns + 1 entries
         atomicAdd(&tstat[tt], 1ull);
-        atomicAdd(&tstat[(size_t) t.T + tt], (unsigned long long) L);
-        atomicAdd(&tstat[2 * (size_t) t.T + tt], (unsigned long long) o.mm[r]);
+        atomicAdd(&tstat[(size_t) t.n + tt], (unsigned long long) L);
+        atomicAdd(&tstat[2 * (size_t) t.n + tt], (unsigned long long) o.mm[r]);
     }
 }
 
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_uncovered(PlTargets t, const uint32_t *__restrict__ cover, unsigned long long *__restrict__ tstat) {
     const int lane = threadIdx.x & 63;
-    unsigned long long *unc = tstat + 3 * (size_t) t.T;
+    unsigned long long *unc = tstat + 3 * (size_t) t.n;
     for (uint64_t g0 = ((uint64_t) blockIdx.x * PL_BLOCK + (threadIdx.x & ~63u)); g0 < t.columns; g0 += (uint64_t) gridDim.x * PL_BLOCK) {
         const uint64_t g = g0 + (uint64_t) lane;
         const bool zero = g < t.columns && cover[g] == 0u;
         const unsigned long long m = __ballot(zero);
         if (!m) continue;
         const uint64_t glast = g0 + 63 < t.columns ? g0 + 63 : t.columns - 1;
-        const uint32_t t0 = pl_target_of(t.col_off, t.T, (uint32_t) g0);
-        if ((uint64_t) t.col_off[t0 + 1] > glast) {                           // the wave's columns lie in one target
+        const uint32_t t0 = item_of(t.off, t.n, (uint32_t) g0);
+        if ((uint64_t) t.off[t0 + 1] > glast) {                           // the wave's columns lie in one target
             if (lane == 0) atomicAdd(&unc[t0], (unsigned long long) __popcll(m));
-        } else if (zero) atomicAdd(&unc[pl_target_of(t.col_off, t.T, (uint32_t) g)], 1ull);
+        } else if (zero) atomicAdd(&unc[item_of(t.off, t.n, (uint32_t) g)], 1ull);
     }
 }
 
-__global__ void __launch_bounds__(PL_BLOCK) k_pl_pairs(PlReads rd, const uint8_t *__restrict__ pair_off, PlOut o, int32_t max_insert, unsigned long long *__restrict__ hist,
+__global__ void __launch_bounds__(PL_BLOCK) k_pl_pairs(SeedReads rd, const uint8_t *__restrict__ pair_off, PlOut o, int32_t max_insert, unsigned long long *__restrict__ hist,
                                                        unsigned long long *__restrict__ counters) {
     unsigned long long n_pairs = 0, n_proper = 0, n_improper = 0, n_split = 0, n_nu = 0, sum = 0;
     for (uint64_t r = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; r < rd.R; r += (uint64_t) gridDim.x * PL_BLOCK) {
@@ -380,38 +255,21 @@ void launch_pl_gather(const uint32_t *words, const unsigned long long *begin, co
     if (t.columns) hipLaunchKernelGGL(k_pl_gather, dim3(pl_grid((t.columns + 15) >> 4)), dim3(PL_BLOCK), 0, s, words, begin, t, cols);
 }
 
-void launch_pl_keys(const PlTargets &t, int32_t k, unsigned long long *keys, uint32_t *vals, hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_pl_keys, dim3(pl_grid(t.columns)), dim3(PL_BLOCK), 0, s, t, k, keys, vals);
-}
-
-void launch_pl_dir(const unsigned long long *keys, uint64_t n, int shift, int bits, uint32_t *dir, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_pl_dir, dim3((unsigned) ((n + 1 + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, s, keys, n, shift, 1u << bits, dir, counters);
-}
-
-int pl_place_blocks(uint64_t R, int n_cu) {
-    return (int) std::max<uint64_t>(1, std::min<uint64_t>((R + PL_WAVES - 1) / PL_WAVES, (uint64_t) std::max(1, n_cu) * 8u));
-}
-
-size_t pl_place_scratch_words(int blocks, int64_t max_read_len, int32_t k) {
-    const size_t per_wave = (size_t) std::max<int64_t>(1, (max_read_len / k + 63) / 64);
-    return (size_t) blocks * PL_WAVES * per_wave;
-}
-
-void launch_pl_place(const PlReads &r, const PlTargets &t, const PlIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, const PlOut &o, unsigned long long *scratch,
+void launch_pl_place(const SeedReads &r, const PlTargets &t, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, const PlOut &o, unsigned long long *scratch,
                      uint32_t scratch_words_per_wave, int blocks, unsigned long long *counters, hipStream_t s) {
     if (r.R) hipLaunchKernelGGL(k_pl_place, dim3((unsigned) blocks), dim3(PL_BLOCK), 0, s, r, t, x, k, (uint32_t) max_mm, (uint32_t) max_occ, o, scratch, scratch_words_per_wave,
                                 counters);
 }
 
-void launch_pl_depth_add(const PlReads &r, const PlTargets &t, const PlOut &o, int multi, uint32_t *diff, unsigned long long *tstat, hipStream_t s) {
-    if (r.R && t.T) hipLaunchKernelGGL(k_pl_depth_add, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, t, o, multi, diff, tstat);
+void launch_pl_depth_add(const SeedReads &r, const PlTargets &t, const PlOut &o, int multi, uint32_t *diff, unsigned long long *tstat, hipStream_t s) {
+    if (r.R && t.n) hipLaunchKernelGGL(k_pl_depth_add, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, t, o, multi, diff, tstat);
 }
 
 void launch_pl_uncovered(const PlTargets &t, const uint32_t *cover, unsigned long long *tstat, hipStream_t s) {
     if (t.columns) hipLaunchKernelGGL(k_pl_uncovered, dim3(pl_grid(t.columns, 8192)), dim3(PL_BLOCK), 0, s, t, cover, tstat);
 }
 
-void launch_pl_pairs(const PlReads &r, const uint8_t *pair_off, const PlOut &o, int32_t max_insert, unsigned long long *hist, unsigned long long *counters, hipStream_t s) {
+void launch_pl_pairs(const SeedReads &r, const uint8_t *pair_off, const PlOut &o, int32_t max_insert, unsigned long long *hist, unsigned long long *counters, hipStream_t s) {
     if (r.R && pair_off) hipLaunchKernelGGL(k_pl_pairs, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, pair_off, o, max_insert, hist, counters);
 }
 

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "polish_kernels.h"
+#include "seed_device.h"
 #include "text_record.h"
 
 namespace alga {
@@ -46,16 +47,6 @@ __device__ __forceinline__ uint32_t po_wave_max(uint32_t v) {
 __device__ __forceinline__ uint32_t po_wave_or(uint32_t v) {
     for (int o = 32; o > 0; o >>= 1) v |= (uint32_t) __shfl_xor((int) v, o);
     return v;
-}
-
-// the target of column g < col_off[T]: the last t with col_off[t] <= g
-__device__ __forceinline__ uint32_t po_target_of(const uint32_t *__restrict__ col_off, uint32_t T, uint32_t g) {
-    uint32_t lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (col_off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(PO_BLOCK) k_po_check(PoReads r, PoTargets t, unsigned long long *__restrict__ counters) {
@@ -124,7 +115,7 @@ __device__ __forceinline__ void po_add_targets(const PoTargets &t, const PoVote 
     const int lane = threadIdx.x & 63;
     const uint32_t first = (uint32_t) __shfl((int) (uint32_t) (w << 4), 0);        // lane 0 holds the wave's lowest word and is active where any lane is
     const uint64_t glast = (uint64_t) first + 1023 < t.columns ? (uint64_t) first + 1023 : t.columns - 1;
-    const uint32_t t0 = po_target_of(t.col_off, t.T, first);
+    const uint32_t t0 = item_of(t.col_off, t.T, first);
     const uint32_t nc = po_wave_sum32(active ? (uint32_t) __popc(chm) : 0u), na = po_wave_sum32(active ? (uint32_t) __popc(amm) : 0u);
     if ((uint64_t) t.col_off[t0 + 1] > glast) {
         if (lane == 0) {
@@ -132,8 +123,8 @@ __device__ __forceinline__ void po_add_targets(const PoTargets &t, const PoVote 
             if (na) atomicAdd(&v.t_ambiguous[t0], (unsigned long long) na);
         }
     } else if (active) {
-        for (uint32_t m = chm; m; m &= m - 1) atomicAdd(&v.t_changed[po_target_of(t.col_off, t.T, (uint32_t) (w << 4) + (uint32_t) (__ffs((int) m) - 1))], 1ull);
-        for (uint32_t m = amm; m; m &= m - 1) atomicAdd(&v.t_ambiguous[po_target_of(t.col_off, t.T, (uint32_t) (w << 4) + (uint32_t) (__ffs((int) m) - 1))], 1ull);
+        for (uint32_t m = chm; m; m &= m - 1) atomicAdd(&v.t_changed[item_of(t.col_off, t.T, (uint32_t) (w << 4) + (uint32_t) (__ffs((int) m) - 1))], 1ull);
+        for (uint32_t m = amm; m; m &= m - 1) atomicAdd(&v.t_ambiguous[item_of(t.col_off, t.T, (uint32_t) (w << 4) + (uint32_t) (__ffs((int) m) - 1))], 1ull);
     }
 }
 
@@ -257,8 +248,8 @@ __global__ void __launch_bounds__(PO_BLOCK) k_po_vote_wide(PoReads r, PoTargets 
             if (lane == 0) { v.words[w] = word; v.marks[w] = chm | (amm << 16); v.pop[w] = (uint32_t) __popc(chm); }
             n_changed += (unsigned long long) __popc(chm); n_amb += (unsigned long long) __popc(amm);
             if (lane == 0) {                                          // rare: one atomic per marked column
-                for (uint32_t m = chm; m; m &= m - 1) atomicAdd(&v.t_changed[po_target_of(t.col_off, t.T, (uint32_t) g0 + (uint32_t) (__ffs((int) m) - 1))], 1ull);
-                for (uint32_t m = amm; m; m &= m - 1) atomicAdd(&v.t_ambiguous[po_target_of(t.col_off, t.T, (uint32_t) g0 + (uint32_t) (__ffs((int) m) - 1))], 1ull);
+                for (uint32_t m = chm; m; m &= m - 1) atomicAdd(&v.t_changed[item_of(t.col_off, t.T, (uint32_t) g0 + (uint32_t) (__ffs((int) m) - 1))], 1ull);
+                for (uint32_t m = amm; m; m &= m - 1) atomicAdd(&v.t_ambiguous[item_of(t.col_off, t.T, (uint32_t) g0 + (uint32_t) (__ffs((int) m) - 1))], 1ull);
             }
         }
     }

@@ -215,7 +215,7 @@ TINY_LENS = [0, 21, 22, 37, 0, 0, 64, 65, 16, 100, 5, 48, 0, 20, 129, 1, 63, 0, 
 
 
 def _tiny_targets():
-    # 150 targets, 39 of them empty: several seams inside one word of k_pl_gather, one wave of k_pl_uncovered, and equal offsets in pl_target_of
+    # 150 targets, 39 of them empty: several seams inside one word of k_pl_gather, one wave of k_pl_uncovered, and equal offsets in item_of
     rng = _rng(15)
     targets = [_seq(rng, TINY_LENS[i % 19]) for i in range(150)]
     reads = []

@@ -1,8 +1,8 @@
 """The merge stage on the GPU (alga_merge_targets_device, alga_write_merged_fasta_device): every output array and every counter equal to the
 Python definition (tests/merge_checker.py) on the cases of tests/merge_cases.py, from host arrays and from tensors and with directories of 1, 4
-and auto bits; the FASTA bytes and the TSV; a wave of k_mg_overlap that takes a second end; a second round on Merged.targets(); the caller's
-stream; refusals leave an earlier result valid; a result stays valid across a later placement, polish, break, grow and scaffold; the planted
-genome end to end; the command line."""
+and auto bits; the FASTA bytes and the TSV; the one index workspace shared with the placement and the grow stage; a wave of k_mg_overlap that
+takes a second end; a second round on Merged.targets(); the caller's stream; refusals leave an earlier result valid; a result stays valid across
+a later placement, polish, break, grow and scaffold; the planted genome end to end; the command line."""
 import os
 import subprocess
 
@@ -66,6 +66,39 @@ def test_every_case_equals_the_checker(eng, name, tmp_path):
         assert_same(eng.merge_ends(tg, **v).to_host(), QC.checked(name, i), (name, i, "tensors"))
     for a, b in zip(tg, keep):
         assert (a == b).all()
+
+
+def test_one_index_workspace_serves_the_stages_in_turn(eng):
+    """place, merge and grow build their seed index in one workspace of the engine: on one engine, calls of different stages, k, directory
+    widths and seed counts in turn, each equal to its checker -- no index, directory size, k or usable-seed mask is left over from the call
+    before (many_seeds and second_chunk have reads of more than 64 seeds: they use the per-wave scratch; seeds64 has exactly 64)"""
+    import grow_cases as GQC
+    import place_cases as PC
+
+    def same(got, want, arrays, what):
+        for k in arrays:
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and (got[k] == want[k]).all(), (what, k)
+        assert {k: v for k, v in got["info"].items() if not k.startswith("ms_")} == want["info"], (what, got["info"], want["info"])
+
+    def place(c):
+        return eng.place_reads(c["rows"], c["lens"], targets=(c["twords"], c["tbegin"], c["tlen"]), pair_off=c.get("pair_off"), **c["params"])
+
+    try:
+        same(place(PC.case("many_seeds")).to_host(), PC.checked("many_seeds"), P.ARRAYS, "place many_seeds")
+        eng.set_option("place_dir_bits", 3)
+        c = QC.case("seeds64")
+        assert c["variants"][0]["k"] == 8
+        assert_same(eng.merge_ends(QC.targets(c), **c["variants"][0]).to_host(), QC.checked("seeds64"), "merge seeds64, 3 directory bits")
+        c = GQC.case("second_chunk")
+        pl = place(c)
+        assert (pl.to_host()["state"] == GQC.placed("second_chunk")["state"]).all()
+        same(eng.grow_ends(c["rows"], c["lens"], pl, **c["variants"][0]).to_host(), GQC.checked("second_chunk"), GC.ARRAYS, "grow second_chunk")
+        eng.set_option("place_dir_bits", 0)
+        same(place(PC.case("repeat")).to_host(), PC.checked("repeat"), P.ARRAYS, "place repeat")
+        c = QC.case("pairings")
+        assert_same(eng.merge_ends(QC.targets(c), **c["variants"][0]).to_host(), QC.checked("pairings"), "merge pairings")
+    finally:
+        eng.set_option("place_dir_bits", 0)
 
 
 def test_a_wave_takes_a_second_end(eng):

@@ -15,7 +15,7 @@ import grow_checker as GC
 import place_checker as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["k_gr_check", "k_gr_candidates", "k_gr_compact", "k_gr_end_lens", "k_gr_ends", "k_gr_keys", "k_gr_place", "k_gr_vote", "k_gr_decide", "k_gr_lens", "k_gr_build",
+KERNELS = ["k_gr_check", "k_gr_candidates", "k_gr_compact", "k_gr_end_lens", "k_gr_ends", "k_gr_place", "k_gr_vote", "k_gr_decide", "k_gr_lens", "k_gr_build",
            "k_gr_fasta_sizes", "k_gr_fasta_write"]
 SYMBOLS = ("alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device")
 # (candidates, overhanging, voting, bases_added) of every variant of every case

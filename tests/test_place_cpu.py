@@ -17,7 +17,7 @@ import place_checker as P
 import unitig_checker as U
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["k_pl_node_check", "k_pl_target_check", "k_pl_final_targets", "k_pl_gather", "k_pl_keys", "k_pl_dir", "k_pl_place", "k_pl_depth_add",
+KERNELS = ["k_pl_node_check", "k_pl_target_check", "k_pl_final_targets", "k_pl_gather", "k_pl_place", "k_pl_depth_add",
            "k_pl_uncovered", "k_pl_pairs", "k_pl_fasta_sizes", "k_pl_fasta_write"]
 
 
