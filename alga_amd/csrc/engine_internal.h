@@ -234,6 +234,13 @@ struct alga_engine {
     int         mg_cur = 0;                        // the set that holds the result
     bool        mg_valid = false;
     uint64_t    mg_targets = 0, mg_merged = 0, mg_columns = 0, mg_longest = 0;   // ... of this many targets, merged contigs and columns; the longest merged contig
+    // the unplaced reads laid with indels (engine_gapped.hip).  Workspaces: counters, the participation flags, their scan and the list, this
+    // stage's column array, the best key per participating read, the strided runs and their numbers, the difference array and its scan.  The
+    // result: per read target / pos / end / edits / state, the CIGAR offsets and runs, the cover, the per-target sums
+    DevBuf      gp_cnt, gp_flag, gp_pos, gp_list, gp_cols, gp_best, gp_runs, gp_nruns, gp_diff, gp_scan;
+    DevBuf      gp_target, gp_rpos, gp_end, gp_edits, gp_state, gp_cigoff, gp_cigar, gp_cover, gp_tstat;
+    bool        gp_valid = false;                  // the result buffers hold a gapped placement
+    uint64_t    gp_reads = 0, gp_targets = 0, gp_columns = 0, gp_ncigar = 0;   // ... of this many reads, targets and columns; its runs
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

@@ -183,7 +183,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device",
            "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device",
            "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device",
-           "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device"]
+           "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device",
+           "alga_gapped_default_params", "alga_place_gapped_device", "alga_write_gapped_tsv_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -783,6 +784,66 @@ def merge_tsv(h, tlen):
     return "".join(lines)
 
 
+GAPPED_MAX_READ = 1024                                           # ALGA_GAPPED_MAX_READ
+GAPPED_PLACED, GAPPED_UNIQUE, GAPPED_MINUS, GAPPED_INDEL = 1, 2, 4, 8   # bits of Gapped.state
+CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2                              # the low two bits of a Gapped.cigar entry
+
+
+class GappedParams(C.Structure):
+    """alga_gapped_params"""
+    _fields_ = [(k, C.c_int32) for k in ("k", "max_edits", "max_occ", "flags")] + [("reserved", C.c_int32 * 4)]
+
+
+class GappedInfo(C.Structure):
+    """alga_gapped_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("tried", "skipped_long", "placed", "unique", "with_indel", "edits", "insertions", "deletions", "candidates", "seeds",
+                                          "seeds_over_max_occ")] + \
+               [(k, C.c_double) for k in ("ms_index", "ms_place", "ms_trace", "ms_depth", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GappedC(C.Structure):
+    """alga_gapped"""
+    _fields_ = [("n_reads", C.c_int64), ("n_targets", C.c_int64), ("n_columns", C.c_uint64), ("n_cigar", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_target", "d_pos", "d_end", "d_edits", "d_state", "d_cigar_off", "d_cigar", "d_cover", "d_t_reads", "d_t_bases", "d_t_edits")]
+
+
+class Gapped:
+    """Result of Engine.place_gapped: zero-copy torch views of the engine's device memory (valid until the next Engine.place_gapped call on that
+    engine; clone what has to live longer) -- target / pos / end int32 [n_reads], edits / state uint8 [n_reads], cigar_off int32 [n_reads + 1]
+    and cigar int32 [n_cigar] (the bits of uint32: len << 2 | op), cover int32 [n_columns] (the bits of uint32), t_reads / t_bases / t_edits
+    int64 [n_targets] -- and .info (dict of alga_gapped_info)."""
+    KEYS = (("target", "<i4", np.int32, "r"), ("pos", "<i4", np.int32, "r"), ("end", "<i4", np.int32, "r"), ("edits", "|u1", np.uint8, "r"), ("state", "|u1", np.uint8, "r"),
+            ("cigar_off", "<i4", np.uint32, "r1"), ("cigar", "<i4", np.uint32, "c"), ("cover", "<i4", np.uint32, "g"), ("t_reads", "<i8", np.uint64, "t"),
+            ("t_bases", "<i8", np.uint64, "t"), ("t_edits", "<i8", np.uint64, "t"))
+
+    def __init__(self, c, info, device, placements=None):
+        self._c, self.info, self._placements = c, info, placements
+        self.n_reads, self.n_targets, self.n_columns, self.n_cigar = int(c.n_reads), int(c.n_targets), int(c.n_columns), int(c.n_cigar)
+        dev = "cuda:%d" % device
+        size = dict(r=self.n_reads, r1=self.n_reads + 1, c=self.n_cigar, g=self.n_columns, t=self.n_targets)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/gapped_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+    def cigar_strings(self, host=None):
+        """the CIGAR of every read as text ('' where it is not placed), for example 57M1D93M"""
+        return cigar_strings(host if host is not None else self.to_host())
+
+
+def cigar_strings(h):
+    """the scripts of a gapped result read back (Gapped.to_host())"""
+    off = h["cigar_off"]
+    return ["".join("%d%s" % (int(x) >> 2, "MID"[int(x) & 3]) for x in h["cigar"][int(off[r]):int(off[r + 1])]) for r in range(len(off) - 1)]
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -947,6 +1008,11 @@ def load_library():
     lib.alga_merge_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MergeParams), C.c_void_p, C.POINTER(MergedC),
                                               C.POINTER(MergeInfo)]
     lib.alga_write_merged_fasta_device.argtypes = [C.c_void_p, C.POINTER(MergedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_gapped_default_params.argtypes = [C.POINTER(GappedParams)]
+    lib.alga_gapped_default_params.restype = None
+    lib.alga_place_gapped_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PlacementsC), C.POINTER(GappedParams),
+                                             C.c_void_p, C.POINTER(GappedC), C.POINTER(GappedInfo)]
+    lib.alga_write_gapped_tsv_device.argtypes = [C.c_void_p, C.POINTER(GappedC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -2050,6 +2116,61 @@ class Engine:
         records): `>contig_id=<j>_length=<len>_contigs=<m>` per merged contig."""
         info = GfaInfo()
         self._check(self._lib.alga_write_merged_fasta_device(self._h, C.byref(merged._c), os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    def place_gapped(self, words, lens, placements, targets=None, final=None, stream=None, **params):
+        """The reads the Hamming placement left unplaced laid onto the same targets by edit distance (alga_place_gapped_device) -> Gapped.
+        words / lens: the node set that was placed; placements: the result of the LAST Engine.place_reads call; targets = the (packed words,
+        begin int64 [T], len int32 [T]) that call was given, or final = the Engine.final_contigs result it was given.  Host arrays are
+        uploaded first; tensors are used where they are and left untouched.  params: k, max_edits, max_occ (the fields of alga_gapped_params;
+        the library's defaults where not given)."""
+        import torch
+        assert (targets is None) != (final is None), "give targets or final"
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if final is not None:
+            # the targets of alga_place_reads_on_final_device: target j = the window of the pair order[j] in the consensus words
+            u, fin = final._unitigs, final
+            order = fin.order.to(torch.int64)
+            live = fin.verdict.to(torch.int64)[order] == 2
+            zero = torch.zeros_like(order)
+            tbegin = (16 * u.word_off.to(torch.int64)[order] + torch.where(live, fin.begin.to(torch.int64)[order], zero)).contiguous()
+            tlen = torch.where(live, fin.len.to(torch.int64)[order], zero).to(torch.int32).contiguous()
+            targets = (final._consensus.words, tbegin, tlen)
+        twords, tbegin, tlen = targets
+        twords, tlen = up(twords, np.uint32, np.int32), up(tlen, np.int32)
+        if isinstance(tbegin, np.ndarray):
+            tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
+        assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = GappedParams(), GappedC(), GappedInfo()
+        self._lib.alga_gapped_default_params(C.byref(pp))
+        for k, v in params.items():
+            if k not in ("k", "max_edits", "max_occ", "flags"):
+                raise TypeError("Engine.place_gapped: unknown parameter %r" % k)
+            setattr(pp, k, int(v))
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_place_gapped_device(self._h, C.byref(nd), C.c_void_p(_ptr(twords) or None), C.c_void_p(_ptr(tbegin) or None),
+                                                       C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(placements._c), C.byref(pp), st, C.byref(out),
+                                                       C.byref(info)))
+        return Gapped(out, info.as_dict(), self.device, (placements, twords, tbegin, tlen))
+
+    def write_gapped_tsv(self, path, gapped):
+        """The gapped placements of the LAST Engine.place_gapped call as text (alga_write_gapped_tsv_device) -> dict of alga_gfa_info (segments =
+        lines): `read target pos end strand edits unique cigar` (tabs) per gapped-placed read, in read order."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_gapped_tsv_device(self._h, C.byref(gapped._c), os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

@@ -97,6 +97,11 @@
 // `>contig_id=<j>_length=<len>_contigs=<m>` (alga_write_merged_fasta_device); --merge_layout=PATH: one line `merged rank contig orient start
 // length overlap_after mm` per member, tab separated (both need --merge_ends=1).  One line on stderr gives overlaps / ambiguous ends / joins /
 // bases removed / N50 before -> after.  Without --merge_ends=1 every file is what it was.  None is passed through.
+// --gapped=1 (default 0; needs --contigs_final=; implies the placement): behind the placement on the final contigs the reads it left unplaced are
+// laid onto the same contigs by edit distance (alga_place_gapped_device: --gapped_edits= (6, 1 .. 15)).  --gapped_placements=PATH (needs
+// --gapped=1): one line `read target pos end strand edits unique cigar` per gapped-placed read, tab separated, formatted on the device
+// (alga_write_gapped_tsv_device).  One line on stderr gives tried / placed / unique / with indel / edits.  It changes no other output: the depth
+// headers and --placements= are the Hamming placement's.  Neither is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -125,7 +130,8 @@ static const char *USAGE =
     "         [--break_misjoins=0|1] [--break_min_span=1] [--break_inset=21] [--break_margin=N] [--broken=pieces.fasta] [--break_cuts=cuts.tsv]\n"
     "         [--grow_ends=N] [--grown=grown.fasta] [--grow_layout=grow.tsv] [--grow_min_anchor=63] [--grow_max_mismatches=2] [--grow_min_cover=3]\n"
     "         [--grow_min_percent=80] [--grow_max=64]\n"
-    "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n";
+    "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n"
+    "         [--gapped=0|1] [--gapped_edits=6] [--gapped_placements=gapped.tsv]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -155,6 +161,8 @@ int main(int argc, char **argv) {
     alga_grow_params grp;
     alga_grow_default_params(&grp);
     int merge_ends = 0;
+    int gapped = 0, gapped_edits = -1;
+    std::string gapped_placements;
     std::string merged_path, merge_layout;
     alga_merge_params mgp;
     alga_merge_default_params(&mgp);
@@ -213,6 +221,9 @@ int main(int argc, char **argv) {
         else if (opt(a, "--grow_min_percent", v)) grp.min_percent = atoi(v.c_str());
         else if (opt(a, "--grow_max", v)) grp.max_grow = atoi(v.c_str());
         else if (opt(a, "--merge_ends", v)) merge_ends = atoi(v.c_str());
+        else if (opt(a, "--gapped_placements", v)) gapped_placements = v;
+        else if (opt(a, "--gapped_edits", v)) gapped_edits = atoi(v.c_str());
+        else if (opt(a, "--gapped", v)) gapped = atoi(v.c_str());
         else if (opt(a, "--merged", v)) merged_path = v;
         else if (opt(a, "--merge_layout", v)) merge_layout = v;
         else if (opt(a, "--merge_min_overlap", v)) mgp.min_overlap = atoi(v.c_str());
@@ -265,6 +276,10 @@ int main(int argc, char **argv) {
                         "--grow_max in [1, 4096]\n");
         return 2;
     }
+    if (gapped != 0 && gapped != 1) { fprintf(stderr, "alga_hip: --gapped must be 0 or 1 (got %d)\n", gapped); return 2; }
+    if (gapped && contigs_final.empty()) { fprintf(stderr, "alga_hip: --gapped=1 needs --contigs_final=\n"); return 2; }
+    if (!gapped && (!gapped_placements.empty() || gapped_edits != -1)) { fprintf(stderr, "alga_hip: --gapped_placements= and --gapped_edits= need --gapped=1\n"); return 2; }
+    if (gapped && gapped_edits != -1 && (gapped_edits < 1 || gapped_edits > 15)) { fprintf(stderr, "alga_hip: --gapped_edits must be in [1, 15] (got %d)\n", gapped_edits); return 2; }
     if (merge_ends != 0 && merge_ends != 1) { fprintf(stderr, "alga_hip: --merge_ends must be 0 or 1 (got %d)\n", merge_ends); return 2; }
     if (merge_ends && !grow_ends) { fprintf(stderr, "alga_hip: --merge_ends=1 needs --grow_ends >= 1\n"); return 2; }
     if (!merge_ends && (!merged_path.empty() || !merge_layout.empty())) { fprintf(stderr, "alga_hip: --merged= and --merge_layout= need --merge_ends=1\n"); return 2; }
@@ -563,7 +578,7 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
-                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins || grow_ends)) {
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins || grow_ends || gapped)) {
                     // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
                     alga_parsed_reads pr{};
                     char perr[512] = {0};
@@ -608,6 +623,44 @@ int main(int argc, char **argv) {
                             fprintf(f, "%zu\t%d\t%d\t%c\t%d\t%d\n", r, tg[r], ps[r], !(state[r] & ALGA_PLACE_PLACED) ? '.' : (state[r] & ALGA_PLACE_MINUS) ? '-' : '+',
                                     (int) mm[r], (int) hits[r]);
                         if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", placements.c_str()); return 1; }
+                    }
+                    if (rc == ALGA_OK && gapped) {
+                        // the targets of that placement once more, as arrays: target j = the window of the pair order[j] (not a hot path: made on the host)
+                        const size_t np = (size_t) fc.n_pairs, nt = (size_t) fc.n_accepted;
+                        std::vector<uint64_t> woff(np + 1), tb(nt + 1);
+                        std::vector<uint8_t> verdict(np + 1);
+                        std::vector<int32_t> order(nt + 1), fb(np + 1), fl(np + 1), tl(nt + 1);
+                        rc = alga_copy_to_host(engine, woff.data(), cu.d_word_off, (np + 1) * sizeof(uint64_t));
+                        if (rc == ALGA_OK && np) rc = alga_copy_to_host(engine, verdict.data(), fc.d_verdict, np);
+                        if (rc == ALGA_OK && np) rc = alga_copy_to_host(engine, fb.data(), fc.d_begin, np * sizeof(int32_t));
+                        if (rc == ALGA_OK && np) rc = alga_copy_to_host(engine, fl.data(), fc.d_len, np * sizeof(int32_t));
+                        if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, order.data(), fc.d_order, nt * sizeof(int32_t));
+                        for (size_t j = 0; rc == ALGA_OK && j < nt; j++) {
+                            const size_t q = (size_t) order[j];
+                            const bool live = verdict[q] == ALGA_FINAL_ACCEPTED;
+                            tb[j] = 16ull * woff[q] + (uint64_t) (live ? fb[q] : 0);
+                            tl[j] = live ? fl[q] : 0;
+                        }
+                        void *d_tb = nullptr, *d_tl = nullptr;
+                        if (rc == ALGA_OK) rc = alga_device_alloc(engine, (nt + 1) * sizeof(uint64_t), &d_tb);
+                        if (rc == ALGA_OK) rc = alga_device_alloc(engine, (nt + 1) * sizeof(int32_t), &d_tl);
+                        if (rc == ALGA_OK && nt) rc = alga_copy_to_device(engine, d_tb, tb.data(), nt * sizeof(uint64_t));
+                        if (rc == ALGA_OK && nt) rc = alga_copy_to_device(engine, d_tl, tl.data(), nt * sizeof(int32_t));
+                        alga_gapped_params gq;
+                        alga_gapped_default_params(&gq);
+                        if (gapped_edits != -1) gq.max_edits = gapped_edits;
+                        alga_gapped gp;
+                        alga_gapped_info gi;
+                        if (rc == ALGA_OK) rc = alga_place_gapped_device(engine, &pnd, cs.d_words, (const uint64_t *) d_tb, (const int32_t *) d_tl, (int32_t) nt, &pl, &gq, nullptr, &gp, &gi);
+                        if (rc == ALGA_OK)
+                            fprintf(stderr, "Unplaced reads laid with indels (up to %d edits): %llu tried, %llu placed, %llu unique, %llu with indel, %llu edits; "
+                                    "device ms: index %.3f place %.3f trace %.3f depth %.3f, call %.1f ms wall\n", gq.max_edits, (unsigned long long) gi.tried,
+                                    (unsigned long long) gi.placed, (unsigned long long) gi.unique, (unsigned long long) gi.with_indel, (unsigned long long) gi.edits,
+                                    gi.ms_index, gi.ms_place, gi.ms_trace, gi.ms_depth, gi.ms_total);
+                        alga_gfa_info gti;
+                        if (rc == ALGA_OK && !gapped_placements.empty()) rc = alga_write_gapped_tsv_device(engine, &gp, gapped_placements.c_str(), &gti);
+                        alga_device_free(engine, d_tb);
+                        alga_device_free(engine, d_tl);
                     }
                     alga_polished pol{};
                     if (rc == ALGA_OK && polish) {

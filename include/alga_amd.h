@@ -1702,6 +1702,92 @@ int  alga_merge_targets_device(alga_engine *e, const uint32_t *d_words, const ui
                                const alga_merge_params *p, void *hip_stream, alga_merged *out, alga_merge_info *info /* may be NULL */);
 int  alga_write_merged_fasta_device(alga_engine *e, const alga_merged *merged, const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- gapped placement: the unplaced reads laid with indels, CIGARs (alga_amd/csrc/gapped_kernels.hip, engine_gapped.hip) -----------------
+ * alga_place_reads_device verifies by Hamming distance, so a read with one inserted or deleted base is unplaced.  This second pass lays the
+ * reads the Hamming pass left unplaced onto the same targets by edit distance, reports where they lie and how, and adds their cover.  Integers
+ * only, free of any order (thread, sort); tests/gapped_checker.py states the rule twice in Python and the device result equals it array for
+ * array.
+ *
+ * Inputs: the node set in twin layout and the ragged target set exactly as alga_place_reads_device takes them; the engine's current placement
+ * result `pl` on those targets; alga_gapped_params: k 8 .. 31 (default 21), max_edits E 1 .. 15 (6), max_occ 1 .. 65535 (256), flags 0;
+ * anything else answers ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Who takes part.  Read r takes part iff pl.d_state[r] lacks ALGA_PLACE_PLACED, len >= k and len <= ALGA_GAPPED_MAX_READ (1024).  A read
+ *      above the cap is counted in skipped_long; a read the Hamming pass placed is never touched.
+ *   2. Index and seeds: rules 1 and 2 of the placement.  Position (t, q) is indexed for q + k <= len[t]; node v of length L has
+ *      S = floor(L / k) seeds, seed j = bases jk .. jk + k - 1, USABLE iff 1 <= occ <= max_occ.  Both nodes of the read (both strands) are tried.
+ *   3. Candidates.  Usable seed j of node v equal to the k-mer at indexed position (t, q) is a candidate (j, t, q).  It COUNTS iff no usable
+ *      seed j' < j of v equals t[q - (j - j') k .. + k) (the same diagonal, inside t).
+ *   4. Distance.  Unit costs: substitution, insertion (a read base alone), deletion (a target base alone).  The alignment passes through the
+ *      seed, is global in the read and free-ended in the target, inside target t only.  Right part: v[jk + k .. L) against t[q + k ..);
+ *      left part: v[0 .. jk) reversed against t[0 .. q) reversed.  For a part with n read bases and avail target bases, D[i][c] is the usual
+ *      edit-distance table from (0, 0) (D[0][c] = c, D[i][0] = i).  The part's end is the column c in [max(0, n - E), min(avail, n + E)]
+ *      with the smallest D[n][c]; ties go to the smallest |c - n|, then the smaller c; no such c: not a placement.  d = d_left + d_right; the
+ *      candidate is a gapped placement iff d <= E.  Its first column is p = q - c_left, its end (exclusive) e = q + k + c_right.  A read
+ *      hanging over a target end by at most E bases is thereby placed with insertions at the edge; there are no clipped ends.
+ *   5. Canonical script.  Each part is traced back from its end cell to (0, 0); at every cell it takes the first of diagonal, up (insertion),
+ *      left (deletion) whose predecessor attains the value (row 0 goes left, column 0 goes up).  The CIGAR is the left part (reversed back),
+ *      k M for the seed, the right part, equal neighbouring ops merged; ops ALGA_CIGAR_M (match or substitution), _I, _D; at most 2 E + 1
+ *      runs.  Banding to |c - i| <= E changes no decision: a value <= E is exact inside the band (a path of cost <= E leaves diagonal 0 by at
+ *      most E), a banded value > E says the true one is > E, the trace visits only cells <= d <= E, and a predecessor that attains such a
+ *      value is itself <= E.  The checker asserts banded == full on every case.
+ *   6. Per read.  best = the smallest (d, strand, t, p, e) over its counting candidates that are placements, with + < - (the strand before the
+ *      position, so that uniqueness follows from a minimum and a maximum); among candidates equal in all five the one with the smallest
+ *      (j, q) gives the script.  ALGA_GAPPED_UNIQUE iff every such candidate with d == best.d has best's strand and target and
+ *      p <= best.p + E.  State bits ALGA_GAPPED_PLACED, _UNIQUE, _MINUS, _INDEL (the script has an I or a D).  Per read, with these defaults
+ *      where it is not placed: d_target (-1), d_pos (-1), d_end (-1), d_edits (0), d_state (0).  d_cigar_off has n_reads + 1 entries (the
+ *      exclusive scan of the run counts, 0 runs where not placed); d_cigar is uint32 len << 2 | op, n_cigar = d_cigar_off[n_reads] entries.
+ *   7. Cover.  A gapped read COUNTS iff it is UNIQUE.  d_cover[c] = pl.d_cover[c] + the counting gapped reads whose [p, e) contains c: deleted
+ *      columns count as covered, inserted bases cover nothing.  Per target, the gapped reads alone: d_t_reads, d_t_bases (the sum of
+ *      e - p), d_t_edits.
+ *   8. Counters (alga_gapped_info): tried (the reads that take part), skipped_long, placed, unique, with_indel, edits (the sum of d over the
+ *      placed), insertions, deletions (inserted / deleted bases of their scripts), candidates (those that count, rule 3), seeds,
+ *      seeds_over_max_occ (of the reads that take part, both strands); ms_index, ms_place, ms_trace, ms_depth (HIP events), ms_total (wall).
+ *   9. Refusals, all before anything of the result is written (ALGA_ERR_INVALID_ARGUMENT): `pl` is not the engine's current placement result;
+ *      nodes->n / 2 != pl.n_reads; n_targets != pl.n_targets; on the device: a target length that differs from pl's col_off (so n_columns
+ *      agrees), the twin property of the node set.
+ * The result (alga_gapped) is engine-owned, valid until the next gapped call on `e`; a refused call leaves an earlier result valid; `pl` and
+ * every other result stay valid.  The seed index is built in the engine's one index workspace (option "place_dir_bits" as for the placement).
+ * Read-backs: the refusal flags with the participating reads; the number of runs (d_cigar is allocated at its size); the counters.
+ *
+ * alga_write_gapped_tsv_device: one line per gapped-placed read in read order, `read target pos end strand edits unique cigar` separated by
+ * tabs (strand + or -, unique 0 or 1, the CIGAR as text, for example 57M1D93M), formatted on the device.  `gapped` must be the engine's
+ * current gapped result.  ABI stays 7: the calls add. */
+#define ALGA_GAPPED_MAX_READ 1024
+#define ALGA_GAPPED_PLACED 1         /* bits of alga_gapped.d_state                                                                    */
+#define ALGA_GAPPED_UNIQUE 2
+#define ALGA_GAPPED_MINUS  4
+#define ALGA_GAPPED_INDEL  8
+#define ALGA_CIGAR_M 0               /* the low two bits of a d_cigar entry                                                            */
+#define ALGA_CIGAR_I 1
+#define ALGA_CIGAR_D 2
+typedef struct {
+    int32_t k, max_edits, max_occ, flags;
+    int32_t reserved[4];             /* 0                                                                                             */
+} alga_gapped_params;
+typedef struct {
+    int64_t         n_reads;         /* n / 2                                                                                         */
+    int64_t         n_targets;
+    uint64_t        n_columns;       /* pl.n_columns                                                                                  */
+    uint64_t        n_cigar;         /* d_cigar_off[n_reads]                                                                          */
+    const int32_t  *d_target, *d_pos, *d_end;        /* n_reads                                                                       */
+    const uint8_t  *d_edits, *d_state;               /* n_reads                                                                       */
+    const uint32_t *d_cigar_off;     /* n_reads + 1                                                                                   */
+    const uint32_t *d_cigar;         /* n_cigar                                                                                       */
+    const uint32_t *d_cover;         /* n_columns                                                                                     */
+    const uint64_t *d_t_reads, *d_t_bases, *d_t_edits;   /* n_targets                                                                 */
+} alga_gapped;
+typedef struct {
+    uint64_t tried, skipped_long, placed, unique, with_indel, edits, insertions, deletions, candidates, seeds, seeds_over_max_occ;
+    double   ms_index, ms_place, ms_trace, ms_depth; /* device time (HIP events): list + gather + index, the score kernel, trace + CIGAR, depth */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_gapped_info;
+void alga_gapped_default_params(alga_gapped_params *p);
+int  alga_place_gapped_device(alga_engine *e, const alga_nodes *nodes, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len,
+                              int32_t n_targets, const alga_placements *pl, const alga_gapped_params *p, void *hip_stream, alga_gapped *out,
+                              alga_gapped_info *info /* may be NULL */);
+int  alga_write_gapped_tsv_device(alga_engine *e, const alga_gapped *gapped, const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
