@@ -182,6 +182,7 @@ def _finish(found, lens, pl, targets, E, info):
         cigar_off.append(len(cigar))
     out["cigar_off"], out["cigar"] = np.array(cigar_off, dtype=np.uint32), np.array(cigar, dtype=np.uint32)
     out["info"] = {k_: int(v) for k_, v in info.items()}
+    out["found"] = [[x[:7] for x in f] for f in found]                 # every placement found, (d, strand, t, p, e, j, q): no result, for the tests' own questions
     return out
 
 
