@@ -141,7 +141,7 @@ int gapped_impl(alga_engine *e, const alga_nodes *nodes, const uint32_t *d_words
     HIP_TRY(e, hipMemcpyAsync(hc, cnt, GP_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
 
-    e->gp_valid = true; e->gp_reads = R; e->gp_targets = T; e->gp_columns = columns; e->gp_ncigar = n_cigar;
+    e->gp_valid = true; e->gp_reads = R; e->gp_targets = T; e->gp_columns = columns; e->gp_ncigar = n_cigar; e->gp_pl_serial = e->pl_serial;
     out->n_reads = (int64_t) R; out->n_targets = (int64_t) T; out->n_columns = columns; out->n_cigar = n_cigar;
     out->d_target = go.target; out->d_pos = go.pos; out->d_end = go.end; out->d_edits = go.edits; out->d_state = go.state;
     out->d_cigar_off = cig_off; out->d_cigar = (const uint32_t *) e->gp_cigar.p; out->d_cover = cover;

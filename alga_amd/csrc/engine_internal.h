@@ -241,6 +241,19 @@ struct alga_engine {
     DevBuf      gp_target, gp_rpos, gp_end, gp_edits, gp_state, gp_cigoff, gp_cigar, gp_cover, gp_tstat;
     bool        gp_valid = false;                  // the result buffers hold a gapped placement
     uint64_t    gp_reads = 0, gp_targets = 0, gp_columns = 0, gp_ncigar = 0;   // ... of this many reads, targets and columns; its runs
+    uint64_t    gp_pl_serial = 0;                  // ... made from this placement result
+    // the placed targets voted by the Hamming-placed and the gapped reads together (engine_ipolish.hip).  Workspaces: counters, the H voters'
+    // (first column, node) pairs before and after the sort and what the polish's vote kernels write beside their counts, the four counts and the
+    // `-` votes per column, the difference array of the span and its scan, the insertion votes (key, slot) before and after their two sorts, the
+    // winner / its votes / all votes per slot, width / events / verdict per old column and the scan of the events.  The result, twice, as for
+    // the grow
+    DevBuf      ip_cnt, ip_keys[2], ip_vals[2], ip_marks, ip_pop, ip_pwords, ip_ptstat, ip_counts4, ip_del, ip_diff, ip_scan, ip_ikey[2], ip_islot[2], ip_winkey,
+                ip_winvotes, ip_insall, ip_width, ip_evn, ip_evoff, ip_code;
+    struct IpolishSet { DevBuf len, coloff, begin, words, newcol, evcol, evkind, evlen, evbases, evvotes, evcover, tstat, counts, span, oldoff; } ip_set[2];
+    int         ip_cur = 0;                        // the set that holds the result
+    int         opt_ipolish_max_blocks = 8192;     // option "ipolish_max_blocks": the cap of the k_ip_* grids (tests make every grid-stride loop take further passes)
+    bool        ip_valid = false;
+    uint64_t    ip_targets = 0, ip_columns = 0, ip_columns_before = 0, ip_events = 0, ip_longest = 0;   // ... of this many targets, new and old columns, events; the longest new target
     // seed-bucket-sharded N-GPU build (engine_shard.hip): state between its phases (the exchanges in between are the caller's)
     DevBuf      sh_keys[2], sh_vals[2], sh_store, sh_dir, sh_desc_out, sh_dkey[2], sh_dval[2], sh_small_top, sh_pending, sh_bitmap, sh_small_out,
                 sh_ssrc[2], sh_skey[2], sh_edges_out, sh_deg, sh_rowptr, sh_cursor, sh_edges, sh_flagged, sh_cnt, sh_gflag, sh_gpos, sh_gstart;

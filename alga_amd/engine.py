@@ -184,7 +184,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device",
            "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device",
            "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device",
-           "alga_gapped_default_params", "alga_place_gapped_device", "alga_write_gapped_tsv_device"]
+           "alga_gapped_default_params", "alga_place_gapped_device", "alga_write_gapped_tsv_device",
+           "alga_ipolish_default_params", "alga_polish_indels_device", "alga_write_ipolished_fasta_device", "alga_write_ipolish_events_tsv_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -844,6 +845,71 @@ def cigar_strings(h):
     return ["".join("%d%s" % (int(x) >> 2, "MID"[int(x) & 3]) for x in h["cigar"][int(off[r]):int(off[r + 1])]) for r in range(len(off) - 1)]
 
 
+IPOLISH_COUNTS = 1                                               # alga_ipolish_params.flags
+IPOLISH_MAX_INS = 13                                             # ALGA_IPOLISH_MAX_INS
+EVENT_S, EVENT_I, EVENT_D = 0, 1, 2                              # IndelPolished.ev_kind
+
+
+class IpolishParams(C.Structure):
+    """alga_ipolish_params"""
+    _fields_ = [(k, C.c_int32) for k in ("min_cover", "min_percent", "max_ins", "flags")] + [("reserved", C.c_int32 * 4)]
+
+
+class IpolishInfo(C.Structure):
+    """alga_ipolish_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("columns", "voters_hamming", "voters_gapped", "votes", "del_votes", "ins_votes", "ins_too_long", "ins_edge", "shifted_runs",
+                                          "shifted_bases", "voted_columns", "substituted", "deleted", "inserted_slots", "inserted_bases", "ambiguous_columns",
+                                          "ambiguous_slots", "columns_after", "max_cover")] + \
+               [(k, C.c_double) for k in ("ms_votes", "ms_inserts", "ms_build", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class IpolishedC(C.Structure):
+    """alga_ipolished"""
+    _fields_ = [("n_targets", C.c_int64), ("n_columns_before", C.c_uint64), ("n_columns", C.c_uint64), ("n_events", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_len", "d_col_off", "d_begin", "d_words", "d_new_col", "d_ev_col", "d_ev_kind", "d_ev_len", "d_ev_bases", "d_ev_votes",
+                                          "d_ev_cover", "d_t_subs", "d_t_dels", "d_t_ins_bases", "d_t_ambiguous", "d_counts", "d_span")]
+
+
+class IndelPolished:
+    """Result of Engine.polish_indels: zero-copy torch views of the engine's device memory (valid until the next Engine.polish_indels call but
+    one on that engine -- the result is double-buffered; clone what has to live longer) -- len int32 [n_targets], col_off int32 [n_targets + 1]
+    (the bits of uint32), begin int64 [n_targets], words int32 [(n_columns + 15) / 16 + 2], new_col int32 [n_columns_before + 1]; the events
+    ev_col / ev_bases / ev_votes / ev_cover int32 and ev_kind / ev_len uint8 [n_events]; t_subs / t_dels / t_ins_bases / t_ambiguous int64
+    [n_targets]; counts int32 [n_columns_before, 5] and span int32 [n_columns_before] or None -- and .info (dict of alga_ipolish_info)."""
+    KEYS = (("len", "<i4", np.int32, "t"), ("col_off", "<i4", np.uint32, "t1"), ("begin", "<i8", np.uint64, "t"), ("words", "<i4", np.uint32, "w"),
+            ("new_col", "<i4", np.uint32, "g1"), ("ev_col", "<i4", np.uint32, "e"), ("ev_kind", "|u1", np.uint8, "e"), ("ev_len", "|u1", np.uint8, "e"),
+            ("ev_bases", "<i4", np.uint32, "e"), ("ev_votes", "<i4", np.uint32, "e"), ("ev_cover", "<i4", np.uint32, "e"), ("t_subs", "<i8", np.uint64, "t"),
+            ("t_dels", "<i8", np.uint64, "t"), ("t_ins_bases", "<i8", np.uint64, "t"), ("t_ambiguous", "<i8", np.uint64, "t"))
+
+    def __init__(self, c, info, device, source=None):
+        self._c, self.info, self._source = c, info, source
+        self.n_targets, self.n_columns_before, self.n_columns, self.n_events = int(c.n_targets), int(c.n_columns_before), int(c.n_columns), int(c.n_events)
+        dev = "cuda:%d" % device
+        size = dict(t=self.n_targets, t1=self.n_targets + 1, w=(self.n_columns + 15) // 16 + 2, g1=self.n_columns_before + 1, e=self.n_events)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+        self.counts = device_view(c.d_counts, (self.n_columns_before, 5), dev, "<i4") if c.d_counts else None
+        self.span = device_view(c.d_span, (self.n_columns_before,), dev, "<i4") if c.d_span else None
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/ipolish_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        if self.counts is not None:
+            d["counts"] = self.counts.cpu().numpy().copy().view(np.uint32)
+            d["span"] = self.span.cpu().numpy().copy().view(np.uint32)
+        d["info"] = dict(self.info)
+        return d
+
+    @property
+    def targets(self):
+        """(words, begin int64 [n_targets], len int32 [n_targets]): the new targets as the ragged target set Engine.place_reads(targets=...)
+        takes (the tensors are the engine's)"""
+        return self.words, self.begin, self.len
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libalga_amd.so")
 
@@ -1013,6 +1079,12 @@ def load_library():
     lib.alga_place_gapped_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PlacementsC), C.POINTER(GappedParams),
                                              C.c_void_p, C.POINTER(GappedC), C.POINTER(GappedInfo)]
     lib.alga_write_gapped_tsv_device.argtypes = [C.c_void_p, C.POINTER(GappedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_ipolish_default_params.argtypes = [C.POINTER(IpolishParams)]
+    lib.alga_ipolish_default_params.restype = None
+    lib.alga_polish_indels_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(PlacementsC), C.POINTER(GappedC), C.POINTER(IpolishParams), C.c_void_p,
+                                              C.POINTER(IpolishedC), C.POINTER(IpolishInfo)]
+    lib.alga_write_ipolished_fasta_device.argtypes = [C.c_void_p, C.POINTER(IpolishedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_write_ipolish_events_tsv_device.argtypes = [C.c_void_p, C.POINTER(IpolishedC), C.c_char_p, C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -2171,6 +2243,47 @@ class Engine:
         lines): `read target pos end strand edits unique cigar` (tabs) per gapped-placed read, in read order."""
         info = GfaInfo()
         self._check(self._lib.alga_write_gapped_tsv_device(self._h, C.byref(gapped._c), os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    def polish_indels(self, words, lens, placements, gapped, min_cover=3, min_percent=60, max_ins=6, counts=False, stream=None):
+        """The placed targets voted by the Hamming-placed and the gapped reads together (alga_polish_indels_device) -> IndelPolished: columns
+        substituted or deleted, strings of at most max_ins bases inserted between two columns, the new targets.  words / lens: the node set
+        that was placed; placements: the result of the LAST Engine.place_reads call; gapped: the result of the LAST Engine.place_gapped call,
+        made from those placements.  counts: keep the five counts per column and the span per slot.  A further round is a placement on
+        IndelPolished.targets."""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        pp, out, info = IpolishParams(), IpolishedC(), IpolishInfo()
+        pp.min_cover, pp.min_percent, pp.max_ins, pp.flags = int(min_cover), int(min_percent), int(max_ins), IPOLISH_COUNTS if counts else 0
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_polish_indels_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(gapped._c), C.byref(pp), st, C.byref(out), C.byref(info)))
+        return IndelPolished(out, info.as_dict(), self.device, (placements, gapped))
+
+    def write_ipolished_fasta(self, path, ipolished):
+        """The new targets of the LAST Engine.polish_indels call as FASTA (alga_write_ipolished_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>contig_id=<t>_length=<len>_subs=<s>_ins=<i>_dels=<d>` per target with a length."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_ipolished_fasta_device(self._h, C.byref(ipolished._c), os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
+    def write_ipolish_events_tsv(self, path, ipolished):
+        """The events of the LAST Engine.polish_indels call as text (alga_write_ipolish_events_tsv_device) -> dict of alga_gfa_info (segments =
+        lines): `contig pos kind len old new votes cover` (tabs) per event, pos the old position inside the contig."""
+        info = GfaInfo()
+        self._check(self._lib.alga_write_ipolish_events_tsv_device(self._h, C.byref(ipolished._c), os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
     def write_graph(self, path, n_nodes, edges):

@@ -102,6 +102,12 @@
 // --gapped=1): one line `read target pos end strand edits unique cigar` per gapped-placed read, tab separated, formatted on the device
 // (alga_write_gapped_tsv_device).  One line on stderr gives tried / placed / unique / with indel / edits.  It changes no other output: the depth
 // headers and --placements= are the Hamming placement's.  Neither is passed through.
+// --polish_indels=1 (default 0; needs --gapped=1): the final contigs voted by the Hamming-placed and the gapped reads together
+// (alga_polish_indels_device: --polish_max_ins= (6, 1 .. 13)): columns substituted or deleted, strings inserted, contigs that change length.
+// --ipolished=PATH: the new contigs, `>contig_id=<t>_length=<len>_subs=<s>_ins=<i>_dels=<d>` (alga_write_ipolished_fasta_device);
+// --ipolish_events=PATH: one line `contig pos kind len old new votes cover` per event, tab separated (alga_write_ipolish_events_tsv_device); both
+// need --polish_indels=1.  One line on stderr gives voters / substituted / deleted / inserted / ambiguous / columns before -> after.  Like
+// --gapped it changes no other output.  None is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -131,7 +137,8 @@ static const char *USAGE =
     "         [--grow_ends=N] [--grown=grown.fasta] [--grow_layout=grow.tsv] [--grow_min_anchor=63] [--grow_max_mismatches=2] [--grow_min_cover=3]\n"
     "         [--grow_min_percent=80] [--grow_max=64]\n"
     "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n"
-    "         [--gapped=0|1] [--gapped_edits=6] [--gapped_placements=gapped.tsv]\n";
+    "         [--gapped=0|1] [--gapped_edits=6] [--gapped_placements=gapped.tsv]\n"
+    "         [--polish_indels=0|1] [--polish_max_ins=6] [--ipolished=ipolished.fasta] [--ipolish_events=events.tsv]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -163,6 +170,8 @@ int main(int argc, char **argv) {
     int merge_ends = 0;
     int gapped = 0, gapped_edits = -1;
     std::string gapped_placements;
+    int polish_indels = 0, polish_max_ins = -1;
+    std::string ipolished, ipolish_events;
     std::string merged_path, merge_layout;
     alga_merge_params mgp;
     alga_merge_default_params(&mgp);
@@ -224,6 +233,10 @@ int main(int argc, char **argv) {
         else if (opt(a, "--gapped_placements", v)) gapped_placements = v;
         else if (opt(a, "--gapped_edits", v)) gapped_edits = atoi(v.c_str());
         else if (opt(a, "--gapped", v)) gapped = atoi(v.c_str());
+        else if (opt(a, "--polish_indels", v)) polish_indels = atoi(v.c_str());
+        else if (opt(a, "--polish_max_ins", v)) polish_max_ins = atoi(v.c_str());
+        else if (opt(a, "--ipolished", v)) ipolished = v;
+        else if (opt(a, "--ipolish_events", v)) ipolish_events = v;
         else if (opt(a, "--merged", v)) merged_path = v;
         else if (opt(a, "--merge_layout", v)) merge_layout = v;
         else if (opt(a, "--merge_min_overlap", v)) mgp.min_overlap = atoi(v.c_str());
@@ -280,6 +293,14 @@ int main(int argc, char **argv) {
     if (gapped && contigs_final.empty()) { fprintf(stderr, "alga_hip: --gapped=1 needs --contigs_final=\n"); return 2; }
     if (!gapped && (!gapped_placements.empty() || gapped_edits != -1)) { fprintf(stderr, "alga_hip: --gapped_placements= and --gapped_edits= need --gapped=1\n"); return 2; }
     if (gapped && gapped_edits != -1 && (gapped_edits < 1 || gapped_edits > 15)) { fprintf(stderr, "alga_hip: --gapped_edits must be in [1, 15] (got %d)\n", gapped_edits); return 2; }
+    if (polish_indels != 0 && polish_indels != 1) { fprintf(stderr, "alga_hip: --polish_indels must be 0 or 1 (got %d)\n", polish_indels); return 2; }
+    if (polish_indels && !gapped) { fprintf(stderr, "alga_hip: --polish_indels=1 needs --gapped=1\n"); return 2; }
+    if (!polish_indels && (!ipolished.empty() || !ipolish_events.empty() || polish_max_ins != -1)) {
+        fprintf(stderr, "alga_hip: --ipolished=, --ipolish_events= and --polish_max_ins= need --polish_indels=1\n"); return 2;
+    }
+    if (polish_indels && polish_max_ins != -1 && (polish_max_ins < 1 || polish_max_ins > ALGA_IPOLISH_MAX_INS)) {
+        fprintf(stderr, "alga_hip: --polish_max_ins must be in [1, 13] (got %d)\n", polish_max_ins); return 2;
+    }
     if (merge_ends != 0 && merge_ends != 1) { fprintf(stderr, "alga_hip: --merge_ends must be 0 or 1 (got %d)\n", merge_ends); return 2; }
     if (merge_ends && !grow_ends) { fprintf(stderr, "alga_hip: --merge_ends=1 needs --grow_ends >= 1\n"); return 2; }
     if (!merge_ends && (!merged_path.empty() || !merge_layout.empty())) { fprintf(stderr, "alga_hip: --merged= and --merge_layout= need --merge_ends=1\n"); return 2; }
@@ -659,6 +680,24 @@ int main(int argc, char **argv) {
                                     gi.ms_index, gi.ms_place, gi.ms_trace, gi.ms_depth, gi.ms_total);
                         alga_gfa_info gti;
                         if (rc == ALGA_OK && !gapped_placements.empty()) rc = alga_write_gapped_tsv_device(engine, &gp, gapped_placements.c_str(), &gti);
+                        if (rc == ALGA_OK && polish_indels) {
+                            alga_ipolish_params iq;
+                            alga_ipolish_default_params(&iq);
+                            if (polish_max_ins != -1) iq.max_ins = polish_max_ins;
+                            alga_ipolished ipo;
+                            alga_ipolish_info ii;
+                            rc = alga_polish_indels_device(engine, &pnd, &pl, &gp, &iq, nullptr, &ipo, &ii);
+                            if (rc == ALGA_OK)
+                                fprintf(stderr, "Final contigs polished with the gapped reads (cover %d, %d %%, insertions up to %d): %llu + %llu voters, %llu substituted, %llu deleted, "
+                                        "%llu inserted in %llu slots, %llu + %llu ambiguous, columns %llu -> %llu; device ms: votes %.3f inserts %.3f build %.3f, call %.1f ms wall\n",
+                                        iq.min_cover, iq.min_percent, iq.max_ins, (unsigned long long) ii.voters_hamming, (unsigned long long) ii.voters_gapped,
+                                        (unsigned long long) ii.substituted, (unsigned long long) ii.deleted, (unsigned long long) ii.inserted_bases,
+                                        (unsigned long long) ii.inserted_slots, (unsigned long long) ii.ambiguous_columns, (unsigned long long) ii.ambiguous_slots,
+                                        (unsigned long long) ii.columns, (unsigned long long) ii.columns_after, ii.ms_votes, ii.ms_inserts, ii.ms_build, ii.ms_total);
+                            alga_gfa_info iti;
+                            if (rc == ALGA_OK && !ipolished.empty()) rc = alga_write_ipolished_fasta_device(engine, &ipo, ipolished.c_str(), &iti);
+                            if (rc == ALGA_OK && !ipolish_events.empty()) rc = alga_write_ipolish_events_tsv_device(engine, &ipo, ipolish_events.c_str(), &iti);
+                        }
                         alga_device_free(engine, d_tb);
                         alga_device_free(engine, d_tl);
                     }

@@ -1788,6 +1788,101 @@ int  alga_place_gapped_device(alga_engine *e, const alga_nodes *nodes, const uin
                               alga_gapped_info *info /* may be NULL */);
 int  alga_write_gapped_tsv_device(alga_engine *e, const alga_gapped *gapped, const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- polish with the gapped reads: indel votes, targets that change length (alga_amd/csrc/ipolish_kernels.hip, engine_ipolish.hip) --------
+ * alga_polish_placed_device repairs substitutions only: at a column where a target has a base too many or too few the Hamming pass places no
+ * read.  Here the Hamming-placed and the gapped reads vote together, on every column (a base, or "delete this column") and on every slot
+ * between two columns ("insert these bases"); the result is a new target set whose lengths may differ.  Integers only, free of any order
+ * (thread, sort); tests/ipolish_checker.py states the rule twice in Python and the device result equals it array for array.
+ *
+ * Inputs: the node set that was placed (twin layout); `pl`, the engine's current placement result; `gp`, the engine's current gapped result,
+ * made from that placement; alga_ipolish_params: min_cover 1 .. 2^31 - 1 (default 3), min_percent 1 .. 100 (60), max_ins 1 .. 13 (6), flags
+ * 0 or ALGA_IPOLISH_COUNTS, reserved 0; anything else answers ALGA_ERR_INVALID_ARGUMENT.  The current bases `t` come from the column array
+ * the placement call kept (column g = col_off[target] + index), never from the caller.
+ *
+ *   1. Voters.  H voter: read r with ALGA_PLACE_UNIQUE in pl; node v = 2r if MINUS else 2r + 1; its script is one M run of len[v] columns
+ *      from column col_off[target] + pos.  G voter: read r with ALGA_GAPPED_UNIQUE in gp; v = 2r if ALGA_GAPPED_MINUS else 2r + 1; its script
+ *      is gp.d_cigar[d_cigar_off[r] .. d_cigar_off[r + 1]) from column col_off[gp.d_target[r]] + gp.d_pos[r] on, in target orientation over the
+ *      bases of v.  The two sets are disjoint (the gapped pass touches only reads the Hamming pass left unplaced).
+ *   2. Normalisation of a G script.  This is a DEFINITION of where a gap votes, not a claim that the result is the leftmost form.  Every gap
+ *      run that is neither the first nor the last run of its script is shifted left; the shifts are found on the script's ORIGINAL runs.  m =
+ *      the length of the M run directly in front of the gap, 0 if that run is not M.  A D run over columns [c, c + n) moves by the largest
+ *      s <= m with t[c - j] == t[c + n - j] for all 1 <= j <= s.  An I run of read bases v[a .. a + n) before column c moves by the largest
+ *      s <= m with v[a - j] == v[a + n - j] for all 1 <= j <= s and becomes v[a - s .. a - s + n) before column c - s (the string rotates).
+ *      The M run in front shrinks by s; the s cells the gap passed over are M cells directly behind it (they join a following M run; behind
+ *      a gap followed by another gap they stand between the two).  A gap never leaves its own M run, so the events keep their order; [p, e)
+ *      and the read's bases are unchanged.
+ *   3. Votes, after rule 2.  An M cell: one vote for the read base at its column, count[g][b].  A D cell: one vote into del[g].  An inner I run
+ *      of n <= max_ins bases before column c: one vote for (n, string) at slot c, key n << 26 | string, the first base in the highest used
+ *      bits.  An inner I run longer than max_ins adds only to long_ins[c].  An I run that is the first or last run of its script votes nothing
+ *      (an overhang over a target end: the grow stage's business).  A voter over [p, e) adds one to span[c] for every slot c with p < c < e.
+ *      Slot c is the place between columns c - 1 and c of one target; a target's first column has no slot.
+ *      cover[g] = sum_b count[g][b] + del[g] (== gp.d_cover[g] where the placement's depth counts the UNIQUE reads).
+ *   4. Column decision.  Candidates A, C, G, T and `-` (votes del[g]).  The winner w has the most votes; a tie goes to cur if it is among the
+ *      tied, else to the smallest of A < C < G < T < `-`.  The column CHANGES iff w != cur, cover >= min_cover and 100 * votes[w] >=
+ *      min_percent * cover (64-bit products): substituted if w is a base, deleted if w is `-`.  AMBIGUOUS iff w != cur, cover >= min_cover and
+ *      the percentage test fails.  With no G voter this is rule 3 of the polish, bit for bit.
+ *   5. Slot decision.  The winner w is the (n, string) with the most votes at the slot, a tie goes to the smallest key.  INSERTED iff
+ *      span[c] >= min_cover and 100 * votes[w] >= min_percent * span[c].  AMBIGUOUS iff span[c] >= min_cover, not inserted, and 100 * (all
+ *      insertion votes at c, the long ones included) >= min_percent * span[c].  Column and slot decisions are independent.
+ *   6. New targets.  Target t from its columns in order: first the string of the column's slot if INSERTED, then the column unless DELETED,
+ *      with its new base if substituted.  Result (alga_ipolished; engine-owned, double-buffered: a call writes the set that is not the current
+ *      one and swaps it in at its end, so a call that fails anywhere leaves the earlier result valid): n_targets, n_columns_before,
+ *      n_columns; d_len, d_col_off [T + 1], d_begin (== col_off), d_words (the result's own copy, 16 columns a word, two zero words of padding,
+ *      the bits past n_columns zero) -- (d_words, d_begin, d_len, n_targets) is a target set as alga_place_reads_device takes it;
+ *      d_new_col [n_columns_before + 1]: the new column of each old column (a deleted column: the index of the next kept one; the last entry
+ *      n_columns); the events, n_events, ascending by old column, an insertion before the column's own event: d_ev_col, d_ev_kind (0 S, 1 I,
+ *      2 D), d_ev_len (S 1, D 1, I n), d_ev_bases (S old | new << 2, D old, I the string), d_ev_votes, d_ev_cover (cover, for I span); per
+ *      target d_t_subs, d_t_dels, d_t_ins_bases, d_t_ambiguous (columns and slots); with ALGA_IPOLISH_COUNTS d_counts uint32
+ *      [5 * n_columns_before] (A C G T - per column) and d_span uint32 [n_columns_before], else both NULL.  ALGA_ERR_CAPACITY where the new
+ *      targets hold more than 2^32 - 2 bases or one is longer than 2^31 - 1.
+ *   7. Counters (alga_ipolish_info): columns, voters_hamming, voters_gapped, votes (M cells), del_votes (D cells), ins_votes (inner I runs
+ *      that vote), ins_too_long, ins_edge (runs), shifted_runs, shifted_bases (sum of s), voted_columns (cover >= min_cover), substituted,
+ *      deleted, inserted_slots, inserted_bases, ambiguous_columns, ambiguous_slots, columns_after, max_cover; ms_votes, ms_inserts, ms_build
+ *      (HIP events), ms_total (wall).
+ *   8. Refusals, all before anything of the result is written (ALGA_ERR_INVALID_ARGUMENT).  Host: `pl` is not the current placement; `gp` is
+ *      not the engine's current gapped result or was made from an earlier placement; nodes->n / 2 != pl.n_reads; the parameters.  Device, one
+ *      read-back: the twin property; an H voter's length above the stride, target out of range, pos < 0, pos + len > len[target]; a G
+ *      voter whose script's read length differs from len[v], whose column length differs from end - pos, that does not lie inside its target,
+ *      or that has no run, more than 31 runs or an op that is none of M, I, D.  The vote kernels rely on these checks and on nothing else.
+ * Read-backs: the checks with the insertion votes; the new column and event counts; the counters.
+ *
+ * alga_write_ipolished_fasta_device: `>contig_id=<t>_length=<len>_subs=<s>_ins=<i>_dels=<d>` and the new sequence, one record per target with
+ * a length.  alga_write_ipolish_events_tsv_device: one line per event, `contig pos kind len old new votes cover` separated by tabs; pos is the
+ * OLD position inside the contig, kind S / I / D, old and new as letters with `-` where there is none (I: old `-`, new the string; D: new `-`).
+ * Both are formatted on the device; `ipol` must be the engine's current result of this stage.  ABI stays 7: the calls add. */
+#define ALGA_IPOLISH_COUNTS 1        /* alga_ipolish_params.flags                                                                      */
+#define ALGA_IPOLISH_MAX_INS 13
+typedef struct {
+    int32_t min_cover, min_percent, max_ins, flags;
+    int32_t reserved[4];             /* 0                                                                                             */
+} alga_ipolish_params;
+typedef struct {
+    int64_t         n_targets;
+    uint64_t        n_columns_before, n_columns, n_events;
+    const int32_t  *d_len;           /* n_targets                                                                                     */
+    const uint32_t *d_col_off;       /* n_targets + 1                                                                                 */
+    const uint64_t *d_begin;         /* n_targets                                                                                     */
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+    const uint32_t *d_new_col;       /* n_columns_before + 1                                                                          */
+    const uint32_t *d_ev_col;        /* n_events, as are the next five                                                                */
+    const uint8_t  *d_ev_kind, *d_ev_len;
+    const uint32_t *d_ev_bases, *d_ev_votes, *d_ev_cover;
+    const uint64_t *d_t_subs, *d_t_dels, *d_t_ins_bases, *d_t_ambiguous;   /* n_targets                                               */
+    const uint32_t *d_counts;        /* 5 * n_columns_before, or NULL                                                                 */
+    const uint32_t *d_span;          /* n_columns_before, or NULL                                                                     */
+} alga_ipolished;
+typedef struct {
+    uint64_t columns, voters_hamming, voters_gapped, votes, del_votes, ins_votes, ins_too_long, ins_edge, shifted_runs, shifted_bases, voted_columns, substituted,
+             deleted, inserted_slots, inserted_bases, ambiguous_columns, ambiguous_slots, columns_after, max_cover;
+    double   ms_votes, ms_inserts, ms_build;         /* device time (HIP events): checks' follow-up + all votes + span, the insertion votes' sorts and winners, decision + build */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_ipolish_info;
+void alga_ipolish_default_params(alga_ipolish_params *p);
+int  alga_polish_indels_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_gapped *gp, const alga_ipolish_params *p,
+                               void *hip_stream, alga_ipolished *out, alga_ipolish_info *info /* may be NULL */);
+int  alga_write_ipolished_fasta_device(alga_engine *e, const alga_ipolished *ipol, const char *path, alga_gfa_info *info /* may be NULL */);
+int  alga_write_ipolish_events_tsv_device(alga_engine *e, const alga_ipolished *ipol, const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
