@@ -809,6 +809,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
     } else if (!strcmp(name, "ipolish_max_blocks")) {
         if (value < 1 || value > 8192) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option ipolish_max_blocks: 1 .. 8192");
         e->opt_ipolish_max_blocks = (int) value;
+    } else if (!strcmp(name, "merge_max_blocks")) {
+        if (value < 1 || value > 8192) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option merge_max_blocks: 1 .. 8192");
+        e->opt_merge_max_blocks = (int) value;
     } else if (!strcmp(name, "auto_reduction_per_target")) {
         e->opt_force_per_target = value != 0;
     } else return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unknown option");

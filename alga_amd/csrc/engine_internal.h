@@ -232,6 +232,7 @@ struct alga_engine {
     DevBuf      mg_cnt, mg_elen, mg_epad, mg_eoff, mg_ecols, mg_pcols, mg_join, mg_lists[2], mg_head, mg_first, mg_scan;
     struct MergeSet { DevBuf partner, olen, mm, hits, estate, merged, rank, orient, start, ovafter, moff, mmembers, len, coloff, begin, words; } mg_set[2];
     int         mg_cur = 0;                        // the set that holds the result
+    int         opt_merge_max_blocks = 8192;       // option "merge_max_blocks": the cap of the k_mg_* grids (tests make every grid-stride loop take further passes)
     bool        mg_valid = false;
     uint64_t    mg_targets = 0, mg_merged = 0, mg_columns = 0, mg_longest = 0;   // ... of this many targets, merged contigs and columns; the longest merged contig
     // the unplaced reads laid with indels (engine_gapped.hip).  Workspaces: counters, the participation flags, their scan and the list, this

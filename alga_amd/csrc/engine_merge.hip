@@ -50,7 +50,7 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     if ((rc = alga_ensure(e, e->mg_cnt, MG_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->mg_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, MG_COUNTERS * sizeof(unsigned long long), s));
-    const MgTargets tg{d_words, d_begin, d_len, (uint32_t) T};
+    const MgTargets tg{d_words, d_begin, d_len, (uint32_t) T, (uint32_t) e->opt_merge_max_blocks};
 
     // the check: nothing of the result is written before its verdict
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
@@ -111,7 +111,7 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     if ((rc = alga_check_launch(e, "k_mg_overlap"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 
-    launch_mg_joins(eo, (uint32_t) E, join, s);
+    launch_mg_joins(eo, (uint32_t) E, join, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_mg_joins"))) return rc;
     // the lists over the 2T states: after this many doublings a jump is longer than any path
     int rounds = 1;
@@ -123,14 +123,14 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
         set[j].nxt = (uint32_t *) (set[j].wsum + E + 2); set[j].aux = set[j].nxt + E; set[j].tail = set[j].aux + E;
     }
     int cur = 0;
-    launch_mg_cycle_init(join, (uint32_t) E, set[0], s);
-    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_cycle_jump((uint32_t) E, set[cur], set[cur ^ 1], s);
+    launch_mg_cycle_init(join, (uint32_t) E, set[0], tg.max_blocks, s);
+    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_cycle_jump((uint32_t) E, set[cur], set[cur ^ 1], tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_mg_cycle_jump"))) return rc;
-    launch_mg_cycle_drop(set[cur], (uint32_t) T, join, eo.state, cnt, s);
+    launch_mg_cycle_drop(set[cur], (uint32_t) T, join, eo.state, cnt, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_mg_cycle_drop"))) return rc;
     cur = 0;
     launch_mg_rank_init(tg, join, eo.olen, set[0], s);
-    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_rank_jump((uint32_t) E, set[cur], set[cur ^ 1], s);
+    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_rank_jump((uint32_t) E, set[cur], set[cur ^ 1], tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_mg_rank_jump"))) return rc;
 
     uint32_t *first = (uint32_t *) e->mg_first.p, *members = first + T + 2, *first_scan = (uint32_t *) e->mg_scan.p, *members_scan = first_scan + T + 2;

@@ -22,6 +22,7 @@ struct MgTargets {
     const unsigned long long *begin;  // T: base index of the first base
     const int32_t *len;               // T
     uint32_t T;
+    uint32_t max_blocks;              // the cap of every grid here but k_mg_overlap's and the FASTA kernels' (8192; option "merge_max_blocks")
 };
 // the 2T end sequences in a column space of their own, the space their index is built over (alga_seed_index): end x is the columns
 // off[x] .. off[x] + len[x] (len[x] = W_x), off[x] a multiple of 16; cols holds E_x, the contig end at the right; n = 2T
@@ -57,14 +58,14 @@ void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32
 void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
                        unsigned long long *counters, hipStream_t s);
 // one thread per end: join[x] = the end x is joined with, MG_NONE without; JOINED into the end's state
-void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, hipStream_t s);
+void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, uint32_t max_blocks, hipStream_t s);
 // pointer jumping over the 2T states with the smallest contig id riding along; the smallest contig of a cycle drops the join at its left end
-void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, hipStream_t s);
-void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s);
-void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, hipStream_t s);
+void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, uint32_t max_blocks, hipStream_t s);
+void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s);
+void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
 // the same jumps over the paths that are left: states, len - overlap and the last state to the end of the path
 void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const MgLists &l, hipStream_t s);
-void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s);
+void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s);
 // per contig: rank, orientation, start, overlap_after; head / first / members (T + 1 entries of the last two) for the scans; the join counters
 void launch_mg_place(const MgTargets &t, const MgLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
                      unsigned long long *counters, hipStream_t s);

@@ -22,7 +22,8 @@
 //   k_mg_build        every output word gathered by one lane: a column finds its member by bisection over the starts, an overlapped column is
 //                     the earlier contig's; minus-oriented members complemented and mirrored
 //   k_mg_fasta_sizes / k_mg_fasta_write   one record per merged contig, one wave per record
-// No LDS.  Block 256 and the grid caps are picked, not tuned.
+// No LDS.  Block 256 and the grid caps are picked, not tuned; MgTargets::max_blocks lowers the cap of every grid that goes through mg_grid
+// (option "merge_max_blocks": a knob of the tests, which make every grid-stride loop here take further passes).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -345,7 +346,7 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_fasta_write(MgFasta f, const un
     text_write_body<MgRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned mg_grid(uint64_t items, uint64_t cap = 8192) {
+inline unsigned mg_grid(uint64_t items, uint64_t cap) {                  // cap: MgTargets::max_blocks, 8192 unless a test lowers it
     const uint64_t g = (items + MG_BLOCK - 1) / MG_BLOCK;
     return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
 }
@@ -353,15 +354,15 @@ inline unsigned mg_grid(uint64_t items, uint64_t cap = 8192) {
 }  // namespace
 
 void launch_mg_check(const MgTargets &t, unsigned long long *counters, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_mg_check, dim3(mg_grid(t.T, 4096)), dim3(MG_BLOCK), 0, s, t, counters);
+    if (t.T) hipLaunchKernelGGL(k_mg_check, dim3(mg_grid(t.T, std::min<uint64_t>(4096, t.max_blocks))), dim3(MG_BLOCK), 0, s, t, counters);
 }
 
 void launch_mg_end_lens(const MgTargets &t, int32_t max_overlap, int32_t min_overlap, int32_t k, int32_t *elen, uint32_t *epad, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_end_lens, dim3(mg_grid(2ull * t.T + 1)), dim3(MG_BLOCK), 0, s, t, max_overlap, min_overlap, k, elen, epad, counters);
+    hipLaunchKernelGGL(k_mg_end_lens, dim3(mg_grid(2ull * t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, max_overlap, min_overlap, k, elen, epad, counters);
 }
 
 void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32_t *pcols, hipStream_t s) {
-    if (e.columns) hipLaunchKernelGGL(k_mg_ends, dim3(mg_grid(e.columns >> 4)), dim3(MG_BLOCK), 0, s, t, e, ecols, pcols);
+    if (e.columns) hipLaunchKernelGGL(k_mg_ends, dim3(mg_grid(e.columns >> 4, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, e, ecols, pcols);
 }
 
 void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
@@ -369,44 +370,44 @@ void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t m
     if (e.n) hipLaunchKernelGGL(k_mg_overlap, dim3((unsigned) blocks), dim3(MG_BLOCK), 0, s, e, x, k, (uint32_t) max_mm, (uint32_t) max_occ, min_overlap, o, counters);
 }
 
-void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_joins, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, o, E, join);
+void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, uint32_t max_blocks, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_joins, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, o, E, join);
 }
 
-void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_cycle_init, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, join, E, l);
+void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, uint32_t max_blocks, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_cycle_init, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, join, E, l);
 }
 
-void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_cycle_jump, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, E, from, to);
+void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_cycle_jump, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, E, from, to);
 }
 
-void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, hipStream_t s) {
-    if (T) hipLaunchKernelGGL(k_mg_cycle_drop, dim3(mg_grid(T)), dim3(MG_BLOCK), 0, s, l, T, join, end_state, counters);
+void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
+    if (T) hipLaunchKernelGGL(k_mg_cycle_drop, dim3(mg_grid(T, max_blocks)), dim3(MG_BLOCK), 0, s, l, T, join, end_state, counters);
 }
 
 void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const MgLists &l, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_mg_rank_init, dim3(mg_grid(2ull * t.T)), dim3(MG_BLOCK), 0, s, t, join, olen, l);
+    if (t.T) hipLaunchKernelGGL(k_mg_rank_init, dim3(mg_grid(2ull * t.T, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, join, olen, l);
 }
 
-void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_rank_jump, dim3(mg_grid(E)), dim3(MG_BLOCK), 0, s, E, from, to);
+void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_mg_rank_jump, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, E, from, to);
 }
 
 void launch_mg_place(const MgTargets &t, const MgLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
                      unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_place, dim3(mg_grid((uint64_t) t.T + 1)), dim3(MG_BLOCK), 0, s, t, l, join, o, lo, head, first, members, counters);
+    hipLaunchKernelGGL(k_mg_place, dim3(mg_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, join, o, lo, head, first, members, counters);
 }
 
 void launch_mg_layout(const MgTargets &t, const MgLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
                       unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_layout, dim3(mg_grid((uint64_t) t.T + 1)), dim3(MG_BLOCK), 0, s, t, l, head, first_scan, members_scan, lo, counters);
+    hipLaunchKernelGGL(k_mg_layout, dim3(mg_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, head, first_scan, members_scan, lo, counters);
 }
 
 void launch_mg_build(const MgTargets &t, const MgLayout &lo, const uint32_t *col_off, uint32_t n_merged, uint64_t columns, uint32_t *words, unsigned long long *begin,
                      hipStream_t s) {
     const uint64_t n_words = ((columns + 15) >> 4) + 2;
-    hipLaunchKernelGGL(k_mg_build, dim3(mg_grid(std::max<uint64_t>(n_words, n_merged))), dim3(MG_BLOCK), 0, s, t, lo, col_off, n_merged, columns, words, begin);
+    hipLaunchKernelGGL(k_mg_build, dim3(mg_grid(std::max<uint64_t>(n_words, n_merged), t.max_blocks)), dim3(MG_BLOCK), 0, s, t, lo, col_off, n_merged, columns, words, begin);
 }
 
 void launch_mg_fasta_sizes(const MgFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
