@@ -9,4 +9,4 @@ from .engine import (Engine, MultiEngine, AlgaError, PrefSufParams, load_library
                      EDGE_DTYPE, PolishParams, PolishInfo, PolishedC, Polished, ScaffoldParams, ScaffoldInfo, ScaffoldsC, Scaffolds,
                      BreakParams, BreakInfo, BrokenC, Broken, GrowParams, GrowInfo, GrownC, Grown,
                      MergeParams, MergeInfo, MergedC, Merged, GappedParams, GappedInfo, GappedC, Gapped,
-                     IpolishParams, IpolishInfo, IpolishedC, IndelPolished)
+                     IpolishParams, IpolishInfo, IpolishedC, IndelPolished, PairParams, PairInfo, PairCallsC, PairCalls, SamParams)

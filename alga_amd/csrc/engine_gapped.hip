@@ -73,7 +73,7 @@ int gapped_impl(alga_engine *e, const alga_nodes *nodes, const uint32_t *d_words
     const uint64_t n_index = hc[GP_INDEX_POS], n_list = hc[GP_TRIED], skipped_long = hc[GP_SKIPPED_LONG];
 
     // from here on the result is rewritten
-    e->gp_valid = false;
+    e->gp_valid = false; e->gp_serial++;
     const size_t col_words = (size_t) ((columns + 15) >> 4) + 2;
     const int blocks = seed_blocks(n_list, e->n_cu);
     for (DevBuf *b : {&e->gp_target, &e->gp_rpos, &e->gp_end}) if ((rc = alga_ensure(e, *b, (R + 1) * sizeof(int32_t)))) return rc;

@@ -67,6 +67,7 @@ int gfa_impl(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_
     float ms = 0.0f;
     HIP_TRY(e, hipEventElapsedTime(&ms, evs.ev[0], evs.ev[1]));
     double ms_format = ms;
+    if (job.verdict && (rc = job.verdict(e->h_counters))) return rc;
     const uint64_t total = e->h_counters[GFA_COUNTERS], max_line = e->h_counters[GFA_MAX_LINE], head = strlen(job.head);
     if (info) {
         info->segments = e->h_counters[GFA_SEGMENTS]; info->links = e->h_counters[GFA_LINKS]; info->links_merged = e->h_counters[GFA_MERGED];

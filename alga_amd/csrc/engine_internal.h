@@ -243,6 +243,13 @@ struct alga_engine {
     bool        gp_valid = false;                  // the result buffers hold a gapped placement
     uint64_t    gp_reads = 0, gp_targets = 0, gp_columns = 0, gp_ncigar = 0;   // ... of this many reads, targets and columns; its runs
     uint64_t    gp_pl_serial = 0;                  // ... made from this placement result
+    uint64_t    gp_serial = 0;                     // counts the gapped results written
+    // the pair calls over both passes (engine_sam.hip).  Workspace: counters.  The result: FLAG and TLEN per read, the insert histogram
+    DevBuf      sj_cnt, sj_flag, sj_tlen, sj_hist;
+    bool        sj_valid = false;                  // the result buffers hold pair calls
+    uint64_t    sj_reads = 0, sj_nhist = 0;        // ... of this many reads, with this many bins
+    uint64_t    sj_pl_serial = 0, sj_gp_serial = 0;   // ... made from this placement and this gapped result (0: without one)
+    int         opt_sam_max_blocks = 0;            // option "sam_max_blocks": the cap of the k_sam_* grids, 0 = the launches' own (tests make the loops take further passes)
     // the placed targets voted by the Hamming-placed and the gapped reads together (engine_ipolish.hip).  Workspaces: counters, the H voters'
     // (first column, node) pairs before and after the sort and what the polish's vote kernels write beside their counts, the four counts and the
     // `-` votes per column, the difference array of the span and its scan, the insertion votes (key, slot) before and after their two sorts, the
@@ -398,6 +405,8 @@ struct AlgaTextJob {
     const char *head = "";            // the text before the first item
     // optional: what has to hold or exist before the sizes (the device's verdict on the input, tables); an error code ends the job
     std::function<int(unsigned long long *counters, hipStream_t s)> prepare;
+    // optional: the verdict on the counters the sizes pass left, as they came back (host copy); an error code ends the job before the file is touched
+    std::function<int(const unsigned long long *h_counters)> verdict;
 };
 int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info,
                       std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now());

@@ -185,7 +185,8 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device",
            "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device",
            "alga_gapped_default_params", "alga_place_gapped_device", "alga_write_gapped_tsv_device",
-           "alga_ipolish_default_params", "alga_polish_indels_device", "alga_write_ipolished_fasta_device", "alga_write_ipolish_events_tsv_device"]
+           "alga_ipolish_default_params", "alga_polish_indels_device", "alga_write_ipolished_fasta_device", "alga_write_ipolish_events_tsv_device",
+           "alga_pair_default_params", "alga_judge_pairs_device", "alga_write_sam_device"]
 
 GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa_device flags
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
@@ -845,8 +846,57 @@ def cigar_strings(h):
     return ["".join("%d%s" % (int(x) >> 2, "MID"[int(x) & 3]) for x in h["cigar"][int(off[r]):int(off[r + 1])]) for r in range(len(off) - 1)]
 
 
+SAM_NAMES_DEPTH, SAM_SKIP_UNPLACED = 1, 2                         # alga_sam_params.flags
+
+
+class PairParams(C.Structure):
+    """alga_pair_params"""
+    _fields_ = [("max_insert", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class PairInfo(C.Structure):
+    """alga_pair_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("reads", "live", "placed_h", "placed_g", "unplaced", "pairs", "pairs_proper", "pairs_improper", "pairs_split", "pairs_not_unique",
+                                          "pairs_with_gapped", "proper_with_gapped")] + \
+               [(k, C.c_int64) for k in ("insert_median", "insert_mean_x100")] + [(k, C.c_double) for k in ("ms_judge", "ms_total")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PairCallsC(C.Structure):
+    """alga_pair_calls"""
+    _fields_ = [("n_reads", C.c_int64), ("n_hist", C.c_int64), ("d_flag", C.c_void_p), ("d_tlen", C.c_void_p), ("d_insert_hist", C.c_void_p)]
+
+
+class SamParams(C.Structure):
+    """alga_sam_params"""
+    _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class PairCalls:
+    """Result of Engine.judge_pairs: zero-copy torch views of the engine's device memory (valid until the next Engine.judge_pairs call on that
+    engine; clone what has to live longer) -- flag int16 [n_reads] (the bits of uint16: the SAM FLAG), tlen int32 [n_reads], insert_hist int64
+    [max_insert + 1] -- and .info (dict of alga_pair_info)."""
+    KEYS = (("flag", "<i2", np.uint16, "r"), ("tlen", "<i4", np.int32, "r"), ("insert_hist", "<i8", np.uint64, "h"))
+
+    def __init__(self, c, info, device, source=None):
+        self._c, self.info, self._source = c, info, source
+        self.n_reads, self.n_hist = int(c.n_reads), int(c.n_hist)
+        dev = "cuda:%d" % device
+        size = dict(r=self.n_reads, h=self.n_hist)
+        for k, typestr, _, n in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
+
+    def to_host(self):
+        """numpy copies, in the dtypes of tests/sam_checker.py"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+
 IPOLISH_COUNTS = 1                                               # alga_ipolish_params.flags
-IPOLISH_MAX_INS = 13                                             # ALGA_IPOLISH_MAX_INS
+IPOLISH_MAX_INS = 13                                            # ALGA_IPOLISH_MAX_INS
 EVENT_S, EVENT_I, EVENT_D = 0, 1, 2                              # IndelPolished.ev_kind
 
 
@@ -1085,6 +1135,12 @@ def load_library():
                                               C.POINTER(IpolishedC), C.POINTER(IpolishInfo)]
     lib.alga_write_ipolished_fasta_device.argtypes = [C.c_void_p, C.POINTER(IpolishedC), C.c_char_p, C.POINTER(GfaInfo)]
     lib.alga_write_ipolish_events_tsv_device.argtypes = [C.c_void_p, C.POINTER(IpolishedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_pair_default_params.argtypes = [C.POINTER(PairParams)]
+    lib.alga_pair_default_params.restype = None
+    lib.alga_judge_pairs_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.POINTER(PlacementsC), C.POINTER(GappedC), C.POINTER(PairParams), C.c_void_p,
+                                            C.POINTER(PairCallsC), C.POINTER(PairInfo)]
+    lib.alga_write_sam_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.POINTER(PlacementsC), C.POINTER(GappedC), C.POINTER(PairCallsC), C.POINTER(SamParams), C.c_char_p,
+                                          C.POINTER(GfaInfo)]
     _LIB = lib
     return lib
 
@@ -2286,6 +2342,71 @@ class Engine:
         self._check(self._lib.alga_write_ipolish_events_tsv_device(self._h, C.byref(ipolished._c), os.fsencode(path), C.byref(info)))
         return info.as_dict()
 
+    def _placed_nodes(self, words, lens, pair_off=None):
+        """the node set of a placement as the C ABI takes it: host arrays uploaded, tensors used where they are -> (_Nodes, the tensors kept alive)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def up(x, dt, view=None):
+            if x is None or not isinstance(x, np.ndarray):
+                return x
+            a = np.ascontiguousarray(x, dtype=dt)
+            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
+        n = int(lens.shape[0])
+        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        if pair_off is not None:
+            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
+        return _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None), (words, lens, pair_off)
+
+    def judge_pairs(self, words, lens, placements, gapped=None, pair_off=None, max_insert=None, stream=None, **params):
+        """Every pair judged over the Hamming and the gapped placement together, the SAM FLAG and TLEN of every read
+        (alga_judge_pairs_device) -> PairCalls.  words / lens / pair_off: the node set that was placed and its pairing (None: no pairs);
+        placements: the result of the LAST Engine.place_reads call; gapped: the result of the LAST Engine.place_gapped call made from it, or
+        None: the Hamming pass alone.  max_insert: the library's default (1000) where not given.  params: flags, reserved (tests)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        nd, keep = self._placed_nodes(words, lens, pair_off)
+        if stream is not None:
+            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        pp, out, info = PairParams(), PairCallsC(), PairInfo()
+        self._lib.alga_pair_default_params(C.byref(pp))
+        if max_insert is not None:
+            pp.max_insert = int(max_insert)
+        for k, v in params.items():
+            if k == "flags":
+                pp.flags = int(v)
+            elif k == "reserved":
+                pp.reserved[0] = int(v)
+            else:
+                raise TypeError("Engine.judge_pairs: unknown parameter %r" % k)
+        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._lib.alga_judge_pairs_device(self._h, C.byref(nd), C.c_void_p(_ptr(keep[2]) or None), C.byref(placements._c),
+                                                      C.byref(gapped._c) if gapped is not None else None, C.byref(pp), st, C.byref(out), C.byref(info)))
+        return PairCalls(out, info.as_dict(), self.device, (placements, gapped))
+
+    def write_sam(self, path, words, lens, placements, calls, gapped=None, names_depth=False, skip_unplaced=False, **params):
+        """Every live read as a SAM record, formatted on the device (alga_write_sam_device) -> dict of alga_gfa_info (segments = records).
+        words / lens: the node set that was placed; placements / gapped: as Engine.judge_pairs was given them; calls: the result of the LAST
+        Engine.judge_pairs call.  names_depth: the @SQ names as the depth FASTA's header token (contig_id=.._length=.._reads=.._depth=..),
+        else as the plain final FASTA's; skip_unplaced: no records for unplaced reads.  QNAME is r<index>: the engine keeps no read names."""
+        import torch
+        nd, keep = self._placed_nodes(words, lens)
+        pp, info = SamParams(), GfaInfo()
+        pp.flags = (SAM_NAMES_DEPTH if names_depth else 0) | (SAM_SKIP_UNPLACED if skip_unplaced else 0)
+        for k, v in params.items():
+            if k == "flags":
+                pp.flags = int(v)
+            elif k == "reserved":
+                pp.reserved[0] = int(v)
+            else:
+                raise TypeError("Engine.write_sam: unknown parameter %r" % k)
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+        self._check(self._lib.alga_write_sam_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(gapped._c) if gapped is not None else None,
+                                                    C.byref(calls._c), C.byref(pp), os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
     def write_graph(self, path, n_nodes, edges):
         edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 3)
         rc = self._lib.alga_write_graph(path.encode(), int(n_nodes), edges.ctypes.data, len(edges))
@@ -2428,7 +2549,7 @@ def device_view(ptr, shape, device=None, typestr="<i4"):
     the buffer."""
     import torch
     if int(np.prod(shape)) == 0:
-        return torch.empty(tuple(shape), dtype={"<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8}[typestr], device=device or "cuda")
+        return torch.empty(tuple(shape), dtype={"<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8, "<i2": torch.int16}[typestr], device=device or "cuda")
     return torch.as_tensor(_DevArray(ptr, shape, typestr), device=device or "cuda")
 
 

@@ -108,6 +108,13 @@
 // --ipolish_events=PATH: one line `contig pos kind len old new votes cover` per event, tab separated (alga_write_ipolish_events_tsv_device); both
 // need --polish_indels=1.  One line on stderr gives voters / substituted / deleted / inserted / ambiguous / columns before -> after.  Like
 // --gapped it changes no other output.  None is passed through.
+// --sam=PATH (needs --contigs_final=; implies the placement): every input read as a SAM record on the final contigs, from the first placement
+// (alga_judge_pairs_device with the placement's max_insert, alga_write_sam_device; formatted on the device).  With --gapped=1 the gapped reads
+// are in it with their CIGARs and the pairs are judged over both passes; with --contigs_depth=1 the @SQ names are the depth form, the first
+// token of the headers the same run writes to --contigs_final=.  --sam_unplaced=0 (default 1; needs --sam=): no records for unplaced reads.
+// QNAME is r<read index> (the engine keeps no read names), QUAL is `*`.  One line on stderr gives pairs / proper / improper / split / not unique,
+// the pairs and proper pairs with a gapped mate and the median insert.  --sam= with --polish=1 is refused: NM and the names would describe
+// sequences the FASTA no longer holds.  It changes no other output.  Neither is passed through.
 #include <spawn.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -138,7 +145,8 @@ static const char *USAGE =
     "         [--grow_min_percent=80] [--grow_max=64]\n"
     "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n"
     "         [--gapped=0|1] [--gapped_edits=6] [--gapped_placements=gapped.tsv]\n"
-    "         [--polish_indels=0|1] [--polish_max_ins=6] [--ipolished=ipolished.fasta] [--ipolish_events=events.tsv]\n";
+    "         [--polish_indels=0|1] [--polish_max_ins=6] [--ipolished=ipolished.fasta] [--ipolish_events=events.tsv]\n"
+    "         [--sam=reads.sam] [--sam_unplaced=0|1]\n";
 
 static bool opt(const char *arg, const char *name, std::string &val) {
     size_t n = strlen(name);
@@ -172,6 +180,8 @@ int main(int argc, char **argv) {
     std::string gapped_placements;
     int polish_indels = 0, polish_max_ins = -1;
     std::string ipolished, ipolish_events;
+    std::string sam;
+    int sam_unplaced = -1;
     std::string merged_path, merge_layout;
     alga_merge_params mgp;
     alga_merge_default_params(&mgp);
@@ -237,6 +247,8 @@ int main(int argc, char **argv) {
         else if (opt(a, "--polish_max_ins", v)) polish_max_ins = atoi(v.c_str());
         else if (opt(a, "--ipolished", v)) ipolished = v;
         else if (opt(a, "--ipolish_events", v)) ipolish_events = v;
+        else if (opt(a, "--sam_unplaced", v)) sam_unplaced = atoi(v.c_str());
+        else if (opt(a, "--sam", v)) sam = v;
         else if (opt(a, "--merged", v)) merged_path = v;
         else if (opt(a, "--merge_layout", v)) merge_layout = v;
         else if (opt(a, "--merge_min_overlap", v)) mgp.min_overlap = atoi(v.c_str());
@@ -258,7 +270,7 @@ int main(int argc, char **argv) {
         // ... and --serialize / --deserialize_graph: the hand-off always goes through the dump this program writes
         const bool is_er = !strncmp(a, "--error_rate", 12) || !strncmp(a, "--error-rate", 12) || !strncmp(a, "--er=", 5);
         const bool is_ser = !strncmp(a, "--serialize", 11) || !strncmp(a, "--deserialize_graph", 19);
-        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && strncmp(a, "--break_", 8) && strncmp(a, "--broken=", 9) && strncmp(a, "--grow", 6) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
+        if (strncmp(a, "--device", 8) && strncmp(a, "--alga", 6) && strncmp(a, "--gpus", 6) && strncmp(a, "--gpu-list", 10) && strncmp(a, "--gfa=", 6) && strncmp(a, "--unitigs=", 10) && strncmp(a, "--clip_tips=", 12) && strncmp(a, "--parallel_paths=", 17) && strncmp(a, "--consensus", 11) && strncmp(a, "--contigs", 9) && strncmp(a, "--paired_extend=", 16) && strncmp(a, "--correct", 9) && strncmp(a, "--placements=", 13) && strncmp(a, "--polish", 8) && strncmp(a, "--scaffold", 10) && strncmp(a, "--break_", 8) && strncmp(a, "--broken=", 9) && strncmp(a, "--grow", 6) && strncmp(a, "--sam", 5) && !is_er && !is_ser) { passthrough.push_back(a); if (!strcmp(a, "-l")) passthrough.push_back(argv[i]); }
     }
     if (file1.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE INPUT FILE using --file1 option!\n"); return 1; }
     if (output.empty()) { fprintf(stderr, "\nERROR - PLEASE PROVIDE THE OUTPUT FILE NAME!\n"); return 1; }
@@ -301,6 +313,10 @@ int main(int argc, char **argv) {
     if (polish_indels && polish_max_ins != -1 && (polish_max_ins < 1 || polish_max_ins > ALGA_IPOLISH_MAX_INS)) {
         fprintf(stderr, "alga_hip: --polish_max_ins must be in [1, 13] (got %d)\n", polish_max_ins); return 2;
     }
+    if (!sam.empty() && contigs_final.empty()) { fprintf(stderr, "alga_hip: --sam= needs --contigs_final=\n"); return 2; }
+    if (sam.empty() && sam_unplaced != -1) { fprintf(stderr, "alga_hip: --sam_unplaced= needs --sam=\n"); return 2; }
+    if (!sam.empty() && sam_unplaced != -1 && sam_unplaced != 0 && sam_unplaced != 1) { fprintf(stderr, "alga_hip: --sam_unplaced must be 0 or 1 (got %d)\n", sam_unplaced); return 2; }
+    if (!sam.empty() && polish) { fprintf(stderr, "alga_hip: --sam= must be used without --polish=1 (its NM and names describe the unpolished contigs)\n"); return 2; }
     if (merge_ends != 0 && merge_ends != 1) { fprintf(stderr, "alga_hip: --merge_ends must be 0 or 1 (got %d)\n", merge_ends); return 2; }
     if (merge_ends && !grow_ends) { fprintf(stderr, "alga_hip: --merge_ends=1 needs --grow_ends >= 1\n"); return 2; }
     if (!merge_ends && (!merged_path.empty() || !merge_layout.empty())) { fprintf(stderr, "alga_hip: --merged= and --merge_layout= need --merge_ends=1\n"); return 2; }
@@ -599,7 +615,7 @@ int main(int argc, char **argv) {
                 alga_final_info fci;
                 alga_gfa_info ffi;
                 rc = alga_final_contigs_device(engine, &cu, &cs, min_len, contigs_new_reads_percent, contigs_trim_threshold, 0, nullptr, &fc, &fci);
-                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins || grow_ends || gapped)) {
+                if (rc == ALGA_OK && (contigs_depth || !placements.empty() || polish || !scaffolds.empty() || break_misjoins || grow_ends || gapped || !sam.empty())) {
                     // every input read, as the files give it (corrected where the graph's reads were), laid over the final contigs
                     alga_parsed_reads pr{};
                     char perr[512] = {0};
@@ -645,6 +661,28 @@ int main(int argc, char **argv) {
                                     (int) mm[r], (int) hits[r]);
                         if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", placements.c_str()); return 1; }
                     }
+                    // --sam=: the pairs judged over the passes at hand, every read as a record
+                    auto write_sam = [&](const alga_gapped *gpp) -> int {
+                        alga_pair_params jq;
+                        alga_pair_default_params(&jq);
+                        jq.max_insert = pp.max_insert;
+                        alga_pair_calls jc;
+                        alga_pair_info ji;
+                        int r = alga_judge_pairs_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, &pl, gpp, &jq, nullptr, &jc, &ji);
+                        if (r != ALGA_OK) return r;
+                        alga_sam_params sq{};
+                        sq.flags = (contigs_depth ? ALGA_SAM_NAMES_DEPTH : 0) | (sam_unplaced == 0 ? ALGA_SAM_SKIP_UNPLACED : 0);
+                        alga_gfa_info si;
+                        r = alga_write_sam_device(engine, &pnd, &pl, gpp, &jc, &sq, sam.c_str(), &si);
+                        if (r != ALGA_OK) return r;
+                        fprintf(stderr, "SAM written: %llu records; %llu pairs: %llu proper, %llu improper, %llu split, %llu not unique; with a gapped mate %llu pairs, %llu proper; "
+                                "median insert %lld; device ms: judge %.3f format %.3f, %llu bytes\n", (unsigned long long) si.segments, (unsigned long long) ji.pairs,
+                                (unsigned long long) ji.pairs_proper, (unsigned long long) ji.pairs_improper, (unsigned long long) ji.pairs_split,
+                                (unsigned long long) ji.pairs_not_unique, (unsigned long long) ji.pairs_with_gapped, (unsigned long long) ji.proper_with_gapped,
+                                (long long) ji.insert_median, ji.ms_judge, si.ms_format, (unsigned long long) si.bytes);
+                        return ALGA_OK;
+                    };
+                    if (rc == ALGA_OK && !gapped && !sam.empty()) rc = write_sam(nullptr);
                     if (rc == ALGA_OK && gapped) {
                         // the targets of that placement once more, as arrays: target j = the window of the pair order[j] (not a hot path: made on the host)
                         const size_t np = (size_t) fc.n_pairs, nt = (size_t) fc.n_accepted;
@@ -680,6 +718,7 @@ int main(int argc, char **argv) {
                                     gi.ms_index, gi.ms_place, gi.ms_trace, gi.ms_depth, gi.ms_total);
                         alga_gfa_info gti;
                         if (rc == ALGA_OK && !gapped_placements.empty()) rc = alga_write_gapped_tsv_device(engine, &gp, gapped_placements.c_str(), &gti);
+                        if (rc == ALGA_OK && !sam.empty()) rc = write_sam(&gp);
                         if (rc == ALGA_OK && polish_indels) {
                             alga_ipolish_params iq;
                             alga_ipolish_default_params(&iq);

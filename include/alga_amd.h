@@ -1883,6 +1883,92 @@ int  alga_polish_indels_device(alga_engine *e, const alga_nodes *nodes, const al
 int  alga_write_ipolished_fasta_device(alga_engine *e, const alga_ipolished *ipol, const char *path, alga_gfa_info *info /* may be NULL */);
 int  alga_write_ipolish_events_tsv_device(alga_engine *e, const alga_ipolished *ipol, const char *path, alga_gfa_info *info /* may be NULL */);
 
+/* ---- SAM output and pair calls over both placement passes (alga_amd/csrc/sam_kernels.hip, engine_sam.hip) ---------------------------------
+ * The Hamming placement judges its pairs by pos + len; a pair with a gapped mate stays pairs_not_unique there.  alga_judge_pairs_device judges
+ * every pair again over both passes, with the ends the gapped pass reports, and gives every read its SAM FLAG and TLEN;
+ * alga_write_sam_device writes all reads as SAM, formatted on the device.  Integers only, free of any order; tests/sam_checker.py states both
+ * in Python and the device result equals it array for array and byte for byte.  No other result is touched.
+ *
+ * Inputs: the node set that was placed (twin layout) and its pair_off (NULL = no pairs); `pl`, the engine's current placement result; `gp`,
+ * the engine's current gapped result made from `pl`, or NULL: the Hamming pass alone.  alga_pair_params: max_insert 1 .. 2^20 (1000), flags 0,
+ * reserved 0.
+ *
+ *   1. The combined view of read r, L = len[2r + 1].  H iff pl.d_state[r] has ALGA_PLACE_PLACED: target and pos from pl, end = pos + L, strand
+ *      from ALGA_PLACE_MINUS, nm = d_mm, unique = ALGA_PLACE_UNIQUE, the script is the one run `L M`.  Otherwise G iff gp is given and
+ *      gp.d_state[r] has ALGA_GAPPED_PLACED: target, pos, end, strand, nm = d_edits, unique and the runs from gp.  Otherwise unplaced.  A read
+ *      is LIVE iff L >= 1 (a removed read, len -1, is not).
+ *   2. Pairs.  The pair is (r, r + 1) where pair_off[2r + 1] == 1; the smaller index judges.  A pair is LIVE iff both reads are live; only live
+ *      pairs are counted, a read of a pair that is not live is a single read.  Not both unique: pairs_not_unique.  Different targets:
+ *      pairs_split.  Same strand: pairs_improper.  Otherwise with a, ea the pos and end of the `+` read and b, eb of the `-` read the pair is
+ *      PROPER iff a <= b, ea <= eb and insert = eb - a <= max_insert; a proper pair does d_insert_hist[insert]++ (max_insert + 1 bins);
+ *      anything else is pairs_improper.  insert_median and insert_mean_x100 as the placement computes them (rule 6 there; -1 without proper
+ *      pairs).  For two H reads this is the placement's rule 6 word for word: with no gapped-placed read, every pair live and max_insert the
+ *      placement's, the five pair counters, the histogram, the median and the mean equal those of `pl`.
+ *   3. d_flag[r], the SAM FLAG: 0x1 r is in a live pair; 0x2 the pair is proper; 0x4 r is unplaced; 0x8 r is paired and its mate is
+ *      unplaced; 0x10 r is placed on the minus strand; 0x20 r is paired and its mate is placed on the minus strand; 0x40 / 0x80 r is the
+ *      smaller / the larger index of a live pair.  No other bit is ever set; a read that is not live gets 0.
+ *   4. d_tlen[r]: both mates of a live pair placed on the same target: max(e1, e2) - min(p1, p2), positive for the mate with the smaller p,
+ *      negative for the other, at equal p positive for the smaller read index; 0 in every other case.
+ *   5. Counters (alga_pair_info): reads = n / 2, live, placed_h, placed_g, unplaced (of the live reads); pairs = pairs_proper + pairs_improper +
+ *      pairs_split + pairs_not_unique; pairs_with_gapped = the live pairs with at least one G mate, proper_with_gapped the proper ones among
+ *      them; ms_judge (HIP events), ms_total (wall).
+ *   6. Refusals (ALGA_ERR_INVALID_ARGUMENT; nothing of the result is written, an earlier result stays valid).  Host: `pl` is not the current
+ *      placement; `gp` is given but is not the current gapped result or was made from an earlier placement; nodes->n / 2 != pl.n_reads; the
+ *      parameters.  Device, one read-back: pair_off[v] <= 2, pair_off[v] == pair_off[v ^ 1], the mate in range and pointing back.
+ * The result (alga_pair_calls) is engine-owned, valid until the next judge call on `e`; it remembers the placement and the gapped result
+ * (or that there was none) it was made from.  `pl`, `gp` and every other result stay valid.  Read-backs: the check; the counters and the
+ * histogram.
+ *
+ * alga_write_sam_device.  `calls` must be the engine's current pair calls, made from this `pl` and this `gp` (NULL where they were made
+ * without one); anything else is refused.  Target lengths come from pl.d_col_off; no target bases are needed.
+ *   Header: `@HD VN:1.6 SO:unsorted GO:query`, one `@SQ SN:<name(t)> LN:<len[t]>` per target with len >= 1 in target order (SAM forbids LN:0;
+ *   nothing lies on such a target), `@PG ID:alga_amd PN:alga_amd`, tab separated, formatted on the host from T lengths.  name(t) =
+ *   `contig_id=<t>_length=<len>`, the first token of alga_write_final_fasta_device's header; with ALGA_SAM_NAMES_DEPTH that plus
+ *   `_reads=<t_reads>_depth=<q>.<dd>` from pl, the token of alga_write_final_fasta_depth_device.
+ *   Records: one per live read in read order (mates adjacent), eleven tab-separated fields and the tags.  QNAME `r<q>`, q the smaller read
+ *   index of the live pair, for a single read its own (the engine keeps no read names).  FLAG d_flag[r].  RNAME, POS: placed: name(target),
+ *   pos + 1; unplaced with a placed live mate: the mate's; otherwise `*`, 0.  MAPQ 60 if placed and unique, else 0 (there is no second-best
+ *   score to grade with).  CIGAR: unplaced `*`; H `<L>M`; G the runs of gp.d_cigar, a leading and / or trailing I run written as S (a read
+ *   hanging over a target end; the clipped bases stay in SEQ).  RNEXT, PNEXT: single read `*`, 0; in a live pair the RNAME and POS fields of
+ *   the mate's record (borrowed values included), `=` where the names are equal; both unplaced `*`, 0.  TLEN d_tlen[r].  SEQ the bases of
+ *   node 2r if placed on the minus strand, else of node 2r + 1.  QUAL `*` (the engine keeps no qualities).  Tags, placed reads only:
+ *   `NM:i:<nm>` (G: edits minus the soft-clipped bases), `XP:A:H` or `XP:A:G`.
+ *   ALGA_SAM_SKIP_UNPLACED: no records for unplaced reads; every other record byte for byte as without the flag.
+ *   Refusals: as for the judge; on the device, in the read-back of the sizes pass, before the file is touched: a live read with
+ *   len > 16 * stride_words; a G read whose script's query length differs from len or that has no run.
+ *   Not written: MD tags, qualities and read names, BAM, secondary and supplementary records, graded MAPQ, coordinate order.
+ * ABI stays 7: the calls add. */
+#define ALGA_SAM_NAMES_DEPTH   1     /* alga_sam_params.flags: names as the depth FASTA's header token, else as the plain final FASTA's */
+#define ALGA_SAM_SKIP_UNPLACED 2     /* no records for unplaced reads                                                                 */
+typedef struct {
+    int32_t max_insert, flags;
+    int32_t reserved[6];             /* 0                                                                                             */
+} alga_pair_params;
+typedef struct {
+    int64_t         n_reads, n_hist; /* n / 2, max_insert + 1                                                                         */
+    const uint16_t *d_flag;          /* n_reads: the SAM FLAG of the read's record                                                    */
+    const int32_t  *d_tlen;          /* n_reads                                                                                       */
+    const uint64_t *d_insert_hist;   /* n_hist                                                                                        */
+} alga_pair_calls;
+typedef struct {
+    uint64_t reads, live, placed_h, placed_g, unplaced;
+    uint64_t pairs, pairs_proper, pairs_improper, pairs_split, pairs_not_unique;
+    uint64_t pairs_with_gapped, proper_with_gapped;   /* pairs with >= 1 mate from the gapped pass, and the proper ones among them    */
+    int64_t  insert_median, insert_mean_x100;
+    double   ms_judge;               /* device time (HIP events)                                                                      */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_pair_info;
+typedef struct {
+    int32_t flags;
+    int32_t reserved[7];             /* 0                                                                                             */
+} alga_sam_params;
+void alga_pair_default_params(alga_pair_params *p);
+int  alga_judge_pairs_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off /* may be NULL */, const alga_placements *pl,
+                             const alga_gapped *gp /* may be NULL: the Hamming pass alone */, const alga_pair_params *p, void *hip_stream,
+                             alga_pair_calls *out, alga_pair_info *info /* may be NULL */);
+int  alga_write_sam_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_gapped *gp /* may be NULL */,
+                           const alga_pair_calls *calls, const alga_sam_params *p, const char *path, alga_gfa_info *info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
