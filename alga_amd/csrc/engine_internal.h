@@ -208,6 +208,7 @@ struct alga_engine {
     DevBuf      sc_cnt, sc_keys[2], sc_vals[2], sc_span, sc_heads, sc_pos, sc_bstart, sc_best, sc_choice, sc_partner, sc_lists[2], sc_head, sc_first, sc_scan;
     DevBuf      sc_ba, sc_bb, sc_blinks, sc_bspan, sc_bgap, sc_bstate, sc_estate, sc_scaffold, sc_rank, sc_orient, sc_start, sc_gapafter, sc_jlinks, sc_soff,
                 sc_smembers, sc_slen;
+    int         opt_scaffold_max_blocks = 8192;    // option "scaffold_max_blocks": the cap of the k_sc_* grids (tests make every grid-stride loop take further passes)
     bool        sc_valid = false;                  // the result buffers hold scaffolds
     uint64_t    sc_targets = 0, sc_scaffolds = 0, sc_longest = 0;   // ... of this many targets, this many of them, the longest with its gaps
     uint64_t    sc_pl_serial = 0;                  // ... made from this placement result

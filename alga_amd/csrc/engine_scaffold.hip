@@ -57,9 +57,10 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
     HIP_TRY(e, hipMemsetAsync(cnt, 0, SC_COUNTERS * sizeof(unsigned long long), s));
     const ScReads rd{nodes->len, nodes->stride_words, R, d_pair_off, pl->d_target, pl->d_pos, pl->d_state};
     const ScTargets tg{pl->d_col_off, (uint32_t) T};
+    const uint32_t mb = (uint32_t) e->opt_scaffold_max_blocks;               // 8192 unless a test lowers it
 
     // the check: nothing of the result is written before its verdict
-    launch_sc_check(rd, tg, cnt, s);
+    launch_sc_check(rd, tg, cnt, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_check"))) return rc;
     HIP_TRY(e, hipMemcpyAsync(hc, cnt, SC_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -82,7 +83,7 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
             if ((rc = alga_ensure(e, e->sc_vals[j], (R + 2) * sizeof(uint32_t)))) return rc;
         }
         if ((rc = alga_ensure(e, e->sc_span, (R + 2) * sizeof(uint32_t)))) return rc;
-        launch_sc_links(rd, tg, p->max_insert, sentinel, (unsigned long long *) e->sc_keys[0].p, (uint32_t *) e->sc_vals[0].p, (uint32_t *) e->sc_span.p, cnt, s);
+        launch_sc_links(rd, tg, p->max_insert, sentinel, (unsigned long long *) e->sc_keys[0].p, (uint32_t *) e->sc_vals[0].p, (uint32_t *) e->sc_span.p, cnt, mb, s);
         if ((rc = alga_check_launch(e, "k_sc_links"))) return rc;
         HIP_TRY(e, hipMemcpyAsync(hc, cnt, SC_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HIP_TRY(e, hipStreamSynchronize(s));
@@ -96,7 +97,7 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
             // the links come first: the sentinel is above every key
             HIP_TRY(e, sort_u64_u32(e->sort_temp.p, temp, (const unsigned long long *) e->sc_keys[0].p, (unsigned long long *) e->sc_keys[1].p, (const uint32_t *) e->sc_vals[0].p,
                                     (uint32_t *) e->sc_vals[1].p, R, bits, s));
-            launch_sc_heads((const unsigned long long *) e->sc_keys[1].p, n_links, (uint32_t *) e->sc_heads.p, cnt, s);
+            launch_sc_heads((const unsigned long long *) e->sc_keys[1].p, n_links, (uint32_t *) e->sc_heads.p, cnt, mb, s);
             if ((rc = alga_check_launch(e, "k_sc_heads"))) return rc;
             launch_exclusive_scan((const uint32_t *) e->sc_heads.p, n_links, (uint32_t *) e->sc_pos.p, (uint64_t *) e->scan_scratch.p, s);
             if ((rc = alga_check_launch(e, "scan(bundle heads)"))) return rc;
@@ -125,18 +126,18 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
     HIP_TRY(e, hipMemsetAsync(partner, 0xFF, (2 * n_ends + 2) * sizeof(uint32_t), s));
     if (n_bundles) {
         launch_sc_bundle_fill((const uint32_t *) e->sc_vals[1].p, (const uint32_t *) e->sc_span.p, (const uint32_t *) e->sc_heads.p, (const uint32_t *) e->sc_pos.p, n_links,
-                              n_bundles, (uint32_t *) e->sc_bstart.p, (unsigned long long *) e->sc_bspan.p, s);
+                              n_bundles, (uint32_t *) e->sc_bstart.p, (unsigned long long *) e->sc_bspan.p, mb, s);
         if ((rc = alga_check_launch(e, "k_sc_bundle_fill"))) return rc;
-        launch_sc_bundles((const unsigned long long *) e->sc_keys[1].p, (const uint32_t *) e->sc_bstart.p, bd, sp, best, cnt, s);
+        launch_sc_bundles((const unsigned long long *) e->sc_keys[1].p, (const uint32_t *) e->sc_bstart.p, bd, sp, best, cnt, mb, s);
         if ((rc = alga_check_launch(e, "k_sc_bundles"))) return rc;
     }
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
-    launch_sc_second(bd, best, second, s);
+    launch_sc_second(bd, best, second, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_second"))) return rc;
-    launch_sc_choice(best, second, n_ends, p->max_second_percent, choice, (uint8_t *) e->sc_estate.p, cnt, s);
+    launch_sc_choice(best, second, n_ends, p->max_second_percent, choice, (uint8_t *) e->sc_estate.p, cnt, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_choice"))) return rc;
-    launch_sc_joins(bd, choice, partner, join_bundle, s);
+    launch_sc_joins(bd, choice, partner, join_bundle, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_joins"))) return rc;
 
     // the lists over the 2T states: after this many doublings a jump is longer than any path
@@ -150,15 +151,15 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
     }
     int cur = 0;
     if (n_bundles && T) {                                                     // without a bundle there is no join and no cycle
-        launch_sc_cycle_init(partner, n_ends, set[0], s);
-        for (int k = 0; k < rounds; k++, cur ^= 1) launch_sc_cycle_jump(n_ends, set[cur], set[cur ^ 1], s);
+        launch_sc_cycle_init(partner, n_ends, set[0], mb, s);
+        for (int k = 0; k < rounds; k++, cur ^= 1) launch_sc_cycle_jump(n_ends, set[cur], set[cur ^ 1], mb, s);
         if ((rc = alga_check_launch(e, "k_sc_cycle_jump"))) return rc;
-        launch_sc_cycle_drop(set[cur], (uint32_t) T, partner, join_bundle, bd.state, cnt, s);
+        launch_sc_cycle_drop(set[cur], (uint32_t) T, partner, join_bundle, bd.state, cnt, mb, s);
         if ((rc = alga_check_launch(e, "k_sc_cycle_drop"))) return rc;
     }
     cur = 0;
-    launch_sc_rank_init(tg, partner, join_bundle, bd.gap, p->min_gap, set[0], s);
-    if (n_bundles) for (int k = 0; k < rounds; k++, cur ^= 1) launch_sc_rank_jump(n_ends, set[cur], set[cur ^ 1], s);
+    launch_sc_rank_init(tg, partner, join_bundle, bd.gap, p->min_gap, set[0], mb, s);
+    if (n_bundles) for (int k = 0; k < rounds; k++, cur ^= 1) launch_sc_rank_jump(n_ends, set[cur], set[cur ^ 1], mb, s);
     if ((rc = alga_check_launch(e, "k_sc_rank_jump"))) return rc;
 
     // the per-contig and per-scaffold arrays
@@ -172,12 +173,12 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
     uint32_t *first = (uint32_t *) e->sc_first.p, *members = first + T + 2, *first_scan = (uint32_t *) e->sc_scan.p, *members_scan = first_scan + T + 2;
     const ScLayout lo{(int32_t *) e->sc_scaffold.p, (int32_t *) e->sc_rank.p, (uint8_t *) e->sc_orient.p, (unsigned long long *) e->sc_start.p, (int32_t *) e->sc_gapafter.p,
                       (uint32_t *) e->sc_jlinks.p, (uint32_t *) e->sc_soff.p, (int32_t *) e->sc_smembers.p, (unsigned long long *) e->sc_slen.p, (uint8_t *) e->sc_estate.p};
-    launch_sc_place(tg, set[cur], partner, join_bundle, bd.gap, bd.links, p->min_gap, lo, (uint32_t *) e->sc_head.p, first, members, cnt, s);
+    launch_sc_place(tg, set[cur], partner, join_bundle, bd.gap, bd.links, p->min_gap, lo, (uint32_t *) e->sc_head.p, first, members, cnt, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_place"))) return rc;
     launch_exclusive_scan(first, T + 1, first_scan, (uint64_t *) e->scan_scratch.p, s);
     launch_exclusive_scan(members, T + 1, members_scan, (uint64_t *) e->scan_scratch.p, s);
     if ((rc = alga_check_launch(e, "scan(scaffolds)"))) return rc;
-    launch_sc_layout(tg, set[cur], (const uint32_t *) e->sc_head.p, first_scan, members_scan, lo, cnt, s);
+    launch_sc_layout(tg, set[cur], (const uint32_t *) e->sc_head.p, first_scan, members_scan, lo, cnt, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_layout"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
     HIP_TRY(e, hipMemcpyAsync(hc, cnt, SC_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -260,6 +261,7 @@ extern "C" int alga_write_scaffold_fasta_device(alga_engine *e, const alga_place
     if (e->sc_longest + 64 > 0xFFFFFFFFull) return alga_fail(e, ALGA_ERR_CAPACITY, "a scaffold record of more than 2^32 bytes");
     HIP_TRY(e, hipSetDevice(e->device));
     const ScFasta f{pol ? pol->d_words : (const uint32_t *) e->pl_cols.p, pl->d_col_off, scaf->d_s_off, scaf->d_s_members, (const unsigned long long *) scaf->d_s_len,
-                    (const unsigned long long *) scaf->d_start, scaf->d_orient, (uint64_t) scaf->n_scaffolds};
+                    (const unsigned long long *) scaf->d_start, scaf->d_orient, (uint64_t) scaf->n_scaffolds,
+                    e->opt_scaffold_max_blocks < 8192 ? (uint32_t) e->opt_scaffold_max_blocks : 16384u};   // the write grid's own cap unless a test lowers it
     return alga_text_records(e, f, launch_sc_fasta_sizes, launch_sc_fasta_write, path, info);
 }

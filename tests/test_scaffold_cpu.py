@@ -14,6 +14,7 @@ import place_cases as PC
 import place_checker as P
 import scaffold_cases as QC
 import scaffold_checker as SC
+import scaffold_invariants as INV
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ["k_sc_check", "k_sc_links", "k_sc_heads", "k_sc_bundle_fill", "k_sc_bundles", "k_sc_second", "k_sc_choice", "k_sc_joins", "k_sc_cycle_init",
@@ -38,9 +39,7 @@ def assert_same(got, want, what=""):
     assert got["info"] == want["info"], (what, got["info"], want["info"])
 
 
-def layout(res):
-    """the scaffolds as [[(contig, orient)]]"""
-    return [[(int(c), int(res["orient"][c])) for c in res["s_members"][int(res["s_off"][j]):int(res["s_off"][j + 1])]] for j in range(len(res["s_len"]))]
+layout = INV.layout                                                            # the scaffolds as [[(contig, orient)]]
 
 
 @pytest.mark.parametrize("name,i", QC.every())
@@ -51,24 +50,7 @@ def test_the_two_statements_agree(name, i):
     assert_same(got, want, (name, i))
     info = want["info"]
     assert tuple(info[k] for k in ("links", "bundles_supported", "ends_ambiguous", "joins", "joins_dropped_cycle", "scaffolds", "scaffolds_multi")) == OUTCOMES[name][i], info
-    # what holds for every result
-    tlen = c["tlen"].astype(np.int64)
-    assert info["pairs_split"] == pl["info"]["pairs_split"] == info["links"] + info["links_too_far"] == (len(c["links"]) if c["pair_off"] is not None else 0)
-    assert int(want["b_links"].sum()) == info["links"] and info["bundles"] == len(want["b_a"]) and (want["b_a"] < want["b_b"]).all()
-    keys = (want["b_a"].astype(np.int64) << 32) | want["b_b"]
-    assert (np.diff(keys) > 0).all()
-    assert ((want["scaffold"] == -1) == (tlen == 0)).all() and ((want["rank"] == -1) == (tlen == 0)).all()
-    assert len(want["s_members"]) == int((tlen > 0).sum()) == int(want["s_off"][-1]) and sorted(want["s_members"].tolist()) == np.nonzero(tlen > 0)[0].tolist()
-    firsts = [int(want["s_members"][o]) for o in want["s_off"][:-1]]
-    assert firsts == sorted(firsts) and all(p[0][0] <= p[-1][0] for p in layout(want))
-    assert int(want["s_len"].sum()) == int(tlen.sum()) + int(want["gap_after"].sum()) and info["joins"] == int((want["join_links"] > 0).sum()) == int((want["gap_after"] > 0).sum())
-    assert (want["gap_after"][want["gap_after"] > 0] >= v["min_gap"]).all()
-    joined = (want["end_state"] & SC.E_JOINED).astype(bool)
-    assert int(joined.sum()) == 2 * info["joins"] and not (joined & (want["end_state"] & SC.E_AMBIGUOUS).astype(bool)).any()
-    # the rendered FASTA: one record per scaffold, as long as s_len says, the gaps as N
-    text = SC.fasta(want, c["seqs"]).decode().split("\n")
-    assert text[-1] == "" and [len(s) for s in text[1::2]] == want["s_len"].tolist() and sum(s.count("N") for s in text[1::2]) == int(want["gap_after"].sum())
-    assert len(SC.layout_tsv(want, tlen).decode().splitlines()) == len(want["s_members"])
+    INV.every_result(c, pl["info"]["pairs_split"], want, v)                   # what holds for every result (tests/scaffold_invariants.py)
     print(name, i, info)
 
 
