@@ -63,7 +63,7 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     unsigned long long *cnt = (unsigned long long *) e->gr_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, GR_COUNTERS * sizeof(unsigned long long), s));
     const SeedReads rd{nodes->words, nodes->stride_words, nodes->len, R};
-    const GrTargets tg{pl->d_col_off, (uint32_t) T, C, pol ? pol->d_words : (const uint32_t *) e->pl_cols.p};
+    const GrTargets tg{pl->d_col_off, (uint32_t) T, C, pol ? pol->d_words : (const uint32_t *) e->pl_cols.p, (uint32_t) e->opt_grow_max_blocks};
 
     // the check: nothing of the result is written before its verdict
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
@@ -89,7 +89,7 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(std::max<uint64_t>(std::max(R, E), T) + 2)))) return rc;
     uint32_t *flag = (uint32_t *) e->gr_flag.p, *pos = (uint32_t *) e->gr_pos.p, *eoff = (uint32_t *) e->gr_eoff.p;
     int32_t *elen = (int32_t *) e->gr_elen.p;
-    launch_gr_candidates(rd, pl->d_state, p->min_anchor, flag, s);
+    launch_gr_candidates(rd, pl->d_state, p->min_anchor, flag, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_gr_candidates"))) return rc;
     launch_exclusive_scan(flag, R + 1, pos, (uint64_t *) e->scan_scratch.p, s);
     if ((rc = alga_check_launch(e, "scan(candidates)"))) return rc;
@@ -106,13 +106,13 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
 
     // the list, the end sequences, the index
     const size_t ec_words = (size_t) ((EC + 15) >> 4) + 2;
-    const int blocks = seed_blocks(n_cand, e->n_cu);
+    const int blocks = std::min(seed_blocks(n_cand, e->n_cu), e->opt_grow_max_blocks);   // the scratch and its words per wave follow from the capped count
     const size_t ub_words = seed_scratch_words(blocks, max_len, p->k);
     if ((rc = alga_ensure(e, e->gr_cand, (n_cand + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gr_ecols, ec_words * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->seed_ub, ub_words * sizeof(unsigned long long)))) return rc;
     uint32_t *cand = (uint32_t *) e->gr_cand.p, *ecols = (uint32_t *) e->gr_ecols.p;
-    launch_gr_compact(flag, pos, R, cand, s);
+    launch_gr_compact(flag, pos, R, cand, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_gr_compact"))) return rc;
     const GrEnds en{eoff, elen, (uint32_t) E, EC, ecols};
     HIP_TRY(e, hipMemsetAsync(ecols, 0, ec_words * sizeof(uint32_t), s));
@@ -148,9 +148,9 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     if ((rc = alga_check_launch(e, "k_gr_place"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 
-    launch_gr_vote(rd, cand, n_cand, go, p->max_grow, count, voters, s);
+    launch_gr_vote(rd, cand, n_cand, go, p->max_grow, count, voters, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_gr_vote"))) return rc;
-    launch_gr_decide(count, voters, (uint32_t) E, p->max_grow, p->min_cover, p->min_percent, x, (uint8_t *) e->gr_g.p, (uint8_t *) rs.estop.p, cnt, s);
+    launch_gr_decide(count, voters, (uint32_t) E, p->max_grow, p->min_cover, p->min_percent, x, (uint8_t *) e->gr_g.p, (uint8_t *) rs.estop.p, cnt, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_gr_decide"))) return rc;
     launch_gr_lens(tg, x, (uint32_t *) rs.left.p, (uint32_t *) rs.right.p, (int32_t *) rs.len.p, cnt, s);
     if ((rc = alga_check_launch(e, "k_gr_lens"))) return rc;
@@ -244,6 +244,7 @@ extern "C" int alga_write_grown_fasta_device(alga_engine *e, const alga_grown *g
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_grow_placed_device call on this engine");
     if (e->gr_longest + 96 > 0xFFFFFFFFull) return alga_fail(e, ALGA_ERR_CAPACITY, "a contig record of more than 2^32 bytes");
     HIP_TRY(e, hipSetDevice(e->device));
-    const GrFasta f{grown->d_words, grown->d_col_off, grown->d_len, grown->d_left, grown->d_right, (uint64_t) grown->n_targets};
+    const GrFasta f{grown->d_words, grown->d_col_off, grown->d_len, grown->d_left, grown->d_right, (uint64_t) grown->n_targets,
+                    e->opt_grow_max_blocks < 8192 ? (uint32_t) e->opt_grow_max_blocks : 16384u};   // the write grid's own cap unless a test lowers it
     return alga_text_records(e, f, launch_gr_fasta_sizes, launch_gr_fasta_write, path, info);
 }

@@ -225,6 +225,7 @@ struct alga_engine {
     DevBuf      gr_cnt, gr_flag, gr_pos, gr_cand, gr_elen, gr_eoff, gr_ecols, gr_x, gr_g;
     struct GrowSet { DevBuf end, over, mm, hits, state, count, estop, evoters, left, right, len, coloff, begin, words; } gr_set[2];
     int         gr_cur = 0;                        // the set that holds the result
+    int         opt_grow_max_blocks = 8192;        // option "grow_max_blocks": the cap of the k_gr_* grids, k_gr_place's and the FASTA write grid's included (tests make every grid-stride and wave-stride loop take further passes)
     bool        gr_valid = false;
     uint64_t    gr_reads = 0, gr_targets = 0, gr_columns = 0, gr_longest = 0;   // ... of this many reads, targets and columns; the longest grown target
     // contigs whose ends overlap merged into one sequence (engine_merge.hip).  Workspaces: counters, the end lengths, their padded lengths and

@@ -20,7 +20,10 @@
 //   k_gr_lens         left / right / new length per target; (scan): the new col_off
 //   k_gr_build        every output word gathered by one lane, from the old column array or from the growth
 //   k_gr_fasta_sizes / k_gr_fasta_write   one record per target with a length, one wave per record, a lane a byte
-// Block 256 and the grid caps are picked, not tuned.
+// Block 256 and the grid caps are picked, not tuned; the launches' max_blocks lowers the cap of every grid that goes through gr_grid (the check
+// keeps min(4096, cap)), of k_gr_place (whose per-wave scratch the host sizes from the capped block count) and of the FASTA write grid (option
+// "grow_max_blocks": a knob of the tests, which make every grid-stride and wave-stride loop here take further passes).  k_gr_fasta_sizes has one
+// thread per item and no loop: its grid is exact.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -284,7 +287,7 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_fasta_write(GrFasta f, const un
     text_write_body<GrRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned gr_grid(uint64_t items, uint64_t cap = 8192) {
+inline unsigned gr_grid(uint64_t items, uint64_t cap) {                  // cap: the launch's max_blocks, 8192 unless a test lowers it
     const uint64_t g = (items + GR_BLOCK - 1) / GR_BLOCK;
     return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
 }
@@ -292,23 +295,23 @@ inline unsigned gr_grid(uint64_t items, uint64_t cap = 8192) {
 }  // namespace
 
 void launch_gr_check(const SeedReads &r, const GrTargets &t, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_check, dim3(gr_grid(2 * r.R, 4096)), dim3(GR_BLOCK), 0, s, r, t, counters);
+    hipLaunchKernelGGL(k_gr_check, dim3(gr_grid(2 * r.R, std::min<uint64_t>(4096, t.max_blocks))), dim3(GR_BLOCK), 0, s, r, t, counters);
 }
 
-void launch_gr_candidates(const SeedReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_candidates, dim3(gr_grid(r.R + 1)), dim3(GR_BLOCK), 0, s, r, pl_state, min_anchor, flag);
+void launch_gr_candidates(const SeedReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, uint32_t max_blocks, hipStream_t s) {
+    hipLaunchKernelGGL(k_gr_candidates, dim3(gr_grid(r.R + 1, max_blocks)), dim3(GR_BLOCK), 0, s, r, pl_state, min_anchor, flag);
 }
 
-void launch_gr_compact(const uint32_t *flag, const uint32_t *pos, uint64_t R, uint32_t *cand, hipStream_t s) {
-    if (R) hipLaunchKernelGGL(k_gr_compact, dim3(gr_grid(R)), dim3(GR_BLOCK), 0, s, flag, pos, R, cand);
+void launch_gr_compact(const uint32_t *flag, const uint32_t *pos, uint64_t R, uint32_t *cand, uint32_t max_blocks, hipStream_t s) {
+    if (R) hipLaunchKernelGGL(k_gr_compact, dim3(gr_grid(R, max_blocks)), dim3(GR_BLOCK), 0, s, flag, pos, R, cand);
 }
 
 void launch_gr_end_lens(const GrTargets &t, int32_t max_len, int32_t k, int32_t *elen, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_end_lens, dim3(gr_grid(2ull * t.T + 1)), dim3(GR_BLOCK), 0, s, t, max_len, k, elen, counters);
+    hipLaunchKernelGGL(k_gr_end_lens, dim3(gr_grid(2ull * t.T + 1, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, max_len, k, elen, counters);
 }
 
 void launch_gr_ends(const GrTargets &t, const GrEnds &e, uint32_t *ecols, hipStream_t s) {
-    if (e.columns) hipLaunchKernelGGL(k_gr_ends, dim3(gr_grid((e.columns + 15) >> 4)), dim3(GR_BLOCK), 0, s, t, e, ecols);
+    if (e.columns) hipLaunchKernelGGL(k_gr_ends, dim3(gr_grid((e.columns + 15) >> 4, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, e, ecols);
 }
 
 void launch_gr_place(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ,
@@ -318,23 +321,24 @@ void launch_gr_place(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, 
                                    scratch, scratch_words_per_wave, counters);
 }
 
-void launch_gr_vote(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, hipStream_t s) {
-    if (n_cand) hipLaunchKernelGGL(k_gr_vote, dim3(gr_grid(n_cand * 64)), dim3(GR_BLOCK), 0, s, r, cand, n_cand, o, max_grow, count, voters);
+void launch_gr_vote(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, uint32_t max_blocks,
+                    hipStream_t s) {
+    if (n_cand) hipLaunchKernelGGL(k_gr_vote, dim3(gr_grid(n_cand * 64, max_blocks)), dim3(GR_BLOCK), 0, s, r, cand, n_cand, o, max_grow, count, voters);
 }
 
 void launch_gr_decide(const uint32_t *count, const uint32_t *voters, uint32_t E, int32_t max_grow, int32_t min_cover, int32_t min_percent, uint32_t *x, uint8_t *g,
-                      uint8_t *stop, unsigned long long *counters, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_gr_decide, dim3(gr_grid(E)), dim3(GR_BLOCK), 0, s, count, voters, E, max_grow, (uint32_t) min_cover, (uint32_t) min_percent, x, g, stop, counters);
+                      uint8_t *stop, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
+    if (E) hipLaunchKernelGGL(k_gr_decide, dim3(gr_grid(E, max_blocks)), dim3(GR_BLOCK), 0, s, count, voters, E, max_grow, (uint32_t) min_cover, (uint32_t) min_percent, x, g, stop, counters);
 }
 
 void launch_gr_lens(const GrTargets &t, const uint32_t *x, uint32_t *left, uint32_t *right, int32_t *newlen, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_lens, dim3(gr_grid((uint64_t) t.T + 1)), dim3(GR_BLOCK), 0, s, t, x, left, right, newlen, counters);
+    hipLaunchKernelGGL(k_gr_lens, dim3(gr_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, x, left, right, newlen, counters);
 }
 
 void launch_gr_build(const GrTargets &t, const uint32_t *new_off, uint64_t new_columns, const uint32_t *left, const uint8_t *g, int32_t max_grow, uint32_t *words,
                      unsigned long long *begin, hipStream_t s) {
     const uint64_t n_words = ((new_columns + 15) >> 4) + 2;
-    hipLaunchKernelGGL(k_gr_build, dim3(gr_grid(std::max<uint64_t>(n_words, t.T))), dim3(GR_BLOCK), 0, s, t, new_off, new_columns, left, g, max_grow, words, begin);
+    hipLaunchKernelGGL(k_gr_build, dim3(gr_grid(std::max<uint64_t>(n_words, t.T), t.max_blocks)), dim3(GR_BLOCK), 0, s, t, new_off, new_columns, left, g, max_grow, words, begin);
 }
 
 void launch_gr_fasta_sizes(const GrFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
@@ -344,7 +348,7 @@ void launch_gr_fasta_sizes(const GrFasta &f, uint32_t *sizes, unsigned long long
 void launch_gr_fasta_write(const GrFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
     const uint64_t g = (i1 - i0 + GR_WAVES - 1) / GR_WAVES;
-    hipLaunchKernelGGL(k_gr_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GR_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_gr_fasta_write, dim3((unsigned) std::min<uint64_t>(g, f.max_blocks)), dim3(GR_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -231,6 +231,9 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                fit is done by grid stride (tests lower it to make small inputs stride)
  *   "scaffold_max_blocks"        1..8192 (default 8192): the largest grid of the kernels of alga_scaffold_placed_device and of the write kernel of
  *                                alga_write_scaffold_fasta_device; what does not fit is done by grid stride (tests lower it to make small inputs stride)
+ *   "grow_max_blocks"            1..8192 (default 8192): the largest grid of the kernels of alga_grow_placed_device, the placement of the overhanging
+ *                                reads (its per-wave scratch follows the grid) and the write kernel of alga_write_grown_fasta_device included; what does
+ *                                not fit is done by grid or wave stride (tests lower it to make small inputs stride)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
