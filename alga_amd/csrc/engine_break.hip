@@ -21,11 +21,6 @@ using namespace alga;
 
 namespace {
 
-struct BrEvents {
-    hipEvent_t ev[3] = {};
-    ~BrEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_break_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "break parameters must not be NULL");
     if (p->min_span < 1) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "break: min_span must be >= 1");
@@ -35,21 +30,13 @@ int check_params(alga_engine *e, const alga_break_params *p) {
     return ALGA_OK;
 }
 
-// `pl` names the buffers and every size of the placement the engine holds: n_columns sizes the column arrays here, n_hist - 1 is max_insert
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p && pl->d_state == (const uint8_t *) e->pl_state.p &&
-           pl->d_col_off == (const uint32_t *) e->pl_coloff.p && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p && pl->n_columns == e->pl_ncolumns &&
-           pl->n_columns <= 0xFFFFFFFEull && pl->n_hist >= 1 && (uint64_t) pl->n_hist == e->pl_nhist;
-}
-
 int break_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_polished *pol, const alga_break_params *p,
                hipStream_t s, alga_broken *out, alga_break_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = (uint64_t) pl->n_reads, T = (uint64_t) pl->n_targets, C = pl->n_columns;
     int rc;
-    BrEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->br_cnt, BR_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->br_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, BR_COUNTERS * sizeof(unsigned long long), s));
@@ -155,10 +142,9 @@ int break_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
         } catch (const std::bad_alloc &) {
             return alga_fail(e, ALGA_ERR_OUT_OF_MEMORY, "break: no host memory for the lengths of the N50s");
         }
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_span = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_cut = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_span))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_cut))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -174,30 +160,22 @@ extern "C" void alga_break_default_params(alga_break_params *p) {
 
 extern "C" int alga_break_placed_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_polished *pol,
                                         const alga_break_params *p, void *hip_stream, alga_broken *out, alga_break_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_break_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!nodes || !pl || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes, placements and out must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if ((rc = alga_check_twin_nodes(e, nodes, false))) return rc;
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "break: the node set does not have the placement's reads (n / 2 != n_reads)");
-    if (pol && (!e->po_valid || e->po_pl_serial != e->pl_serial || e->po_targets != e->pl_targets || pol->n_targets < 0 || (uint64_t) pol->n_targets != e->po_targets ||
-                pol->n_columns != e->po_columns || pol->n_columns != pl->n_columns || pol->d_words != (const uint32_t *) e->po_words.p))
+    if (pol && !alga_polished_is_current(e, pl, pol))
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_polish_placed_device call on this placement");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = break_impl(e, nodes, d_pair_off, pl, pol, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return break_impl(e, nodes, d_pair_off, pl, pol, p, call.s, out, info);
 }
 
 extern "C" int alga_write_broken_fasta_device(alga_engine *e, const alga_broken *brk, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!brk || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "broken and path must not be NULL");
     if (!e->br_valid || brk->n_targets < 0 || (uint64_t) brk->n_targets != e->br_targets || brk->n_pieces < 0 || (uint64_t) brk->n_pieces != e->br_pieces ||
         brk->n_columns != e->br_columns || brk->d_words != (const uint32_t *) e->br_words.p || brk->d_piece_off != (const uint32_t *) e->br_poff.p ||

@@ -14,17 +14,12 @@ using namespace alga;
 
 namespace {
 
-struct CsEvents {
-    hipEvent_t ev[3] = {};
-    ~CsEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int consensus_impl(alga_engine *e, const alga_nodes *nodes, const alga_unitigs *u, int32_t min_votes, int32_t flags, hipStream_t s, alga_consensus *out,
                    alga_consensus_info *info) {
     const uint64_t P = (uint64_t) u->n_pairs;
     int rc;
-    CsEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     // the sizes of the ragged arrays: the last entries of the two offset arrays
     unsigned long long totals[2] = {0, 0};
     if (P) {
@@ -86,9 +81,8 @@ int consensus_impl(alga_engine *e, const alga_nodes *nodes, const alga_unitigs *
         info->pairs = P; info->pairs_kept = e->h_counters[CS_KEPT]; info->trimmed_bases = e->h_counters[CS_TRIMMED];
         info->changed = e->h_counters[CS_CHANGED]; info->max_depth = e->h_counters[CS_MAX_DEPTH]; info->wide_words = wide;
         info->columns = e->ut_total_bases;
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); info->ms_vote = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); info->ms_window = t;
+        if ((rc = evs.ms(e, 0, 1, &info->ms_vote))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &info->ms_window))) return rc;
     }
     return ALGA_OK;
 }
@@ -116,6 +110,6 @@ extern "C" int alga_unitig_consensus_device(alga_engine *e, const alga_nodes *no
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = consensus_impl(e, nodes, u, min_votes, flags, s, out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }

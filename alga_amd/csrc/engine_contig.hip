@@ -19,11 +19,6 @@ using namespace alga;
 
 namespace {
 
-struct CtEvents {
-    hipEvent_t ev[6] = {};
-    ~CtEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int read_u32(alga_engine *e, const void *d_src, hipStream_t s, uint64_t *out) {
     HIP_TRY(e, hipMemcpyAsync(e->h_counters, d_src, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -36,8 +31,8 @@ int contigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
     const int32_t n = nodes->n;
     const size_t N = (size_t) n;
     int rc;
-    CtEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<6> evs;
+    if ((rc = evs.create(e))) return rc;
     const size_t n_ucnt = UT_COUNTERS + ALGA_UT_MAX_ROUNDS;
     if ((rc = alga_ensure(e, e->ut_cnt, n_ucnt * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->ct_cnt, CT_COUNTERS * sizeof(unsigned long long)))) return rc;
@@ -251,7 +246,7 @@ int contigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
         info->longest_nodes = c[CT_LONGEST_NODES]; info->longest_bases = c[CT_LONGEST_BASES]; info->total_bases = c[CT_TOTAL_BASES];
         info->rank_rounds = rank_rounds_total;
         double *part[5] = {&info->ms_sym, &info->ms_rounds, &info->ms_layout, &info->ms_seq, &info->ms_edges};
-        for (int k = 0; k < 5; k++) { float t = 0.0f; HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[k], evs.ev[k + 1])); *part[k] = t; }
+        for (int k = 0; k < 5; k++) if ((rc = evs.ms(e, k, k + 1, part[k]))) return rc;
     }
     return ALGA_OK;
 }
@@ -276,6 +271,6 @@ extern "C" int alga_contigs_device(alga_engine *e, const alga_nodes *nodes, cons
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = contigs_impl(e, nodes, (const alga_edge_dev *) d_edges, n_edges, max_offset, s, out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }

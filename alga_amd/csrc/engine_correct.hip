@@ -17,11 +17,6 @@ using namespace alga;
 
 namespace {
 
-struct CrEvents {
-    hipEvent_t ev[4] = {};
-    ~CrEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 // counters (64-bit words of cr_cnt): the emit cursor, the two flags, the run heads of all slices, then the sums of k_cr_fix's table
 enum { CC_CURSOR = 0, CC_BAD_TWIN, CC_BAD_DIR, CC_DISTINCT, CC_FIX, CC_WORDS = CC_FIX + CR_COLS };
 
@@ -48,8 +43,8 @@ int alga_correct_impl(alga_engine *e, uint32_t *d_rows, int32_t stride, const in
     const uint64_t R = (uint64_t) n_nodes / 2;
     if (R == 0) return ALGA_OK;
     int rc;
-    CrEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<4> evs;
+    if ((rc = evs.create(e))) return rc;
     const int fix_blocks = cr_fix_blocks(R, e->n_cu);
     const size_t table_words = std::max<size_t>((size_t) CR_HIST_BLOCKS * CR_HIST_COLS, std::max<size_t>((size_t) fix_blocks * CR_COLS, CR_RUNS_BLOCKS));
     if ((rc = alga_ensure(e, e->cr_cnt, CC_WORDS * sizeof(unsigned long long)))) return rc;
@@ -147,36 +142,29 @@ int alga_correct_impl(alga_engine *e, uint32_t *d_rows, int32_t stride, const in
     out.kmers_distinct = hc[CC_DISTINCT];
     out.runs = hc[CC_FIX + CR_RUNS]; out.runs_fixed = hc[CC_FIX + CR_FIXED]; out.runs_ambiguous = hc[CC_FIX + CR_AMBIGUOUS];
     out.runs_no_candidate = hc[CC_FIX + CR_NO_CANDIDATE]; out.runs_skipped = hc[CC_FIX + CR_SKIPPED]; out.reads_changed = hc[CC_FIX + CR_CHANGED];
-    float t = 0.0f;
-    HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); out.ms_count = t;
-    HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); out.ms_index = t;
-    HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[2], evs.ev[3])); out.ms_fix = t;
-    out.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if ((rc = evs.ms(e, 0, 1, &out.ms_count))) return rc;
+    if ((rc = evs.ms(e, 1, 2, &out.ms_index))) return rc;
+    if ((rc = evs.ms(e, 2, 3, &out.ms_fix))) return rc;
+    out.ms_total = alga_ms_since(t0);
     if (info) *info = out;
     return ALGA_OK;
 }
 
 extern "C" int alga_correct_reads_device(alga_engine *e, uint32_t *d_rows, int32_t stride_words, const int32_t *d_len, int64_t n_nodes, const alga_correct_params *p,
                                          void *hip_stream, alga_correct_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_correct_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = alga_correct_check_params(e, p))) return rc;
     if (n_nodes < 0 || (n_nodes & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n_nodes must be even and >= 0");
     if (n_nodes >= 0x7FFFFFFELL) return alga_fail(e, ALGA_ERR_CAPACITY, "too many nodes");
     if (n_nodes && (!d_rows || !d_len || stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = alga_correct_impl(e, d_rows, stride_words, d_len, n_nodes, p, s, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return alga_correct_impl(e, d_rows, stride_words, d_len, n_nodes, p, call.s, info);
 }
 
 extern "C" int alga_correct_parsed_reads(alga_engine *e, alga_parsed_reads *pr, const alga_correct_params *p, alga_correct_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_correct_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = alga_correct_check_params(e, p))) return rc;
     if (!pr) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "parsed reads must not be NULL");

@@ -21,11 +21,6 @@ using namespace alga;
 
 namespace {
 
-struct ExEvents {
-    hipEvent_t ev[6] = {};
-    ~ExEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int read_u32(alga_engine *e, const void *d_src, hipStream_t s, uint64_t *out) {
     HIP_TRY(e, hipMemcpyAsync(e->h_counters, d_src, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -46,8 +41,8 @@ int extend_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_o
     const uint64_t P = (uint64_t) u->n_pairs, n2 = 2 * P, mu_in = u->n_edges;
     const size_t N2 = (size_t) n2;
     int rc;
-    ExEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<6> evs;
+    if ((rc = evs.create(e))) return rc;
     const size_t n_ucnt = UT_COUNTERS + ALGA_UT_MAX_ROUNDS;
     if ((rc = alga_ensure(e, e->ut_cnt, n_ucnt * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->ex_cnt, EX_COUNTERS * sizeof(unsigned long long)))) return rc;
@@ -198,7 +193,7 @@ int extend_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_o
         info->longest_nodes = c[EX_LONGEST_NODES]; info->longest_bases = c[EX_LONGEST_BASES]; info->total_bases = c[EX_TOTAL_BASES];
         info->rank_rounds = rounds + rounds2;
         double *part[5] = {&info->ms_count, &info->ms_paths, &info->ms_layout, &info->ms_seq, &info->ms_edges};
-        for (int k = 0; k < 5; k++) { float t = 0.0f; HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[k], evs.ev[k + 1])); *part[k] = t; }
+        for (int k = 0; k < 5; k++) if ((rc = evs.ms(e, k, k + 1, part[k]))) return rc;
     }
     return ALGA_OK;
 }
@@ -225,7 +220,7 @@ extern "C" int alga_extend_contigs_device(alga_engine *e, const alga_nodes *node
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = extend_impl(e, nodes, d_pair_off, u, min_chain_weight, min_connections, max_insert, s, out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }
 

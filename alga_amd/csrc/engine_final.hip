@@ -17,11 +17,6 @@ using namespace alga;
 
 namespace {
 
-struct FcEvents {
-    hipEvent_t ev[3] = {};
-    ~FcEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 // max_capped_len: the longest capped length if the caller knows it (the final call's number kernel), -1: ask the device (and check the lengths)
 int trim_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long *d_begin, const int32_t *d_len, int32_t n, int32_t threshold,
               int64_t max_capped_len, hipStream_t s, int32_t *d_trim_left, uint64_t *edges_out) {
@@ -85,8 +80,8 @@ int final_impl(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons
     const uint32_t P = (uint32_t) u->n_pairs;
     const size_t reads = (size_t) e->ut_n_nodes / 2;
     int rc;
-    FcEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     e->fc_valid = false;
     if ((rc = alga_ensure(e, e->fc_cnt, FC_COUNTERS * sizeof(unsigned long long)))) return rc;
     for (DevBuf *b : {&e->fc_keys[0], &e->fc_keys[1], &e->fc_vals, &e->fc_list[0], &e->fc_list[1], &e->fc_ids, &e->fc_flag})
@@ -160,9 +155,8 @@ int final_impl(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons
     if (info) {
         info->pairs = P; info->n_short = n_short; info->rejected = n_rej; info->accepted = n_acc - away; info->trimmed_away = away;
         info->filter_rounds = rounds; info->trim_edges = trim_edges;
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); info->ms_filter = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); info->ms_trim = t;
+        if ((rc = evs.ms(e, 0, 1, &info->ms_filter))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &info->ms_trim))) return rc;
     }
     return ALGA_OK;
 }
@@ -212,15 +206,13 @@ extern "C" int alga_final_contigs_device(alga_engine *e, const alga_unitigs *u, 
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = final_impl(e, u, cons, min_length, new_reads_percent, trim_threshold, s, out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }
 
 extern "C" int alga_write_final_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin, const char *path,
                                              alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!u || !cons || !fin || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs, consensus, final contigs and path must not be NULL");
     const char *why = nullptr;
     if (!alga_final_is_current(e, u, cons, fin, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);

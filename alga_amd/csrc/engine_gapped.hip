@@ -20,11 +20,6 @@ using namespace alga;
 
 namespace {
 
-struct GpEvents {
-    hipEvent_t ev[5] = {};
-    ~GpEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_gapped_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "gapped placement parameters must not be NULL");
     if (p->k < 8 || p->k > 31) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "gapped placement: k must be in [8, 31]");
@@ -34,21 +29,13 @@ int check_params(alga_engine *e, const alga_gapped_params *p) {
     return ALGA_OK;
 }
 
-// `pl` names the buffers and sizes of the placement the engine holds
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->n_columns == e->pl_ncolumns && pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p &&
-           pl->d_state == (const uint8_t *) e->pl_state.p && pl->d_col_off == (const uint32_t *) e->pl_coloff.p &&
-           pl->d_cover == (const uint32_t *) e->pl_cover.p + 1 && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p && pl->n_columns <= 0xFFFFFFFEull;
-}
-
 int gapped_impl(alga_engine *e, const alga_nodes *nodes, const uint32_t *d_words, const unsigned long long *d_begin, const int32_t *d_len, const alga_placements *pl,
                 const alga_gapped_params *p, hipStream_t s, alga_gapped *out, alga_gapped_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = (uint64_t) pl->n_reads, T = (uint64_t) pl->n_targets, columns = pl->n_columns;
     int rc;
-    GpEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<5> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->gp_cnt, GP_COUNTERS * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->gp_flag, (R + 2) * sizeof(uint32_t)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->gp_cnt.p, *hc = e->h_counters;
@@ -146,16 +133,16 @@ int gapped_impl(alga_engine *e, const alga_nodes *nodes, const uint32_t *d_words
     out->d_target = go.target; out->d_pos = go.pos; out->d_end = go.end; out->d_edits = go.edits; out->d_state = go.state;
     out->d_cigar_off = cig_off; out->d_cigar = (const uint32_t *) e->gp_cigar.p; out->d_cover = cover;
     out->d_t_reads = (const uint64_t *) tstat; out->d_t_bases = (const uint64_t *) (tstat + T); out->d_t_edits = (const uint64_t *) (tstat + 2 * T);
+    e->gp_out = *out;                                                 // what alga_gapped_is_current compares a consumer's handle with
     if (info) {
         alga_gapped_info o{};
         o.tried = n_list; o.skipped_long = skipped_long; o.placed = hc[GP_PLACED]; o.unique = hc[GP_UNIQUE]; o.with_indel = hc[GP_WITH_INDEL]; o.edits = hc[GP_EDITS];
         o.insertions = hc[GP_INSERTIONS]; o.deletions = hc[GP_DELETIONS]; o.candidates = hc[GP_CANDIDATES]; o.seeds = hc[GP_SEEDS]; o.seeds_over_max_occ = hc[GP_SEEDS_OVER];
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_index = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_place = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[2], evs.ev[3])); o.ms_trace = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[3], evs.ev[4])); o.ms_depth = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_index))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_place))) return rc;
+        if ((rc = evs.ms(e, 2, 3, &o.ms_trace))) return rc;
+        if ((rc = evs.ms(e, 3, 4, &o.ms_depth))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -171,29 +158,22 @@ extern "C" void alga_gapped_default_params(alga_gapped_params *p) {
 
 extern "C" int alga_place_gapped_device(alga_engine *e, const alga_nodes *nodes, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
                                         const alga_placements *pl, const alga_gapped_params *p, void *hip_stream, alga_gapped *out, alga_gapped_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gapped_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!nodes || !pl || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes, placements and out must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->words || !nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
+    if ((rc = alga_check_twin_nodes(e, nodes, true))) return rc;
     if (n_targets < 0 || (n_targets && (!d_words || !d_begin || !d_len))) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad target arrays");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "gapped placement: the node set does not have the placement's reads (n / 2 != n_reads)");
     if ((int64_t) n_targets != pl->n_targets) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "gapped placement: the targets are not the placement's (n_targets differs)");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = gapped_impl(e, nodes, d_words, (const unsigned long long *) d_begin, d_len, pl, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return gapped_impl(e, nodes, d_words, (const unsigned long long *) d_begin, d_len, pl, p, call.s, out, info);
 }
 
 extern "C" int alga_write_gapped_tsv_device(alga_engine *e, const alga_gapped *gp, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!gp || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "gapped placements and path must not be NULL");
     if (!e->gp_valid || gp->n_reads < 0 || (uint64_t) gp->n_reads != e->gp_reads || gp->n_cigar != e->gp_ncigar || gp->d_target != (const int32_t *) e->gp_target.p ||
         gp->d_pos != (const int32_t *) e->gp_rpos.p || gp->d_end != (const int32_t *) e->gp_end.p || gp->d_edits != (const uint8_t *) e->gp_edits.p ||

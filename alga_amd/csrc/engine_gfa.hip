@@ -34,20 +34,14 @@ bool write_all(int fd, const char *p, size_t bytes, uint64_t at) {
     return true;
 }
 
-struct GfaEvents {
-    std::vector<hipEvent_t> ev;
-    ~GfaEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int gfa_impl(alga_engine *e, const AlgaTextJob &job, const char *path, alga_gfa_info *info, int &fd) {
     hipStream_t s = e->own_stream;
     const uint64_t N = job.items;
     int rc;
-    GfaEvents evs;
+    AlgaEvents<12> evs;
     // [0, 1] checks .. scan, [2, 3] the copies' ends (one per pinned slot), [4 + 2 * (k % 4), 5 + 2 * (k % 4)] the formatting of chunk k
     // (read back once the write of chunk k is done, two chunks later: four pairs are never overwritten before that)
-    evs.ev.assign(12, nullptr);
-    for (int k = 0; k < 12; k++) HIP_TRY(e, hipEventCreate(&evs.ev[(size_t) k]));
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->counters, GFA_COUNTERS * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_sizes, (size_t) (N + 1) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->gfa_off, (size_t) (N + 1) * sizeof(unsigned long long)))) return rc;
@@ -182,7 +176,7 @@ int alga_text_job_run(alga_engine *e, const AlgaTextJob &job, const char *path, 
         if (fd >= 0) { close(fd); unlink(path); }                  // no partial file is left behind
         return rc;
     }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }
 

@@ -25,11 +25,6 @@ using namespace alga;
 
 namespace {
 
-struct GrEvents {
-    hipEvent_t ev[4] = {};
-    ~GrEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_grow_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "grow parameters must not be NULL");
     if (p->k < 8 || p->k > 31) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "grow: k must be in [8, 31]");
@@ -43,22 +38,14 @@ int check_params(alga_engine *e, const alga_grow_params *p) {
     return ALGA_OK;
 }
 
-// `pl` names the buffers and every size of the placement the engine holds: n_columns sizes the column arrays here
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p && pl->d_state == (const uint8_t *) e->pl_state.p &&
-           pl->d_col_off == (const uint32_t *) e->pl_coloff.p && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p && pl->n_columns == e->pl_ncolumns &&
-           pl->n_columns <= 0xFFFFFFFEull && pl->n_hist >= 1 && (uint64_t) pl->n_hist == e->pl_nhist;
-}
-
 int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polished *pol, const alga_grow_params *p, hipStream_t s, alga_grown *out,
               alga_grow_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = (uint64_t) pl->n_reads, T = (uint64_t) pl->n_targets, C = pl->n_columns, G = (uint64_t) p->max_grow, E = 2 * T;
     if (E * G > (1ull << 30)) return alga_fail(e, ALGA_ERR_CAPACITY, "grow: 2 * n_targets * max_grow exceeds 2^30");
     int rc;
-    GrEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<4> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->gr_cnt, GR_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->gr_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, GR_COUNTERS * sizeof(unsigned long long), s));
@@ -123,7 +110,7 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
     // the result, into the set that is not the current one
-    const int nxt = e->gr_valid ? 1 - e->gr_cur : e->gr_cur;
+    const int nxt = alga_other_set(e->gr_valid, e->gr_cur);
     alga_engine::GrowSet &rs = e->gr_set[nxt];
     const size_t count_bytes = (size_t) (E * G) * 4 * sizeof(uint32_t);
     for (DevBuf *b : {&rs.end, &rs.over}) if ((rc = alga_ensure(e, *b, (R + 1) * sizeof(int32_t)))) return rc;
@@ -192,11 +179,10 @@ int grow_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl
         } catch (const std::bad_alloc &) {
             return alga_fail(e, ALGA_ERR_OUT_OF_MEMORY, "grow: no host memory for the lengths of the N50s");
         }
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_index = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_place = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[2], evs.ev[3])); o.ms_build = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_index))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_place))) return rc;
+        if ((rc = evs.ms(e, 2, 3, &o.ms_build))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -212,30 +198,22 @@ extern "C" void alga_grow_default_params(alga_grow_params *p) {
 
 extern "C" int alga_grow_placed_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polished *pol, const alga_grow_params *p,
                                        void *hip_stream, alga_grown *out, alga_grow_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_grow_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!nodes || !pl || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes, placements and out must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->words || !nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if ((rc = alga_check_twin_nodes(e, nodes, true))) return rc;
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "grow: the node set does not have the placement's reads (n / 2 != n_reads)");
-    if (pol && (!e->po_valid || e->po_pl_serial != e->pl_serial || e->po_targets != e->pl_targets || pol->n_targets < 0 || (uint64_t) pol->n_targets != e->po_targets ||
-                pol->n_columns != e->po_columns || pol->n_columns != pl->n_columns || pol->d_words != (const uint32_t *) e->po_words.p))
+    if (pol && !alga_polished_is_current(e, pl, pol))
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_polish_placed_device call on this placement");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = grow_impl(e, nodes, pl, pol, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return grow_impl(e, nodes, pl, pol, p, call.s, out, info);
 }
 
 extern "C" int alga_write_grown_fasta_device(alga_engine *e, const alga_grown *grown, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!grown || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "grown and path must not be NULL");
     const alga_engine::GrowSet &rs = e->gr_set[e->gr_cur];
     if (!e->gr_valid || grown->n_targets < 0 || (uint64_t) grown->n_targets != e->gr_targets || grown->n_columns != e->gr_columns ||

@@ -190,6 +190,7 @@ struct alga_engine {
     uint64_t    pl_targets = 0, pl_reads = 0;      // ... of this many reads on this many targets
     uint64_t    pl_ncolumns = 0, pl_nhist = 0;      // ... its col_off[pl_targets] and the bins of its insert histogram (max_insert + 1)
     uint64_t    pl_final_epoch = 0;                // ... made on the final result of this epoch (0: on caller's targets)
+    alga_placements pl_out{};                      // ... the handle that was handed out for it (stage_common.h: alga_placement_is_current)
     uint64_t    fc_epoch = 0;                      // counts the alga_final_contigs_device calls that wrote a result
     int         opt_place_dir_bits = 0;            // option "place_dir_bits": bits of the seed index's directory, 0 = about two positions per bucket
     // the placed targets voted again (engine_polish.hip).  Workspaces: counters, the (first column, node) pairs before and after the sort, the
@@ -200,6 +201,7 @@ struct alga_engine {
     bool        po_valid = false;                  // the result buffers hold a polish
     uint64_t    po_targets = 0, po_columns = 0;    // ... of this many targets and columns
     uint64_t    po_final_epoch = 0;                // ... of a placement on the final result of this epoch (0: on caller's targets)
+    alga_polished po_out{};                        // ... the handle that was handed out for it (alga_polished_is_current)
     uint64_t    pl_serial = 0, po_pl_serial = 0;   // counts the placement results written; the one the polish at hand was made from
     // scaffolds from split pairs (engine_scaffold.hip).  Workspaces: counters, the link keys / judging reads before and after the sort, the spans,
     // the heads and their scan, the first link of every bundle, best / second / choice / partner / join bundle per end, the two sets of list
@@ -246,6 +248,7 @@ struct alga_engine {
     uint64_t    gp_reads = 0, gp_targets = 0, gp_columns = 0, gp_ncigar = 0;   // ... of this many reads, targets and columns; its runs
     uint64_t    gp_pl_serial = 0;                  // ... made from this placement result
     uint64_t    gp_serial = 0;                     // counts the gapped results written
+    alga_gapped gp_out{};                          // the handle that was handed out for the gapped result at hand (alga_gapped_is_current)
     // the pair calls over both passes (engine_sam.hip).  Workspace: counters.  The result: FLAG and TLEN per read, the insert histogram
     DevBuf      sj_cnt, sj_flag, sj_tlen, sj_hist;
     bool        sj_valid = false;                  // the result buffers hold pair calls
@@ -438,3 +441,5 @@ inline int alga_check_launch(alga_engine *e, const char *what) {
     if (err != hipSuccess) return alga_fail(e, ALGA_ERR_HIP, what, err);
     return ALGA_OK;
 }
+
+#include "stage_common.h"

@@ -22,11 +22,6 @@ using namespace alga;
 
 namespace {
 
-struct IpEventsHip {
-    hipEvent_t ev[4] = {};
-    ~IpEventsHip() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_ipolish_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "indel polish parameters must not be NULL");
     if (p->min_cover < 1) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "indel polish: min_cover must be >= 1");
@@ -37,31 +32,14 @@ int check_params(alga_engine *e, const alga_ipolish_params *p) {
     return ALGA_OK;
 }
 
-// `pl` names the buffers and sizes of the placement the engine holds
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->n_columns == e->pl_ncolumns && pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p &&
-           pl->d_state == (const uint8_t *) e->pl_state.p && pl->d_col_off == (const uint32_t *) e->pl_coloff.p && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p &&
-           pl->n_columns <= 0xFFFFFFFEull;
-}
-
-// `gp` names the buffers and sizes of the gapped result the engine holds, and that was made from the placement at hand
-bool gapped_is_current(const alga_engine *e, const alga_gapped *gp) {
-    return e->gp_valid && e->gp_pl_serial == e->pl_serial && gp->n_reads >= 0 && (uint64_t) gp->n_reads == e->gp_reads && (uint64_t) gp->n_reads == e->pl_reads &&
-           gp->n_targets >= 0 && (uint64_t) gp->n_targets == e->gp_targets && gp->n_columns == e->gp_columns && gp->n_columns == e->pl_ncolumns &&
-           gp->n_cigar == e->gp_ncigar && gp->d_target == (const int32_t *) e->gp_target.p && gp->d_pos == (const int32_t *) e->gp_rpos.p &&
-           gp->d_end == (const int32_t *) e->gp_end.p && gp->d_state == (const uint8_t *) e->gp_state.p && gp->d_cigar_off == (const uint32_t *) e->gp_cigoff.p &&
-           gp->d_cigar == (const uint32_t *) e->gp_cigar.p;
-}
-
 int ipolish_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_gapped *gp, const alga_ipolish_params *p, hipStream_t s, alga_ipolished *out,
                  alga_ipolish_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = (uint64_t) pl->n_reads, T = (uint64_t) pl->n_targets, columns = pl->n_columns;
     const bool want_counts = (p->flags & ALGA_IPOLISH_COUNTS) != 0;
     int rc;
-    IpEventsHip evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<4> evs;
+    if ((rc = evs.create(e))) return rc;
     constexpr int N_CNT = IP_COUNTERS + PO_COUNTERS;
     if ((rc = alga_ensure(e, e->ip_cnt, N_CNT * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->ip_cnt.p, *pcnt = cnt + IP_COUNTERS, *hc = e->h_counters, *hp = hc + IP_COUNTERS;
@@ -113,7 +91,7 @@ int ipolish_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements 
     const size_t temp32 = rsort_u32_pairs_temp_bytes(R), temp64 = rsort_u64_pairs_temp_bytes(n_ins);
     if ((rc = alga_ensure(e, e->sort_temp, std::max(temp32, temp64)))) return rc;
     if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(columns + 2)))) return rc;
-    const int nxt = e->ip_valid ? 1 - e->ip_cur : e->ip_cur;
+    const int nxt = alga_other_set(e->ip_valid, e->ip_cur);
     alga_engine::IpolishSet &rs = e->ip_set[nxt];
     if ((rc = alga_ensure(e, rs.len, (T + 1) * sizeof(int32_t)))) return rc;
     if ((rc = alga_ensure(e, rs.coloff, (T + 2) * sizeof(uint32_t)))) return rc;
@@ -225,11 +203,10 @@ int ipolish_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements 
     if (info) {
         o.voted_columns = hc[IP_VOTED]; o.substituted = hc[IP_SUBST]; o.deleted = hc[IP_DELETED]; o.inserted_slots = hc[IP_INS_SLOTS]; o.inserted_bases = hc[IP_INS_BASES];
         o.ambiguous_columns = hc[IP_AMB_COLS]; o.ambiguous_slots = hc[IP_AMB_SLOTS]; o.columns_after = NC; o.max_cover = hc[IP_MAX_COVER];
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_votes = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_inserts = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[2], evs.ev[3])); o.ms_build = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_votes))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_inserts))) return rc;
+        if ((rc = evs.ms(e, 2, 3, &o.ms_build))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -260,28 +237,21 @@ extern "C" void alga_ipolish_default_params(alga_ipolish_params *p) {
 
 extern "C" int alga_polish_indels_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_gapped *gp, const alga_ipolish_params *p,
                                          void *hip_stream, alga_ipolished *out, alga_ipolish_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_ipolish_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!nodes || !pl || !gp || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes, placements, gapped placements and out must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->words || !nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
-    if (!gapped_is_current(e, gp)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_place_gapped_device call on this placement");
+    if ((rc = alga_check_twin_nodes(e, nodes, true))) return rc;
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if (!alga_gapped_is_current(e, gp)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_place_gapped_device call on this placement");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "indel polish: the node set does not have the placement's reads (n / 2 != n_reads)");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = ipolish_impl(e, nodes, pl, gp, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return ipolish_impl(e, nodes, pl, gp, p, call.s, out, info);
 }
 
 extern "C" int alga_write_ipolished_fasta_device(alga_engine *e, const alga_ipolished *ipol, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!ipol || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "the indel polish result and path must not be NULL");
     int rc;
     if ((rc = ipolished_is_current(e, ipol))) return rc;
@@ -293,9 +263,7 @@ extern "C" int alga_write_ipolished_fasta_device(alga_engine *e, const alga_ipol
 }
 
 extern "C" int alga_write_ipolish_events_tsv_device(alga_engine *e, const alga_ipolished *ipol, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!ipol || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "the indel polish result and path must not be NULL");
     int rc;
     if ((rc = ipolished_is_current(e, ipol))) return rc;

@@ -24,11 +24,6 @@ using namespace alga;
 
 namespace {
 
-struct MgEvents {
-    hipEvent_t ev[4] = {};
-    ~MgEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_merge_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "merge parameters must not be NULL");
     if (p->k < 8 || p->k > 31) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "merge: k must be in [8, 31]");
@@ -45,8 +40,8 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t T = (uint64_t) n_targets, E = 2 * T;
     int rc;
-    MgEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<4> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->mg_cnt, MG_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->mg_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, MG_COUNTERS * sizeof(unsigned long long), s));
@@ -93,7 +88,7 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
     // the result, into the set that is not the current one
-    const int nxt = e->mg_valid ? 1 - e->mg_cur : e->mg_cur;
+    const int nxt = alga_other_set(e->mg_valid, e->mg_cur);
     alga_engine::MergeSet &rs = e->mg_set[nxt];
     for (DevBuf *b : {&rs.partner, &rs.olen}) if ((rc = alga_ensure(e, *b, (E + 2) * sizeof(int32_t)))) return rc;
     for (DevBuf *b : {&rs.mm, &rs.hits, &rs.estate}) if ((rc = alga_ensure(e, *b, E + 16))) return rc;
@@ -180,11 +175,10 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
         } catch (const std::bad_alloc &) {
             return alga_fail(e, ALGA_ERR_OUT_OF_MEMORY, "merge: no host memory for the lengths of the N50s");
         }
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_index = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_overlap = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[2], evs.ev[3])); o.ms_build = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_index))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_overlap))) return rc;
+        if ((rc = evs.ms(e, 2, 3, &o.ms_build))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -200,25 +194,19 @@ extern "C" void alga_merge_default_params(alga_merge_params *p) {
 
 extern "C" int alga_merge_targets_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
                                          const alga_merge_params *p, void *hip_stream, alga_merged *out, alga_merge_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_merge_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "out must not be NULL");
     if (n_targets < 0 || (n_targets && (!d_words || !d_begin || !d_len))) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad target arrays");
     if (n_targets > (1 << 30)) return alga_fail(e, ALGA_ERR_CAPACITY, "merge: more than 2^30 targets");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = merge_impl(e, d_words, (const unsigned long long *) d_begin, d_len, n_targets, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return merge_impl(e, d_words, (const unsigned long long *) d_begin, d_len, n_targets, p, call.s, out, info);
 }
 
 extern "C" int alga_write_merged_fasta_device(alga_engine *e, const alga_merged *merged, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!merged || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "merged and path must not be NULL");
     const alga_engine::MergeSet &rs = e->mg_set[e->mg_cur];
     if (!e->mg_valid || merged->n_targets < 0 || (uint64_t) merged->n_targets != e->mg_targets || merged->n_merged < 0 || (uint64_t) merged->n_merged != e->mg_merged ||

@@ -20,11 +20,6 @@ using namespace alga;
 
 namespace {
 
-struct PlEvents {
-    hipEvent_t ev[4] = {};
-    ~PlEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_place_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "placement parameters must not be NULL");
     if (p->k < 8 || p->k > 31) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "placement: k must be in [8, 31]");
@@ -37,9 +32,7 @@ int check_params(alga_engine *e, const alga_place_params *p) {
 
 int check_nodes(alga_engine *e, const alga_nodes *nodes) {
     if (!nodes) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->words || !nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    return ALGA_OK;
+    return alga_check_twin_nodes(e, nodes, true);
 }
 
 int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const uint32_t *d_words, const unsigned long long *d_begin, const int32_t *d_len,
@@ -47,8 +40,8 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t n = (uint64_t) nodes->n, R = n / 2, T = (uint64_t) n_targets;
     int rc;
-    PlEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<4> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->pl_cnt, PL_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->pl_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, PL_COUNTERS * sizeof(unsigned long long), s));
@@ -134,6 +127,7 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     out->d_col_off = col_off; out->d_cover = scan + 1;
     out->d_t_reads = (const uint64_t *) tstat; out->d_t_bases = (const uint64_t *) (tstat + T); out->d_t_mismatches = (const uint64_t *) (tstat + 2 * T);
     out->d_t_uncovered = (const uint64_t *) (tstat + 3 * T); out->d_insert_hist = (const uint64_t *) hist;
+    e->pl_out = *out;                                                 // what alga_placement_is_current compares a consumer's handle with
     if (info) {
         alga_place_info o{};
         o.reads = R; o.placed = hc[PL_PLACED]; o.unique = hc[PL_UNIQUE]; o.multi = o.placed - o.unique; o.unplaced = R - o.placed;
@@ -147,11 +141,10 @@ int place_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
             for (size_t i = 0; i < n_hist; i++) { cum += h[i]; if (cum >= half) { o.insert_median = (int64_t) i; break; } }
             o.insert_mean_x100 = (int64_t) ((100ull * hc[PL_INSERT_SUM]) / o.pairs_proper);
         }
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_index = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_place = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[2], evs.ev[3])); o.ms_depth = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_index))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_place))) return rc;
+        if ((rc = evs.ms(e, 2, 3, &o.ms_depth))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -167,55 +160,45 @@ extern "C" void alga_place_default_params(alga_place_params *p) {
 
 extern "C" int alga_place_reads_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const uint32_t *d_words, const uint64_t *d_begin,
                                        const int32_t *d_len, int32_t n_targets, const alga_place_params *p, void *hip_stream, alga_placements *out, alga_place_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_place_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if ((rc = check_nodes(e, nodes))) return rc;
     if (!out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "out must not be NULL");
     if (n_targets < 0 || (n_targets && (!d_words || !d_begin || !d_len))) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad target arrays");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = place_impl(e, nodes, d_pair_off, d_words, (const unsigned long long *) d_begin, d_len, n_targets, p, s, 0, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return place_impl(e, nodes, d_pair_off, d_words, (const unsigned long long *) d_begin, d_len, n_targets, p, call.s, 0, out, info);
 }
 
 extern "C" int alga_place_reads_on_final_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_unitigs *u, const alga_consensus *cons,
                                                 const alga_final_contigs *fin, const alga_place_params *p, void *hip_stream, alga_placements *out, alga_place_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_place_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if ((rc = check_nodes(e, nodes))) return rc;
     if (!u || !cons || !fin || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs, consensus, final contigs and out must not be NULL");
     const char *why = nullptr;
     if (!alga_final_is_current(e, u, cons, fin, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    hipStream_t s = call.s;
     const uint64_t T = (uint64_t) fin->n_accepted;
     if ((rc = alga_ensure(e, e->pl_fbegin, (T + 1) * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->pl_flen, (T + 1) * sizeof(int32_t)))) return rc;
     launch_pl_final_targets((const unsigned long long *) u->d_word_off, fin->d_verdict, fin->d_order, fin->d_begin, fin->d_len, T, (unsigned long long *) e->pl_fbegin.p,
                             (int32_t *) e->pl_flen.p, s);
     if ((rc = alga_check_launch(e, "k_pl_final_targets"))) return rc;
-    rc = place_impl(e, nodes, d_pair_off, cons->d_words, (const unsigned long long *) e->pl_fbegin.p, (const int32_t *) e->pl_flen.p, (int32_t) T, p, s, e->fc_epoch, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    return place_impl(e, nodes, d_pair_off, cons->d_words, (const unsigned long long *) e->pl_fbegin.p, (const int32_t *) e->pl_flen.p, (int32_t) T, p, s, e->fc_epoch, out, info);
 }
 
 extern "C" int alga_write_final_fasta_depth_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin,
                                                    const alga_placements *pl, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!u || !cons || !fin || !pl || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs, consensus, final contigs, placements and path must not be NULL");
     const char *why = nullptr;
     if (!alga_final_is_current(e, u, cons, fin, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
-    if (!e->pl_valid || e->pl_final_epoch == 0 || e->pl_final_epoch != e->fc_epoch || (uint64_t) pl->n_targets != e->pl_targets || e->pl_targets != (uint64_t) fin->n_accepted ||
-        pl->d_t_reads != (const uint64_t *) e->pl_tstat.p || pl->d_t_bases != (const uint64_t *) e->pl_tstat.p + e->pl_targets)
+    if (!alga_placement_is_current(e, pl) || e->pl_final_epoch == 0 || e->pl_final_epoch != e->fc_epoch || e->pl_targets != (uint64_t) fin->n_accepted)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_place_reads_on_final_device call on this final result");
     HIP_TRY(e, hipSetDevice(e->device));
     const PlFasta f{cons->d_words, (const unsigned long long *) u->d_word_off, fin->d_verdict, fin->d_order, fin->d_begin, fin->d_len,

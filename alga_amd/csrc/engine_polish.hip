@@ -17,11 +17,6 @@ using namespace alga;
 
 namespace {
 
-struct PoEvents {
-    hipEvent_t ev[3] = {};
-    ~PoEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_polish_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "polish parameters must not be NULL");
     if (p->min_cover < 1) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "polish: min_cover must be >= 1");
@@ -30,20 +25,13 @@ int check_params(alga_engine *e, const alga_polish_params *p) {
     return ALGA_OK;
 }
 
-// `pl` names the buffers and sizes of the placement the engine holds
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p && pl->d_state == (const uint8_t *) e->pl_state.p &&
-           pl->d_col_off == (const uint32_t *) e->pl_coloff.p && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p && pl->n_columns <= 0xFFFFFFFEull;
-}
-
 int polish_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polish_params *p, hipStream_t s, alga_polished *out, alga_polish_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = (uint64_t) pl->n_reads, T = (uint64_t) pl->n_targets, columns = pl->n_columns;
     const bool want_counts = (p->flags & ALGA_POLISH_COUNTS) != 0;
     int rc;
-    PoEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->po_cnt, PO_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->po_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, PO_COUNTERS * sizeof(unsigned long long), s));
@@ -116,14 +104,14 @@ int polish_impl(alga_engine *e, const alga_nodes *nodes, const alga_placements *
     out->d_col_off = col_off; out->d_words = words; out->d_changed_cols = (const uint32_t *) e->po_ccols.p; out->d_changed_bases = (const uint8_t *) e->po_cbases.p;
     out->d_t_changed = (const uint64_t *) tstat; out->d_t_ambiguous = (const uint64_t *) (tstat + T);
     out->d_counts = want_counts ? (const uint32_t *) e->po_counts.p : nullptr;
+    e->po_out = *out;                                                 // what alga_polished_is_current compares a consumer's handle with
     if (info) {
         alga_polish_info o{};
         o.columns = columns; o.voters = voters; o.votes = votes; o.voted_columns = hc[PO_VOTED]; o.changed = n_changed; o.ambiguous = hc[PO_AMBIGUOUS];
         o.max_cover = hc[PO_MAX_COVER];
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_sort = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_vote = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_sort))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_vote))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -139,39 +127,30 @@ extern "C" void alga_polish_default_params(alga_polish_params *p) {
 
 extern "C" int alga_polish_placed_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_polish_params *p, void *hip_stream,
                                          alga_polished *out, alga_polish_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_polish_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!nodes || !pl || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes, placements and out must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->words || !nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if ((rc = alga_check_twin_nodes(e, nodes, true))) return rc;
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "polish: the node set does not have the placement's reads (n / 2 != n_reads)");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = polish_impl(e, nodes, pl, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return polish_impl(e, nodes, pl, p, call.s, out, info);
 }
 
 extern "C" int alga_write_polished_fasta_device(alga_engine *e, const alga_unitigs *u, const alga_consensus *cons, const alga_final_contigs *fin, const alga_placements *pl,
                                                 const alga_polished *pol, int32_t depth_header, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!u || !cons || !fin || !pl || !pol || !path || !*path)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "unitigs, consensus, final contigs, placements, polished and path must not be NULL");
     const char *why = nullptr;
     if (!alga_final_is_current(e, u, cons, fin, &why)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, why);
-    if (!placement_is_current(e, pl) || e->pl_final_epoch == 0 || e->pl_final_epoch != e->fc_epoch || e->pl_targets != (uint64_t) fin->n_accepted ||
-        pl->d_t_bases != (const uint64_t *) e->pl_tstat.p + e->pl_targets)
+    if (!alga_placement_is_current(e, pl) || e->pl_final_epoch == 0 || e->pl_final_epoch != e->fc_epoch || e->pl_targets != (uint64_t) fin->n_accepted)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_place_reads_on_final_device call on this final result");
-    // the polish is matched on what makes the records safe to format: the final result's epoch, the targets and columns, the buffers
-    if (!e->po_valid || e->po_final_epoch != e->pl_final_epoch || e->po_targets != e->pl_targets || pol->n_targets < 0 || (uint64_t) pol->n_targets != e->po_targets ||
-        pol->n_columns != e->po_columns || pol->n_columns != pl->n_columns || pol->d_words != (const uint32_t *) e->po_words.p ||
-        pol->d_col_off != (const uint32_t *) e->po_coloff.p)
+    // the polish is the engine's, and matched on what makes the records safe to format: the final result's epoch, the targets and columns (a polish
+    // of an earlier placement on the same final result has them: this writer, alone, does not ask for the placement's serial)
+    if (!e->po_valid || !alga_same_handle(pol, e->po_out) || e->po_final_epoch != e->pl_final_epoch || e->po_targets != e->pl_targets || pol->n_columns != pl->n_columns)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_polish_placed_device call on this placement");
     HIP_TRY(e, hipSetDevice(e->device));
     const PoFasta f{pol->d_words, pol->d_col_off, fin->d_verdict, fin->d_order, (const unsigned long long *) pl->d_t_reads, (const unsigned long long *) pl->d_t_bases,

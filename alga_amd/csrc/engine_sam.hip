@@ -21,36 +21,14 @@ using namespace alga;
 
 namespace {
 
-struct SamEvents {
-    hipEvent_t ev[2] = {};
-    ~SamEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
-// `pl` names the buffers and sizes of the placement the engine holds
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->n_columns == e->pl_ncolumns && pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p &&
-           pl->d_mm == (const uint8_t *) e->pl_mm.p && pl->d_state == (const uint8_t *) e->pl_state.p && pl->d_col_off == (const uint32_t *) e->pl_coloff.p &&
-           pl->d_t_reads == (const uint64_t *) e->pl_tstat.p && pl->d_t_bases == (const uint64_t *) e->pl_tstat.p + e->pl_targets;
-}
-
-// `gp` names the buffers and sizes of the gapped result the engine holds, and that was made from the placement at hand
-bool gapped_is_current(const alga_engine *e, const alga_gapped *gp) {
-    return e->gp_valid && e->gp_pl_serial == e->pl_serial && gp->n_reads >= 0 && (uint64_t) gp->n_reads == e->gp_reads && (uint64_t) gp->n_reads == e->pl_reads &&
-           gp->n_targets >= 0 && (uint64_t) gp->n_targets == e->gp_targets && gp->n_columns == e->gp_columns && gp->n_columns == e->pl_ncolumns &&
-           gp->n_cigar == e->gp_ncigar && gp->d_target == (const int32_t *) e->gp_target.p && gp->d_pos == (const int32_t *) e->gp_rpos.p &&
-           gp->d_end == (const int32_t *) e->gp_end.p && gp->d_edits == (const uint8_t *) e->gp_edits.p && gp->d_state == (const uint8_t *) e->gp_state.p &&
-           gp->d_cigar_off == (const uint32_t *) e->gp_cigoff.p && gp->d_cigar == (const uint32_t *) e->gp_cigar.p;
-}
-
 // what both calls refuse on the host
 int check_inputs(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_gapped *gp, const char *what) {
     auto fail = [&](const char *why) { return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, (std::string(what) + ": " + why).c_str()); };
     if (!nodes || !pl) return fail("nodes and placements must not be NULL");
     if (nodes->n < 0 || (nodes->n & 1)) return fail("n must be even and >= 0");
     if (nodes->n && (!nodes->words || !nodes->len || nodes->stride_words <= 0)) return fail("bad node arrays");
-    if (!placement_is_current(e, pl)) return fail("not the result of the last placement call on this engine");
-    if (gp && !gapped_is_current(e, gp)) return fail("not the result of the last alga_place_gapped_device call on this engine, or made from an earlier placement");
+    if (!alga_placement_is_current(e, pl)) return fail("not the result of the last placement call on this engine");
+    if (gp && !alga_gapped_is_current(e, gp)) return fail("not the result of the last alga_place_gapped_device call on this engine, or made from an earlier placement");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return fail("the node set does not have the placement's reads (n / 2 != n_reads)");
     return ALGA_OK;
 }
@@ -72,8 +50,8 @@ int judge_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
     const uint64_t R = (uint64_t) pl->n_reads;
     const size_t n_hist = (size_t) p->max_insert + 1;
     int rc;
-    SamEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<2> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->sj_cnt, SAM_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->sj_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, SAM_COUNTERS * sizeof(unsigned long long), s));
@@ -118,9 +96,8 @@ int judge_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_of
             for (size_t i = 0; i < n_hist; i++) { cum += h[i]; if (cum >= half) { o.insert_median = (int64_t) i; break; } }
             o.insert_mean_x100 = (int64_t) ((100ull * hc[SAM_INSERT_SUM]) / o.pairs_proper);
         }
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_judge = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_judge))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -145,9 +122,7 @@ extern "C" void alga_pair_default_params(alga_pair_params *p) {
 
 extern "C" int alga_judge_pairs_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_gapped *gp,
                                        const alga_pair_params *p, void *hip_stream, alga_pair_calls *out, alga_pair_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_pair_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "pair parameters must not be NULL");
     if (p->max_insert < 1 || p->max_insert > (1 << 20)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "pair calls: max_insert must be in [1, 2^20]");
     if (p->flags) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "pair calls: unknown flag");
@@ -155,19 +130,15 @@ extern "C" int alga_judge_pairs_device(alga_engine *e, const alga_nodes *nodes, 
     if (!out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "out must not be NULL");
     int rc;
     if ((rc = check_inputs(e, nodes, pl, gp, "pair calls"))) return rc;
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = judge_impl(e, nodes, d_pair_off, pl, gp, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return judge_impl(e, nodes, d_pair_off, pl, gp, p, call.s, out, info);
 }
 
 extern "C" int alga_write_sam_device(alga_engine *e, const alga_nodes *nodes, const alga_placements *pl, const alga_gapped *gp, const alga_pair_calls *calls,
                                      const alga_sam_params *p, const char *path, alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
     const auto t0 = std::chrono::steady_clock::now();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "SAM parameters must not be NULL");
     if (p->flags & ~(ALGA_SAM_NAMES_DEPTH | ALGA_SAM_SKIP_UNPLACED)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "SAM: unknown flag");
     for (int32_t r : p->reserved) if (r) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "SAM: reserved must be 0");

@@ -22,11 +22,6 @@ using namespace alga;
 
 namespace {
 
-struct ScEvents {
-    hipEvent_t ev[3] = {};
-    ~ScEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int check_params(alga_engine *e, const alga_scaffold_params *p) {
     if (!p) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "scaffold parameters must not be NULL");
     if (p->insert < 0 || p->insert > (1 << 20)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "scaffold: insert must be in [0, 2^20]");
@@ -38,20 +33,13 @@ int check_params(alga_engine *e, const alga_scaffold_params *p) {
     return ALGA_OK;
 }
 
-// `pl` names the buffers and sizes of the placement the engine holds
-bool placement_is_current(const alga_engine *e, const alga_placements *pl) {
-    return e->pl_valid && pl->n_reads >= 0 && (uint64_t) pl->n_reads == e->pl_reads && pl->n_targets >= 0 && (uint64_t) pl->n_targets == e->pl_targets &&
-           pl->d_target == (const int32_t *) e->pl_target.p && pl->d_pos == (const int32_t *) e->pl_pos.p && pl->d_state == (const uint8_t *) e->pl_state.p &&
-           pl->d_col_off == (const uint32_t *) e->pl_coloff.p && pl->d_t_reads == (const uint64_t *) e->pl_tstat.p;
-}
-
 int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_scaffold_params *p, hipStream_t s,
                   alga_scaffolds *out, alga_scaffold_info *info) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t R = (uint64_t) pl->n_reads, T = (uint64_t) pl->n_targets, n_ends = 2 * T;
     int rc;
-    ScEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     if ((rc = alga_ensure(e, e->sc_cnt, SC_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->sc_cnt.p, *hc = e->h_counters;
     HIP_TRY(e, hipMemsetAsync(cnt, 0, SC_COUNTERS * sizeof(unsigned long long), s));
@@ -207,10 +195,9 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
         } catch (const std::bad_alloc &) {
             return alga_fail(e, ALGA_ERR_OUT_OF_MEMORY, "scaffold: no host memory for the lengths of the N50s");
         }
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); o.ms_links = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); o.ms_chain = t;
-        o.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if ((rc = evs.ms(e, 0, 1, &o.ms_links))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &o.ms_chain))) return rc;
+        o.ms_total = alga_ms_since(t0);
         *info = o;
     }
     return ALGA_OK;
@@ -226,37 +213,29 @@ extern "C" void alga_scaffold_default_params(alga_scaffold_params *p) {
 
 extern "C" int alga_scaffold_placed_device(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair_off, const alga_placements *pl, const alga_scaffold_params *p,
                                            void *hip_stream, alga_scaffolds *out, alga_scaffold_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_scaffold_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     int rc;
     if ((rc = check_params(e, p))) return rc;
     if (!nodes || !pl || !out) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "nodes, placements and out must not be NULL");
-    if (nodes->n < 0 || (nodes->n & 1)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "n must be even and >= 0");
-    if (nodes->n && (!nodes->len || nodes->stride_words <= 0)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "bad node arrays");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if ((rc = alga_check_twin_nodes(e, nodes, false))) return rc;
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
     if ((int64_t) (nodes->n / 2) != pl->n_reads) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "scaffold: the node set does not have the placement's reads (n / 2 != n_reads)");
-    HIP_TRY(e, hipSetDevice(e->device));
-    hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
-    rc = scaffold_impl(e, nodes, d_pair_off, pl, p, s, out, info);
-    (void) hipStreamSynchronize(s);
-    return rc;
+    AlgaStageCall call;
+    if ((rc = call.begin(e, hip_stream))) return rc;
+    return scaffold_impl(e, nodes, d_pair_off, pl, p, call.s, out, info);
 }
 
 extern "C" int alga_write_scaffold_fasta_device(alga_engine *e, const alga_placements *pl, const alga_scaffolds *scaf, const alga_polished *pol, const char *path,
                                                 alga_gfa_info *info) {
-    if (!e) return ALGA_ERR_INVALID_ARGUMENT;
-    e->err.clear();
-    if (info) *info = alga_gfa_info{};
+    if (!alga_enter(e, info)) return ALGA_ERR_INVALID_ARGUMENT;
     if (!pl || !scaf || !path || !*path) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "placements, scaffolds and path must not be NULL");
-    if (!placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
+    if (!alga_placement_is_current(e, pl)) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last placement call on this engine");
     if (!e->sc_valid || e->sc_pl_serial != e->pl_serial || scaf->n_targets < 0 || (uint64_t) scaf->n_targets != e->sc_targets || e->sc_targets != e->pl_targets ||
         scaf->n_scaffolds < 0 || (uint64_t) scaf->n_scaffolds != e->sc_scaffolds || scaf->d_s_off != (const uint32_t *) e->sc_soff.p ||
         scaf->d_s_members != (const int32_t *) e->sc_smembers.p || scaf->d_s_len != (const uint64_t *) e->sc_slen.p || scaf->d_start != (const uint64_t *) e->sc_start.p ||
         scaf->d_orient != (const uint8_t *) e->sc_orient.p)
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_scaffold_placed_device call on this placement");
-    if (pol && (!e->po_valid || e->po_pl_serial != e->pl_serial || e->po_targets != e->pl_targets || pol->n_targets < 0 || (uint64_t) pol->n_targets != e->po_targets ||
-                pol->n_columns != e->po_columns || pol->n_columns != pl->n_columns || pol->d_words != (const uint32_t *) e->po_words.p))
+    if (pol && !alga_polished_is_current(e, pl, pol))
         return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "not the result of the last alga_polish_placed_device call on this placement");
     if (e->sc_longest + 64 > 0xFFFFFFFFull) return alga_fail(e, ALGA_ERR_CAPACITY, "a scaffold record of more than 2^32 bytes");
     HIP_TRY(e, hipSetDevice(e->device));

@@ -46,18 +46,13 @@ int cut_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, i
     return ALGA_OK;
 }
 
-struct TipEvents {
-    hipEvent_t ev[3] = {};
-    ~TipEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 // Host side of the dangling-branch removal: the graph once, then per iteration a down and an up pass and ONE read-back (the two counts of
 // the iteration, which decide whether there is another one).
 int tips_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, int32_t max_offset, hipStream_t s, const alga_edge **d_out, uint64_t *m_out,
               alga_tips_info *info) {
     int rc;
-    TipEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     const size_t N = (size_t) n;
     if ((rc = alga_ensure(e, e->tp_cnt, (TIP_COUNTERS + UT_COUNTERS) * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->tp_cnt.p;
@@ -169,9 +164,8 @@ int tips_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, 
     if (info) {
         info->edges_in = m; info->edges_unique = ms; info->edges_out = ms - removed_total; info->iterations = iterations; info->passes = 2 * iterations;
         info->removed_total = removed_total; info->branching_nodes = e->h_counters[TIP_BRANCH_TOTAL]; info->overflow_nodes = e->h_counters[TIP_OVERFLOW_TOTAL];
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); info->ms_prepare = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); info->ms_passes = t;
+        if ((rc = evs.ms(e, 0, 1, &info->ms_prepare))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &info->ms_passes))) return rc;
     }
     return ALGA_OK;
 }
@@ -181,8 +175,8 @@ int tips_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, 
 int mst_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, int32_t max_offset, hipStream_t s, const alga_edge **d_out, uint64_t *m_out,
              alga_mst_info *info) {
     int rc;
-    TipEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<3> evs;
+    if ((rc = evs.create(e))) return rc;
     const size_t N = (size_t) n;
     if ((rc = alga_ensure(e, e->mp_cnt, MST_COUNTERS * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->mp_cnt.p;
@@ -292,9 +286,8 @@ int mst_impl(alga_engine *e, int32_t n, const alga_edge_dev *d_in, uint64_t m, i
     if (info) {
         info->edges_in = m; info->edges_out = *m_out; info->branching_nodes = branching; info->begs_run = begs_run; info->rounds = rounds;
         info->overflow_begs = e->h_counters[MST_OVERFLOW_TOTAL]; info->ball_max = e->h_counters[MST_BALL_MAX];
-        float t = 0.0f;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[0], evs.ev[1])); info->ms_prepare = t;
-        HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[1], evs.ev[2])); info->ms_rounds = t;
+        if ((rc = evs.ms(e, 0, 1, &info->ms_prepare))) return rc;
+        if ((rc = evs.ms(e, 1, 2, &info->ms_rounds))) return rc;
     }
     return ALGA_OK;
 }
@@ -318,7 +311,7 @@ int alga_remove_short_parallel_paths_device(alga_engine *e, int32_t n_nodes, con
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = mst_impl(e, n_nodes, (const alga_edge_dev *) d_edges, n_edges, max_offset, s, d_edges_out, n_edges_out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); if (info) *info = alga_mst_info{}; *d_edges_out = nullptr; *n_edges_out = 0; return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }
 
@@ -337,7 +330,7 @@ int alga_remove_dangling_branches_device(alga_engine *e, int32_t n_nodes, const 
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = tips_impl(e, n_nodes, (const alga_edge_dev *) d_edges, n_edges, max_offset, s, d_edges_out, n_edges_out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); if (info) *info = alga_tips_info{}; return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }
 

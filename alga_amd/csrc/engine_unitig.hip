@@ -18,11 +18,6 @@ using namespace alga;
 
 namespace {
 
-struct UtEvents {
-    hipEvent_t ev[6] = {};
-    ~UtEvents() { for (hipEvent_t x : ev) if (x) (void) hipEventDestroy(x); }
-};
-
 int read_u64(alga_engine *e, const void *d_src, int n_words, hipStream_t s) {
     HIP_TRY(e, hipMemcpyAsync(e->h_counters, d_src, (size_t) n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -167,8 +162,8 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
     const int32_t n = nodes->n;
     const uint64_t m2 = 2 * m;
     int rc;
-    UtEvents evs;
-    for (hipEvent_t &x : evs.ev) HIP_TRY(e, hipEventCreate(&x));
+    AlgaEvents<6> evs;
+    if ((rc = evs.create(e))) return rc;
     const size_t n_cnt = UT_COUNTERS + ALGA_UT_MAX_ROUNDS;
     if ((rc = alga_ensure(e, e->ut_cnt, n_cnt * sizeof(unsigned long long)))) return rc;
     unsigned long long *cnt = (unsigned long long *) e->ut_cnt.p;
@@ -274,7 +269,7 @@ int unitigs_impl(alga_engine *e, const alga_nodes *nodes, const alga_edge_dev *d
         info->isolated_skipped = c[UT_ISOLATED]; info->longest_nodes = c[UT_LONGEST_NODES]; info->longest_bases = c[UT_LONGEST_BASES];
         info->total_bases = c[UT_TOTAL_BASES]; info->total_nodes = c[UT_TOTAL_NODES]; info->rank_rounds = rounds;
         double *part[5] = {&info->ms_sym, &info->ms_rank, &info->ms_layout, &info->ms_seq, &info->ms_edges};
-        for (int k = 0; k < 5; k++) { float t = 0.0f; HIP_TRY(e, hipEventElapsedTime(&t, evs.ev[k], evs.ev[k + 1])); *part[k] = t; }
+        for (int k = 0; k < 5; k++) if ((rc = evs.ms(e, k, k + 1, part[k]))) return rc;
     }
     return ALGA_OK;
 }
@@ -298,6 +293,6 @@ extern "C" int alga_unitigs_device(alga_engine *e, const alga_nodes *nodes, cons
     hipStream_t s = hip_stream ? (hipStream_t) hip_stream : e->own_stream;
     const int rc = unitigs_impl(e, nodes, (const alga_edge_dev *) d_edges, n_edges, flags, s, out, info);
     if (rc != ALGA_OK) { (void) hipStreamSynchronize(s); return rc; }
-    if (info) info->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) info->ms_total = alga_ms_since(t0);
     return ALGA_OK;
 }

@@ -21,6 +21,17 @@ class AlgaError(RuntimeError):
         self.code = code
 
 
+class _Info(C.Structure):
+    """base of the info and stats structs.  _PER_ROUND = {array field: (its count field, its capacity)}: as_dict() cuts that list at the count"""
+    _PER_ROUND = {}
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k, (count, cap) in self._PER_ROUND.items():
+            d[k] = [int(x) for x in d[k][: min(int(getattr(self, count)), cap)]]
+        return d
+
+
 class _Nodes(C.Structure):
     _fields_ = [("words", C.c_void_p), ("stride_words", C.c_int32), ("len", C.c_void_p), ("n", C.c_int32),
                 ("align_from", C.c_void_p), ("align_to", C.c_void_p)]
@@ -38,7 +49,7 @@ class CompactEdges(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_edges", C.c_uint64), ("degree", C.c_void_p), ("dst", C.c_void_p), ("offset", C.c_void_p)]
 
 
-class PrefSufStats(C.Structure):
+class PrefSufStats(_Info):
     """alga_prefsuf_stats"""
     _fields_ = [("raw_overlaps", C.c_uint64), ("transitive_listed", C.c_uint64), ("transitive_compares", C.c_uint64),
                 ("transitive_removed", C.c_uint64), ("windows_probed", C.c_uint64), ("slots_scanned", C.c_uint64),
@@ -51,9 +62,6 @@ class PrefSufStats(C.Structure):
                 ("pile_buckets", C.c_uint64), ("pile_irregular", C.c_uint64), ("pile_list_checked", C.c_uint64), ("pile_list_mismatch", C.c_uint64),
                 ("pile_own_lists", C.c_uint64), ("host_ms_check", C.c_double), ("host_ms_upload", C.c_double), ("host_ms_build", C.c_double),
                 ("host_ms_download", C.c_double), ("pile_mixed", C.c_uint64), ("pile_deferred", C.c_uint64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class IngestParams(C.Structure):
@@ -103,14 +111,11 @@ class CorrectParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("solid_min", C.c_int32), ("min_run", C.c_int32), ("reserved", C.c_int32)]
 
 
-class CorrectInfo(C.Structure):
+class CorrectInfo(_Info):
     """alga_correct_info"""
     _fields_ = [(k, C.c_uint64) for k in ("reads", "kmers_total", "kmers_distinct", "kmers_solid", "runs", "runs_fixed", "runs_ambiguous",
                                           "runs_no_candidate", "runs_skipped", "reads_changed", "slices")] + \
                [(k, C.c_double) for k in ("ms_count", "ms_index", "ms_fix", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PkbParams(C.Structure):
@@ -141,14 +146,11 @@ class MultiStats(C.Structure):
                 ("ms_shard_place", C.c_double)]
 
 
-class ShardStats(C.Structure):
+class ShardStats(_Info):
     """alga_shard_stats"""
     _fields_ = [(k, C.c_uint64) for k in ("targets_owned", "descriptors_out", "descriptors_in", "flagged_sources", "records", "pending", "pending_sources",
                                           "small_keys_out", "small_keys_in", "dropped", "edges_out", "edges_in", "edges", "join_passes", "join_passes_serial")] + \
                [(k, C.c_double) for k in ("ms_index", "ms_export", "ms_sort", "ms_join", "ms_cap", "ms_edges_out", "ms_place")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 MULTI_FORM = {"auto": 0, "replicated": 1, "bucket_sharded": 2}   # alga_multi_form
@@ -192,43 +194,32 @@ GFA_TWINS, GFA_SEQUENCES = 1, 2                                 # alga_write_gfa
 GFA_CONSENSUS = 4                                                # alga_write_unitig_gfa_device: segments carry the consensus
 
 
-class GfaInfo(C.Structure):
+class GfaInfo(_Info):
     """alga_gfa_info"""
     _fields_ = [("segments", C.c_uint64), ("links", C.c_uint64), ("links_merged", C.c_uint64), ("bytes", C.c_uint64),
                 ("ms_format", C.c_double), ("ms_total", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 TIPS_MAX_PASSES = 64                                             # ALGA_TIPS_MAX_PASSES
 
 
-class TipsInfo(C.Structure):
+class TipsInfo(_Info):
     """alga_tips_info"""
+    _PER_ROUND = {"removed": ("passes", TIPS_MAX_PASSES)}
     _fields_ = [("edges_in", C.c_uint64), ("edges_unique", C.c_uint64), ("edges_out", C.c_uint64), ("iterations", C.c_int32), ("passes", C.c_int32),
                 ("removed", C.c_uint64 * TIPS_MAX_PASSES), ("removed_total", C.c_uint64), ("branching_nodes", C.c_uint64), ("overflow_nodes", C.c_uint64),
                 ("ms_prepare", C.c_double), ("ms_passes", C.c_double), ("ms_total", C.c_double)]
-
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "removed"}
-        d["removed"] = [int(x) for x in self.removed[: min(self.passes, TIPS_MAX_PASSES)]]
-        return d
 
 
 MST_MAX_ROUNDS = 64                                              # ALGA_MST_MAX_ROUNDS
 
 
-class MstInfo(C.Structure):
+class MstInfo(_Info):
     """alga_mst_info"""
+    _PER_ROUND = {"winners": ("rounds", MST_MAX_ROUNDS)}
     _fields_ = [("edges_in", C.c_uint64), ("edges_out", C.c_uint64), ("branching_nodes", C.c_uint64), ("begs_run", C.c_uint64), ("rounds", C.c_uint64),
                 ("winners", C.c_uint64 * MST_MAX_ROUNDS), ("overflow_begs", C.c_uint64), ("ball_max", C.c_uint64),
                 ("ms_prepare", C.c_double), ("ms_rounds", C.c_double), ("ms_total", C.c_double)]
-
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "winners"}
-        d["winners"] = [int(x) for x in self.winners[: min(self.rounds, MST_MAX_ROUNDS)]]
-        return d
 
 
 UNITIG_SKIP_ISOLATED = 1                                         # alga_unitigs_device flag
@@ -240,45 +231,33 @@ class UnitigsC(C.Structure):
                 ("d_path_pos", C.c_void_p), ("d_path_off", C.c_void_p), ("d_edges", C.c_void_p), ("n_edges", C.c_uint64)]
 
 
-class UnitigInfo(C.Structure):
+class UnitigInfo(_Info):
     """alga_unitig_info"""
     _fields_ = [(k, C.c_uint64) for k in ("edges_in", "edges_sym", "twins_added", "compactable", "cycles_cut", "isolated_skipped", "longest_nodes",
                                           "longest_bases", "total_bases", "total_nodes")] + [("rank_rounds", C.c_int32)] + \
                [(k, C.c_double) for k in ("ms_sym", "ms_rank", "ms_layout", "ms_seq", "ms_edges", "ms_total")]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
 
 CONTIG_MAX_ROUNDS = 64
 
 
-class ContigInfo(C.Structure):
+class ContigInfo(_Info):
     """alga_contig_info"""
-    _PER_ROUND = ("chains", "parallel_drops", "groups_cut", "base_edges_dropped")
+    _PER_ROUND = {k: ("rounds", CONTIG_MAX_ROUNDS) for k in ("chains", "parallel_drops", "groups_cut", "base_edges_dropped")}
     _fields_ = [(k, C.c_uint64) for k in ("edges_in", "edges_sym", "rounds")] + [(k, C.c_uint64 * CONTIG_MAX_ROUNDS) for k in _PER_ROUND] + \
                [(k, C.c_uint64) for k in ("final_edges", "path_nodes", "junction_nodes", "cycles_cut", "closed_chains", "reads_dropped", "longest_nodes",
                                           "longest_bases", "total_bases")] + [("rank_rounds", C.c_int32)] + \
                [(k, C.c_double) for k in ("ms_sym", "ms_rounds", "ms_layout", "ms_seq", "ms_edges", "ms_total")]
 
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in self._PER_ROUND}
-        for k in self._PER_ROUND:
-            d[k] = list(getattr(self, k))[: min(int(self.rounds), CONTIG_MAX_ROUNDS)]
-        return d
-
 
 EXTEND_HEAD_SLICE = 1024                                          # ALGA_EXTEND_HEAD_SLICE
 
 
-class ExtendInfo(C.Structure):
+class ExtendInfo(_Info):
     """alga_extend_info"""
     _fields_ = [(k, C.c_uint64) for k in ("candidates", "direct_links", "links", "joinable", "ambiguous", "cycles_cut", "pairs_in", "pairs_out", "head_max",
                                           "head_passes", "longest_nodes", "longest_bases", "total_bases")] + [("rank_rounds", C.c_int32)] + \
                [(k, C.c_double) for k in ("ms_count", "ms_paths", "ms_layout", "ms_seq", "ms_edges", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ExtendSeamsC(C.Structure):
@@ -321,13 +300,10 @@ class ConsensusC(C.Structure):
                 ("d_votes", C.c_void_p)]
 
 
-class ConsensusInfo(C.Structure):
+class ConsensusInfo(_Info):
     """alga_consensus_info"""
     _fields_ = [(k, C.c_uint64) for k in ("pairs", "pairs_kept", "columns", "trimmed_bases", "changed", "max_depth", "wide_words")] + \
                [(k, C.c_double) for k in ("ms_vote", "ms_window", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Consensus:
@@ -364,13 +340,10 @@ class FinalContigsC(C.Structure):
                 ("d_len", C.c_void_p), ("d_order", C.c_void_p)]
 
 
-class FinalInfo(C.Structure):
+class FinalInfo(_Info):
     """alga_final_info"""
     _fields_ = [(k, C.c_uint64) for k in ("pairs", "n_short", "rejected", "accepted", "trimmed_away", "filter_rounds", "trim_edges")] + \
                [(k, C.c_double) for k in ("ms_filter", "ms_trim", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class FinalContigs:
@@ -397,6 +370,38 @@ class FinalContigs:
         return d
 
 
+class _Result:
+    """base of the stages' result wrappers.  COUNTS: the integer fields of the C struct that become attributes; KEYS = ((name, typestr of the
+    view, dtype of to_host(), size key), ...): attribute `name` is the zero-copy view of c.d_<name> with _sizes()[size key] entries (an entry
+    without a size key: _sizes()[name], and n_targets where that has none); KEPT: the attribute that keeps what the result was made from alive"""
+    COUNTS, KEYS, KEPT = (), (), "_source"
+
+    def __init__(self, c, info, device, source=None):
+        self._c, self.info = c, info
+        setattr(self, self.KEPT, source)
+        for k in self.COUNTS:
+            setattr(self, k, int(getattr(c, k)))
+        self._dev = "cuda:%d" % device
+        size = self._sizes()
+        for k, typestr, *rest in self.KEYS:
+            setattr(self, k, device_view(getattr(c, "d_" + k), (size[rest[1]] if len(rest) > 1 else size.get(k, getattr(self, "n_targets", 0)),), self._dev, typestr))
+
+    def to_host(self):
+        """numpy copies of every array of KEYS, in the dtypes of the stage's checker under tests/, and info"""
+        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, *_ in self.KEYS}
+        d["info"] = dict(self.info)
+        return d
+
+
+class _RaggedResult(_Result):
+    """a result that carries sequences of its own: words, begin, len"""
+
+    def targets(self):
+        """(words, begin int64, len int32): the result's sequences as the ragged target set Engine.place_reads(targets=...) and Engine.merge_ends
+        take; sequence j is target j of that call (the tensors are the engine's)"""
+        return self.words, self.begin, self.len
+
+
 PLACE_DEPTH_MULTI = 1                                            # alga_place_params.flags
 PLACE_PLACED, PLACE_UNIQUE, PLACE_MINUS = 1, 2, 4                # bits of Placements.state
 
@@ -406,14 +411,11 @@ class PlaceParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("k", "max_mismatches", "max_occ", "max_insert", "flags")] + [("reserved", C.c_int32 * 3)]
 
 
-class PlaceInfo(C.Structure):
+class PlaceInfo(_Info):
     """alga_place_info"""
     _fields_ = [(k, C.c_uint64) for k in ("reads", "placed", "unique", "multi", "unplaced", "hits_saturated", "seeds", "seeds_over_max_occ", "index_positions",
                                           "index_distinct", "pairs", "pairs_proper", "pairs_improper", "pairs_split", "pairs_not_unique")] + \
                [(k, C.c_int64) for k in ("insert_median", "insert_mean_x100")] + [(k, C.c_double) for k in ("ms_index", "ms_place", "ms_depth", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PlacementsC(C.Structure):
@@ -423,7 +425,7 @@ class PlacementsC(C.Structure):
                                           "d_t_uncovered", "d_insert_hist")]
 
 
-class Placements:
+class Placements(_Result):
     """Result of Engine.place_reads: zero-copy torch views of the engine's device memory (valid until the next Engine.place_reads call on that
     engine; clone what has to live longer) -- target / pos int32 [n_reads], mm / hits / state uint8 [n_reads], col_off int32 [n_targets + 1]
     and cover int32 [n_columns] (the bits of uint32), t_reads / t_bases / t_mismatches / t_uncovered int64 [n_targets], insert_hist int64
@@ -431,21 +433,11 @@ class Placements:
     KEYS = (("target", "<i4", np.int32), ("pos", "<i4", np.int32), ("mm", "|u1", np.uint8), ("hits", "|u1", np.uint8), ("state", "|u1", np.uint8),
             ("col_off", "<i4", np.uint32), ("cover", "<i4", np.uint32), ("t_reads", "<i8", np.uint64), ("t_bases", "<i8", np.uint64),
             ("t_mismatches", "<i8", np.uint64), ("t_uncovered", "<i8", np.uint64), ("insert_hist", "<i8", np.uint64))
+    COUNTS, KEPT = ("n_reads", "n_targets", "n_columns", "n_hist"), "_final"
 
-    def __init__(self, c, info, device, final=None):
-        self._c, self.info, self._final = c, info, final
-        self.n_reads, self.n_targets, self.n_columns, self.n_hist = int(c.n_reads), int(c.n_targets), int(c.n_columns), int(c.n_hist)
-        dev = "cuda:%d" % device
-        shape = dict(target=self.n_reads, pos=self.n_reads, mm=self.n_reads, hits=self.n_reads, state=self.n_reads, col_off=self.n_targets + 1,
-                     cover=self.n_columns, insert_hist=self.n_hist)
-        for k, typestr, _ in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (shape.get(k, self.n_targets),), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/place_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
+    def _sizes(self):
+        return dict(target=self.n_reads, pos=self.n_reads, mm=self.n_reads, hits=self.n_reads, state=self.n_reads, col_off=self.n_targets + 1,
+                    cover=self.n_columns, insert_hist=self.n_hist)
 
 
 POLISH_MULTI, POLISH_COUNTS = 1, 2                               # alga_polish_params.flags
@@ -456,13 +448,10 @@ class PolishParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("min_cover", "min_percent", "flags")] + [("reserved", C.c_int32 * 5)]
 
 
-class PolishInfo(C.Structure):
+class PolishInfo(_Info):
     """alga_polish_info"""
     _fields_ = [(k, C.c_uint64) for k in ("columns", "voters", "votes", "voted_columns", "changed", "ambiguous", "max_cover")] + \
                [(k, C.c_double) for k in ("ms_sort", "ms_vote", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PolishedC(C.Structure):
@@ -471,28 +460,25 @@ class PolishedC(C.Structure):
                [(k, C.c_void_p) for k in ("d_col_off", "d_words", "d_changed_cols", "d_changed_bases", "d_t_changed", "d_t_ambiguous", "d_counts")]
 
 
-class Polished:
+class Polished(_Result):
     """Result of Engine.polish: zero-copy torch views of the engine's device memory (valid until the next Engine.polish call on that engine;
     clone what has to live longer) -- col_off int32 [n_targets + 1], words int32 [(n_columns + 15) / 16 + 2] (the bits of uint32: column g
     in word g >> 4 at bits 2 * (g & 15)), changed_cols int32 [n_changed] (the bits of uint32, ascending), changed_bases uint8 [n_changed]
     (old | new << 2), t_changed / t_ambiguous int64 [n_targets], counts int32 [n_columns, 4] or None -- and .info (dict of alga_polish_info)."""
     KEYS = (("col_off", "<i4", np.uint32), ("words", "<i4", np.uint32), ("changed_cols", "<i4", np.uint32), ("changed_bases", "|u1", np.uint8),
             ("t_changed", "<i8", np.uint64), ("t_ambiguous", "<i8", np.uint64))
+    COUNTS, KEPT = ("n_targets", "n_columns", "n_changed"), "_placements"
 
     def __init__(self, c, info, device, placements=None):
-        self._c, self.info, self._placements = c, info, placements
-        self.n_targets, self.n_columns, self.n_changed = int(c.n_targets), int(c.n_columns), int(c.n_changed)
-        dev = "cuda:%d" % device
-        shape = dict(col_off=self.n_targets + 1, words=(self.n_columns + 15) // 16 + 2, changed_cols=self.n_changed, changed_bases=self.n_changed)
-        for k, typestr, _ in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (shape.get(k, self.n_targets),), dev, typestr))
-        self.counts = device_view(c.d_counts, (self.n_columns, 4), dev, "<i4") if c.d_counts else None
+        super().__init__(c, info, device, placements)
+        self.counts = device_view(c.d_counts, (self.n_columns, 4), self._dev, "<i4") if c.d_counts else None
+
+    def _sizes(self):
+        return dict(col_off=self.n_targets + 1, words=(self.n_columns + 15) // 16 + 2, changed_cols=self.n_changed, changed_bases=self.n_changed)
 
     def to_host(self):
-        """numpy copies, in the dtypes of tests/polish_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt in self.KEYS}
+        d = super().to_host()
         d["counts"] = None if self.counts is None else self.counts.cpu().numpy().copy().view(np.uint32)
-        d["info"] = dict(self.info)
         return d
 
     def targets(self):
@@ -512,14 +498,11 @@ class ScaffoldParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("insert", "max_insert", "min_links", "max_second_percent", "min_gap", "flags")] + [("reserved", C.c_int32 * 2)]
 
 
-class ScaffoldInfo(C.Structure):
+class ScaffoldInfo(_Info):
     """alga_scaffold_info"""
     _fields_ = [(k, C.c_uint64) for k in ("pairs_split", "links", "links_too_far", "bundles", "bundles_supported", "ends_ambiguous", "joins", "joins_dropped_cycle",
                                           "scaffolds", "scaffolds_multi", "longest", "n50_targets", "n50_scaffolds")] + \
                [(k, C.c_double) for k in ("ms_links", "ms_chain", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ScaffoldsC(C.Structure):
@@ -529,7 +512,7 @@ class ScaffoldsC(C.Structure):
                                           "d_gap_after", "d_join_links", "d_s_off", "d_s_members", "d_s_len")]
 
 
-class Scaffolds:
+class Scaffolds(_Result):
     """Result of Engine.scaffold: zero-copy torch views of the engine's device memory (valid until the next Engine.scaffold call on that engine;
     clone what has to live longer) -- per bundle b_a / b_b / b_links int32 (the bits of uint32), b_span int64, b_gap int32, b_state uint8; end_state
     uint8 [2 * n_targets]; per target scaffold / rank int32, orient uint8, start int64, gap_after int32, join_links int32; s_off int32
@@ -538,20 +521,10 @@ class Scaffolds:
             ("b_gap", "<i4", np.int32, "b"), ("b_state", "|u1", np.uint8, "b"), ("end_state", "|u1", np.uint8, "e"), ("scaffold", "<i4", np.int32, "t"),
             ("rank", "<i4", np.int32, "t"), ("orient", "|u1", np.uint8, "t"), ("start", "<i8", np.uint64, "t"), ("gap_after", "<i4", np.int32, "t"),
             ("join_links", "<i4", np.uint32, "t"), ("s_off", "<i4", np.uint32, "s1"), ("s_members", "<i4", np.int32, "m"), ("s_len", "<i8", np.uint64, "s"))
+    COUNTS, KEPT = ("n_targets", "n_bundles", "n_scaffolds", "n_members"), "_placements"
 
-    def __init__(self, c, info, device, placements=None):
-        self._c, self.info, self._placements = c, info, placements
-        self.n_targets, self.n_bundles, self.n_scaffolds, self.n_members = int(c.n_targets), int(c.n_bundles), int(c.n_scaffolds), int(c.n_members)
-        dev = "cuda:%d" % device
-        size = dict(b=self.n_bundles, e=2 * self.n_targets, t=self.n_targets, s1=self.n_scaffolds + 1, m=self.n_members, s=self.n_scaffolds)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/scaffold_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
+    def _sizes(self):
+        return dict(b=self.n_bundles, e=2 * self.n_targets, t=self.n_targets, s1=self.n_scaffolds + 1, m=self.n_members, s=self.n_scaffolds)
 
     def layout_tsv(self, host=None):
         """one line per member contig in (scaffold, rank) order: scaffold, rank, contig, orient (+/-), start, length, gap_after, links (tabs);
@@ -583,14 +556,11 @@ class BreakParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("min_span", "inset", "margin", "flags")] + [("reserved", C.c_int32 * 4)]
 
 
-class BreakInfo(C.Structure):
+class BreakInfo(_Info):
     """alga_break_info"""
     _fields_ = [(k, C.c_uint64) for k in ("pairs_proper", "pairs_spanning", "candidate_columns", "weak_columns", "runs", "runs_open", "cuts", "targets_cut", "pieces",
                                           "max_span", "longest_piece", "n50_targets", "n50_pieces")] + \
                [(k, C.c_double) for k in ("ms_span", "ms_cut", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class BrokenC(C.Structure):
@@ -600,7 +570,7 @@ class BrokenC(C.Structure):
                                           "d_piece_start", "d_words")]
 
 
-class Broken:
+class Broken(_RaggedResult):
     """Result of Engine.break_contigs: zero-copy torch views of the engine's device memory (valid until the next Engine.break_contigs call on
     that engine; clone what has to live longer) -- span int32 [n_columns] (the bits of uint32), cut_cols / cut_first / cut_last int32 [n_cuts]
     (column space), t_cuts int32 [n_targets], piece_off int32 [n_pieces + 1], begin int64, len int32, piece_target int32, piece_start int32
@@ -608,25 +578,10 @@ class Broken:
     KEYS = (("span", "<i4", np.uint32, "c"), ("cut_cols", "<i4", np.uint32, "k"), ("cut_first", "<i4", np.uint32, "k"), ("cut_last", "<i4", np.uint32, "k"),
             ("t_cuts", "<i4", np.uint32, "t"), ("piece_off", "<i4", np.uint32, "p1"), ("begin", "<i8", np.uint64, "p"), ("len", "<i4", np.int32, "p"),
             ("piece_target", "<i4", np.int32, "p"), ("piece_start", "<i4", np.uint32, "p"), ("words", "<i4", np.uint32, "w"))
+    COUNTS, KEPT = ("n_targets", "n_pieces", "n_cuts", "n_columns"), "_placements"
 
-    def __init__(self, c, info, device, placements=None):
-        self._c, self.info, self._placements = c, info, placements
-        self.n_targets, self.n_pieces, self.n_cuts, self.n_columns = int(c.n_targets), int(c.n_pieces), int(c.n_cuts), int(c.n_columns)
-        dev = "cuda:%d" % device
-        size = dict(c=self.n_columns, k=self.n_cuts, t=self.n_targets, p1=self.n_pieces + 1, p=self.n_pieces, w=(self.n_columns + 15) // 16 + 2)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/break_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
-
-    def targets(self):
-        """(words, begin int64 [n_pieces], len int32 [n_pieces]): the pieces as the ragged target set Engine.place_reads(targets=...) takes;
-        piece j is target j of that placement (the tensors are the engine's)"""
-        return self.words, self.begin, self.len
+    def _sizes(self):
+        return dict(c=self.n_columns, k=self.n_cuts, t=self.n_targets, p1=self.n_pieces + 1, p=self.n_pieces, w=(self.n_columns + 15) // 16 + 2)
 
     def cuts_tsv(self, host=None):
         """one line per cut: contig, cut, run_first, run_last (tabs) in target-local columns; the text alga_hip --break_cuts= writes"""
@@ -651,15 +606,12 @@ class GrowParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("k", "max_mismatches", "max_occ", "min_anchor", "min_cover", "min_percent", "max_grow", "flags")] + [("reserved", C.c_int32 * 4)]
 
 
-class GrowInfo(C.Structure):
+class GrowInfo(_Info):
     """alga_grow_info"""
     _fields_ = [(k, C.c_uint64) for k in ("candidates", "overhanging", "voting", "multi", "hits_saturated", "seeds", "seeds_over_max_occ", "index_positions",
                                           "ends_with_voters", "ends_grown", "bases_added", "longest_growth", "stops_cover", "stops_percent", "stops_max",
                                           "columns_before", "columns_after", "n50_before", "n50_after")] + \
                [(k, C.c_double) for k in ("ms_index", "ms_place", "ms_build", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class GrownC(C.Structure):
@@ -669,7 +621,7 @@ class GrownC(C.Structure):
                                           "d_begin", "d_words")]
 
 
-class Grown:
+class Grown(_RaggedResult):
     """Result of Engine.grow_ends: zero-copy torch views of the engine's device memory (valid until the next Engine.grow_ends call on that
     engine; clone what has to live longer) -- per read end / over int32, mm / hits / state uint8; count int32 [2 * n_targets * max_grow * 4] (the
     bits of uint32); e_stop uint8, e_voters int32 [2 * n_targets]; left / right / len int32 [n_targets], col_off int32 [n_targets + 1], begin
@@ -678,26 +630,11 @@ class Grown:
             ("count", "<i4", np.uint32, "c"), ("e_stop", "|u1", np.uint8, "e"), ("e_voters", "<i4", np.uint32, "e"), ("left", "<i4", np.uint32, "t"),
             ("right", "<i4", np.uint32, "t"), ("len", "<i4", np.int32, "t"), ("col_off", "<i4", np.uint32, "t1"), ("begin", "<i8", np.uint64, "t"),
             ("words", "<i4", np.uint32, "w"))
+    COUNTS, KEPT = ("n_reads", "n_targets", "max_grow", "n_columns"), "_placements"
 
-    def __init__(self, c, info, device, placements=None):
-        self._c, self.info, self._placements = c, info, placements
-        self.n_reads, self.n_targets, self.max_grow, self.n_columns = int(c.n_reads), int(c.n_targets), int(c.max_grow), int(c.n_columns)
-        dev = "cuda:%d" % device
-        size = dict(r=self.n_reads, c=8 * self.n_targets * self.max_grow, e=2 * self.n_targets, t=self.n_targets, t1=self.n_targets + 1,
+    def _sizes(self):
+        return dict(r=self.n_reads, c=8 * self.n_targets * self.max_grow, e=2 * self.n_targets, t=self.n_targets, t1=self.n_targets + 1,
                     w=(self.n_columns + 15) // 16 + 2)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/grow_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
-
-    def targets(self):
-        """(words, begin int64 [n_targets], len int32 [n_targets]): the grown targets as the ragged target set Engine.place_reads(targets=...)
-        takes (the tensors are the engine's)"""
-        return self.words, self.begin, self.len
 
     def grow_tsv(self, host=None):
         """one line per target: contig, left, right, voters_left, voters_right, stop_left, stop_right (tabs); the text alga_hip --grow_layout= writes"""
@@ -718,15 +655,12 @@ class MergeParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("k", "max_mismatches", "max_occ", "min_overlap", "max_overlap", "flags")] + [("reserved", C.c_int32 * 2)]
 
 
-class MergeInfo(C.Structure):
+class MergeInfo(_Info):
     """alga_merge_info"""
     _fields_ = [(k, C.c_uint64) for k in ("ends", "index_positions", "seeds", "seeds_over_max_occ", "ends_with_overlap", "ends_ambiguous", "hits_saturated", "joins",
                                           "joins_dropped_cycle", "join_mismatches", "bases_removed", "longest_overlap", "merged", "merged_multi", "longest",
                                           "columns_before", "columns_after", "n50_before", "n50_after")] + \
                [(k, C.c_double) for k in ("ms_index", "ms_overlap", "ms_build", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class MergedC(C.Structure):
@@ -736,7 +670,7 @@ class MergedC(C.Structure):
                                           "d_m_members", "d_len", "d_col_off", "d_begin", "d_words")]
 
 
-class Merged:
+class Merged(_RaggedResult):
     """Result of Engine.merge_ends: zero-copy torch views of the engine's device memory (valid until the next Engine.merge_ends call on that
     engine; clone what has to live longer) -- per end partner / olen int32, mm / hits / end_state uint8 [2 * n_targets]; per target merged /
     rank int32, orient uint8, start int32 (the bits of uint32), overlap_after int32; m_off int32 [n_merged + 1], m_members int32 [n_members];
@@ -746,25 +680,10 @@ class Merged:
             ("end_state", "|u1", np.uint8, "e"), ("merged", "<i4", np.int32, "t"), ("rank", "<i4", np.int32, "t"), ("orient", "|u1", np.uint8, "t"),
             ("start", "<i4", np.uint32, "t"), ("overlap_after", "<i4", np.int32, "t"), ("m_off", "<i4", np.uint32, "m1"), ("m_members", "<i4", np.int32, "mm"),
             ("len", "<i4", np.int32, "m"), ("col_off", "<i4", np.uint32, "m1"), ("begin", "<i8", np.uint64, "m"), ("words", "<i4", np.uint32, "w"))
+    COUNTS = ("n_targets", "n_merged", "n_members", "n_columns")
 
-    def __init__(self, c, info, device, source=None):
-        self._c, self.info, self._source = c, info, source                 # source: the tensors the targets came from, kept alive with the result
-        self.n_targets, self.n_merged, self.n_members, self.n_columns = int(c.n_targets), int(c.n_merged), int(c.n_members), int(c.n_columns)
-        dev = "cuda:%d" % device
-        size = dict(e=2 * self.n_targets, t=self.n_targets, m=self.n_merged, m1=self.n_merged + 1, mm=self.n_members, w=(self.n_columns + 15) // 16 + 2)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/merge_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
-
-    def targets(self):
-        """(words, begin int64 [n_merged], len int32 [n_merged]): the merged contigs as the ragged target set Engine.place_reads(targets=...) and
-        Engine.merge_ends take (the tensors are the engine's)"""
-        return self.words, self.begin, self.len
+    def _sizes(self):
+        return dict(e=2 * self.n_targets, t=self.n_targets, m=self.n_merged, m1=self.n_merged + 1, mm=self.n_members, w=(self.n_columns + 15) // 16 + 2)
 
     def merge_tsv(self, tlen=None, host=None):
         """one line per member in (merged, rank) order: merged, rank, contig, orient, start, length, overlap_after, mm (tabs); tlen: the lengths
@@ -796,14 +715,11 @@ class GappedParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("k", "max_edits", "max_occ", "flags")] + [("reserved", C.c_int32 * 4)]
 
 
-class GappedInfo(C.Structure):
+class GappedInfo(_Info):
     """alga_gapped_info"""
     _fields_ = [(k, C.c_uint64) for k in ("tried", "skipped_long", "placed", "unique", "with_indel", "edits", "insertions", "deletions", "candidates", "seeds",
                                           "seeds_over_max_occ")] + \
                [(k, C.c_double) for k in ("ms_index", "ms_place", "ms_trace", "ms_depth", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class GappedC(C.Structure):
@@ -812,7 +728,7 @@ class GappedC(C.Structure):
                [(k, C.c_void_p) for k in ("d_target", "d_pos", "d_end", "d_edits", "d_state", "d_cigar_off", "d_cigar", "d_cover", "d_t_reads", "d_t_bases", "d_t_edits")]
 
 
-class Gapped:
+class Gapped(_Result):
     """Result of Engine.place_gapped: zero-copy torch views of the engine's device memory (valid until the next Engine.place_gapped call on that
     engine; clone what has to live longer) -- target / pos / end int32 [n_reads], edits / state uint8 [n_reads], cigar_off int32 [n_reads + 1]
     and cigar int32 [n_cigar] (the bits of uint32: len << 2 | op), cover int32 [n_columns] (the bits of uint32), t_reads / t_bases / t_edits
@@ -820,20 +736,10 @@ class Gapped:
     KEYS = (("target", "<i4", np.int32, "r"), ("pos", "<i4", np.int32, "r"), ("end", "<i4", np.int32, "r"), ("edits", "|u1", np.uint8, "r"), ("state", "|u1", np.uint8, "r"),
             ("cigar_off", "<i4", np.uint32, "r1"), ("cigar", "<i4", np.uint32, "c"), ("cover", "<i4", np.uint32, "g"), ("t_reads", "<i8", np.uint64, "t"),
             ("t_bases", "<i8", np.uint64, "t"), ("t_edits", "<i8", np.uint64, "t"))
+    COUNTS, KEPT = ("n_reads", "n_targets", "n_columns", "n_cigar"), "_placements"
 
-    def __init__(self, c, info, device, placements=None):
-        self._c, self.info, self._placements = c, info, placements
-        self.n_reads, self.n_targets, self.n_columns, self.n_cigar = int(c.n_reads), int(c.n_targets), int(c.n_columns), int(c.n_cigar)
-        dev = "cuda:%d" % device
-        size = dict(r=self.n_reads, r1=self.n_reads + 1, c=self.n_cigar, g=self.n_columns, t=self.n_targets)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/gapped_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
+    def _sizes(self):
+        return dict(r=self.n_reads, r1=self.n_reads + 1, c=self.n_cigar, g=self.n_columns, t=self.n_targets)
 
     def cigar_strings(self, host=None):
         """the CIGAR of every read as text ('' where it is not placed), for example 57M1D93M"""
@@ -854,14 +760,11 @@ class PairParams(C.Structure):
     _fields_ = [("max_insert", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
-class PairInfo(C.Structure):
+class PairInfo(_Info):
     """alga_pair_info"""
     _fields_ = [(k, C.c_uint64) for k in ("reads", "live", "placed_h", "placed_g", "unplaced", "pairs", "pairs_proper", "pairs_improper", "pairs_split", "pairs_not_unique",
                                           "pairs_with_gapped", "proper_with_gapped")] + \
                [(k, C.c_int64) for k in ("insert_median", "insert_mean_x100")] + [(k, C.c_double) for k in ("ms_judge", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PairCallsC(C.Structure):
@@ -874,25 +777,15 @@ class SamParams(C.Structure):
     _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
-class PairCalls:
+class PairCalls(_Result):
     """Result of Engine.judge_pairs: zero-copy torch views of the engine's device memory (valid until the next Engine.judge_pairs call on that
     engine; clone what has to live longer) -- flag int16 [n_reads] (the bits of uint16: the SAM FLAG), tlen int32 [n_reads], insert_hist int64
     [max_insert + 1] -- and .info (dict of alga_pair_info)."""
     KEYS = (("flag", "<i2", np.uint16, "r"), ("tlen", "<i4", np.int32, "r"), ("insert_hist", "<i8", np.uint64, "h"))
+    COUNTS = ("n_reads", "n_hist")
 
-    def __init__(self, c, info, device, source=None):
-        self._c, self.info, self._source = c, info, source
-        self.n_reads, self.n_hist = int(c.n_reads), int(c.n_hist)
-        dev = "cuda:%d" % device
-        size = dict(r=self.n_reads, h=self.n_hist)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-
-    def to_host(self):
-        """numpy copies, in the dtypes of tests/sam_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
-        d["info"] = dict(self.info)
-        return d
+    def _sizes(self):
+        return dict(r=self.n_reads, h=self.n_hist)
 
 
 IPOLISH_COUNTS = 1                                               # alga_ipolish_params.flags
@@ -905,15 +798,12 @@ class IpolishParams(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("min_cover", "min_percent", "max_ins", "flags")] + [("reserved", C.c_int32 * 4)]
 
 
-class IpolishInfo(C.Structure):
+class IpolishInfo(_Info):
     """alga_ipolish_info"""
     _fields_ = [(k, C.c_uint64) for k in ("columns", "voters_hamming", "voters_gapped", "votes", "del_votes", "ins_votes", "ins_too_long", "ins_edge", "shifted_runs",
                                           "shifted_bases", "voted_columns", "substituted", "deleted", "inserted_slots", "inserted_bases", "ambiguous_columns",
                                           "ambiguous_slots", "columns_after", "max_cover")] + \
                [(k, C.c_double) for k in ("ms_votes", "ms_inserts", "ms_build", "ms_total")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class IpolishedC(C.Structure):
@@ -923,7 +813,7 @@ class IpolishedC(C.Structure):
                                           "d_ev_cover", "d_t_subs", "d_t_dels", "d_t_ins_bases", "d_t_ambiguous", "d_counts", "d_span")]
 
 
-class IndelPolished:
+class IndelPolished(_Result):
     """Result of Engine.polish_indels: zero-copy torch views of the engine's device memory (valid until the next Engine.polish_indels call but
     one on that engine -- the result is double-buffered; clone what has to live longer) -- len int32 [n_targets], col_off int32 [n_targets + 1]
     (the bits of uint32), begin int64 [n_targets], words int32 [(n_columns + 15) / 16 + 2], new_col int32 [n_columns_before + 1]; the events
@@ -933,24 +823,21 @@ class IndelPolished:
             ("new_col", "<i4", np.uint32, "g1"), ("ev_col", "<i4", np.uint32, "e"), ("ev_kind", "|u1", np.uint8, "e"), ("ev_len", "|u1", np.uint8, "e"),
             ("ev_bases", "<i4", np.uint32, "e"), ("ev_votes", "<i4", np.uint32, "e"), ("ev_cover", "<i4", np.uint32, "e"), ("t_subs", "<i8", np.uint64, "t"),
             ("t_dels", "<i8", np.uint64, "t"), ("t_ins_bases", "<i8", np.uint64, "t"), ("t_ambiguous", "<i8", np.uint64, "t"))
+    COUNTS = ("n_targets", "n_columns_before", "n_columns", "n_events")
 
     def __init__(self, c, info, device, source=None):
-        self._c, self.info, self._source = c, info, source
-        self.n_targets, self.n_columns_before, self.n_columns, self.n_events = int(c.n_targets), int(c.n_columns_before), int(c.n_columns), int(c.n_events)
-        dev = "cuda:%d" % device
-        size = dict(t=self.n_targets, t1=self.n_targets + 1, w=(self.n_columns + 15) // 16 + 2, g1=self.n_columns_before + 1, e=self.n_events)
-        for k, typestr, _, n in self.KEYS:
-            setattr(self, k, device_view(getattr(c, "d_" + k), (size[n],), dev, typestr))
-        self.counts = device_view(c.d_counts, (self.n_columns_before, 5), dev, "<i4") if c.d_counts else None
-        self.span = device_view(c.d_span, (self.n_columns_before,), dev, "<i4") if c.d_span else None
+        super().__init__(c, info, device, source)
+        self.counts = device_view(c.d_counts, (self.n_columns_before, 5), self._dev, "<i4") if c.d_counts else None
+        self.span = device_view(c.d_span, (self.n_columns_before,), self._dev, "<i4") if c.d_span else None
+
+    def _sizes(self):
+        return dict(t=self.n_targets, t1=self.n_targets + 1, w=(self.n_columns + 15) // 16 + 2, g1=self.n_columns_before + 1, e=self.n_events)
 
     def to_host(self):
-        """numpy copies, in the dtypes of tests/ipolish_checker.py"""
-        d = {k: getattr(self, k).cpu().numpy().copy().view(dt) for k, _, dt, _ in self.KEYS}
+        d = super().to_host()
         if self.counts is not None:
             d["counts"] = self.counts.cpu().numpy().copy().view(np.uint32)
             d["span"] = self.span.cpu().numpy().copy().view(np.uint32)
-        d["info"] = dict(self.info)
         return d
 
     @property
@@ -2002,12 +1889,8 @@ class Engine:
                                                                    C.byref(placements._c), C.byref(polished._c), 1 if depth else 0, os.fsencode(path), C.byref(info)))
             return info.as_dict()
         if placements is not None:
-            self._check(self._lib.alga_write_final_fasta_depth_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
-                                                                      C.byref(placements._c), os.fsencode(path), C.byref(info)))
-            return info.as_dict()
-        self._check(self._lib.alga_write_final_fasta_device(self._h, C.byref(final._unitigs._c), C.byref(final._consensus._c), C.byref(final._c),
-                                                            os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+            return self._write(self._lib.alga_write_final_fasta_depth_device, path, final._unitigs, final._consensus, final, placements)
+        return self._write(self._lib.alga_write_final_fasta_device, path, final._unitigs, final._consensus, final)
 
     # ---- reads placed on sequences: depth, pairs, inserts (the definition: include/alga_amd.h) -----
     @staticmethod
@@ -2017,70 +1900,47 @@ class Engine:
         p.flags = int(flags) if flags is not None else (PLACE_DEPTH_MULTI if depth_multi else 0)
         return p
 
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    def _write(self, fn, path, *handles):
+        """a text writer of the C ABI over result handles (None where one is optional) -> dict of alga_gfa_info"""
+        info = GfaInfo()
+        self._check(fn(self._h, *[C.byref(h._c) if h is not None else None for h in handles], os.fsencode(path), C.byref(info)))
+        return info.as_dict()
+
     def place_reads(self, words, lens, targets=None, final=None, pair_off=None, stream=None, **params):
         """Every read of a node set in twin layout placed on target sequences (alga_place_reads_device) -> Placements.  words [n, stride] /
         lens [n]: node 2r + 1 is read r, node 2r its reverse complement; pair_off uint8 [n] or None.  targets = (packed words, begin int64 [T],
         len int32 [T]): ragged sequences, sequence t from base index begin[t] on; or final = the result of the LAST Engine.final_contigs
         call: target id == contig id (alga_place_reads_on_final_device).  Host arrays are uploaded first; tensors are used where they are and
         left untouched.  params: k, max_mismatches, max_occ, max_insert, depth_multi."""
-        import torch
         assert (targets is None) != (final is None), "give targets or final"
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if pair_off is not None:
-            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        dev = self._dev()
+        nd, (words, lens, pair_off) = _twin_nodes(words, lens, dev, pair_off)
         pp, out, info = self.place_params(**params), PlacementsC(), PlaceInfo()
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
         if final is not None:
-            torch.cuda.current_stream(dev).synchronize()
             self._check(self._lib.alga_place_reads_on_final_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(final._unitigs._c),
-                                                                   C.byref(final._consensus._c), C.byref(final._c), C.byref(pp), st, C.byref(out), C.byref(info)))
+                                                                   C.byref(final._consensus._c), C.byref(final._c), C.byref(pp), _stream_arg(stream, dev),
+                                                                   C.byref(out), C.byref(info)))
         else:
-            twords, tbegin, tlen = targets
-            twords, tlen = up(twords, np.uint32, np.int32), up(tlen, np.int32)
-            if isinstance(tbegin, np.ndarray):
-                tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
-            assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
-            torch.cuda.current_stream(dev).synchronize()
+            twords, tbegin, tlen = _ragged_targets(targets, dev)
             self._check(self._lib.alga_place_reads_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.c_void_p(_ptr(twords) or None),
-                                                          C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(pp), st,
-                                                          C.byref(out), C.byref(info)))
+                                                          C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(pp),
+                                                          _stream_arg(stream, dev), C.byref(out), C.byref(info)))
         return Placements(out, info.as_dict(), self.device, final)
 
     def polish(self, words, lens, placements, min_cover=3, min_percent=60, multi=False, counts=False, stream=None):
         """The placed targets voted again by every placed read (alga_polish_placed_device) -> Polished.  words / lens: the node set that was
         placed; placements: the result of the LAST Engine.place_reads call.  A column changes to the base with the most votes iff its cover is
         at least min_cover and that base has at least min_percent of it; multi: MULTI reads vote too; counts: keep the four counts per column."""
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        dev = self._dev()
+        nd, keep = _twin_nodes(words, lens, dev)
         pp, out, info = PolishParams(), PolishedC(), PolishInfo()
         pp.min_cover, pp.min_percent, pp.flags = int(min_cover), int(min_percent), (POLISH_MULTI if multi else 0) | (POLISH_COUNTS if counts else 0)
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
-        self._check(self._lib.alga_polish_placed_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(pp), st, C.byref(out), C.byref(info)))
+        self._check(self._lib.alga_polish_placed_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(pp), _stream_arg(stream, dev), C.byref(out),
+                                                        C.byref(info)))
         return Polished(out, info.as_dict(), self.device, placements)
 
     def scaffold(self, words, lens, pair_off, placements, insert=None, max_insert=1000, min_links=5, max_second_percent=50, min_gap=10, stream=None):
@@ -2088,42 +1948,23 @@ class Engine:
         the node set that was placed and its pairing (None: no pairs); placements: the result of the LAST Engine.place_reads call.  insert: the
         library's insert size, by default the placement's insert_median (refused where that is -1: no proper pair was seen).  Two ends are joined
         iff each is the other's only choice: at least min_links links within max_insert, and no second bundle with max_second_percent of them."""
-        import torch
-        dev = torch.device("cuda", self.device)
+        dev = self._dev()
         if insert is None:
             insert = int(placements.info["insert_median"])
             if insert < 0:
                 raise AlgaError(-1, "Engine.scaffold: the placement saw no proper pair (insert_median -1): give insert")
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if pair_off is not None:
-            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        nd, (words, lens, pair_off) = _twin_nodes(words, lens, dev, pair_off)
         pp, out, info = ScaffoldParams(), ScaffoldsC(), ScaffoldInfo()
         pp.insert, pp.max_insert, pp.min_links, pp.max_second_percent, pp.min_gap = int(insert), int(max_insert), int(min_links), int(max_second_percent), int(min_gap)
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
-        self._check(self._lib.alga_scaffold_placed_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(placements._c), C.byref(pp), st, C.byref(out),
-                                                          C.byref(info)))
+        self._check(self._lib.alga_scaffold_placed_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(placements._c), C.byref(pp),
+                                                          _stream_arg(stream, dev), C.byref(out), C.byref(info)))
         return Scaffolds(out, info.as_dict(), self.device, placements)
 
     def write_scaffold_fasta(self, path, placements, scaffolds, polished=None):
         """The scaffolds of the LAST Engine.scaffold call as FASTA (alga_write_scaffold_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>scaffold_id=<j>_length=<len>_contigs=<m>` and the contigs with their gaps as runs of N on one line, in id order.  polished:
         the result of the LAST Engine.polish of those placements -- the bases are then the polished ones."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_scaffold_fasta_device(self._h, C.byref(placements._c), C.byref(scaffolds._c),
-                                                               C.byref(polished._c) if polished is not None else None, os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+        return self._write(self._lib.alga_write_scaffold_fasta_device, path, placements, scaffolds, polished)
 
     def break_contigs(self, words, lens, pair_off, placements, polished=None, margin=None, min_span=1, inset=21, stream=None):
         """The placed targets cut where no proper pair spans them (alga_break_placed_device) -> Broken.  words / lens / pair_off: the node set
@@ -2132,40 +1973,23 @@ class Engine:
         inset behind its first to inset before its last; a stretch of columns spanned by fewer than min_span pairs, at least margin columns
         from both ends of its target and with spanned columns on both sides, is cut in its middle.  margin: by default the placement's
         insert_median (refused where that is -1: no proper pair was seen)."""
-        import torch
-        dev = torch.device("cuda", self.device)
+        dev = self._dev()
         if margin is None:
             margin = int(placements.info["insert_median"])
             if margin < 0:
                 raise AlgaError(-1, "Engine.break_contigs: the placement saw no proper pair (insert_median -1): give margin")
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if pair_off is not None:
-            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        nd, (words, lens, pair_off) = _twin_nodes(words, lens, dev, pair_off)
         pp, out, info = BreakParams(), BrokenC(), BreakInfo()
         pp.min_span, pp.inset, pp.margin = int(min_span), int(inset), int(margin)
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
         self._check(self._lib.alga_break_placed_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(placements._c),
-                                                       C.byref(polished._c) if polished is not None else None, C.byref(pp), st, C.byref(out), C.byref(info)))
+                                                       C.byref(polished._c) if polished is not None else None, C.byref(pp), _stream_arg(stream, dev),
+                                                       C.byref(out), C.byref(info)))
         return Broken(out, info.as_dict(), self.device, placements)
 
     def write_broken_fasta(self, path, broken):
         """The pieces of the LAST Engine.break_contigs call as FASTA (alga_write_broken_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>contig_id=<j>_length=<len>_from=<t>_start=<s>` per piece with a length, j the piece id."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_broken_fasta_device(self._h, C.byref(broken._c), os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+        return self._write(self._lib.alga_write_broken_fasta_device, path, broken)
 
     def grow_ends(self, words, lens, placements, polished=None, stream=None, **params):
         """The ends of the placed targets grown with the unplaced reads that hang over them (alga_grow_placed_device) -> Grown.  words / lens:
@@ -2173,78 +1997,39 @@ class Engine:
         Engine.polish of those placements -- the grown targets then carry the polished bases.  params: k, max_mismatches, max_occ, min_anchor,
         min_cover, min_percent, max_grow (the fields of alga_grow_params; the library's defaults where not given).  A further round is a
         placement on Grown.targets() and a further call."""
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        dev = self._dev()
+        nd, keep = _twin_nodes(words, lens, dev)
         pp, out, info = GrowParams(), GrownC(), GrowInfo()
         self._lib.alga_grow_default_params(C.byref(pp))
-        for k, v in params.items():
-            if k not in ("k", "max_mismatches", "max_occ", "min_anchor", "min_cover", "min_percent", "max_grow", "flags"):
-                raise TypeError("Engine.grow_ends: unknown parameter %r" % k)
-            setattr(pp, k, int(v))
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
+        _set_params(pp, params, ("k", "max_mismatches", "max_occ", "min_anchor", "min_cover", "min_percent", "max_grow", "flags"), "Engine.grow_ends")
         self._check(self._lib.alga_grow_placed_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(polished._c) if polished is not None else None,
-                                                      C.byref(pp), st, C.byref(out), C.byref(info)))
+                                                      C.byref(pp), _stream_arg(stream, dev), C.byref(out), C.byref(info)))
         return Grown(out, info.as_dict(), self.device, placements)
 
     def write_grown_fasta(self, path, grown):
         """The grown targets of the LAST Engine.grow_ends call as FASTA (alga_write_grown_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>contig_id=<t>_length=<len>_left=<xl>_right=<xr>` per target with a length."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_grown_fasta_device(self._h, C.byref(grown._c), os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+        return self._write(self._lib.alga_write_grown_fasta_device, path, grown)
 
     def merge_ends(self, targets, stream=None, **params):
         """Contigs whose ends overlap merged into one sequence (alga_merge_targets_device) -> Merged.  targets = (packed words, begin int64 [T],
         len int32 [T]): ragged sequences as Engine.place_reads takes them, for instance Grown.targets() or the Merged.targets() of the call
         before.  Host arrays are uploaded first; tensors are used where they are and left untouched.  params: k, max_mismatches, max_occ,
         min_overlap, max_overlap (the fields of alga_merge_params; the library's defaults where not given)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        twords, tbegin, tlen = targets
-        twords, tlen = up(twords, np.uint32, np.int32), up(tlen, np.int32)
-        if isinstance(tbegin, np.ndarray):
-            tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
-        assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
+        dev = self._dev()
+        twords, tbegin, tlen = _ragged_targets(targets, dev)
         assert twords.is_contiguous()
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
         pp, out, info = MergeParams(), MergedC(), MergeInfo()
         self._lib.alga_merge_default_params(C.byref(pp))
-        for k, v in params.items():
-            if k not in ("k", "max_mismatches", "max_occ", "min_overlap", "max_overlap", "flags"):
-                raise TypeError("Engine.merge_ends: unknown parameter %r" % k)
-            setattr(pp, k, int(v))
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
+        _set_params(pp, params, ("k", "max_mismatches", "max_occ", "min_overlap", "max_overlap", "flags"), "Engine.merge_ends")
         self._check(self._lib.alga_merge_targets_device(self._h, C.c_void_p(_ptr(twords) or None), C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None),
-                                                        int(tlen.shape[0]), C.byref(pp), st, C.byref(out), C.byref(info)))
-        return Merged(out, info.as_dict(), self.device, (twords, tbegin, tlen))
+                                                        int(tlen.shape[0]), C.byref(pp), _stream_arg(stream, dev), C.byref(out), C.byref(info)))
+        return Merged(out, info.as_dict(), self.device, (twords, tbegin, tlen))     # the tensors the targets came from stay alive with the result
 
     def write_merged_fasta(self, path, merged):
         """The merged contigs of the LAST Engine.merge_ends call as FASTA (alga_write_merged_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>contig_id=<j>_length=<len>_contigs=<m>` per merged contig."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_merged_fasta_device(self._h, C.byref(merged._c), os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+        return self._write(self._lib.alga_write_merged_fasta_device, path, merged)
 
     def place_gapped(self, words, lens, placements, targets=None, final=None, stream=None, **params):
         """The reads the Hamming placement left unplaced laid onto the same targets by edit distance (alga_place_gapped_device) -> Gapped.
@@ -2254,16 +2039,8 @@ class Engine:
         the library's defaults where not given)."""
         import torch
         assert (targets is None) != (final is None), "give targets or final"
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+        dev = self._dev()
+        nd, keep = _twin_nodes(words, lens, dev)
         if final is not None:
             # the targets of alga_place_reads_on_final_device: target j = the window of the pair order[j] in the consensus words
             u, fin = final._unitigs, final
@@ -2273,33 +2050,19 @@ class Engine:
             tbegin = (16 * u.word_off.to(torch.int64)[order] + torch.where(live, fin.begin.to(torch.int64)[order], zero)).contiguous()
             tlen = torch.where(live, fin.len.to(torch.int64)[order], zero).to(torch.int32).contiguous()
             targets = (final._consensus.words, tbegin, tlen)
-        twords, tbegin, tlen = targets
-        twords, tlen = up(twords, np.uint32, np.int32), up(tlen, np.int32)
-        if isinstance(tbegin, np.ndarray):
-            tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
-        assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        twords, tbegin, tlen = _ragged_targets(targets, dev)
         pp, out, info = GappedParams(), GappedC(), GappedInfo()
         self._lib.alga_gapped_default_params(C.byref(pp))
-        for k, v in params.items():
-            if k not in ("k", "max_edits", "max_occ", "flags"):
-                raise TypeError("Engine.place_gapped: unknown parameter %r" % k)
-            setattr(pp, k, int(v))
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
+        _set_params(pp, params, ("k", "max_edits", "max_occ", "flags"), "Engine.place_gapped")
         self._check(self._lib.alga_place_gapped_device(self._h, C.byref(nd), C.c_void_p(_ptr(twords) or None), C.c_void_p(_ptr(tbegin) or None),
-                                                       C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(placements._c), C.byref(pp), st, C.byref(out),
-                                                       C.byref(info)))
+                                                       C.c_void_p(_ptr(tlen) or None), int(tlen.shape[0]), C.byref(placements._c), C.byref(pp),
+                                                       _stream_arg(stream, dev), C.byref(out), C.byref(info)))
         return Gapped(out, info.as_dict(), self.device, (placements, twords, tbegin, tlen))
 
     def write_gapped_tsv(self, path, gapped):
         """The gapped placements of the LAST Engine.place_gapped call as text (alga_write_gapped_tsv_device) -> dict of alga_gfa_info (segments =
         lines): `read target pos end strand edits unique cigar` (tabs) per gapped-placed read, in read order."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_gapped_tsv_device(self._h, C.byref(gapped._c), os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+        return self._write(self._lib.alga_write_gapped_tsv_device, path, gapped)
 
     def polish_indels(self, words, lens, placements, gapped, min_cover=3, min_percent=60, max_ins=6, counts=False, stream=None):
         """The placed targets voted by the Hamming-placed and the gapped reads together (alga_polish_indels_device) -> IndelPolished: columns
@@ -2307,83 +2070,39 @@ class Engine:
         that was placed; placements: the result of the LAST Engine.place_reads call; gapped: the result of the LAST Engine.place_gapped call,
         made from those placements.  counts: keep the five counts per column and the span per slot.  A further round is a placement on
         IndelPolished.targets."""
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens = up(words, np.uint32, np.int32), up(lens, np.int32)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
-        nd = _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None)
+        dev = self._dev()
+        nd, keep = _twin_nodes(words, lens, dev)
         pp, out, info = IpolishParams(), IpolishedC(), IpolishInfo()
         pp.min_cover, pp.min_percent, pp.max_ins, pp.flags = int(min_cover), int(min_percent), int(max_ins), IPOLISH_COUNTS if counts else 0
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
-        self._check(self._lib.alga_polish_indels_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(gapped._c), C.byref(pp), st, C.byref(out), C.byref(info)))
+        self._check(self._lib.alga_polish_indels_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(gapped._c), C.byref(pp), _stream_arg(stream, dev),
+                                                        C.byref(out), C.byref(info)))
         return IndelPolished(out, info.as_dict(), self.device, (placements, gapped))
 
     def write_ipolished_fasta(self, path, ipolished):
         """The new targets of the LAST Engine.polish_indels call as FASTA (alga_write_ipolished_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>contig_id=<t>_length=<len>_subs=<s>_ins=<i>_dels=<d>` per target with a length."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_ipolished_fasta_device(self._h, C.byref(ipolished._c), os.fsencode(path), C.byref(info)))
-        return info.as_dict()
+        return self._write(self._lib.alga_write_ipolished_fasta_device, path, ipolished)
 
     def write_ipolish_events_tsv(self, path, ipolished):
         """The events of the LAST Engine.polish_indels call as text (alga_write_ipolish_events_tsv_device) -> dict of alga_gfa_info (segments =
         lines): `contig pos kind len old new votes cover` (tabs) per event, pos the old position inside the contig."""
-        info = GfaInfo()
-        self._check(self._lib.alga_write_ipolish_events_tsv_device(self._h, C.byref(ipolished._c), os.fsencode(path), C.byref(info)))
-        return info.as_dict()
-
-    def _placed_nodes(self, words, lens, pair_off=None):
-        """the node set of a placement as the C ABI takes it: host arrays uploaded, tensors used where they are -> (_Nodes, the tensors kept alive)"""
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def up(x, dt, view=None):
-            if x is None or not isinstance(x, np.ndarray):
-                return x
-            a = np.ascontiguousarray(x, dtype=dt)
-            return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
-        words, lens, pair_off = up(words, np.uint32, np.int32), up(lens, np.int32), up(pair_off, np.uint8)
-        n = int(lens.shape[0])
-        assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
-        if pair_off is not None:
-            assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
-        return _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None), (words, lens, pair_off)
+        return self._write(self._lib.alga_write_ipolish_events_tsv_device, path, ipolished)
 
     def judge_pairs(self, words, lens, placements, gapped=None, pair_off=None, max_insert=None, stream=None, **params):
         """Every pair judged over the Hamming and the gapped placement together, the SAM FLAG and TLEN of every read
         (alga_judge_pairs_device) -> PairCalls.  words / lens / pair_off: the node set that was placed and its pairing (None: no pairs);
         placements: the result of the LAST Engine.place_reads call; gapped: the result of the LAST Engine.place_gapped call made from it, or
         None: the Hamming pass alone.  max_insert: the library's default (1000) where not given.  params: flags, reserved (tests)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        nd, keep = self._placed_nodes(words, lens, pair_off)
-        if stream is not None:
-            torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+        dev = self._dev()
+        nd, (words, lens, pair_off) = _twin_nodes(words, lens, dev, pair_off)
         pp, out, info = PairParams(), PairCallsC(), PairInfo()
         self._lib.alga_pair_default_params(C.byref(pp))
         if max_insert is not None:
             pp.max_insert = int(max_insert)
-        for k, v in params.items():
-            if k == "flags":
-                pp.flags = int(v)
-            elif k == "reserved":
-                pp.reserved[0] = int(v)
-            else:
-                raise TypeError("Engine.judge_pairs: unknown parameter %r" % k)
-        st = C.c_void_p(stream) if isinstance(stream, int) and stream else None
-        torch.cuda.current_stream(dev).synchronize()
-        self._check(self._lib.alga_judge_pairs_device(self._h, C.byref(nd), C.c_void_p(_ptr(keep[2]) or None), C.byref(placements._c),
-                                                      C.byref(gapped._c) if gapped is not None else None, C.byref(pp), st, C.byref(out), C.byref(info)))
+        _set_params(pp, params, ("flags", "reserved"), "Engine.judge_pairs")
+        self._check(self._lib.alga_judge_pairs_device(self._h, C.byref(nd), C.c_void_p(_ptr(pair_off) or None), C.byref(placements._c),
+                                                      C.byref(gapped._c) if gapped is not None else None, C.byref(pp), _stream_arg(stream, dev), C.byref(out),
+                                                      C.byref(info)))
         return PairCalls(out, info.as_dict(), self.device, (placements, gapped))
 
     def write_sam(self, path, words, lens, placements, calls, gapped=None, names_depth=False, skip_unplaced=False, **params):
@@ -2391,18 +2110,12 @@ class Engine:
         words / lens: the node set that was placed; placements / gapped: as Engine.judge_pairs was given them; calls: the result of the LAST
         Engine.judge_pairs call.  names_depth: the @SQ names as the depth FASTA's header token (contig_id=.._length=.._reads=.._depth=..),
         else as the plain final FASTA's; skip_unplaced: no records for unplaced reads.  QNAME is r<index>: the engine keeps no read names."""
-        import torch
-        nd, keep = self._placed_nodes(words, lens)
+        dev = self._dev()
+        nd, keep = _twin_nodes(words, lens, dev)
         pp, info = SamParams(), GfaInfo()
         pp.flags = (SAM_NAMES_DEPTH if names_depth else 0) | (SAM_SKIP_UNPLACED if skip_unplaced else 0)
-        for k, v in params.items():
-            if k == "flags":
-                pp.flags = int(v)
-            elif k == "reserved":
-                pp.reserved[0] = int(v)
-            else:
-                raise TypeError("Engine.write_sam: unknown parameter %r" % k)
-        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+        _set_params(pp, params, ("flags", "reserved"), "Engine.write_sam")
+        _stream_arg(None, dev)
         self._check(self._lib.alga_write_sam_device(self._h, C.byref(nd), C.byref(placements._c), C.byref(gapped._c) if gapped is not None else None,
                                                     C.byref(calls._c), C.byref(pp), os.fsencode(path), C.byref(info)))
         return info.as_dict()
@@ -2526,6 +2239,60 @@ class MultiEngine:
         d = {k: getattr(st, k) for k, _ in st._fields_}
         d["ranks"] = [x.as_dict() for x in per]
         return d
+
+
+def _upload(x, dt, dev, view=None):
+    """a host array as a tensor on `dev` (converted to dt, its bits seen as `view` where given); None and tensors are passed through"""
+    if x is None or not isinstance(x, np.ndarray):
+        return x
+    import torch
+    a = np.ascontiguousarray(x, dtype=dt)
+    return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+
+
+def _twin_nodes(words, lens, dev, pair_off=None):
+    """a node set in twin layout as the C ABI takes it: host arrays uploaded, tensors used where they are -> (_Nodes, (words, lens, pair_off): the
+    tensors behind its pointers, for the caller to keep alive)"""
+    import torch
+    words, lens, pair_off = _upload(words, np.uint32, dev, np.int32), _upload(lens, np.int32, dev), _upload(pair_off, np.uint8, dev)
+    n = int(lens.shape[0])
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and words.is_contiguous()
+    if pair_off is not None:
+        assert pair_off.dtype == torch.uint8 and pair_off.is_contiguous() and int(pair_off.shape[0]) == n
+    return _Nodes(_ptr(words), int(words.shape[1]) if words.dim() == 2 and n else 1, _ptr(lens), n, None, None), (words, lens, pair_off)
+
+
+def _ragged_targets(targets, dev):
+    """(packed words, begin int64 [T], len int32 [T]) as tensors on `dev`: host arrays uploaded, tensors used where they are"""
+    import torch
+    twords, tbegin, tlen = targets
+    twords, tlen = _upload(twords, np.uint32, dev, np.int32), _upload(tlen, np.int32, dev)
+    if isinstance(tbegin, np.ndarray):
+        tbegin = torch.from_numpy(np.ascontiguousarray(tbegin).astype(np.int64)).to(dev)
+    assert tbegin.dtype == torch.int64 and tlen.dtype == torch.int32 and tbegin.shape == tlen.shape and tbegin.is_contiguous() and tlen.is_contiguous()
+    return twords, tbegin, tlen
+
+
+def _stream_arg(stream, dev):
+    """what a stage call needs of the streams: the caller's stream (a torch stream or a raw handle) and torch's current one have finished what
+    they were given (the uploads among it) -> the raw handle as the C ABI takes it (None: the engine's own stream)"""
+    import torch
+    if stream is not None:
+        torch.cuda.ExternalStream(stream).synchronize() if isinstance(stream, int) else stream.synchronize()
+    torch.cuda.current_stream(dev).synchronize()
+    return C.c_void_p(stream) if isinstance(stream, int) and stream else None
+
+
+def _set_params(pp, params, names, who):
+    """the fields `names` of a params struct from **params (`reserved`: its first entry); another name is a TypeError"""
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError("%s: unknown parameter %r" % (who, k))
+        if k == "reserved":
+            pp.reserved[0] = int(v)
+        else:
+            setattr(pp, k, int(v))
+    return pp
 
 
 def _ptr(x):
