@@ -239,6 +239,16 @@ struct alga_engine {
     int         opt_merge_max_blocks = 8192;       // option "merge_max_blocks": the cap of the k_mg_* grids (tests make every grid-stride loop take further passes)
     bool        mg_valid = false;
     uint64_t    mg_targets = 0, mg_merged = 0, mg_columns = 0, mg_longest = 0;   // ... of this many targets, merged contigs and columns; the longest merged contig
+    // scaffold joins whose contig ends overlap stitched into one sequence (engine_stitch.hip).  Workspaces of its own: counters, the per-end
+    // count, the per-end arrays the merge stage's launchers take (partner, olen, mm, hits, state), begin / len of a placement's targets; the
+    // join of every end, the lists, head / first / members and their scans are the merge stage's workspaces (mg_join, mg_lists, mg_head,
+    // mg_first, mg_scan: nothing in them outlives a call).  The result, twice, as for the grow
+    DevBuf      st_cnt, st_endcnt, st_epartner, st_eolen, st_emm, st_ehits, st_estate, st_tbegin, st_tlen;
+    struct StitchSet { DevBuf jolen, jmm, jhits, jstate, endentry, stitched, rank, orient, start, ovafter, soff, smembers, len, coloff, begin, words; } st_set[2];
+    int         st_cur = 0;                        // the set that holds the result
+    int         opt_stitch_max_blocks = 8192;      // option "stitch_max_blocks": the cap of the k_st_* grids and of the merge stage's kernels launched from the stitch (tests make every grid-stride loop take further passes)
+    bool        st_valid = false;
+    uint64_t    st_targets = 0, st_entries = 0, st_stitched = 0, st_columns = 0, st_longest = 0;   // ... of this many targets, entries, stitched contigs and columns; the longest stitched contig
     // the unplaced reads laid with indels (engine_gapped.hip).  Workspaces: counters, the participation flags, their scan and the list, this
     // stage's column array, the best key per participating read, the strided runs and their numbers, the difference array and its scan.  The
     // result: per read target / pos / end / edits / state, the CIGAR offsets and runs, the cover, the per-target sums

@@ -186,6 +186,7 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device",
            "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device",
            "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device",
+           "alga_stitch_default_params", "alga_stitch_targets_device", "alga_stitch_scaffolds_device", "alga_write_stitched_fasta_device",
            "alga_gapped_default_params", "alga_place_gapped_device", "alga_write_gapped_tsv_device",
            "alga_ipolish_default_params", "alga_polish_indels_device", "alga_write_ipolished_fasta_device", "alga_write_ipolish_events_tsv_device",
            "alga_pair_default_params", "alga_judge_pairs_device", "alga_write_sam_device"]
@@ -705,6 +706,65 @@ def merge_tsv(h, tlen):
     return "".join(lines)
 
 
+STITCH_SELECTED, STITCH_HAS_OVERLAP, STITCH_AMBIGUOUS, STITCH_STITCHED, STITCH_DROPPED_CYCLE = 1, 2, 4, 8, 16   # bits of Stitched.j_state
+
+
+class StitchParams(C.Structure):
+    """alga_stitch_params"""
+    _fields_ = [(k, C.c_int32) for k in ("max_mismatches", "min_overlap", "max_overlap", "slack", "flags")] + [("reserved", C.c_int32 * 3)]
+
+
+class StitchInfo(_Info):
+    """alga_stitch_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("entries", "selected", "with_overlap", "ambiguous", "hits_saturated", "candidates_outside_slack", "stitched", "dropped_cycle",
+                                          "join_mismatches", "bases_removed", "longest_overlap", "contigs", "contigs_multi", "longest", "columns_before",
+                                          "columns_after", "n50_before", "n50_after")] + \
+               [(k, C.c_double) for k in ("ms_overlap", "ms_build", "ms_total")]
+
+
+class StitchedC(C.Structure):
+    """alga_stitched"""
+    _fields_ = [(k, C.c_int64) for k in ("n_targets", "n_entries", "n_stitched", "n_members")] + [("n_columns", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_j_olen", "d_j_mm", "d_j_hits", "d_j_state", "d_end_entry", "d_stitched", "d_rank", "d_orient", "d_start", "d_overlap_after",
+                                          "d_s_off", "d_s_members", "d_len", "d_col_off", "d_begin", "d_words")]
+
+
+class Stitched(_RaggedResult):
+    """Result of Engine.stitch / Engine.stitch_targets: zero-copy torch views of the engine's device memory (valid until the next stitch call on
+    that engine; clone what has to live longer) -- per entry j_olen int32, j_mm / j_hits / j_state uint8 [n_entries]; end_entry int32
+    [2 * n_targets]; per target stitched / rank int32, orient uint8, start int32 (the bits of uint32), overlap_after int32; s_off int32
+    [n_stitched + 1], s_members int32 [n_members]; len int32 [n_stitched], col_off int32 [n_stitched + 1], begin int64 [n_stitched], words int32
+    [(n_columns + 15) / 16 + 2] (the result's own copy of the bases) -- and .info (dict of alga_stitch_info)."""
+    KEYS = (("j_olen", "<i4", np.int32, "j"), ("j_mm", "|u1", np.uint8, "j"), ("j_hits", "|u1", np.uint8, "j"), ("j_state", "|u1", np.uint8, "j"),
+            ("end_entry", "<i4", np.int32, "e"), ("stitched", "<i4", np.int32, "t"), ("rank", "<i4", np.int32, "t"), ("orient", "|u1", np.uint8, "t"),
+            ("start", "<i4", np.uint32, "t"), ("overlap_after", "<i4", np.int32, "t"), ("s_off", "<i4", np.uint32, "s1"), ("s_members", "<i4", np.int32, "sm"),
+            ("len", "<i4", np.int32, "s"), ("col_off", "<i4", np.uint32, "s1"), ("begin", "<i8", np.uint64, "s"), ("words", "<i4", np.uint32, "w"))
+    COUNTS = ("n_targets", "n_entries", "n_stitched", "n_members", "n_columns")
+
+    def _sizes(self):
+        return dict(j=self.n_entries, e=2 * self.n_targets, t=self.n_targets, s=self.n_stitched, s1=self.n_stitched + 1, sm=self.n_members,
+                    w=(self.n_columns + 15) // 16 + 2)
+
+    def stitch_tsv(self, tlen=None, host=None):
+        """one line per member in (stitched, rank) order: stitched, rank, contig, orient, start, length, overlap_after, mm (tabs); tlen: the
+        lengths of the targets that were stitched (by default read back from the targets of the call); the text alga_hip --stitch_layout= writes"""
+        if tlen is None:
+            tlen = self._source[2].cpu().numpy()
+        return stitch_tsv(host if host is not None else self.to_host(), tlen)
+
+
+def stitch_tsv(h, tlen):
+    """the layout of a stitch result read back (Stitched.to_host())"""
+    lines = []
+    for j in range(len(h["len"])):
+        for c in h["s_members"][int(h["s_off"][j]):int(h["s_off"][j + 1])]:
+            c = int(c)
+            out = 2 * c + (int(h["orient"][c]) ^ 1)
+            lines.append("%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\n" % (j, int(h["rank"][c]), c, "-" if h["orient"][c] else "+", int(h["start"][c]), int(tlen[c]),
+                                                             int(h["overlap_after"][c]), int(h["j_mm"][int(h["end_entry"][out])]) if h["overlap_after"][c] else 0))
+    return "".join(lines)
+
+
 GAPPED_MAX_READ = 1024                                           # ALGA_GAPPED_MAX_READ
 GAPPED_PLACED, GAPPED_UNIQUE, GAPPED_MINUS, GAPPED_INDEL = 1, 2, 4, 8   # bits of Gapped.state
 CIGAR_M, CIGAR_I, CIGAR_D = 0, 1, 2                              # the low two bits of a Gapped.cigar entry
@@ -1011,6 +1071,13 @@ def load_library():
     lib.alga_merge_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MergeParams), C.c_void_p, C.POINTER(MergedC),
                                               C.POINTER(MergeInfo)]
     lib.alga_write_merged_fasta_device.argtypes = [C.c_void_p, C.POINTER(MergedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_stitch_default_params.argtypes = [C.POINTER(StitchParams)]
+    lib.alga_stitch_default_params.restype = None
+    lib.alga_stitch_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.POINTER(StitchParams), C.c_void_p, C.POINTER(StitchedC), C.POINTER(StitchInfo)]
+    lib.alga_stitch_scaffolds_device.argtypes = [C.c_void_p, C.POINTER(PlacementsC), C.POINTER(ScaffoldsC), C.POINTER(PolishedC), C.POINTER(StitchParams), C.c_void_p,
+                                                 C.POINTER(StitchedC), C.POINTER(StitchInfo)]
+    lib.alga_write_stitched_fasta_device.argtypes = [C.c_void_p, C.POINTER(StitchedC), C.c_char_p, C.POINTER(GfaInfo)]
     lib.alga_gapped_default_params.argtypes = [C.POINTER(GappedParams)]
     lib.alga_gapped_default_params.restype = None
     lib.alga_place_gapped_device.argtypes = [C.c_void_p, C.POINTER(_Nodes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PlacementsC), C.POINTER(GappedParams),
@@ -2030,6 +2097,54 @@ class Engine:
         """The merged contigs of the LAST Engine.merge_ends call as FASTA (alga_write_merged_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>contig_id=<j>_length=<len>_contigs=<m>` per merged contig."""
         return self._write(self._lib.alga_write_merged_fasta_device, path, merged)
+
+    _STITCH_PARAMS = ("max_mismatches", "min_overlap", "max_overlap", "slack", "flags")
+
+    def stitch(self, placements, scaffolds, polished=None, stream=None, **params):
+        """The joins of the scaffolds whose two contig ends overlap stitched into one sequence (alga_stitch_scaffolds_device) -> Stitched.
+        placements: the result of the LAST Engine.place_reads call; scaffolds: the result of the LAST Engine.scaffold call on it (its bundles
+        are the entries); polished: the result of the LAST Engine.polish of those placements -- the stitched contigs then carry the polished
+        bases.  params: max_mismatches, min_overlap, max_overlap, slack (the fields of alga_stitch_params; the library's defaults where not
+        given).  A further round is a placement on Stitched.targets(), a scaffold call and a further call."""
+        import torch
+        dev = self._dev()
+        pp, out, info = StitchParams(), StitchedC(), StitchInfo()
+        self._lib.alga_stitch_default_params(C.byref(pp))
+        _set_params(pp, params, self._STITCH_PARAMS, "Engine.stitch")
+        self._check(self._lib.alga_stitch_scaffolds_device(self._h, C.byref(placements._c), C.byref(scaffolds._c), C.byref(polished._c) if polished is not None else None,
+                                                           C.byref(pp), _stream_arg(stream, dev), C.byref(out), C.byref(info)))
+        off = placements.col_off.to(torch.int64) & 0xFFFFFFFF                    # (the bits of uint32)
+        return Stitched(out, info.as_dict(), self.device, (placements, scaffolds, (off[1:] - off[:-1]).to(torch.int32)))
+
+    def stitch_targets(self, targets, entries, stream=None, **params):
+        """The entries whose two contig ends overlap stitched into one sequence (alga_stitch_targets_device) -> Stitched.  targets = (packed
+        words, begin int64 [T], len int32 [T]): ragged sequences as Engine.place_reads takes them, for instance Merged.targets() or the
+        Stitched.targets() of the call before.  entries = (a, b, gap[, state]): ends a / b (uint32 as host arrays, int32 with the same bits as
+        tensors; x = 2t left, 2t + 1 right), gap int32, state uint8 as Scaffolds.b_state (None or left out: every entry is selected).  Host
+        arrays are uploaded first; tensors are used where they are and left untouched.  params: as Engine.stitch."""
+        import torch
+        dev = self._dev()
+        twords, tbegin, tlen = _ragged_targets(targets, dev)
+        assert twords.is_contiguous()
+        ja, jb, jgap = _upload(entries[0], np.uint32, dev, np.int32), _upload(entries[1], np.uint32, dev, np.int32), _upload(entries[2], np.int32, dev)
+        jstate = _upload(entries[3], np.uint8, dev) if len(entries) > 3 else None
+        J = int(ja.shape[0])
+        for x in (ja, jb, jgap):
+            assert x.dtype == torch.int32 and x.shape == (J,) and x.is_contiguous()
+        assert jstate is None or (jstate.dtype == torch.uint8 and jstate.shape == (J,) and jstate.is_contiguous())
+        pp, out, info = StitchParams(), StitchedC(), StitchInfo()
+        self._lib.alga_stitch_default_params(C.byref(pp))
+        _set_params(pp, params, self._STITCH_PARAMS, "Engine.stitch_targets")
+        self._check(self._lib.alga_stitch_targets_device(self._h, C.c_void_p(_ptr(twords) or None), C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None),
+                                                         int(tlen.shape[0]), C.c_void_p(_ptr(ja) or None), C.c_void_p(_ptr(jb) or None), C.c_void_p(_ptr(jgap) or None),
+                                                         C.c_void_p(_ptr(jstate) or None) if jstate is not None else None, J, C.byref(pp), _stream_arg(stream, dev),
+                                                         C.byref(out), C.byref(info)))
+        return Stitched(out, info.as_dict(), self.device, (twords, tbegin, tlen, ja, jb, jgap, jstate))   # what the call read stays alive with the result
+
+    def write_stitched_fasta(self, path, stitched):
+        """The stitched contigs of the LAST stitch call as FASTA (alga_write_stitched_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>contig_id=<j>_length=<len>_contigs=<m>` per stitched contig."""
+        return self._write(self._lib.alga_write_stitched_fasta_device, path, stitched)
 
     def place_gapped(self, words, lens, placements, targets=None, final=None, stream=None, **params):
         """The reads the Hamming placement left unplaced laid onto the same targets by edit distance (alga_place_gapped_device) -> Gapped.

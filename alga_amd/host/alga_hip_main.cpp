@@ -97,6 +97,13 @@
 // `>contig_id=<j>_length=<len>_contigs=<m>` (alga_write_merged_fasta_device); --merge_layout=PATH: one line `merged rank contig orient start
 // length overlap_after mm` per member, tab separated (both need --merge_ends=1).  One line on stderr gives overlaps / ambiguous ends / joins /
 // bases removed / N50 before -> after.  Without --merge_ends=1 every file is what it was.  None is passed through.
+// --stitch=1 (default 0; needs --scaffolds=): the placement the scaffolds would be made from is scaffolded a first time, the joins whose two contig
+// ends overlap are stitched into one sequence (alga_stitch_scaffolds_device: --stitch_min_overlap= (16), --stitch_max_mismatches= (2),
+// --stitch_slack= (2^20); with --polish=1 the bases are the polished ones), the reads are placed again on the stitched contigs, and --scaffolds= and
+// --scaffold_layout= describe the scaffolding of that placement (contig ids there are stitched ids).  --stitched=PATH: the stitched contigs,
+// `>contig_id=<j>_length=<len>_contigs=<m>` (alga_write_stitched_fasta_device); --stitch_layout=PATH: one line `stitched rank contig orient start
+// length overlap_after mm` per member, tab separated (both need --stitch=1).  One line on stderr gives selected / with an overlap / ambiguous /
+// stitched / bases removed / N50 before -> after.  Without --stitch=1 every file is what it was.  None is passed through.
 // --gapped=1 (default 0; needs --contigs_final=; implies the placement): behind the placement on the final contigs the reads it left unplaced are
 // laid onto the same contigs by edit distance (alga_place_gapped_device: --gapped_edits= (6, 1 .. 15)).  --gapped_placements=PATH (needs
 // --gapped=1): one line `read target pos end strand edits unique cigar` per gapped-placed read, tab separated, formatted on the device
@@ -144,6 +151,7 @@ static const char *USAGE =
     "         [--grow_ends=N] [--grown=grown.fasta] [--grow_layout=grow.tsv] [--grow_min_anchor=63] [--grow_max_mismatches=2] [--grow_min_cover=3]\n"
     "         [--grow_min_percent=80] [--grow_max=64]\n"
     "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n"
+    "         [--stitch=0|1] [--stitched=stitched.fasta] [--stitch_layout=stitch.tsv] [--stitch_min_overlap=16] [--stitch_max_mismatches=2] [--stitch_slack=1048576]\n"
     "         [--gapped=0|1] [--gapped_edits=6] [--gapped_placements=gapped.tsv]\n"
     "         [--polish_indels=0|1] [--polish_max_ins=6] [--ipolished=ipolished.fasta] [--ipolish_events=events.tsv]\n"
     "         [--sam=reads.sam] [--sam_unplaced=0|1]\n";
@@ -185,6 +193,10 @@ int main(int argc, char **argv) {
     std::string merged_path, merge_layout;
     alga_merge_params mgp;
     alga_merge_default_params(&mgp);
+    int stitch = 0;
+    std::string stitched_path, stitch_layout;
+    alga_stitch_params stp;
+    alga_stitch_default_params(&stp);
     alga_correct_params crp;
     alga_correct_default_params(&crp);
     std::vector<int32_t> gpu_list;
@@ -253,6 +265,12 @@ int main(int argc, char **argv) {
         else if (opt(a, "--merge_layout", v)) merge_layout = v;
         else if (opt(a, "--merge_min_overlap", v)) mgp.min_overlap = atoi(v.c_str());
         else if (opt(a, "--merge_max_mismatches", v)) mgp.max_mismatches = atoi(v.c_str());
+        else if (opt(a, "--stitch", v)) stitch = atoi(v.c_str());
+        else if (opt(a, "--stitched", v)) stitched_path = v;
+        else if (opt(a, "--stitch_layout", v)) stitch_layout = v;
+        else if (opt(a, "--stitch_min_overlap", v)) stp.min_overlap = atoi(v.c_str());
+        else if (opt(a, "--stitch_max_mismatches", v)) stp.max_mismatches = atoi(v.c_str());
+        else if (opt(a, "--stitch_slack", v)) stp.slack = atoi(v.c_str());
         else if (opt(a, "--contigs_new_reads_percent", v)) contigs_new_reads_percent = atoi(v.c_str());
         else if (opt(a, "--contigs_trim_threshold", v)) contigs_trim_threshold = atoi(v.c_str());
         else if (opt(a, "--paired_extend", v)) paired_extend = atoi(v.c_str());
@@ -320,6 +338,13 @@ int main(int argc, char **argv) {
     if (merge_ends != 0 && merge_ends != 1) { fprintf(stderr, "alga_hip: --merge_ends must be 0 or 1 (got %d)\n", merge_ends); return 2; }
     if (merge_ends && !grow_ends) { fprintf(stderr, "alga_hip: --merge_ends=1 needs --grow_ends >= 1\n"); return 2; }
     if (!merge_ends && (!merged_path.empty() || !merge_layout.empty())) { fprintf(stderr, "alga_hip: --merged= and --merge_layout= need --merge_ends=1\n"); return 2; }
+    if (stitch != 0 && stitch != 1) { fprintf(stderr, "alga_hip: --stitch must be 0 or 1 (got %d)\n", stitch); return 2; }
+    if (stitch && scaffolds.empty()) { fprintf(stderr, "alga_hip: --stitch=1 needs --scaffolds=\n"); return 2; }
+    if (!stitch && (!stitched_path.empty() || !stitch_layout.empty())) { fprintf(stderr, "alga_hip: --stitched= and --stitch_layout= need --stitch=1\n"); return 2; }
+    if (stp.min_overlap < 8 || stp.min_overlap > stp.max_overlap || stp.max_mismatches < 0 || stp.max_mismatches > 254 || stp.slack < 0 || stp.slack > (1 << 20)) {
+        fprintf(stderr, "alga_hip: --stitch_min_overlap must be in [8, 512], --stitch_max_mismatches in [0, 254], --stitch_slack in [0, 2^20]\n");
+        return 2;
+    }
     if (mgp.min_overlap < mgp.k || mgp.min_overlap > mgp.max_overlap || mgp.max_mismatches < 0 || mgp.max_mismatches > 254) {
         fprintf(stderr, "alga_hip: --merge_min_overlap must be in [21, 512], --merge_max_mismatches in [0, 254]\n");
         return 2;
@@ -928,6 +953,68 @@ int main(int argc, char **argv) {
                                         (long long) pi3.insert_median, pi3.ms_total);
                                 spl = &pl3; spi = &pi3; spol = nullptr;
                             }
+                        }
+                    }
+                    alga_placements pl4{};
+                    alga_place_info pi4{};
+                    if (rc == ALGA_OK && stitch) {                           // the joins of a first scaffolding whose two ends overlap become sequence, and the reads are placed on that
+                        const bool have = pr.paired && spi->insert_median >= 0;
+                        scp.insert = have ? (int32_t) spi->insert_median : 0;
+                        scp.max_insert = pp.max_insert;
+                        alga_scaffolds sc0;
+                        alga_stitched sd{};
+                        alga_stitch_info sti;
+                        rc = alga_scaffold_placed_device(engine, &pnd, have ? (const uint8_t *) d_po : nullptr, spl, &scp, nullptr, &sc0, nullptr);
+                        if (rc == ALGA_OK) rc = alga_stitch_scaffolds_device(engine, spl, &sc0, spol, &stp, nullptr, &sd, &sti);
+                        if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot stitch the scaffold joins: %s (status %d)\n", alga_last_error(engine), rc); return 1; }
+                        fprintf(stderr, "Scaffold joins stitched: %llu selected, %llu with an overlap, %llu ambiguous, %llu stitched, %llu bases removed, N50 %llu -> %llu; %llu "
+                                "entries, %llu candidates outside the slack, %llu stitches dropped for cycles, %llu mismatches in the stitches, longest overlap %llu, %llu contigs "
+                                "(%llu of several), %llu -> %llu columns; device ms: overlap %.3f build %.3f, call %.1f ms wall\n", (unsigned long long) sti.selected,
+                                (unsigned long long) sti.with_overlap, (unsigned long long) sti.ambiguous, (unsigned long long) sti.stitched, (unsigned long long) sti.bases_removed,
+                                (unsigned long long) sti.n50_before, (unsigned long long) sti.n50_after, (unsigned long long) sti.entries,
+                                (unsigned long long) sti.candidates_outside_slack, (unsigned long long) sti.dropped_cycle, (unsigned long long) sti.join_mismatches,
+                                (unsigned long long) sti.longest_overlap, (unsigned long long) sti.contigs, (unsigned long long) sti.contigs_multi,
+                                (unsigned long long) sti.columns_before, (unsigned long long) sti.columns_after, sti.ms_overlap, sti.ms_build, sti.ms_total);
+                        if (!stitched_path.empty()) {
+                            alga_gfa_info sgi;
+                            rc = alga_write_stitched_fasta_device(engine, &sd, stitched_path.c_str(), &sgi);
+                            if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", stitched_path.c_str(), alga_last_error(engine), rc); return 1; }
+                            fprintf(stderr, "Stitched contigs written -> %s: %llu records, %llu bytes\n", stitched_path.c_str(), (unsigned long long) sgi.segments,
+                                    (unsigned long long) sgi.bytes);
+                        }
+                        if (!stitch_layout.empty()) {                        // not a hot path: the host formats from the arrays that came back
+                            const size_t nt = (size_t) sd.n_targets, nj = (size_t) sd.n_stitched, nm = (size_t) sd.n_members, ne = (size_t) sd.n_entries;
+                            std::vector<uint32_t> s_off(nj + 1), start(nt), off(nt + 1);
+                            std::vector<int32_t> members(nm), rank(nt), ov(nt), entry(2 * nt);
+                            std::vector<uint8_t> orient(nt), mm(ne);
+                            rc = alga_copy_to_host(engine, s_off.data(), sd.d_s_off, (nj + 1) * sizeof(uint32_t));
+                            if (rc == ALGA_OK) rc = alga_copy_to_host(engine, off.data(), spl->d_col_off, (nt + 1) * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nm) rc = alga_copy_to_host(engine, members.data(), sd.d_s_members, nm * sizeof(int32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, rank.data(), sd.d_rank, nt * sizeof(int32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, ov.data(), sd.d_overlap_after, nt * sizeof(int32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, start.data(), sd.d_start, nt * sizeof(uint32_t));
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, orient.data(), sd.d_orient, nt);
+                            if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, entry.data(), sd.d_end_entry, 2 * nt * sizeof(int32_t));
+                            if (rc == ALGA_OK && ne) rc = alga_copy_to_host(engine, mm.data(), sd.d_j_mm, ne);
+                            FILE *f = rc == ALGA_OK ? fopen(stitch_layout.c_str(), "w") : nullptr;
+                            if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", stitch_layout.c_str()); return 1; }
+                            for (size_t j = 0; f && j < nj; j++)
+                                for (uint32_t k = s_off[j]; k < s_off[j + 1]; k++) {
+                                    const size_t c = (size_t) members[k];
+                                    fprintf(f, "%zu\t%d\t%zu\t%c\t%u\t%u\t%d\t%d\n", j, rank[c], c, orient[c] ? '-' : '+', start[c], off[c + 1] - off[c], ov[c],
+                                            ov[c] ? (int) mm[(size_t) entry[2 * c + (orient[c] ^ 1)]] : 0);
+                                }
+                            if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", stitch_layout.c_str()); return 1; }
+                        }
+                        // the same reads on the stitched contigs (the stitch result keeps its own copy of the bases)
+                        if (rc == ALGA_OK) rc = alga_place_reads_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, sd.d_words, sd.d_begin, sd.d_len,
+                                                                        (int32_t) sd.n_stitched, &pp, nullptr, &pl4, &pi4);
+                        if (rc == ALGA_OK) {
+                            fprintf(stderr, "Reads placed on the stitched contigs: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
+                                    "median insert %lld; call %.1f ms wall\n", (unsigned long long) pi4.reads, (unsigned long long) pi4.placed, (unsigned long long) pi4.unique,
+                                    (unsigned long long) pi4.multi, (unsigned long long) pi4.unplaced, (unsigned long long) pi4.pairs_proper, (unsigned long long) pi4.pairs,
+                                    (long long) pi4.insert_median, pi4.ms_total);
+                            spl = &pl4; spi = &pi4; spol = nullptr;
                         }
                     }
                     if (rc == ALGA_OK && !scaffolds.empty()) {

@@ -234,6 +234,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *   "grow_max_blocks"            1..8192 (default 8192): the largest grid of the kernels of alga_grow_placed_device, the placement of the overhanging
  *                                reads (its per-wave scratch follows the grid) and the write kernel of alga_write_grown_fasta_device included; what does
  *                                not fit is done by grid or wave stride (tests lower it to make small inputs stride)
+ *   "stitch_max_blocks"          1..8192 (default 8192): the largest grid of the kernels of alga_stitch_targets_device, k_st_overlap's (one wave per
+ *                                entry) included; what does not fit is done by grid stride (tests lower it to make small inputs stride)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
@@ -1706,6 +1708,104 @@ void alga_merge_default_params(alga_merge_params *p);
 int  alga_merge_targets_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
                                const alga_merge_params *p, void *hip_stream, alga_merged *out, alga_merge_info *info /* may be NULL */);
 int  alga_write_merged_fasta_device(alga_engine *e, const alga_merged *merged, const char *path, alga_gfa_info *info /* may be NULL */);
+
+/* ---- scaffold joins whose contig ends overlap stitched into one sequence (alga_amd/csrc/stitch_kernels.hip, engine_stitch.hip) ---------------
+ * The scaffolder bridges two contigs with max(gap, min_gap) Ns, also where the gap estimate is negative and the two ends share bases.  The
+ * merge stage in front of it compares all ends at once through a seed index, so it refuses an overlap under k * (max_mismatches + 1) bases, an
+ * end with two overlaps and an overlap with more than one mismatch.  After the scaffolder the mates have made that choice: a bundle with state
+ * JOIN names exactly two ends and a gap.  Here those two ends alone are compared, at every overlap length, with no index and no seed
+ * condition; the entries with exactly one admissible overlap are stitched, and everything behind that decision (cycles, ranking, layout, the
+ * bases, FASTA) is the merge stage's.  No reads, no voting, nothing of the engine's state but the stage's own result.  Integers only, free
+ * of any order (thread, atomics); tests/stitch_checker.py states the rule twice in Python and the device result equals it array for array.
+ * ... -> place -> scaffold -> stitch -> place on the stitched contigs -> scaffold; a further round is a further call.
+ *
+ * Inputs: a ragged target set as alga_place_reads_device takes it (d_words, d_begin uint64 base index, d_len int32, n_targets = T); an entry
+ * list of J entries: d_j_a, d_j_b (uint32 ends, x = 2t left, 2t + 1 right), d_j_gap (int32), d_j_state (uint8, may be NULL) -- exactly
+ * alga_scaffolds.d_b_a / d_b_b / d_b_gap / d_b_state / n_bundles; and alga_stitch_params: max_mismatches 0 .. 254 (default 2), min_overlap
+ * 8 .. max_overlap (16: with at most 2 mismatches a random pair of 16-mers matches with probability (1 + 48 + 1080) / 4^16 = 2.6e-7 per overlap
+ * length, and the sum over the longer lengths is dominated by that term), max_overlap min_overlap .. 4096 (512), slack 0 .. 2^20 (2^20: excludes
+ * nothing in practice), flags 0, reserved 0; anything else answers ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Selected entries.  Entry j is SELECTED iff d_j_state is NULL, or state & ALGA_SCAFFOLD_BUNDLE_JOIN and not state &
+ *      ALGA_SCAFFOLD_BUNDLE_DROPPED_CYCLE.  Nothing of an unselected entry is read or checked.
+ *   2. Refusals, all decided on the device before anything of the result is written, with one read-back, ALGA_ERR_INVALID_ARGUMENT: a
+ *      negative target length; a selected entry with a >= 2T or b >= 2T, or with a >> 1 == b >> 1; an end named by more than one selected
+ *      entry.  ALGA_ERR_CAPACITY as in merge: a column sum above 2^32 - 2, more than 2^30 targets, a stitched length above 2^31 - 1; also
+ *      J > 2^31 - 1.
+ *   3. Ends.  Target t of n bases has two ends, x = 2t (left) and x = 2t + 1 (right); W_x = min(n >> 1, max_overlap).  E_{2t+1} is the last
+ *      W_x bases of t, E_{2t} the reverse complement of the first W_x bases: in both the contig end is at the right.  P_x is the reverse
+ *      complement of E_x: the first W_x bases read inward from end x.  (Item 1 of the merge definition.)
+ *   4. Overlaps of a selected entry (a, b, gap).  o is a CANDIDATE iff min_overlap <= o <= min(W_a, W_b) and mm(o) <= max_mismatches, mm(o) the
+ *      Hamming distance between P_a[0 .. o) and the last o bases of E_b; mm is the same with a and b exchanged.  No seed condition, no index:
+ *      every o is compared.  A candidate is ADMISSIBLE iff |gap + o| <= slack, in 64-bit arithmetic.  hits = the number of admissible
+ *      candidates, saturated at 255; best = the smallest (mm, o descending) among them.  Per entry: d_j_olen = best.o (0 without), d_j_mm,
+ *      d_j_hits, d_j_state: ALGA_STITCH_SELECTED, ALGA_STITCH_HAS_OVERLAP, ALGA_STITCH_AMBIGUOUS (hits > 1), ALGA_STITCH_STITCHED,
+ *      ALGA_STITCH_DROPPED_CYCLE.  Unselected entries are all 0.
+ *   5. Stitches.  A selected entry is STITCHED iff hits == 1.  A second admissible overlap length (a periodic end) stops it; a smaller slack
+ *      is the caller's way to decide such an end.
+ *   6. Cycles, paths, orientation, numbering, layout, bases: items 6, 7 and 8 of the merge definition with "join" read as "stitched entry".
+ *      A raw entry list may hold a ring (the scaffolder's own joins cannot: it drops them).  A cycle is opened at its smallest contig id c:
+ *      the stitch at end 2c is dropped, its entry gets DROPPED_CYCLE and loses STITCHED.  The overlapped bases are the earlier contig's.
+ *   7. Result (alga_stitched; engine-owned, valid until the next stitch call on `e`: no other call invalidates it; kept twice and swapped at
+ *      the end of a call, so a refused or failed call leaves the earlier result valid and a call may take its targets from the previous
+ *      result).  Per entry (J): d_j_olen, d_j_mm, d_j_hits, d_j_state.  Per end (2T): d_end_entry, the selected entry that names the end, -1
+ *      without.  Per target (T): d_stitched, d_rank, d_orient, d_start, d_overlap_after.  d_s_off [n_stitched + 1] and d_s_members
+ *      [n_members].  d_len [n_stitched], d_col_off [n_stitched + 1], d_begin [n_stitched] (= col_off), d_words: the result's OWN copy in column
+ *      space (the polish's layout, (n_columns + 15) / 16 + 2 words, the bits past n_columns zero).  (d_words, d_begin, d_len, n_stitched) is a
+ *      target set as the placement and the merge take it.
+ *   8. Counters (alga_stitch_info): entries, selected, with_overlap, ambiguous, hits_saturated, candidates_outside_slack (the (j, o) that are
+ *      candidates but not admissible), stitched (the kept ones), dropped_cycle, join_mismatches, bases_removed, longest_overlap (over the kept
+ *      ones); contigs, contigs_multi, longest, columns_before, columns_after; n50_before, n50_after (on the host from lengths read back only
+ *      when `info` is given); ms_overlap (k_st_overlap), ms_build (joins, cycles, ranks, layout, scan, build) (HIP events), ms_total (wall).
+ * Read-backs: the refusal flags with the column sum; the stitched contigs, members and columns (d_words is allocated at its size); the lengths
+ * for the N50s.
+ *
+ * alga_stitch_scaffolds_device: the same on the engine's current placement and scaffold result.  The bases come from where
+ * alga_write_scaffold_fasta_device takes them (the column array the placement kept, or pol->d_words), begin = col_off, the lengths from
+ * col_off, the entries are the scaffold result's bundles; it refuses exactly what alga_write_scaffold_fasta_device refuses.
+ * alga_write_stitched_fasta_device: one record per stitched contig, in id order, `>contig_id=<j>_length=<len>_contigs=<m>`.  `stitched` must be
+ * the engine's current stitch result.  ABI stays 7: the calls add. */
+#define ALGA_STITCH_SELECTED      1    /* bits of d_j_state                                                                           */
+#define ALGA_STITCH_HAS_OVERLAP   2
+#define ALGA_STITCH_AMBIGUOUS     4
+#define ALGA_STITCH_STITCHED      8
+#define ALGA_STITCH_DROPPED_CYCLE 16
+typedef struct {
+    int32_t max_mismatches, min_overlap, max_overlap, slack, flags;
+    int32_t reserved[3];             /* 0                                                                                             */
+} alga_stitch_params;
+typedef struct {
+    int64_t         n_targets, n_entries, n_stitched, n_members;
+    uint64_t        n_columns;       /* of the stitched contigs: d_col_off[n_stitched]                                                */
+    const int32_t  *d_j_olen;        /* n_entries                                                                                     */
+    const uint8_t  *d_j_mm, *d_j_hits, *d_j_state;
+    const int32_t  *d_end_entry;     /* 2 * n_targets                                                                                 */
+    const int32_t  *d_stitched, *d_rank;  /* n_targets                                                                                */
+    const uint8_t  *d_orient;
+    const uint32_t *d_start;
+    const int32_t  *d_overlap_after;
+    const uint32_t *d_s_off;         /* n_stitched + 1                                                                                */
+    const int32_t  *d_s_members;     /* n_members                                                                                     */
+    const int32_t  *d_len;           /* n_stitched                                                                                    */
+    const uint32_t *d_col_off;       /* n_stitched + 1                                                                                */
+    const uint64_t *d_begin;         /* n_stitched                                                                                    */
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+} alga_stitched;
+typedef struct {
+    uint64_t entries, selected, with_overlap, ambiguous, hits_saturated, candidates_outside_slack, stitched, dropped_cycle, join_mismatches,
+             bases_removed, longest_overlap, contigs, contigs_multi, longest, columns_before, columns_after;
+    uint64_t n50_before, n50_after;
+    double   ms_overlap, ms_build;   /* device time (HIP events)                                                                      */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_stitch_info;
+void alga_stitch_default_params(alga_stitch_params *p);
+int  alga_stitch_targets_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
+                                const uint32_t *d_j_a, const uint32_t *d_j_b, const int32_t *d_j_gap, const uint8_t *d_j_state /* may be NULL */,
+                                int64_t n_entries, const alga_stitch_params *p, void *hip_stream, alga_stitched *out,
+                                alga_stitch_info *info /* may be NULL */);
+int  alga_stitch_scaffolds_device(alga_engine *e, const alga_placements *pl, const alga_scaffolds *scaf, const alga_polished *pol /* may be NULL */,
+                                  const alga_stitch_params *p, void *hip_stream, alga_stitched *out, alga_stitch_info *info /* may be NULL */);
+int  alga_write_stitched_fasta_device(alga_engine *e, const alga_stitched *stitched, const char *path, alga_gfa_info *info /* may be NULL */);
 
 /* ---- gapped placement: the unplaced reads laid with indels, CIGARs (alga_amd/csrc/gapped_kernels.hip, engine_gapped.hip) -----------------
  * alga_place_reads_device verifies by Hamming distance, so a read with one inserted or deleted base is unplaced.  This second pass lays the
