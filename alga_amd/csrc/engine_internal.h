@@ -203,11 +203,14 @@ struct alga_engine {
     uint64_t    po_final_epoch = 0;                // ... of a placement on the final result of this epoch (0: on caller's targets)
     alga_polished po_out{};                        // ... the handle that was handed out for it (alga_polished_is_current)
     uint64_t    pl_serial = 0, po_pl_serial = 0;   // counts the placement results written; the one the polish at hand was made from
+    // the chain workspace of the call at hand (chain_kernels.hip: alga_chain_work carves it for the scaffolder, the merge and the stitch stage): the
+    // two sets of lists over the 2T states, the join of every end, head / first / members and their scans.  Nothing in it outlives a call and no
+    // result handle points into it; a stage call ends with the wait for its stream (AlgaStageCall), so the stages take it in turn
+    DevBuf      chain_work;
     // scaffolds from split pairs (engine_scaffold.hip).  Workspaces: counters, the link keys / judging reads before and after the sort, the spans,
-    // the heads and their scan, the first link of every bundle, best / second / choice / partner / join bundle per end, the two sets of list
-    // records, head / first / members per contig and their scans.  The result: the bundle arrays, the end states, the per-contig and
-    // per-scaffold arrays
-    DevBuf      sc_cnt, sc_keys[2], sc_vals[2], sc_span, sc_heads, sc_pos, sc_bstart, sc_best, sc_choice, sc_partner, sc_lists[2], sc_head, sc_first, sc_scan;
+    // the heads and their scan, the first link of every bundle, best / second / choice / partner / join bundle per end.  The result: the bundle
+    // arrays, the end states, the per-contig and per-scaffold arrays
+    DevBuf      sc_cnt, sc_keys[2], sc_vals[2], sc_span, sc_heads, sc_pos, sc_bstart, sc_best, sc_choice, sc_partner;
     DevBuf      sc_ba, sc_bb, sc_blinks, sc_bspan, sc_bgap, sc_bstate, sc_estate, sc_scaffold, sc_rank, sc_orient, sc_start, sc_gapafter, sc_jlinks, sc_soff,
                 sc_smembers, sc_slen;
     int         opt_scaffold_max_blocks = 8192;    // option "scaffold_max_blocks": the cap of the k_sc_* grids (tests make every grid-stride loop take further passes)
@@ -231,18 +234,16 @@ struct alga_engine {
     bool        gr_valid = false;
     uint64_t    gr_reads = 0, gr_targets = 0, gr_columns = 0, gr_longest = 0;   // ... of this many reads, targets and columns; the longest grown target
     // contigs whose ends overlap merged into one sequence (engine_merge.hip).  Workspaces: counters, the end lengths, their padded lengths and
-    // the scan, the end sequences and their reverse complements, the join of every end, the lists over the 2T states (twice), head / first /
-    // members and their scans.  The result, twice, as for the grow
-    DevBuf      mg_cnt, mg_elen, mg_epad, mg_eoff, mg_ecols, mg_pcols, mg_join, mg_lists[2], mg_head, mg_first, mg_scan;
+    // the scan, the end sequences and their reverse complements.  The result, twice, as for the grow
+    DevBuf      mg_cnt, mg_elen, mg_epad, mg_eoff, mg_ecols, mg_pcols;
     struct MergeSet { DevBuf partner, olen, mm, hits, estate, merged, rank, orient, start, ovafter, moff, mmembers, len, coloff, begin, words; } mg_set[2];
     int         mg_cur = 0;                        // the set that holds the result
     int         opt_merge_max_blocks = 8192;       // option "merge_max_blocks": the cap of the k_mg_* grids (tests make every grid-stride loop take further passes)
     bool        mg_valid = false;
     uint64_t    mg_targets = 0, mg_merged = 0, mg_columns = 0, mg_longest = 0;   // ... of this many targets, merged contigs and columns; the longest merged contig
     // scaffold joins whose contig ends overlap stitched into one sequence (engine_stitch.hip).  Workspaces of its own: counters, the per-end
-    // count, the per-end arrays the merge stage's launchers take (partner, olen, mm, hits, state), begin / len of a placement's targets; the
-    // join of every end, the lists, head / first / members and their scans are the merge stage's workspaces (mg_join, mg_lists, mg_head,
-    // mg_first, mg_scan: nothing in them outlives a call).  The result, twice, as for the grow
+    // count, the per-end arrays the merge stage's launchers take (partner, olen, mm, hits, state), begin / len of a placement's targets.  The
+    // result, twice, as for the grow
     DevBuf      st_cnt, st_endcnt, st_epartner, st_eolen, st_emm, st_ehits, st_estate, st_tbegin, st_tlen;
     struct StitchSet { DevBuf jolen, jmm, jhits, jstate, endentry, stitched, rank, orient, start, ovafter, soff, smembers, len, coloff, begin, words; } st_set[2];
     int         st_cur = 0;                        // the set that holds the result

@@ -22,6 +22,40 @@
 
 using namespace alga;
 
+int alga_merge_tail(alga_engine *e, const MgTargets &tg, const MgEndOut &eo, const ChainWork &w, const MgLayout &lo, uint32_t *col_off, DevBuf &words, unsigned long long *begin,
+                    unsigned long long *cnt, size_t n_counters, const char *stage, const char *noun, const std::function<int()> &after_drop, hipStream_t s) {
+    const uint64_t T = tg.T, E = 2 * T;
+    const std::string nn(noun);
+    unsigned long long *hc = e->h_counters;
+    int rc;
+    // the joins into paths (the chain core, chain_kernels.h)
+    const ChainLists *l;
+    if ((rc = alga_chain_cycles(e, w, w.join, E, true, tg.max_blocks, s, &l))) return rc;
+    launch_mg_cycle_drop(*l, (uint32_t) T, w.join, eo.state, cnt, tg.max_blocks, s);
+    if ((rc = alga_check_launch(e, "k_mg_cycle_drop"))) return rc;
+    if (after_drop && (rc = after_drop())) return rc;
+    launch_mg_rank_init(tg, w.join, eo.olen, w.set[0], s);
+    if ((rc = alga_chain_ranks(e, w, E, true, tg.max_blocks, s, &l))) return rc;
+
+    HIP_TRY(e, hipMemsetAsync(lo.m_len, 0, (T + 2) * sizeof(int32_t), s));
+    HIP_TRY(e, hipMemsetAsync(col_off, 0, (T + 2) * sizeof(uint32_t), s));
+    launch_mg_place(tg, *l, w.join, eo, lo, w.head, w.first, w.members, cnt, s);
+    if ((rc = alga_check_launch(e, "k_mg_place"))) return rc;
+    if ((rc = alga_chain_scans(e, w, T, ("scan(" + nn + " contigs)").c_str(), s))) return rc;
+    launch_mg_layout(tg, *l, w.head, w.first_scan, w.members_scan, lo, cnt, s);
+    if ((rc = alga_check_launch(e, "k_mg_layout"))) return rc;
+    HIP_TRY(e, hipMemcpyAsync(hc, cnt, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (hc[MG_BAD_MERGED_LEN]) return alga_fail(e, ALGA_ERR_CAPACITY, (std::string(stage) + ": a " + nn + " contig is longer than 2^31 - 1").c_str());
+    const uint64_t NM = hc[MG_MERGED], NC = hc[MG_COLUMNS_AFTER];
+    const size_t new_words = (size_t) ((NC + 15) >> 4) + 2;
+    if ((rc = alga_ensure(e, words, new_words * sizeof(uint32_t)))) return rc;
+    if (NM) launch_exclusive_scan((const uint32_t *) lo.m_len, NM + 1, col_off, (uint64_t *) e->scan_scratch.p, s);
+    if ((rc = alga_check_launch(e, ("scan(" + nn + " lengths)").c_str()))) return rc;
+    launch_mg_build(tg, lo, col_off, (uint32_t) NM, NC, (uint32_t *) words.p, begin, s);
+    return alga_check_launch(e, "k_mg_build");
+}
+
 namespace {
 
 int check_params(alga_engine *e, const alga_merge_params *p) {
@@ -95,61 +129,20 @@ int merge_impl(alga_engine *e, const uint32_t *d_words, const unsigned long long
     for (DevBuf *b : {&rs.merged, &rs.rank, &rs.start, &rs.ovafter, &rs.moff, &rs.mmembers, &rs.len, &rs.coloff}) if ((rc = alga_ensure(e, *b, (T + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, rs.orient, T + 16))) return rc;
     if ((rc = alga_ensure(e, rs.begin, (T + 2) * sizeof(unsigned long long)))) return rc;
-    if ((rc = alga_ensure(e, e->mg_join, (E + 2) * sizeof(uint32_t)))) return rc;
-    for (int j = 0; j < 2; j++) if ((rc = alga_ensure(e, e->mg_lists[j], (E + 2) * (sizeof(unsigned long long) + 3 * sizeof(uint32_t))))) return rc;
-    if ((rc = alga_ensure(e, e->mg_head, (T + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->mg_first, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                    // first, members
-    if ((rc = alga_ensure(e, e->mg_scan, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                     // their scans
+    ChainWork w;
+    if ((rc = alga_chain_work(e, T, &w))) return rc;
     const MgEndOut eo{(int32_t *) rs.partner.p, (int32_t *) rs.olen.p, (uint8_t *) rs.mm.p, (uint8_t *) rs.hits.p, (uint8_t *) rs.estate.p};
-    uint32_t *join = (uint32_t *) e->mg_join.p, *col_off = (uint32_t *) rs.coloff.p;
+    uint32_t *col_off = (uint32_t *) rs.coloff.p;
     launch_mg_overlap(en, ix, p->k, p->max_mismatches, p->max_occ, p->min_overlap, eo, seed_blocks(E, e->n_cu), cnt, s);
     if ((rc = alga_check_launch(e, "k_mg_overlap"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
 
-    launch_mg_joins(eo, (uint32_t) E, join, tg.max_blocks, s);
+    launch_mg_joins(eo, (uint32_t) E, w.join, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_mg_joins"))) return rc;
-    // the lists over the 2T states: after this many doublings a jump is longer than any path
-    int rounds = 1;
-    while (rounds < 33 && (1ull << rounds) < E) rounds++;                     // ceil(log2(2T)) ...
-    rounds += 1;                                                              // ... + 1
-    MgLists set[2];
-    for (int j = 0; j < 2; j++) {
-        set[j].wsum = (unsigned long long *) e->mg_lists[j].p;
-        set[j].nxt = (uint32_t *) (set[j].wsum + E + 2); set[j].aux = set[j].nxt + E; set[j].tail = set[j].aux + E;
-    }
-    int cur = 0;
-    launch_mg_cycle_init(join, (uint32_t) E, set[0], tg.max_blocks, s);
-    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_cycle_jump((uint32_t) E, set[cur], set[cur ^ 1], tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_mg_cycle_jump"))) return rc;
-    launch_mg_cycle_drop(set[cur], (uint32_t) T, join, eo.state, cnt, tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_mg_cycle_drop"))) return rc;
-    cur = 0;
-    launch_mg_rank_init(tg, join, eo.olen, set[0], s);
-    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_rank_jump((uint32_t) E, set[cur], set[cur ^ 1], tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_mg_rank_jump"))) return rc;
-
-    uint32_t *first = (uint32_t *) e->mg_first.p, *members = first + T + 2, *first_scan = (uint32_t *) e->mg_scan.p, *members_scan = first_scan + T + 2;
     const MgLayout lo{(int32_t *) rs.merged.p, (int32_t *) rs.rank.p, (uint8_t *) rs.orient.p, (uint32_t *) rs.start.p, (int32_t *) rs.ovafter.p, (uint32_t *) rs.moff.p,
                       (int32_t *) rs.mmembers.p, (int32_t *) rs.len.p};
-    HIP_TRY(e, hipMemsetAsync(lo.m_len, 0, (T + 2) * sizeof(int32_t), s));
-    HIP_TRY(e, hipMemsetAsync(col_off, 0, (T + 2) * sizeof(uint32_t), s));
-    launch_mg_place(tg, set[cur], join, eo, lo, (uint32_t *) e->mg_head.p, first, members, cnt, s);
-    if ((rc = alga_check_launch(e, "k_mg_place"))) return rc;
-    launch_exclusive_scan(first, T + 1, first_scan, (uint64_t *) e->scan_scratch.p, s);
-    launch_exclusive_scan(members, T + 1, members_scan, (uint64_t *) e->scan_scratch.p, s);
-    if ((rc = alga_check_launch(e, "scan(merged contigs)"))) return rc;
-    launch_mg_layout(tg, set[cur], (const uint32_t *) e->mg_head.p, first_scan, members_scan, lo, cnt, s);
-    if ((rc = alga_check_launch(e, "k_mg_layout"))) return rc;
-    HIP_TRY(e, hipMemcpyAsync(hc, cnt, MG_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    if (hc[MG_BAD_MERGED_LEN]) return alga_fail(e, ALGA_ERR_CAPACITY, "merge: a merged contig is longer than 2^31 - 1");
+    if ((rc = alga_merge_tail(e, tg, eo, w, lo, col_off, rs.words, (unsigned long long *) rs.begin.p, cnt, MG_COUNTERS, "merge", "merged", nullptr, s))) return rc;
     const uint64_t NM = hc[MG_MERGED], NC = hc[MG_COLUMNS_AFTER];
-    const size_t new_words = (size_t) ((NC + 15) >> 4) + 2;
-    if ((rc = alga_ensure(e, rs.words, new_words * sizeof(uint32_t)))) return rc;
-    if (NM) launch_exclusive_scan((const uint32_t *) lo.m_len, NM + 1, col_off, (uint64_t *) e->scan_scratch.p, s);
-    if ((rc = alga_check_launch(e, "scan(merged lengths)"))) return rc;
-    launch_mg_build(tg, lo, col_off, (uint32_t) NM, NC, (uint32_t *) rs.words.p, (unsigned long long *) rs.begin.p, s);
-    if ((rc = alga_check_launch(e, "k_mg_build"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[3], s));
     HIP_TRY(e, hipStreamSynchronize(s));
 

@@ -103,7 +103,8 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
     if ((rc = alga_ensure(e, e->sc_choice, (n_ends + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, e->sc_partner, (2 * n_ends + 2) * sizeof(uint32_t)))) return rc;              // partner, join bundle
     if ((rc = alga_ensure(e, e->sc_estate, n_ends + 16))) return rc;
-    for (int j = 0; j < 2; j++) if ((rc = alga_ensure(e, e->sc_lists[j], (n_ends + 2) * (sizeof(unsigned long long) + 3 * sizeof(uint32_t))))) return rc;
+    ChainWork w;
+    if ((rc = alga_chain_work(e, T, &w))) return rc;
     unsigned long long *best = (unsigned long long *) e->sc_best.p, *second = best + n_ends;
     uint32_t *choice = (uint32_t *) e->sc_choice.p, *partner = (uint32_t *) e->sc_partner.p, *join_bundle = partner + n_ends;
     const ScBundles bd{n_bundles, (uint32_t *) e->sc_ba.p, (uint32_t *) e->sc_bb.p, (uint32_t *) e->sc_blinks.p, (const unsigned long long *) e->sc_bspan.p,
@@ -128,45 +129,26 @@ int scaffold_impl(alga_engine *e, const alga_nodes *nodes, const uint8_t *d_pair
     launch_sc_joins(bd, choice, partner, join_bundle, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_joins"))) return rc;
 
-    // the lists over the 2T states: after this many doublings a jump is longer than any path
-    int rounds = 1;
-    while (rounds < 33 && (1ull << rounds) < n_ends) rounds++;               // ceil(log2(2T)) ...
-    rounds += 1;                                                              // ... + 1
-    ScLists set[2];
-    for (int j = 0; j < 2; j++) {
-        set[j].wsum = (unsigned long long *) e->sc_lists[j].p;
-        set[j].nxt = (uint32_t *) (set[j].wsum + n_ends + 2); set[j].aux = set[j].nxt + n_ends; set[j].tail = set[j].aux + n_ends;
-    }
-    int cur = 0;
-    if (n_bundles && T) {                                                     // without a bundle there is no join and no cycle
-        launch_sc_cycle_init(partner, n_ends, set[0], mb, s);
-        for (int k = 0; k < rounds; k++, cur ^= 1) launch_sc_cycle_jump(n_ends, set[cur], set[cur ^ 1], mb, s);
-        if ((rc = alga_check_launch(e, "k_sc_cycle_jump"))) return rc;
-        launch_sc_cycle_drop(set[cur], (uint32_t) T, partner, join_bundle, bd.state, cnt, mb, s);
-        if ((rc = alga_check_launch(e, "k_sc_cycle_drop"))) return rc;
-    }
-    cur = 0;
-    launch_sc_rank_init(tg, partner, join_bundle, bd.gap, p->min_gap, set[0], mb, s);
-    if (n_bundles) for (int k = 0; k < rounds; k++, cur ^= 1) launch_sc_rank_jump(n_ends, set[cur], set[cur ^ 1], mb, s);
-    if ((rc = alga_check_launch(e, "k_sc_rank_jump"))) return rc;
+    // the joins into paths (the chain core, chain_kernels.h)
+    const bool may_join = n_bundles && T;                                     // without a bundle there is no join: no cycle, and every path is one contig
+    const ChainLists *l;
+    if ((rc = alga_chain_cycles(e, w, partner, n_ends, may_join, mb, s, &l))) return rc;
+    if (l) launch_sc_cycle_drop(*l, (uint32_t) T, partner, join_bundle, bd.state, cnt, mb, s);
+    if ((rc = alga_check_launch(e, "k_sc_cycle_drop"))) return rc;
+    launch_sc_rank_init(tg, partner, join_bundle, bd.gap, p->min_gap, w.set[0], mb, s);
+    if ((rc = alga_chain_ranks(e, w, n_ends, may_join, mb, s, &l))) return rc;
 
     // the per-contig and per-scaffold arrays
-    for (DevBuf *b : {&e->sc_scaffold, &e->sc_rank, &e->sc_gapafter, &e->sc_jlinks, &e->sc_smembers, &e->sc_head}) if ((rc = alga_ensure(e, *b, (T + 2) * sizeof(uint32_t)))) return rc;
+    for (DevBuf *b : {&e->sc_scaffold, &e->sc_rank, &e->sc_gapafter, &e->sc_jlinks, &e->sc_smembers}) if ((rc = alga_ensure(e, *b, (T + 2) * sizeof(uint32_t)))) return rc;
     for (DevBuf *b : {&e->sc_start, &e->sc_slen}) if ((rc = alga_ensure(e, *b, (T + 2) * sizeof(unsigned long long)))) return rc;
     if ((rc = alga_ensure(e, e->sc_orient, T + 16))) return rc;
     if ((rc = alga_ensure(e, e->sc_soff, (T + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->sc_first, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                    // first, members
-    if ((rc = alga_ensure(e, e->sc_scan, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                     // their scans
-    if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(T + 2)))) return rc;
-    uint32_t *first = (uint32_t *) e->sc_first.p, *members = first + T + 2, *first_scan = (uint32_t *) e->sc_scan.p, *members_scan = first_scan + T + 2;
     const ScLayout lo{(int32_t *) e->sc_scaffold.p, (int32_t *) e->sc_rank.p, (uint8_t *) e->sc_orient.p, (unsigned long long *) e->sc_start.p, (int32_t *) e->sc_gapafter.p,
                       (uint32_t *) e->sc_jlinks.p, (uint32_t *) e->sc_soff.p, (int32_t *) e->sc_smembers.p, (unsigned long long *) e->sc_slen.p, (uint8_t *) e->sc_estate.p};
-    launch_sc_place(tg, set[cur], partner, join_bundle, bd.gap, bd.links, p->min_gap, lo, (uint32_t *) e->sc_head.p, first, members, cnt, mb, s);
+    launch_sc_place(tg, *l, partner, join_bundle, bd.gap, bd.links, p->min_gap, lo, w.head, w.first, w.members, cnt, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_place"))) return rc;
-    launch_exclusive_scan(first, T + 1, first_scan, (uint64_t *) e->scan_scratch.p, s);
-    launch_exclusive_scan(members, T + 1, members_scan, (uint64_t *) e->scan_scratch.p, s);
-    if ((rc = alga_check_launch(e, "scan(scaffolds)"))) return rc;
-    launch_sc_layout(tg, set[cur], (const uint32_t *) e->sc_head.p, first_scan, members_scan, lo, cnt, mb, s);
+    if ((rc = alga_chain_scans(e, w, T, "scan(scaffolds)", s))) return rc;
+    launch_sc_layout(tg, *l, w.head, w.first_scan, w.members_scan, lo, cnt, mb, s);
     if ((rc = alga_check_launch(e, "k_sc_layout"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
     HIP_TRY(e, hipMemcpyAsync(hc, cnt, SC_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

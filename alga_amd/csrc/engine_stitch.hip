@@ -3,7 +3,7 @@
 //
 // Host side: the checks (the merge stage's over the lengths, k_st_check over the selected entries) run on workspaces and on the set of result
 // buffers that does NOT hold the current result, and end in one read-back (the refusal flags, the column sum).  Then k_st_overlap, the joins,
-// and the merge stage's launchers as they are: cycles, ranks, places, layout; a read-back of the counters (the stitched contigs, their
+// and the merge stage's path as it is (alga_merge_tail): cycles, ranks, places, layout; a read-back of the counters (the stitched contigs, their
 // members and columns size what follows, and the longest stitched contig is the last refusal); the scan and the build.  The sets are swapped at
 // the end, so a call that is refused or fails anywhere leaves an earlier result as it was, and a call may take its targets from that result.
 // The lengths for the N50s come back only when `info` is given.  No step walks on the host.
@@ -74,66 +74,24 @@ int stitch_impl(alga_engine *e, const uint32_t *d_words, const unsigned long lon
     for (DevBuf *b : {&rs.stitched, &rs.rank, &rs.start, &rs.ovafter, &rs.soff, &rs.smembers, &rs.len, &rs.coloff}) if ((rc = alga_ensure(e, *b, (T + 2) * sizeof(uint32_t)))) return rc;
     if ((rc = alga_ensure(e, rs.orient, T + 16))) return rc;
     if ((rc = alga_ensure(e, rs.begin, (T + 2) * sizeof(unsigned long long)))) return rc;
-    if ((rc = alga_ensure(e, e->mg_join, (E + 2) * sizeof(uint32_t)))) return rc;
-    for (int j = 0; j < 2; j++) if ((rc = alga_ensure(e, e->mg_lists[j], (E + 2) * (sizeof(unsigned long long) + 3 * sizeof(uint32_t))))) return rc;
-    if ((rc = alga_ensure(e, e->mg_head, (T + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = alga_ensure(e, e->mg_first, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                    // first, members
-    if ((rc = alga_ensure(e, e->mg_scan, 2 * (T + 2) * sizeof(uint32_t)))) return rc;                     // their scans
-    if ((rc = alga_ensure(e, e->scan_scratch, scan_scratch_bytes(T + 2)))) return rc;
+    ChainWork w;
+    if ((rc = alga_chain_work(e, T, &w))) return rc;
     const StEntryOut jo{(int32_t *) rs.jolen.p, (uint8_t *) rs.jmm.p, (uint8_t *) rs.jhits.p, (uint8_t *) rs.jstate.p};
     const MgEndOut eo{(int32_t *) e->st_epartner.p, (int32_t *) e->st_eolen.p, (uint8_t *) e->st_emm.p, (uint8_t *) e->st_ehits.p, (uint8_t *) e->st_estate.p};
-    uint32_t *join = (uint32_t *) e->mg_join.p, *col_off = (uint32_t *) rs.coloff.p;
+    uint32_t *col_off = (uint32_t *) rs.coloff.p;
     HIP_TRY(e, hipEventRecord(evs.ev[0], s));
     launch_st_overlap(tg, en, StParams{p->max_mismatches, p->min_overlap, p->max_overlap, p->slack}, jo, cnt, s);
     if ((rc = alga_check_launch(e, "k_st_overlap"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[1], s));
 
-    launch_st_joins(en, jo, end_entry, (uint32_t) E, eo, join, tg.max_blocks, s);
+    launch_st_joins(en, jo, end_entry, (uint32_t) E, eo, w.join, tg.max_blocks, s);
     if ((rc = alga_check_launch(e, "k_st_joins"))) return rc;
-    // the lists over the 2T states: after this many doublings a jump is longer than any path
-    int rounds = 1;
-    while (rounds < 33 && (1ull << rounds) < E) rounds++;                     // ceil(log2(2T)) ...
-    rounds += 1;                                                              // ... + 1
-    MgLists set[2];
-    for (int j = 0; j < 2; j++) {
-        set[j].wsum = (unsigned long long *) e->mg_lists[j].p;
-        set[j].nxt = (uint32_t *) (set[j].wsum + E + 2); set[j].aux = set[j].nxt + E; set[j].tail = set[j].aux + E;
-    }
-    int cur = 0;
-    launch_mg_cycle_init(join, (uint32_t) E, set[0], tg.max_blocks, s);
-    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_cycle_jump((uint32_t) E, set[cur], set[cur ^ 1], tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_mg_cycle_jump"))) return rc;
-    launch_mg_cycle_drop(set[cur], (uint32_t) T, join, eo.state, cnt, tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_mg_cycle_drop"))) return rc;
-    launch_st_dropped(en, join, jo.state, tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_st_dropped"))) return rc;
-    cur = 0;
-    launch_mg_rank_init(tg, join, eo.olen, set[0], s);
-    for (int k = 0; k < rounds; k++, cur ^= 1) launch_mg_rank_jump((uint32_t) E, set[cur], set[cur ^ 1], tg.max_blocks, s);
-    if ((rc = alga_check_launch(e, "k_mg_rank_jump"))) return rc;
-
-    uint32_t *first = (uint32_t *) e->mg_first.p, *members = first + T + 2, *first_scan = (uint32_t *) e->mg_scan.p, *members_scan = first_scan + T + 2;
     const MgLayout lo{(int32_t *) rs.stitched.p, (int32_t *) rs.rank.p, (uint8_t *) rs.orient.p, (uint32_t *) rs.start.p, (int32_t *) rs.ovafter.p, (uint32_t *) rs.soff.p,
                       (int32_t *) rs.smembers.p, (int32_t *) rs.len.p};
-    HIP_TRY(e, hipMemsetAsync(lo.m_len, 0, (T + 2) * sizeof(int32_t), s));
-    HIP_TRY(e, hipMemsetAsync(col_off, 0, (T + 2) * sizeof(uint32_t), s));
-    launch_mg_place(tg, set[cur], join, eo, lo, (uint32_t *) e->mg_head.p, first, members, cnt, s);
-    if ((rc = alga_check_launch(e, "k_mg_place"))) return rc;
-    launch_exclusive_scan(first, T + 1, first_scan, (uint64_t *) e->scan_scratch.p, s);
-    launch_exclusive_scan(members, T + 1, members_scan, (uint64_t *) e->scan_scratch.p, s);
-    if ((rc = alga_check_launch(e, "scan(stitched contigs)"))) return rc;
-    launch_mg_layout(tg, set[cur], (const uint32_t *) e->mg_head.p, first_scan, members_scan, lo, cnt, s);
-    if ((rc = alga_check_launch(e, "k_mg_layout"))) return rc;
-    HIP_TRY(e, hipMemcpyAsync(hc, cnt, ST_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipStreamSynchronize(s));
-    if (hc[MG_BAD_MERGED_LEN]) return alga_fail(e, ALGA_ERR_CAPACITY, "stitch: a stitched contig is longer than 2^31 - 1");
+    // the merge stage's path from here on; a stitch the cycles lost is turned into DROPPED_CYCLE between the drop and the ranks
+    const auto dropped = [&]() { launch_st_dropped(en, w.join, jo.state, tg.max_blocks, s); return alga_check_launch(e, "k_st_dropped"); };
+    if ((rc = alga_merge_tail(e, tg, eo, w, lo, col_off, rs.words, (unsigned long long *) rs.begin.p, cnt, ST_COUNTERS, "stitch", "stitched", dropped, s))) return rc;
     const uint64_t NS = hc[MG_MERGED], NC = hc[MG_COLUMNS_AFTER];
-    const size_t new_words = (size_t) ((NC + 15) >> 4) + 2;
-    if ((rc = alga_ensure(e, rs.words, new_words * sizeof(uint32_t)))) return rc;
-    if (NS) launch_exclusive_scan((const uint32_t *) lo.m_len, NS + 1, col_off, (uint64_t *) e->scan_scratch.p, s);
-    if ((rc = alga_check_launch(e, "scan(stitched lengths)"))) return rc;
-    launch_mg_build(tg, lo, col_off, (uint32_t) NS, NC, (uint32_t *) rs.words.p, (unsigned long long *) rs.begin.p, s);
-    if ((rc = alga_check_launch(e, "k_mg_build"))) return rc;
     HIP_TRY(e, hipEventRecord(evs.ev[2], s));
     HIP_TRY(e, hipStreamSynchronize(s));
 

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+
+#include "chain_kernels.h"
 #include "seed_index.h"
 
 namespace alga {
@@ -13,7 +16,6 @@ enum { MG_BAD = 0, MG_COLUMNS, MG_END_COLUMNS, MG_INDEX_POS, MG_ENDS, MG_SEEDS, 
        MG_REMOVED, MG_LONGEST_OVERLAP, MG_MERGED, MG_MULTI, MG_MEMBERS, MG_LONGEST, MG_COLUMNS_AFTER, MG_BAD_MERGED_LEN, MG_COUNTERS };
 constexpr uint32_t MG_BAD_LEN = 1;                                       // bit of counters[MG_BAD]
 constexpr uint8_t  MG_E_HAS_OVERLAP = 1, MG_E_AMBIGUOUS = 2, MG_E_JOINED = 4, MG_E_DROPPED_CYCLE = 8;   // ALGA_MERGE_END_* of include/alga_amd.h
-constexpr uint32_t MG_NONE = 0xFFFFFFFFu;
 constexpr int32_t  MG_MAX_OVERLAP = 4096;
 
 // a ragged target set as the placement takes it
@@ -32,11 +34,6 @@ struct MgEnds : SeedSpace {
 struct MgEndOut {
     int32_t *partner, *olen;
     uint8_t *mm, *hits, *state;
-};
-// the lists over the 2T states (contig, entry end), twice: a jump reads one set and writes the other
-struct MgLists {
-    unsigned long long *wsum;
-    uint32_t *nxt, *aux, *tail;
 };
 struct MgLayout {
     int32_t *merged, *rank;
@@ -57,20 +54,18 @@ void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32
 // one wave per end (blocks: seed_blocks(2T))
 void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
                        unsigned long long *counters, hipStream_t s);
-// one thread per end: join[x] = the end x is joined with, MG_NONE without; JOINED into the end's state
+// one thread per end: join[x] = the end x is joined with, CHAIN_NONE without; JOINED into the end's state
 void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, uint32_t max_blocks, hipStream_t s);
-// pointer jumping over the 2T states with the smallest contig id riding along; the smallest contig of a cycle drops the join at its left end
-void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, uint32_t max_blocks, hipStream_t s);
-void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s);
-void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
-// the same jumps over the paths that are left: states, len - overlap and the last state to the end of the path
-void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const MgLists &l, hipStream_t s);
-void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s);
+// The joins into paths: the chain core (chain_kernels.h).  A state that still has a successor after the cycle phase lies on a cycle: the join at
+// end 2c of its smallest contig c is dropped, both ends lose JOINED and get DROPPED_CYCLE
+void launch_mg_cycle_drop(const ChainLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
+// the rank phase's init: the weight of a state is len - overlap at the end it is left at
+void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const ChainLists &l, hipStream_t s);
 // per contig: rank, orientation, start, overlap_after; head / first / members (T + 1 entries of the last two) for the scans; the join counters
-void launch_mg_place(const MgTargets &t, const MgLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
+void launch_mg_place(const MgTargets &t, const ChainLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
                      unsigned long long *counters, hipStream_t s);
 // merged ids, the member lists, the merged lengths; counters[MG_MERGED], [MG_MULTI], [MG_MEMBERS], [MG_LONGEST], [MG_COLUMNS_AFTER], [MG_BAD_MERGED_LEN]
-void launch_mg_layout(const MgTargets &t, const MgLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
+void launch_mg_layout(const MgTargets &t, const ChainLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
                       unsigned long long *counters, hipStream_t s);
 // the merged contigs' column array, one thread per word; begin[j] = col_off[j]
 void launch_mg_build(const MgTargets &t, const MgLayout &lo, const uint32_t *col_off, uint32_t n_merged, uint64_t columns, uint32_t *words, unsigned long long *begin,
@@ -86,3 +81,11 @@ void launch_mg_fasta_sizes(const MgFasta &f, uint32_t *sizes, unsigned long long
 void launch_mg_fasta_write(const MgFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s);
 
 }  // namespace alga
+
+// engine_merge.hip, shared with engine_stitch.hip: from the joins (w.join and the per-end arrays, as k_mg_joins leaves them) to the built sequences:
+// cycles, drop, `after_drop` where the caller has a step there, ranks, places, scans, layout, the read-back of n_counters words of cnt into
+// e->h_counters with the refusal of a contig above 2^31 - 1, `words` at its size, the length scan, the build.  stage / noun word the refusal.
+struct DevBuf;
+int alga_merge_tail(alga_engine *e, const alga::MgTargets &tg, const alga::MgEndOut &eo, const alga::ChainWork &w, const alga::MgLayout &lo, uint32_t *col_off, DevBuf &words,
+                    unsigned long long *begin, unsigned long long *cnt, size_t n_counters, const char *stage, const char *noun, const std::function<int()> &after_drop,
+                    hipStream_t s);

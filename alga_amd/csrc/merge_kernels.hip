@@ -13,12 +13,9 @@
 //                     of E_y gives o = W_y - q + j k; the o bases only are verified, so every (y, o) counts once.  The minimum key
 //                     (mm, y, o descending) and the number of (y, o) are reduced across the wave.
 //   k_mg_joins        one thread per end: joined where both ends have one overlap, each other, at one o
-//   k_mg_cycle_init / _jump / _drop   pointer jumping over the 2T states (contig, entry end) with the smallest contig id carried along: a state
-//                     that still has a successor after ceil(log2(2T)) + 1 doublings is on a cycle, and the contig that is its own minimum drops
-//                     the join at its left end
-//   k_mg_rank_init / _jump            the same jumps over the paths that are left: states, len - overlap and the last state to the end
-//   k_mg_place        per contig the direction whose first contig has the smaller id, rank, orientation, start, overlap_after
-//   k_mg_layout       merged ids, member lists and merged lengths from the scans over "is the first contig" and "members of what it starts"
+//   k_mg_cycle_drop / k_mg_rank_init / k_mg_place / k_mg_layout   the joins turned into ordered, oriented paths by the chain core (chain_kernels.h;
+//                     these four instantiate chain_device.h): a dropped join loses JOINED and gets DROPPED_CYCLE on both ends, a state weighs len -
+//                     overlap; start, overlap_after and the join counters; the 32-bit merged lengths (a flag for one above 2^31 - 1), count and sum
 //   k_mg_build        every output word gathered by one lane: a column finds its member by bisection over the starts, an overlapped column is
 //                     the earlier contig's; minus-oriented members complemented and mirrored
 //   k_mg_fasta_sizes / k_mg_fasta_write   one record per merged contig, one wave per record
@@ -32,6 +29,7 @@
 #include "merge_kernels.h"
 #include "seed_device.h"
 #include "text_record.h"
+#include "chain_device.h"
 #include "prefsuf_common.h"
 
 namespace alga {
@@ -39,6 +37,7 @@ namespace alga {
 namespace {
 
 constexpr int MG_BLOCK = 256, MG_WAVES = MG_BLOCK / 64;
+static_assert(MG_BLOCK == CHAIN_BLOCK, "the bodies of chain_device.h stride by CHAIN_BLOCK");
 
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_check(MgTargets t, unsigned long long *__restrict__ counters) {
     unsigned long long sum = 0, bad = 0;
@@ -168,68 +167,30 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_overlap(MgEnds en, SeedIndex ix
 // (a thread writes its own end only; partner[x] < 2T wherever hits[x] > 0)
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_joins(MgEndOut o, uint32_t E, uint32_t *__restrict__ join) {
     for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
-        uint32_t j = MG_NONE;
+        uint32_t j = CHAIN_NONE;
         if (o.hits[x] == 1) {
             const uint32_t y = (uint32_t) o.partner[x];
             if (o.hits[y] == 1 && (uint32_t) o.partner[y] == (uint32_t) x && o.olen[y] == o.olen[x]) j = y;
         }
         join[x] = j;
-        if (j != MG_NONE) o.state[x] |= MG_E_JOINED;
+        if (j != CHAIN_NONE) o.state[x] |= MG_E_JOINED;
     }
 }
 
-// state x = 2c + e: contig c entered at end e, left at e ^ 1 through that end's join into the partner end's contig
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_init(const uint32_t *__restrict__ join, uint32_t E, MgLists l) {
-    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
-        l.nxt[x] = join[x ^ 1]; l.aux[x] = (uint32_t) (x >> 1);
-    }
-}
-
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_jump(uint32_t E, MgLists from, MgLists to) {
-    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
-        const uint32_t y = from.nxt[x];
-        uint32_t m = from.aux[x], z = MG_NONE;
-        if (y != MG_NONE) { const uint32_t my = from.aux[y]; m = my < m ? my : m; z = from.nxt[y]; }
-        to.nxt[x] = z; to.aux[x] = m;
-    }
-}
-
-// one thread per contig; only the smallest contig of a cycle writes, and only the two ends of the join at its left end
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_drop(MgLists l, uint32_t T, uint32_t *__restrict__ join, uint8_t *__restrict__ end_state,
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_cycle_drop(ChainLists l, uint32_t T, uint32_t *__restrict__ join, uint8_t *__restrict__ end_state,
                                                             unsigned long long *__restrict__ counters) {
-    unsigned long long n = 0;
-    for (uint64_t c = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; c < T; c += (uint64_t) gridDim.x * MG_BLOCK) {
-        if (l.nxt[2 * c] == MG_NONE || l.aux[2 * c] != (uint32_t) c) continue;
-        const uint32_t y = join[2 * c];
-        join[2 * c] = MG_NONE; join[y] = MG_NONE;
-        end_state[2 * c] = (uint8_t) ((end_state[2 * c] & ~MG_E_JOINED) | MG_E_DROPPED_CYCLE);
+    chain_cycle_drop_body(l, T, join, [=](uint64_t x, uint32_t y) {
+        end_state[x] = (uint8_t) ((end_state[x] & ~MG_E_JOINED) | MG_E_DROPPED_CYCLE);
         end_state[y] = (uint8_t) ((end_state[y] & ~MG_E_JOINED) | MG_E_DROPPED_CYCLE);
-        n++;
-    }
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[MG_DROPPED], n);
+    }, &counters[MG_DROPPED]);
 }
 
 // (a joined end has 42 <= olen <= len / 2: len - olen > 0)
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_rank_init(MgTargets t, const uint32_t *__restrict__ join, const int32_t *__restrict__ olen, MgLists l) {
-    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < 2ull * t.T; x += (uint64_t) gridDim.x * MG_BLOCK) {
-        const uint32_t out = (uint32_t) (x ^ 1);
-        l.nxt[x] = join[out]; l.aux[x] = 1u; l.tail[x] = (uint32_t) x;
-        l.wsum[x] = (unsigned long long) (t.len[x >> 1] - (join[out] != MG_NONE ? olen[out] : 0));
-    }
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_rank_init(MgTargets t, const uint32_t *__restrict__ join, const int32_t *__restrict__ olen, ChainLists l) {
+    chain_rank_init_body(join, 2ull * t.T, l, [=](uint32_t x, bool joined) { return (unsigned long long) (t.len[x >> 1] - (joined ? olen[x ^ 1u] : 0)); });
 }
 
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_rank_jump(uint32_t E, MgLists from, MgLists to) {
-    for (uint64_t x = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * MG_BLOCK) {
-        const uint32_t y = from.nxt[x];
-        uint32_t d = from.aux[x], tl = from.tail[x], z = MG_NONE;
-        unsigned long long w = from.wsum[x];
-        if (y != MG_NONE) { d += from.aux[y]; w += from.wsum[y]; tl = from.tail[y]; z = from.nxt[y]; }
-        to.nxt[x] = z; to.aux[x] = d; to.tail[x] = tl; to.wsum[x] = w;
-    }
-}
-
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_place(MgTargets t, MgLists l, const uint32_t *__restrict__ join, MgEndOut eo, MgLayout o, uint32_t *__restrict__ head,
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_place(MgTargets t, ChainLists l, const uint32_t *__restrict__ join, MgEndOut eo, MgLayout o, uint32_t *__restrict__ head,
                                                        uint32_t *__restrict__ first, uint32_t *__restrict__ members, unsigned long long *__restrict__ counters) {
     unsigned long long n_joins = 0, n_mm = 0, n_removed = 0, longest = 0;
     for (uint64_t c = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; c <= t.T; c += (uint64_t) gridDim.x * MG_BLOCK) {
@@ -239,20 +200,14 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_place(MgTargets t, MgLists l, c
             head[c] = (uint32_t) c; first[c] = 0; members[c] = 0;
             continue;
         }
-        // the list of state 2c + e begins at the contig the other direction ends at
-        const uint32_t f0 = l.tail[2 * c + 1] >> 1, l0 = l.tail[2 * c] >> 1;   // first and last contig of the direction that enters c at end 0
-        const uint32_t e = f0 <= l0 ? 0u : 1u;                                 // (f0 == l0: a path of one contig, orientation +)
-        const uint32_t x = 2 * (uint32_t) c + e;
-        const uint32_t m = l.aux[x] + l.aux[x ^ 1] - 1u, rank = m - l.aux[x];
-        const uint32_t hx = l.tail[x ^ 1] ^ 1u;                                // the state of the first contig in this direction
-        const uint32_t out = x ^ 1u;                                           // c is left at this end
-        const bool joined = join[out] != MG_NONE;
-        const uint32_t ov = joined ? (uint32_t) eo.olen[out] : 0u;
-        o.rank[c] = (int32_t) rank; o.orient[c] = (uint8_t) e;
-        o.start[c] = (uint32_t) (l.wsum[hx] - l.wsum[x]);
+        const ChainPos p = chain_position(l, (uint32_t) c);
+        const bool joined = join[p.out] != CHAIN_NONE;
+        const uint32_t ov = joined ? (uint32_t) eo.olen[p.out] : 0u;
+        o.rank[c] = (int32_t) p.rank; o.orient[c] = (uint8_t) p.e;
+        o.start[c] = (uint32_t) (l.wsum[p.hx] - l.wsum[p.x]);
         o.overlap_after[c] = (int32_t) ov;
-        if (joined) { n_joins++; n_mm += eo.mm[out]; n_removed += ov; longest = ov > longest ? ov : longest; }
-        head[c] = hx >> 1; first[c] = rank == 0; members[c] = rank == 0 ? m : 0u;
+        if (joined) { n_joins++; n_mm += eo.mm[p.out]; n_removed += ov; longest = ov > longest ? ov : longest; }
+        head[c] = p.hx >> 1; first[c] = p.rank == 0; members[c] = p.rank == 0 ? p.m : 0u;
     }
     n_joins = wave_sum(n_joins); n_mm = wave_sum(n_mm); n_removed = wave_sum(n_removed); longest = wave_max(longest);
     if ((threadIdx.x & 63) == 0 && n_joins) {
@@ -261,26 +216,17 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_place(MgTargets t, MgLists l, c
     }
 }
 
-__global__ void __launch_bounds__(MG_BLOCK) k_mg_layout(MgTargets t, MgLists l, const uint32_t *__restrict__ head, const uint32_t *__restrict__ first_scan,
+__global__ void __launch_bounds__(MG_BLOCK) k_mg_layout(MgTargets t, ChainLists l, const uint32_t *__restrict__ head, const uint32_t *__restrict__ first_scan,
                                                         const uint32_t *__restrict__ members_scan, MgLayout o, unsigned long long *__restrict__ counters) {
     unsigned long long n_mg = 0, n_multi = 0, n_mem = 0, longest = 0, sum = 0, bad = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) o.m_off[first_scan[t.T]] = members_scan[t.T];
-    for (uint64_t c = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; c < t.T; c += (uint64_t) gridDim.x * MG_BLOCK) {
-        const int32_t rank = o.rank[c];
-        if (rank < 0) continue;
-        const uint32_t h = head[c], mid = first_scan[h], at = members_scan[h];
-        o.merged[c] = (int32_t) mid;
-        o.m_members[at + (uint32_t) rank] = (int32_t) c;
-        if (rank == 0) {
-            const uint32_t x = 2 * (uint32_t) c + o.orient[c];
-            unsigned long long bases = l.wsum[x];
-            if (bases > 0x7FFFFFFFull) { bad = 1; bases = 0; }
-            o.m_off[mid] = at; o.m_len[mid] = (int32_t) bases;
-            n_mg++; n_multi += l.aux[x] > 1u; n_mem += l.aux[x]; sum += bases;
-            longest = bases > longest ? bases : longest;
-        }
-    }
-    n_mg = wave_sum(n_mg); n_multi = wave_sum(n_multi); n_mem = wave_sum(n_mem); longest = wave_max(longest); sum = wave_sum(sum); bad = wave_max(bad);
+    chain_layout_body(l, t.T, o.rank, o.orient, head, first_scan, members_scan, o.merged, o.m_off, o.m_members,
+                      [&](uint32_t, uint32_t mid, uint32_t, unsigned long long bases, uint32_t members) {      // the 32-bit length: one above 2^31 - 1 is refused
+                          if (bases > 0x7FFFFFFFull) { bad = 1; bases = 0; }
+                          o.m_len[mid] = (int32_t) bases;
+                          n_mg++; n_multi += members > 1u; n_mem += members; sum += bases;
+                          longest = bases > longest ? bases : longest;
+                      });
+    bad = wave_max(bad); n_mg = wave_sum(n_mg); n_multi = wave_sum(n_multi); n_mem = wave_sum(n_mem); longest = wave_max(longest); sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0 && n_mg) {
         atomicAdd(&counters[MG_MERGED], n_mg); atomicAdd(&counters[MG_MEMBERS], n_mem); atomicMax(&counters[MG_LONGEST], longest);
         atomicAdd(&counters[MG_COLUMNS_AFTER], sum);
@@ -374,32 +320,20 @@ void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, uint32_t max
     if (E) hipLaunchKernelGGL(k_mg_joins, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, o, E, join);
 }
 
-void launch_mg_cycle_init(const uint32_t *join, uint32_t E, const MgLists &l, uint32_t max_blocks, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_cycle_init, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, join, E, l);
-}
-
-void launch_mg_cycle_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_cycle_jump, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, E, from, to);
-}
-
-void launch_mg_cycle_drop(const MgLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
+void launch_mg_cycle_drop(const ChainLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
     if (T) hipLaunchKernelGGL(k_mg_cycle_drop, dim3(mg_grid(T, max_blocks)), dim3(MG_BLOCK), 0, s, l, T, join, end_state, counters);
 }
 
-void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const MgLists &l, hipStream_t s) {
+void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const ChainLists &l, hipStream_t s) {
     if (t.T) hipLaunchKernelGGL(k_mg_rank_init, dim3(mg_grid(2ull * t.T, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, join, olen, l);
 }
 
-void launch_mg_rank_jump(uint32_t E, const MgLists &from, const MgLists &to, uint32_t max_blocks, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_rank_jump, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, E, from, to);
-}
-
-void launch_mg_place(const MgTargets &t, const MgLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
+void launch_mg_place(const MgTargets &t, const ChainLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
                      unsigned long long *counters, hipStream_t s) {
     hipLaunchKernelGGL(k_mg_place, dim3(mg_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, join, o, lo, head, first, members, counters);
 }
 
-void launch_mg_layout(const MgTargets &t, const MgLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
+void launch_mg_layout(const MgTargets &t, const ChainLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
                       unsigned long long *counters, hipStream_t s) {
     hipLaunchKernelGGL(k_mg_layout, dim3(mg_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, head, first_scan, members_scan, lo, counters);
 }

@@ -4,13 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "chain_kernels.h"
+
 namespace alga {
 
 // counters[] (unsigned long long): the refusal flags, then what the kernels count
 enum { SC_BAD = 0, SC_SPLIT, SC_LINKS, SC_TOO_FAR, SC_BUNDLES, SC_SUPPORTED, SC_AMBIGUOUS, SC_JOINS, SC_DROPPED, SC_SCAFFOLDS, SC_MULTI, SC_MEMBERS, SC_LONGEST,
        SC_COUNTERS };
 constexpr uint32_t SC_BAD_PAIR = 1, SC_BAD_LEN = 2, SC_BAD_PLACE = 4;       // bits of counters[SC_BAD]
-constexpr uint32_t SC_NONE = 0xFFFFFFFFu;                                  // no choice / no partner / no successor (a memset of 0xFF)
+constexpr uint32_t SC_NONE = 0xFFFFFFFFu;                                  // no choice (no partner: CHAIN_NONE, a memset of 0xFF)
 constexpr uint8_t  SC_B_SUPPORTED = 1, SC_B_JOIN = 2, SC_B_DROPPED = 4;    // ALGA_SCAFFOLD_BUNDLE_* (bits of d_b_state)
 constexpr uint8_t  SC_E_SUPPORTED = 1, SC_E_AMBIGUOUS = 2, SC_E_JOINED = 4; // ALGA_SCAFFOLD_END_* (bits of d_end_state)
 
@@ -59,17 +61,11 @@ void launch_sc_choice(const unsigned long long *best, const unsigned long long *
 // JOIN of every bundle both of whose ends chose the other; partner[end] (0xFF-filled) and join_bundle[end] of the joined ends
 void launch_sc_joins(const ScBundles &b, const uint32_t *choice, uint32_t *partner, uint32_t *join_bundle, uint32_t max_blocks, hipStream_t s);
 
-// The directed lists over the states 2c + e ("contig c entered at end e"), succ(x) = partner[x ^ 1].  Two sets of arrays, jumped from one to the other.
-struct ScLists {
-    uint32_t *nxt, *aux, *tail;       // aux: the smallest contig id seen (cycle phase) / the states from here to the list's end (rank phase)
-    unsigned long long *wsum;         // rank phase: length + gap behind, summed from here to the list's end
-};
-void launch_sc_cycle_init(const uint32_t *partner, uint64_t n_states, const ScLists &l, uint32_t max_blocks, hipStream_t s);
-void launch_sc_cycle_jump(uint64_t n_states, const ScLists &from, const ScLists &to, uint32_t max_blocks, hipStream_t s);
-// a state that still has a successor lies on a cycle: the join at end 2c of its smallest contig c is dropped
-void launch_sc_cycle_drop(const ScLists &l, uint32_t T, uint32_t *partner, const uint32_t *join_bundle, uint8_t *b_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
-void launch_sc_rank_init(const ScTargets &t, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, int32_t min_gap, const ScLists &l, uint32_t max_blocks, hipStream_t s);
-void launch_sc_rank_jump(uint64_t n_states, const ScLists &from, const ScLists &to, uint32_t max_blocks, hipStream_t s);
+// The joins into paths: the chain core (chain_kernels.h) with partner[] as its join[].  A state that still has a successor after the cycle phase
+// lies on a cycle: the join at end 2c of its smallest contig c is dropped, DROPPED into its bundle's state
+void launch_sc_cycle_drop(const ChainLists &l, uint32_t T, uint32_t *partner, const uint32_t *join_bundle, uint8_t *b_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
+// the rank phase's init: the weight of a state is its contig's length and the gap behind it
+void launch_sc_rank_init(const ScTargets &t, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, int32_t min_gap, const ChainLists &l, uint32_t max_blocks, hipStream_t s);
 
 struct ScLayout {
     int32_t *scaffold, *rank;
@@ -84,10 +80,10 @@ struct ScLayout {
 };
 // per contig: rank, orientation, start, gap_after, join_links in the direction item 7 chooses; head[c] = the first contig of its scaffold,
 // first[c] = 1 and members[c] = the scaffold's contigs where c is that contig, else 0 (T + 1 entries each, the last 0); JOINED of its two ends
-void launch_sc_place(const ScTargets &t, const ScLists &l, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, const uint32_t *b_links, int32_t min_gap,
+void launch_sc_place(const ScTargets &t, const ChainLists &l, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, const uint32_t *b_links, int32_t min_gap,
                      const ScLayout &o, uint32_t *head, uint32_t *first, uint32_t *members, unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
 // scaffold ids and member lists from the exclusive scans of first[] and members[] (T + 1 entries: the totals are entry T)
-void launch_sc_layout(const ScTargets &t, const ScLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const ScLayout &o,
+void launch_sc_layout(const ScTargets &t, const ChainLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const ScLayout &o,
                       unsigned long long *counters, uint32_t max_blocks, hipStream_t s);
 
 // `>scaffold_id=<j>_length=<s_len>_contigs=<m>\n<sequence>\n`, one record per scaffold, the sequence from a column array

@@ -10,11 +10,9 @@
 //                     the wave's links are of one bundle: a bundle over several blocks is a few adds)
 //   k_sc_bundles      a, b, links, gap, SUPPORTED; best[end]       k_sc_second   second[end]
 //   k_sc_choice       AMBIGUOUS and choice per end                 k_sc_joins    JOIN where both ends chose each other; partner[end]
-//   k_sc_cycle_init / _jump / _drop   pointer jumping over the 2T states with the smallest contig id carried along: a state that still has a
-//                     successor after ceil(log2(2T)) + 1 doublings is on a cycle, and the contig that is its own minimum drops the join at 2c
-//   k_sc_rank_init / _jump            the same jumps over the paths that are left: states to the end, bases and gaps to the end, the last state
-//   k_sc_place        per contig the direction item 7 chooses (the list whose first contig has the smaller id), rank, orientation, start
-//   k_sc_layout       scaffold ids and the member lists from the scans over "is the first contig" and "members of the scaffold it starts"
+//   k_sc_cycle_drop / k_sc_rank_init / k_sc_place / k_sc_layout   the joins turned into ordered, oriented paths by the chain core (chain_kernels.h;
+//                     these four instantiate chain_device.h): a dropped join is DROPPED on its bundle, a state weighs its contig's length and the
+//                     gap behind it; start, gap_after, join_links, JOINED per contig in the direction item 7 chooses; the 64-bit scaffold lengths
 //   k_sc_fasta_sizes / k_sc_fasta_write   one record per scaffold, one wave per record; a byte finds its contig by bisection over the starts
 // Block 256 and the grid caps are picked, not tuned; the launches' max_blocks lowers the cap of every grid that goes through sc_grid and of the
 // FASTA write grid (option "scaffold_max_blocks": a knob of the tests, which make every grid-stride loop here take further passes).
@@ -25,12 +23,14 @@
 
 #include "scaffold_kernels.h"
 #include "text_record.h"
+#include "chain_device.h"
 
 namespace alga {
 
 namespace {
 
 constexpr int SC_BLOCK = 256, SC_WAVES = SC_BLOCK / 64;
+static_assert(SC_BLOCK == CHAIN_BLOCK, "the bodies of chain_device.h stride by CHAIN_BLOCK");
 constexpr uint8_t SC_ST_UNIQUE = 2, SC_ST_MINUS = 4;                    // ALGA_PLACE_UNIQUE, ALGA_PLACE_MINUS
 
 __device__ __forceinline__ uint32_t sc_wave_or(uint32_t v) {
@@ -193,64 +193,32 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_joins(ScBundles b, const uint32
     }
 }
 
-// state x = 2c + e: contig c entered at end e, left at e ^ 1 through that end's join into the partner end's contig
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_init(const uint32_t *__restrict__ partner, uint64_t n_states, ScLists l) {
-    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_states; x += (uint64_t) gridDim.x * SC_BLOCK) {
-        l.nxt[x] = partner[x ^ 1]; l.aux[x] = (uint32_t) (x >> 1);
-    }
-}
-
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_jump(uint64_t n_states, ScLists from, ScLists to) {
-    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_states; x += (uint64_t) gridDim.x * SC_BLOCK) {
-        const uint32_t y = from.nxt[x];
-        uint32_t m = from.aux[x], z = SC_NONE;
-        if (y != SC_NONE) { const uint32_t my = from.aux[y]; m = my < m ? my : m; z = from.nxt[y]; }
-        to.nxt[x] = z; to.aux[x] = m;
-    }
-}
-
-// one thread per contig; only the smallest contig of a cycle writes, and only the two ends of the join at its left end
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_drop(ScLists l, uint32_t T, uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_cycle_drop(ChainLists l, uint32_t T, uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
                                                             uint8_t *__restrict__ b_state, unsigned long long *__restrict__ counters) {
-    unsigned long long n = 0;
-    for (uint64_t c = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; c < T; c += (uint64_t) gridDim.x * SC_BLOCK) {
-        if (l.nxt[2 * c] == SC_NONE || l.aux[2 * c] != (uint32_t) c) continue;
-        const uint32_t y = partner[2 * c];
-        partner[2 * c] = SC_NONE; partner[y] = SC_NONE;
-        b_state[join_bundle[2 * c]] = SC_B_SUPPORTED | SC_B_JOIN | SC_B_DROPPED;
-        n++;
-    }
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(&counters[SC_DROPPED], n);
+    chain_cycle_drop_body(l, T, partner, [=](uint64_t x, uint32_t) { b_state[join_bundle[x]] = SC_B_SUPPORTED | SC_B_JOIN | SC_B_DROPPED; }, &counters[SC_DROPPED]);
 }
 
-__device__ __forceinline__ uint32_t sc_gap_behind(const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle, const int32_t *__restrict__ b_gap,
-                                                  int32_t min_gap, uint32_t end) {
-    if (partner[end] == SC_NONE) return 0u;
-    const int32_t g = b_gap[join_bundle[end]];
-    return (uint32_t) (g > min_gap ? g : min_gap);
-}
+// the gap behind a joined end (its bundle's, at least min_gap); as Weight, a contig's length and the gap behind the end it is left at
+struct ScGap {
+    const uint32_t *col_off, *join_bundle;
+    const int32_t *b_gap;
+    int32_t min_gap;
+    __device__ __forceinline__ uint32_t behind(uint32_t end, bool joined) const {
+        if (!joined) return 0u;
+        const int32_t g = b_gap[join_bundle[end]];
+        return (uint32_t) (g > min_gap ? g : min_gap);
+    }
+    __device__ __forceinline__ unsigned long long operator()(uint32_t x, bool joined) const {
+        return (unsigned long long) (col_off[(x >> 1) + 1] - col_off[x >> 1]) + behind(x ^ 1u, joined);
+    }
+};
 
 __global__ void __launch_bounds__(SC_BLOCK) k_sc_rank_init(ScTargets t, const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
-                                                           const int32_t *__restrict__ b_gap, int32_t min_gap, ScLists l) {
-    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < 2ull * t.T; x += (uint64_t) gridDim.x * SC_BLOCK) {
-        const uint32_t c = (uint32_t) (x >> 1);
-        l.nxt[x] = partner[x ^ 1]; l.aux[x] = 1u; l.tail[x] = (uint32_t) x;
-        l.wsum[x] = (unsigned long long) (t.col_off[c + 1] - t.col_off[c]) + sc_gap_behind(partner, join_bundle, b_gap, min_gap, (uint32_t) (x ^ 1));
-    }
+                                                           const int32_t *__restrict__ b_gap, int32_t min_gap, ChainLists l) {
+    chain_rank_init_body(partner, 2ull * t.T, l, ScGap{t.col_off, join_bundle, b_gap, min_gap});
 }
 
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_rank_jump(uint64_t n_states, ScLists from, ScLists to) {
-    for (uint64_t x = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; x < n_states; x += (uint64_t) gridDim.x * SC_BLOCK) {
-        const uint32_t y = from.nxt[x];
-        uint32_t d = from.aux[x], tl = from.tail[x], z = SC_NONE;
-        unsigned long long w = from.wsum[x];
-        if (y != SC_NONE) { d += from.aux[y]; w += from.wsum[y]; tl = from.tail[y]; z = from.nxt[y]; }
-        to.nxt[x] = z; to.aux[x] = d; to.tail[x] = tl; to.wsum[x] = w;
-    }
-}
-
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_place(ScTargets t, ScLists l, const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_place(ScTargets t, ChainLists l, const uint32_t *__restrict__ partner, const uint32_t *__restrict__ join_bundle,
                                                        const int32_t *__restrict__ b_gap, const uint32_t *__restrict__ b_links, int32_t min_gap, ScLayout o,
                                                        uint32_t *__restrict__ head, uint32_t *__restrict__ first, uint32_t *__restrict__ members,
                                                        unsigned long long *__restrict__ counters) {
@@ -258,50 +226,33 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_place(ScTargets t, ScLists l, c
     for (uint64_t c = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; c <= t.T; c += (uint64_t) gridDim.x * SC_BLOCK) {
         if (c == t.T) { first[c] = 0; members[c] = 0; continue; }               // the place of the scans' totals
         const uint32_t len = t.col_off[c + 1] - t.col_off[c];
-        o.end_state[2 * c] |= partner[2 * c] != SC_NONE ? SC_E_JOINED : (uint8_t) 0;
-        o.end_state[2 * c + 1] |= partner[2 * c + 1] != SC_NONE ? SC_E_JOINED : (uint8_t) 0;
+        o.end_state[2 * c] |= partner[2 * c] != CHAIN_NONE ? SC_E_JOINED : (uint8_t) 0;
+        o.end_state[2 * c + 1] |= partner[2 * c + 1] != CHAIN_NONE ? SC_E_JOINED : (uint8_t) 0;
         if (len == 0) {                                                        // in no scaffold (nothing is placed on it: it has no join)
             o.scaffold[c] = -1; o.rank[c] = -1; o.orient[c] = 0; o.start[c] = 0; o.gap_after[c] = 0; o.join_links[c] = 0;
             head[c] = (uint32_t) c; first[c] = 0; members[c] = 0;
             continue;
         }
-        // the list of state 2c + e begins at the contig the other direction ends at
-        const uint32_t f0 = l.tail[2 * c + 1] >> 1, l0 = l.tail[2 * c] >> 1;   // first and last contig of the direction that enters c at end 0
-        const uint32_t e = (f0 < l0 || f0 == l0) ? 0u : 1u;                    // (f0 == l0: a path of one contig, orientation +)
-        const uint32_t x = 2 * (uint32_t) c + e;
-        const uint32_t m = l.aux[x] + l.aux[x ^ 1] - 1u, rank = m - l.aux[x];
-        const uint32_t hx = l.tail[x ^ 1] ^ 1u;                                // the state of the first contig in this direction
-        const uint32_t out = x ^ 1u;                                           // c is left at this end
-        const bool joined = partner[out] != SC_NONE;
-        o.rank[c] = (int32_t) rank; o.orient[c] = (uint8_t) e;
-        o.start[c] = l.wsum[hx] - l.wsum[x];
-        o.gap_after[c] = (int32_t) sc_gap_behind(partner, join_bundle, b_gap, min_gap, out);
-        o.join_links[c] = joined ? b_links[join_bundle[out]] : 0u;
+        const ChainPos p = chain_position(l, (uint32_t) c);
+        const bool joined = partner[p.out] != CHAIN_NONE;
+        o.rank[c] = (int32_t) p.rank; o.orient[c] = (uint8_t) p.e;
+        o.start[c] = l.wsum[p.hx] - l.wsum[p.x];
+        o.gap_after[c] = (int32_t) ScGap{t.col_off, join_bundle, b_gap, min_gap}.behind(p.out, joined);
+        o.join_links[c] = joined ? b_links[join_bundle[p.out]] : 0u;
         n_joins += joined;
-        head[c] = hx >> 1; first[c] = rank == 0; members[c] = rank == 0 ? m : 0u;
+        head[c] = p.hx >> 1; first[c] = p.rank == 0; members[c] = p.rank == 0 ? p.m : 0u;
     }
     n_joins = wave_sum(n_joins);
     if ((threadIdx.x & 63) == 0 && n_joins) atomicAdd(&counters[SC_JOINS], n_joins);
 }
 
-__global__ void __launch_bounds__(SC_BLOCK) k_sc_layout(ScTargets t, ScLists l, const uint32_t *__restrict__ head, const uint32_t *__restrict__ first_scan,
+__global__ void __launch_bounds__(SC_BLOCK) k_sc_layout(ScTargets t, ChainLists l, const uint32_t *__restrict__ head, const uint32_t *__restrict__ first_scan,
                                                         const uint32_t *__restrict__ members_scan, ScLayout o, unsigned long long *__restrict__ counters) {
     unsigned long long n_sc = 0, n_multi = 0, n_mem = 0, longest = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) o.s_off[first_scan[t.T]] = members_scan[t.T];
-    for (uint64_t c = (uint64_t) blockIdx.x * SC_BLOCK + threadIdx.x; c < t.T; c += (uint64_t) gridDim.x * SC_BLOCK) {
-        const int32_t rank = o.rank[c];
-        if (rank < 0) continue;
-        const uint32_t h = head[c], sid = first_scan[h], at = members_scan[h];
-        o.scaffold[c] = (int32_t) sid;
-        o.s_members[at + (uint32_t) rank] = (int32_t) c;
-        if (rank == 0) {
-            const uint32_t x = 2 * (uint32_t) c + o.orient[c];
-            const unsigned long long bases = l.wsum[x];
-            o.s_off[sid] = at; o.s_len[sid] = bases;
-            n_sc++; n_multi += l.aux[x] > 1u; n_mem += l.aux[x];
-            longest = bases > longest ? bases : longest;
-        }
-    }
+    chain_layout_body(l, t.T, o.rank, o.orient, head, first_scan, members_scan, o.scaffold, o.s_off, o.s_members,
+                      [&](uint32_t, uint32_t sid, uint32_t, unsigned long long bases, uint32_t members) {      // the 64-bit length
+                          o.s_len[sid] = bases; n_sc++; n_multi += members > 1u; n_mem += members; longest = bases > longest ? bases : longest;
+                      });
     n_sc = wave_sum(n_sc); n_multi = wave_sum(n_multi); n_mem = wave_sum(n_mem); longest = wave_max(longest);
     if ((threadIdx.x & 63) == 0 && n_sc) {
         atomicAdd(&counters[SC_SCAFFOLDS], n_sc); atomicAdd(&counters[SC_MEMBERS], n_mem); atomicMax(&counters[SC_LONGEST], longest);
@@ -395,32 +346,20 @@ void launch_sc_joins(const ScBundles &b, const uint32_t *choice, uint32_t *partn
     if (b.n) hipLaunchKernelGGL(k_sc_joins, dim3(sc_grid(b.n, max_blocks)), dim3(SC_BLOCK), 0, s, b, choice, partner, join_bundle);
 }
 
-void launch_sc_cycle_init(const uint32_t *partner, uint64_t n_states, const ScLists &l, uint32_t max_blocks, hipStream_t s) {
-    if (n_states) hipLaunchKernelGGL(k_sc_cycle_init, dim3(sc_grid(n_states, max_blocks)), dim3(SC_BLOCK), 0, s, partner, n_states, l);
-}
-
-void launch_sc_cycle_jump(uint64_t n_states, const ScLists &from, const ScLists &to, uint32_t max_blocks, hipStream_t s) {
-    if (n_states) hipLaunchKernelGGL(k_sc_cycle_jump, dim3(sc_grid(n_states, max_blocks)), dim3(SC_BLOCK), 0, s, n_states, from, to);
-}
-
-void launch_sc_cycle_drop(const ScLists &l, uint32_t T, uint32_t *partner, const uint32_t *join_bundle, uint8_t *b_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
+void launch_sc_cycle_drop(const ChainLists &l, uint32_t T, uint32_t *partner, const uint32_t *join_bundle, uint8_t *b_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
     if (T) hipLaunchKernelGGL(k_sc_cycle_drop, dim3(sc_grid(T, max_blocks)), dim3(SC_BLOCK), 0, s, l, T, partner, join_bundle, b_state, counters);
 }
 
-void launch_sc_rank_init(const ScTargets &t, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, int32_t min_gap, const ScLists &l, uint32_t max_blocks, hipStream_t s) {
+void launch_sc_rank_init(const ScTargets &t, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, int32_t min_gap, const ChainLists &l, uint32_t max_blocks, hipStream_t s) {
     if (t.T) hipLaunchKernelGGL(k_sc_rank_init, dim3(sc_grid(2ull * t.T, max_blocks)), dim3(SC_BLOCK), 0, s, t, partner, join_bundle, b_gap, min_gap, l);
 }
 
-void launch_sc_rank_jump(uint64_t n_states, const ScLists &from, const ScLists &to, uint32_t max_blocks, hipStream_t s) {
-    if (n_states) hipLaunchKernelGGL(k_sc_rank_jump, dim3(sc_grid(n_states, max_blocks)), dim3(SC_BLOCK), 0, s, n_states, from, to);
-}
-
-void launch_sc_place(const ScTargets &t, const ScLists &l, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, const uint32_t *b_links, int32_t min_gap,
+void launch_sc_place(const ScTargets &t, const ChainLists &l, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, const uint32_t *b_links, int32_t min_gap,
                      const ScLayout &o, uint32_t *head, uint32_t *first, uint32_t *members, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
     hipLaunchKernelGGL(k_sc_place, dim3(sc_grid((uint64_t) t.T + 1, max_blocks)), dim3(SC_BLOCK), 0, s, t, l, partner, join_bundle, b_gap, b_links, min_gap, o, head, first, members, counters);
 }
 
-void launch_sc_layout(const ScTargets &t, const ScLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const ScLayout &o,
+void launch_sc_layout(const ScTargets &t, const ChainLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const ScLayout &o,
                       unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
     hipLaunchKernelGGL(k_sc_layout, dim3(sc_grid((uint64_t) t.T + 1, max_blocks)), dim3(SC_BLOCK), 0, s, t, l, head, first_scan, members_scan, o, counters);
 }

@@ -158,14 +158,14 @@ __global__ void __launch_bounds__(ST_BLOCK) k_st_overlap(MgTargets t, StEntries 
 __global__ void __launch_bounds__(ST_BLOCK) k_st_joins(StEntries en, StEntryOut o, const int32_t *__restrict__ end_entry, uint32_t E, MgEndOut eo, uint32_t *__restrict__ join) {
     for (uint64_t x = (uint64_t) blockIdx.x * ST_BLOCK + threadIdx.x; x < E; x += (uint64_t) gridDim.x * ST_BLOCK) {
         const int32_t j = end_entry[x];
-        uint32_t y = MG_NONE;
+        uint32_t y = CHAIN_NONE;
         int32_t ol = 0;
         uint8_t mm = 0;
         if (j >= 0 && (o.state[j] & ST_J_STITCHED)) {
             const uint32_t a = en.a[j];
             y = a == (uint32_t) x ? en.b[j] : a; ol = o.olen[j]; mm = o.mm[j];
         }
-        const bool joined = y != MG_NONE;
+        const bool joined = y != CHAIN_NONE;
         join[x] = y;
         eo.partner[x] = joined ? (int32_t) y : -1; eo.olen[x] = ol; eo.mm[x] = mm; eo.hits[x] = joined ? 1 : 0;
         eo.state[x] = joined ? (uint8_t) (MG_E_HAS_OVERLAP | MG_E_JOINED) : (uint8_t) 0;
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(ST_BLOCK) k_st_joins(StEntries en, StEntryOut 
 __global__ void __launch_bounds__(ST_BLOCK) k_st_dropped(StEntries en, const uint32_t *__restrict__ join, uint8_t *__restrict__ state) {
     for (uint64_t j = (uint64_t) blockIdx.x * ST_BLOCK + threadIdx.x; j < en.J; j += (uint64_t) gridDim.x * ST_BLOCK) {
         const uint8_t st = state[j];
-        if ((st & ST_J_STITCHED) && join[en.a[j]] == MG_NONE) state[j] = (uint8_t) ((st & ~ST_J_STITCHED) | ST_J_DROPPED_CYCLE);
+        if ((st & ST_J_STITCHED) && join[en.a[j]] == CHAIN_NONE) state[j] = (uint8_t) ((st & ~ST_J_STITCHED) | ST_J_DROPPED_CYCLE);
     }
 }
 

@@ -1,6 +1,7 @@
 """The merge stage on the GPU (alga_merge_targets_device, alga_write_merged_fasta_device): every output array and every counter equal to the
 Python definition (tests/merge_checker.py) on the cases of tests/merge_cases.py, from host arrays and from tensors and with directories of 1, 4
-and auto bits; the FASTA bytes and the TSV; the one index workspace shared with the placement and the grow stage; a wave of k_mg_overlap that
+and auto bits; the FASTA bytes and the TSV; the one index workspace shared with the placement and the grow stage, the one chain workspace shared with the
+scaffolder and the stitch stage; a wave of k_mg_overlap that
 takes a second end; a second round on Merged.targets(); the caller's stream; refusals leave an earlier result valid; a result stays valid across
 a later placement, polish, break, grow and scaffold; the planted genome end to end; the command line."""
 import os
@@ -99,6 +100,48 @@ def test_one_index_workspace_serves_the_stages_in_turn(eng):
         assert_same(eng.merge_ends(QC.targets(c), **c["variants"][0]).to_host(), QC.checked("pairings"), "merge pairings")
     finally:
         eng.set_option("place_dir_bits", 0)
+
+
+def test_one_chain_workspace_serves_the_stages_in_turn(tmp_path):
+    """scaffold, merge and stitch order their contigs in one chain workspace of the engine (the two sets of lists over the 2T states, join, head,
+    first / members and their scans, carved for the call's T): on an engine of its own, calls of the three stages in turn with T going
+    260 -> 3 -> 3 -> 5 -> 2 569 (the `chains` family, which holds the longest chain: 1 025 windows), a ring behind a ring and chains behind rings, each result equal to its checker array for array and counter
+    for counter; the scaffold FASTA of the fourth call is written after the fifth.  No nxt, tail or carve offset is left over from the call
+    before.  (Where every stage has buffers of its own the calls cannot meet: there the test passes trivially.)"""
+    import merge_fuzz as MF
+    import scaffold_cases as SQ
+    import scaffold_checker as SC
+    import scaffold_fuzz as SF
+    import stitch_cases as TQ
+    import stitch_checker as ST
+
+    def same(got, want, arrays, what):
+        for k in arrays:
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape and (got[k] == want[k]).all(), (what, k)
+        assert {k: v for k, v in got["info"].items() if not k.startswith("ms_")} == want["info"], (what, got["info"], want["info"])
+
+    def scaffold(e, c, v):
+        pl = e.place_reads(c["rows"], c["lens"], targets=(c["twords"], c["tbegin"], c["tlen"]), pair_off=c["pair_off"], **c["params"])
+        return pl, e.scaffold(c["rows"], c["lens"], c["pair_off"], pl, **v)
+
+    key = "rings/%d" % max(SF.RING_M)
+    big, ring_sc, ring_mg, ring_st, chains = SF.case(key), SQ.case("ring3"), QC.case("ring3"), TQ.case("ring3"), MF.case("chains")
+    assert len(big["tlen"]) == 260 and len(ring_mg["tlen"]) == len(ring_st["tlen"]) == 3 and len(ring_sc["tlen"]) < 260 < len(chains["tlen"])
+    assert SF.checked(key)["info"]["joins_dropped_cycle"] == QC.checked("ring3")["info"]["joins_dropped_cycle"] == SQ.checked("ring3")["info"]["joins_dropped_cycle"] == 1
+    assert max(MF.CHAIN_LENGTHS) == 1025 and MF.checked("chains")["info"]["merged_multi"] >= len(MF.CHAIN_LENGTHS)
+    e = alga_amd.Engine(0)
+    try:
+        same(scaffold(e, big, big["variants"][0])[1].to_host(), SF.checked(key), SC.ARRAYS, "1: scaffold " + key)
+        same(e.merge_ends(QC.targets(ring_mg), **ring_mg["variants"][0]).to_host(), QC.checked("ring3"), MC.ARRAYS, "2: merge ring3")
+        same(e.stitch_targets(TQ.targets(ring_st), TQ.entries(ring_st), **ring_st["variants"][0]).to_host(), TQ.checked("ring3"), ST.ARRAYS, "3: stitch ring3")
+        pl, sc = scaffold(e, ring_sc, ring_sc["variants"][0])
+        same(sc.to_host(), SQ.checked("ring3"), SC.ARRAYS, "4: scaffold ring3")
+        same(e.merge_ends(MF.targets(chains), **chains["variants"][0]).to_host(), MF.checked("chains"), MC.ARRAYS, "5: merge chains")
+        path = str(tmp_path / "s.fasta")
+        e.write_scaffold_fasta(path, pl, sc)
+        assert open(path, "rb").read() == SC.fasta(SQ.checked("ring3"), ring_sc["seqs"])
+    finally:
+        e.close()
 
 
 def test_a_wave_takes_a_second_end(eng):

@@ -1,6 +1,6 @@
 """The merge stage without a GPU: the two Python statements of the definition (tests/merge_checker.py) agree on the cases of
 tests/merge_cases.py, the outcomes the cases were made for, the planted genome; the refusals of the checker; the library exports the calls
-and the header declares them; the compiler's resource report of merge_kernels.hip and seed_index.hip."""
+and the header declares them; the compiler's resource report of merge_kernels.hip, seed_index.hip and chain_kernels.hip."""
 import ctypes as C
 import os
 import re
@@ -18,9 +18,10 @@ import merge_invariants as MI
 import place_checker as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["k_mg_check", "k_mg_end_lens", "k_mg_ends", "k_mg_overlap", "k_mg_joins", "k_mg_cycle_init", "k_mg_cycle_jump", "k_mg_cycle_drop", "k_mg_rank_init",
-           "k_mg_rank_jump", "k_mg_place", "k_mg_layout", "k_mg_build", "k_mg_fasta_sizes", "k_mg_fasta_write",
-           "k_seed_keys", "k_seed_dir"]                         # (seed_index.hip: the index the placement, the grow and the merge stage build)
+KERNELS = ["k_mg_check", "k_mg_end_lens", "k_mg_ends", "k_mg_overlap", "k_mg_joins", "k_mg_cycle_drop", "k_mg_rank_init", "k_mg_place", "k_mg_layout", "k_mg_build",
+           "k_mg_fasta_sizes", "k_mg_fasta_write",
+           "k_seed_keys", "k_seed_dir",                         # (seed_index.hip: the index the placement, the grow and the merge stage build)
+           "k_ch_cycle_init", "k_ch_cycle_jump", "k_ch_rank_jump"]   # (chain_kernels.hip: the jumps the scaffolder, the merge and the stitch stage share)
 SYMBOLS = ("alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device")
 # (ends_with_overlap, ends_ambiguous, joins, joins_dropped_cycle, merged) of every variant of every case
 OUTCOMES = {"pairings": [(8, 0, 4, 0, 5), (0, 0, 0, 0, 9)], "half_length": [(2, 0, 1, 0, 3)], "max_overlap": [(2, 0, 1, 0, 3)], "partial_word": [(6, 0, 3, 0, 9)],
@@ -168,12 +169,12 @@ def test_library_exports_the_calls_and_the_header_declares_them():
 
 
 def test_new_kernels_resources():
-    """The compiler's resource report of merge_kernels.hip and seed_index.hip: every k_mg_* and k_seed_* is there, no VGPR spill and no scratch in
-    any of them"""
+    """The compiler's resource report of merge_kernels.hip, seed_index.hip and chain_kernels.hip: every k_mg_*, k_seed_* and k_ch_* is there, no
+    VGPR spill and no scratch in any of them"""
     out = os.path.join(os.environ.get("TMPDIR", "/tmp"), "alga_merge_resources_%d.o" % os.getpid())
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     lines = []
-    for name in ("merge_kernels.hip", "seed_index.hip"):
+    for name in ("merge_kernels.hip", "seed_index.hip", "chain_kernels.hip"):
         src = os.path.join(ROOT, "alga_amd", "csrc", name)
         try:
             r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", src, "-o", out, "-Rpass-analysis=kernel-resource-usage"],
@@ -184,7 +185,7 @@ def test_new_kernels_resources():
         lines += r.stderr.splitlines()
     reps = {}
     for i, s in enumerate(lines):
-        m = re.search(r"Function Name: \S*?(k_(?:mg|seed)_[a-z_]+)E", s)
+        m = re.search(r"Function Name: \S*?(k_(?:mg|seed|ch)_[a-z_]+)E", s)
         if not m:
             continue
         rep = {}

@@ -1,6 +1,6 @@
 """The scaffolds without a GPU: the two Python statements of the definition (tests/scaffold_checker.py) agree on the cases of
 tests/scaffold_cases.py, the outcomes the cases were made for, the planted genome; the refusals of the checker; the library exports the
-calls and the header declares them; the compiler's resource report of scaffold_kernels.hip."""
+calls and the header declares them; the compiler's resource report of scaffold_kernels.hip and chain_kernels.hip."""
 import ctypes as C
 import os
 import re
@@ -17,8 +17,9 @@ import scaffold_checker as SC
 import scaffold_invariants as INV
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ["k_sc_check", "k_sc_links", "k_sc_heads", "k_sc_bundle_fill", "k_sc_bundles", "k_sc_second", "k_sc_choice", "k_sc_joins", "k_sc_cycle_init",
-           "k_sc_cycle_jump", "k_sc_cycle_drop", "k_sc_rank_init", "k_sc_rank_jump", "k_sc_place", "k_sc_layout", "k_sc_fasta_sizes", "k_sc_fasta_write"]
+KERNELS = ["k_sc_check", "k_sc_links", "k_sc_heads", "k_sc_bundle_fill", "k_sc_bundles", "k_sc_second", "k_sc_choice", "k_sc_joins", "k_sc_cycle_drop",
+           "k_sc_rank_init", "k_sc_place", "k_sc_layout", "k_sc_fasta_sizes", "k_sc_fasta_write",
+           "k_ch_cycle_init", "k_ch_cycle_jump", "k_ch_rank_jump"]   # (chain_kernels.hip: the jumps the scaffolder, the merge and the stitch stage share)
 SYMBOLS = ("alga_scaffold_default_params", "alga_scaffold_placed_device", "alga_write_scaffold_fasta_device")
 # (links, bundles_supported, ends_ambiguous, joins, joins_dropped_cycle, scaffolds, scaffolds_multi) of every variant of every case
 OUTCOMES = {"two": [(5, 1, 0, 1, 0, 1, 1), (5, 0, 0, 0, 0, 2, 0), (5, 1, 0, 1, 0, 1, 1)],
@@ -198,20 +199,23 @@ def test_library_exports_the_calls_and_the_header_declares_them():
 
 
 def test_new_kernels_resources():
-    """The compiler's resource report of scaffold_kernels.hip: every k_sc_* is there, no VGPR spill and no scratch in any of them"""
-    src = os.path.join(ROOT, "alga_amd", "csrc", "scaffold_kernels.hip")
+    """The compiler's resource report of scaffold_kernels.hip and chain_kernels.hip: every k_sc_* and k_ch_* is there, no VGPR spill and no
+    scratch in any of them"""
     out = os.path.join(os.environ.get("TMPDIR", "/tmp"), "alga_scaffold_resources_%d.o" % os.getpid())
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
-    try:
-        r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", src, "-o", out, "-Rpass-analysis=kernel-resource-usage"],
-                           capture_output=True, text=True, check=True)
-    finally:
-        if os.path.exists(out):
-            os.remove(out)
-    lines = r.stderr.splitlines()
+    lines = []
+    for name in ("scaffold_kernels.hip", "chain_kernels.hip"):
+        src = os.path.join(ROOT, "alga_amd", "csrc", name)
+        try:
+            r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", src, "-o", out, "-Rpass-analysis=kernel-resource-usage"],
+                               capture_output=True, text=True, check=True)
+        finally:
+            if os.path.exists(out):
+                os.remove(out)
+        lines += r.stderr.splitlines()
     reps = {}
     for i, s in enumerate(lines):
-        m = re.search(r"Function Name: \S*?(k_sc_[a-z_]+)E", s)
+        m = re.search(r"Function Name: \S*?(k_(?:sc|ch)_[a-z_]+)E", s)
         if not m:
             continue
         rep = {}
