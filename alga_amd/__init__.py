@@ -8,5 +8,5 @@ torch.distributed only.  There is no CPU fallback: importing works anywhere, com
 from .engine import (Engine, MultiEngine, AlgaError, PrefSufParams, load_library, library_path, pack_reads, derive_params, ingest_files, parse_files,  # noqa: F401
                      EDGE_DTYPE, PolishParams, PolishInfo, PolishedC, Polished, ScaffoldParams, ScaffoldInfo, ScaffoldsC, Scaffolds,
                      BreakParams, BreakInfo, BrokenC, Broken, GrowParams, GrowInfo, GrownC, Grown,
-                     MergeParams, MergeInfo, MergedC, Merged, StitchParams, StitchInfo, StitchedC, Stitched, GappedParams, GappedInfo, GappedC, Gapped,
+                     MergeParams, MergeInfo, MergedC, Merged, ContainParams, ContainInfo, KeptC, Kept, StitchParams, StitchInfo, StitchedC, Stitched, GappedParams, GappedInfo, GappedC, Gapped,
                      IpolishParams, IpolishInfo, IpolishedC, IndelPolished, PairParams, PairInfo, PairCallsC, PairCalls, SamParams)

@@ -812,6 +812,9 @@ int alga_engine_set_option(alga_engine *e, const char *name, int64_t value) {
     } else if (!strcmp(name, "merge_max_blocks")) {
         if (value < 1 || value > 8192) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option merge_max_blocks: 1 .. 8192");
         e->opt_merge_max_blocks = (int) value;
+    } else if (!strcmp(name, "contain_max_blocks")) {
+        if (value < 1 || value > 8192) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option contain_max_blocks: 1 .. 8192");
+        e->opt_contain_max_blocks = (int) value;
     } else if (!strcmp(name, "stitch_max_blocks")) {
         if (value < 1 || value > 8192) return alga_fail(e, ALGA_ERR_INVALID_ARGUMENT, "option stitch_max_blocks: 1 .. 8192");
         e->opt_stitch_max_blocks = (int) value;

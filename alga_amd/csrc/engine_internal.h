@@ -241,6 +241,15 @@ struct alga_engine {
     int         opt_merge_max_blocks = 8192;       // option "merge_max_blocks": the cap of the k_mg_* grids (tests make every grid-stride loop take further passes)
     bool        mg_valid = false;
     uint64_t    mg_targets = 0, mg_merged = 0, mg_columns = 0, mg_longest = 0;   // ... of this many targets, merged contigs and columns; the longest merged contig
+    // contigs contained in another contig dropped (engine_contain.hip).  Workspaces: counters, the padded lengths and their scan, the targets and
+    // their reverse complements in a column space of their own, what k_ct_contain leaves per (c, s), the kept flags and their scan.  The
+    // result, twice, as for the grow (the roots in both buffers of the pointer jumping: the handle names the one the last round wrote)
+    DevBuf      cn_cnt, cn_pad, cn_off, cn_cols, cn_rcols, cn_qmm, cn_qhits, cn_qhost, cn_qpos, cn_keep, cn_keepscan;
+    struct ContainSet { DevBuf host, hostpos, hostorient, mm, hits, state, root[2], rootpos[2], rootorient[2], absorbed, newid, old, len, coloff, begin, words; } cn_set[2];
+    int         cn_cur = 0;                        // the set that holds the result
+    int         opt_contain_max_blocks = 8192;     // option "contain_max_blocks": the cap of the k_ct_* grids but k_ct_contain's and the FASTA kernels' (tests make every grid-stride loop take further passes)
+    bool        cn_valid = false;
+    uint64_t    cn_targets = 0, cn_kept = 0, cn_columns = 0, cn_longest = 0;   // ... of this many targets, kept targets and columns; the longest kept target
     // scaffold joins whose contig ends overlap stitched into one sequence (engine_stitch.hip).  Workspaces of its own: counters, the per-end
     // count, the per-end arrays the merge stage's launchers take (partner, olen, mm, hits, state), begin / len of a placement's targets.  The
     // result, twice, as for the grow

@@ -186,6 +186,7 @@ EXPORTS = ["alga_abi_version", "alga_engine_set_option", "alga_engine_create", "
            "alga_break_default_params", "alga_break_placed_device", "alga_write_broken_fasta_device",
            "alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device",
            "alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device",
+           "alga_contain_default_params", "alga_drop_contained_device", "alga_write_kept_fasta_device",
            "alga_stitch_default_params", "alga_stitch_targets_device", "alga_stitch_scaffolds_device", "alga_write_stitched_fasta_device",
            "alga_gapped_default_params", "alga_place_gapped_device", "alga_write_gapped_tsv_device",
            "alga_ipolish_default_params", "alga_polish_indels_device", "alga_write_ipolished_fasta_device", "alga_write_ipolish_events_tsv_device",
@@ -706,6 +707,59 @@ def merge_tsv(h, tlen):
     return "".join(lines)
 
 
+CONTAIN_CONTAINED, CONTAIN_MINUS, CONTAIN_AMBIGUOUS, CONTAIN_DUPLICATE, CONTAIN_KEPT = 1, 2, 4, 8, 16   # bits of Kept.state
+
+
+class ContainParams(C.Structure):
+    """alga_contain_params"""
+    _fields_ = [(k, C.c_int32) for k in ("k", "max_permille", "max_occ", "flags")] + [("reserved", C.c_int32 * 2)]
+
+
+class ContainInfo(_Info):
+    """alga_contain_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("queries", "index_positions", "seeds", "seeds_over_max_occ", "candidates", "contained", "contained_minus", "duplicates",
+                                          "ambiguous", "hits_saturated", "kept", "bases_removed", "longest_contained", "columns_before", "columns_after",
+                                          "n50_before", "n50_after")] + \
+               [(k, C.c_double) for k in ("ms_index", "ms_contain", "ms_build", "ms_total")]
+
+
+class KeptC(C.Structure):
+    """alga_kept"""
+    _fields_ = [(k, C.c_int64) for k in ("n_targets", "n_kept")] + [("n_columns", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in ("d_host", "d_host_pos", "d_host_orient", "d_mm", "d_hits", "d_state", "d_root", "d_root_pos", "d_root_orient", "d_absorbed", "d_new",
+                                          "d_old", "d_len", "d_col_off", "d_begin", "d_words")]
+
+
+class Kept(_RaggedResult):
+    """Result of Engine.drop_contained: zero-copy torch views of the engine's device memory (valid until the next Engine.drop_contained call on
+    that engine; clone what has to live longer) -- per input target host / host_pos int32, host_orient uint8, mm int32 (the bits of uint32),
+    hits / state uint8, root / root_pos int32, root_orient uint8, absorbed int32 (the bits of uint32), new int32 [n_targets]; old int32
+    [n_kept]; len int32 [n_kept], col_off int32 [n_kept + 1], begin int64 [n_kept], words int32 [(n_columns + 15) / 16 + 2] (the result's own
+    copy of the bases) -- and .info (dict of alga_contain_info)."""
+    KEYS = (("host", "<i4", np.int32, "t"), ("host_pos", "<i4", np.int32, "t"), ("host_orient", "|u1", np.uint8, "t"), ("mm", "<i4", np.uint32, "t"),
+            ("hits", "|u1", np.uint8, "t"), ("state", "|u1", np.uint8, "t"), ("root", "<i4", np.int32, "t"), ("root_pos", "<i4", np.int32, "t"),
+            ("root_orient", "|u1", np.uint8, "t"), ("absorbed", "<i4", np.uint32, "t"), ("new", "<i4", np.int32, "t"), ("old", "<i4", np.int32, "m"),
+            ("len", "<i4", np.int32, "m"), ("col_off", "<i4", np.uint32, "m1"), ("begin", "<i8", np.uint64, "m"), ("words", "<i4", np.uint32, "w"))
+    COUNTS = ("n_targets", "n_kept", "n_columns")
+
+    def _sizes(self):
+        return dict(t=self.n_targets, m=self.n_kept, m1=self.n_kept + 1, w=(self.n_columns + 15) // 16 + 2)
+
+    def contain_tsv(self, tlen=None, host=None):
+        """one line per input target: contig, length, state, new, host, host_pos, host_orient, mm, hits, root, root_pos, root_orient (tabs); tlen:
+        the lengths of the targets of the call (by default read back from them); the text alga_hip --contain_layout= writes"""
+        if tlen is None:
+            tlen = self._source[2].cpu().numpy()
+        return contain_tsv(host if host is not None else self.to_host(), tlen)
+
+
+def contain_tsv(h, tlen):
+    """the layout of a containment result read back (Kept.to_host())"""
+    return "".join("%d\t%d\t%d\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%s\n" % (
+        c, int(tlen[c]), int(h["state"][c]), int(h["new"][c]), int(h["host"][c]), int(h["host_pos"][c]), "-" if h["host_orient"][c] else "+", int(h["mm"][c]),
+        int(h["hits"][c]), int(h["root"][c]), int(h["root_pos"][c]), "-" if h["root_orient"][c] else "+") for c in range(len(h["state"])))
+
+
 STITCH_SELECTED, STITCH_HAS_OVERLAP, STITCH_AMBIGUOUS, STITCH_STITCHED, STITCH_DROPPED_CYCLE = 1, 2, 4, 8, 16   # bits of Stitched.j_state
 
 
@@ -1071,6 +1125,11 @@ def load_library():
     lib.alga_merge_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(MergeParams), C.c_void_p, C.POINTER(MergedC),
                                               C.POINTER(MergeInfo)]
     lib.alga_write_merged_fasta_device.argtypes = [C.c_void_p, C.POINTER(MergedC), C.c_char_p, C.POINTER(GfaInfo)]
+    lib.alga_contain_default_params.argtypes = [C.POINTER(ContainParams)]
+    lib.alga_contain_default_params.restype = None
+    lib.alga_drop_contained_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ContainParams), C.c_void_p, C.POINTER(KeptC),
+                                               C.POINTER(ContainInfo)]
+    lib.alga_write_kept_fasta_device.argtypes = [C.c_void_p, C.POINTER(KeptC), C.c_char_p, C.POINTER(GfaInfo)]
     lib.alga_stitch_default_params.argtypes = [C.POINTER(StitchParams)]
     lib.alga_stitch_default_params.restype = None
     lib.alga_stitch_targets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -2097,6 +2156,26 @@ class Engine:
         """The merged contigs of the LAST Engine.merge_ends call as FASTA (alga_write_merged_fasta_device) -> dict of alga_gfa_info (segments =
         records): `>contig_id=<j>_length=<len>_contigs=<m>` per merged contig."""
         return self._write(self._lib.alga_write_merged_fasta_device, path, merged)
+
+    def drop_contained(self, targets, stream=None, **params):
+        """Contigs contained in another contig dropped (alga_drop_contained_device) -> Kept.  targets = (packed words, begin int64 [T], len int32
+        [T]): ragged sequences as Engine.place_reads takes them, for instance Merged.targets() or the Kept.targets() of the call before.  Host
+        arrays are uploaded first; tensors are used where they are and left untouched.  params: k, max_permille, max_occ (the fields of
+        alga_contain_params; the library's defaults where not given)."""
+        dev = self._dev()
+        twords, tbegin, tlen = _ragged_targets(targets, dev)
+        assert twords.is_contiguous()
+        pp, out, info = ContainParams(), KeptC(), ContainInfo()
+        self._lib.alga_contain_default_params(C.byref(pp))
+        _set_params(pp, params, ("k", "max_permille", "max_occ", "flags", "reserved"), "Engine.drop_contained")
+        self._check(self._lib.alga_drop_contained_device(self._h, C.c_void_p(_ptr(twords) or None), C.c_void_p(_ptr(tbegin) or None), C.c_void_p(_ptr(tlen) or None),
+                                                         int(tlen.shape[0]), C.byref(pp), _stream_arg(stream, dev), C.byref(out), C.byref(info)))
+        return Kept(out, info.as_dict(), self.device, (twords, tbegin, tlen))       # the tensors the targets came from stay alive with the result
+
+    def write_kept_fasta(self, path, kept):
+        """The kept contigs of the LAST Engine.drop_contained call as FASTA (alga_write_kept_fasta_device) -> dict of alga_gfa_info (segments =
+        records): `>contig_id=<j>_length=<len>_absorbed=<m>` per kept contig."""
+        return self._write(self._lib.alga_write_kept_fasta_device, path, kept)
 
     _STITCH_PARAMS = ("max_mismatches", "min_overlap", "max_overlap", "slack", "flags")
 

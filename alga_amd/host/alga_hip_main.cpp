@@ -97,6 +97,13 @@
 // `>contig_id=<j>_length=<len>_contigs=<m>` (alga_write_merged_fasta_device); --merge_layout=PATH: one line `merged rank contig orient start
 // length overlap_after mm` per member, tab separated (both need --merge_ends=1).  One line on stderr gives overlaps / ambiguous ends / joins /
 // bases removed / N50 before -> after.  Without --merge_ends=1 every file is what it was.  None is passed through.
+// --drop_contained=1 (default 0; needs --merge_ends=1): the merged contigs whose whole sequence, or its reverse complement, lies inside a longer
+// one within --contain_max_permille= (10) substitutions per 1000 bases are dropped (alga_drop_contained_device), the reads are placed on the kept
+// contigs instead of the merged ones, and the scaffolds and their layout come from that placement (contig ids there are kept ids).
+// --kept=PATH: the kept contigs, `>contig_id=<j>_length=<len>_absorbed=<m>` (alga_write_kept_fasta_device); --contain_layout=PATH: one line
+// `contig length state new host host_pos host_orient mm hits root root_pos root_orient` per merged contig, tab separated (both need
+// --drop_contained=1).  One line on stderr gives queries / candidates / contained (minus, duplicates) / ambiguous / bases removed / N50 before ->
+// after.  Without --drop_contained=1 every file is what it was.  None is passed through.
 // --stitch=1 (default 0; needs --scaffolds=): the placement the scaffolds would be made from is scaffolded a first time, the joins whose two contig
 // ends overlap are stitched into one sequence (alga_stitch_scaffolds_device: --stitch_min_overlap= (16), --stitch_max_mismatches= (2),
 // --stitch_slack= (2^20); with --polish=1 the bases are the polished ones), the reads are placed again on the stitched contigs, and --scaffolds= and
@@ -151,6 +158,7 @@ static const char *USAGE =
     "         [--grow_ends=N] [--grown=grown.fasta] [--grow_layout=grow.tsv] [--grow_min_anchor=63] [--grow_max_mismatches=2] [--grow_min_cover=3]\n"
     "         [--grow_min_percent=80] [--grow_max=64]\n"
     "         [--merge_ends=0|1] [--merged=merged.fasta] [--merge_layout=merge.tsv] [--merge_min_overlap=42] [--merge_max_mismatches=1]\n"
+    "         [--drop_contained=0|1] [--kept=kept.fasta] [--contain_layout=contain.tsv] [--contain_max_permille=10]\n"
     "         [--stitch=0|1] [--stitched=stitched.fasta] [--stitch_layout=stitch.tsv] [--stitch_min_overlap=16] [--stitch_max_mismatches=2] [--stitch_slack=1048576]\n"
     "         [--gapped=0|1] [--gapped_edits=6] [--gapped_placements=gapped.tsv]\n"
     "         [--polish_indels=0|1] [--polish_max_ins=6] [--ipolished=ipolished.fasta] [--ipolish_events=events.tsv]\n"
@@ -193,6 +201,10 @@ int main(int argc, char **argv) {
     std::string merged_path, merge_layout;
     alga_merge_params mgp;
     alga_merge_default_params(&mgp);
+    int drop_contained = 0;
+    std::string kept_path, contain_layout;
+    alga_contain_params ctp;
+    alga_contain_default_params(&ctp);
     int stitch = 0;
     std::string stitched_path, stitch_layout;
     alga_stitch_params stp;
@@ -262,6 +274,10 @@ int main(int argc, char **argv) {
         else if (opt(a, "--sam_unplaced", v)) sam_unplaced = atoi(v.c_str());
         else if (opt(a, "--sam", v)) sam = v;
         else if (opt(a, "--merged", v)) merged_path = v;
+        else if (opt(a, "--drop_contained", v)) drop_contained = atoi(v.c_str());
+        else if (opt(a, "--kept", v)) kept_path = v;
+        else if (opt(a, "--contain_layout", v)) contain_layout = v;
+        else if (opt(a, "--contain_max_permille", v)) ctp.max_permille = atoi(v.c_str());
         else if (opt(a, "--merge_layout", v)) merge_layout = v;
         else if (opt(a, "--merge_min_overlap", v)) mgp.min_overlap = atoi(v.c_str());
         else if (opt(a, "--merge_max_mismatches", v)) mgp.max_mismatches = atoi(v.c_str());
@@ -338,6 +354,10 @@ int main(int argc, char **argv) {
     if (merge_ends != 0 && merge_ends != 1) { fprintf(stderr, "alga_hip: --merge_ends must be 0 or 1 (got %d)\n", merge_ends); return 2; }
     if (merge_ends && !grow_ends) { fprintf(stderr, "alga_hip: --merge_ends=1 needs --grow_ends >= 1\n"); return 2; }
     if (!merge_ends && (!merged_path.empty() || !merge_layout.empty())) { fprintf(stderr, "alga_hip: --merged= and --merge_layout= need --merge_ends=1\n"); return 2; }
+    if (drop_contained != 0 && drop_contained != 1) { fprintf(stderr, "alga_hip: --drop_contained must be 0 or 1 (got %d)\n", drop_contained); return 2; }
+    if (drop_contained && !merge_ends) { fprintf(stderr, "alga_hip: --drop_contained=1 needs --merge_ends=1\n"); return 2; }
+    if (!drop_contained && (!kept_path.empty() || !contain_layout.empty())) { fprintf(stderr, "alga_hip: --kept= and --contain_layout= need --drop_contained=1\n"); return 2; }
+    if (ctp.max_permille < 0 || ctp.max_permille > 100) { fprintf(stderr, "alga_hip: --contain_max_permille must be in [0, 100]\n"); return 2; }
     if (stitch != 0 && stitch != 1) { fprintf(stderr, "alga_hip: --stitch must be 0 or 1 (got %d)\n", stitch); return 2; }
     if (stitch && scaffolds.empty()) { fprintf(stderr, "alga_hip: --stitch=1 needs --scaffolds=\n"); return 2; }
     if (!stitch && (!stitched_path.empty() || !stitch_layout.empty())) { fprintf(stderr, "alga_hip: --stitched= and --stitch_layout= need --stitch=1\n"); return 2; }
@@ -943,12 +963,56 @@ int main(int argc, char **argv) {
                                     }
                                 if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", merge_layout.c_str()); return 1; }
                             }
-                            // the same reads on the merged contigs (the merge result keeps its own copy of the bases)
-                            if (rc == ALGA_OK) rc = alga_place_reads_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, mg.d_words, mg.d_begin, mg.d_len,
-                                                                            (int32_t) mg.n_merged, &pp, nullptr, &pl3, &pi3);
+                            const uint32_t *t_words = mg.d_words;
+                            const uint64_t *t_begin = mg.d_begin;
+                            const int32_t *t_len = mg.d_len;
+                            int32_t t_n = (int32_t) mg.n_merged;
+                            const char *t_what = "merged";
+                            alga_kept kp{};
+                            if (rc == ALGA_OK && drop_contained) {            // the merged contigs that lie inside a longer one are dropped, and the reads are placed on the kept ones
+                                alga_contain_info ci;
+                                rc = alga_drop_contained_device(engine, mg.d_words, mg.d_begin, mg.d_len, (int32_t) mg.n_merged, &ctp, nullptr, &kp, &ci);
+                                if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot drop the contained contigs: %s (status %d)\n", alga_last_error(engine), rc); return 1; }
+                                fprintf(stderr, "Contained contigs dropped: %llu queries, %llu candidates, %llu contained (%llu minus, %llu duplicates), %llu ambiguous, %llu bases "
+                                        "removed, N50 %llu -> %llu; %llu kept of %llu contigs, %llu seeds (%llu over max_occ), longest contained %llu, %llu -> %llu columns; device "
+                                        "ms: index %.3f contain %.3f build %.3f, call %.1f ms wall\n", (unsigned long long) ci.queries, (unsigned long long) ci.candidates,
+                                        (unsigned long long) ci.contained, (unsigned long long) ci.contained_minus, (unsigned long long) ci.duplicates, (unsigned long long) ci.ambiguous,
+                                        (unsigned long long) ci.bases_removed, (unsigned long long) ci.n50_before, (unsigned long long) ci.n50_after, (unsigned long long) ci.kept,
+                                        (unsigned long long) kp.n_targets, (unsigned long long) ci.seeds, (unsigned long long) ci.seeds_over_max_occ,
+                                        (unsigned long long) ci.longest_contained, (unsigned long long) ci.columns_before, (unsigned long long) ci.columns_after, ci.ms_index,
+                                        ci.ms_contain, ci.ms_build, ci.ms_total);
+                                if (!kept_path.empty()) {
+                                    alga_gfa_info kgi;
+                                    rc = alga_write_kept_fasta_device(engine, &kp, kept_path.c_str(), &kgi);
+                                    if (rc != ALGA_OK) { fprintf(stderr, "alga_amd: cannot write %s: %s (status %d)\n", kept_path.c_str(), alga_last_error(engine), rc); return 1; }
+                                    fprintf(stderr, "Kept contigs written -> %s: %llu records, %llu bytes\n", kept_path.c_str(), (unsigned long long) kgi.segments,
+                                            (unsigned long long) kgi.bytes);
+                                }
+                                if (!contain_layout.empty()) {                // not a hot path: the host formats from the arrays that came back
+                                    const size_t nt = (size_t) kp.n_targets;
+                                    std::vector<int32_t> tlen(nt), nw(nt), host(nt), hpos(nt), root(nt), rpos(nt);
+                                    std::vector<uint32_t> mm(nt);
+                                    std::vector<uint8_t> state(nt), hor(nt), hits(nt), ror(nt);
+                                    const struct { void *dst; const void *src; size_t bytes; } copies[] = {
+                                        {tlen.data(), mg.d_len, nt * 4}, {nw.data(), kp.d_new, nt * 4}, {host.data(), kp.d_host, nt * 4}, {hpos.data(), kp.d_host_pos, nt * 4},
+                                        {root.data(), kp.d_root, nt * 4}, {rpos.data(), kp.d_root_pos, nt * 4}, {mm.data(), kp.d_mm, nt * 4}, {state.data(), kp.d_state, nt},
+                                        {hor.data(), kp.d_host_orient, nt}, {hits.data(), kp.d_hits, nt}, {ror.data(), kp.d_root_orient, nt}};
+                                    for (const auto &cp : copies) if (rc == ALGA_OK && nt) rc = alga_copy_to_host(engine, cp.dst, cp.src, cp.bytes);
+                                    FILE *f = rc == ALGA_OK ? fopen(contain_layout.c_str(), "w") : nullptr;
+                                    if (rc == ALGA_OK && !f) { fprintf(stderr, "alga_hip: cannot write %s\n", contain_layout.c_str()); return 1; }
+                                    for (size_t c = 0; f && c < nt; c++)
+                                        fprintf(f, "%zu\t%d\t%d\t%d\t%d\t%d\t%c\t%u\t%d\t%d\t%d\t%c\n", c, tlen[c], (int) state[c], nw[c], host[c], hpos[c], hor[c] ? '-' : '+', mm[c],
+                                                (int) hits[c], root[c], rpos[c], ror[c] ? '-' : '+');
+                                    if (f && fclose(f) != 0) { fprintf(stderr, "alga_hip: cannot write %s\n", contain_layout.c_str()); return 1; }
+                                }
+                                t_words = kp.d_words; t_begin = kp.d_begin; t_len = kp.d_len; t_n = (int32_t) kp.n_kept; t_what = "kept";
+                            }
+                            // the same reads on the merged contigs, or on the kept ones (the result keeps its own copy of the bases)
+                            if (rc == ALGA_OK) rc = alga_place_reads_device(engine, &pnd, pr.paired ? (const uint8_t *) d_po : nullptr, t_words, t_begin, t_len, t_n, &pp, nullptr,
+                                                                            &pl3, &pi3);
                             if (rc == ALGA_OK) {
-                                fprintf(stderr, "Reads placed on the merged contigs: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
-                                        "median insert %lld; call %.1f ms wall\n", (unsigned long long) pi3.reads, (unsigned long long) pi3.placed, (unsigned long long) pi3.unique,
+                                fprintf(stderr, "Reads placed on the %s contigs: %llu reads, %llu placed (%llu unique, %llu multi), %llu unplaced; %llu proper pairs of %llu, "
+                                        "median insert %lld; call %.1f ms wall\n", t_what, (unsigned long long) pi3.reads, (unsigned long long) pi3.placed, (unsigned long long) pi3.unique,
                                         (unsigned long long) pi3.multi, (unsigned long long) pi3.unplaced, (unsigned long long) pi3.pairs_proper, (unsigned long long) pi3.pairs,
                                         (long long) pi3.insert_median, pi3.ms_total);
                                 spl = &pl3; spi = &pi3; spol = nullptr;

@@ -236,6 +236,8 @@ int         alga_engine_device_name(const alga_engine *e, char *buf, size_t bufl
  *                                not fit is done by grid or wave stride (tests lower it to make small inputs stride)
  *   "stitch_max_blocks"          1..8192 (default 8192): the largest grid of the kernels of alga_stitch_targets_device, k_st_overlap's (one wave per
  *                                entry) included; what does not fit is done by grid stride (tests lower it to make small inputs stride)
+ *   "contain_max_blocks"         1..8192 (default 8192): the largest grid of the kernels of alga_drop_contained_device but k_ct_contain's (one wave per
+ *                                query) and the FASTA kernels'; what does not fit is done by grid stride (tests lower it to make small inputs stride)
  *   "shard_bucket_max"           1..4096 (default 4096): run descriptors of ONE bucket the bucket-sharded join (alga_shard_join_device) takes; a
  *                                bucket with more makes the call answer ALGA_ERR_UNSUPPORTED (tests lower it to exercise that)
  *   "own_sort"                   default 1: the (key, id) sort of the index build and the descriptor sort of the bucket-sharded form are the engine's own
@@ -1708,6 +1710,97 @@ void alga_merge_default_params(alga_merge_params *p);
 int  alga_merge_targets_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
                                const alga_merge_params *p, void *hip_stream, alga_merged *out, alga_merge_info *info /* may be NULL */);
 int  alga_write_merged_fasta_device(alga_engine *e, const alga_merged *merged, const char *path, alga_gfa_info *info /* may be NULL */);
+
+/* ---- contigs contained in another contig dropped (alga_amd/csrc/contain_kernels.hip, engine_contain.hip) ---------------------------------------
+ * Every stage behind the graph joins contigs or cuts them; none removes a contig that adds nothing: an exact duplicate, a haplotype bubble the
+ * parallel-path pass kept, a repeat copy that became a contig of its own, a fragment the grow rounds overtook.  The merge stage cannot see it
+ * (its windows are W_x <= n / 2: an overlap never contains a whole target).  Such a contig inflates the FASTA, and every read on the doubled
+ * stretch is placed twice: PLACED but not UNIQUE, so it votes in no polish, makes no link and spans nothing.  Here every target is a query: a
+ * target whose whole sequence, or its reverse complement, lies inside a longer target within a few substitutions is dropped, and the kept
+ * targets come out as a new target set with its own copy of the bases.  No reads, no placement, nothing of the engine's state but the stage's
+ * own result.  Integers only, free of any order (thread, atomics, sort); tests/contain_checker.py states the rule twice in Python and the
+ * device result equals it array for array.  ... -> grow -> merge -> drop contained -> place on the kept contigs -> scaffold.
+ *
+ * Inputs: a ragged target set as alga_place_reads_device takes it (d_words, d_begin uint64 base index, any residue mod 16, d_len int32,
+ * n_targets = T; a negative length answers ALGA_ERR_INVALID_ARGUMENT, found on the device before anything of the result is written; a column
+ * sum above 2^32 - 2, also of the lengths rounded up to 16, or more than 2^30 targets answers ALGA_ERR_CAPACITY), and alga_contain_params: k
+ * 8 .. 31 (default 21), max_permille 0 .. 100 (10), max_occ 1 .. 65535 (256), flags 0, reserved 0; anything else answers
+ * ALGA_ERR_INVALID_ARGUMENT.
+ *
+ *   1. Queries.  Target c of n bases has two query strings: Q_c^0 = c and Q_c^1, its reverse complement.  M(n) = floor(n * max_permille /
+ *      1000) in 64-bit arithmetic.
+ *   2. Index.  Position q of target t is indexed for 0 <= q <= len[t] - k, forward strands only; no k-mer spans two targets.  occ(v) = the
+ *      number of indexed positions over all targets whose k-mer is v.
+ *   3. Containers.  (h, p, s) is a container of c iff h != c; len[h] > n, or len[h] == n and h < c; 0 <= p and p + n <= len[h]; mm, the
+ *      Hamming distance between Q_c^s and h[p .. p + n), is <= M(n); some seed j < S = min(floor(n / k), 64) of Q_c^s (bases jk .. jk + k - 1)
+ *      is USABLE (1 <= occ <= max_occ) and equals h[p + jk ..) exactly.  The seed condition is part of the rule, as in merge.  A target with
+ *      n < k has no container.  (len descending, id ascending) is a strict order: containers form no cycle, and the first target of that
+ *      order in any group of near-duplicates is never contained.
+ *   4. Per target.  hits[c] = the number of distinct (h, p, s), saturated at 255; best = the smallest (mm, h, p, s).  d_host[c] = best.h (-1
+ *      without a container), d_host_pos = best.p, d_host_orient = best.s, d_mm (uint32), d_hits (uint8), d_state: ALGA_CONTAIN_CONTAINED,
+ *      ALGA_CONTAIN_MINUS (best.s == 1), ALGA_CONTAIN_AMBIGUOUS (hits > 1), ALGA_CONTAIN_DUPLICATE (len[host] == n), ALGA_CONTAIN_KEPT.  A
+ *      target is KEPT iff n > 0 and it has no container.  A target of length 0 is neither kept nor contained (state 0, new id -1).
+ *   5. Roots.  Following d_host from c ends at a kept target d_root[c]; a kept target is its own root at position 0 with orientation 0; a
+ *      target of length 0 has d_root -1.  Position and orientation compose: let c lie in h at (p, s) and h in g at (p', s'); with s' = 0, c
+ *      lies in g at p' + p with orientation s; with s' = 1, at p' + len[h] - p - n with orientation s xor 1.  d_root_pos and d_root_orient
+ *      hold the result.  The Hamming distance against the ROOT's bases is NOT bounded by M: every step of the walk may add its own
+ *      mismatches.  d_absorbed[r] (per input target) = the number of contained targets whose root is r.
+ *   6. Result (alga_kept; engine-owned, valid until the next alga_drop_contained_device call on `e`: no other call invalidates it; kept
+ *      twice and swapped at the end of a call, so a refused or failed call leaves the earlier result valid and a call may take its targets
+ *      from the result before).  Kept targets are numbered by ascending old id: d_new[c] (T; -1 where the target is not kept), d_old[j]
+ *      (n_kept).  d_len [n_kept], d_col_off [n_kept + 1], d_begin [n_kept] (= col_off), d_words: the result's OWN copy in column space (the
+ *      polish's layout, (n_columns + 15) / 16 + 2 words, the bits past n_columns zero).  (d_words, d_begin, d_len, n_kept) is a target set as
+ *      alga_place_reads_device takes it.
+ *   7. Counters (alga_contain_info): queries (targets with n >= k), index_positions, seeds (S of every (c, s): twice per query),
+ *      seeds_over_max_occ (of those), candidates (distinct (c, h, p, s) that pass item 3 except for the Hamming bound), contained,
+ *      contained_minus, duplicates, ambiguous, hits_saturated (all four over the contained targets), kept, bases_removed (the bases of the
+ *      contained targets), longest_contained, columns_before, columns_after; n50_before, n50_after (the scaffold's N50, on the host from
+ *      lengths read back only when `info` is given); ms_index (check, column arrays, keys, sort, directory), ms_contain (k_ct_contain),
+ *      ms_build (decision, roots, scans, build) (HIP events), ms_total (wall).
+ * Read-backs: the refusal flag with the column sums and the indexed positions (the column arrays, the sort and the directory are sized by
+ * them); the contained and kept targets and their columns (the jumps are skipped where nothing is contained, d_words is allocated at its
+ * size); the lengths for the N50s.  The seed index is built in the engine's one index workspace (option "place_dir_bits" as for the
+ * placement).
+ *
+ * alga_write_kept_fasta_device: one record per kept target, in new-id order, `>contig_id=<j>_length=<len>_absorbed=<m>`.  `kept` must be the
+ * engine's current containment result.  ABI stays 7: the calls add. */
+#define ALGA_CONTAIN_CONTAINED 1
+#define ALGA_CONTAIN_MINUS     2
+#define ALGA_CONTAIN_AMBIGUOUS 4
+#define ALGA_CONTAIN_DUPLICATE 8
+#define ALGA_CONTAIN_KEPT      16
+typedef struct {
+    int32_t k, max_permille, max_occ, flags;
+    int32_t reserved[2];             /* 0                                                                                             */
+} alga_contain_params;
+typedef struct {
+    int64_t         n_targets, n_kept;
+    uint64_t        n_columns;       /* of the kept targets: d_col_off[n_kept]                                                        */
+    const int32_t  *d_host, *d_host_pos;  /* n_targets                                                                                */
+    const uint8_t  *d_host_orient;
+    const uint32_t *d_mm;
+    const uint8_t  *d_hits, *d_state;
+    const int32_t  *d_root, *d_root_pos;
+    const uint8_t  *d_root_orient;
+    const uint32_t *d_absorbed;
+    const int32_t  *d_new;
+    const int32_t  *d_old;           /* n_kept                                                                                        */
+    const int32_t  *d_len;           /* n_kept                                                                                        */
+    const uint32_t *d_col_off;       /* n_kept + 1                                                                                    */
+    const uint64_t *d_begin;         /* n_kept                                                                                        */
+    const uint32_t *d_words;         /* (n_columns + 15) / 16 + 2                                                                     */
+} alga_kept;
+typedef struct {
+    uint64_t queries, index_positions, seeds, seeds_over_max_occ, candidates, contained, contained_minus, duplicates, ambiguous, hits_saturated, kept, bases_removed,
+             longest_contained, columns_before, columns_after;
+    uint64_t n50_before, n50_after;
+    double   ms_index, ms_contain, ms_build;   /* device time (HIP events)                                                            */
+    double   ms_total;               /* wall time of the call                                                                         */
+} alga_contain_info;
+void alga_contain_default_params(alga_contain_params *p);
+int  alga_drop_contained_device(alga_engine *e, const uint32_t *d_words, const uint64_t *d_begin, const int32_t *d_len, int32_t n_targets,
+                                const alga_contain_params *p, void *hip_stream, alga_kept *out, alga_contain_info *info /* may be NULL */);
+int  alga_write_kept_fasta_device(alga_engine *e, const alga_kept *kept, const char *path, alga_gfa_info *info /* may be NULL */);
 
 /* ---- scaffold joins whose contig ends overlap stitched into one sequence (alga_amd/csrc/stitch_kernels.hip, engine_stitch.hip) ---------------
  * The scaffolder bridges two contigs with max(gap, min_gap) Ns, also where the gap estimate is negative and the two ends share bases.  The
