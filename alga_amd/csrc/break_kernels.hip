@@ -22,7 +22,7 @@
 #include <algorithm>
 
 #include "break_kernels.h"
-#include "seed_device.h"
+#include "packed_device.h"
 #include "text_record.h"
 
 namespace alga {
@@ -232,57 +232,51 @@ __global__ void __launch_bounds__(BR_BLOCK) k_br_fasta_write(BrFasta f, const un
     text_write_body<BrRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned br_grid(uint64_t items, uint64_t cap = 8192) {
-    const uint64_t g = (items + BR_BLOCK - 1) / BR_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_br_check(const BrReads &r, const BrTargets &t, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_br_check, dim3(br_grid(2 * r.R, 4096)), dim3(BR_BLOCK), 0, s, r, t, counters);
+    hipLaunchKernelGGL(k_br_check, dim3(stage_grid(2 * r.R, BR_BLOCK, 4096)), dim3(BR_BLOCK), 0, s, r, t, counters);
 }
 
 void launch_br_pairs(const BrReads &r, const BrTargets &t, int32_t max_insert, int32_t inset, uint32_t *diff, unsigned long long *counters, hipStream_t s) {
-    if (r.R && r.pair_off && t.T) hipLaunchKernelGGL(k_br_pairs, dim3(br_grid(r.R)), dim3(BR_BLOCK), 0, s, r, t, max_insert, inset, diff, counters);
+    if (r.R && r.pair_off && t.T) hipLaunchKernelGGL(k_br_pairs, dim3(stage_grid(r.R, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, r, t, max_insert, inset, diff, counters);
 }
 
 void launch_br_flags(const BrTargets &t, const uint32_t *span, uint32_t min_span, uint32_t margin, uint32_t *starts, uint8_t *marks, unsigned long long *counters,
                      hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_br_flags, dim3(br_grid(t.columns)), dim3(BR_BLOCK), 0, s, t, span, min_span, margin, starts, marks, counters);
+    if (t.columns) hipLaunchKernelGGL(k_br_flags, dim3(stage_grid(t.columns, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, t, span, min_span, margin, starts, marks, counters);
 }
 
 void launch_br_runs(const BrTargets &t, const uint32_t *run_pos, const uint8_t *marks, uint64_t n_runs, uint32_t *run_first, uint32_t *run_last, hipStream_t s) {
-    if (t.columns && n_runs) hipLaunchKernelGGL(k_br_runs, dim3(br_grid(t.columns)), dim3(BR_BLOCK), 0, s, t, run_pos, marks, n_runs, run_first, run_last);
+    if (t.columns && n_runs) hipLaunchKernelGGL(k_br_runs, dim3(stage_grid(t.columns, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, t, run_pos, marks, n_runs, run_first, run_last);
 }
 
 void launch_br_closed(const uint32_t *run_first, const uint32_t *run_last, const uint8_t *marks, uint64_t n_runs, uint32_t *closed, unsigned long long *counters,
                       hipStream_t s) {
-    if (n_runs) hipLaunchKernelGGL(k_br_closed, dim3(br_grid(n_runs + 1)), dim3(BR_BLOCK), 0, s, run_first, run_last, marks, n_runs, closed, counters);
+    if (n_runs) hipLaunchKernelGGL(k_br_closed, dim3(stage_grid(n_runs + 1, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, run_first, run_last, marks, n_runs, closed, counters);
 }
 
 void launch_br_cuts(const BrTargets &t, const uint32_t *run_first, const uint32_t *run_last, const uint32_t *closed, const uint32_t *cut_pos, uint64_t n_runs, const BrCuts &c,
                     hipStream_t s) {
-    if (n_runs && c.n) hipLaunchKernelGGL(k_br_cuts, dim3(br_grid(n_runs)), dim3(BR_BLOCK), 0, s, t, run_first, run_last, closed, cut_pos, n_runs, c);
+    if (n_runs && c.n) hipLaunchKernelGGL(k_br_cuts, dim3(stage_grid(n_runs, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, t, run_first, run_last, closed, cut_pos, n_runs, c);
 }
 
 void launch_br_pieces(const BrTargets &t, const BrCuts &c, const BrPieces &p, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_br_pieces, dim3(br_grid((uint64_t) t.T + c.n + 1)), dim3(BR_BLOCK), 0, s, t, c, p, counters);
+    hipLaunchKernelGGL(k_br_pieces, dim3(stage_grid((uint64_t) t.T + c.n + 1, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, t, c, p, counters);
 }
 
 void launch_br_copy(const uint32_t *src, uint64_t columns, uint32_t *dst, hipStream_t s) {
     const uint64_t n_words = ((columns + 15) >> 4) + 2;
-    hipLaunchKernelGGL(k_br_copy, dim3(br_grid(n_words)), dim3(BR_BLOCK), 0, s, src, columns, n_words, dst);
+    hipLaunchKernelGGL(k_br_copy, dim3(stage_grid(n_words, BR_BLOCK, 8192)), dim3(BR_BLOCK), 0, s, src, columns, n_words, dst);
 }
 
 void launch_br_fasta_sizes(const BrFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_br_fasta_sizes, dim3((unsigned) ((f.n + BR_BLOCK - 1) / BR_BLOCK)), dim3(BR_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_br_fasta_sizes, dim3(text_sizes_blocks(f.n, BR_BLOCK)), dim3(BR_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_br_fasta_write(const BrFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + BR_WAVES - 1) / BR_WAVES;
-    hipLaunchKernelGGL(k_br_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(BR_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_br_fasta_write, dim3(text_write_blocks(i0, i1, BR_WAVES)), dim3(BR_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

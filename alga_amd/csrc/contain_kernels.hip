@@ -22,7 +22,7 @@
 //   k_ct_fasta_sizes / k_ct_fasta_write   one record per kept target, one wave per record
 // The kernels carry the prefix k_ct_ inside this file's unnamed namespace (contig_kernels.hip has kernels of that prefix in its own); what the
 // host sees of this stage is named Cn / CN_ / launch_cn_ / cn_, apart from the contig stage's Ct / CT_ / launch_ct_ / ct_.
-// No LDS.  Block 256 and the grid caps are picked, not tuned; CnTargets::max_blocks lowers the cap of every grid that goes through cn_grid
+// No LDS.  Block 256 and the grid caps are picked, not tuned; CnTargets::max_blocks lowers the cap of every grid that goes through stage_grid
 // (option "contain_max_blocks": a knob of the tests, which make every grid-stride loop here take further passes).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -241,22 +241,8 @@ __global__ void __launch_bounds__(CN_BLOCK) k_ct_number(CnTargets t, const uint3
 // (col_off is the scan of the kept lengths, columns its total; every kept target has a length)
 __global__ void __launch_bounds__(CN_BLOCK) k_ct_build(CnTargets t, const int32_t *__restrict__ d_old, const uint32_t *__restrict__ col_off, uint32_t n_kept, uint64_t columns,
                                                        uint32_t *__restrict__ words, unsigned long long *__restrict__ begin) {
-    const uint64_t n_words = ((columns + 15) >> 4) + 2, step = (uint64_t) gridDim.x * CN_BLOCK;
-    for (uint64_t i = (uint64_t) blockIdx.x * CN_BLOCK + threadIdx.x; i < n_kept; i += step) begin[i] = col_off[i];
-    for (uint64_t w = (uint64_t) blockIdx.x * CN_BLOCK + threadIdx.x; w < n_words; w += step) {
-        const uint64_t g0 = w << 4;
-        uint32_t v = 0;
-        if (g0 < columns) {
-            uint32_t j = item_of(col_off, n_kept, (uint32_t) g0);
-            for (int b = 0; b < 16; b++) {
-                const uint64_t gg = g0 + (uint64_t) b;
-                if (gg >= columns) break;
-                while ((uint64_t) col_off[j + 1] <= gg) j++;                 // (gg < columns = col_off[n_kept]: ends at a kept target)
-                v |= base_at(t.words, t.begin[d_old[j]] + (gg - col_off[j])) << (2 * b);
-            }
-        }
-        words[w] = v;
-    }
+    for (uint64_t i = (uint64_t) blockIdx.x * CN_BLOCK + threadIdx.x; i < n_kept; i += (uint64_t) gridDim.x * CN_BLOCK) begin[i] = col_off[i];
+    packed_words_body<CN_BLOCK>(col_off, n_kept, columns, ((columns + 15) >> 4) + 2, words, [&](uint32_t j, uint32_t q) { return base_at(t.words, t.begin[d_old[j]] + q); });
 }
 
 // ---- FASTA of the kept contigs ---------------------------------------------------------------------------------------------------------
@@ -280,19 +266,14 @@ __global__ void __launch_bounds__(CN_BLOCK) k_ct_fasta_write(CnFasta f, const un
     text_write_body<CnRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned cn_grid(uint64_t items, uint64_t cap) {                  // cap: CnTargets::max_blocks, 8192 unless a test lowers it
-    const uint64_t g = (items + CN_BLOCK - 1) / CN_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_cn_check(const CnTargets &t, int32_t k, uint32_t *pad, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_ct_check, dim3(cn_grid((uint64_t) t.T + 1, std::min<uint64_t>(4096, t.max_blocks))), dim3(CN_BLOCK), 0, s, t, k, pad, counters);
+    hipLaunchKernelGGL(k_ct_check, dim3(stage_grid((uint64_t) t.T + 1, CN_BLOCK, std::min<uint64_t>(4096, t.max_blocks))), dim3(CN_BLOCK), 0, s, t, k, pad, counters);
 }
 
 void launch_cn_cols(const CnTargets &t, const CnSpace &sp, uint32_t *cols, uint32_t *rcols, hipStream_t s) {
-    if (sp.columns) hipLaunchKernelGGL(k_ct_cols, dim3(cn_grid(sp.columns >> 4, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, sp, cols, rcols);
+    if (sp.columns) hipLaunchKernelGGL(k_ct_cols, dim3(stage_grid(sp.columns >> 4, CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, sp, cols, rcols);
 }
 
 void launch_cn_contain(const CnSpace &sp, const SeedIndex &x, int32_t k, int32_t max_permille, int32_t max_occ, const CnQueryOut &q, int blocks, unsigned long long *counters,
@@ -301,39 +282,38 @@ void launch_cn_contain(const CnSpace &sp, const SeedIndex &x, int32_t k, int32_t
 }
 
 void launch_cn_decide(const CnTargets &t, const CnQueryOut &q, const CnOut &o, uint32_t *keep, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_ct_decide, dim3(cn_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, q, o, keep, counters);
+    hipLaunchKernelGGL(k_ct_decide, dim3(stage_grid((uint64_t) t.T + 1, CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, q, o, keep, counters);
 }
 
 void launch_cn_root_init(const CnTargets &t, const CnOut &o, const CnRoots &a, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_ct_root_init, dim3(cn_grid(t.T, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, o, a);
+    if (t.T) hipLaunchKernelGGL(k_ct_root_init, dim3(stage_grid(t.T, CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, o, a);
 }
 
 void launch_cn_root_jump(const CnTargets &t, const CnRoots &a, const CnRoots &b, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_ct_root_jump, dim3(cn_grid(t.T, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, a, b);
+    if (t.T) hipLaunchKernelGGL(k_ct_root_jump, dim3(stage_grid(t.T, CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, a, b);
 }
 
 void launch_cn_absorbed(const CnTargets &t, const CnOut &o, const CnRoots &r, uint32_t *absorbed, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_ct_absorbed, dim3(cn_grid(t.T, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, o, r, absorbed);
+    if (t.T) hipLaunchKernelGGL(k_ct_absorbed, dim3(stage_grid(t.T, CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, o, r, absorbed);
 }
 
 void launch_cn_number(const CnTargets &t, const uint32_t *keep, const uint32_t *keep_scan, int32_t *d_new, int32_t *d_old, int32_t *klen, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_ct_number, dim3(cn_grid(t.T, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, keep, keep_scan, d_new, d_old, klen);
+    if (t.T) hipLaunchKernelGGL(k_ct_number, dim3(stage_grid(t.T, CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, keep, keep_scan, d_new, d_old, klen);
 }
 
 void launch_cn_build(const CnTargets &t, const int32_t *d_old, const uint32_t *col_off, uint32_t n_kept, uint64_t columns, uint32_t *words, unsigned long long *begin,
                      hipStream_t s) {
     const uint64_t n_words = ((columns + 15) >> 4) + 2;
-    hipLaunchKernelGGL(k_ct_build, dim3(cn_grid(std::max<uint64_t>(n_words, n_kept), t.max_blocks)), dim3(CN_BLOCK), 0, s, t, d_old, col_off, n_kept, columns, words, begin);
+    hipLaunchKernelGGL(k_ct_build, dim3(stage_grid(std::max<uint64_t>(n_words, n_kept), CN_BLOCK, t.max_blocks)), dim3(CN_BLOCK), 0, s, t, d_old, col_off, n_kept, columns, words, begin);
 }
 
 void launch_cn_fasta_sizes(const CnFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_ct_fasta_sizes, dim3((unsigned) ((f.n + CN_BLOCK - 1) / CN_BLOCK)), dim3(CN_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_ct_fasta_sizes, dim3(text_sizes_blocks(f.n, CN_BLOCK)), dim3(CN_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_cn_fasta_write(const CnFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + CN_WAVES - 1) / CN_WAVES;
-    hipLaunchKernelGGL(k_ct_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(CN_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_ct_fasta_write, dim3(text_write_blocks(i0, i1, CN_WAVES)), dim3(CN_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "final_kernels.h"
+#include "packed_device.h"
 #include "text_record.h"
 
 namespace alga {
@@ -263,20 +264,15 @@ __global__ void __launch_bounds__(FC_BLOCK) k_fc_fasta_write(FcFasta f, const un
     text_write_body<FcRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned fc_grid(uint64_t items, uint64_t cap = 1u << 20) {
-    const uint64_t g = (items + FC_BLOCK - 1) / FC_BLOCK;
-    return (unsigned) (g < cap ? g : cap);
-}
-
 }  // namespace
 
 void launch_fc_len_check(const int32_t *len, uint64_t n, unsigned long long *counters, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_fc_len_check, dim3(fc_grid(n, 4096)), dim3(FC_BLOCK), 0, s, len, n, counters);
+    if (n) hipLaunchKernelGGL(k_fc_len_check, dim3(stage_grid(n, FC_BLOCK, 4096)), dim3(FC_BLOCK), 0, s, len, n, counters);
 }
 
 void launch_fc_gather(const uint32_t *words, const unsigned long long *begin, const int32_t *len, uint64_t n, int32_t stride, uint32_t *rows, int32_t *rlen,
                       hipStream_t s) {
-    if (n && stride > 0) hipLaunchKernelGGL(k_fc_gather, dim3(fc_grid(n * (uint64_t) stride)), dim3(FC_BLOCK), 0, s, words, begin, len, n, stride, rows, rlen);
+    if (n && stride > 0) hipLaunchKernelGGL(k_fc_gather, dim3(stage_grid(n * (uint64_t) stride, FC_BLOCK, 1u << 20)), dim3(FC_BLOCK), 0, s, words, begin, len, n, stride, rows, rlen);
 }
 
 void launch_fc_rank_keys(const int32_t *cons_len, uint32_t P, uint32_t *keys, hipStream_t s) {
@@ -307,13 +303,12 @@ void launch_fc_apply_trim(const FcCfg &c, const int32_t *trim_by_id, uint32_t n_
 }
 
 void launch_fc_fasta_sizes(const FcFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_fc_fasta_sizes, dim3((unsigned) ((f.n + FC_BLOCK - 1) / FC_BLOCK)), dim3(FC_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_fc_fasta_sizes, dim3(text_sizes_blocks(f.n, FC_BLOCK)), dim3(FC_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_fc_fasta_write(const FcFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + FC_BLOCK / 64 - 1) / (FC_BLOCK / 64);
-    hipLaunchKernelGGL(k_fc_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(FC_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_fc_fasta_write, dim3(text_write_blocks(i0, i1, FC_BLOCK / 64)), dim3(FC_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -392,23 +392,18 @@ __global__ void __launch_bounds__(GP_BLOCK) k_gp_tsv_write(GpTsv f, const unsign
     text_write_body<GpRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned gp_grid(uint64_t items, uint64_t cap = 1u << 16) {
-    const uint64_t g = (items + GP_BLOCK - 1) / GP_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_gp_target_check(const int32_t *tlen, const uint32_t *col_off, uint64_t T, uint64_t columns, int32_t k, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gp_target_check, dim3(gp_grid(T, 4096)), dim3(GP_BLOCK), 0, s, tlen, col_off, T, columns, k, counters);
+    hipLaunchKernelGGL(k_gp_target_check, dim3(stage_grid(T, GP_BLOCK, 4096)), dim3(GP_BLOCK), 0, s, tlen, col_off, T, columns, k, counters);
 }
 
 void launch_gp_flag(const SeedReads &r, const uint8_t *pl_state, int32_t k, uint32_t *flag, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gp_flag, dim3(gp_grid(r.R + 1, 8192)), dim3(GP_BLOCK), 0, s, r, pl_state, k, flag, counters);
+    hipLaunchKernelGGL(k_gp_flag, dim3(stage_grid(r.R + 1, GP_BLOCK, 8192)), dim3(GP_BLOCK), 0, s, r, pl_state, k, flag, counters);
 }
 
 void launch_gp_scatter(const uint32_t *flag, const uint32_t *pos, uint64_t R, uint32_t *list, hipStream_t s) {
-    if (R) hipLaunchKernelGGL(k_gp_scatter, dim3(gp_grid(R, 8192)), dim3(GP_BLOCK), 0, s, flag, pos, R, list);
+    if (R) hipLaunchKernelGGL(k_gp_scatter, dim3(stage_grid(R, GP_BLOCK, 8192)), dim3(GP_BLOCK), 0, s, flag, pos, R, list);
 }
 
 void launch_gp_score(const SeedReads &r, const SeedSpace &t, const SeedIndex &x, int32_t k, int32_t E, int32_t max_occ, const uint32_t *list, uint64_t n_list, const GpOut &o,
@@ -424,25 +419,24 @@ void launch_gp_trace(const SeedReads &r, const SeedSpace &t, int32_t k, int32_t 
 }
 
 void launch_gp_cigar(const uint32_t *list, uint64_t n_list, const uint32_t *runs, const uint32_t *cigar_off, uint32_t *cigar, hipStream_t s) {
-    if (n_list) hipLaunchKernelGGL(k_gp_cigar, dim3(gp_grid(n_list * GP_MAX_RUNS, 8192)), dim3(GP_BLOCK), 0, s, list, n_list, runs, cigar_off, cigar);
+    if (n_list) hipLaunchKernelGGL(k_gp_cigar, dim3(stage_grid(n_list * GP_MAX_RUNS, GP_BLOCK, 8192)), dim3(GP_BLOCK), 0, s, list, n_list, runs, cigar_off, cigar);
 }
 
 void launch_gp_depth_add(const SeedSpace &t, const uint32_t *list, uint64_t n_list, const GpOut &o, uint32_t *diff, unsigned long long *tstat, hipStream_t s) {
-    if (n_list && t.n) hipLaunchKernelGGL(k_gp_depth_add, dim3(gp_grid(n_list, 8192)), dim3(GP_BLOCK), 0, s, t, list, n_list, o, diff, tstat);
+    if (n_list && t.n) hipLaunchKernelGGL(k_gp_depth_add, dim3(stage_grid(n_list, GP_BLOCK, 8192)), dim3(GP_BLOCK), 0, s, t, list, n_list, o, diff, tstat);
 }
 
 void launch_gp_cover(const uint32_t *pl_cover, const uint32_t *scan, uint64_t columns, uint32_t *cover, hipStream_t s) {
-    if (columns) hipLaunchKernelGGL(k_gp_cover, dim3(gp_grid(columns, 8192)), dim3(GP_BLOCK), 0, s, pl_cover, scan, columns, cover);
+    if (columns) hipLaunchKernelGGL(k_gp_cover, dim3(stage_grid(columns, GP_BLOCK, 8192)), dim3(GP_BLOCK), 0, s, pl_cover, scan, columns, cover);
 }
 
 void launch_gp_tsv_sizes(const GpTsv &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_gp_tsv_sizes, dim3((unsigned) ((f.n + GP_BLOCK - 1) / GP_BLOCK)), dim3(GP_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_gp_tsv_sizes, dim3(text_sizes_blocks(f.n, GP_BLOCK)), dim3(GP_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_gp_tsv_write(const GpTsv &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + GP_WAVES - 1) / GP_WAVES;
-    hipLaunchKernelGGL(k_gp_tsv_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GP_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_gp_tsv_write, dim3(text_write_blocks(i0, i1, GP_WAVES)), dim3(GP_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -272,7 +272,7 @@ void launch_gfa_check(const GfaCfg &c, unsigned long long *counters, hipStream_t
 }
 
 void launch_gfa_sizes(const GfaCfg &c, const uint32_t *rowptr, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (c.n_seg) hipLaunchKernelGGL(k_gfa_seg_sizes, dim3(grid_of(c.n_seg, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, c, sizes, counters);
+    if (c.n_seg) hipLaunchKernelGGL(k_gfa_seg_sizes, dim3(text_sizes_blocks(c.n_seg, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, c, sizes, counters);
     if (c.m) hipLaunchKernelGGL(k_gfa_link_sizes, dim3(grid_of(c.m, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, c, rowptr, sizes, counters);
 }
 
@@ -292,10 +292,7 @@ void launch_gfa_bounds(const unsigned long long *off, uint64_t n, uint64_t step,
 
 void launch_gfa_format(const GfaCfg &c, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     const uint64_t s1 = i1 < c.n_seg ? i1 : c.n_seg;
-    if (i0 < s1) {
-        const uint64_t g = grid_of(s1 - i0, GFA_BLOCK / 64);
-        hipLaunchKernelGGL(k_gfa_seg_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
-    }
+    if (i0 < s1) hipLaunchKernelGGL(k_gfa_seg_write, dim3(text_write_blocks(i0, s1, GFA_BLOCK / 64)), dim3(GFA_BLOCK), 0, s, c, off, i0, s1, buf);
     const uint64_t l0 = i0 > c.n_seg ? i0 : c.n_seg;
     if (l0 < i1) {
         // the chunk's bytes start at off[i0]: its link lines are placed relative to that
@@ -305,14 +302,13 @@ void launch_gfa_format(const GfaCfg &c, const unsigned long long *off, uint64_t 
 
 void launch_gfa_fasta_sizes(const GfaFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
     if (!f.n) return;
-    if (f.rec_rank) hipLaunchKernelGGL(k_gfa_fasta_sizes<ContigRecord>, dim3(grid_of(f.n, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, f, sizes, counters);
-    else hipLaunchKernelGGL(k_gfa_fasta_sizes<UnitigRecord>, dim3(grid_of(f.n, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, f, sizes, counters);
+    if (f.rec_rank) hipLaunchKernelGGL(k_gfa_fasta_sizes<ContigRecord>, dim3(text_sizes_blocks(f.n, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, f, sizes, counters);
+    else hipLaunchKernelGGL(k_gfa_fasta_sizes<UnitigRecord>, dim3(text_sizes_blocks(f.n, GFA_BLOCK)), dim3(GFA_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_gfa_fasta_write(const GfaFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = grid_of(i1 - i0, GFA_BLOCK / 64);
-    const dim3 grid((unsigned) (g < 16384 ? g : 16384));
+    const dim3 grid(text_write_blocks(i0, i1, GFA_BLOCK / 64));
     if (f.rec_rank) hipLaunchKernelGGL(k_gfa_fasta_write<ContigRecord>, grid, dim3(GFA_BLOCK), 0, s, f, off, i0, i1, buf);
     else hipLaunchKernelGGL(k_gfa_fasta_write<UnitigRecord>, grid, dim3(GFA_BLOCK), 0, s, f, off, i0, i1, buf);
 }

@@ -20,7 +20,7 @@
 //   k_gr_lens         left / right / new length per target; (scan): the new col_off
 //   k_gr_build        every output word gathered by one lane, from the old column array or from the growth
 //   k_gr_fasta_sizes / k_gr_fasta_write   one record per target with a length, one wave per record, a lane a byte
-// Block 256 and the grid caps are picked, not tuned; the launches' max_blocks lowers the cap of every grid that goes through gr_grid (the check
+// Block 256 and the grid caps are picked, not tuned; the launches' max_blocks lowers the cap of every grid that goes through stage_grid (the check
 // keeps min(4096, cap)), of k_gr_place (whose per-wave scratch the host sizes from the capped block count) and of the FASTA write grid (option
 // "grow_max_blocks": a knob of the tests, which make every grid-stride and wave-stride loop here take further passes).  k_gr_fasta_sizes has one
 // thread per item and no loop: its grid is exact.
@@ -91,22 +91,11 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_end_lens(GrTargets t, int32_t m
 
 // (after the check: columns is col_off[T]; W_e <= the target's length, so every source column lies in its target)
 __global__ void __launch_bounds__(GR_BLOCK) k_gr_ends(GrTargets t, GrEnds e, uint32_t *__restrict__ ecols) {
-    const uint64_t n_words = (e.columns + 15) >> 4;
-    for (uint64_t w = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * GR_BLOCK) {
-        const uint64_t g0 = w << 4;
-        uint32_t ee = item_of(e.off, e.n, (uint32_t) g0), v = 0;
-        for (int j = 0; j < 16; j++) {
-            const uint64_t g = g0 + (uint64_t) j;
-            if (g >= e.columns) break;
-            while ((uint64_t) e.off[ee + 1] <= g) ee++;                  // (g < columns = end_off[2T]: ends at an end that has a length)
-            const uint32_t tt = ee >> 1, q = (uint32_t) (g - e.off[ee]), W = (uint32_t) e.len[ee];
-            uint32_t b;
-            if (ee & 1u) b = base_at(t.cols, (uint64_t) t.col_off[tt + 1] - W + q);            // the last W bases
-            else b = 3u - base_at(t.cols, (uint64_t) t.col_off[tt] + (W - 1u - q));            // the first W, complemented and mirrored
-            v |= b << (2 * j);
-        }
-        ecols[w] = v;
-    }
+    packed_words_body<GR_BLOCK>(e.off, e.n, e.columns, (e.columns + 15) >> 4, ecols, [&](uint32_t ee, uint32_t q) {
+        const uint32_t tt = ee >> 1, W = (uint32_t) e.len[ee];
+        if (ee & 1u) return base_at(t.cols, (uint64_t) t.col_off[tt + 1] - W + q);             // the last W bases
+        return 3u - base_at(t.cols, (uint64_t) t.col_off[tt] + (W - 1u - q));                  // the first W, complemented and mirrored
+    });
 }
 
 // Geometry of a read of L bases on the ends: seed js at position q of end e puts v[js k] on E[q], so v[a], a = W_e - q + js k, is the first
@@ -243,27 +232,13 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_lens(GrTargets t, const uint32_
 // target or in its right growth, and left[t] / the rest below x <= max_grow)
 __global__ void __launch_bounds__(GR_BLOCK) k_gr_build(GrTargets t, const uint32_t *__restrict__ new_off, uint64_t new_columns, const uint32_t *__restrict__ left,
                                                        const uint8_t *__restrict__ g, int32_t max_grow, uint32_t *__restrict__ words, unsigned long long *__restrict__ begin) {
-    const uint64_t n_words = ((new_columns + 15) >> 4) + 2, step = (uint64_t) gridDim.x * GR_BLOCK;
-    for (uint64_t i = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; i < t.T; i += step) begin[i] = new_off[i];
-    for (uint64_t w = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; w < n_words; w += step) {
-        const uint64_t g0 = w << 4;
-        uint32_t v = 0;
-        if (g0 < new_columns) {
-            uint32_t tt = item_of(new_off, t.T, (uint32_t) g0);
-            for (int j = 0; j < 16; j++) {
-                const uint64_t gg = g0 + (uint64_t) j;
-                if (gg >= new_columns) break;
-                while ((uint64_t) new_off[tt + 1] <= gg) tt++;               // (gg < new_columns = new_off[T]: ends at a target that has a length)
-                const uint64_t q = gg - new_off[tt], l = left[tt], n = (uint64_t) t.col_off[tt + 1] - t.col_off[tt];
-                uint32_t b;
-                if (q < l) b = 3u - g[(2ull * tt) * (uint64_t) max_grow + (l - 1 - q)];
-                else if (q < l + n) b = base_at(t.cols, (uint64_t) t.col_off[tt] + (q - l));
-                else b = g[(2ull * tt + 1) * (uint64_t) max_grow + (q - l - n)];
-                v |= b << (2 * j);
-            }
-        }
-        words[w] = v;
-    }
+    for (uint64_t i = (uint64_t) blockIdx.x * GR_BLOCK + threadIdx.x; i < t.T; i += (uint64_t) gridDim.x * GR_BLOCK) begin[i] = new_off[i];
+    packed_words_body<GR_BLOCK>(new_off, t.T, new_columns, ((new_columns + 15) >> 4) + 2, words, [&](uint32_t tt, uint64_t q) -> uint32_t {
+        const uint64_t l = left[tt], n = (uint64_t) t.col_off[tt + 1] - t.col_off[tt];
+        if (q < l) return 3u - g[(2ull * tt) * (uint64_t) max_grow + (l - 1 - q)];
+        if (q < l + n) return base_at(t.cols, (uint64_t) t.col_off[tt] + (q - l));
+        return g[(2ull * tt + 1) * (uint64_t) max_grow + (q - l - n)];
+    });
 }
 
 // ---- FASTA of the grown targets --------------------------------------------------------------------------------------------------------
@@ -287,31 +262,26 @@ __global__ void __launch_bounds__(GR_BLOCK) k_gr_fasta_write(GrFasta f, const un
     text_write_body<GrRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned gr_grid(uint64_t items, uint64_t cap) {                  // cap: the launch's max_blocks, 8192 unless a test lowers it
-    const uint64_t g = (items + GR_BLOCK - 1) / GR_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_gr_check(const SeedReads &r, const GrTargets &t, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_check, dim3(gr_grid(2 * r.R, std::min<uint64_t>(4096, t.max_blocks))), dim3(GR_BLOCK), 0, s, r, t, counters);
+    hipLaunchKernelGGL(k_gr_check, dim3(stage_grid(2 * r.R, GR_BLOCK, std::min<uint64_t>(4096, t.max_blocks))), dim3(GR_BLOCK), 0, s, r, t, counters);
 }
 
 void launch_gr_candidates(const SeedReads &r, const uint8_t *pl_state, int32_t min_anchor, uint32_t *flag, uint32_t max_blocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_candidates, dim3(gr_grid(r.R + 1, max_blocks)), dim3(GR_BLOCK), 0, s, r, pl_state, min_anchor, flag);
+    hipLaunchKernelGGL(k_gr_candidates, dim3(stage_grid(r.R + 1, GR_BLOCK, max_blocks)), dim3(GR_BLOCK), 0, s, r, pl_state, min_anchor, flag);
 }
 
 void launch_gr_compact(const uint32_t *flag, const uint32_t *pos, uint64_t R, uint32_t *cand, uint32_t max_blocks, hipStream_t s) {
-    if (R) hipLaunchKernelGGL(k_gr_compact, dim3(gr_grid(R, max_blocks)), dim3(GR_BLOCK), 0, s, flag, pos, R, cand);
+    if (R) hipLaunchKernelGGL(k_gr_compact, dim3(stage_grid(R, GR_BLOCK, max_blocks)), dim3(GR_BLOCK), 0, s, flag, pos, R, cand);
 }
 
 void launch_gr_end_lens(const GrTargets &t, int32_t max_len, int32_t k, int32_t *elen, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_end_lens, dim3(gr_grid(2ull * t.T + 1, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, max_len, k, elen, counters);
+    hipLaunchKernelGGL(k_gr_end_lens, dim3(stage_grid(2ull * t.T + 1, GR_BLOCK, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, max_len, k, elen, counters);
 }
 
 void launch_gr_ends(const GrTargets &t, const GrEnds &e, uint32_t *ecols, hipStream_t s) {
-    if (e.columns) hipLaunchKernelGGL(k_gr_ends, dim3(gr_grid((e.columns + 15) >> 4, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, e, ecols);
+    if (e.columns) hipLaunchKernelGGL(k_gr_ends, dim3(stage_grid((e.columns + 15) >> 4, GR_BLOCK, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, e, ecols);
 }
 
 void launch_gr_place(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ,
@@ -323,32 +293,31 @@ void launch_gr_place(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, 
 
 void launch_gr_vote(const SeedReads &r, const uint32_t *cand, uint64_t n_cand, const GrOut &o, int32_t max_grow, uint32_t *count, uint32_t *voters, uint32_t max_blocks,
                     hipStream_t s) {
-    if (n_cand) hipLaunchKernelGGL(k_gr_vote, dim3(gr_grid(n_cand * 64, max_blocks)), dim3(GR_BLOCK), 0, s, r, cand, n_cand, o, max_grow, count, voters);
+    if (n_cand) hipLaunchKernelGGL(k_gr_vote, dim3(stage_grid(n_cand * 64, GR_BLOCK, max_blocks)), dim3(GR_BLOCK), 0, s, r, cand, n_cand, o, max_grow, count, voters);
 }
 
 void launch_gr_decide(const uint32_t *count, const uint32_t *voters, uint32_t E, int32_t max_grow, int32_t min_cover, int32_t min_percent, uint32_t *x, uint8_t *g,
                       uint8_t *stop, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_gr_decide, dim3(gr_grid(E, max_blocks)), dim3(GR_BLOCK), 0, s, count, voters, E, max_grow, (uint32_t) min_cover, (uint32_t) min_percent, x, g, stop, counters);
+    if (E) hipLaunchKernelGGL(k_gr_decide, dim3(stage_grid(E, GR_BLOCK, max_blocks)), dim3(GR_BLOCK), 0, s, count, voters, E, max_grow, (uint32_t) min_cover, (uint32_t) min_percent, x, g, stop, counters);
 }
 
 void launch_gr_lens(const GrTargets &t, const uint32_t *x, uint32_t *left, uint32_t *right, int32_t *newlen, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_gr_lens, dim3(gr_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, x, left, right, newlen, counters);
+    hipLaunchKernelGGL(k_gr_lens, dim3(stage_grid((uint64_t) t.T + 1, GR_BLOCK, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, x, left, right, newlen, counters);
 }
 
 void launch_gr_build(const GrTargets &t, const uint32_t *new_off, uint64_t new_columns, const uint32_t *left, const uint8_t *g, int32_t max_grow, uint32_t *words,
                      unsigned long long *begin, hipStream_t s) {
     const uint64_t n_words = ((new_columns + 15) >> 4) + 2;
-    hipLaunchKernelGGL(k_gr_build, dim3(gr_grid(std::max<uint64_t>(n_words, t.T), t.max_blocks)), dim3(GR_BLOCK), 0, s, t, new_off, new_columns, left, g, max_grow, words, begin);
+    hipLaunchKernelGGL(k_gr_build, dim3(stage_grid(std::max<uint64_t>(n_words, t.T), GR_BLOCK, t.max_blocks)), dim3(GR_BLOCK), 0, s, t, new_off, new_columns, left, g, max_grow, words, begin);
 }
 
 void launch_gr_fasta_sizes(const GrFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_gr_fasta_sizes, dim3((unsigned) ((f.n + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_gr_fasta_sizes, dim3(text_sizes_blocks(f.n, GR_BLOCK)), dim3(GR_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_gr_fasta_write(const GrFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + GR_WAVES - 1) / GR_WAVES;
-    hipLaunchKernelGGL(k_gr_fasta_write, dim3((unsigned) std::min<uint64_t>(g, f.max_blocks)), dim3(GR_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_gr_fasta_write, dim3(text_write_blocks(i0, i1, GR_WAVES, f.max_blocks)), dim3(GR_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -261,28 +261,13 @@ __global__ void __launch_bounds__(IP_BLOCK) k_ip_decide(IpTargets t, IpDecide d,
 }
 
 __global__ void __launch_bounds__(IP_BLOCK) k_ip_words(IpTargets t, IpBuild b, uint32_t *__restrict__ words) {
-    const uint64_t n_words = ((b.new_columns + 15) >> 4) + 2;
-    for (uint64_t w = (uint64_t) blockIdx.x * IP_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * IP_BLOCK) {
-        const uint64_t j0 = w << 4;
-        uint32_t word = 0;
-        if (j0 < b.new_columns) {                                      // (then there is an old column: new_col[0] == 0 <= j0)
-            uint64_t lo = 0, hi = t.columns;                          // the old columns that start at or before j0
-            while (lo < hi) {
-                const uint64_t mid = lo + ((hi - lo) >> 1);
-                if ((uint64_t) b.new_col[mid] <= j0) lo = mid + 1; else hi = mid;
-            }
-            uint64_t g = lo - 1;
-            for (uint32_t k = 0; k < 16 && j0 + k < b.new_columns; k++) {
-                const uint64_t j = j0 + k;
-                while (g + 1 < t.columns && (uint64_t) b.new_col[g + 1] <= j) g++;        // the LAST old column that starts at or before j: it has a width
-                const uint32_t off = (uint32_t) (j - b.new_col[g]), cd = b.code[g];
-                const uint32_t key = (cd & IP_C_INSERTED) ? b.win_key[g] : 0u, nins = key >> 26;
-                const uint32_t base = off < nins ? (key >> (2 * (nins - 1 - off))) & 3u : cd & IP_C_BASE;
-                word |= base << (2 * k);
-            }
-        }
-        words[w] = word;
-    }
+    // the items are the old columns, item g as wide as the new columns it becomes (new_col is the scan of the widths over columns + 1 entries, the
+    // last width 0: new_col[columns] == new_columns); a deleted column is an empty item
+    packed_words_body<IP_BLOCK>(b.new_col, (uint32_t) t.columns, b.new_columns, ((b.new_columns + 15) >> 4) + 2, words, [&](uint32_t g, uint32_t off) {
+        const uint32_t cd = b.code[g];
+        const uint32_t key = (cd & IP_C_INSERTED) ? b.win_key[g] : 0u, nins = key >> 26;
+        return off < nins ? (key >> (2 * (nins - 1 - off))) & 3u : cd & IP_C_BASE;
+    });
 }
 
 __global__ void __launch_bounds__(IP_BLOCK) k_ip_events(IpTargets t, IpBuild b, IpEvents ev) {
@@ -385,65 +370,58 @@ __global__ void __launch_bounds__(IP_BLOCK) k_ip_tsv_write(IpTsv f, const unsign
     text_write_body<IpLine>(f, off, i0, i1, buf);
 }
 
-inline unsigned ip_grid(uint64_t items, uint64_t cap) {
-    const uint64_t g = (items + IP_BLOCK - 1) / IP_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_ip_check(const IpReads &r, const IpTargets &t, int32_t max_ins, unsigned long long *counters, hipStream_t s) {
-    if (r.R) hipLaunchKernelGGL(k_ip_check, dim3(ip_grid(r.R, t.max_blocks)), dim3(IP_BLOCK), 0, s, r, t, max_ins, counters);
+    if (r.R) hipLaunchKernelGGL(k_ip_check, dim3(stage_grid(r.R, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, r, t, max_ins, counters);
 }
 
 void launch_ip_vote_gapped(const IpReads &r, const IpTargets &t, int32_t max_ins, uint32_t *counts4, uint32_t *del, unsigned long long *ins_key, unsigned long long *ins_slot,
                            uint32_t *ins_all, unsigned long long *counters, hipStream_t s) {
-    if (r.R) hipLaunchKernelGGL(k_ip_vote_gapped, dim3(ip_grid(r.R, t.max_blocks)), dim3(IP_BLOCK), 0, s, r, t, max_ins, counts4, del, ins_key, ins_slot, ins_all, counters);
+    if (r.R) hipLaunchKernelGGL(k_ip_vote_gapped, dim3(stage_grid(r.R, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, r, t, max_ins, counts4, del, ins_key, ins_slot, ins_all, counters);
 }
 
 void launch_ip_span(const IpReads &r, const IpTargets &t, const int32_t *pl_target, const int32_t *pl_pos, const uint8_t *pl_state, uint32_t *diff, hipStream_t s) {
-    if (r.R) hipLaunchKernelGGL(k_ip_span, dim3(ip_grid(r.R, t.max_blocks)), dim3(IP_BLOCK), 0, s, r, t, pl_target, pl_pos, pl_state, diff);
+    if (r.R) hipLaunchKernelGGL(k_ip_span, dim3(stage_grid(r.R, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, r, t, pl_target, pl_pos, pl_state, diff);
 }
 
 void launch_ip_ins_pick(const unsigned long long *slot, const unsigned long long *key, uint64_t n, uint32_t *win_key, uint32_t *win_votes, uint32_t *ins_all, uint32_t max_blocks,
                         hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_ip_ins_pick, dim3(ip_grid(n, max_blocks)), dim3(IP_BLOCK), 0, s, slot, key, n, win_key, win_votes, ins_all);
+    if (n) hipLaunchKernelGGL(k_ip_ins_pick, dim3(stage_grid(n, IP_BLOCK, max_blocks)), dim3(IP_BLOCK), 0, s, slot, key, n, win_key, win_votes, ins_all);
 }
 
 void launch_ip_decide(const IpTargets &t, const IpDecide &d, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_ip_decide, dim3(ip_grid(t.columns + 1, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, d, counters);
+    hipLaunchKernelGGL(k_ip_decide, dim3(stage_grid(t.columns + 1, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, d, counters);
 }
 
 void launch_ip_words(const IpTargets &t, const IpBuild &b, uint32_t *words, hipStream_t s) {
-    hipLaunchKernelGGL(k_ip_words, dim3(ip_grid(((b.new_columns + 15) >> 4) + 2, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, b, words);
+    hipLaunchKernelGGL(k_ip_words, dim3(stage_grid(((b.new_columns + 15) >> 4) + 2, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, b, words);
 }
 
 void launch_ip_events(const IpTargets &t, const IpBuild &b, const IpEvents &ev, hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_ip_events, dim3(ip_grid(t.columns, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, b, ev);
+    if (t.columns) hipLaunchKernelGGL(k_ip_events, dim3(stage_grid(t.columns, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, b, ev);
 }
 
 void launch_ip_targets(const IpTargets &t, const uint32_t *new_col, uint32_t *col_off, int32_t *len, unsigned long long *begin, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_ip_targets, dim3(ip_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, new_col, col_off, len, begin, counters);
+    hipLaunchKernelGGL(k_ip_targets, dim3(stage_grid((uint64_t) t.T + 1, IP_BLOCK, t.max_blocks)), dim3(IP_BLOCK), 0, s, t, new_col, col_off, len, begin, counters);
 }
 
 void launch_ip_fasta_sizes(const IpFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_ip_fasta_sizes, dim3((unsigned) ((f.n + IP_BLOCK - 1) / IP_BLOCK)), dim3(IP_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_ip_fasta_sizes, dim3(text_sizes_blocks(f.n, IP_BLOCK)), dim3(IP_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_ip_fasta_write(const IpFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + IP_WAVES - 1) / IP_WAVES;
-    hipLaunchKernelGGL(k_ip_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(IP_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_ip_fasta_write, dim3(text_write_blocks(i0, i1, IP_WAVES)), dim3(IP_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 void launch_ip_tsv_sizes(const IpTsv &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_ip_tsv_sizes, dim3((unsigned) ((f.n + IP_BLOCK - 1) / IP_BLOCK)), dim3(IP_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_ip_tsv_sizes, dim3(text_sizes_blocks(f.n, IP_BLOCK)), dim3(IP_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_ip_tsv_write(const IpTsv &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + IP_WAVES - 1) / IP_WAVES;
-    hipLaunchKernelGGL(k_ip_tsv_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(IP_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_ip_tsv_write, dim3(text_write_blocks(i0, i1, IP_WAVES)), dim3(IP_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -19,7 +19,7 @@
 //   k_mg_build        every output word gathered by one lane: a column finds its member by bisection over the starts, an overlapped column is
 //                     the earlier contig's; minus-oriented members complemented and mirrored
 //   k_mg_fasta_sizes / k_mg_fasta_write   one record per merged contig, one wave per record
-// No LDS.  Block 256 and the grid caps are picked, not tuned; MgTargets::max_blocks lowers the cap of every grid that goes through mg_grid
+// No LDS.  Block 256 and the grid caps are picked, not tuned; MgTargets::max_blocks lowers the cap of every grid that goes through stage_grid
 // (option "merge_max_blocks": a knob of the tests, which make every grid-stride loop here take further passes).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -239,36 +239,23 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_layout(MgTargets t, ChainLists 
 // lies in that member's target: p - start < len)
 __global__ void __launch_bounds__(MG_BLOCK) k_mg_build(MgTargets t, MgLayout o, const uint32_t *__restrict__ col_off, uint32_t n_merged, uint64_t columns,
                                                        uint32_t *__restrict__ words, unsigned long long *__restrict__ begin) {
-    const uint64_t n_words = ((columns + 15) >> 4) + 2, step = (uint64_t) gridDim.x * MG_BLOCK;
-    for (uint64_t i = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; i < n_merged; i += step) begin[i] = col_off[i];
-    for (uint64_t w = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; w < n_words; w += step) {
-        const uint64_t g0 = w << 4;
-        uint32_t v = 0;
-        if (g0 < columns) {
-            uint32_t j = item_of(col_off, n_merged, (uint32_t) g0);
-            for (int b = 0; b < 16; b++) {
-                const uint64_t gg = g0 + (uint64_t) b;
-                if (gg >= columns) break;
-                while ((uint64_t) col_off[j + 1] <= gg) j++;                 // (gg < columns = col_off[n_merged]: ends at a merged contig)
-                const uint32_t p = (uint32_t) (gg - col_off[j]), m0 = o.m_off[j], m = o.m_off[j + 1] - m0;
-                const int32_t *mem = o.m_members + m0;
-                uint32_t lo = 0, hi = m;                                     // the member of largest rank that starts at or before p
-                while (hi - lo > 1) {
-                    const uint32_t mid = lo + ((hi - lo) >> 1);
-                    if (o.start[mem[mid]] <= p) lo = mid; else hi = mid;
-                }
-                uint32_t c = (uint32_t) mem[lo];
-                if (lo > 0) {                                                // an overlapped column is the earlier contig's
-                    const uint32_t cp = (uint32_t) mem[lo - 1];
-                    if (p < o.start[cp] + (uint32_t) t.len[cp]) c = cp;
-                }
-                const uint32_t q = p - o.start[c], n = (uint32_t) t.len[c];
-                const uint32_t code = o.orient[c] ? 3u - base_at(t.words, t.begin[c] + (n - 1u - q)) : base_at(t.words, t.begin[c] + q);
-                v |= code << (2 * b);
-            }
+    for (uint64_t i = (uint64_t) blockIdx.x * MG_BLOCK + threadIdx.x; i < n_merged; i += (uint64_t) gridDim.x * MG_BLOCK) begin[i] = col_off[i];
+    packed_words_body<MG_BLOCK>(col_off, n_merged, columns, ((columns + 15) >> 4) + 2, words, [&](uint32_t j, uint32_t p) {
+        const uint32_t m0 = o.m_off[j], m = o.m_off[j + 1] - m0;
+        const int32_t *mem = o.m_members + m0;
+        uint32_t lo = 0, hi = m;                                             // the member of largest rank that starts at or before p
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (o.start[mem[mid]] <= p) lo = mid; else hi = mid;
         }
-        words[w] = v;
-    }
+        uint32_t c = (uint32_t) mem[lo];
+        if (lo > 0) {                                                        // an overlapped column is the earlier contig's
+            const uint32_t cp = (uint32_t) mem[lo - 1];
+            if (p < o.start[cp] + (uint32_t) t.len[cp]) c = cp;
+        }
+        const uint32_t q = p - o.start[c], n = (uint32_t) t.len[c];
+        return o.orient[c] ? 3u - base_at(t.words, t.begin[c] + (n - 1u - q)) : base_at(t.words, t.begin[c] + q);
+    });
 }
 
 // ---- FASTA of the merged contigs -------------------------------------------------------------------------------------------------------
@@ -292,23 +279,18 @@ __global__ void __launch_bounds__(MG_BLOCK) k_mg_fasta_write(MgFasta f, const un
     text_write_body<MgRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned mg_grid(uint64_t items, uint64_t cap) {                  // cap: MgTargets::max_blocks, 8192 unless a test lowers it
-    const uint64_t g = (items + MG_BLOCK - 1) / MG_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_mg_check(const MgTargets &t, unsigned long long *counters, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_mg_check, dim3(mg_grid(t.T, std::min<uint64_t>(4096, t.max_blocks))), dim3(MG_BLOCK), 0, s, t, counters);
+    if (t.T) hipLaunchKernelGGL(k_mg_check, dim3(stage_grid(t.T, MG_BLOCK, std::min<uint64_t>(4096, t.max_blocks))), dim3(MG_BLOCK), 0, s, t, counters);
 }
 
 void launch_mg_end_lens(const MgTargets &t, int32_t max_overlap, int32_t min_overlap, int32_t k, int32_t *elen, uint32_t *epad, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_end_lens, dim3(mg_grid(2ull * t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, max_overlap, min_overlap, k, elen, epad, counters);
+    hipLaunchKernelGGL(k_mg_end_lens, dim3(stage_grid(2ull * t.T + 1, MG_BLOCK, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, max_overlap, min_overlap, k, elen, epad, counters);
 }
 
 void launch_mg_ends(const MgTargets &t, const MgEnds &e, uint32_t *ecols, uint32_t *pcols, hipStream_t s) {
-    if (e.columns) hipLaunchKernelGGL(k_mg_ends, dim3(mg_grid(e.columns >> 4, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, e, ecols, pcols);
+    if (e.columns) hipLaunchKernelGGL(k_mg_ends, dim3(stage_grid(e.columns >> 4, MG_BLOCK, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, e, ecols, pcols);
 }
 
 void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, int32_t min_overlap, const MgEndOut &o, int blocks,
@@ -317,41 +299,40 @@ void launch_mg_overlap(const MgEnds &e, const SeedIndex &x, int32_t k, int32_t m
 }
 
 void launch_mg_joins(const MgEndOut &o, uint32_t E, uint32_t *join, uint32_t max_blocks, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_mg_joins, dim3(mg_grid(E, max_blocks)), dim3(MG_BLOCK), 0, s, o, E, join);
+    if (E) hipLaunchKernelGGL(k_mg_joins, dim3(stage_grid(E, MG_BLOCK, max_blocks)), dim3(MG_BLOCK), 0, s, o, E, join);
 }
 
 void launch_mg_cycle_drop(const ChainLists &l, uint32_t T, uint32_t *join, uint8_t *end_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (T) hipLaunchKernelGGL(k_mg_cycle_drop, dim3(mg_grid(T, max_blocks)), dim3(MG_BLOCK), 0, s, l, T, join, end_state, counters);
+    if (T) hipLaunchKernelGGL(k_mg_cycle_drop, dim3(stage_grid(T, MG_BLOCK, max_blocks)), dim3(MG_BLOCK), 0, s, l, T, join, end_state, counters);
 }
 
 void launch_mg_rank_init(const MgTargets &t, const uint32_t *join, const int32_t *olen, const ChainLists &l, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_mg_rank_init, dim3(mg_grid(2ull * t.T, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, join, olen, l);
+    if (t.T) hipLaunchKernelGGL(k_mg_rank_init, dim3(stage_grid(2ull * t.T, MG_BLOCK, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, join, olen, l);
 }
 
 void launch_mg_place(const MgTargets &t, const ChainLists &l, const uint32_t *join, const MgEndOut &o, const MgLayout &lo, uint32_t *head, uint32_t *first, uint32_t *members,
                      unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_place, dim3(mg_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, join, o, lo, head, first, members, counters);
+    hipLaunchKernelGGL(k_mg_place, dim3(stage_grid((uint64_t) t.T + 1, MG_BLOCK, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, join, o, lo, head, first, members, counters);
 }
 
 void launch_mg_layout(const MgTargets &t, const ChainLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const MgLayout &lo,
                       unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_layout, dim3(mg_grid((uint64_t) t.T + 1, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, head, first_scan, members_scan, lo, counters);
+    hipLaunchKernelGGL(k_mg_layout, dim3(stage_grid((uint64_t) t.T + 1, MG_BLOCK, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, l, head, first_scan, members_scan, lo, counters);
 }
 
 void launch_mg_build(const MgTargets &t, const MgLayout &lo, const uint32_t *col_off, uint32_t n_merged, uint64_t columns, uint32_t *words, unsigned long long *begin,
                      hipStream_t s) {
     const uint64_t n_words = ((columns + 15) >> 4) + 2;
-    hipLaunchKernelGGL(k_mg_build, dim3(mg_grid(std::max<uint64_t>(n_words, n_merged), t.max_blocks)), dim3(MG_BLOCK), 0, s, t, lo, col_off, n_merged, columns, words, begin);
+    hipLaunchKernelGGL(k_mg_build, dim3(stage_grid(std::max<uint64_t>(n_words, n_merged), MG_BLOCK, t.max_blocks)), dim3(MG_BLOCK), 0, s, t, lo, col_off, n_merged, columns, words, begin);
 }
 
 void launch_mg_fasta_sizes(const MgFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_mg_fasta_sizes, dim3((unsigned) ((f.n + MG_BLOCK - 1) / MG_BLOCK)), dim3(MG_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_mg_fasta_sizes, dim3(text_sizes_blocks(f.n, MG_BLOCK)), dim3(MG_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_mg_fasta_write(const MgFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + MG_WAVES - 1) / MG_WAVES;
-    hipLaunchKernelGGL(k_mg_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(MG_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_mg_fasta_write, dim3(text_write_blocks(i0, i1, MG_WAVES)), dim3(MG_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

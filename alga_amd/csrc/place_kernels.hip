@@ -85,19 +85,7 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_final_targets(const unsigned lo
 
 __global__ void __launch_bounds__(PL_BLOCK) k_pl_gather(const uint32_t *__restrict__ words, const unsigned long long *__restrict__ begin, PlTargets t,
                                                         uint32_t *__restrict__ cols) {
-    const uint64_t n_words = (t.columns + 15) >> 4;
-    for (uint64_t w = (uint64_t) blockIdx.x * PL_BLOCK + threadIdx.x; w < n_words; w += (uint64_t) gridDim.x * PL_BLOCK) {
-        const uint64_t g0 = w << 4;
-        uint32_t tt = item_of(t.off, t.n, (uint32_t) g0), v = 0;
-        for (int j = 0; j < 16; j++) {
-            const uint64_t g = g0 + (uint64_t) j;
-            if (g >= t.columns) break;
-            while ((uint64_t) t.off[tt + 1] <= g) tt++;                  // (g < columns = col_off[T]: ends at a target that has a length)
-            const unsigned long long src = begin[tt] + (g - (uint64_t) t.off[tt]);
-            v |= ((words[src >> 4] >> ((src & 15ull) << 1)) & 3u) << (2 * j);
-        }
-        cols[w] = v;
-    }
+    packed_words_body<PL_BLOCK>(t.off, t.n, t.columns, (t.columns + 15) >> 4, cols, [&](uint32_t tt, uint32_t q) { return base_at(words, begin[tt] + q); });
 }
 
 // Geometry of a read of L bases on the targets: (seed js, column g) is the placement at g - js k where it lies in g's target
@@ -231,19 +219,14 @@ __global__ void __launch_bounds__(PL_BLOCK) k_pl_fasta_write(PlFasta f, const un
     text_write_body<PlRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned pl_grid(uint64_t items, uint64_t cap = 1u << 16) {
-    const uint64_t g = (items + PL_BLOCK - 1) / PL_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_pl_node_check(const uint8_t *pair_off, const int32_t *len, uint64_t n, unsigned long long *counters, hipStream_t s) {
-    if (n) hipLaunchKernelGGL(k_pl_node_check, dim3(pl_grid(n, 4096)), dim3(PL_BLOCK), 0, s, pair_off, len, n, counters);
+    if (n) hipLaunchKernelGGL(k_pl_node_check, dim3(stage_grid(n, PL_BLOCK, 4096)), dim3(PL_BLOCK), 0, s, pair_off, len, n, counters);
 }
 
 void launch_pl_target_check(const int32_t *tlen, uint64_t T, int32_t k, unsigned long long *counters, hipStream_t s) {
-    if (T) hipLaunchKernelGGL(k_pl_target_check, dim3(pl_grid(T, 4096)), dim3(PL_BLOCK), 0, s, tlen, T, k, counters);
+    if (T) hipLaunchKernelGGL(k_pl_target_check, dim3(stage_grid(T, PL_BLOCK, 4096)), dim3(PL_BLOCK), 0, s, tlen, T, k, counters);
 }
 
 void launch_pl_final_targets(const unsigned long long *word_off, const uint8_t *verdict, const int32_t *order, const int32_t *begin, const int32_t *len, uint64_t n,
@@ -252,7 +235,7 @@ void launch_pl_final_targets(const unsigned long long *word_off, const uint8_t *
 }
 
 void launch_pl_gather(const uint32_t *words, const unsigned long long *begin, const PlTargets &t, uint32_t *cols, hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_pl_gather, dim3(pl_grid((t.columns + 15) >> 4)), dim3(PL_BLOCK), 0, s, words, begin, t, cols);
+    if (t.columns) hipLaunchKernelGGL(k_pl_gather, dim3(stage_grid((t.columns + 15) >> 4, PL_BLOCK, 1u << 16)), dim3(PL_BLOCK), 0, s, words, begin, t, cols);
 }
 
 void launch_pl_place(const SeedReads &r, const PlTargets &t, const SeedIndex &x, int32_t k, int32_t max_mm, int32_t max_occ, const PlOut &o, unsigned long long *scratch,
@@ -262,25 +245,24 @@ void launch_pl_place(const SeedReads &r, const PlTargets &t, const SeedIndex &x,
 }
 
 void launch_pl_depth_add(const SeedReads &r, const PlTargets &t, const PlOut &o, int multi, uint32_t *diff, unsigned long long *tstat, hipStream_t s) {
-    if (r.R && t.n) hipLaunchKernelGGL(k_pl_depth_add, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, t, o, multi, diff, tstat);
+    if (r.R && t.n) hipLaunchKernelGGL(k_pl_depth_add, dim3(stage_grid(r.R, PL_BLOCK, 8192)), dim3(PL_BLOCK), 0, s, r, t, o, multi, diff, tstat);
 }
 
 void launch_pl_uncovered(const PlTargets &t, const uint32_t *cover, unsigned long long *tstat, hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_pl_uncovered, dim3(pl_grid(t.columns, 8192)), dim3(PL_BLOCK), 0, s, t, cover, tstat);
+    if (t.columns) hipLaunchKernelGGL(k_pl_uncovered, dim3(stage_grid(t.columns, PL_BLOCK, 8192)), dim3(PL_BLOCK), 0, s, t, cover, tstat);
 }
 
 void launch_pl_pairs(const SeedReads &r, const uint8_t *pair_off, const PlOut &o, int32_t max_insert, unsigned long long *hist, unsigned long long *counters, hipStream_t s) {
-    if (r.R && pair_off) hipLaunchKernelGGL(k_pl_pairs, dim3(pl_grid(r.R, 8192)), dim3(PL_BLOCK), 0, s, r, pair_off, o, max_insert, hist, counters);
+    if (r.R && pair_off) hipLaunchKernelGGL(k_pl_pairs, dim3(stage_grid(r.R, PL_BLOCK, 8192)), dim3(PL_BLOCK), 0, s, r, pair_off, o, max_insert, hist, counters);
 }
 
 void launch_pl_fasta_sizes(const PlFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_pl_fasta_sizes, dim3((unsigned) ((f.n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_pl_fasta_sizes, dim3(text_sizes_blocks(f.n, PL_BLOCK)), dim3(PL_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_pl_fasta_write(const PlFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + PL_WAVES - 1) / PL_WAVES;
-    hipLaunchKernelGGL(k_pl_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(PL_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_pl_fasta_write, dim3(text_write_blocks(i0, i1, PL_WAVES)), dim3(PL_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -25,7 +25,7 @@
 #include <algorithm>
 
 #include "polish_kernels.h"
-#include "seed_device.h"
+#include "packed_device.h"
 #include "text_record.h"
 
 namespace alga {
@@ -299,42 +299,36 @@ __global__ void __launch_bounds__(PO_BLOCK) k_po_fasta_write(PoFasta f, const un
     text_write_body<PoRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned po_grid(uint64_t items, uint64_t cap = 1u << 16) {
-    const uint64_t g = (items + PO_BLOCK - 1) / PO_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_po_check(const PoReads &r, const PoTargets &t, unsigned long long *counters, hipStream_t s) {
-    hipLaunchKernelGGL(k_po_check, dim3(po_grid(r.R, 4096)), dim3(PO_BLOCK), 0, s, r, t, counters);
+    hipLaunchKernelGGL(k_po_check, dim3(stage_grid(r.R, PO_BLOCK, 4096)), dim3(PO_BLOCK), 0, s, r, t, counters);
 }
 
 void launch_po_keys(const PoReads &r, const PoTargets &t, uint32_t *keys, uint32_t *vals, hipStream_t s) {
-    if (r.R) hipLaunchKernelGGL(k_po_keys, dim3(po_grid(r.R, 8192)), dim3(PO_BLOCK), 0, s, r, t, keys, vals);
+    if (r.R) hipLaunchKernelGGL(k_po_keys, dim3(stage_grid(r.R, PO_BLOCK, 8192)), dim3(PO_BLOCK), 0, s, r, t, keys, vals);
 }
 
 void launch_po_vote(const PoReads &r, const PoTargets &t, const PoVote &v, unsigned long long *counters, hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_po_vote, dim3(po_grid((t.columns + 15) >> 4, 1u << 18)), dim3(PO_BLOCK), 0, s, r, t, v, counters);
+    if (t.columns) hipLaunchKernelGGL(k_po_vote, dim3(stage_grid((t.columns + 15) >> 4, PO_BLOCK, 1u << 18)), dim3(PO_BLOCK), 0, s, r, t, v, counters);
 }
 
 void launch_po_vote_wide(const PoReads &r, const PoTargets &t, const PoVote &v, unsigned long long *counters, hipStream_t s) {
     // a wave takes 64 consecutive words at a time
-    if (t.columns) hipLaunchKernelGGL(k_po_vote_wide, dim3(po_grid((((t.columns + 15) >> 4) + 63) / 64 * 64)), dim3(PO_BLOCK), 0, s, r, t, v, counters);
+    if (t.columns) hipLaunchKernelGGL(k_po_vote_wide, dim3(stage_grid((((t.columns + 15) >> 4) + 63) / 64 * 64, PO_BLOCK, 1u << 16)), dim3(PO_BLOCK), 0, s, r, t, v, counters);
 }
 
 void launch_po_changes(const PoTargets &t, const uint32_t *words, const uint32_t *marks, const uint32_t *pos, uint32_t *cols_out, uint8_t *bases_out, hipStream_t s) {
-    if (t.columns) hipLaunchKernelGGL(k_po_changes, dim3(po_grid((t.columns + 15) >> 4)), dim3(PO_BLOCK), 0, s, t, words, marks, pos, cols_out, bases_out);
+    if (t.columns) hipLaunchKernelGGL(k_po_changes, dim3(stage_grid((t.columns + 15) >> 4, PO_BLOCK, 1u << 16)), dim3(PO_BLOCK), 0, s, t, words, marks, pos, cols_out, bases_out);
 }
 
 void launch_po_fasta_sizes(const PoFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_po_fasta_sizes, dim3((unsigned) ((f.n + PO_BLOCK - 1) / PO_BLOCK)), dim3(PO_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_po_fasta_sizes, dim3(text_sizes_blocks(f.n, PO_BLOCK)), dim3(PO_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_po_fasta_write(const PoFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + PO_WAVES - 1) / PO_WAVES;
-    hipLaunchKernelGGL(k_po_fasta_write, dim3((unsigned) (g < 16384 ? g : 16384)), dim3(PO_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_po_fasta_write, dim3(text_write_blocks(i0, i1, PO_WAVES)), dim3(PO_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

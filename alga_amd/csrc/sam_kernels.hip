@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "sam_kernels.h"
+#include "packed_device.h"
 #include "text_record.h"
 
 namespace alga {
@@ -261,31 +262,25 @@ __global__ void __launch_bounds__(SAM_BLOCK) k_sam_write(SamText f, const unsign
     text_write_body<SamRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned sam_grid(uint64_t items, uint64_t cap) {
-    const uint64_t g = (items + SAM_BLOCK - 1) / SAM_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_sam_pair_check(const uint8_t *pair_off, uint64_t n, unsigned long long *counters, int max_blocks, hipStream_t s) {
-    if (n && pair_off) hipLaunchKernelGGL(k_sam_pair_check, dim3(sam_grid(n, max_blocks > 0 ? std::min(max_blocks, 4096) : 4096)), dim3(SAM_BLOCK), 0, s, pair_off, n, counters);
+    if (n && pair_off) hipLaunchKernelGGL(k_sam_pair_check, dim3(stage_grid(n, SAM_BLOCK, max_blocks > 0 ? std::min(max_blocks, 4096) : 4096)), dim3(SAM_BLOCK), 0, s, pair_off, n, counters);
 }
 
 void launch_sam_judge(const SamReads &v, int32_t max_insert, uint16_t *flag, int32_t *tlen, unsigned long long *hist, unsigned long long *counters, int max_blocks,
                       hipStream_t s) {
-    if (v.R) hipLaunchKernelGGL(k_sam_judge, dim3(sam_grid(v.R, max_blocks > 0 ? std::min(max_blocks, 8192) : 8192)), dim3(SAM_BLOCK), 0, s, v, max_insert, flag, tlen, hist,
+    if (v.R) hipLaunchKernelGGL(k_sam_judge, dim3(stage_grid(v.R, SAM_BLOCK, max_blocks > 0 ? std::min(max_blocks, 8192) : 8192)), dim3(SAM_BLOCK), 0, s, v, max_insert, flag, tlen, hist,
                                 counters);
 }
 
 void launch_sam_sizes(const SamText &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_sam_sizes, dim3((unsigned) ((f.n + SAM_BLOCK - 1) / SAM_BLOCK)), dim3(SAM_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_sam_sizes, dim3(text_sizes_blocks(f.n, SAM_BLOCK)), dim3(SAM_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_sam_write(const SamText &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + SAM_WAVES - 1) / SAM_WAVES, cap = f.max_blocks > 0 ? (uint64_t) f.max_blocks : 16384;
-    hipLaunchKernelGGL(k_sam_write, dim3((unsigned) (g < cap ? g : cap)), dim3(SAM_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_sam_write, dim3(text_write_blocks(i0, i1, SAM_WAVES, f.max_blocks > 0 ? (uint64_t) f.max_blocks : 16384)), dim3(SAM_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

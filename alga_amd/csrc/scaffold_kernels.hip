@@ -14,7 +14,7 @@
 //                     these four instantiate chain_device.h): a dropped join is DROPPED on its bundle, a state weighs its contig's length and the
 //                     gap behind it; start, gap_after, join_links, JOINED per contig in the direction item 7 chooses; the 64-bit scaffold lengths
 //   k_sc_fasta_sizes / k_sc_fasta_write   one record per scaffold, one wave per record; a byte finds its contig by bisection over the starts
-// Block 256 and the grid caps are picked, not tuned; the launches' max_blocks lowers the cap of every grid that goes through sc_grid and of the
+// Block 256 and the grid caps are picked, not tuned; the launches' max_blocks lowers the cap of every grid that goes through stage_grid and of the
 // FASTA write grid (option "scaffold_max_blocks": a knob of the tests, which make every grid-stride loop here take further passes).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "scaffold_kernels.h"
+#include "packed_device.h"
 #include "text_record.h"
 #include "chain_device.h"
 
@@ -303,75 +304,69 @@ __global__ void __launch_bounds__(SC_BLOCK) k_sc_fasta_write(ScFasta f, const un
     text_write_body<ScRecord>(f, off, i0, i1, buf);
 }
 
-inline unsigned sc_grid(uint64_t items, uint64_t cap) {                  // cap: the launch's max_blocks, 8192 unless a test lowers it
-    const uint64_t g = (items + SC_BLOCK - 1) / SC_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_sc_check(const ScReads &r, const ScTargets &t, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (r.R) hipLaunchKernelGGL(k_sc_check, dim3(sc_grid(2 * r.R, std::min<uint64_t>(4096, max_blocks))), dim3(SC_BLOCK), 0, s, r, t, counters);
+    if (r.R) hipLaunchKernelGGL(k_sc_check, dim3(stage_grid(2 * r.R, SC_BLOCK, std::min<uint64_t>(4096, max_blocks))), dim3(SC_BLOCK), 0, s, r, t, counters);
 }
 
 void launch_sc_links(const ScReads &r, const ScTargets &t, int32_t max_insert, unsigned long long sentinel, unsigned long long *keys, uint32_t *vals, uint32_t *span,
                      unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (r.R && r.pair_off) hipLaunchKernelGGL(k_sc_links, dim3(sc_grid(r.R, max_blocks)), dim3(SC_BLOCK), 0, s, r, t, max_insert, sentinel, keys, vals, span, counters);
+    if (r.R && r.pair_off) hipLaunchKernelGGL(k_sc_links, dim3(stage_grid(r.R, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, r, t, max_insert, sentinel, keys, vals, span, counters);
 }
 
 void launch_sc_heads(const unsigned long long *keys, uint64_t n_links, uint32_t *heads, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (n_links) hipLaunchKernelGGL(k_sc_heads, dim3(sc_grid(n_links, max_blocks)), dim3(SC_BLOCK), 0, s, keys, n_links, heads, counters);
+    if (n_links) hipLaunchKernelGGL(k_sc_heads, dim3(stage_grid(n_links, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, keys, n_links, heads, counters);
 }
 
 void launch_sc_bundle_fill(const uint32_t *vals, const uint32_t *span, const uint32_t *heads, const uint32_t *pos, uint64_t n_links, uint64_t n_bundles, uint32_t *b_start,
                            unsigned long long *b_span, uint32_t max_blocks, hipStream_t s) {
-    if (n_links) hipLaunchKernelGGL(k_sc_bundle_fill, dim3(sc_grid(n_links, max_blocks)), dim3(SC_BLOCK), 0, s, vals, span, heads, pos, n_links, n_bundles, b_start, b_span);
+    if (n_links) hipLaunchKernelGGL(k_sc_bundle_fill, dim3(stage_grid(n_links, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, vals, span, heads, pos, n_links, n_bundles, b_start, b_span);
 }
 
 void launch_sc_bundles(const unsigned long long *keys, const uint32_t *b_start, const ScBundles &b, const ScParams &p, unsigned long long *best, unsigned long long *counters,
                        uint32_t max_blocks, hipStream_t s) {
-    if (b.n) hipLaunchKernelGGL(k_sc_bundles, dim3(sc_grid(b.n, max_blocks)), dim3(SC_BLOCK), 0, s, keys, b_start, b, p, best, counters);
+    if (b.n) hipLaunchKernelGGL(k_sc_bundles, dim3(stage_grid(b.n, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, keys, b_start, b, p, best, counters);
 }
 
 void launch_sc_second(const ScBundles &b, const unsigned long long *best, unsigned long long *second, uint32_t max_blocks, hipStream_t s) {
-    if (b.n) hipLaunchKernelGGL(k_sc_second, dim3(sc_grid(b.n, max_blocks)), dim3(SC_BLOCK), 0, s, b, best, second);
+    if (b.n) hipLaunchKernelGGL(k_sc_second, dim3(stage_grid(b.n, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, b, best, second);
 }
 
 void launch_sc_choice(const unsigned long long *best, const unsigned long long *second, uint64_t n_ends, int32_t max_second_percent, uint32_t *choice, uint8_t *end_state,
                       unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (n_ends) hipLaunchKernelGGL(k_sc_choice, dim3(sc_grid(n_ends, max_blocks)), dim3(SC_BLOCK), 0, s, best, second, n_ends, max_second_percent, choice, end_state, counters);
+    if (n_ends) hipLaunchKernelGGL(k_sc_choice, dim3(stage_grid(n_ends, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, best, second, n_ends, max_second_percent, choice, end_state, counters);
 }
 
 void launch_sc_joins(const ScBundles &b, const uint32_t *choice, uint32_t *partner, uint32_t *join_bundle, uint32_t max_blocks, hipStream_t s) {
-    if (b.n) hipLaunchKernelGGL(k_sc_joins, dim3(sc_grid(b.n, max_blocks)), dim3(SC_BLOCK), 0, s, b, choice, partner, join_bundle);
+    if (b.n) hipLaunchKernelGGL(k_sc_joins, dim3(stage_grid(b.n, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, b, choice, partner, join_bundle);
 }
 
 void launch_sc_cycle_drop(const ChainLists &l, uint32_t T, uint32_t *partner, const uint32_t *join_bundle, uint8_t *b_state, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (T) hipLaunchKernelGGL(k_sc_cycle_drop, dim3(sc_grid(T, max_blocks)), dim3(SC_BLOCK), 0, s, l, T, partner, join_bundle, b_state, counters);
+    if (T) hipLaunchKernelGGL(k_sc_cycle_drop, dim3(stage_grid(T, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, l, T, partner, join_bundle, b_state, counters);
 }
 
 void launch_sc_rank_init(const ScTargets &t, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, int32_t min_gap, const ChainLists &l, uint32_t max_blocks, hipStream_t s) {
-    if (t.T) hipLaunchKernelGGL(k_sc_rank_init, dim3(sc_grid(2ull * t.T, max_blocks)), dim3(SC_BLOCK), 0, s, t, partner, join_bundle, b_gap, min_gap, l);
+    if (t.T) hipLaunchKernelGGL(k_sc_rank_init, dim3(stage_grid(2ull * t.T, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, t, partner, join_bundle, b_gap, min_gap, l);
 }
 
 void launch_sc_place(const ScTargets &t, const ChainLists &l, const uint32_t *partner, const uint32_t *join_bundle, const int32_t *b_gap, const uint32_t *b_links, int32_t min_gap,
                      const ScLayout &o, uint32_t *head, uint32_t *first, uint32_t *members, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_sc_place, dim3(sc_grid((uint64_t) t.T + 1, max_blocks)), dim3(SC_BLOCK), 0, s, t, l, partner, join_bundle, b_gap, b_links, min_gap, o, head, first, members, counters);
+    hipLaunchKernelGGL(k_sc_place, dim3(stage_grid((uint64_t) t.T + 1, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, t, l, partner, join_bundle, b_gap, b_links, min_gap, o, head, first, members, counters);
 }
 
 void launch_sc_layout(const ScTargets &t, const ChainLists &l, const uint32_t *head, const uint32_t *first_scan, const uint32_t *members_scan, const ScLayout &o,
                       unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    hipLaunchKernelGGL(k_sc_layout, dim3(sc_grid((uint64_t) t.T + 1, max_blocks)), dim3(SC_BLOCK), 0, s, t, l, head, first_scan, members_scan, o, counters);
+    hipLaunchKernelGGL(k_sc_layout, dim3(stage_grid((uint64_t) t.T + 1, SC_BLOCK, max_blocks)), dim3(SC_BLOCK), 0, s, t, l, head, first_scan, members_scan, o, counters);
 }
 
 void launch_sc_fasta_sizes(const ScFasta &f, uint32_t *sizes, unsigned long long *counters, hipStream_t s) {
-    if (f.n) hipLaunchKernelGGL(k_sc_fasta_sizes, dim3((unsigned) ((f.n + SC_BLOCK - 1) / SC_BLOCK)), dim3(SC_BLOCK), 0, s, f, sizes, counters);
+    if (f.n) hipLaunchKernelGGL(k_sc_fasta_sizes, dim3(text_sizes_blocks(f.n, SC_BLOCK)), dim3(SC_BLOCK), 0, s, f, sizes, counters);
 }
 
 void launch_sc_fasta_write(const ScFasta &f, const unsigned long long *off, uint64_t i0, uint64_t i1, char *buf, hipStream_t s) {
     if (i0 >= i1) return;
-    const uint64_t g = (i1 - i0 + SC_WAVES - 1) / SC_WAVES;
-    hipLaunchKernelGGL(k_sc_fasta_write, dim3((unsigned) std::min<uint64_t>(g, f.max_blocks)), dim3(SC_BLOCK), 0, s, f, off, i0, i1, buf);
+    hipLaunchKernelGGL(k_sc_fasta_write, dim3(text_write_blocks(i0, i1, SC_WAVES, f.max_blocks)), dim3(SC_BLOCK), 0, s, f, off, i0, i1, buf);
 }
 
 }  // namespace alga

@@ -1,6 +1,6 @@
-// alga_amd/csrc/seed_device.h -- device side of the seed index (seed_index.h): the helpers over packed 2-bit arrays and offset tables, the
-// look-up, the verification, and the wave loop that seeds a query and verifies what the seeds find.  Included by the *_kernels.hip files only;
-// everything here is internal to the including file (the build has no relocatable device code).
+// alga_amd/csrc/seed_device.h -- device side of the seed index (seed_index.h): the k-mers of packed 2-bit arrays, the look-up, the
+// verification, and the wave loop that seeds a query and verifies what the seeds find (item_of and base_at: packed_device.h).  Included by the
+// *_kernels.hip files only; everything here is internal to the including file (the build has no relocatable device code).
 //
 // seed_and_verify: one wave, one query of S seeds (seed j is the k-mer at base j k of the query), one SeedIndex over a column array.  Lanes
 // take seeds, 64 at a time: one directory read, a bisection to the lower bound, a scan of at most max_occ + 1 equal keys; a seed with 1 ..
@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "seed_index.h"
+#include "packed_device.h"
 #include "prefsuf_common.h"
 
 namespace alga {
@@ -33,18 +34,6 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     }
     return v;
 }
-
-// the item of position g < off[n]: the last i with off[i] <= g (it has a length: off[i + 1] > g)
-__device__ __forceinline__ uint32_t item_of(const uint32_t *__restrict__ off, uint32_t n, uint32_t g) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t base_at(const uint32_t *__restrict__ words, uint64_t g) { return (words[g >> 4] >> ((g & 15ull) << 1)) & 3u; }
 
 // the k-mer at column g of a column array (two words of padding behind the last column)
 __device__ __forceinline__ unsigned long long col_kmer(const uint32_t *__restrict__ cols, uint32_t g, int k) {

@@ -179,19 +179,14 @@ __global__ void __launch_bounds__(ST_BLOCK) k_st_dropped(StEntries en, const uin
     }
 }
 
-inline unsigned st_grid(uint64_t items, uint64_t cap) {                  // cap: option "stitch_max_blocks", 8192 unless a test lowers it
-    const uint64_t g = (items + ST_BLOCK - 1) / ST_BLOCK;
-    return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(g, cap));
-}
-
 }  // namespace
 
 void launch_st_targets(const uint32_t *col_off, uint32_t T, unsigned long long *begin, int32_t *len, uint32_t max_blocks, hipStream_t s) {
-    if (T) hipLaunchKernelGGL(k_st_targets, dim3(st_grid(T, max_blocks)), dim3(ST_BLOCK), 0, s, col_off, T, begin, len);
+    if (T) hipLaunchKernelGGL(k_st_targets, dim3(stage_grid(T, ST_BLOCK, max_blocks)), dim3(ST_BLOCK), 0, s, col_off, T, begin, len);
 }
 
 void launch_st_check(const StEntries &en, uint32_t T, uint32_t *end_count, int32_t *end_entry, unsigned long long *counters, uint32_t max_blocks, hipStream_t s) {
-    if (en.J) hipLaunchKernelGGL(k_st_check, dim3(st_grid(en.J, max_blocks)), dim3(ST_BLOCK), 0, s, en, T, end_count, end_entry, counters);
+    if (en.J) hipLaunchKernelGGL(k_st_check, dim3(stage_grid(en.J, ST_BLOCK, max_blocks)), dim3(ST_BLOCK), 0, s, en, T, end_count, end_entry, counters);
 }
 
 void launch_st_overlap(const MgTargets &t, const StEntries &en, const StParams &p, const StEntryOut &o, unsigned long long *counters, hipStream_t s) {
@@ -201,11 +196,11 @@ void launch_st_overlap(const MgTargets &t, const StEntries &en, const StParams &
 }
 
 void launch_st_joins(const StEntries &en, const StEntryOut &o, const int32_t *end_entry, uint32_t E, const MgEndOut &eo, uint32_t *join, uint32_t max_blocks, hipStream_t s) {
-    if (E) hipLaunchKernelGGL(k_st_joins, dim3(st_grid(E, max_blocks)), dim3(ST_BLOCK), 0, s, en, o, end_entry, E, eo, join);
+    if (E) hipLaunchKernelGGL(k_st_joins, dim3(stage_grid(E, ST_BLOCK, max_blocks)), dim3(ST_BLOCK), 0, s, en, o, end_entry, E, eo, join);
 }
 
 void launch_st_dropped(const StEntries &en, const uint32_t *join, uint8_t *state, uint32_t max_blocks, hipStream_t s) {
-    if (en.J) hipLaunchKernelGGL(k_st_dropped, dim3(st_grid(en.J, max_blocks)), dim3(ST_BLOCK), 0, s, en, join, state);
+    if (en.J) hipLaunchKernelGGL(k_st_dropped, dim3(stage_grid(en.J, ST_BLOCK, max_blocks)), dim3(ST_BLOCK), 0, s, en, join, state);
 }
 
 }  // namespace alga

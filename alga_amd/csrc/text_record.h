@@ -187,6 +187,15 @@ template <class R, class Src> __device__ __forceinline__ void text_write_body(co
     }
 }
 
+// ---- the grids of a *_sizes / *_write kernel pair (host)
+// text_sizes_body has one thread per item and no loop: its grid is exact (n > 0)
+inline unsigned text_sizes_blocks(uint64_t n, int block) { return (unsigned) ((n + (uint64_t) block - 1) / (uint64_t) block); }
+// text_write_body strides by waves: a wave per record of [i0, i1) (i0 < i1), at most `cap` blocks
+inline unsigned text_write_blocks(uint64_t i0, uint64_t i1, int waves_per_block, uint64_t cap = 16384) {
+    const uint64_t g = (i1 - i0 + (uint64_t) waves_per_block - 1) / (uint64_t) waves_per_block;
+    return (unsigned) (g < cap ? g : cap);
+}
+
 }  // namespace
 
 }  // namespace alga

@@ -195,7 +195,17 @@ def _one():
     return _make([_seq(_rng(412), 333)], [dict()], [{0: None}])
 
 
-CASES = {"word_edges": _word_edges, "pass_edges": _pass_edges, "permille": _permille, "first_last_base": _first_last_base, "minus": _minus, "duplicates": _duplicates,
+def _word_seams():
+    """k_ct_build at its seams: kept targets of 1, 15, 16, 17, 31, 32 and 33 bases around a host of 4200 whose window of 300 is dropped, an empty
+    target between them; 4345 kept columns (no multiple of 16: the last word is partial, the two behind it are padding; 274 words: with
+    contain_max_blocks 1 every lane takes two).  An empty target is not kept: the kept set has no empty item"""
+    rng = _rng(414)
+    h = _seq(rng, 4200)
+    t = [_seq(rng, n) for n in (1, 15, 16)] + [_seq(rng, 0), _seq(rng, 17), h, h[1000:1300]] + [_seq(rng, n) for n in (31, 32, 33)]
+    return _make(t, [dict()], [{**{i: None for i in (0, 1, 2, 4, 5, 7, 8, 9)}, 6: (5, 1000, 0, 0, 1)}])
+
+
+CASES = {"word_seams": _word_seams, "word_edges": _word_edges, "pass_edges": _pass_edges, "permille": _permille, "first_last_base": _first_last_base, "minus": _minus, "duplicates": _duplicates,
          "chain": _chain, "seed63": _seed63, "one_hit": _one_hit, "repeats": _repeats, "two_hosts": _two_hosts, "short": _short, "t0": _t0, "all_empty": _all_empty,
          "one": _one}
 

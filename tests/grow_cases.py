@@ -164,7 +164,31 @@ def _all_placed():
     return _make([g[p:p + 100] for p in range(0, 400, 40)], [g], [dict()])
 
 
-CASES = {"h_extremes": _h_extremes, "a_equals_w": _a_equals_w, "partial_word": _partial_word, "mm_bound": _mm_bound, "tiny_targets": _tiny_targets, "period3": _period3,
+SEAM_LENS = (1, 15, 16, 17, 0, 15, 16, 17, 31, 32, 33)
+SEAM_NEW_LENS = [1, 31, 32, 33, 0, 15, 16, 17, 51, 52, 53, 2364, 2300]
+
+
+def _word_seams():
+    """k_gr_ends and k_gr_build at their seams.  Ends of 1, 15, 16, 17, 31, 32 and 33 columns, two of width 0 between them (an empty target), 9182 end
+    columns in all (no multiple of 16; 574 words).  Targets 1 .. 3 grow by 8 at both ends, 8 .. 10 by 20 at the right end, target 11 by the 64 of
+    max_grow: the new lengths (SEAM_NEW_LENS) hold 1, 15, 16, 17, 31, 32, 33 and a 0, 4965 new columns in all (no multiple of 16; 311 words and
+    the two of padding).  k = 8 and min_anchor = 8, so that the short ends anchor a read; the 2200-base read makes W = len for every short target"""
+    g, G = _seq(_rng(117), 1300), _seq(_rng(118), 5200)
+    targets, reads = [], []
+    for i, n in enumerate(SEAM_LENS):
+        s = 60 + 100 * i
+        e = s + n
+        targets.append(g[s:e])
+        if i in (1, 2, 3):
+            reads += [g[e - 12:e + 8], g[s - 8:s + 12]]
+        if i >= 8:
+            reads.append(g[e - 20:e + 20])
+    targets += [G[100:2400], G[2700:5000]]
+    reads.append(G[300:2500])                                                 # a = 2100, h = 100 at the right end of target 11
+    return dict(_make(reads, targets, [dict(k=8, min_anchor=8, min_cover=1)]), g=g)
+
+
+CASES = {"word_seams": _word_seams, "h_extremes": _h_extremes, "a_equals_w": _a_equals_w, "partial_word": _partial_word, "mm_bound": _mm_bound, "tiny_targets": _tiny_targets, "period3": _period3,
          "equal_ends": _equal_ends, "second_chunk": _second_chunk, "cover": _cover, "percent": _percent, "minus_only": _minus_only, "left_grow": _left_grow,
          "both_ends": _both_ends, "n0": _n0, "t0": _t0, "all_placed": _all_placed}
 

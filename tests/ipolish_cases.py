@@ -215,7 +215,27 @@ def _no_targets():
     return make([rand(113, 100), rand(114, 50)], [])
 
 
-CASES = {"normalise": _normalise, "ties": _ties, "insert_vote": _insert_vote, "adjacent": _adjacent, "seams": _seams, "deep": _deep, "beside": _beside, "carries": _carries, "no_gapped": _no_gapped,
+WORD_SEAM_LENS = [1, 15, 16, 0, 17, 31, 32, 33]
+
+
+def _word_seams():
+    """k_ip_words at its seams.  Targets of 1, 15, 16, 17, 31, 32 and 33 columns and an empty one keep their length (no read of 50 nt lies on them: a
+    target this short has no voter) behind, between and in front of three targets of 120 columns that each lose a column (a deleted column between
+    kept ones: an empty item of the walk) and gain bases at a slot, with net changes of +1, -1 and +2: every short target starts at another offset
+    in its word than before.  A last target of 4200 columns without a voter: more than 256 new words, so that with ipolish_max_blocks 1 every lane
+    takes two; the new total is no multiple of 16"""
+    seqs, reads = [], []
+    short = [plain(450 + i, n) for i, n in enumerate(WORD_SEAM_LENS)]
+    for j, ev in enumerate(([("I", 15, None), ("D", 100, 2)], [("I", 15, None), ("I", 70, None), ("D", 100, 1)], [("I", 40, None), ("D", 80, 3)])):
+        g = plain(460 + j, 120)
+        seqs += short[3 * j:3 * j + 3]
+        seqs.append(edit(g, [(e[0], e[1], other(g[e[1]])) if e[0] == "I" else e for e in ev]))
+        reads += windows(g, list(range(0, 71, 2)), 50)
+    seqs.append(plain(470, 4200))
+    return make(reads, seqs, [dict(), dict(min_cover=2)])
+
+
+CASES = {"word_seams": _word_seams, "normalise": _normalise, "ties": _ties, "insert_vote": _insert_vote, "adjacent": _adjacent, "seams": _seams, "deep": _deep, "beside": _beside, "carries": _carries, "no_gapped": _no_gapped,
          "no_voters": _no_voters, "no_reads": _no_reads, "no_targets": _no_targets}
 
 

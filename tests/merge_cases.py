@@ -181,7 +181,17 @@ def _short():
     return _make([g[:83], g[41:101], _seq(rng, 20), _seq(rng, 1), _seq(rng, 0)], [dict()])
 
 
-CASES = {"pairings": _pairings, "half_length": _half_length, "max_overlap": _max_overlap, "partial_word": _partial_word, "seeds64": _seeds64, "one_sided": _one_sided,
+def _word_seams():
+    """k_mg_build at its seams: merged contigs of 1, 15, 16, 17, 31, 32 and 33 bases (targets that join nothing) around two joined pairs, one of
+    them minus-oriented; 9045 columns in all (no multiple of 16: the last word is partial, the two behind it are padding; 568 words with them: with
+    merge_max_blocks 1 every lane takes several).  The empty target is in no merged contig: the stage has no empty item"""
+    rng = _rng(317)
+    t = [_seq(rng, n) for n in (1, 15, 16)] + [_seq(rng, 0), _seq(rng, 17)] + list(_pair(rng, 2300, 2200, 50)) + [_seq(rng, n) for n in (31, 32)]
+    t += list(_pair(rng, 2250, 2250, 50, "LR")) + [_seq(rng, 33)]
+    return _make(t, [dict()])
+
+
+CASES = {"word_seams": _word_seams, "pairings": _pairings, "half_length": _half_length, "max_overlap": _max_overlap, "partial_word": _partial_word, "seeds64": _seeds64, "one_sided": _one_sided,
          "two_partners": _two_partners, "periodic": _periodic, "mismatch_column": _mismatch_column, "path5": _path5, "ring3": _ring3, "ring2": _ring2,
          "self_overlap": _self_overlap, "t0": _t0, "all_empty": _all_empty, "one": _one, "short": _short}
 

@@ -229,7 +229,21 @@ def _tiny_targets():
     return _make(reads, targets, shifts=[5 * i % 16 for i in range(150)], gaps=[i % 4 != 1 for i in range(150)])
 
 
-CASES = {"exact": _exact, "bound": _bound, "last_seed_only": _last_seed_only, "every_seed_hit": _every_seed_hit, "ends": _ends, "unaligned": _unaligned,
+SEAM_LENS = [1, 15, 16, 17, 0, 31, 32, 33, 4100]
+
+
+def _word_seams():
+    # k_pl_gather at its seams: targets that end 1 base before, at and 1 base behind a word boundary, an empty one between them, 4245 columns in all
+    # (no multiple of 16: the last word is partial; 266 words: more than one block of 256 lanes).  k = 8, so that every target of 15 bases or more is
+    # the whole of a read in one orientation or the other, and the long one is read across every boundary of 256 columns
+    rng = _rng(19)
+    targets = [_seq(rng, n) for n in SEAM_LENS]
+    reads = [P.revcomp(t) if i & 1 else t for i, t in enumerate(targets[:-1]) if len(t) >= 15]
+    reads += [targets[-1][p - 20:p + 20] for p in range(256, 4100, 256)] + [targets[-1][:30], P.revcomp(targets[-1][-30:])]
+    return _make(reads, targets, shifts=[7 * i % 16 for i in range(len(targets))], gaps=[i % 2 == 0 for i in range(len(targets))], k=8)
+
+
+CASES = {"word_seams": _word_seams, "exact": _exact, "bound": _bound, "last_seed_only": _last_seed_only, "every_seed_hit": _every_seed_hit, "ends": _ends, "unaligned": _unaligned,
          "repeat": _repeat, "palindrome": _palindrome, "saturate": _saturate, "pairs": _pairs, "rand": _rand, "empty_targets": _empty_targets,
          "empty_reads": _empty_reads, "empty_short": _empty_short, "many_seeds": _many_seeds, "mm_limit": _mm_limit, "tiny_targets": _tiny_targets}
 

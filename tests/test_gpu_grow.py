@@ -1,6 +1,6 @@
 """The grow stage on the GPU (alga_grow_placed_device, alga_write_grown_fasta_device): every output array and every counter equal to the
 Python definition (tests/grow_checker.py) on the cases of tests/grow_cases.py, from host arrays and from tensors, with and without a polish
-between and with directories of 1, 4 and auto bits; the FASTA bytes and the TSV; a wave of k_gr_place that takes a second candidate; the
+between and with directories of 1, 4 and auto bits; the FASTA bytes and the TSV; the word seams of k_gr_ends and k_gr_build; a wave of k_gr_place that takes a second candidate; the
 planted genome end to end with a scaffold call on the last placement; the caller's stream; refusals leave an earlier result valid; a result
 stays valid across a later placement, polish, break and scaffold; the command line."""
 import os
@@ -81,6 +81,23 @@ def test_every_case_equals_the_checker(eng, name, tmp_path):
         assert (a == b).all()
     after = pl.to_host()
     assert all((before[k] == after[k]).all() for k in P.ARRAYS)                 # the placement is left as it was
+
+
+def test_word_seams_of_the_end_columns_and_of_the_grown_targets(eng):
+    """k_gr_ends and k_gr_build on tests/grow_cases.py: word_seams, at 8192 blocks and at one: ends of 1, 15, 16, 17, 31, 32 and 33 columns (those of
+    15 and more anchor a read that grows them: a wrong end column loses it) and two of width 0; new lengths of the same values and a 0; totals
+    that are no multiple of 16 (the last word partial, the two of padding zero) and, with grow_max_blocks 1, several words per lane in both"""
+    c, want = QC.case("word_seams"), QC.checked("word_seams")
+    assert want["len"].tolist() == QC.SEAM_NEW_LENS and want["left"][:4].tolist() == [0, 8, 8, 8] and want["right"][8:12].tolist() == [20, 20, 20, 64]
+    assert int(want["col_off"][-1]) % 16 and int(want["col_off"][-1]) > 16 * 256
+    pl = eng.place_reads(c["rows"], c["lens"], targets=targets(c), **c["params"])
+    try:
+        for blocks in (8192, 1):
+            eng.set_option("grow_max_blocks", blocks)
+            gw = eng.grow_ends(c["rows"], c["lens"], pl, **c["variants"][0])
+            assert_same(gw.to_host(), want, ("word_seams", blocks))
+    finally:
+        eng.set_option("grow_max_blocks", 8192)
 
 
 def test_polished_bases_are_grown(eng):

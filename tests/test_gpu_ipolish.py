@@ -105,6 +105,24 @@ def test_grid_stride_loops_take_further_passes(eng, name, tmp_path):
         eng.set_option("ipolish_max_blocks", 8192)
 
 
+def test_word_seams_of_the_new_column_array(eng, tmp_path):
+    """k_ip_words on tests/ipolish_cases.py: word_seams, at 8192 blocks and at one: targets whose new length is 1, 15, 16, 17, 31, 32 and 33 at
+    offsets that insertions and deletions in the targets before them have moved, deleted columns between kept ones, a new total that is no
+    multiple of 16 (the last word partial, the two of padding zero) and, with ipolish_max_blocks 1, two words per lane"""
+    c = XC.case("word_seams")
+    want_pl, want_gp = XC.placed("word_seams")
+    want = XC.checked("word_seams", 0, False)
+    assert want["len"].tolist() == [1, 15, 16, 120, 0, 17, 31, 120, 32, 33, 120, 4200] and c["tlen"].tolist() != want["len"].tolist()
+    assert (want["t_dels"] > 0).sum() == (want["t_ins_bases"] > 0).sum() == 3 and int(want["col_off"][-1]) % 16 and (int(want["col_off"][-1]) + 15) // 16 + 2 > 256
+    rows, lens, pl, gp = stage(eng, c, want_pl, want_gp)
+    try:
+        for blocks in (8192, 1):
+            eng.set_option("ipolish_max_blocks", blocks)
+            check_result(eng, eng.polish_indels(rows, lens, pl, gp), want, want_gp["cover"], tmp_path, ("word_seams", blocks))
+    finally:
+        eng.set_option("ipolish_max_blocks", 8192)
+
+
 def run_planted_many(eng, m, tmp_path, **params):
     """place -> gapped -> polish_indels on a set of tests/ipolish_cases.py: many; every array, counter and both texts against what the planting
     says -> (the placement, the result, its host copy)"""

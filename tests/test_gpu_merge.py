@@ -69,6 +69,21 @@ def test_every_case_equals_the_checker(eng, name, tmp_path):
         assert (a == b).all()
 
 
+def test_word_seams_of_the_merged_contigs(eng):
+    """k_mg_build on tests/merge_cases.py: word_seams, at 8192 blocks and at one: merged contigs of 1, 15, 16, 17, 31, 32 and 33 bases around two
+    joined pairs (one of them minus-oriented), a total that is no multiple of 16 (the last word partial, the two of padding zero) and, with
+    merge_max_blocks 1, several words per lane.  The stage has no empty item: the empty target is in no merged contig"""
+    c, want = QC.case("word_seams"), QC.checked("word_seams")
+    assert want["len"].tolist() == [1, 15, 16, 17, 4450, 31, 32, 4450, 33] and want["orient"].sum() == 2 and len(c["tlen"]) == 12
+    assert int(want["col_off"][-1]) % 16 and int(want["col_off"][-1]) > 16 * 256
+    try:
+        for blocks in (8192, 1):
+            eng.set_option("merge_max_blocks", blocks)
+            assert_same(eng.merge_ends(QC.targets(c)).to_host(), want, ("word_seams", blocks))
+    finally:
+        eng.set_option("merge_max_blocks", 8192)
+
+
 def test_one_index_workspace_serves_the_stages_in_turn(eng):
     """place, merge and grow build their seed index in one workspace of the engine: on one engine, calls of different stages, k, directory
     widths and seed counts in turn, each equal to its checker -- no index, directory size, k or usable-seed mask is left over from the call

@@ -19,7 +19,7 @@ KERNELS = ["k_gr_check", "k_gr_candidates", "k_gr_compact", "k_gr_end_lens", "k_
            "k_gr_fasta_sizes", "k_gr_fasta_write"]
 SYMBOLS = ("alga_grow_default_params", "alga_grow_placed_device", "alga_write_grown_fasta_device")
 # (candidates, overhanging, voting, bases_added) of every variant of every case
-OUTCOMES = {"h_extremes": [(6, 4, 4, 74)], "a_equals_w": [(4, 3, 3, 60)], "partial_word": [(5, 5, 5, 36)], "mm_bound": [(5, 3, 3, 60)], "tiny_targets": [(5, 3, 3, 104)],
+OUTCOMES = {"word_seams": [(10, 10, 10, 172)], "h_extremes": [(6, 4, 4, 74)], "a_equals_w": [(4, 3, 3, 60)], "partial_word": [(5, 5, 5, 36)], "mm_bound": [(5, 3, 3, 60)], "tiny_targets": [(5, 3, 3, 104)],
             "period3": [(2, 2, 1, 30)], "equal_ends": [(2, 2, 0, 0), (2, 0, 0, 0)], "second_chunk": [(4, 3, 3, 10), (4, 1, 1, 10)],
             "cover": [(3, 3, 3, 10), (3, 3, 3, 20), (3, 3, 3, 8)], "percent": [(5, 5, 5, 8), (5, 5, 5, 5), (5, 5, 5, 30)], "minus_only": [(3, 3, 3, 20)],
             "left_grow": [(3, 3, 3, 20)], "both_ends": [(6, 6, 6, 20)], "n0": [(0, 0, 0, 0)], "t0": [(1, 0, 0, 0)], "all_placed": [(0, 0, 0, 0)]}

@@ -24,7 +24,7 @@ KERNELS = ["k_mg_check", "k_mg_end_lens", "k_mg_ends", "k_mg_overlap", "k_mg_joi
            "k_ch_cycle_init", "k_ch_cycle_jump", "k_ch_rank_jump"]   # (chain_kernels.hip: the jumps the scaffolder, the merge and the stitch stage share)
 SYMBOLS = ("alga_merge_default_params", "alga_merge_targets_device", "alga_write_merged_fasta_device")
 # (ends_with_overlap, ends_ambiguous, joins, joins_dropped_cycle, merged) of every variant of every case
-OUTCOMES = {"pairings": [(8, 0, 4, 0, 5), (0, 0, 0, 0, 9)], "half_length": [(2, 0, 1, 0, 3)], "max_overlap": [(2, 0, 1, 0, 3)], "partial_word": [(6, 0, 3, 0, 9)],
+OUTCOMES = {"word_seams": [(4, 0, 2, 0, 9)], "pairings": [(8, 0, 4, 0, 5), (0, 0, 0, 0, 9)], "half_length": [(2, 0, 1, 0, 3)], "max_overlap": [(2, 0, 1, 0, 3)], "partial_word": [(6, 0, 3, 0, 9)],
             "seeds64": [(2, 0, 1, 0, 1), (0, 0, 0, 0, 2)], "one_sided": [(1, 0, 0, 0, 3), (2, 0, 1, 0, 2)], "two_partners": [(3, 1, 0, 0, 3)], "periodic": [(2, 2, 0, 0, 2)],
             "mismatch_column": [(2, 0, 1, 0, 1)], "path5": [(8, 0, 4, 0, 1)], "ring3": [(6, 0, 2, 1, 1)], "ring2": [(4, 0, 1, 1, 1)], "self_overlap": [(0, 0, 0, 0, 2)],
             "t0": [(0, 0, 0, 0, 0)], "all_empty": [(0, 0, 0, 0, 0)], "one": [(0, 0, 0, 0, 1)], "short": [(0, 0, 0, 0, 4)]}
